@@ -598,6 +598,27 @@ def run_ab(args, variants, B, barrier, world):
                 rounds=args.ab_rounds, passes_per_block=n, order="A B, B A, ... (one untimed pass before every block)", all_verified=nbad == 0)
 
 
+DUMP_BYTES = 60 * 1000 * 1000   # --dump-outputs: the arrays of all ranks together; with the .npy headers within 64 MB
+
+
+def dump_outputs(dirname, last, psz, rank, world):
+    """--dump-outputs: what the last timed step returned to its caller, the contexts' shares in batch order.  verdicts.npy: every proof's
+    cpx_batch_verify verdict (CPX_OK = 0); proofs.npy: [proofs, proof_size] serialized proof bytes (0..255); proof_index.npy: the batch
+    position of each row.  The arrays of all ranks share DUMP_BYTES: when all proofs do not fit, the rows are a fixed sample (seed 0) of the
+    batch, the same from run to run.  float32 holds every byte and verdict exactly.  With several ranks each writes *_rank<r>.npy."""
+    import numpy as np
+    rows = [np.frombuffer(p, dtype=np.uint8).reshape(-1, psz) for p, _ in last]
+    verdicts = np.concatenate([np.asarray(v, dtype=np.float32) for _, v in last])
+    B, Bk = len(verdicts), len(rows[0])
+    keep = min(B, (DUMP_BYTES // world - 12 * B) // (4 * psz))
+    index = np.arange(B) if keep == B else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    proofs = np.stack([rows[i // Bk][i % Bk] for i in index]).astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in (("verdicts", verdicts), ("proofs", proofs), ("proof_index", index.astype(np.float64))):
+        np.save(os.path.join(dirname, name + suffix + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -629,7 +650,14 @@ def main():
     ap.add_argument("--ab-passes", type=int, default=0, help="timed passes per block (0 = about 2 s worth)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc child passes that measure roofline.traffic (then null)")
     ap.add_argument("--traffic-child", default="", help=argparse.SUPPRESS)   # internal: the process rocprofv3 wraps (one pass of one context under counters)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what their last step returned as DIR/*.npy (float32): "
+                    "every proof's verdict and the bytes of the proofs (a fixed, seeded sample when all of them exceed 64 MB); the inputs are seeded, "
+                    "so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.fused_verify or args.ab or args.ab_lib):
+        ap.error("--dump-outputs applies to the prove + verify steps, not to --fused-verify / --ab / --ab-lib")
     if args.traffic_child:
         return traffic_child(args)
 
@@ -857,7 +885,7 @@ def main():
                 t.start()
             for t in th:
                 t.join()
-        return [o[0] for o in out], sum(bad)
+        return out, sum(bad)
 
     warm = {}   # kernel statistics of the warm-up launches (only used for the all-launches average rocprofv3 reports)
     if args.warmup:
@@ -875,9 +903,12 @@ def main():
         c.reset_stats()
     barrier()
     t0 = time.perf_counter()
-    proofs, nbad = steps(args.steps)
+    last, nbad = steps(args.steps)
     barrier()
     dt = time.perf_counter() - t0
+    proofs = [o[0] for o in last]
+    if args.dump_outputs:   # (before the upload legs below: their proves reuse the raw proof buffers)
+        dump_outputs(args.dump_outputs, last, ctx.proof_size, rank, world)
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -125,3 +125,43 @@ def test_every_msm_kernel_the_engine_reports_has_a_price():
     for k in cpx.Context.KERNELS:
         if not k.startswith(("k_msm_fix", "k_msm_tblw", "k_msm_accw")):
             assert bench.msm_pair_cost(k) == 0.0, k   # (k_msm_tail, k_smul, k_reduce_sets ...: no pairs)
+
+
+def test_bench_rejects_zero_steps_and_dumps_of_the_other_modes():
+    """--steps is the number of timed steps ms_per_step divides by: 0 is refused before anything runs; --dump-outputs writes the prove + verify
+    steps' outputs and is refused beside the modes that time something else."""
+    for extra in (["--steps", "0"], ["--dump-outputs", "d", "--fused-verify"], ["--dump-outputs", "d", "--ab", "fix_bits=12,16"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=120)
+        assert out.returncode == 2 and "error:" in out.stderr, (extra, out.stderr[-2000:])
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.dump_outputs on raw proof buffers as prove_batch(raw=True) returns them (one per context): every verdict, the proof bytes as float32
+    rows at the batch positions proof_index names, all of them while they fit and a sample that is the same from run to run when they do not,
+    the files within 64 MB (shared by the ranks)."""
+    import ctypes
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    psz = 4976
+    for B, K, world, rank in ((512, 2, 1, 0), (16384, 4, 1, 0), (16384, 2, 4, 3)):
+        raw = np.random.default_rng(B).integers(0, 256, (B, psz), dtype=np.uint8)
+        last = []
+        for k in range(K):
+            buf = (ctypes.c_uint8 * (B // K * psz)).from_buffer_copy(raw[k * B // K:(k + 1) * B // K].tobytes())
+            last.append((buf, [0] * (B // K - 1) + [-4]))
+        files = []
+        for run in range(2):
+            d = tmp_path / ("%d_%d_%d" % (B, world, run))
+            bench.dump_outputs(str(d), last, psz, rank, world)
+            sfx = "_rank%d" % rank if world > 1 else ""
+            files.append({f: np.load(d / (f + sfx + ".npy")) for f in ("verdicts", "proofs", "proof_index")})
+            assert sum(p.stat().st_size for p in d.iterdir()) * world <= 64 * 1000 * 1000
+        a, b = files
+        for f in a:
+            assert np.array_equal(a[f], b[f]), f
+        idx = a["proof_index"].astype(np.int64)
+        assert a["verdicts"].dtype == np.float32 and a["proofs"].dtype == np.float32
+        assert a["verdicts"].shape == (B,) and list(np.flatnonzero(a["verdicts"])) == [(k + 1) * B // K - 1 for k in range(K)]
+        assert np.array_equal(a["proofs"], raw[idx].astype(np.float32)) and len(np.unique(idx)) == len(idx)
+        assert (len(idx) == B) == (B * psz * 4 < 60 * 1000 * 1000)

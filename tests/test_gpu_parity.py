@@ -1618,6 +1618,39 @@ def test_bench_measures_hbm_traffic_in_the_run_and_reports_the_upload_inclusive_
     assert d["setup_s"]["total"] > 0
 
 
+def test_bench_dump_outputs_hold_the_last_steps_proofs(orc, tmp_path):
+    """bench.py --dump-outputs DIR: the verdicts and proof bytes the last timed step returned, as float32 .npy.  Two runs of the same command dump the
+    same arrays (seeded inputs), and the proof rows are the oracle's proofs of the instances bench.synth_batch draws for rank 0 — across both contexts'
+    shares."""
+    import sys
+    import numpy as np
+    import curdleproofs_amd as cpx
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ell, B = 28, 256
+    runs = []
+    for r in range(2):
+        out = tmp_path / ("run%d" % r)
+        d = _run_bench(["--ell", str(ell), "--batch", str(B), "--ctxs", "2", "--steps", "2", "--warmup", "1", "--no-extra-shapes", "--no-cpu-baseline",
+                        "--no-traffic", "--dump-outputs", str(out)])
+        assert d["steps"] == 2 and d["all_verified"] is True and d["ms_per_step"] > 0
+        runs.append({f: np.load(out / (f + ".npy")) for f in ("verdicts", "proofs", "proof_index")})
+    a, b = runs
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.array_equal(a[f], b[f]), f
+    assert a["verdicts"].shape == (B,) and not a["verdicts"].any()
+    assert a["proofs"].shape == (B, 48 * (18 + 10 * 5) + 7 * 32) and np.array_equal(a["proof_index"], np.arange(B))
+    sys.path.insert(0, root)
+    import bench
+    c = cpx.Context(0)
+    data = bench.synth_batch(c, ell, B, seed=1234)
+    for i in (0, 97, B // 2, B - 1):
+        it = bench._instance(data, ell, i)
+        want = orc.prove(ell, data["crs"], it["vec_R"], it["vec_S"], it["vec_T"], it["vec_U"], it["M"], it["permutation"], it["k"], it["vec_m_blinders"],
+                         it["prover_rand"])
+        assert bytes(a["proofs"][i].astype(np.uint8)) == want, i
+    c.close()
+
+
 def test_staged_instance_upload_keeps_the_loaded_batch_and_then_replaces_it(orc):
     """cpx_batch_load_begin / _end: the NEXT batch's instance is uploaded beside the loaded batch's prove + verify and becomes the loaded batch at
     _end.  Between the two calls the loaded batch still proves to ITS oracle bytes; after _end the staged instances prove to theirs — on the
