@@ -14,6 +14,7 @@
 #pragma once
 #include "mont32.hpp"
 #include "modinv30.hpp"
+#include <utility>
 
 namespace cpx {
 
@@ -116,7 +117,8 @@ CPX_HD F28 f28_cneg(const F28& a, bool neg) {
 
 // Montgomery product a * b / 2^392 mod p (lazy range).  Product scanning: column k gathers a_i b_(k-i) and
 // m_i p_(k-i) into one signed 64-bit accumulator (|sum| < 2^62), emits one limb, shifts by 28 bits.
-CPX_HD F28 f28_mul_body(const F28& a, const F28& b) {
+// Schoolbook form (196 + 196 multiply-adds); f28_mul_body_kara computes the same column sums with 147 + 196.
+CPX_HD F28 f28_mul_body_school(const F28& a, const F28& b) {
   int32_t m[14];
   F28 t;
   int64_t acc = 0;
@@ -145,7 +147,7 @@ CPX_HD F28 f28_mul_body(const F28& a, const F28& b) {
 // for normalised limbs): 588 multiply-adds instead of the 784 of two products.  The mixed addition ends in such a difference
 // (Y3 = R (Q - X3) - Y1 PPP).  Result in (-1.62 p - eps, 2.62 p) for operands at the bound of f28_mul_body, the same interval
 // the difference of two reduced products spans; NOT a "product" for f28_product_is_zero.
-CPX_HD F28 f28_mulsub_body(const F28& a, const F28& b, const F28& c, const F28& d) {
+CPX_HD F28 f28_mulsub_body_school(const F28& a, const F28& b, const F28& c, const F28& d) {
   int32_t m[14], nc[14];
   CPX_UNROLL for (int i = 0; i < 14; i++) nc[i] = -c.v[i];
   F28 t;
@@ -174,16 +176,109 @@ CPX_HD F28 f28_mulsub_body(const F28& a, const F28& b, const F28& c, const F28& 
   t.v[13] = (int32_t)acc;
   return t;
 }
+// Karatsuba form of the same columns: sum_n x_n * y_n (N = 1: a product; N = 2: a b + (-c) d) with one Montgomery reduction.
+// Split every operand at limb 7 (x = x0 + 2^196 x1) and use x0 y1 + x1 y0 = x0 y0 + x1 y1 + (x0 - x1)(y1 - y0):
+//   L_j = (x0 y0)_j, H_j = (x1 y1)_j, D_j = ((x0 - x1)(y1 - y0))_j, j = 0..12 (three 7 x 7 blocks: 147 multiply-adds, not 196);
+//   column k of x y = L_k + (L_(k-7) + H_(k-7) + D_(k-7)) + H_(k-14) = E_k + E_(k-7) + D_(k-7) with E_k = L_k + H_(k-7).
+// E_k is summed once (k = 0..19), added to its own column and kept in registers for column k + 7; the N products share the
+// E / D merges.  The column sums are the same integers as the schoolbook body's, so the digits m_k and the result are bit-identical.
+// Bounds: every operand limb that reaches a product is below 2^28 in magnitude (normalised values: limbs 0..12 in [0, 2^28), the
+// top limb below 2^23 for |x| <= 38 p; f28_sub_lazy / f28_cneg_lazy: limbs in (-2^28, 2^28)), so a half difference is below 2^29.
+// E_k has at most 7 terms per product (k <= 6: k + 1; 7..12: (13 - k) + (k - 6); 13..19: 20 - k) of < 2^56, D_j at most 7 of < 2^58,
+// the reduction 14 terms m_i p_(k-i) of < 2^56 and the carry < 2^35.  Every partial sum of column k is therefore below
+//   N = 1: 14 * 2^56 (E_k, E_(k-7)) + 7 * 2^58 (D) + 14 * 2^56 + 2^35 = 56 * 2^56 + 2^35 < 2^61.9   (schoolbook: 28 * 2^56)
+//   N = 2: 28 * 2^56 + 14 * 2^58 + 14 * 2^56 + 2^35 = 98 * 2^56 + 2^35 < 2^62.7 < 2^63          (schoolbook: 42 * 2^56)
+// so both products of f28_mulsub_body stay in Karatsuba form.  Cost: 14 limb differences per product and two 64-bit additions
+// per column where E_k and E_(k-7) meet (k = 7..19) instead of one.
+// One column k of f28_kara_redc (k a template argument: every loop below has constant bounds and unrolls in full).
+template <int K, int N> CPX_HD void f28_kara_col(const F28 (&x)[N], const F28 (&y)[N], const int32_t (&dx)[N][7], const int32_t (&dy)[N][7],
+                                                 int64_t (&e)[20], int32_t (&m)[14], int64_t& acc, F28& t) {
+  if constexpr (K < 20) {
+    int64_t s = 0;
+    CPX_UNROLL for (int n = 0; n < N; n++) {
+      if constexpr (K <= 12) {
+        CPX_UNROLL for (int i = (K > 6 ? K - 6 : 0); i <= (K < 6 ? K : 6); i++) s += (int64_t)x[n].v[i] * y[n].v[K - i];
+      }
+      if constexpr (K >= 7) {
+        constexpr int J = K - 7;
+        CPX_UNROLL for (int i = (J > 6 ? J - 6 : 0); i <= (J < 6 ? J : 6); i++) s += (int64_t)x[n].v[i + 7] * y[n].v[J - i + 7];
+      }
+    }
+    e[K] = s;
+    acc += s;
+  }
+  if constexpr (K >= 7) {
+    constexpr int J = K - 7;
+    acc += e[J];
+    if constexpr (J <= 12) {
+      CPX_UNROLL for (int n = 0; n < N; n++) {
+        CPX_UNROLL for (int i = (J > 6 ? J - 6 : 0); i <= (J < 6 ? J : 6); i++) acc += (int64_t)dx[n][i] * dy[n][J - i];
+      }
+    }
+  }
+  if constexpr (K < 14) {
+    CPX_UNROLL for (int i = 0; i < K; i++) acc += (int64_t)m[i] * F28Cfg::P[K - i];
+    m[K] = (int32_t)(((uint32_t)acc * F28Cfg::INV) & (uint32_t)F28Cfg::MASK);
+    acc += (int64_t)m[K] * F28Cfg::P[0];
+  } else {
+    CPX_UNROLL for (int i = K - 13; i < 14; i++) acc += (int64_t)m[i] * F28Cfg::P[K - i];
+    t.v[K - 14] = (int32_t)acc & F28Cfg::MASK;
+  }
+  acc >>= 28;
+}
+template <int N, int... K> CPX_HD F28 f28_kara_cols(const F28 (&x)[N], const F28 (&y)[N], std::integer_sequence<int, K...>) {
+  int32_t dx[N][7], dy[N][7], m[14];
+  CPX_UNROLL for (int n = 0; n < N; n++) {
+    CPX_UNROLL for (int i = 0; i < 7; i++) {
+      dx[n][i] = x[n].v[i] - x[n].v[i + 7];   // |.| < 2^29
+      dy[n][i] = y[n].v[i + 7] - y[n].v[i];
+    }
+  }
+  int64_t e[20];
+  F28 t;
+  int64_t acc = 0;
+  (f28_kara_col<K, N>(x, y, dx, dy, e, m, acc, t), ...);
+  t.v[13] = (int32_t)acc;
+  return t;
+}
+template <int N> CPX_HD F28 f28_kara_redc(const F28 (&x)[N], const F28 (&y)[N]) {
+  return f28_kara_cols<N>(x, y, std::make_integer_sequence<int, 27>());
+}
+CPX_HD F28 f28_mul_body_kara(const F28& a, const F28& b) {
+  const F28 x[1] = {a}, y[1] = {b};
+  return f28_kara_redc<1>(x, y);
+}
+CPX_HD F28 f28_mulsub_body_kara(const F28& a, const F28& b, const F28& c, const F28& d) {
+  F28 nc;
+  CPX_UNROLL for (int i = 0; i < 14; i++) nc.v[i] = -c.v[i];
+  const F28 x[2] = {a, nc}, y[2] = {b, d};
+  return f28_kara_redc<2>(x, y);
+}
+
+// Which body a product uses is a compile-time choice (template argument KARA), per call site; the default is the Karatsuba
+// form.  CPX_F28_KARATSUBA=0 at build time makes the schoolbook form the default everywhere (A/B builds, the CPU tests).
+#ifndef CPX_F28_KARATSUBA
+#define CPX_F28_KARATSUBA 1
+#endif
+constexpr bool F28_KARA = CPX_F28_KARATSUBA != 0;
+template <bool KARA = F28_KARA> CPX_HD F28 f28_mul_body(const F28& a, const F28& b) {
+  if constexpr (KARA) return f28_mul_body_kara(a, b);
+  else return f28_mul_body_school(a, b);
+}
+template <bool KARA = F28_KARA> CPX_HD F28 f28_mulsub_body(const F28& a, const F28& b, const F28& c, const F28& d) {
+  if constexpr (KARA) return f28_mulsub_body_kara(a, b, c, d);
+  else return f28_mulsub_body_school(a, b, c, d);
+}
 // out-of-line entry with scalar register arguments (same calling-convention reasoning as fe_mul_regs12)
 #define CPX_L14(p) p##0, p##1, p##2, p##3, p##4, p##5, p##6, p##7, p##8, p##9, p##10, p##11, p##12, p##13
 #define CPX_A14(p) int32_t p##0, int32_t p##1, int32_t p##2, int32_t p##3, int32_t p##4, int32_t p##5, int32_t p##6, int32_t p##7, int32_t p##8, int32_t p##9, int32_t p##10, int32_t p##11, int32_t p##12, int32_t p##13
-CPX_HD_FN F28 f28_mul_regs(CPX_A14(a), CPX_A14(b)) {
+template <bool KARA> CPX_HD_FN F28 f28_mul_regs(CPX_A14(a), CPX_A14(b)) {
   const F28 x{{CPX_L14(a)}}, y{{CPX_L14(b)}};
-  return f28_mul_body(x, y);
+  return f28_mul_body<KARA>(x, y);
 }
-CPX_HD F28 f28_mul(const F28& a, const F28& b) {
-  return f28_mul_regs(a.v[0], a.v[1], a.v[2], a.v[3], a.v[4], a.v[5], a.v[6], a.v[7], a.v[8], a.v[9], a.v[10], a.v[11], a.v[12], a.v[13],
-                      b.v[0], b.v[1], b.v[2], b.v[3], b.v[4], b.v[5], b.v[6], b.v[7], b.v[8], b.v[9], b.v[10], b.v[11], b.v[12], b.v[13]);
+template <bool KARA = F28_KARA> CPX_HD F28 f28_mul(const F28& a, const F28& b) {
+  return f28_mul_regs<KARA>(a.v[0], a.v[1], a.v[2], a.v[3], a.v[4], a.v[5], a.v[6], a.v[7], a.v[8], a.v[9], a.v[10], a.v[11], a.v[12], a.v[13],
+                            b.v[0], b.v[1], b.v[2], b.v[3], b.v[4], b.v[5], b.v[6], b.v[7], b.v[8], b.v[9], b.v[10], b.v[11], b.v[12], b.v[13]);
 }
 // Squaring: the 91 off-diagonal limb products are taken once against the doubled operand (301 multiply-adds
 // instead of 392).
