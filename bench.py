@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — shuffle proofs/sec (prove + verify) at ell = 252 on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--ell 252]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--ell 252] [--full]
 
 A "step" = one pass of the hot path over one batch: CurdleproofsProof::new followed by
 CurdleproofsProof::verify for B independent ell = 252 instances (BASELINE configs[1] instance shape,
 B of them = the per-GPU share of configs[3]) whose public inputs are already resident in HBM.
 Weak scaling: every rank / GPU processes its own B instances, no data-path collective.
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 with `roofline` (from the timed region's kernel statistics) and `cpu_baseline` (null).
+A plain run does only what that line needs: set-up, warm-up, the timed steps, --dump-outputs.  --full adds everything else after the
+timed region: the upload-inclusive rate, the isolated pass and the product roofline, config 5, the literal BASELINE shapes, ell = 508 / 1020,
+the CPU baselines (and their comparison of GPU proofs with the oracle's bytes) and the HBM traffic from rocprofv3 child passes.
 """
 import argparse
 import json
@@ -16,6 +19,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before anything touches HIP:
 import random
 import sys
 import time
+T_START = time.perf_counter()   # (setup_s.since_start: the run's own time before its warm-up)
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -35,55 +39,85 @@ def synth_scalars(seed, n):
     return a.tobytes()
 
 
+def commitments(ctx, crs_G, scalars, B):
+    """M of B instances, M_p = msm(crs_G, scalars_p) (util.rs:99-103: the permutation's indices and the 4 blinders over the n = ell + 4 bases
+    G_i), for all instances at once: ONE scale launch takes every product s_{p,i} G_i, then log2 n folds with gamma = 1 add the halves of every
+    instance's row (PL + 1 * PR).  Every point is affine and canonical on the way, so M_p is the same point util::msm gives (which costs one call
+    per instance); it is handed over in Jacobian form with Z = 1 (Z = 0 for the identity): cpx_batch_load takes any Jacobian representation, the
+    prover and the verifier normalise M before they use it."""
+    import numpy as np
+    import curdleproofs_amd as cpx
+    from curdleproofs_amd import params as pr
+    AFF = cpx.AFF
+    n = len(crs_G) // AFF
+    pts = np.frombuffer(ctx.scale(crs_G * B, scalars), dtype=np.uint8).reshape(B, n, AFF)
+    one = pr.fr_to_wire(1)
+    h = n
+    while h > 1:   # n is a power of two (CPX_ERR_NOT_POW2 otherwise)
+        h //= 2
+        pts = np.frombuffer(ctx.fold(pts[:, :h].tobytes(), pts[:, h:2 * h].tobytes(), one), dtype=np.uint8).reshape(B, h, AFF)
+    aff = pts.reshape(B, AFF)
+    z = np.where(aff.any(axis=1)[:, None], np.frombuffer(pr.fp_to_wire(1), dtype=np.uint8)[None, :], np.uint8(0))
+    return np.concatenate([aff, z], axis=1).tobytes()
+
+
 def synth_batch(ctx, ell, B, seed, helpers=()):
-    """Synthetic CRS + B shuffle instances built through the product API only (GPU scale / msm).  `helpers`: further contexts whose host threads share
-    the per-proof util::msm calls (M of every instance: 0.8 ms per call, one call at a time per context)."""
+    """Synthetic CRS + B shuffle instances built through the product API only (GPU scale / fold).  `helpers`: further contexts; the first one
+    computes the commitments M beside the scalar multiplications of `ctx`."""
     import threading
     import numpy as np
     import curdleproofs_amd as cpx
     from curdleproofs_amd import params as pr
     t_start = time.perf_counter()
     n = ell + 4
+    AFF, FR = cpx.AFF, cpx.FR
     gen = pr.g1_generator_wire()
     crs = ctx.scale(gen * (ell + 7), synth_scalars(seed * 16 + 1, ell + 7))
     ctx.set_crs(ell, crs)
-    vec_R = ctx.scale(gen * (B * ell), synth_scalars(seed * 16 + 2, B * ell))
-    vec_S = ctx.scale(vec_R, synth_scalars(seed * 16 + 3, B * ell))
-    k_wire = synth_scalars(seed * 16 + 4, B)
+    # M needs the CRS points, the permutations and the blinders only: drawn first, committed on a helper context while `ctx` builds the ciphertexts
     mbl_all = synth_scalars(seed * 16 + 5, 4 * B)
-    AFF, FR = cpx.AFF, cpx.FR
-    k_rep = np.repeat(np.frombuffer(k_wire, dtype=np.uint8).reshape(B, FR), ell, axis=0).tobytes()
-    kR_all = np.frombuffer(ctx.scale(vec_R, k_rep), dtype=np.uint8).reshape(B, ell, AFF)   # util.rs:94-95, all proofs in one launch
-    kS_all = np.frombuffer(ctx.scale(vec_S, k_rep), dtype=np.uint8).reshape(B, ell, AFF)
-    del k_rep
-    t_points = time.perf_counter()
     rng = np.random.default_rng(seed)
     perm_all = np.stack([rng.permutation(ell) for _ in range(B)]).astype(np.uint32)      # [B][ell]
-    rows = np.arange(B)[:, None]
-    vec_T = kR_all[rows, perm_all].tobytes()                                               # T_i = k R_sigma(i)
-    vec_U = kS_all[rows, perm_all].tobytes()
-    del kR_all, kS_all
     idx_wire = np.frombuffer(b"".join(pr.fr_to_wire(i) for i in range(ell)), dtype=np.uint8).reshape(ell, FR)
-    sigma_all = idx_wire[perm_all]                                                         # [B][ell][32]: util.rs:99-103
-    crs_G = ctx.marshal(crs[:n * AFF])
-    Ms = [None] * B
-    workers = [ctx] + list(helpers)
+    m_scalars = np.concatenate([idx_wire[perm_all], np.frombuffer(mbl_all, dtype=np.uint8).reshape(B, 4, FR)], axis=1).tobytes()   # util.rs:99-103
+    commit = dict(ctx=helpers[0] if helpers else ctx)
 
-    def commit(w):
-        c = workers[w]
-        for p in range(w, B, len(workers)):
-            Ms[p] = c.msm(crs_G, sigma_all[p].tobytes() + mbl_all[p * 4 * FR:(p + 1) * 4 * FR])
-    th = [threading.Thread(target=commit, args=(w,)) for w in range(1, len(workers))]
-    for t in th:
-        t.start()
-    commit(0)
-    for t in th:
-        t.join()
+    def commit_all():
+        t0 = time.perf_counter()
+        try:
+            commit["M"] = commitments(commit["ctx"], crs[:n * AFF], m_scalars, B)
+        except BaseException as e:   # (re-raised by the caller)
+            commit["error"] = e
+        commit["s"] = time.perf_counter() - t0
+    th = None
+    if helpers:
+        th = threading.Thread(target=commit_all)
+        th.start()
+    try:
+        vec_R = ctx.scale(gen * (B * ell), synth_scalars(seed * 16 + 2, B * ell))
+        vec_S = ctx.scale(vec_R, synth_scalars(seed * 16 + 3, B * ell))
+        k_wire = synth_scalars(seed * 16 + 4, B)
+        k_rep = np.repeat(np.frombuffer(k_wire, dtype=np.uint8).reshape(B, FR), ell, axis=0).tobytes()
+        kR_all = np.frombuffer(ctx.scale(vec_R, k_rep), dtype=np.uint8).reshape(B, ell, AFF)   # util.rs:94-95, all proofs in one launch
+        kS_all = np.frombuffer(ctx.scale(vec_S, k_rep), dtype=np.uint8).reshape(B, ell, AFF)
+        del k_rep
+        t_points = time.perf_counter()
+        rows = np.arange(B)[:, None]
+        vec_T = kR_all[rows, perm_all].tobytes()                                               # T_i = k R_sigma(i)
+        vec_U = kS_all[rows, perm_all].tobytes()
+        del kR_all, kS_all
+    finally:
+        if th is not None:
+            th.join()
+    if th is None:
+        commit_all()
+    if "error" in commit:
+        raise commit["error"]
     t_end = time.perf_counter()
-    return dict(crs=crs, vec_R=vec_R, vec_S=vec_S, vec_T=vec_T, vec_U=vec_U, M=b"".join(Ms), perms=perm_all.reshape(-1).tolist(),
+    return dict(crs=crs, vec_R=vec_R, vec_S=vec_S, vec_T=vec_T, vec_U=vec_U, M=commit["M"], perms=perm_all.reshape(-1).tolist(),
                 k=k_wire, mbl=mbl_all, prand=synth_scalars(seed * 16 + 6, B * (3 * n + 9)), vrand=synth_scalars(seed * 16 + 7, B * 8),
-                setup_s=dict(total=time.perf_counter() - t_start, crs_and_scalar_multiplications=t_points - t_start, per_proof_permute_and_commit=t_end - t_points,
-                             commit_threads=len(workers)))
+                setup_s=dict(total=time.perf_counter() - t_start, crs_and_scalar_multiplications=t_points - t_start, permute_and_commit=t_end - t_points,
+                             commitments=commit["s"], commitments_beside_the_scalar_multiplications=th is not None))
 
 
 def _instance(data, ell, i):
@@ -272,7 +306,7 @@ def run_config5(args, ctxs, shares, data, ell, B, K, world, rank, dist, torch, r
                                  achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS, traffic=None, avg_launch_ms=avg_ms,
                                  launches=st["launches"], alg_bytes_per_launch=bpl, units_per_launch=st["units"] / max(st["launches"], 1)),
                    cpu_baseline=None)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             base = cpu_baseline(ell, data, None)
             out["cpu_baseline"] = dict(value=1.0 / base["verify_s"], unit="proofs/s", cores=1, kind="port",
                                        sample="CurdleproofsProof::verify of instance 0 (oracle/, single thread, %.3f s each); the oracle has no batched verifier" % base["verify_s"])
@@ -629,7 +663,11 @@ def main():
     ap.add_argument("--ell", type=int, default=252)
     ap.add_argument("--fused-verify", action="store_true", help="measure BASELINE config 5 instead: the batched verifier (one accumulated MSM over "
                     "all proofs of all GPUs, one all-gather of 144-byte partial sums); not the headline metric")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline, after the timed region: the rates with the instances uploaded "
+                    "in every pass, an isolated pass per kernel, the product peak and roofline.valu, single_proof, config5, the literal BASELINE shapes, "
+                    "ell=508 / 1020, the CPU baselines and roofline.traffic (rocprofv3 child passes); --fused-verify: its cpu_baseline.  Without it a run "
+                    "sets up, warms up, times the steps, dumps (--dump-outputs) and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--host-threads", type=int, default=0, help="host worker threads per engine context (0 = cores / (ranks x contexts), clamped to [2, 24])")
     ap.add_argument("--synth-cache", default="", help="pickle file for the synthetic batch (created if missing): keeps profiled runs free of setup kernels")
     ap.add_argument("--ctxs", type=int, default=4, help="engine contexts (HIP streams, one host thread each) per GPU; the batch is split over them: the "
@@ -637,7 +675,7 @@ def main():
                     "kernels) and the tails of its launches run beside the others' MSM waves.  4 x 8192 since round 6 (one box, processes alternating: "
                     "2 x 8192 16.44 k, 4 x 8192 16.84 k proofs/s, +2.4 %% in both pairs, profiles/r06_ctxs_2_vs_4.txt; 233 of the 288 GB of HBM; round 5 "
                     "kept 2 x 8192 for the footprint).  --ab-lib doubles the contexts: run it with --ctxs 2 --batch 16384")
-    ap.add_argument("--no-extra-shapes", action="store_true", help="skip the extra keys: throughput at BASELINE's literal batch shapes (128 / 1024 proofs per "
+    ap.add_argument("--no-extra-shapes", action="store_true", help="with --full: skip the extra keys: throughput at BASELINE's literal batch shapes (128 / 1024 proofs per "
                     "GPU), ell=1020 throughput and the all-cores CPU baseline")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="engine option for every context (cpx_ctx_set_option), e.g. "
                     "--opt late_rounds=0 for an A/B run")
@@ -648,7 +686,7 @@ def main():
                     "curdleproofs_amd.build.build_variant): a second set of contexts with the same instances lives beside the first, blocks of passes alternate")
     ap.add_argument("--ab-rounds", type=int, default=6, help="rounds of the A/B (each round = one block per variant)")
     ap.add_argument("--ab-passes", type=int, default=0, help="timed passes per block (0 = about 2 s worth)")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc child passes that measure roofline.traffic (then null)")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the rocprofv3 --pmc child passes that measure roofline.traffic (then null)")
     ap.add_argument("--traffic-child", default="", help=argparse.SUPPRESS)   # internal: the process rocprofv3 wraps (one pass of one context under counters)
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what their last step returned as DIR/*.npy (float32): "
                     "every proof's verdict and the bytes of the proofs (a fixed, seeded sample when all of them exceed 64 MB); the inputs are seeded, "
@@ -747,7 +785,9 @@ def main():
         try:
             if K_ > int(os.environ.get("CPX_BENCH_FAIL_SETUP_ABOVE", "1000000")):   # test hook: rehearses the fallback without exhausting HBM
                 raise cpx.CpxError(cpx.CPX_ERR_HIP, "CPX_BENCH_FAIL_SETUP_ABOVE: set-up with %d contexts refused" % K_)
+            t_begin = time.perf_counter()
             cs = [cpx.Context(local_rank, options=engine_opts) for _ in range(K_)]          # raises without a GPU: no CPU fallback
+            t_contexts = time.perf_counter()
             # host worker threads per context: the cores of the node divided over ranks x contexts (all ranks share one node)
             ht = args.host_threads or max(2, min(24, effective_cores() // (world * K_)))
             for c in cs:
@@ -770,7 +810,9 @@ def main():
                     import pickle
                     with open(cache, "wb") as f:
                         pickle.dump(data_, f)
+            t_batch = time.perf_counter()
             shs = make_shares(cs, data_, B_ // K_, cs[0])
+            t_shares = time.perf_counter()
             errs = []
 
             def probe(k):
@@ -786,6 +828,9 @@ def main():
                 t.join()
             if errs:
                 raise errs[0]
+            # set-up by stage (synthetic_batch: synth_batch's own split beside it): what a plain run spends before its warm-up
+            data_["setup_s"] = dict(data_["setup_s"], contexts=t_contexts - t_begin, synthetic_batch=t_batch - t_contexts, shares_and_upload=t_shares - t_batch,
+                                    first_pass=time.perf_counter() - t_shares, since_start=time.perf_counter() - T_START)
             return cs, ht, data_, shs
         except Exception:
             for c in cs:
@@ -962,18 +1007,21 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             d_ = float(t.item())
         return d_, nb_
-    dt_up, nbad_up = timed_upload_leg(True)
-    dt_up_sync, nbad_sync = timed_upload_leg(False)
-    nbad_up += nbad_sync
+    nbad_up = 0
+    if args.full:
+        dt_up, nbad_up = timed_upload_leg(True)
+        dt_up_sync, nbad_sync = timed_upload_leg(False)
+        nbad_up += nbad_sync
     hbm_used_gb = None
     if torch.cuda.is_available():
         free_b, total_b = torch.cuda.mem_get_info()
         hbm_used_gb = round((total_b - free_b) / 1e9, 1)   # with every context's batch resident: the working set of the timed region
-    for c in ctxs[2:]:   # what follows (isolated pass, literal shapes, other proof sizes) runs on one or two contexts: the others give their HBM back
-        c.close()
-    ctxs = ctxs[:2]
+    if args.full:
+        for c in ctxs[2:]:   # what follows (isolated pass, literal shapes, other proof sizes) runs on one or two contexts: the others give their HBM back
+            c.close()
+        ctxs = ctxs[:2]
     iso = None
-    if rank == 0:   # one more pass of context 0 ALONE, outside the timed region, with its side stream's kernels in line on the main stream
+    if rank == 0 and args.full:   # one more pass of context 0 ALONE, outside the timed region, with its side stream's kernels in line on the main stream
         c = ctxs[0]  # (option serial_streams): every kernel then has the GPU to itself and its duration is its own — in the timed region a
         c.set_option("serial_streams", 1)   # kernel shares the GPU with the other context AND with its own context's side stream
         c.set_profiling(True)
@@ -1007,55 +1055,56 @@ def main():
         avg_ms = st["ms"] / max(st["launches"], 1)
         bytes_per_launch = st["alg_bytes"] / max(st["launches"], 1)
         achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms else 0.0
-        traffic, traffic_src = None, dict(skipped="--no-traffic")   # measured at the end of this run (measure_traffic), or null
+        traffic, traffic_src = None, dict(skipped="--no-traffic" if args.full else "measured with --full")   # measured at the end of a --full run (measure_traffic), or null
         roofline = dict(bound="hbm", kernel=dom, achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
                         traffic=traffic, traffic_source=traffic_src, avg_launch_ms=avg_ms, launches=st["launches"], alg_bytes_per_launch=bytes_per_launch,
                         units_per_launch=st["units"] / max(st["launches"], 1),
-                        # every launch of this process (warm-up + timed region + the isolated pass): the population
+                        # every launch of this process (warm-up + timed region + with --full the isolated pass): the population
                         # `rocprofv3 --kernel-trace --stats` averages over when it wraps this command
                         avg_launch_ms_all_launches=(st["ms"] + warm.get(dom, {}).get("ms", 0.0) + (iso or {}).get(dom, {}).get("ms", 0.0))
                         / max(1, st["launches"] + warm.get(dom, {}).get("launches", 0) + (iso or {}).get(dom, {}).get("launches", 0)),
                         note="integer big-number path: VALU (v_mad_i64_i32) bound, the HBM fraction is tiny by construction; "
-                             "roofline.valu gives the modular-multiplication roofline (DESIGN.md section 5)")
+                             "roofline.valu (--full) gives the modular-multiplication roofline (DESIGN.md section 5)")
         # The honest bound of this integer path: modular multiplications on the VALU.  Peak = dependent
         # Montgomery-product chains on the table kernels' 28-bit-limb field at full occupancy, measured now on this GPU
         # (k_bench_f28mul: 392 multiply-adds per product); achieved = the dominant kernel's point additions x the product equivalents
         # of one mixed addition.  The extended-Jacobian mixed addition of the bucket loops is 8M + 2S with the two products of Y3
         # under one reduction: 3542 multiply-adds = 9.04 products of 392 (rounds 1-2 of this build counted 11, the Jacobian 7M + 4S,
         # for an addition that cost 9.5: their fractions read 16 % too high).
-        mulmods_per_point = msm_pair_cost(dom)
-        ctxs[0].set_option("bench_field", 28)
-        peak_mm = ctxs[0].bench_fpmul(2048, 1000, 2)
-        ach_mm = st["units"] * mulmods_per_point / (st["ms"] * 1e-3) if st["ms"] else 0.0
-        roofline["valu"] = dict(achieved=ach_mm, peak=peak_mm, unit="381-bit modular products/s", frac=ach_mm / peak_mm if peak_mm else None,
-                                mulmods_per_point=mulmods_per_point,
-                                note="kernel time is measured with all engine contexts sharing the GPU, so it includes the other contexts' kernels; "
-                                     "'isolated' repeats the measurement after the timed region with one context alone and its side stream's kernels in line "
-                                     "(option serial_streams): the kernel has the GPU to itself")
-        pair_cost = msm_pair_cost
-        # The whole pass against the same peak: the products of the MSM additions of a prove + verify (every point-scalar pair of every MSM kernel of
-        # the timed region x the additions a pair costs x 9.04 products) x the measured rate.  Everything else a pass executes — per-proof table
-        # build, late-round materialisation, bucket reductions, decompression, transcripts — is overhead by this count, and so is idle issue time.
-        useful = sum(v["units"] * pair_cost(k) for k, v in stats.items() if msm_pair_cost(k) and v["launches"]) / max(1.0, float(B * args.steps))
-        roofline["valu"]["whole_pass"] = dict(frac=useful * (value / world) / peak_mm if peak_mm else None, useful_products_per_proof=useful,
-                                              useful_products_per_s_per_gpu=useful * value / world,
-                                              note="useful = modular products of the MSM additions only; per GPU against the product peak measured in this run")
-        if iso:   # every MSM kernel, one context alone: point-scalar pairs, additions x their product equivalents against the measured peak
-            roofline["valu"]["isolated_by_kernel"] = {
-                k: dict(pairs_per_proof=v["units"] / (B // K), ms_per_proof_batch=v["ms"],
-                        frac=(v["units"] * pair_cost(k) / (v["ms"] * 1e-3) / peak_mm) if v["ms"] and peak_mm else None,
-                        # the same measurement in the accounting of rounds 1-2a (11 products per addition), for comparison with their numbers
-                        frac_at_11_products_per_addition=(v["units"] * pair_cost(k) * (11.0 / PROD_PER_ADD if k.split("<")[0] != "k_msm_accw" else 1.0)
-                                                          / (v["ms"] * 1e-3) / peak_mm) if v["ms"] and peak_mm else None)
-                for k, v in iso.items() if msm_pair_cost(k) and v["ms"] and v["launches"] > 0}
-        if iso and dom in iso and iso[dom]["ms"]:
-            ist = iso[dom]
-            iso_mm = ist["units"] * mulmods_per_point / (ist["ms"] * 1e-3)
-            roofline["valu"]["isolated"] = dict(achieved=iso_mm, frac=iso_mm / peak_mm if peak_mm else None, launches=ist["launches"],
-                                                avg_launch_ms=ist["ms"] / max(ist["launches"], 1))
-            # the isolated pass as a whole: one context, one stream — the pass is the plain sum of its kernels
-            roofline["valu"]["isolated_pass"] = dict(proofs=B // K, kernel_ms={k: v["ms"] for k, v in iso.items() if v["launches"] and not k.startswith("host_")},
-                                                     wall_ms=iso.get("host_prove_wall", {}).get("ms", 0.0) + iso.get("host_verify_wall", {}).get("ms", 0.0))
+        if args.full:
+            mulmods_per_point = msm_pair_cost(dom)
+            ctxs[0].set_option("bench_field", 28)
+            peak_mm = ctxs[0].bench_fpmul(2048, 1000, 2)
+            ach_mm = st["units"] * mulmods_per_point / (st["ms"] * 1e-3) if st["ms"] else 0.0
+            roofline["valu"] = dict(achieved=ach_mm, peak=peak_mm, unit="381-bit modular products/s", frac=ach_mm / peak_mm if peak_mm else None,
+                                    mulmods_per_point=mulmods_per_point,
+                                    note="kernel time is measured with all engine contexts sharing the GPU, so it includes the other contexts' kernels; "
+                                         "'isolated' repeats the measurement after the timed region with one context alone and its side stream's kernels in line "
+                                         "(option serial_streams): the kernel has the GPU to itself")
+            pair_cost = msm_pair_cost
+            # The whole pass against the same peak: the products of the MSM additions of a prove + verify (every point-scalar pair of every MSM kernel of
+            # the timed region x the additions a pair costs x 9.04 products) x the measured rate.  Everything else a pass executes — per-proof table
+            # build, late-round materialisation, bucket reductions, decompression, transcripts — is overhead by this count, and so is idle issue time.
+            useful = sum(v["units"] * pair_cost(k) for k, v in stats.items() if msm_pair_cost(k) and v["launches"]) / max(1.0, float(B * args.steps))
+            roofline["valu"]["whole_pass"] = dict(frac=useful * (value / world) / peak_mm if peak_mm else None, useful_products_per_proof=useful,
+                                                  useful_products_per_s_per_gpu=useful * value / world,
+                                                  note="useful = modular products of the MSM additions only; per GPU against the product peak measured in this run")
+            if iso:   # every MSM kernel, one context alone: point-scalar pairs, additions x their product equivalents against the measured peak
+                roofline["valu"]["isolated_by_kernel"] = {
+                    k: dict(pairs_per_proof=v["units"] / (B // K), ms_per_proof_batch=v["ms"],
+                            frac=(v["units"] * pair_cost(k) / (v["ms"] * 1e-3) / peak_mm) if v["ms"] and peak_mm else None,
+                            # the same measurement in the accounting of rounds 1-2a (11 products per addition), for comparison with their numbers
+                            frac_at_11_products_per_addition=(v["units"] * pair_cost(k) * (11.0 / PROD_PER_ADD if k.split("<")[0] != "k_msm_accw" else 1.0)
+                                                              / (v["ms"] * 1e-3) / peak_mm) if v["ms"] and peak_mm else None)
+                    for k, v in iso.items() if msm_pair_cost(k) and v["ms"] and v["launches"] > 0}
+            if iso and dom in iso and iso[dom]["ms"]:
+                ist = iso[dom]
+                iso_mm = ist["units"] * mulmods_per_point / (ist["ms"] * 1e-3)
+                roofline["valu"]["isolated"] = dict(achieved=iso_mm, frac=iso_mm / peak_mm if peak_mm else None, launches=ist["launches"],
+                                                    avg_launch_ms=ist["ms"] / max(ist["launches"], 1))
+                # the isolated pass as a whole: one context, one stream — the pass is the plain sum of its kernels
+                roofline["valu"]["isolated_pass"] = dict(proofs=B // K, kernel_ms={k: v["ms"] for k, v in iso.items() if v["launches"] and not k.startswith("host_")},
+                                                         wall_ms=iso.get("host_prove_wall", {}).get("ms", 0.0) + iso.get("host_verify_wall", {}).get("ms", 0.0))
         out = dict(metric="shuffle proofs/sec (prove+verify) at ell=%d, BLS12-381" % ell, value=value, unit="proofs/s", n_gpus=world,
                    steps=args.steps, warmup=args.warmup, ms_per_step=1e3 * dt / args.steps, higher_is_better=True, scaling="weak",
                    vs_baseline=None, dtype="int64", data="synthetic",
@@ -1065,23 +1114,24 @@ def main():
                                ell=ell, batch_per_gpu=B, global_batch=B * world, engine_contexts_per_gpu=K, host_threads_per_context=host_threads,
                                fix_bits=ctxs[0].get_option("fix_bits"), fix_bits_effective=ctxs[0].get_option("fix_bits_effective"), gpu_max_hw_queues=os.environ.get("GPU_MAX_HW_QUEUES"), hbm_used_gb=hbm_used_gb, fallback=fallback, parallelism="proofs sharded over %d GPU(s), no collective" % world),
                    all_verified=all_ok and nbad_up == 0,
-                   # the same metric with the 97 KB public instance of every proof uploaded (cpx_batch_load) inside the timed region on every pass
-                   value_incl_instance_upload=world * B * up_steps / dt_up,
-                   instance_upload=dict(steps=up_steps, ms_per_step=1e3 * dt_up / up_steps, ratio_to_value=(world * B * up_steps / dt_up) / value,
-                                        bytes_per_proof=4 * ell * cpx.AFF + cpx.JAC,
-                                        sync_load=dict(value=world * B * up_steps / dt_up_sync, ratio_to_value=(world * B * up_steps / dt_up_sync) / value,
-                                                       note="cpx_batch_load at the top of every pass: the context's streams idle during its own upload"),
-                                        note="value: instances resident in HBM before the clock starts (the contract's 'inputs already resident'); here every pass of "
-                                             "every context uploads an instance of its share from page-locked host memory: cpx_batch_load_begin before the prove (the next "
-                                             "pass's instance, beside this pass's kernels), cpx_batch_load_end after the verify; measured right after the timed region"),
                    setup_s=data.get("setup_s"), host_rss_peak_gb=round(__import__("resource").getrusage(__import__("resource").RUSAGE_SELF).ru_maxrss / 1e6, 2),
                    algorithmic_bytes_per_proof=b_prove + b_verify,
                    algorithmic_GBps=value * (b_prove + b_verify) / 1e9,
                    kernel_ms_per_step={k: v["ms"] / args.steps for k, v in stats.items() if v["launches"]},
-                   vs_readme_i7_8550u=value / README_I7_PROOFS_PER_S, roofline=roofline)
-        # Everything below runs on rank 0 only, outside the timed region, at ANY N (the other ranks wait at the final barrier): the
-        # literal BASELINE shapes, the batched verifier, the other proof sizes and the CPU baseline belong to every line.  Every stage is guarded: a
-        # failure in an extra (round 5: a KeyError after the timed region took rank 0 down, and the line with it) is recorded under `errors` and the
+                   vs_readme_i7_8550u=value / README_I7_PROOFS_PER_S, roofline=roofline, cpu_baseline=None)
+        if args.full:
+            # the same metric with the 97 KB public instance of every proof uploaded (cpx_batch_load) inside the timed region on every pass
+            out["value_incl_instance_upload"] = world * B * up_steps / dt_up
+            out["instance_upload"] = dict(steps=up_steps, ms_per_step=1e3 * dt_up / up_steps, ratio_to_value=(world * B * up_steps / dt_up) / value,
+                                          bytes_per_proof=4 * ell * cpx.AFF + cpx.JAC,
+                                          sync_load=dict(value=world * B * up_steps / dt_up_sync, ratio_to_value=(world * B * up_steps / dt_up_sync) / value,
+                                                         note="cpx_batch_load at the top of every pass: the context's streams idle during its own upload"),
+                                          note="value: instances resident in HBM before the clock starts (the contract's 'inputs already resident'); here every pass of "
+                                               "every context uploads an instance of its share from page-locked host memory: cpx_batch_load_begin before the prove (the next "
+                                               "pass's instance, beside this pass's kernels), cpx_batch_load_end after the verify; measured right after the timed region")
+        # With --full, everything below runs on rank 0 only, outside the timed region, at ANY N (the other ranks wait at the final barrier): the
+        # literal BASELINE shapes, the batched verifier, the other proof sizes and the CPU baseline belong to every --full line.  Every stage is guarded:
+        # a failure in an extra (round 5: a KeyError after the timed region took rank 0 down, and the line with it) is recorded under `errors` and the
         # contract line is still printed.
         AFF, FR, JAC = cpx.AFF, cpx.FR, cpx.JAC
         c0, n_ = ctxs[0], ell + 4
@@ -1168,21 +1218,21 @@ def main():
             if tr:
                 out["roofline"]["traffic_over_algorithmic"] = tr / bytes_per_launch if bytes_per_launch else None
 
-        out["cpu_baseline"] = None
-        if not args.no_extra_shapes:
-            stage("config5", st_config5)
-        stage("single_proof", st_single)
-        if not args.no_extra_shapes:
-            stage("baseline_shapes", st_shapes)
-            stage("config5_literal_shapes", st_config5_literal)
-            if ell == 252:
-                stage("other_proof_sizes", st_other_ells)
-        if not args.no_cpu_baseline:   # the CPU oracle beside the GPU number in the same run, on rank 0 at every N
-            stage("cpu_baseline", st_cpu)
+        if args.full:
             if not args.no_extra_shapes:
-                stage("cpu_baseline_all_cores", st_cpu_all)
-        if not args.no_traffic and os.environ.get("CPX_BENCH_TRAFFIC", "1") != "0":
-            stage("traffic", st_traffic)
+                stage("config5", st_config5)
+            stage("single_proof", st_single)
+            if not args.no_extra_shapes:
+                stage("baseline_shapes", st_shapes)
+                stage("config5_literal_shapes", st_config5_literal)
+                if ell == 252:
+                    stage("other_proof_sizes", st_other_ells)
+            if not args.no_cpu_baseline:   # the CPU oracle beside the GPU number in the same run, on rank 0 at every N
+                stage("cpu_baseline", st_cpu)
+                if not args.no_extra_shapes:
+                    stage("cpu_baseline_all_cores", st_cpu_all)
+            if not args.no_traffic and os.environ.get("CPX_BENCH_TRAFFIC", "1") != "0":
+                stage("traffic", st_traffic)
         if errors:
             out["errors"] = errors
         print(json.dumps(out))

@@ -8,12 +8,12 @@ RND=${RND:-r06}
 R=$PWD
 O=$R/gpurun_out/prof
 S="--synth-cache /tmp/synth.pkl"
-LEAN="--no-cpu-baseline --no-extra-shapes --no-traffic"
+LEAN="--full --no-cpu-baseline --no-extra-shapes --no-traffic"
 mkdir -p $O
 echo "commit ${COMMIT:-unknown}  $(date -u +%FT%TZ)" > $O/${RND}_collection.txt
 python bench.py $LEAN $S --steps 1 --warmup 0 > /dev/null 2>&1   # builds the synthetic batch cache
-# 1. the bench line as the driver runs it (20 steps, 5 warm-up): THE line DESIGN.md / README.md quote
-python bench.py $S --steps 20 --warmup 5 > $O/bench_default.log 2>&1
+# 1. the --full bench line at the driver's 20 steps, 5 warm-up: THE line DESIGN.md / README.md quote
+python bench.py $S --full --steps 20 --warmup 5 > $O/bench_default.log 2>&1
 tail -1 $O/bench_default.log > $O/${RND}_bench.json
 cd /tmp && export TMPDIR=/tmp
 # 2. kernel statistics of the same command (rocprofv3 --kernel-trace --stats) + the line the profiled process printed
@@ -35,7 +35,7 @@ python bench.py --batch 1024 --ctxs 1 --ab late_min_batch=2048,1024 --ab-rounds 
 python bench.py --batch 128 --ctxs 1 --ab fused_rounds_max=0,256 --ab-rounds 6 2>/dev/null | tail -1 > $O/${RND}_ab_fused_rounds_128_proofs.json
 [ "$1" = quick ] && exit 0
 # 5. config 5 across the contexts of one GPU, one context alone, every kernel alone (serial_streams)
-python bench.py --fused-verify $S 2>/dev/null | tail -1 > $O/${RND}_bench_config5.json
+python bench.py --fused-verify --full $S 2>/dev/null | tail -1 > $O/${RND}_bench_config5.json
 python bench.py $S $LEAN --ctxs 1 --batch 8192 --steps 4 2>/dev/null | tail -1 > $O/${RND}_bench_one_context.json
 python bench.py --synth-cache /tmp/synth2.pkl $LEAN --ctxs 2 --batch 16384 --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/${RND}_bench_two_contexts.json   # round 5's default
 python bench.py $S $LEAN --ctxs 1 --batch 8192 --steps 4 --opt serial_streams=1 2>/dev/null | tail -1 > $O/${RND}_bench_serial_streams.json

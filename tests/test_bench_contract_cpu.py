@@ -165,3 +165,36 @@ def test_dump_outputs_keeps_a_fixed_sample_within_64_mb(tmp_path):
         assert a["verdicts"].shape == (B,) and list(np.flatnonzero(a["verdicts"])) == [(k + 1) * B // K - 1 for k in range(K)]
         assert np.array_equal(a["proofs"], raw[idx].astype(np.float32)) and len(np.unique(idx)) == len(idx)
         assert (len(idx) == B) == (B * psz * 4 < 60 * 1000 * 1000)
+
+
+def test_batched_commitments_are_the_points_util_msm_gives(orc):
+    """bench.commitments builds the M of every synthetic instance at once (one scale of all products, then log2 n folds with gamma = 1) where
+    util::msm takes one call per instance.  Run on the oracle's scale / fold, which Context.scale / .fold mirror: every row is the point msm gives,
+    in Jacobian form with Z = 1 — and a row whose products sum to the identity (all scalars zero) is the identity, Z = 0."""
+    import random
+    sys.path.insert(0, ROOT)
+    import bench
+    from curdleproofs_amd import params as pr
+
+    class OracleOps:
+        scale = staticmethod(orc.g1_scale)
+        fold = staticmethod(orc.g1_fold)
+    ell, B, AFF, JAC = 28, 5, 96, 144
+    n = ell + 4
+    crs = orc.generate_crs_points(ell)
+    rng = random.Random(5)
+    rows = []
+    for p in range(B):
+        perm = list(range(ell))
+        rng.shuffle(perm)
+        rows.append(b"".join(pr.fr_to_wire(i) for i in perm) + b"".join(pr.fr_to_wire(rng.randrange(pr.R)) for _ in range(4)))
+    rows[3] = pr.fr_to_wire(0) * n
+    M = bench.commitments(OracleOps, crs[:n * AFF], b"".join(rows), B)
+    assert len(M) == B * JAC
+    for p in range(B):
+        want = orc.g1_msm(crs[:n * AFF], rows[p])
+        got = M[p * JAC:(p + 1) * JAC]
+        assert orc.g1_eq_jac(got, want), p
+        assert orc.g1_to_affine(got) == orc.g1_to_affine(want), p
+        assert got[2 * 48:] == (pr.fp_to_wire(1) if p != 3 else bytes(48)), p
+    assert M[3 * JAC:4 * JAC] == bytes(JAC)

@@ -1488,7 +1488,7 @@ def test_bench_two_ranks_on_one_gpu(fused):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--ell", "28", "--batch", "128", "--ctxs", "2", "--steps", "2", "--warmup", "1",
-           "--no-extra-shapes", "--no-traffic"] + (["--fused-verify"] if fused else [])
+           "--full", "--no-extra-shapes", "--no-traffic"] + (["--fused-verify"] if fused else [])
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     if r.returncode != 0:   # no second go (round 5 retried once): the whole output of a failed launch is kept for the reader and the test fails
         os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
@@ -1527,7 +1527,7 @@ def test_bench_eight_ranks_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--ell", "28", "--batch", "64", "--ctxs", "1", "--steps", "2", "--warmup", "1",
-           "--no-extra-shapes", "--no-traffic"]
+           "--full", "--no-extra-shapes", "--no-traffic"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-6000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1607,9 +1607,9 @@ def test_bench_interleaved_ab_of_an_option_and_of_two_library_builds(tmp_path):
 
 
 def test_bench_measures_hbm_traffic_in_the_run_and_reports_the_upload_inclusive_rate():
-    """The bench line's roofline.traffic comes from rocprofv3 --pmc child passes of the run itself (FETCH_SIZE and WRITE_SIZE apart, counters only), the
+    """The --full bench line's roofline.traffic comes from rocprofv3 --pmc child passes of the run itself (FETCH_SIZE and WRITE_SIZE apart, counters only), the
     whole-pass product fraction and the rate with the public instances uploaded inside the timed region sit beside the headline."""
-    d = _run_bench(["--ell", "28", "--batch", "256", "--ctxs", "2", "--steps", "2", "--warmup", "1", "--no-extra-shapes", "--no-cpu-baseline"])
+    d = _run_bench(["--ell", "28", "--batch", "256", "--ctxs", "2", "--steps", "2", "--warmup", "1", "--full", "--no-extra-shapes", "--no-cpu-baseline"])
     r = d["roofline"]
     assert r["traffic"] is not None and r["traffic"] > 0, r["traffic_source"]
     assert r["traffic_source"]["FETCH_SIZE"]["dispatches"] > 0 and r["traffic_source"]["WRITE_SIZE"]["dispatches"] > 0
@@ -1649,6 +1649,45 @@ def test_bench_dump_outputs_hold_the_last_steps_proofs(orc, tmp_path):
                          it["prover_rand"])
         assert bytes(a["proofs"][i].astype(np.uint8)) == want, i
     c.close()
+
+
+def test_plain_bench_run_prints_the_headline_and_nothing_else():
+    """Without --full a run sets up, warms up, times its steps and prints the line: the contract fields, the roofline of the timed region's kernel
+    statistics, cpu_baseline null — no extra stage (upload legs, isolated pass, product peak, config 5, shapes, CPU baselines, traffic) runs."""
+    d = _run_bench(["--ell", "28", "--batch", "256", "--ctxs", "2", "--steps", "2", "--warmup", "1"])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline", "cpu_baseline"):
+        assert k in d, k
+    assert d["all_verified"] is True and d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "int64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 * d["steps"] / (d["ms_per_step"] * 1e-3 * d["steps"])) < 1e-6 * d["value"]
+    assert d["cpu_baseline"] is None and d["roofline"]["frac"] > 0 and d["roofline"]["traffic"] is None and "valu" not in d["roofline"]
+    for k in ("value_incl_instance_upload", "instance_upload", "single_proof", "config5", "baseline_shapes", "ell_508", "ell_1020", "cpu_baseline_all_cores"):
+        assert k not in d, k
+    s = d["setup_s"]
+    assert s["commitments_beside_the_scalar_multiplications"] is True and 0 < s["synthetic_batch"] < s["since_start"]
+
+
+def test_bench_synthetic_commitments_are_the_points_util_msm_gives():
+    """bench.synth_batch commits to every instance at once (bench.commitments: one scale, log2 n folds) on a helper context; every M is the point
+    Context.msm gives instance by instance (util.rs:99-103), in Jacobian form with Z = 1."""
+    import sys
+    import curdleproofs_amd as cpx
+    from curdleproofs_amd import params as pr
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    ell, B = 28, 64
+    c, h = cpx.Context(0), cpx.Context(0)
+    data = bench.synth_batch(c, ell, B, seed=77, helpers=[h])
+    idx = [pr.fr_to_wire(i) for i in range(ell)]
+    crs_G = data["crs"][:(ell + 4) * AFF]
+    for p in range(B):
+        sigma = b"".join(idx[i] for i in data["perms"][p * ell:(p + 1) * ell])
+        want = c.msm(crs_G, sigma + data["mbl"][p * 4 * FR:(p + 1) * 4 * FR])
+        got = data["M"][p * JAC:(p + 1) * JAC]
+        assert c.normalize(got) == c.normalize(want), p
+        assert got[96:] == pr.fp_to_wire(1), p
+    c.close()
+    h.close()
 
 
 def test_staged_instance_upload_keeps_the_loaded_batch_and_then_replaces_it(orc):
