@@ -465,19 +465,20 @@ void Engine::set_crs_impl(size_t ell, const uint8_t* points) {
   while ((size_t(1) << L_) < n) L_++;
   const Aff* pts = reinterpret_cast<const Aff*>(points);
   crs_host_.assign(pts, pts + ell + 7);
+  const CtabCols cc(n);   // (the CRS table columns up to G_u are the indices of the input points)
   std::vector<Aff> crs(n + 1), gb(n);
   for (size_t i = 0; i < n; i++) crs[i] = pts[i];   // G | Hvec
-  crs[n] = pts[n];                                  // H
-  for (size_t i = 0; i < ell + 2; i++) gb[i] = pts[i];
-  gb[ell + 2] = pts[n + 1];   // G_t
-  gb[ell + 3] = pts[n + 2];   // G_u
+  crs[n] = pts[cc.H()];                             // H
+  std::vector<uint32_t> gb_cols(n);
+  cc.same_msm_basis(gb_cols.data());
+  for (size_t i = 0; i < n; i++) gb[i] = pts[gb_cols[i]];
   d_crs_.ensure(n + 1);
   d_crs_gb_.ensure(n);
   CPX_HIP(hipMemcpy(d_crs_.p, crs.data(), (n + 1) * sizeof(Aff), hipMemcpyHostToDevice));
   CPX_HIP(hipMemcpy(d_crs_gb_.p, gb.data(), n * sizeof(Aff), hipMemcpyHostToDevice));
-  crs_single_[0] = pts[n];
-  crs_single_[1] = pts[n + 1];
-  crs_single_[2] = pts[n + 2];
+  crs_single_[0] = pts[cc.H()];
+  crs_single_[1] = pts[cc.G_t()];
+  crs_single_[2] = pts[cc.G_u()];
   // G_sum, H_sum (crs.rs:46-47) as unit-scalar MSMs on the device
   B_ = 0;
   consts_rows_ = 0;
@@ -539,9 +540,9 @@ void Engine::set_crs_impl(size_t ell, const uint8_t* points) {
       tab->key = std::move(key);
       tab->ctab.ensure((size_t)copies_ * NC);
       std::vector<Aff> row(NC);
-      for (size_t i = 0; i < n + 3; i++) row[i] = pts[i];   // G | Hvec | H | G_t | G_u
-      row[n + 3] = crs_single_[3];                          // G_sum, H_sum (crs.rs:46-47): B, D are built from them
-      row[n + 4] = crs_single_[4];
+      for (int i = 0; i <= cc.G_u(); i++) row[i] = pts[i];   // G | Hvec | H | G_t | G_u
+      row[cc.G_sum()] = crs_single_[3];                      // G_sum, H_sum (crs.rs:46-47): B, D are built from them
+      row[cc.H_sum()] = crs_single_[4];
       DevBuf<Aff> d_row;
       d_row.ensure(NC);
       CPX_HIP(hipMemcpy(d_row.p, row.data(), NC * sizeof(Aff), hipMemcpyHostToDevice));
@@ -991,23 +992,19 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   TeamScope team(this, B);   // 2 ... device_min_batch - 1 (55) proofs: the host loops between the phases on spinning helper threads
   StreamSwap lat_main(stream_, B <= 8 ? side_.lat_main : nullptr, side_.lat_ev);   // a few proofs: the phases on the lower half of the CUs
   const SlotMap sm(L);
-  const size_t nrand = 3 * n + 9;
+  const RandIdx ri((int)n);
+  const PtabRow row(n);
+  const CtabCols cc(n);
+  const size_t nrand = ri.count();
   const int NS = sm.count();
   const size_t NP = np();
   std::vector<ProverState> st(B);
   std::vector<uint8_t> comp;
-  const size_t I_AB = 0, I_CB = 2, I_IR = 6, I_IZ = 6 + n, I_RT = 2 * n + 4, I_RU = 2 * n + 5, I_RA = 2 * n + 6, I_RB = 2 * n + 7,
-               I_RK = 2 * n + 8, I_VR = 2 * n + 9;
-  // table offsets inside a per-proof row
-  const size_t O_M = 0, O_T = 1, O_U = 1 + n;
-  // CRS table indices: G | Hvec at 0..n-1, H at n, G_t at n+1, G_u at n+2
-  const uint32_t* iH = idx_list({(uint32_t)n});
-  const uint32_t* iGt = idx_list({(uint32_t)(n + 1)});
-  const uint32_t* iGu = idx_list({(uint32_t)(n + 2)});
-  std::vector<uint32_t> gb(n);   // SameMSM basis G | Hvec[0..2) | G_t | G_u as CRS-table indices
-  for (size_t i = 0; i < ell + 2; i++) gb[i] = (uint32_t)i;
-  gb[ell + 2] = (uint32_t)(n + 1);
-  gb[ell + 3] = (uint32_t)(n + 2);
+  const uint32_t* iH = idx_list({(uint32_t)cc.H()});
+  const uint32_t* iGt = idx_list({(uint32_t)cc.G_t()});
+  const uint32_t* iGu = idx_list({(uint32_t)cc.G_u()});
+  std::vector<uint32_t> gb(n);
+  cc.same_msm_basis(gb.data());
   const uint32_t* iGb = idx_list(gb);
   const TblSeg none{nullptr, nullptr, 0, 0};
 
@@ -1025,7 +1022,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     d_dst_.ensure(B);
     d_mcomp_.ensure(B * 48);
     uint32_t* dst = h_u32_.p;
-    for (size_t p = 0; p < B; p++) dst[p] = (uint32_t)(p * NP + O_M);
+    for (size_t p = 0; p < B; p++) dst[p] = (uint32_t)(p * NP + row.M());
     CPX_HIP(hipMemcpyAsync(d_dst_.p, dst, B * 4, hipMemcpyHostToDevice, stream_));
     launch_finalize(d_Mjac_.p, (int)B, d_psrc_.p, d_dst_.p, d_mcomp_.p, stream_);
     transcript_prefix_async(B);   // side stream: copies of the compressed bytes for the host's transcripts
@@ -1043,7 +1040,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     const size_t tmp_m = B * (size_t)(copies_ / 2 - 1);   // scratch entries of the M launch; the T | U launch takes the rest
     launch_table_build(opt_, d_psrc_.p, NP, d_ptab_.p, (int)B, (size_t)copies_ * NP, 1, (int)NP, copies_, true, d_tbltmp_.p, tab_.stream);
     CPX_HIP(hipEventRecord(tab_.ev_m, tab_.stream));
-    launch_table_build(opt_, d_psrc_.p + 1, NP, d_ptab_.p + 1, (int)B, (size_t)copies_ * NP, (int)(2 * n), (int)NP, copies_, true, d_tbltmp_.p + tmp_m, tab_.stream);
+    launch_table_build(opt_, d_psrc_.p + row.T(), NP, d_ptab_.p + row.T(), (int)B, (size_t)copies_ * NP, (int)(2 * n), (int)NP, copies_, true, d_tbltmp_.p + tmp_m, tab_.stream);
     const uint8_t* mcomp = h_mcomp_.p;
     wait_side();
     parallel_for(B, [&](size_t p) {
@@ -1060,21 +1057,21 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       const uint32_t* perm = permutation + p * ell;
       s.a_perm.resize(ell);
       for (size_t i = 0; i < ell; i++) s.a_perm[i] = s.vec_a[perm[i]];
-      const S kk = S_from_wire(k_in + 32 * p), r_k = s.draw(I_RK);
+      const S kk = S_from_wire(k_in + 32 * p), r_k = s.draw(ri.RK());
       // scalar vectors of phase 1
       s.scal[0] = s.a_perm;                                   // A (and the head of A') over G | Hvec
-      s.scal[0].push_back(s.draw(I_AB));
-      s.scal[0].push_back(s.draw(I_AB + 1));
+      s.scal[0].push_back(s.draw(ri.AB()));
+      s.scal[0].push_back(s.draw(ri.AB() + 1));
       s.scal[0].push_back(S::zero());
       s.scal[0].push_back(S::zero());
-      s.scal[0].push_back(s.draw(I_RT));                      // ... then r_t on G_t, r_u on G_u for A' (curdleproofs.rs:134)
-      s.scal[0].push_back(s.draw(I_RU));
+      s.scal[0].push_back(s.draw(ri.RT()));                   // ... then r_t on G_t, r_u on G_u for A' (curdleproofs.rs:134)
+      s.scal[0].push_back(s.draw(ri.RU()));
       s.scal[1].resize(n);                                    // vec_r of SameMSM: B_a, B_t, B_u
-      for (size_t i = 0; i < n; i++) s.scal[1][i] = s.draw(I_VR + i);
-      s.scal[2] = {s.draw(I_RT), s.draw(I_RU), s.draw(I_RA), s.draw(I_RB)};
+      for (size_t i = 0; i < n; i++) s.scal[1][i] = s.draw(ri.VR() + i);
+      s.scal[2] = {s.draw(ri.RT()), s.draw(ri.RU()), s.draw(ri.RA()), s.draw(ri.RB())};
       s.scal[3] = {kk, r_k};                                   // scalars of the four T_2 scalar multiplications
       s.scal[4].resize(n);                                     // r_c of the IPA (inner_product_argument.rs:46): B_c = msm(G | Hvec, r_c)
-      for (size_t i = 0; i < n; i++) s.scal[4][i] = s.draw(I_IR + i);
+      for (size_t i = 0; i < n; i++) s.scal[4][i] = s.draw(ri.IR() + i);
     });
   }
   auto take = [&](size_t p, int slot_id, size_t req_index) { memcpy(&st[p].comp[(size_t)slot_id * 48], &comp[req_index * 48], 48); };
@@ -1157,7 +1154,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       for (size_t i = 0; i < n; i++) hs[p * n + i] = st[p].scal[1][i].f;
       for (int q = 0; q < 2; q++) {
         TblTask t;
-        t.seg[0] = pseg(p, q ? O_U : O_T, (uint32_t)n);
+        t.seg[0] = pseg(p, q ? row.U() : row.T(), (uint32_t)n);
         t.seg[1] = none;
         t.scalars = d_scal + p * n;
         t.flags = 0;
@@ -1227,7 +1224,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       s.c.assign(1, S::one());
       for (size_t i = 0; i + 1 < ell; i++) s.c.push_back(s.c[i] * s.factors[i]);
       s.vec_c_blinders.resize(N_BLINDERS);
-      for (size_t i = 0; i < N_BLINDERS; i++) s.vec_c_blinders[i] = s.draw(I_CB + i);
+      for (size_t i = 0; i < N_BLINDERS; i++) s.vec_c_blinders[i] = s.draw(ri.CB() + i);
       s.c.insert(s.c.end(), s.vec_c_blinders.begin(), s.vec_c_blinders.end());
     });
   }
@@ -1248,7 +1245,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   {
     std::vector<TblReq> reqs;
     for (size_t p = 0; p < B; p++) {
-      TblReq rb{cseg(n + 3, 1), st[p].scal[5].data(), pseg(p, O_M, 1), st[p].scal[6].data(), slot_index(p, SL_B)};
+      TblReq rb{cseg(cc.G_sum(), 1), st[p].scal[5].data(), pseg(p, row.M(), 1), st[p].scal[6].data(), slot_index(p, SL_B)};
       rb.add[0] = slot_index(p, SL_A);
       TblReq ra{none, nullptr, none, nullptr};
       ra.add[0] = slot_index(p, SL_A);
@@ -1270,7 +1267,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       s.alpha_g = s.tr.get_and_append_challenge("gprod_alpha");
       const S mb[4] = {S_from_wire(m_blinders + (p * 4 + 0) * 32), S_from_wire(m_blinders + (p * 4 + 1) * 32),
                        S_from_wire(m_blinders + (p * 4 + 2) * 32), S_from_wire(m_blinders + (p * 4 + 3) * 32)};
-      const S ab[4] = {s.draw(I_AB), s.draw(I_AB + 1), S::zero(), S::zero()};
+      const S ab[4] = {s.draw(ri.AB()), s.draw(ri.AB() + 1), S::zero(), S::zero()};
       s.rb_plus_alpha.resize(N_BLINDERS);
       for (size_t i = 0; i < N_BLINDERS; i++) s.rb_plus_alpha[i] = (ab[i] + s.alpha_sp * mb[i]) + s.alpha_g;
       s.r_p = host::inner_product(s.rb_plus_alpha.data(), s.vec_c_blinders.data(), N_BLINDERS);
@@ -1299,8 +1296,8 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       s.scal[0] = {-s.beta_g_inv, s.alpha_g};
       // generate_ipa_blinders (inner_product_argument.rs:42-82)
       SVec r(n), zz(n);
-      for (size_t i = 0; i < n; i++) r[i] = s.draw(I_IR + i);
-      for (size_t i = 0; i + 2 < n; i++) zz[i] = s.draw(I_IZ + i);
+      for (size_t i = 0; i < n; i++) r[i] = s.draw(ri.IR() + i);
+      for (size_t i = 0; i + 2 < n; i++) zz[i] = s.draw(ri.IZ() + i);
       const S omega = host::inner_product(r.data(), s.d.data(), n) + host::inner_product(zz.data(), s.c.data(), n - 2);
       const S delta = host::inner_product(r.data(), zz.data(), n - 2);
       const S inv_c = s.c[n - 2].inverse();
@@ -1327,7 +1324,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     std::vector<TblReq> reqs;
     for (size_t p = 0; p < B; p++) {
       ProverState& s = st[p];
-      TblReq rd{cseg(n + 3, 2), s.scal[0].data(), none, nullptr};   // G_sum, H_sum are columns n+3, n+4 of the CRS tables
+      TblReq rd{cseg(cc.G_sum(), 2), s.scal[0].data(), none, nullptr};   // G_sum, H_sum: adjacent columns of the CRS tables
       rd.add[0] = slot_index(p, SL_B);
       reqs.push_back(rd);
       reqs.push_back({cseg(0, (uint32_t)n), s.scal[3].data(), none, nullptr});
@@ -1434,9 +1431,9 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       for (int q : pts) s.tr.append_point_bytes("sameexp_points", &s.comp[(size_t)q * 48]);
       const S alpha = s.tr.get_and_append_challenge("same_scalar_alpha");
       const S kk = S_from_wire(k_in + 32 * p);
-      s.z_k = s.draw(I_RK) + kk * alpha;
-      s.z_t = s.draw(I_RA) + s.draw(I_RT) * alpha;
-      s.z_u = s.draw(I_RB) + s.draw(I_RU) * alpha;
+      s.z_k = s.draw(ri.RK()) + kk * alpha;
+      s.z_t = s.draw(ri.RA()) + s.draw(ri.RT()) * alpha;
+      s.z_u = s.draw(ri.RB()) + s.draw(ri.RU()) * alpha;
       s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.APRIME() * 48]);
       s.tr.append_point_bytes("same_msm_step1", &s.comp[SL_CMT2 * 48]);
       s.tr.append_point_bytes("same_msm_step1", &s.comp[SL_CMU2 * 48]);
@@ -1455,11 +1452,11 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.BU() * 48]);
       s.alpha_m = s.tr.get_and_append_challenge("same_msm_alpha");
       s.x.resize(n);
-      for (size_t i = 0; i < ell; i++) s.x[i] = s.draw(I_VR + i) + s.alpha_m * s.a_perm[i];
-      s.x[ell] = s.draw(I_VR + ell) + s.alpha_m * s.draw(I_AB);
-      s.x[ell + 1] = s.draw(I_VR + ell + 1) + s.alpha_m * s.draw(I_AB + 1);
-      s.x[ell + 2] = s.draw(I_VR + ell + 2) + s.alpha_m * s.draw(I_RT);
-      s.x[ell + 3] = s.draw(I_VR + ell + 3) + s.alpha_m * s.draw(I_RU);
+      for (size_t i = 0; i < ell; i++) s.x[i] = s.draw(ri.VR() + i) + s.alpha_m * s.a_perm[i];
+      s.x[ell] = s.draw(ri.VR() + ell) + s.alpha_m * s.draw(ri.AB());
+      s.x[ell + 1] = s.draw(ri.VR() + ell + 1) + s.alpha_m * s.draw(ri.AB() + 1);
+      s.x[ell + 2] = s.draw(ri.VR() + ell + 2) + s.alpha_m * s.draw(ri.RT());
+      s.x[ell + 3] = s.draw(ri.VR() + ell + 3) + s.alpha_m * s.draw(ri.RU());
       s.SM.assign(n, S::one());
       Fr* v = h_rvec_.p + p * 2 * n;   // device-resident round vectors: x | SM
       for (size_t i = 0; i < n; i++) {
@@ -1489,11 +1486,11 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       const Fr* oL = d_rout_.p + p * 2 * hn;   // [L_* scalars (hn) | R_* scalars (hn)]
       const Fr* oR = oL + hn;
       TblReq r[6] = {{cseg(0, (uint32_t)hn, d_ghi), nullptr, none, nullptr},       // L_A
-                     {pseg(p, O_T, (uint32_t)hn, d_hi), nullptr, none, nullptr},   // L_T
-                     {pseg(p, O_U, (uint32_t)hn, d_hi), nullptr, none, nullptr},   // L_U
+                     {pseg(p, row.T(), (uint32_t)hn, d_hi), nullptr, none, nullptr},   // L_T
+                     {pseg(p, row.U(), (uint32_t)hn, d_hi), nullptr, none, nullptr},   // L_U
                      {cseg(0, (uint32_t)hn, d_glo), nullptr, none, nullptr},       // R_A
-                     {pseg(p, O_T, (uint32_t)hn, d_lo), nullptr, none, nullptr},   // R_T
-                     {pseg(p, O_U, (uint32_t)hn, d_lo), nullptr, none, nullptr}};  // R_U
+                     {pseg(p, row.T(), (uint32_t)hn, d_lo), nullptr, none, nullptr},   // R_T
+                     {pseg(p, row.U(), (uint32_t)hn, d_lo), nullptr, none, nullptr}};  // R_U
       for (int q = 0; q < 6; q++) {
         r[q].dev = q < 3 ? oL : oR;
         reqs.push_back(r[q]);
@@ -1538,43 +1535,24 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     trace_scalar("d_final", s.d_final.f);
   }
   // -- serialise
-  const size_t psz = proof_size();
+  const ProofLayout pl(L);
+  const size_t psz = pl.size();
   parallel_for(B, [&](size_t p) {
-    ProverState& s = st[p];
+    const ProverState& s = st[p];
     uint8_t* o = proofs_out + p * psz;
-    auto pt = [&](int slot_id) {
-      memcpy(o, &s.comp[(size_t)slot_id * 48], 48);
-      o += 48;
-    };
-    auto sc = [&](const S& x) {
-      x.to_le_bytes(o);
-      o += 32;
-    };
-    for (int q = SL_A; q <= SL_C; q++) pt(q);
-    sc(s.r_p);
-    pt(SL_BC);
-    pt(SL_BD);
-    for (int q = SL_IPA0; q < SL_IPA0 + 4 * (int)L; q++) pt(q);
-    sc(s.c_final);
-    sc(s.d_final);
-    for (int q = sm.CMA1(); q <= sm.CMB2(); q++) pt(q);
-    sc(s.z_k);
-    sc(s.z_t);
-    sc(s.z_u);
-    for (int q = sm.BA(); q < sm.BA() + 3 + 6 * (int)L; q++) pt(q);
-    {
-      S xf;   // x[0] after the last fold (device-resident vector)
-      memcpy(xf.f.v, &h_rfin_.p[3 * p + 2], sizeof(Fr));
-      sc(xf);
-    }
+    for (int q = 0; q < pl.n_points(); q++) memcpy(o + pl.point_offset(q), &s.comp[(size_t)(SL_A + q) * 48], 48);
+    S xf;   // x[0] after the last fold (device-resident vector)
+    memcpy(xf.f.v, &h_rfin_.p[3 * p + 2], sizeof(Fr));
+    const S* vals[ProofLayout::N_SCALARS] = {&s.r_p, &s.c_final, &s.d_final, &s.z_k, &s.z_t, &s.z_u, &xf};
+    for (int i = 0; i < ProofLayout::N_SCALARS; i++) vals[i]->to_le_bytes(o + pl.scalar_offset(i));
   });
   flush_timers();
 }
 
 // ---------------------------------------------------------------- verifier
-void Engine::batch_verify(const uint8_t* proofs, const uint8_t* rand, int* verdict) { verify_core(proofs, rand, 8, verdict, nullptr, nullptr); }
+void Engine::batch_verify(const uint8_t* proofs, const uint8_t* rand, int* verdict) { verify_core(proofs, rand, VF_COUNT, verdict, nullptr, nullptr); }
 void Engine::batch_verify_fused(const uint8_t* proofs, const uint8_t* rand, uint8_t* partial_jac, int* n_invalid) {
-  verify_core(proofs, rand, 12, nullptr, partial_jac, n_invalid);
+  verify_core(proofs, rand, VF_FUSED_COUNT, nullptr, partial_jac, n_invalid);
 }
 
 // Shared body.  Per-proof mode (verdict != nullptr, 8 random factors per proof): curdleproofs.rs:197.  Fused mode
@@ -1587,15 +1565,16 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
   CPX_HIP(hipSetDevice(device_));
   const size_t B = B_, ell = ell_, n = n_, L = L_;
   const SlotMap sm(L);
-  const size_t psz = proof_size();
-  const int NPP = sm.n_proof_points();
+  const ProofLayout pl(L);
+  const size_t psz = pl.size();
+  const int NPP = pl.n_points();
   // msm_accumulator.rs:44 draws every factor with Fr::rand; the ABI takes them from the caller, so they are validated:
   // a zero (or non-reduced) factor would silently drop the check it weights
   for (size_t i = 0; i < B * rand_stride; i++)
     if (!host::is_valid_factor(rand + 32 * i)) throw ArgError("verifier random factors must be non-zero reduced field elements");
   {   // infinity encodings as ark-bls12-381 ^0.4 reads them (option strict_infinity = 0): canonical before anything hashes or decodes them
     std::vector<size_t> offs((size_t)NPP);
-    for (size_t q = 0; q < (size_t)NPP; q++) offs[q] = 48 * q + (q >= 9 ? 32 : 0) + (q >= 11 + 4 * L ? 64 : 0) + (q >= 15 + 4 * L ? 96 : 0);
+    for (int q = 0; q < NPP; q++) offs[q] = pl.point_offset(q);
     proofs = canonical_infinities(proofs, B * psz, B, psz, offs);
   }
   if (device_prefix(B)) {   // the whole verifier on the GPU (engine_device.cpp); a few proofs: host-driven Fiat-Shamir below
@@ -1616,35 +1595,6 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     SVec scal[8];
   };
   std::vector<VState> st(B);
-
-  // byte offset of each proof point (slot order == serialisation order, scalars interleaved)
-  std::vector<size_t> pt_off(NPP);
-  size_t off_rp, off_c, off_d, off_zk, off_x;
-  {
-    size_t o = 0;
-    int q = 0;
-    auto P = [&](int cnt) {
-      for (int i = 0; i < cnt; i++) {
-        pt_off[q++] = o;
-        o += 48;
-      }
-    };
-    P(9);            // A cmT1 cmT2 cmU1 cmU2 R S B C
-    off_rp = o;
-    o += 32;
-    P(2 + 4 * (int)L);
-    off_c = o;
-    o += 32;
-    off_d = o;
-    o += 32;
-    P(4);
-    off_zk = o;
-    o += 96;
-    P(3 + 6 * (int)L);
-    off_x = o;
-    o += 32;
-    if (o != psz || q != NPP) throw std::logic_error("proof layout");
-  }
 
   // -- V0: compressed instance vectors and M -> affine first (the transcript starts with their bytes: the side stream copies them
   //    to the host), then the proof points are decompressed into their slots — the host hashes (V1a) while that kernel runs
@@ -1673,7 +1623,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     transcript_prefix_async(B);   // side stream: copies of the compressed bytes for the host's transcripts
     parallel_for(B, [&](size_t p) {
       for (int q = 0; q < NPP; q++) {
-        memcpy(&pts[(p * NPP + q) * 48], proofs + p * psz + pt_off[q], 48);
+        memcpy(&pts[(p * NPP + q) * 48], proofs + p * psz + pl.point_offset(q), 48);
         dst[p * NPP + q] = slot_index(p, SL_A + q);
       }
     });
@@ -1697,11 +1647,10 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     VState& s = st[p];
     s.pb = proofs + p * psz;
     const uint8_t* pb = s.pb;
-    auto P = [&](int slot_id) { return pb + pt_off[slot_id - SL_A]; };
-    if (!S::from_le_bytes(pb + off_rp, &s.r_p) || !S::from_le_bytes(pb + off_c, &s.c_fin) || !S::from_le_bytes(pb + off_d, &s.d_fin) ||
-        !S::from_le_bytes(pb + off_zk, &s.z_k) || !S::from_le_bytes(pb + off_zk + 32, &s.z_t) || !S::from_le_bytes(pb + off_zk + 64, &s.z_u) ||
-        !S::from_le_bytes(pb + off_x, &s.x_fin))
-      s.bad = true;
+    auto P = [&](int slot_id) { return pb + pl.point_offset(slot_id - SL_A); };
+    S* vals[ProofLayout::N_SCALARS] = {&s.r_p, &s.c_fin, &s.d_fin, &s.z_k, &s.z_t, &s.z_u, &s.x_fin};
+    for (int i = 0; i < ProofLayout::N_SCALARS; i++)
+      if (!S::from_le_bytes(pb + pl.scalar_offset(i), vals[i])) s.bad = true;
     const uint8_t* ic = &inst_comp[p * 4 * ell * 48];
     // curdleproofs.rs:218: the randomiser must not have wiped the ciphertexts
     if (ic[2 * ell * 48] == ID0) s.reject = true;
@@ -1742,7 +1691,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     const TblSeg none{nullptr, nullptr, 0, 0};
     std::vector<TblReq> reqs;
     for (size_t p = 0; p < B; p++) {
-      TblReq rd{cseg(n + 3, 2), st[p].scal[0].data() + 1, none, nullptr, slot_index(p, sm.D())};
+      TblReq rd{cseg(CtabCols(n).G_sum(), 2), st[p].scal[0].data() + 1, none, nullptr, slot_index(p, sm.D())};
       rd.add[0] = slot_index(p, SL_B);
       TblReq ra{none, nullptr, none, nullptr, slot_index(p, sm.APRIME())};
       ra.add[0] = slot_index(p, SL_A);
@@ -1764,10 +1713,10 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
   parallel_for(B, [&](size_t p) {
     VState& s = st[p];
     const uint8_t* pb = s.pb;
-    auto P = [&](int slot_id) { return pb + pt_off[slot_id - SL_A]; };
-    const S a1 = S_from_wire(rand + (p * rand_stride + 0) * 32), a2 = S_from_wire(rand + (p * rand_stride + 1) * 32), a3 = S_from_wire(rand + (p * rand_stride + 2) * 32),
-            a4 = S_from_wire(rand + (p * rand_stride + 3) * 32), a5 = S_from_wire(rand + (p * rand_stride + 4) * 32), a6 = S_from_wire(rand + (p * rand_stride + 5) * 32),
-            a7 = S_from_wire(rand + (p * rand_stride + 6) * 32), a8 = S_from_wire(rand + (p * rand_stride + 7) * 32);
+    auto P = [&](int slot_id) { return pb + pl.point_offset(slot_id - SL_A); };
+    auto factor = [&](int i) { return S_from_wire(rand + (p * rand_stride + i) * 32); };
+    const S a1 = factor(VF_SAMEPERM), a2 = factor(VF_IPA_C), a3 = factor(VF_IPA_D), a4 = factor(VF_SMSM_A), a5 = factor(VF_SMSM_T), a6 = factor(VF_SMSM_U),
+            a7 = factor(VF_R), a8 = factor(VF_S);
     const S beta_l = s.beta_g.pow_u64(ell), beta_l1 = beta_l * s.beta_g;
     s.z_ip = s.r_p * beta_l1 + s.gprod * beta_l - S::one();
     // inner_product_argument.rs:283-290, 202-250
@@ -1914,10 +1863,10 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
       // the same argument that backs msm_accumulator.rs itself.
       S w1, w2, w3, w4;
       if (fused_partial) {
-        w1 = S_from_wire(rand + (p * rand_stride + 8) * 32);
-        w2 = S_from_wire(rand + (p * rand_stride + 9) * 32);
-        w3 = S_from_wire(rand + (p * rand_stride + 10) * 32);
-        w4 = S_from_wire(rand + (p * rand_stride + 11) * 32);
+        w1 = factor(VF_SS_A1);
+        w2 = factor(VF_SS_A2);
+        w3 = factor(VF_SS_B1);
+        w4 = factor(VF_SS_B2);
       } else {
         w1 = a1 * a2;
         w2 = a3 * a4;

@@ -136,7 +136,7 @@ class Engine {
   size_t ell() const { return ell_; }
   size_t n() const { return n_; }
   size_t log2n() const { return L_; }
-  size_t proof_size() const { return 48 * (18 + 10 * L_) + 32 * 7; }
+  size_t proof_size() const { return ProofLayout(L_).size(); }
   void crs_sums(uint8_t* g_sum, uint8_t* h_sum) const;
 
   // ---- tier 0: the reference's util::msm & friends on caller buffers ----
@@ -400,11 +400,11 @@ class Engine {
   bool device_prefix(size_t B) const;         // run the whole protocol on the GPU (batches >= CPX_DEVICE_MIN_BATCH) or drive it from the host
 
   // per-proof table row: copy-major [copies][NP]
-  size_t np() const { return 1 + 2 * n_; }   // M | T_b | U_b   (R and S are used once: no table)
+  size_t np() const { return PtabRow(n_).count(); }   // M | T_b | U_b
   TAff* ptab(size_t p) const { return d_ptab_.p + p * (size_t)copies_ * np(); }
   TblSeg pseg(size_t p, size_t off, uint32_t cnt, const uint32_t* idx = nullptr) const { return TblSeg{ptab(p) + off, idx, (uint32_t)np(), cnt}; }
   TblSeg cseg(size_t off, uint32_t cnt, const uint32_t* idx = nullptr) const { return TblSeg{ctab() + off, idx, (uint32_t)nc(), cnt}; }
-  size_t nc() const { return n_ + 5; }   // CRS table columns: G | Hvec | H | G_t | G_u | G_sum | H_sum
+  size_t nc() const { return CtabCols(n_).count(); }   // CRS table columns: G | Hvec | H | G_t | G_u | G_sum | H_sum
   Aff* pp(size_t p) const { return d_pp_.p + p * pp_stride_; }
   Aff* slot(size_t p, int s) const { return pp(p) + 4 * ell_ + s; }
   uint32_t slot_index(size_t p, int s) const { return (uint32_t)(p * pp_stride_ + 4 * ell_ + s); }

@@ -167,6 +167,8 @@ void Engine::prepare_device_prover() {
   const size_t B = B_, ell = ell_, n = n_, L = L_;
   const SlotMap sm(L);
   const RandIdx ri((int)n);
+  const PtabRow row(n);
+  const CtabCols cc(n);
   const size_t NS = sm.count(), NP = np(), nrand = ri.count();
   DevProver& dp = dprove_;
   // buffers (sizes only grow; a reallocation changes a pointer and invalidates the plans)
@@ -234,14 +236,11 @@ void Engine::prepare_device_prover() {
   auto vec = [&](size_t p, int v) { return dp.vec.p + (p * V_COUNT + v) * n; };
   auto sc = [&](size_t p, int i) { return dp.sc.p + p * SC_COUNT + i; };
   auto cidx = [&](size_t p, int slot) { return (uint32_t)(p * NS + slot); };
-  const size_t O_M = 0, O_T = 1, O_U = 1 + n;
-  const uint32_t* iH = idx_list({(uint32_t)n});
-  const uint32_t* iGt = idx_list({(uint32_t)(n + 1)});
-  const uint32_t* iGu = idx_list({(uint32_t)(n + 2)});
-  std::vector<uint32_t> gb(n);   // SameMSM basis G | Hvec[0..2) | G_t | G_u as CRS-table indices
-  for (size_t i = 0; i < ell + 2; i++) gb[i] = (uint32_t)i;
-  gb[ell + 2] = (uint32_t)(n + 1);
-  gb[ell + 3] = (uint32_t)(n + 2);
+  const uint32_t* iH = idx_list({(uint32_t)cc.H()});
+  const uint32_t* iGt = idx_list({(uint32_t)cc.G_t()});
+  const uint32_t* iGu = idx_list({(uint32_t)cc.G_u()});
+  std::vector<uint32_t> gb(n);
+  cc.same_msm_basis(gb.data());
   const uint32_t* iGb = idx_list(gb);
   const TblSeg none{nullptr, nullptr, 0, 0};
   auto req = [&](TblSeg s0, TblSeg s1, const Fr* dev, uint32_t dst = ~0u) {
@@ -255,7 +254,7 @@ void Engine::prepare_device_prover() {
   // mdst: where the affine M of proof p goes (table source slot 0)
   {
     std::vector<uint32_t> md(B);
-    for (size_t p = 0; p < B; p++) md[p] = (uint32_t)(p * NP + O_M);
+    for (size_t p = 0; p < B; p++) md[p] = (uint32_t)(p * NP + row.M());
     CPX_HIP(hipMemcpy(dp.mdst.p, md.data(), B * 4, hipMemcpyHostToDevice));
   }
   // (decided before the plans are laid out: the phases of a small batch differ, too)
@@ -325,9 +324,9 @@ void Engine::prepare_device_prover() {
   reqs.clear();
   ci.clear();
   for (size_t p = 0; p < B; p++) {
-    reqs.push_back(req(pseg(p, O_T, (uint32_t)n), none, rnd(p, ri.VR())));
+    reqs.push_back(req(pseg(p, row.T(), (uint32_t)n), none, rnd(p, ri.VR())));
     ci.push_back(cidx(p, sm.BT()));
-    reqs.push_back(req(pseg(p, O_U, (uint32_t)n), none, rnd(p, ri.VR())));
+    reqs.push_back(req(pseg(p, row.U(), (uint32_t)n), none, rnd(p, ri.VR())));
     ci.push_back(cidx(p, sm.BU()));
   }
   dp.p1t.table_stream = true;
@@ -356,7 +355,7 @@ void Engine::prepare_device_prover() {
     // grand-product factors k_ps_sameperm leaves in V_FACT) — a 256-point task of the fixed-base kernel like C beside it, instead of a
     // one-point task of the bucket-list kernel whose 32 bucket sets per proof cost the phase 0.5 ms of reductions at 128 proofs
     TblReq rb = dp.fused_smsm ? req(cseg(0, (uint32_t)n), none, vec(p, V_FACT), slot_index(p, SL_B))
-                         : req(cseg(n + 3, 1), pseg(p, O_M, 1), sc(p, SC_BETA_SP), slot_index(p, SL_B));
+                         : req(cseg(cc.G_sum(), 1), pseg(p, row.M(), 1), sc(p, SC_BETA_SP), slot_index(p, SL_B));
     if (!dp.fused_smsm) rb.add[0] = slot_index(p, SL_A);
     reqs.push_back(rb);
     ci.push_back(cidx(p, SL_B));
@@ -374,7 +373,7 @@ void Engine::prepare_device_prover() {
   reqs.clear();
   ci.clear();
   for (size_t p = 0; p < B; p++) {
-    TblReq rd = req(cseg(n + 3, 2), none, sc(p, SC_NEG_BETA_G_INV));
+    TblReq rd = req(cseg(cc.G_sum(), 2), none, sc(p, SC_NEG_BETA_G_INV));
     rd.add[0] = slot_index(p, SL_B);
     reqs.push_back(rd);
     ci.push_back(cidx(p, sm.D()));
@@ -403,8 +402,8 @@ void Engine::prepare_device_prover() {
     const uint32_t *d_hiH = nullptr, *d_loH = nullptr;
     if (dp.fused) {
       std::vector<uint32_t> hiH(hi), loH(lo);
-      hiH.push_back((uint32_t)n);
-      loH.push_back((uint32_t)n);
+      hiH.push_back((uint32_t)cc.H());
+      loH.push_back((uint32_t)cc.H());
       d_hiH = idx_list(hiH);
       d_loH = idx_list(loH);
     }
@@ -436,15 +435,15 @@ void Engine::prepare_device_prover() {
       const Fr* oR = oL + hn;
       reqs.push_back(req(cseg(0, (uint32_t)hn, d_ghi), none, oL));
       ci.push_back(cidx(p, sm.LA((int)j)));
-      reqs.push_back(req(pseg(p, O_T, (uint32_t)hn, d_hi), none, oL));
+      reqs.push_back(req(pseg(p, row.T(), (uint32_t)hn, d_hi), none, oL));
       ci.push_back(cidx(p, sm.LT((int)j)));
-      reqs.push_back(req(pseg(p, O_U, (uint32_t)hn, d_hi), none, oL));
+      reqs.push_back(req(pseg(p, row.U(), (uint32_t)hn, d_hi), none, oL));
       ci.push_back(cidx(p, sm.LU((int)j)));
       reqs.push_back(req(cseg(0, (uint32_t)hn, d_glo), none, oR));
       ci.push_back(cidx(p, sm.RA((int)j)));
-      reqs.push_back(req(pseg(p, O_T, (uint32_t)hn, d_lo), none, oR));
+      reqs.push_back(req(pseg(p, row.T(), (uint32_t)hn, d_lo), none, oR));
       ci.push_back(cidx(p, sm.RT((int)j)));
-      reqs.push_back(req(pseg(p, O_U, (uint32_t)hn, d_lo), none, oR));
+      reqs.push_back(req(pseg(p, row.U(), (uint32_t)hn, d_lo), none, oR));
       ci.push_back(cidx(p, sm.RU((int)j)));
     }
     dp.smsm.emplace_back(new TblPlan());
@@ -830,14 +829,15 @@ void Engine::batch_prove_device(const uint32_t* permutation, const uint8_t* k_in
 void Engine::prepare_device_verifier(size_t rand_stride) {
   const size_t B = B_, ell = ell_, n = n_, L = L_;
   const SlotMap sm(L);
-  const size_t NS = sm.count(), NPP = sm.n_proof_points(), NM = 6 + NPP, NI = 4 * ell, NPT = NI + NM, psz = proof_size();
+  const ProofLayout pl(L);
+  const size_t NS = sm.count(), NPP = pl.n_points(), NM = 6 + NPP, NI = 4 * ell, NPT = NI + NM, psz = pl.size();
   DevVerifier& dv = dverify_;
   d_bytes_.ensure(B * 4 * ell * 48);
   d_mcomp_.ensure(B * 48);
   d_tstate_.ensure(B * 27);
   d_veca_.ensure(B * ell);
   dv.proofs.ensure(B * psz);
-  dv.rnd.ensure(B * 12);
+  dv.rnd.ensure(B * VF_FUSED_COUNT);
   dv.vsc.ensure(B * (size_t)VSC_COUNT);
   dv.slotcomp.ensure(B * NS * 48);
   dv.status.ensure(B * NPP);
@@ -883,13 +883,10 @@ void Engine::prepare_device_verifier(size_t rand_stride) {
   d.flags = dv.flags.p;
   memcpy(d.crs_h_comp, crs_H_comp_, 48);
 
-  // where the proof points sit inside a serialized proof (slot order == serialisation order, the seven scalars interleaved)
-  std::vector<uint32_t> pt_off(NPP);
-  for (size_t q = 0; q < NPP; q++) pt_off[q] = (uint32_t)(48 * q + (q >= 9 ? 32 : 0) + (q >= 11 + 4 * L ? 64 : 0) + (q >= 15 + 4 * L ? 96 : 0));
   std::vector<uint32_t> so(B * NPP), ds(B * NPP), md(B);
   for (size_t p = 0; p < B; p++) {
     for (size_t q = 0; q < NPP; q++) {
-      so[p * NPP + q] = (uint32_t)(p * psz + pt_off[q]);
+      so[p * NPP + q] = (uint32_t)(p * psz + pl.point_offset((int)q));   // where the proof points sit inside the serialized proofs
       ds[p * NPP + q] = slot_index(p, SL_A + (int)q);
     }
     md[p] = slot_index(p, SL_M);
@@ -904,7 +901,7 @@ void Engine::prepare_device_verifier(size_t rand_stride) {
     std::vector<TblReq> reqs;
     std::vector<uint32_t> ci;
     for (size_t p = 0; p < B; p++) {
-      TblReq rd{cseg(n + 3, 2), nullptr, none, nullptr, slot_index(p, sm.D())};
+      TblReq rd{cseg(CtabCols(n).G_sum(), 2), nullptr, none, nullptr, slot_index(p, sm.D())};
       rd.dev = dv.vsc.p + p * VSC_COUNT + VSC_NEG_BETA_G_INV;
       rd.add[0] = slot_index(p, SL_B);
       TblReq ra{none, nullptr, none, nullptr, slot_index(p, sm.APRIME())};
@@ -961,8 +958,8 @@ void Engine::prepare_device_verifier(size_t rand_stride) {
 void Engine::verify_core_device(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid) {
   CPX_HIP(hipSetDevice(device_));
   const size_t B = B_, ell = ell_, n = n_, L = L_;
-  const SlotMap sm(L);
-  const size_t NPP = sm.n_proof_points(), NM = 6 + NPP, NPT = 4 * ell + NM, psz = proof_size();
+  const ProofLayout pl(L);
+  const size_t NPP = pl.n_points(), NM = 6 + NPP, NPT = 4 * ell + NM, psz = pl.size();
   prepare_device_verifier(rand_stride);
   DevVerifier& dv = dverify_;
   const VerifyDev& d = dv.dev;

@@ -9,56 +9,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mont32.hpp"
+#include "layout.hpp"
 
 namespace cpx {
-
-// ---- per-proof point registry ("slots") that follows the 4*ell instance points in d_pp_ ----
-// CRS singles, M, then every proof point in serialisation order (curdleproofs.rs:300-310), then scratch.
-enum { SL_H = 0, SL_GT, SL_GU, SL_GSUM, SL_HSUM, SL_M, SL_A, SL_CMT1, SL_CMT2, SL_CMU1, SL_CMU2, SL_R, SL_S, SL_B, SL_C, SL_BC, SL_BD, SL_IPA0 };
-struct SlotMap {
-  int L;
-  CPX_HD explicit SlotMap(size_t l) : L((int)l) {}
-  CPX_HD int LC(int j) const { return SL_IPA0 + j; }
-  CPX_HD int RC(int j) const { return SL_IPA0 + L + j; }
-  CPX_HD int LD(int j) const { return SL_IPA0 + 2 * L + j; }
-  CPX_HD int RD(int j) const { return SL_IPA0 + 3 * L + j; }
-  CPX_HD int CMA1() const { return SL_IPA0 + 4 * L; }
-  CPX_HD int CMA2() const { return CMA1() + 1; }
-  CPX_HD int CMB1() const { return CMA1() + 2; }
-  CPX_HD int CMB2() const { return CMA1() + 3; }
-  CPX_HD int BA() const { return CMA1() + 4; }
-  CPX_HD int BT() const { return CMA1() + 5; }
-  CPX_HD int BU() const { return CMA1() + 6; }
-  CPX_HD int LA(int j) const { return CMA1() + 7 + j; }
-  CPX_HD int LT(int j) const { return CMA1() + 7 + L + j; }
-  CPX_HD int LU(int j) const { return CMA1() + 7 + 2 * L + j; }
-  CPX_HD int RA(int j) const { return CMA1() + 7 + 3 * L + j; }
-  CPX_HD int RT(int j) const { return CMA1() + 7 + 4 * L + j; }
-  CPX_HD int RU(int j) const { return CMA1() + 7 + 5 * L + j; }
-  CPX_HD int D() const { return CMA1() + 7 + 6 * L; }
-  CPX_HD int APRIME() const { return D() + 1; }
-  CPX_HD int TMP(int i) const { return D() + 2 + i; }   // 8 scratch results
-  CPX_HD int count() const { return D() + 2 + 8; }
-  CPX_HD int first_proof_point() const { return SL_A; }
-  CPX_HD int n_proof_points() const { return 18 + 10 * L; }   // SL_A .. RU(L-1), contiguous
-};
-
-// ---- the prover's 3n+9 random draws (SURVEY 8b RNG contract), as indices into a proof's `rand` row ----
-struct RandIdx {
-  int n;
-  CPX_HD explicit RandIdx(int n_) : n(n_) {}
-  CPX_HD int AB() const { return 0; }              // vec_a_blinders[2]     curdleproofs.rs:86
-  CPX_HD int CB() const { return 2; }              // vec_c_blinders[4]     grand_product_argument.rs:75
-  CPX_HD int IR() const { return 6; }              // IPA r[n]              inner_product_argument.rs:46
-  CPX_HD int IZ() const { return 6 + n; }          // IPA z[n-2]            inner_product_argument.rs:47
-  CPX_HD int RT() const { return 2 * n + 4; }      // r_t, r_u              curdleproofs.rs:110-111
-  CPX_HD int RU() const { return 2 * n + 5; }
-  CPX_HD int RA() const { return 2 * n + 6; }      // r_a, r_b, r_k         same_scalar_argument.rs:56-58
-  CPX_HD int RB() const { return 2 * n + 7; }
-  CPX_HD int RK() const { return 2 * n + 8; }
-  CPX_HD int VR() const { return 2 * n + 9; }      // SameMSM vec_r[n]      same_multiscalar_argument.rs:78
-  CPX_HD int count() const { return 3 * n + 9; }
-};
 
 // ---- per-proof device state of the device-resident prover ----
 // small scalars (Montgomery form), sc[p][SC_COUNT]; neighbours that one MSM request reads as a scalar vector are adjacent
@@ -110,7 +63,7 @@ struct VerifyDev {
   uint8_t* slotcomp;              // [B][NS][48]: D and A' (computed on the device) land here
   const uint8_t* inst_comp;       // [B][4 ell][48]
   const uint8_t* mcomp;           // [B][48]
-  const uint8_t* status;          // [B][n_proof_points]  decompression status of the proof points
+  const uint8_t* status;          // [B][n_points]  decompression status of the proof points
   Fr* scal;                       // [B][4 ell + NM]: instance part | misc part of the accumulated check
   Fr* scal_crs;                   // [B][n]: its CRS part (G | Hvec)
   uint32_t* flags;                // [B]: bit 0 = undecodable (bad scalar / point encoding), bit 1 = structural rejection

@@ -383,27 +383,24 @@ __global__ __launch_bounds__(64) void k_ps_smsm_round(const ProveDev d, int j) {
 __global__ __launch_bounds__(64) void k_ps_serialize(const ProveDev d) {
   const ProofView v(d, blockIdx.x);
   const int lane = threadIdx.x, L = d.L, n = d.n;
-  const SlotMap sm(L);
+  const ProofLayout pl(L);
   uint8_t* o = d.proofs + (size_t)v.p * d.psz;
-  const int npp = sm.n_proof_points();
-  const int b1 = 9, b2 = 11 + 4 * L, b3 = 15 + 4 * L;   // proof points before r_p / before c, d / before z_k, z_t, z_u
+  const int npp = pl.n_points();
   for (int i = lane; i < npp * 12; i += 64) {           // 48 bytes = 12 words per point
     const int q = i / 12, wd = i % 12;
-    const size_t off = 48 * (size_t)q + (q >= b1 ? 32 : 0) + (q >= b2 ? 64 : 0) + (q >= b3 ? 96 : 0);
     const uint8_t* src = v.slot(SL_A + q) + 4 * wd;
-    uint8_t* dst = o + off + 4 * wd;
+    uint8_t* dst = o + pl.point_offset(q) + 4 * wd;
     dst[0] = src[0];
     dst[1] = src[1];
     dst[2] = src[2];
     dst[3] = src[3];
   }
   const Fr* sc = v.sc();
-  if (lane < 7) {
-    const size_t off_rp = 48 * (size_t)b1, off_c = off_rp + 32 + 48 * (size_t)(b2 - b1), off_zk = off_c + 64 + 48 * (size_t)(b3 - b2),
-                 off_x = off_zk + 96 + 48 * (size_t)(npp - b3);
-    const size_t offs[7] = {off_rp, off_c, off_c + 32, off_zk, off_zk + 32, off_zk + 64, off_x};
+  if (lane < ProofLayout::N_SCALARS) {
     const Fr xf = d.rvec2[(size_t)v.p * 2 * n];   // x[0] after the last fold (same_multiscalar_argument.rs:138-141)
-    const Fr vals[7] = {sc[SC_RP], sc[SC_CFIN], sc[SC_DFIN], sc[SC_ZK], sc[SC_ZT], sc[SC_ZU], xf};
+    const Fr vals[ProofLayout::N_SCALARS] = {sc[SC_RP], sc[SC_CFIN], sc[SC_DFIN], sc[SC_ZK], sc[SC_ZT], sc[SC_ZU], xf};
+    size_t offs[ProofLayout::N_SCALARS];   // (a table of the seven offsets, not scalar_offset(lane): that costs three more VGPRs)
+    CPX_UNROLL for (int i = 0; i < ProofLayout::N_SCALARS; i++) offs[i] = pl.scalar_offset(i);
     store_le32(o + offs[lane], vals[lane]);
   }
 }
@@ -415,13 +412,8 @@ struct VerifyView {
   int p;
   __device__ VerifyView(const VerifyDev& d_, int p_) : d(d_), p(p_) {}
   __device__ const uint8_t* pb() const { return d.proofs + (size_t)p * d.psz; }
-  // byte offset of proof point q (slot SL_A + q) inside the serialized proof: scalars are interleaved after 9, 11 + 4L and 15 + 4L points
-  __device__ size_t pt_off(int q) const { return 48 * (size_t)q + (q >= 9 ? 32 : 0) + (q >= 11 + 4 * d.L ? 64 : 0) + (q >= 15 + 4 * d.L ? 96 : 0); }
-  __device__ const uint8_t* P(int slot) const { return pb() + pt_off(slot - SL_A); }
-  __device__ size_t off_rp() const { return 48 * 9; }
-  __device__ size_t off_c() const { return off_rp() + 32 + 48 * (size_t)(2 + 4 * d.L); }
-  __device__ size_t off_zk() const { return off_c() + 64 + 48 * 4; }
-  __device__ size_t off_x() const { return off_zk() + 96 + 48 * (size_t)(3 + 6 * d.L); }
+  __device__ const uint8_t* P(int slot) const { return pb() + ProofLayout(d.L).point_offset(slot - SL_A); }
+  __device__ const uint8_t* scalar(int i) const { return pb() + ProofLayout(d.L).scalar_offset(i); }
   __device__ uint8_t* slot(int s) const { return d.slotcomp + ((size_t)p * d.NS + s) * 48; }
   __device__ Fr* vsc() const { return d.vsc + (size_t)p * VSC_COUNT; }
   __device__ uint64_t* tstate() const { return d.tstate + (size_t)p * 27; }
@@ -461,17 +453,16 @@ __global__ __launch_bounds__(64) void k_vs_prefix(const VerifyDev d) {
   const VerifyView v(d, blockIdx.x);
   const int lane = threadIdx.x, ell = d.ell;
   const SlotMap sm(d.L);
-  const uint8_t* pb = v.pb();
   // the seven scalars of the proof must be canonical, every proof point must have decoded (status != 0: malformed / off the curve / outside the subgroup)
   Fr r_p, c_fin, d_fin, z_k, z_t, z_u, x_fin;
-  bool ok = load_scalar(pb + v.off_rp(), r_p);
-  ok &= load_scalar(pb + v.off_c(), c_fin);
-  ok &= load_scalar(pb + v.off_c() + 32, d_fin);
-  ok &= load_scalar(pb + v.off_zk(), z_k);
-  ok &= load_scalar(pb + v.off_zk() + 32, z_t);
-  ok &= load_scalar(pb + v.off_zk() + 64, z_u);
-  ok &= load_scalar(pb + v.off_x(), x_fin);
-  const int npp = sm.n_proof_points();
+  bool ok = load_scalar(v.scalar(ProofLayout::r_p), r_p);
+  ok &= load_scalar(v.scalar(ProofLayout::c), c_fin);
+  ok &= load_scalar(v.scalar(ProofLayout::d), d_fin);
+  ok &= load_scalar(v.scalar(ProofLayout::z_k), z_k);
+  ok &= load_scalar(v.scalar(ProofLayout::z_t), z_t);
+  ok &= load_scalar(v.scalar(ProofLayout::z_u), z_u);
+  ok &= load_scalar(v.scalar(ProofLayout::x), x_fin);
+  const int npp = ProofLayout(d.L).n_points();
   int badpt = 0;
   for (int q = lane; q < npp; q += 64) badpt |= d.status[(size_t)v.p * npp + q];
   const bool bad = !ok || __any(badpt != 0);
@@ -609,7 +600,8 @@ __global__ __launch_bounds__(64) void k_vs_scalars(const VerifyDev d) {
   __syncthreads();
   scan_mul(buf, ell + 1);
   const Fr* rnd = v.rnd();
-  const Fr a1 = rnd[0], a2 = rnd[1], a3 = rnd[2], a4 = rnd[3], a5 = rnd[4], a6 = rnd[5], a7 = rnd[6], a8 = rnd[7];
+  const Fr a1 = rnd[VF_SAMEPERM], a2 = rnd[VF_IPA_C], a3 = rnd[VF_IPA_D], a4 = rnd[VF_SMSM_A], a5 = rnd[VF_SMSM_T], a6 = rnd[VF_SMSM_U],
+           a7 = rnd[VF_R], a8 = rnd[VF_S];
   const Fr a2c = fe_mul(a2, c_fin), a3d = fe_mul(a3, d_fin), a4x = fe_mul(a4, x_fin), a5x = fe_mul(a5, x_fin), a6x = fe_mul(a6, x_fin);
   const Fr a1b = fe_mul(a1, beta_sp);
   const bool bad = d.flags[v.p] & 1u;   // an undecodable proof contributes nothing to a fused batch (it is counted as invalid)
@@ -655,11 +647,11 @@ __global__ __launch_bounds__(64) void k_vs_scalars(const VerifyDev d) {
   }
   // (3) misc part: singles, M, proof points.  Slot s sits at misc index s (SL_A == SL_M + 1).
   Fr w1, w2, w3, w4;   // weights of the four SameScalar equalities (same_scalar_argument.rs:127-137; include/cpx.h)
-  if (d.rand_stride >= 12) {
-    w1 = rnd[8];
-    w2 = rnd[9];
-    w3 = rnd[10];
-    w4 = rnd[11];
+  if (d.rand_stride >= VF_FUSED_COUNT) {
+    w1 = rnd[VF_SS_A1];
+    w2 = rnd[VF_SS_A2];
+    w3 = rnd[VF_SS_B1];
+    w4 = rnd[VF_SS_B2];
   } else {
     w1 = fe_mul(a1, a2);
     w2 = fe_mul(a3, a4);

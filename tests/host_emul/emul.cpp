@@ -13,6 +13,7 @@
 #include "../../curdleproofs_amd/csrc/host_math.hpp"
 #include "../../curdleproofs_amd/csrc/quad_program.hpp"
 #include "../../curdleproofs_amd/csrc/host_threads.hpp"
+#include "../../curdleproofs_amd/csrc/layout.hpp"
 #include <stdexcept>
 
 using namespace cpx;
@@ -718,6 +719,23 @@ int emul_thread_helpers(int kind, size_t threads, size_t n, size_t jobs, long th
     if (throw_at < 0 ? got != expect : (got > expect || got + (i + (uint64_t)throw_at + 1) < expect)) return 2;
   }
   return 0;
+}
+
+// layout.hpp at ell: out = [point_offset(q) of every proof point | scalar_offset(i), i < 7 | size() | RandIdx(n).count() |
+// CtabCols(n).count()], n = ell + 4.  Returns the number of proof points, or -1 if out (cap entries) is too short.
+int emul_layout(size_t ell, uint64_t* out, size_t cap) {
+  const size_t n = ell + 4;
+  int L = 0;
+  while ((size_t(1) << L) < n) L++;
+  const ProofLayout pl(L);
+  const int npp = pl.n_points();
+  if ((size_t)npp + ProofLayout::N_SCALARS + 3 > cap) return -1;
+  for (int q = 0; q < npp; q++) *out++ = pl.point_offset(q);
+  for (int i = 0; i < ProofLayout::N_SCALARS; i++) *out++ = pl.scalar_offset(i);
+  *out++ = pl.size();
+  *out++ = (uint64_t)RandIdx((int)n).count();
+  *out++ = (uint64_t)CtabCols(n).count();
+  return npp;
 }
 
 }  // extern "C"

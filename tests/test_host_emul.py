@@ -7,6 +7,8 @@ import subprocess
 
 import pytest
 
+from tests import decoding_ref as dr
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "host_emul", "emul.cpp")
 LIB = os.path.join(HERE, "host_emul", "_emul.so")
@@ -18,7 +20,7 @@ FR, AFF, JAC = 32, 96, 144
 
 @pytest.fixture(scope="module")
 def emul():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("mont32.hpp", "g1.hpp", "recode.hpp", "host_math.hpp", "fp28.hpp", "g1_28.hpp", "modinv30.hpp", "strobe.hpp", "quad_program.hpp", "host_threads.hpp")]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("mont32.hpp", "g1.hpp", "recode.hpp", "host_math.hpp", "fp28.hpp", "g1_28.hpp", "modinv30.hpp", "strobe.hpp", "quad_program.hpp", "host_threads.hpp", "layout.hpp")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", LIB, SRC])
     L = ctypes.CDLL(LIB)
@@ -53,6 +55,8 @@ def emul():
     L.emul_late_uniform.restype = None
     L.emul_late_msm.argtypes = [vp, vp, sz, ctypes.c_int, vp]
     L.emul_late_msm.restype = None
+    L.emul_layout.argtypes = [sz, ctypes.POINTER(ctypes.c_uint64), sz]
+    L.emul_layout.restype = ctypes.c_int
     return L
 
 
@@ -518,3 +522,21 @@ def test_late_msm_straus_matches_oracle_msm(emul, orc, n, slices):
     out = _o(JAC)
     emul.emul_late_msm(_b(bytes(bases)), _b(bytes(scalars)), n, slices, out)
     assert orc.g1_compress_jac(bytes(out)) == orc.g1_compress_jac(orc.g1_msm(bytes(bases), bytes(scalars)))
+
+
+@pytest.mark.parametrize("ell", [28, 60, 124, 252, 508, 1020])
+def test_layout_header_matches_the_serialisation_order(emul, ell):
+    """layout.hpp, the one definition of the index layouts that both prover and verifier paths and the kernels read: ProofLayout's
+    point offsets, scalar offsets and size against the serialisation order of tests/decoding_ref.py (pinned to the parity tests'
+    offsets and, through the decoding tests, to the oracle); the prover's 3n + 9 random draws; the n + 5 CRS table columns."""
+    points, scalars = dr.proof_layout(ell)
+    n, npp = ell + 4, len(points)
+    cap = 2 * npp + 16
+    out = (ctypes.c_uint64 * cap)()
+    assert emul.emul_layout(ell, out, cap) == npp
+    got = list(out)
+    assert got[:npp] == [o for _, o in points]
+    assert got[npp:npp + 7] == [scalars[k] for k in ("r_p", "c", "d", "z_k", "z_t", "z_u", "x")]
+    assert got[npp + 7] == 48 * npp + 32 * 7
+    assert got[npp + 8] == 3 * n + 9
+    assert got[npp + 9] == n + 5
