@@ -36,6 +36,8 @@ struct F28Cfg {
   static constexpr int32_t MASK = 0x0fffffff;
   static constexpr int32_t P[14] = {0xfffaaab, 0xfefffff, 0x3ffffb9, 0xfffeb15, 0x6241eab, 0xa0f6b0f, 0xf6730d2,
                                     0xf38512b, 0x4774b84, 0x4bacd76, 0xba7b643, 0xe69a4b1, 0x1ea397f, 0x001a011};
+  // P_(7+j) - P_j: the constant half difference of the Karatsuba reduction (f28_kara_col), |.| < 2^28
+  static constexpr int32_t DP[7] = {-0x0c75980, -0xb78b47b, 0x0bacdbd, -0x45834d2, 0x8458606, -0x8253190, -0xf6590c1};
   static constexpr uint32_t INV = 0xffcfffd;   // -p^-1 mod 2^28
   // 2^392 mod p (Montgomery one), 2^400 mod p (standard -> internal), 2^384 mod p (internal -> standard)
   static constexpr int32_t ONE[14] = {0x347fcb8, 0xd800000, 0x002b119, 0x0cde6d2, 0xc7212e0, 0x83a2090, 0x037669f,
@@ -53,6 +55,12 @@ struct F28Cfg {
   static constexpr int32_t C_OUT[14] = {0x002fffd, 0x0900000, 0xc000276, 0x000bc40, 0x8baebf4, 0x5753c75, 0x55f4898,
                                         0x7052574, 0x7ce5853, 0x56ec6d7, 0x71a97a2, 0xe4935c0, 0xec3fa80, 0x0015f65};
 };
+constexpr bool f28_dp_consistent() {
+  for (int j = 0; j < 7; j++)
+    if (F28Cfg::DP[j] != F28Cfg::P[7 + j] - F28Cfg::P[j]) return false;
+  return true;
+}
+static_assert(f28_dp_consistent(), "F28Cfg::DP must be P_(7+j) - P_j");
 
 // carry pass: limbs 0..12 into [0, 2^28), the top limb absorbs the (signed) rest
 CPX_HD void f28_normalize(F28& a) {
@@ -117,7 +125,8 @@ CPX_HD F28 f28_cneg(const F28& a, bool neg) {
 
 // Montgomery product a * b / 2^392 mod p (lazy range).  Product scanning: column k gathers a_i b_(k-i) and
 // m_i p_(k-i) into one signed 64-bit accumulator (|sum| < 2^62), emits one limb, shifts by 28 bits.
-// Schoolbook form (196 + 196 multiply-adds); f28_mul_body_kara computes the same column sums with 147 + 196.
+// Schoolbook form (196 + 196 multiply-adds); f28_mul_body_kara computes the same column sums with 147 + 196 (schoolbook
+// reduction) or 147 + 154 (Karatsuba reduction).
 CPX_HD F28 f28_mul_body_school(const F28& a, const F28& b) {
   int32_t m[14];
   F28 t;
@@ -182,19 +191,47 @@ CPX_HD F28 f28_mulsub_body_school(const F28& a, const F28& b, const F28& c, cons
 //   column k of x y = L_k + (L_(k-7) + H_(k-7) + D_(k-7)) + H_(k-14) = E_k + E_(k-7) + D_(k-7) with E_k = L_k + H_(k-7).
 // E_k is summed once (k = 0..19), added to its own column and kept in registers for column k + 7; the N products share the
 // E / D merges.  The column sums are the same integers as the schoolbook body's, so the digits m_k and the result are bit-identical.
+//
+// Montgomery half (RK = true): the digits m = m0 + 2^196 m1 meet the constant p = p0 + 2^196 p1 in the SAME three blocks and
+// share their E / D merges: L gets m_i P_j, H gets m_(7+i) P_(7+j), D gets dm_i dP_j with dm_i = m_i - m_(7+i) and the
+// constants dP_j = P_(7+j) - P_j (F28Cfg::DP).  Digit m_k (k <= 13) enters its own column with total coefficient P_0 in every
+// form: for k <= 6 as L's m_k P_0, for k = 7..13 as H's m_k P_7 plus D's -m_k dP_0.  So column k first sums every term without
+// m_k (for k >= 7 the known half m_(k-7) dP_0 of D's diagonal term among them), takes m_k from the low 28 bits, adds m_k P_0,
+// and completes E_k with m_k's own term for column k + 7 (k <= 6: m_k P_0, k >= 7: m_k P_7); for k >= 7 it also forms
+// dm_(k-7) = m_(k-7) - m_k for the later D columns.  154 multiply-adds instead of 196 (147 + one m_k P_0 for each k = 7..13),
+// 7 subtractions; every column sum is the same integer as the schoolbook body's, so digits and result stay bit-identical.
+// RK = false keeps the reduction in product-scanning columns (196 multiply-adds), the body of r07.
+//
 // Bounds: every operand limb that reaches a product is below 2^28 in magnitude (normalised values: limbs 0..12 in [0, 2^28), the
-// top limb below 2^23 for |x| <= 38 p; f28_sub_lazy / f28_cneg_lazy: limbs in (-2^28, 2^28)), so a half difference is below 2^29.
-// E_k has at most 7 terms per product (k <= 6: k + 1; 7..12: (13 - k) + (k - 6); 13..19: 20 - k) of < 2^56, D_j at most 7 of < 2^58,
-// the reduction 14 terms m_i p_(k-i) of < 2^56 and the carry < 2^35.  Every partial sum of column k is therefore below
-//   N = 1: 14 * 2^56 (E_k, E_(k-7)) + 7 * 2^58 (D) + 14 * 2^56 + 2^35 = 56 * 2^56 + 2^35 < 2^61.9   (schoolbook: 28 * 2^56)
-//   N = 2: 28 * 2^56 + 14 * 2^58 + 14 * 2^56 + 2^35 = 98 * 2^56 + 2^35 < 2^62.7 < 2^63          (schoolbook: 42 * 2^56)
-// so both products of f28_mulsub_body stay in Karatsuba form.  Cost: 14 limb differences per product and two 64-bit additions
-// per column where E_k and E_(k-7) meet (k = 7..19) instead of one.
-// One column k of f28_kara_redc (k a template argument: every loop below has constant bounds and unrolls in full).
-template <int K, int N> CPX_HD void f28_kara_col(const F28 (&x)[N], const F28 (&y)[N], const int32_t (&dx)[N][7], const int32_t (&dy)[N][7],
-                                                 int64_t (&e)[20], int32_t (&m)[14], int64_t& acc, F28& t) {
-  if constexpr (K < 20) {
-    int64_t s = 0;
+// top limb below 2^23 for |x| <= 38 p; f28_sub_lazy / f28_cneg_lazy: limbs in (-2^28, 2^28)), so a half difference is below 2^29;
+// digits m_i lie in [0, 2^28), so |dm_i| < 2^28, and |P_j|, |dP_j| < 2^28.  The a b part of E_k has at most 7 terms per product
+// (k <= 6: k + 1; 7..12: (13 - k) + (k - 6); 13..19: 20 - k) of < 2^56, the a b part of D_j at most 7 per product of < 2^58.
+// Schoolbook reduction: 14 terms m_i p_(k-i) of < 2^56 per column.  Karatsuba reduction: E_k holds at most 7 m p terms of < 2^56
+// (m_k's own P_0 term in column k among them), D_j at most 7 of < 2^56 (m_(k-7) dP_0 included).  With the carry < 2^35 every
+// partial sum of column k is below
+//   RK = false, N = 1: 14 * 2^56 (E_k, E_(k-7)) + 7 * 2^58 (D) + 14 * 2^56 + 2^35 = 56 * 2^56 + 2^35 < 2^61.9   (schoolbook: 28 * 2^56)
+//   RK = false, N = 2: 28 * 2^56 + 14 * 2^58 + 14 * 2^56 + 2^35 = 98 * 2^56 + 2^35 < 2^62.7
+//   RK = true,  N = 1: 2 * (7 + 7) * 2^56 (E_k, E_(k-7)) + (7 * 4 + 7) * 2^56 (D) + 2^35 = 63 * 2^56 + 2^35 < 2^62
+//   RK = true,  N = 2: 2 * (14 + 7) * 2^56 + (14 * 4 + 7) * 2^56 + 2^35 = 105 * 2^56 + 2^35 < 2^62.8 < 2^63
+// so both products of f28_mulsub_body stay in Karatsuba form with either reduction; E_k itself stays below 21 * 2^56.
+// (Squares, f28_sqr_body_kara: a pair of off-diagonal terms taken once against a doubled limb is at most the sum of the two terms
+// it replaces, so the N = 1 bounds hold.)
+//
+// The a b side of the columns is an operand object: Ops::e<K>(s) adds the a b terms of E_K, Ops::d<J>(acc) those of D_J.
+// F28KaraMul: the N products sum_n x_n y_n.
+template <int N> struct F28KaraMul {
+  const F28 (&x)[N];
+  const F28 (&y)[N];
+  int32_t dx[N][7], dy[N][7];
+  CPX_HD F28KaraMul(const F28 (&x_)[N], const F28 (&y_)[N]) : x(x_), y(y_) {
+    CPX_UNROLL for (int n = 0; n < N; n++) {
+      CPX_UNROLL for (int i = 0; i < 7; i++) {
+        dx[n][i] = x[n].v[i] - x[n].v[i + 7];   // |.| < 2^29
+        dy[n][i] = y[n].v[i + 7] - y[n].v[i];
+      }
+    }
+  }
+  template <int K> CPX_HD void e(int64_t& s) const {
     CPX_UNROLL for (int n = 0; n < N; n++) {
       if constexpr (K <= 12) {
         CPX_UNROLL for (int i = (K > 6 ? K - 6 : 0); i <= (K < 6 ? K : 6); i++) s += (int64_t)x[n].v[i] * y[n].v[K - i];
@@ -204,85 +241,156 @@ template <int K, int N> CPX_HD void f28_kara_col(const F28 (&x)[N], const F28 (&
         CPX_UNROLL for (int i = (J > 6 ? J - 6 : 0); i <= (J < 6 ? J : 6); i++) s += (int64_t)x[n].v[i + 7] * y[n].v[J - i + 7];
       }
     }
-    e[K] = s;
+  }
+  template <int J> CPX_HD void d(int64_t& acc) const {
+    CPX_UNROLL for (int n = 0; n < N; n++) {
+      CPX_UNROLL for (int i = (J > 6 ? J - 6 : 0); i <= (J < 6 ? J : 6); i++) acc += (int64_t)dx[n][i] * dy[n][J - i];
+    }
+  }
+};
+// F28KaraSqr: a^2 with symmetric 7 x 7 squares.  L and H take their off-diagonal pairs once against the doubled limb 2 a_i
+// (|.| < 2^29); D_j = ((a0 - a1)(a1 - a0))_j = -((a0 - a1)^2)_j takes them against -2 u_i with u = a0 - a1 (|u_i| < 2^29,
+// |2 u_i| < 2^30) and its diagonal as (-u_i) u_i.  28 multiply-adds per block: 84 instead of the 105 of the schoolbook square.
+struct F28KaraSqr {
+  const F28& a;
+  int32_t a2[14], u[7], n2[7];
+  CPX_HD explicit F28KaraSqr(const F28& a_) : a(a_) {
+    CPX_UNROLL for (int i = 0; i < 14; i++) a2[i] = a.v[i] * 2;
+    CPX_UNROLL for (int i = 0; i < 7; i++) {
+      u[i] = a.v[i] - a.v[i + 7];
+      n2[i] = u[i] * -2;
+    }
+  }
+  template <int J, int O> CPX_HD void sq7(int64_t& s) const {   // column J of (a_O .. a_(O+6))^2
+    CPX_UNROLL for (int i = (J > 6 ? J - 6 : 0); 2 * i < J; i++) s += (int64_t)a2[O + i] * a.v[O + J - i];
+    if constexpr (J % 2 == 0) s += (int64_t)a.v[O + J / 2] * a.v[O + J / 2];
+  }
+  template <int K> CPX_HD void e(int64_t& s) const {
+    if constexpr (K <= 12) sq7<K, 0>(s);
+    if constexpr (K >= 7) sq7<K - 7, 7>(s);
+  }
+  template <int J> CPX_HD void d(int64_t& acc) const {
+    CPX_UNROLL for (int i = (J > 6 ? J - 6 : 0); 2 * i < J; i++) acc += (int64_t)n2[i] * u[J - i];
+    if constexpr (J % 2 == 0) acc += (int64_t)(-u[J / 2]) * u[J / 2];
+  }
+};
+// One column k of f28_kara_redc (k a template argument: every loop below has constant bounds and unrolls in full).
+template <int K, bool RK, class Ops> CPX_HD void f28_kara_col(const Ops& o, int64_t (&e)[20], int32_t (&m)[14], int32_t (&dm)[7], int64_t& acc, F28& t) {
+  constexpr int J = K - 7;
+  [[maybe_unused]] const int64_t carry = acc;
+  [[maybe_unused]] int64_t s = 0;
+  if constexpr (K < 20) {
+    o.template e<K>(s);
+    if constexpr (RK) {   // the m p terms of E_K, m_K's own term left out while m_K is unknown (K <= 13)
+      if constexpr (K <= 12) {
+        CPX_UNROLL for (int i = (K > 6 ? K - 6 : 0); i <= (K < 6 ? K : 6); i++) {
+          if (i != K) s += (int64_t)m[i] * F28Cfg::P[K - i];
+        }
+      }
+      if constexpr (K >= 7) {
+        CPX_UNROLL for (int i = (J > 6 ? J - 6 : 0); i <= (J < 6 ? J : 6); i++) {
+          if (i + 7 != K) s += (int64_t)m[i + 7] * F28Cfg::P[J - i + 7];
+        }
+      }
+    }
+    if constexpr (!RK || K >= 14) e[K] = s;
     acc += s;
   }
   if constexpr (K >= 7) {
-    constexpr int J = K - 7;
     acc += e[J];
     if constexpr (J <= 12) {
-      CPX_UNROLL for (int n = 0; n < N; n++) {
-        CPX_UNROLL for (int i = (J > 6 ? J - 6 : 0); i <= (J < 6 ? J : 6); i++) acc += (int64_t)dx[n][i] * dy[n][J - i];
+      o.template d<J>(acc);
+      if constexpr (RK) {
+        CPX_UNROLL for (int i = (J > 6 ? J - 6 : 0); i <= (J < 6 ? J : 6); i++) {
+          if (K <= 13 && i == J) acc += (int64_t)m[J] * F28Cfg::DP[0];   // the known half of dm_J dP_0
+          else acc += (int64_t)dm[i] * F28Cfg::DP[J - i];
+        }
       }
     }
   }
   if constexpr (K < 14) {
-    CPX_UNROLL for (int i = 0; i < K; i++) acc += (int64_t)m[i] * F28Cfg::P[K - i];
+    if constexpr (!RK) {
+      CPX_UNROLL for (int i = 0; i < K; i++) acc += (int64_t)m[i] * F28Cfg::P[K - i];
+    }
     m[K] = (int32_t)(((uint32_t)acc * F28Cfg::INV) & (uint32_t)F28Cfg::MASK);
-    acc += (int64_t)m[K] * F28Cfg::P[0];
+    if constexpr (RK && K <= 6) {   // column K is E_K alone: its sum is the carry in plus the completed E_K
+      e[K] = s + (int64_t)m[K] * F28Cfg::P[0];
+      acc = carry + e[K];
+    } else {
+      acc += (int64_t)m[K] * F28Cfg::P[0];
+      if constexpr (RK) {
+        e[K] = s + (int64_t)m[K] * F28Cfg::P[7];
+        dm[J] = m[J] - m[K];
+      }
+    }
   } else {
-    CPX_UNROLL for (int i = K - 13; i < 14; i++) acc += (int64_t)m[i] * F28Cfg::P[K - i];
+    if constexpr (!RK) {
+      CPX_UNROLL for (int i = K - 13; i < 14; i++) acc += (int64_t)m[i] * F28Cfg::P[K - i];
+    }
     t.v[K - 14] = (int32_t)acc & F28Cfg::MASK;
   }
   acc >>= 28;
 }
-template <int N, int... K> CPX_HD F28 f28_kara_cols(const F28 (&x)[N], const F28 (&y)[N], std::integer_sequence<int, K...>) {
-  int32_t dx[N][7], dy[N][7], m[14];
-  CPX_UNROLL for (int n = 0; n < N; n++) {
-    CPX_UNROLL for (int i = 0; i < 7; i++) {
-      dx[n][i] = x[n].v[i] - x[n].v[i + 7];   // |.| < 2^29
-      dy[n][i] = y[n].v[i + 7] - y[n].v[i];
-    }
-  }
+template <bool RK, class Ops, int... K> CPX_HD F28 f28_kara_cols(const Ops& o, std::integer_sequence<int, K...>) {
+  int32_t m[14], dm[7];
   int64_t e[20];
   F28 t;
   int64_t acc = 0;
-  (f28_kara_col<K, N>(x, y, dx, dy, e, m, acc, t), ...);
+  (f28_kara_col<K, RK>(o, e, m, dm, acc, t), ...);
   t.v[13] = (int32_t)acc;
   return t;
 }
-template <int N> CPX_HD F28 f28_kara_redc(const F28 (&x)[N], const F28 (&y)[N]) {
-  return f28_kara_cols<N>(x, y, std::make_integer_sequence<int, 27>());
+template <bool RK, class Ops> CPX_HD F28 f28_kara_redc(const Ops& o) {
+  return f28_kara_cols<RK>(o, std::make_integer_sequence<int, 27>());
 }
-CPX_HD F28 f28_mul_body_kara(const F28& a, const F28& b) {
+template <bool RK> CPX_HD F28 f28_mul_body_kara(const F28& a, const F28& b) {
   const F28 x[1] = {a}, y[1] = {b};
-  return f28_kara_redc<1>(x, y);
+  return f28_kara_redc<RK>(F28KaraMul<1>(x, y));
 }
-CPX_HD F28 f28_mulsub_body_kara(const F28& a, const F28& b, const F28& c, const F28& d) {
+template <bool RK> CPX_HD F28 f28_mulsub_body_kara(const F28& a, const F28& b, const F28& c, const F28& d) {
   F28 nc;
   CPX_UNROLL for (int i = 0; i < 14; i++) nc.v[i] = -c.v[i];
   const F28 x[2] = {a, nc}, y[2] = {b, d};
-  return f28_kara_redc<2>(x, y);
+  return f28_kara_redc<RK>(F28KaraMul<2>(x, y));
 }
+// Karatsuba square: symmetric blocks and the Karatsuba reduction, 84 + 154 = 238 multiply-adds (schoolbook square: 301).
+CPX_HD F28 f28_sqr_body_kara(const F28& a) { return f28_kara_redc<true>(F28KaraSqr(a)); }
 
-// Which body a product uses is a compile-time choice (template argument KARA), per call site; the default is the Karatsuba
-// form.  CPX_F28_KARATSUBA=0 at build time makes the schoolbook form the default everywhere (A/B builds, the CPU tests).
+// Which body a product uses is a compile-time choice per call site: template argument KARA (Karatsuba columns for a b) and RKARA
+// (the Karatsuba Montgomery half; it needs KARA's blocks and is ignored without them).  Defaults: both on.  CPX_F28_KARATSUBA=0 at
+// build time makes the schoolbook form the default everywhere; CPX_F28_REDC_KARATSUBA=0 restores the r07 body (Karatsuba a b,
+// schoolbook reduction, schoolbook square) as the default (A/B builds, the CPU tests).
 #ifndef CPX_F28_KARATSUBA
 #define CPX_F28_KARATSUBA 1
 #endif
+#ifndef CPX_F28_REDC_KARATSUBA
+#define CPX_F28_REDC_KARATSUBA 1
+#endif
 constexpr bool F28_KARA = CPX_F28_KARATSUBA != 0;
-template <bool KARA = F28_KARA> CPX_HD F28 f28_mul_body(const F28& a, const F28& b) {
-  if constexpr (KARA) return f28_mul_body_kara(a, b);
+constexpr bool F28_REDC_KARA = CPX_F28_REDC_KARATSUBA != 0;
+constexpr bool F28_SQR_KARA = F28_KARA && F28_REDC_KARA;   // the square's Karatsuba body carries both halves
+template <bool KARA = F28_KARA, bool RKARA = F28_REDC_KARA> CPX_HD F28 f28_mul_body(const F28& a, const F28& b) {
+  if constexpr (KARA) return f28_mul_body_kara<RKARA>(a, b);
   else return f28_mul_body_school(a, b);
 }
-template <bool KARA = F28_KARA> CPX_HD F28 f28_mulsub_body(const F28& a, const F28& b, const F28& c, const F28& d) {
-  if constexpr (KARA) return f28_mulsub_body_kara(a, b, c, d);
+template <bool KARA = F28_KARA, bool RKARA = F28_REDC_KARA> CPX_HD F28 f28_mulsub_body(const F28& a, const F28& b, const F28& c, const F28& d) {
+  if constexpr (KARA) return f28_mulsub_body_kara<RKARA>(a, b, c, d);
   else return f28_mulsub_body_school(a, b, c, d);
 }
 // out-of-line entry with scalar register arguments (same calling-convention reasoning as fe_mul_regs12)
 #define CPX_L14(p) p##0, p##1, p##2, p##3, p##4, p##5, p##6, p##7, p##8, p##9, p##10, p##11, p##12, p##13
 #define CPX_A14(p) int32_t p##0, int32_t p##1, int32_t p##2, int32_t p##3, int32_t p##4, int32_t p##5, int32_t p##6, int32_t p##7, int32_t p##8, int32_t p##9, int32_t p##10, int32_t p##11, int32_t p##12, int32_t p##13
-template <bool KARA> CPX_HD_FN F28 f28_mul_regs(CPX_A14(a), CPX_A14(b)) {
+template <bool KARA, bool RKARA = F28_REDC_KARA> CPX_HD_FN F28 f28_mul_regs(CPX_A14(a), CPX_A14(b)) {
   const F28 x{{CPX_L14(a)}}, y{{CPX_L14(b)}};
-  return f28_mul_body<KARA>(x, y);
+  return f28_mul_body<KARA, RKARA>(x, y);
 }
-template <bool KARA = F28_KARA> CPX_HD F28 f28_mul(const F28& a, const F28& b) {
-  return f28_mul_regs<KARA>(a.v[0], a.v[1], a.v[2], a.v[3], a.v[4], a.v[5], a.v[6], a.v[7], a.v[8], a.v[9], a.v[10], a.v[11], a.v[12], a.v[13],
-                            b.v[0], b.v[1], b.v[2], b.v[3], b.v[4], b.v[5], b.v[6], b.v[7], b.v[8], b.v[9], b.v[10], b.v[11], b.v[12], b.v[13]);
+template <bool KARA = F28_KARA, bool RKARA = F28_REDC_KARA> CPX_HD F28 f28_mul(const F28& a, const F28& b) {
+  return f28_mul_regs<KARA, RKARA>(a.v[0], a.v[1], a.v[2], a.v[3], a.v[4], a.v[5], a.v[6], a.v[7], a.v[8], a.v[9], a.v[10], a.v[11], a.v[12], a.v[13],
+                                   b.v[0], b.v[1], b.v[2], b.v[3], b.v[4], b.v[5], b.v[6], b.v[7], b.v[8], b.v[9], b.v[10], b.v[11], b.v[12], b.v[13]);
 }
-// Squaring: the 91 off-diagonal limb products are taken once against the doubled operand (301 multiply-adds
+// Schoolbook squaring: the 91 off-diagonal limb products are taken once against the doubled operand (301 multiply-adds
 // instead of 392).
-CPX_HD F28 f28_sqr_body(const F28& a) {
+CPX_HD F28 f28_sqr_body_school(const F28& a) {
   int32_t m[14], d[14];
   CPX_UNROLL for (int i = 0; i < 14; i++) d[i] = a.v[i] * 2;   // |limb| < 2^29
   F28 t;
@@ -305,12 +413,16 @@ CPX_HD F28 f28_sqr_body(const F28& a) {
   t.v[13] = (int32_t)acc;
   return t;
 }
-CPX_HD_FN F28 f28_sqr_regs(CPX_A14(a)) {
-  const F28 x{{CPX_L14(a)}};
-  return f28_sqr_body(x);
+template <bool KARA = F28_SQR_KARA> CPX_HD F28 f28_sqr_body(const F28& a) {
+  if constexpr (KARA) return f28_sqr_body_kara(a);
+  else return f28_sqr_body_school(a);
 }
-CPX_HD F28 f28_sqr(const F28& a) {
-  return f28_sqr_regs(a.v[0], a.v[1], a.v[2], a.v[3], a.v[4], a.v[5], a.v[6], a.v[7], a.v[8], a.v[9], a.v[10], a.v[11], a.v[12], a.v[13]);
+template <bool KARA> CPX_HD_FN F28 f28_sqr_regs(CPX_A14(a)) {
+  const F28 x{{CPX_L14(a)}};
+  return f28_sqr_body<KARA>(x);
+}
+template <bool KARA = F28_SQR_KARA> CPX_HD F28 f28_sqr(const F28& a) {
+  return f28_sqr_regs<KARA>(a.v[0], a.v[1], a.v[2], a.v[3], a.v[4], a.v[5], a.v[6], a.v[7], a.v[8], a.v[9], a.v[10], a.v[11], a.v[12], a.v[13]);
 }
 
 CPX_HD F28 f28_const(const int32_t* c) {

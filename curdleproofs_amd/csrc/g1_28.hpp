@@ -115,11 +115,11 @@ CPX_PT_FN Xyzz28 xyzz28_dbl_affine(const Aff28& q) {   // mdbl-2008-s-1: 2 * (x,
 // arguments and returns 14).  Used by the one loop where it pays, k_msm_tblw: +4 % there, and the kernel drops from
 // 256 VGPRs with spills to 231 without; in k_msm_fix (two points in flight) it bought nothing, and inlining
 // everywhere would put several 40 KB loops into the instruction cache two CUs share.
-// KARA: the product body (fp28.hpp) of the inlined products; a kernel whose register budget does not allow the Karatsuba body
-// passes false.
-template <bool INL, bool KARA = F28_KARA> CPX_PT_FN Xyzz28 xyzz28_add_mixed_t(const Xyzz28& p, const Aff28& q) {
-  auto mul = [](const F28& a, const F28& b) { return INL ? f28_mul_body<KARA>(a, b) : f28_mul<KARA>(a, b); };
-  auto sqr = [](const F28& a) { return INL ? f28_sqr_body(a) : f28_sqr(a); };
+// KARA, RKARA: the product bodies (fp28.hpp) of the inlined products and squares (Karatsuba a b columns, Karatsuba Montgomery
+// half); a kernel whose register budget does not allow a Karatsuba body passes false.
+template <bool INL, bool KARA = F28_KARA, bool RKARA = F28_REDC_KARA> CPX_PT_FN Xyzz28 xyzz28_add_mixed_t(const Xyzz28& p, const Aff28& q) {
+  auto mul = [](const F28& a, const F28& b) { return INL ? f28_mul_body<KARA, RKARA>(a, b) : f28_mul<KARA, RKARA>(a, b); };
+  auto sqr = [](const F28& a) { return INL ? f28_sqr_body<KARA && RKARA>(a) : f28_sqr<KARA && RKARA>(a); };
   if (q.is_identity()) return p;
   if (p.is_identity()) {   // (q.y may come from aff28_cneg_lazy: a stored coordinate gets its carry pass)
     F28 qy = q.y;
@@ -138,7 +138,7 @@ template <bool INL, bool KARA = F28_KARA> CPX_PT_FN Xyzz28 xyzz28_add_mixed_t(co
   Xyzz28 r;
   r.x = f28_sub_sub2(sqr(rr), ppp, qq);
   // the two products of Y3 share one Montgomery reduction where the products are inlined (the bucket loops)
-  if (INL) r.y = f28_mulsub_body<KARA>(rr, f28_sub_lazy(qq, r.x), p.y, ppp);
+  if (INL) r.y = f28_mulsub_body<KARA, RKARA>(rr, f28_sub_lazy(qq, r.x), p.y, ppp);
   else r.y = f28_sub(mul(rr, f28_sub_lazy(qq, r.x)), mul(p.y, ppp));
   r.zz = zz3;
   r.zzz = mul(p.zzz, ppp);
@@ -341,7 +341,9 @@ CPX_HD TJac t_jac_from_std(const Jac& p) { return jac28_from_std(p); }
 // bucket accumulators: extended Jacobian coordinates while points are being added, Jacobian for the reductions
 typedef Xyzz28 TAcc;
 CPX_HD TAcc t_acc_add_mixed(const TAcc& p, const TAff& q) { return xyzz28_add_mixed(p, q); }
-template <bool KARA = F28_KARA> CPX_HD TAcc t_acc_add_mixed_inl(const TAcc& p, const TAff& q) { return xyzz28_add_mixed_t<true, KARA>(p, q); }
+template <bool KARA = F28_KARA, bool RKARA = F28_REDC_KARA> CPX_HD TAcc t_acc_add_mixed_inl(const TAcc& p, const TAff& q) {
+  return xyzz28_add_mixed_t<true, KARA, RKARA>(p, q);
+}
 CPX_HD TJac t_acc_to_jac(const TAcc& p) { return xyzz28_to_jac(p); }
 CPX_HD TAcc t_acc_add(const TAcc& p, const TAcc& q) { return xyzz28_add(p, q); }
 CPX_HD TAcc t_acc_dbl(const TAcc& p) { return xyzz28_dbl(p); }

@@ -201,8 +201,9 @@ __device__ __forceinline__ TAcc lds_unpark(const uint32_t* __restrict__ buf, int
   CPX_UNROLL for (int i = 0; i < ACC_WORDS; i++) w[i] = buf[i * 64 + lane];
   return a;
 }
-// Product body (fp28.hpp): Karatsuba (the default) here and in k_reduce_groups; both spilled at 256 VGPRs before it and keep
-// their 176 scratch bytes and two waves per SIMD (profiles/r07_f28_karatsuba.md).
+// Product body (fp28.hpp): Karatsuba with the Karatsuba reduction (the default) here and in k_reduce_groups; both spilled at 256
+// VGPRs before it and keep their 176 scratch bytes, their spill counts (61 / 98) and two waves per SIMD
+// (profiles/r07_f28_karatsuba.md, profiles/r08_f28_redc_karatsuba.md).
 template <bool WEIGHTED> __global__ __launch_bounds__(64, 2) void k_reduce_sets(const uint32_t* __restrict__ raw, int nsets, TAcc* __restrict__ mid) {
   __shared__ uint32_t park[WEIGHTED ? ACC_WORDS * 64 : 1];
   const int t = blockIdx.x * 64 + threadIdx.x, lane = threadIdx.x;
@@ -269,8 +270,9 @@ __global__ __launch_bounds__(64) void k_reduce_sets_wave(const uint32_t* __restr
   if (lane == 0) part[slot[set]] = t_acc_to_jac(buf[prog.result]);
 }
 
-// Product body of the bucket loops below (k_msm_tblw, k_msm_tblw_pair, k_msm_fix): Karatsuba, the default — fewer VGPRs or
-// +1 at most, no scratch, two waves per SIMD, 2.3–3.1 % fewer instructions per addition (profiles/r07_f28_karatsuba.md).
+// Product body of the bucket loops below (k_msm_tblw, k_msm_tblw_pair, k_msm_fix): Karatsuba columns with the Karatsuba
+// reduction, the default — 215–225 VGPRs, no scratch, two waves per SIMD; 2731 multiply-adds per addition against 3155 with the
+// schoolbook reduction (profiles/r08_f28_redc_karatsuba.md).
 template <int WPW, bool PERWIN = false> __global__ __launch_bounds__(64, 2) void k_msm_tblw(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw,
                                                                                             uint32_t* __restrict__ raw_slot, int slices) {
   msm_tblw_body<WPW, PERWIN>(tasks, raw, raw_slot, slices, blockIdx.x);
@@ -464,7 +466,8 @@ __device__ __forceinline__ void tmp_load(const uint32_t* tmp, size_t nthreads, s
 // Thread per base point: reads the standard-form source point, writes copy 0 in table form, then runs a chain
 // of 256 - sb doublings storing every sb-th value; the C-1 Jacobian copies are normalised with the thread's own
 // Montgomery trick plus one inversion per work-group.
-// Product body: Karatsuba through the out-of-line f28_mul (its 120 doublings per base); resources unchanged.
+// Product body: Karatsuba through the out-of-line f28_mul / f28_sqr (its 120 doublings per base), Karatsuba reduction included;
+// resources unchanged (profiles/r08_f28_redc_karatsuba.md).
 __global__ __launch_bounds__(64) void k_table_build(const Aff* __restrict__ src, size_t src_row_stride, TAff* __restrict__ table, int rows, size_t row_stride,
                                                      int npts, int copy_stride, int copies, int endo, TblTmp* __restrict__ tmp_, int step_bits) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -883,7 +886,8 @@ __global__ __launch_bounds__(64) void k_smul_quad(const SmulTask* __restrict__ t
 __device__ __noinline__ F28 f28_sqrt_device(const F28& a) { return f28_sqrt_candidate(a); }
 __device__ __noinline__ bool g1_in_subgroup_device(const Aff28& P) { return g1_28_in_subgroup(P); }
 
-// Product body: Karatsuba through the out-of-line f28_mul; the kernel keeps its 336 scratch bytes and two waves per SIMD.
+// Product body: Karatsuba (reduction included) through the out-of-line f28_mul / f28_sqr; the kernel keeps its 336 scratch bytes,
+// 37 spilled VGPRs and two waves per SIMD.
 __global__ __launch_bounds__(64, 2) void k_decompress(const uint8_t* __restrict__ in, int n, Aff* __restrict__ out,
                                                    const uint32_t* __restrict__ dst_index, uint8_t* __restrict__ status, int check_subgroup,
                                                    const uint32_t* __restrict__ src_offset) {
@@ -1310,8 +1314,8 @@ __global__ __launch_bounds__(256) void k_bench_fpmul(Fp* data, int iters) {
   }
   data[g] = fe_add(x, y);
 }
-// the same chain on the 28-bit-limb field (fp28.hpp), with the product body the hot loops use by default (F28_KARA): the
-// peak roofline.valu divides by stays comparable with the kernels
+// the same chain on the 28-bit-limb field (fp28.hpp), with the product body the hot loops use by default (F28_KARA,
+// F28_REDC_KARA): the peak roofline.valu divides by stays comparable with the kernels
 __global__ __launch_bounds__(256) void k_bench_f28mul(Fp* data, int iters) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   F28 x = f28_from_std(data[g]), y = f28_from_std(data[g + gridDim.x * blockDim.x]);

@@ -80,7 +80,8 @@ template <int CB> __global__ __launch_bounds__(64, 2) void k_late_fix(const Fr* 
 // S_t = sm[t m] are split (glv.hpp) and recoded once, their 32 n/m (t, copy) entries sorted by |digit| into `list`
 // (descending), and every lane adds ITS point of each entry, folding the running sum into its total once per magnitude.
 constexpr int LU_MAX_T = 128;                       // n / m <= 128
-// Product body: Karatsuba (the default); 256 VGPRs and 128 scratch bytes as with the schoolbook body, two waves per SIMD.
+// Product body: Karatsuba with the Karatsuba reduction (the default); 256 VGPRs, 128 scratch bytes and 47 spilled VGPRs as with the
+// r07 body, two waves per SIMD (profiles/r08_f28_redc_karatsuba.md).
 __global__ __launch_bounds__(64, 2) void k_late_uniform(const Fr* __restrict__ sm, size_t sstride, const TAff* __restrict__ ptab, size_t ptab_proof_stride, int NP,
                                                         const TAff* __restrict__ ctab, int nc, const uint32_t* __restrict__ gb_cols, int n, int m, int nfam,
                                                         int split, int waves, TJac* __restrict__ out, size_t fstride) {
@@ -230,7 +231,8 @@ __global__ __launch_bounds__(64) void k_late_tables(const TJac* __restrict__ jac
 // per proof the GPU would stand three quarters empty for its whole length): lane g = (p * nout + o) * slices + slice takes the
 // windows [slice * 32 / slices, (slice + 1) * 32 / slices) and leaves the partial sum out[g] of weight 2^(128 / slices * slice);
 // launch_msm_tail(group = slices, shift = 128 / slices) adds them up (and the round's single CRS term as an extra).
-// Product body: Karatsuba (the default), like k_late_fix: no scratch, two waves per SIMD (profiles/r07_f28_karatsuba.md).
+// Product body: Karatsuba with the Karatsuba reduction (the default), like k_late_fix: no scratch, two waves per SIMD
+// (profiles/r08_f28_redc_karatsuba.md).
 __global__ __launch_bounds__(64, 2) void k_late_msm(const LateRound r) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint32_t* dw = reinterpret_cast<uint32_t*>(smem);   // [2 hm * wph][64]: the lane's digit nibbles (biased by 7), word-interleaved by lane
