@@ -282,160 +282,173 @@ void Engine::run_smul(const std::vector<SmulTask>& tasks, int cnt, const S* scal
   wait_stream();   // staging buffer reuse safety
 }
 
-// raw lane accumulators of the MSM waves (kernels.h) and their reduction to partial sums in d_tpart_
-void Engine::ensure_raw_sets(size_t nsets) {
-  d_raw_.ensure(std::max<size_t>(nsets, 1) * raw_set_words());
-  d_rawslot_.ensure(std::max<size_t>(nsets, 1));
-  d_rawmid_.ensure(std::max<size_t>(nsets, 1) * reduce_mid_per_set());
-}
-void Engine::reduce_sets(size_t nplain, size_t nweighted, TJac* part) {
-  tick("k_reduce_sets", 0, (double)(nplain + nweighted), true);   // up to four launches (groups of 8 lanes, then the groups of a set; plain / bucket sets)
-  launch_reduce_sets(opt_, d_raw_.p, d_rawslot_.p, (int)nplain, (int)nweighted, d_rawmid_.p, part ? part : d_tpart_.p, stream_, (int)B_);
-  tock();
+// the raw lane accumulators of `sc` (kernels.h) reduced to partial sums, in sc.part unless told otherwise
+void Engine::reduce_sets(hipStream_t st, MsmScratch& sc, size_t nplain, size_t nweighted, TJac* part) {
+  const bool span = st == stream_;   // up to four launches (groups of 8 lanes, then the groups of a set; plain / bucket sets): a span is bracketed on the main stream, another stream's is not timed
+  if (span) tick("k_reduce_sets", 0, (double)(nplain + nweighted), true);
+  launch_reduce_sets(opt_, sc.raw.p, sc.rawslot.p, (int)nplain, (int)nweighted, sc.mid.p, part ? part : sc.part.p, st, (int)B_);
+  if (span) tock();
 }
 
 // Table-backed MSM phase: the CRS segments of a request go to k_msm_fix, the per-proof segments to k_msm_tblw (one
 // wave per task and window group); k_reduce_sets turns the raw lane accumulators into partial sums, k_finalize_ranges
-// adds them per request, normalises and compresses.
+// adds them per request, normalises, scatters the affine point and writes the compressed bytes to d_comp (slot
+// comp_index[i] of it where the per-request arrays carry one).  `sc` must hold sh.fix_sets + sh.tbl_sets sets and sh.nparts partial sums.
+void Engine::launch_tbl_phase(const TblShape& sh, const TblTask* d_tt, const FixTask* d_ft, const uint32_t* d_meta, uint8_t* d_comp, hipStream_t st, MsmScratch& sc,
+                              bool timed) {
+  if (!sh.nt) return;
+  Untimed quiet(this, timed);
+  uint32_t* const traw = sc.raw.p + sh.fix_sets * raw_set_words();
+  if (sh.one_launch) {   // a lone proof: both MSM kernels of the phase in one launch
+    tick("k_msm_fix_tblw", 128.0 * (sh.pts_fix + sh.pts_tbl), sh.pts_fix + sh.pts_tbl);
+    launch_msm_fix_tblw(d_ft, (int)sh.nft, fixtab(), (int)nc(), sc.raw.p, sc.rawslot.p, d_tt, (int)sh.ntt, sh.tbl_slices, traw, sc.rawslot.p + sh.fix_sets, st);
+    tock();
+  } else {
+    if (sh.nft) {
+      tick(fix_kernel_name(fix_bits_, sh.fix_wpw), 128.0 * sh.pts_fix, sh.pts_fix);
+      launch_msm_fix(d_ft, (int)sh.nft, fixtab(), fix_bits_, sh.fix_wpw, (int)nc(), sc.raw.p, sc.rawslot.p, st);
+      tock();
+    }
+    if (sh.ntt) {
+      tick(tblw_kernel_name(sh.tbl_wpw), 128.0 * sh.pts_tbl, sh.pts_tbl);
+      launch_msm_tblw(d_tt, (int)sh.ntt, sh.tbl_wpw, traw, sc.rawslot.p + sh.fix_sets, st, sh.tbl_slices);
+      tock();
+    }
+  }
+  reduce_sets(st, sc, sh.fix_sets, sh.tbl_sets);
+  const uint32_t* m = d_meta;
+  tick("k_finalize_ranges", 0, (double)sh.nt);
+  launch_finalize_ranges(opt_, sc.part.p, m, m + sh.nt, (int)sh.nt, d_pp_.p, m + 2 * sh.nt, d_comp, st, sh.any_add ? m + sh.add_offset() : nullptr, sh.has_comp ? m + 3 * sh.nt : nullptr);
+  tock();
+}
+
+// Plans a host-driven phase and brings it to the device: everything the phase's kernels read — scalars, task descriptors, partial
+// ranges, destinations, addends — is staged in ONE pinned buffer with the layout [Fr scalars | TblTask | FixTask | u32 arrays] and
+// uploaded with ONE copy into a device blob of the same layout (a handful of separate small copies cost ~30 us of host time per
+// phase, which a lone proof waits for); then the launches, on stream `st` in scratch `sc`; compressed results (48 B each, request order) in `comp`.
+void Engine::enqueue_tbl_phase(const std::vector<TblReq>& reqs, uint32_t dummy_dst, PinBuf<uint8_t>& stage, DevBuf<uint8_t>& blob, DevBuf<uint8_t>& comp, hipStream_t st,
+                               MsmScratch& sc, bool timed) {
+  const size_t nt = reqs.size();
+  TblShape sh;
+  const bool fix = fix_bits_ && fixtab();
+  const CrsRange crs{fix ? ctab() : nullptr, fix ? ctab() + (size_t)copies_ * nc() : nullptr};
+  tbl_count(reqs, crs, sh);
+  sh.fix_wpw = fix ? msm_fix_windows_per_wave(opt_, (int)sh.nft, fix_bits_) : 16;
+  sh.tbl_wpw = msm_tblw_windows_per_wave(opt_, (int)sh.ntt);   // windows per wave of the shifted-table kernel
+  sh.tbl_slices = msm_tblw_slices(opt_, (int)sh.ntt, sh.tbl_wpw, (int)sh.tbl_max_n);   // a lone proof: several waves share a task's points
+  sh.one_launch = sh.nft && sh.ntt && fix_bits_ == 16 && sh.fix_wpw == 2 && sh.tbl_wpw == 2;
+  const size_t b_scal = sh.nscal * sizeof(Fr), b_tt = sh.ntt * sizeof(TblTask), b_ft = sh.nft * sizeof(FixTask);
+  static_assert(sizeof(TblTask) % 8 == 0 && sizeof(FixTask) % 8 == 0 && sizeof(Fr) % 8 == 0, "blob sections keep pointer alignment");
+  const size_t b_blob = b_scal + b_tt + b_ft + 6 * nt * sizeof(uint32_t);
+  stage.ensure(b_blob);
+  blob.ensure(b_blob);
+  Fr* hs = reinterpret_cast<Fr*>(stage.p);
+  std::vector<size_t> soff(nt);
+  tbl_plan(reqs, crs, fix ? (uint32_t)msm_fix_parts(fix_bits_, sh.fix_wpw) : 0, (uint32_t)(msm_tblw_parts(sh.tbl_wpw) * sh.tbl_slices), dummy_dst,
+           reinterpret_cast<const Fr*>(blob.p), nullptr, sh, reinterpret_cast<TblTask*>(stage.p + b_scal), reinterpret_cast<FixTask*>(stage.p + b_scal + b_tt),
+           reinterpret_cast<uint32_t*>(stage.p + b_scal + b_tt + b_ft), soff.data());
+  parallel_for(nt, [&](size_t i) {
+    const TblReq& r = reqs[i];
+    if (r.dev) return;
+    Fr* d = hs + soff[i];
+    for (uint32_t j = 0; j < r.seg0.n; j++) d[j] = r.s0[j].f;
+    for (uint32_t j = 0; j < r.seg1.n; j++) d[r.seg0.n + j] = r.s1[j].f;
+  });
+  CPX_HIP(hipMemcpyAsync(blob.p, stage.p, b_blob, hipMemcpyHostToDevice, st));
+  comp.ensure(nt * 48);
+  sc.ensure(sh.fix_sets + sh.tbl_sets, sh.nparts);
+  launch_tbl_phase(sh, reinterpret_cast<const TblTask*>(blob.p + b_scal), reinterpret_cast<const FixTask*>(blob.p + b_scal + b_tt),
+                   reinterpret_cast<const uint32_t*>(blob.p + b_scal + b_tt + b_ft), comp.p, st, sc, timed);
+}
+
+// affine results are scattered to d_pp_[dst]; compressed results (48 B each, request order) returned if comp_out != null
 void Engine::run_tbl_phase(const std::vector<TblReq>& reqs, std::vector<uint8_t>* comp_out) {
   const size_t nt = reqs.size();
   if (!nt) return;
-  const bool fix = fix_bits_ && fixtab();
-  const TAff* c_lo = ctab();
-  const TAff* c_hi = ctab() + (size_t)copies_ * nc();
-  auto is_crs = [&](const TblSeg& sg) { return fix && sg.n && sg.base >= c_lo && sg.base < c_hi; };
-  auto needs_tbl = [&](const TblReq& r) { return !fix || (r.seg0.n && !is_crs(r.seg0)) || (r.seg1.n && !is_crs(r.seg1)); };
-  size_t ntt_total = 0, nft_total = 0;
-  for (const TblReq& r : reqs) {
-    ntt_total += needs_tbl(r) ? 1 : 0;
-    nft_total += (is_crs(r.seg0) ? 1 : 0) + (is_crs(r.seg1) ? 1 : 0);
-  }
-  const int fix_wpw = fix ? msm_fix_windows_per_wave(opt_, (int)nft_total, fix_bits_) : 16;
-  const uint32_t fix_parts = fix ? (uint32_t)msm_fix_parts(fix_bits_, fix_wpw) : 0;
-  const int tbl_wpw = msm_tblw_windows_per_wave(opt_, (int)ntt_total);   // windows per wave of the shifted-table kernel
-  uint32_t tbl_max_n = 0;
-  for (const TblReq& r : reqs)
-    if (needs_tbl(r)) tbl_max_n = std::max(tbl_max_n, (is_crs(r.seg0) ? 0u : r.seg0.n) + (is_crs(r.seg1) ? 0u : r.seg1.n));
-  const int tbl_slices = msm_tblw_slices(opt_, (int)ntt_total, tbl_wpw, (int)tbl_max_n);   // a lone proof: several waves share a task's points
-  const uint32_t tbl_parts = (uint32_t)(msm_tblw_parts(tbl_wpw) * tbl_slices);   // partial sums (2 per wave) per task
-  // layout: per request its scalars (seg0 then seg1); shifted-table tasks and fixed-base tasks; partial ranges
-  std::vector<size_t> soff(nt);
-  std::vector<uint32_t> pfirst(nt), pcount(nt), tt_index(nt, ~0u), ft_index(nt * 2, ~0u);
-  size_t total = 0, ntt = 0, nft = 0, nparts = 0;
-  double pts_tbl = 0, pts_fix = 0;
-  for (size_t i = 0; i < nt; i++) {
-    const TblReq& r = reqs[i];
-    soff[i] = total;
-    if (!r.dev) total += r.seg0.n + r.seg1.n;
-    pfirst[i] = (uint32_t)nparts;
-    const bool f0 = is_crs(r.seg0), f1 = is_crs(r.seg1);
-    if (needs_tbl(r)) {
-      tt_index[i] = (uint32_t)ntt++;
-      nparts += tbl_parts;
-    }
-    if (f0) {
-      ft_index[2 * i] = (uint32_t)nft++;
-      nparts += fix_parts;
-    }
-    if (f1) {
-      ft_index[2 * i + 1] = (uint32_t)nft++;
-      nparts += fix_parts;
-    }
-    pcount[i] = (uint32_t)nparts - pfirst[i];
-    pts_fix += (f0 ? r.seg0.n : 0) + (f1 ? r.seg1.n : 0);
-    pts_tbl += (f0 ? 0 : r.seg0.n) + (f1 ? 0 : r.seg1.n);
-  }
-  d_tpart_.ensure(nparts);
-  d_comp_.ensure(nt * 48);
-  // everything the phase's kernels read — scalars, task descriptors, partial ranges, destinations, addends — is staged in ONE pinned
-  // buffer with the layout [Fr scalars | TblTask | FixTask | u32 arrays] and uploaded with ONE copy into a device blob of the same
-  // layout (a handful of separate small copies cost ~30 us of host time per phase, which a lone proof waits for)
-  const size_t b_scal = total * sizeof(Fr), b_tt = ntt * sizeof(TblTask), b_ft = nft * sizeof(FixTask);
-  static_assert(sizeof(TblTask) % 8 == 0 && sizeof(FixTask) % 8 == 0 && sizeof(Fr) % 8 == 0, "blob sections keep pointer alignment");
-  bool any_add = false;
-  for (const TblReq& r : reqs) any_add |= r.add[0] != ~0u;
-  const size_t b_blob = b_scal + b_tt + b_ft + 6 * nt * sizeof(uint32_t);
-  h_stage_.ensure(b_blob);
-  d_blob_.ensure(b_blob);
-  Fr* const d_scal = reinterpret_cast<Fr*>(d_blob_.p);
-  TblTask* const d_tt = reinterpret_cast<TblTask*>(d_blob_.p + b_scal);
-  FixTask* const d_ft = reinterpret_cast<FixTask*>(d_blob_.p + b_scal + b_tt);
-  uint32_t* const d_u32 = reinterpret_cast<uint32_t*>(d_blob_.p + b_scal + b_tt + b_ft);
-  const uint32_t dummy_dst = slot_index(0, SlotMap(L_).TMP(7));   // results nobody reads land in a scratch slot
-  Fr* hs = reinterpret_cast<Fr*>(h_stage_.p);
-  TblTask* ht = reinterpret_cast<TblTask*>(h_stage_.p + b_scal);
-  FixTask* hf = reinterpret_cast<FixTask*>(h_stage_.p + b_scal + b_tt);
-  uint32_t* hp = reinterpret_cast<uint32_t*>(h_stage_.p + b_scal + b_tt + b_ft);
-  const TblSeg none{nullptr, nullptr, 0, 0};
-  parallel_for(nt, [&](size_t i) {
-    const TblReq& r = reqs[i];
-    const Fr* sbase = r.dev ? r.dev : d_scal + soff[i];   // where this request's scalars are (or will be) on the device
-    if (!r.dev) {
-      Fr* d = hs + soff[i];
-      for (uint32_t j = 0; j < r.seg0.n; j++) d[j] = r.s0[j].f;
-      for (uint32_t j = 0; j < r.seg1.n; j++) d[r.seg0.n + j] = r.s1[j].f;
-    }
-    const bool f0 = is_crs(r.seg0), f1 = is_crs(r.seg1);
-    uint32_t slot = pfirst[i];
-    if (tt_index[i] != ~0u) {
-      TblTask t;
-      // the shifted-table task keeps the scalar layout of the request; fixed-base segments are emptied
-      t.seg[0] = f0 ? TblSeg{r.seg0.base, r.seg0.idx, r.seg0.copy_stride, 0} : r.seg0;
-      t.seg[1] = f1 ? none : r.seg1;
-      t.scalars = sbase + (f0 ? r.seg0.n : 0);
-      if (f0) {   // seg0 removed: its scalars are skipped, seg1 becomes the only segment
-        t.seg[0] = f1 ? none : r.seg1;
-        t.seg[1] = none;
-      }
-      t.flags = 0;
-      t.pad = slot;
-      t.digits = nullptr;
-      ht[tt_index[i]] = t;
-      slot += tbl_parts;
-    }
-    if (f0) {
-      hf[ft_index[2 * i]] = FixTask{r.seg0.idx, sbase, (uint32_t)(r.seg0.base - c_lo), r.seg0.n, 0, slot};
-      slot += fix_parts;
-    }
-    if (f1) {
-      hf[ft_index[2 * i + 1]] = FixTask{r.seg1.idx, sbase + r.seg0.n, (uint32_t)(r.seg1.base - c_lo), r.seg1.n, 0, slot};
-      slot += fix_parts;
-    }
-    hp[i] = pfirst[i];
-    hp[nt + i] = pcount[i];
-    hp[2 * nt + i] = r.dst != ~0u ? r.dst : dummy_dst;
-    for (int j = 0; j < 3; j++) hp[3 * nt + 3 * i + j] = r.add[j];
-  });
-  CPX_HIP(hipMemcpyAsync(d_blob_.p, h_stage_.p, b_blob, hipMemcpyHostToDevice, stream_));
-  const size_t fix_sets = nft * fix_parts, tbl_sets = ntt * tbl_parts;   // raw sets: [fixed-base waves | bucket sets of the table waves]
-  ensure_raw_sets(fix_sets + tbl_sets);
-  if (nft && ntt && fix_bits_ == 16 && fix_wpw == 2 && tbl_wpw == 2) {   // a lone proof: both MSM kernels of the phase in one launch
-    tick("k_msm_fix_tblw", 128.0 * (pts_fix + pts_tbl), pts_fix + pts_tbl);
-    launch_msm_fix_tblw(d_ft, (int)nft, fixtab(), (int)nc(), d_raw_.p, d_rawslot_.p, d_tt, (int)ntt, tbl_slices, d_raw_.p + fix_sets * raw_set_words(),
-                        d_rawslot_.p + fix_sets, stream_);
-    tock();
-  } else {
-  if (nft) {
-    tick(fix_kernel_name(fix_bits_, fix_wpw), 128.0 * pts_fix, pts_fix);
-    launch_msm_fix(d_ft, (int)nft, fixtab(), fix_bits_, fix_wpw, (int)nc(), d_raw_.p, d_rawslot_.p, stream_);
-    tock();
-  }
-  if (ntt) {
-    tick(tblw_kernel_name(tbl_wpw), 128.0 * pts_tbl, pts_tbl);
-    launch_msm_tblw(d_tt, (int)ntt, tbl_wpw, d_raw_.p + fix_sets * raw_set_words(), d_rawslot_.p + fix_sets, stream_, tbl_slices);
-    tock();
-  }
-  }
-  reduce_sets(fix_sets, tbl_sets);
-  tick("k_finalize_ranges", 0, (double)nt);
-  launch_finalize_ranges(opt_, d_tpart_.p, d_u32, d_u32 + nt, (int)nt, d_pp_.p, d_u32 + 2 * nt, d_comp_.p, stream_, any_add ? d_u32 + 3 * nt : nullptr);
-  tock();
+  enqueue_tbl_phase(reqs, slot_index(0, SlotMap(L_).TMP(7)), h_stage_, d_blob_, d_comp_, stream_, main_, true);   // results nobody reads land in a scratch slot
   if (comp_out) {
     h_comp_.ensure(nt * 48);
     CPX_HIP(hipMemcpyAsync(h_comp_.p, d_comp_.p, nt * 48, hipMemcpyDeviceToHost, stream_));
     wait_stream();
     comp_out->assign(h_comp_.p, h_comp_.p + nt * 48);
   }
+}
+
+// R = a x vec_R, S = a x vec_S (curdleproofs.rs:112-113) and whatever further tasks over the same points side_.tasks holds: the
+// endomorphism bucket-list kernel (pairs: R and S of a proof share the scalars vec_a — one wave per (proof, window) serves both,
+// kernels.h launch_msm_endo_pairs), reduction and Horner tail in the side scratch on stream `st`; the first nfinal results go to
+// their slots (side_.dst)
+void Engine::launch_rs(size_t ntasks, size_t nfinal, int slices, bool pairs, hipStream_t st, bool timed) {
+  Untimed quiet(this, timed);
+  MsmScratch& sc = side_.scr;
+  tick(pairs ? "k_msm_tblw_pair" : "k_msm_tblw<2, true>", 128.0 * ntasks * ell_, (double)(ntasks * ell_));
+  if (pairs) launch_msm_endo_pairs(side_.tasks.p, (int)(ntasks / 2), (int)ell_, side_.conv.p, side_.digits.p, side_.ttasks.p, sc.raw.p, sc.rawslot.p, st);
+  else launch_msm_endo(side_.tasks.p, (int)ntasks, (int)ell_, side_.conv.p, side_.digits.p, side_.ttasks.p, sc.raw.p, sc.rawslot.p, st, slices);
+  tock();
+  reduce_sets(st, sc, 0, ntasks * 32 * slices);
+  tick("k_msm_tail", 0, (double)ntasks);
+  launch_msm_tail(opt_, sc.part.p, nullptr, side_.res.p, (int)ntasks, 16, 8, st, nullptr, 0, 2 * slices);
+  tock();
+  launch_finalize(side_.res.p, (int)nfinal, d_pp_.p, side_.dst.p, nullptr, st);
+}
+
+// The verifier's accumulated check of every proof as ONE sum: the CRS part on the fixed-base table (d_ft: one task of n scalars per
+// proof, fix_parts partial sums each), all the per-proof points (d_mt: R | S | T | U and the slots, NPT per proof; used once, so no
+// shifted tables — endomorphism split + radix-256 buckets per window) in one bucket MSM; the Horner tail adds the two.  The compressed
+// sums arrive in h_comp_: check_passed(p) once the caller has waited for the stream.
+void Engine::launch_check(const MsmTask* d_mt, const FixTask* d_ft, size_t B, size_t NPT, int fix_wpw, int fix_parts, size_t slices) {
+  d_conv_.ensure(2 * B * NPT);   // points and their endomorphism images
+  d_digits_.ensure(9 * B * NPT);
+  d_ttasks_.ensure(B);
+  d_part_.ensure(B * 32 * slices);
+  d_res_.ensure(B);
+  d_comp_.ensure(B * 48);
+  h_comp_.ensure(B * 48);
+  main_.ensure(B * std::max<size_t>(fix_parts, 32 * slices), B * (size_t)fix_parts);
+  tick(fix_kernel_name(fix_bits_, fix_wpw), 128.0 * n_ * B, (double)(n_ * B));
+  launch_msm_fix(d_ft, (int)B, fixtab(), fix_bits_, fix_wpw, (int)nc(), main_.raw.p, main_.rawslot.p, stream_);
+  tock();
+  reduce_sets(stream_, main_, B * fix_parts, 0);
+  tick("k_msm_tblw<2, true>", 128.0 * NPT * B, (double)(NPT * B));
+  launch_msm_endo(d_mt, (int)B, (int)NPT, d_conv_.p, d_digits_.p, d_ttasks_.p, main_.raw.p, main_.rawslot.p, stream_, (int)slices);
+  tock();
+  reduce_sets(stream_, main_, 0, B * 32 * slices, d_part_.p);
+  tick("k_msm_tail", 0, (double)B);
+  launch_msm_tail(opt_, d_part_.p, nullptr, d_res_.p, (int)B, 16, 8, stream_, main_.part.p, fix_parts, (int)(2 * slices));
+  tock();
+  tick("k_finalize", 0, (double)B);
+  launch_finalize(d_res_.p, (int)B, nullptr, nullptr, d_comp_.p, stream_);
+  tock();
+  CPX_HIP(hipMemcpyAsync(h_comp_.p, d_comp_.p, B * 48, hipMemcpyDeviceToHost, stream_));
+}
+
+// BASELINE config 5: one MSM over the CRS (d_ft: ONE task, the scalars summed over the proofs) and the N = B * NPT per-proof points
+// of NT groups of G proofs (d_gt) through the endomorphism bucket-list kernel (32 additions per point like the per-proof verifier,
+// but one bucket reduction and one Horner tail per GROUP of proofs), then two plain summation levels; the last one adds the
+// fixed-base part and hands the sum over in the standard form: a Jac in h_comp_.
+void Engine::launch_check_fused(const MsmTask* d_gt, const FixTask* d_ft, size_t NT, size_t G, size_t NPT, size_t N, int fix_wpw, int fix_parts) {
+  const size_t NT16 = (NT + 15) / 16 * 16;
+  d_ttasks_.ensure(NT);
+  d_conv_.ensure(2 * N);
+  d_digits_.ensure(9 * N);
+  d_part_.ensure(NT * 32);
+  d_wsum_.ensure(NT16 + NT16 / 16);
+  d_res_.ensure(1);
+  h_comp_.ensure(sizeof(Jac));
+  main_.ensure(std::max<size_t>(NT * 32, fix_parts), fix_parts);
+  launch_msm_fix(d_ft, 1, fixtab(), fix_bits_, fix_wpw, (int)nc(), main_.raw.p, main_.rawslot.p, stream_);
+  reduce_sets(stream_, main_, fix_parts, 0);
+  CPX_HIP(hipMemsetAsync(d_wsum_.p, 0, (NT16 + NT16 / 16) * sizeof(TJac), stream_));   // all-zero = identity: pads the summation levels
+  tick("k_msm_tblw<2, true>", 128.0 * N, (double)N);
+  launch_msm_endo(d_gt, (int)NT, (int)(G * NPT), d_conv_.p, d_digits_.p, d_ttasks_.p, main_.raw.p, main_.rawslot.p, stream_);
+  tock();
+  reduce_sets(stream_, main_, 0, NT * 32, d_part_.p);
+  tick("k_msm_tail", 0, (double)NT, true);
+  launch_msm_tail(opt_, d_part_.p, d_wsum_.p, nullptr, (int)NT, 16, 8, stream_, nullptr, 0, 2);                            // windows of a group
+  launch_msm_tail(opt_, d_wsum_.p, d_wsum_.p + NT16, nullptr, (int)(NT16 / 16), 16, 0, stream_);                           // 16 groups each
+  launch_msm_tail(opt_, d_wsum_.p + NT16, nullptr, d_res_.p, 1, (int)(NT16 / 16), 0, stream_, main_.part.p, fix_parts);    // + the fixed-base part
+  tock();
+  CPX_HIP(hipMemcpyAsync(h_comp_.p, d_res_.p, sizeof(Jac), hipMemcpyDeviceToHost, stream_));
 }
 
 // ---------------------------------------------------------------- CRS
@@ -614,11 +627,11 @@ void Engine::msm(const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t
     tt.ensure(1);
     part.ensure(32 * (size_t)slices);
     dig.ensure(9 * n);
-    ensure_raw_sets(32 * (size_t)slices);
+    main_.ensure(32 * (size_t)slices, 0);
     tick("k_msm_tblw<2, true>", 128.0 * n, (double)n);
-    launch_msm_endo(dt.p, 1, (int)n, conv.p, dig.p, tt.p, d_raw_.p, d_rawslot_.p, stream_, slices);
+    launch_msm_endo(dt.p, 1, (int)n, conv.p, dig.p, tt.p, main_.raw.p, main_.rawslot.p, stream_, slices);
     tock();
-    reduce_sets(0, 32 * (size_t)slices, part.p);
+    reduce_sets(stream_, main_, 0, 32 * (size_t)slices, part.p);
     launch_msm_tail(opt_, part.p, nullptr, res.p, 1, 16, 8, stream_, nullptr, 0, 2 * slices);
     CPX_HIP(hipMemcpyAsync(out_jac, res.p, sizeof(Jac), hipMemcpyDeviceToHost, stream_));
     CPX_HIP(hipStreamSynchronize(stream_));   // the result is in out_jac; the scratch may be reused by the next call
@@ -1117,60 +1130,24 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     CPX_HIP(hipMemcpyAsync(side_.scal.p, hs, 3 * total * sizeof(Fr), hipMemcpyHostToDevice, sside));
     CPX_HIP(hipMemcpyAsync(side_.tasks.p, ht, nt * sizeof(MsmTask), hipMemcpyHostToDevice, sside));
     CPX_HIP(hipMemcpyAsync(side_.dst.p, hd, 2 * nt * sizeof(uint32_t), hipMemcpyHostToDevice, sside));
-    const size_t slices = (size_t)msm_tblw_slices(opt_, (int)nt, 2, (int)ell), nsets = nt * 32 * slices;
+    const int slices = msm_tblw_slices(opt_, (int)nt, 2, (int)ell);
     side_.conv.ensure(2 * nt * ell);   // per task: points and images
     side_.ttasks.ensure(nt);
     side_.digits.ensure(9 * nt * ell);
-    side_.raw.ensure(nsets * raw_set_words());
-    side_.rawslot.ensure(nsets);
-    side_.mid.ensure(nsets * reduce_mid_per_set());
-    side_.part.ensure(nsets);
-    launch_msm_endo(side_.tasks.p, (int)nt, (int)ell, side_.conv.p, side_.digits.p, side_.ttasks.p, side_.raw.p, side_.rawslot.p, sside, (int)slices);
-    launch_reduce_sets(opt_, side_.raw.p, side_.rawslot.p, 0, (int)nsets, side_.mid.p, side_.part.p, sside, (int)B);
-    launch_msm_tail(opt_, side_.part.p, nullptr, side_.res.p, (int)nt, 16, 8, sside, nullptr, 0, (int)(2 * slices));
-    launch_finalize(side_.res.p, (int)(2 * B), d_pp_.p, side_.dst.p, nullptr, sside);
+    side_.scr.ensure(nt * 32 * slices, nt * 32 * slices);
+    launch_rs(nt, 2 * B, slices, false, sside, false);
   }
 
   // -- table stream: B_t = msm(T_b, vec_r), B_u = msm(U_b, vec_r) (same_multiscalar_argument.rs:81-82) right behind the tables of T and U
   {
     const size_t nt = 2 * B;
-    const int wpw = msm_tblw_windows_per_wave(opt_, (int)nt), tslices = msm_tblw_slices(opt_, (int)nt, wpw, (int)n);
-    const uint32_t parts = (uint32_t)(msm_tblw_parts(wpw) * tslices);
-    const size_t b_scal = B * n * sizeof(Fr), b_tt = nt * sizeof(TblTask), b_blob = b_scal + b_tt + 3 * nt * sizeof(uint32_t);
-    tab_.blob.ensure(b_blob);
-    tab_.stage.ensure(b_blob);
-    tab_.raw.ensure(nt * parts * raw_set_words());
-    tab_.rawslot.ensure(nt * parts);
-    tab_.mid.ensure(nt * parts * reduce_mid_per_set());
-    tab_.part.ensure(nt * parts);
-    tab_.comp.ensure(nt * 48);
-    tab_.hcomp.ensure(nt * 48);
-    Fr* hs = reinterpret_cast<Fr*>(tab_.stage.p);
-    TblTask* ht = reinterpret_cast<TblTask*>(tab_.stage.p + b_scal);
-    uint32_t* hu = reinterpret_cast<uint32_t*>(tab_.stage.p + b_scal + b_tt);
-    const Fr* d_scal = reinterpret_cast<const Fr*>(tab_.blob.p);
-    const uint32_t dummy_dst = slot_index(0, sm.TMP(7));
+    std::vector<TblReq> reqs;
     for (size_t p = 0; p < B; p++) {
-      for (size_t i = 0; i < n; i++) hs[p * n + i] = st[p].scal[1][i].f;
-      for (int q = 0; q < 2; q++) {
-        TblTask t;
-        t.seg[0] = pseg(p, q ? row.U() : row.T(), (uint32_t)n);
-        t.seg[1] = none;
-        t.scalars = d_scal + p * n;
-        t.flags = 0;
-        t.pad = (uint32_t)((2 * p + q) * parts);
-        t.digits = nullptr;
-        ht[2 * p + q] = t;
-        hu[2 * p + q] = (uint32_t)((2 * p + q) * parts);
-        hu[nt + 2 * p + q] = parts;
-        hu[2 * nt + 2 * p + q] = dummy_dst;
-      }
+      reqs.push_back({pseg(p, row.T(), (uint32_t)n), st[p].scal[1].data(), none, nullptr});
+      reqs.push_back({pseg(p, row.U(), (uint32_t)n), st[p].scal[1].data(), none, nullptr});
     }
-    CPX_HIP(hipMemcpyAsync(tab_.blob.p, tab_.stage.p, b_blob, hipMemcpyHostToDevice, tab_.stream));
-    const uint32_t* d_u32 = reinterpret_cast<const uint32_t*>(tab_.blob.p + b_scal + b_tt);
-    launch_msm_tblw(reinterpret_cast<const TblTask*>(tab_.blob.p + b_scal), (int)nt, wpw, tab_.raw.p, tab_.rawslot.p, tab_.stream, tslices);
-    launch_reduce_sets(opt_, tab_.raw.p, tab_.rawslot.p, 0, (int)(nt * parts), tab_.mid.p, tab_.part.p, tab_.stream, (int)B);
-    launch_finalize_ranges(opt_, tab_.part.p, d_u32, d_u32 + nt, (int)nt, d_pp_.p, d_u32 + 2 * nt, tab_.comp.p, tab_.stream);
+    enqueue_tbl_phase(reqs, slot_index(0, sm.TMP(7)), tab_.stage, tab_.blob, tab_.comp, tab_.stream, tab_.scr, false);
+    tab_.hcomp.ensure(nt * 48);
     CPX_HIP(hipMemcpyAsync(tab_.hcomp.p, tab_.comp.p, nt * 48, hipMemcpyDeviceToHost, tab_.stream));
     CPX_HIP(hipEventRecord(tab_.ev_done, tab_.stream));
   }
@@ -1639,7 +1616,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     wait_side();
   }
 
-  const uint8_t ID0 = 0xc0;
+  const uint8_t ID0 = kCompIdentity;
   std::vector<uint8_t> comp;
 
   // -- V1a: transcript up to the grand-product beta
@@ -1907,9 +1884,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     const int fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
     d_scal_.ensure(N + n);
     d_big_idx_.ensure(N);
-    d_tpart_.ensure(fix_parts);
     d_ftasks_.ensure(1);
-    d_res_.ensure(1);
     const size_t b_scal = (N + n) * sizeof(Fr), b_idx = N * sizeof(uint32_t);
     h_stage_.ensure(b_scal + b_idx + sizeof(FixTask));
     Fr* hs = reinterpret_cast<Fr*>(h_stage_.p);
@@ -1933,41 +1908,16 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     CPX_HIP(hipMemcpyAsync(d_scal_.p, hs, b_scal, hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(d_big_idx_.p, hi, b_idx, hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(d_ftasks_.p, hf, sizeof(FixTask), hipMemcpyHostToDevice, stream_));
-    ensure_raw_sets(fix_parts);
-    launch_msm_fix(d_ftasks_.p, 1, fixtab(), fix_bits_, fix_wpw, (int)nc(), d_raw_.p, d_rawslot_.p, stream_);
-    reduce_sets(fix_parts, 0);
-    {
-      // The per-proof points of up to 256 groups of proofs through the endomorphism bucket-list kernel (32 additions per
-      // point like the per-proof verifier, but one bucket reduction and one Horner tail per GROUP of proofs), then two
-      // plain summation levels; the last one adds the fixed-base part and hands the sum over in the standard form.
-      const size_t G = (B + 255) / 256, NT = (B + G - 1) / G, NT16 = (NT + 15) / 16 * 16;
-      d_tasks_.ensure(NT);
-      d_ttasks_.ensure(NT);
-      d_conv_.ensure(2 * N);
-      d_digits_.ensure(9 * N);
-      d_part_.ensure(NT * 32);
-      d_wsum_.ensure(NT16 + NT16 / 16);
-      ensure_raw_sets(std::max<size_t>(NT * 32, fix_parts));
-      std::vector<MsmTask> mt(NT);
-      for (size_t g = 0; g < NT; g++) {
-        const size_t off = g * G * NPT, np = std::min(G, B - g * G) * NPT;
-        mt[g] = MsmTask{d_pp_.p, d_big_idx_.p + off, d_scal_.p + off, (uint32_t)np, 0, (uint32_t)off};
-      }
-      CPX_HIP(hipMemcpyAsync(d_tasks_.p, mt.data(), NT * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemsetAsync(d_wsum_.p, 0, (NT16 + NT16 / 16) * sizeof(TJac), stream_));   // all-zero = identity: pads the summation levels
-      tick("k_msm_tblw<2, true>", 128.0 * N, (double)N);
-      launch_msm_endo(d_tasks_.p, (int)NT, (int)(G * NPT), d_conv_.p, d_digits_.p, d_ttasks_.p, d_raw_.p, d_rawslot_.p, stream_);
-      tock();
-      reduce_sets(0, NT * 32, d_part_.p);
-      tick("k_msm_tail", 0, (double)NT, true);
-      launch_msm_tail(opt_, d_part_.p, d_wsum_.p, nullptr, (int)NT, 16, 8, stream_, nullptr, 0, 2);                      // windows of a group
-      launch_msm_tail(opt_, d_wsum_.p, d_wsum_.p + NT16, nullptr, (int)(NT16 / 16), 16, 0, stream_);                     // 16 groups each
-      launch_msm_tail(opt_, d_wsum_.p + NT16, nullptr, d_res_.p, 1, (int)(NT16 / 16), 0, stream_, d_tpart_.p, fix_parts);   // + the fixed-base part
-      tock();
-      CPX_HIP(hipStreamSynchronize(stream_));   // mt (host) was copied asynchronously
+    // the per-proof points in up to 256 groups of proofs, every group one task of the endomorphism bucket-list kernel
+    const size_t G = (B + 255) / 256, NT = (B + G - 1) / G;
+    d_tasks_.ensure(NT);
+    std::vector<MsmTask> mt(NT);   // (copied asynchronously: alive until the wait below)
+    for (size_t g = 0; g < NT; g++) {
+      const size_t off = g * G * NPT, np = std::min(G, B - g * G) * NPT;
+      mt[g] = MsmTask{d_pp_.p, d_big_idx_.p + off, d_scal_.p + off, (uint32_t)np, 0, (uint32_t)off};
     }
-    h_comp_.ensure(sizeof(Jac));
-    CPX_HIP(hipMemcpyAsync(h_comp_.p, d_res_.p, sizeof(Jac), hipMemcpyDeviceToHost, stream_));
+    CPX_HIP(hipMemcpyAsync(d_tasks_.p, mt.data(), NT * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+    launch_check_fused(d_tasks_.p, d_ftasks_.p, NT, G, NPT, N, fix_wpw, fix_parts);
     wait_stream();
     memcpy(fused_partial, h_comp_.p, sizeof(Jac));
     if (fused_invalid) *fused_invalid = invalid;
@@ -1991,14 +1941,6 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     d_scal_.ensure(total);
     d_tasks_.ensure(B);
     d_ftasks_.ensure(B);
-    d_conv_.ensure(2 * B * NPT);   // points and their endomorphism images
-    d_digits_.ensure(9 * B * NPT);
-    d_ttasks_.ensure(B);
-    d_part_.ensure(B * 32 * slices);
-    d_tpart_.ensure(B * (size_t)fix_parts);
-    d_res_.ensure(B);
-    d_comp_.ensure(B * 48);
-    ensure_raw_sets(B * std::max<size_t>(fix_parts, 32 * slices));
     const size_t b_scal = total * sizeof(Fr), b_mt = B * sizeof(MsmTask), b_ft = B * sizeof(FixTask);
     h_stage_.ensure(b_scal + b_mt + b_ft);
     Fr* hs = reinterpret_cast<Fr*>(h_stage_.p);
@@ -2016,29 +1958,11 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     CPX_HIP(hipMemcpyAsync(d_scal_.p, hs, b_scal, hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(d_tasks_.p, hm, b_mt, hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(d_ftasks_.p, hf, b_ft, hipMemcpyHostToDevice, stream_));
-    tick(fix_kernel_name(fix_bits_, fix_wpw), 128.0 * n * B,
-         (double)(n * B));
-    launch_msm_fix(d_ftasks_.p, (int)B, fixtab(), fix_bits_, fix_wpw, (int)nc(), d_raw_.p, d_rawslot_.p, stream_);
-    tock();
-    reduce_sets(B * fix_parts, 0);
-    // per-proof points: used once, so no shifted tables — endomorphism split + radix-256 buckets per window
-    tick("k_msm_tblw<2, true>", 128.0 * NPT * B, (double)(NPT * B));
-    launch_msm_endo(d_tasks_.p, (int)B, (int)NPT, d_conv_.p, d_digits_.p, d_ttasks_.p, d_raw_.p, d_rawslot_.p, stream_, (int)slices);
-    tock();
-    reduce_sets(0, B * 32 * slices, d_part_.p);
-    tick("k_msm_tail", 0, (double)B);
-    launch_msm_tail(opt_, d_part_.p, nullptr, d_res_.p, (int)B, 16, 8, stream_, d_tpart_.p, fix_parts, (int)(2 * slices));
-    tock();
-    tick("k_finalize", 0, (double)B);
-    launch_finalize(d_res_.p, (int)B, nullptr, nullptr, d_comp_.p, stream_);
-    tock();
-    h_comp_.ensure(B * 48);
-    CPX_HIP(hipMemcpyAsync(h_comp_.p, d_comp_.p, B * 48, hipMemcpyDeviceToHost, stream_));
+    launch_check(d_tasks_.p, d_ftasks_.p, B, NPT, fix_wpw, fix_parts, slices);
     wait_stream();
     for (size_t p = 0; p < B; p++) {
       const VState& s = st[p];
-      const bool ok = h_comp_.p[p * 48] == ID0;
-      verdict[p] = s.bad ? CPX_ERR_DESERIALIZE : ((s.reject || !ok) ? CPX_ERR_VERIFY : CPX_OK);
+      verdict[p] = s.bad ? CPX_ERR_DESERIALIZE : ((s.reject || !check_passed(p)) ? CPX_ERR_VERIFY : CPX_OK);
     }
   }
   flush_timers();

@@ -24,6 +24,7 @@
 #include "host_threads.hpp"
 #include "kernels.h"
 #include "protocol.h"
+#include "tbl_plan.hpp"
 
 namespace cpx {
 
@@ -126,6 +127,21 @@ inline const char* tblw_kernel_name(int wpw) {
 
 void trace_scalar(const char* name, const Fr& x);   // CPX_TRACE=1 debugging aid (engine_device.cpp)
 
+// Scratch of one stream's MSM launches: the raw lane accumulators of k_msm_tblw / k_msm_fix and the partial-sum slot of every set
+// (kernels.h), the group sums between the two reduction launches, and the partial sums the reduction leaves.  Together with its stream
+// it says where a phase runs.
+struct MsmScratch {
+  DevBuf<uint32_t> raw, rawslot;
+  DevBuf<TJac> mid, part;
+  void ensure(size_t nsets, size_t nparts) {
+    nsets = std::max<size_t>(nsets, 1);
+    raw.ensure(nsets * raw_set_words());
+    rawslot.ensure(nsets);
+    mid.ensure(nsets * reduce_mid_per_set());
+    part.ensure(std::max<size_t>(nparts, 1));
+  }
+};
+
 class Engine {
  public:
   explicit Engine(int device);
@@ -201,16 +217,6 @@ class Engine {
     uint32_t n;
     uint32_t dst;             // index into d_pp_ (Aff units) receiving the affine result
   };
-  // table-backed MSM request: up to two base segments, each with its own host scalar vector
-  struct TblReq {
-    TblSeg seg0;
-    const host::S* s0;
-    TblSeg seg1;
-    const host::S* s1;
-    uint32_t dst = ~0u;       // optional: index into d_pp_ receiving the affine result
-    const Fr* dev = nullptr;  // optional: the seg0.n + seg1.n scalars already sit in device memory (s0 / s1 unused)
-    uint32_t add[3] = {~0u, ~0u, ~0u};   // optional: d_pp_ indices of affine points of earlier phases added with coefficient 1
-  };
   // second stream + private staging for work that is off the critical path of the phase sequence
   struct SideBufs {
     hipStream_t stream = nullptr;
@@ -221,9 +227,9 @@ class Engine {
     DevBuf<MsmTask> tasks;
     DevBuf<SmulTask> stasks;
     DevBuf<Fr> scal;
-    DevBuf<TJac> part, mid;
+    MsmScratch scr;
     DevBuf<TblTask> ttasks;
-    DevBuf<uint32_t> raw, rawslot, digits;
+    DevBuf<uint32_t> digits;
     DevBuf<TAff> conv;
     DevBuf<Jac> res;
     DevBuf<uint32_t> dst;
@@ -238,10 +244,9 @@ class Engine {
     hipStream_t stream = nullptr;
     hipStream_t dstream = nullptr;   // the device-resident prover's table stream (plain): table build + B_t, B_u beside phase 1 (engine_device.cpp)
     hipEvent_t ev_start = nullptr, ev_m = nullptr, ev_done = nullptr;   // M finalised (main) / M's table row built / B_t, B_u compressed
-    DevBuf<uint8_t> blob;      // vec_r scalars | TblTask | first | count | dst
+    DevBuf<uint8_t> blob;      // scalars | TblTask | per-request arrays (enqueue_tbl_phase)
     PinBuf<uint8_t> stage;
-    DevBuf<uint32_t> raw, rawslot;
-    DevBuf<TJac> mid, part;
+    MsmScratch scr;
     DevBuf<uint8_t> comp;
     PinBuf<uint8_t> hcomp;
   };
@@ -263,11 +268,7 @@ class Engine {
   bool have_gen_ = false;
   std::vector<Aff> crs_host_;   // the ell + 7 CRS points (host copy: M of the Whisk shuffle is an MSM over vec_G | vec_H)
   // ---- device-resident batch prover / verifier (engine_device.cpp) ----
-  struct TblPlan {   // task descriptors of one table-backed MSM phase whose scalars live in device memory, built once
-    size_t nt = 0, ntt = 0, nft = 0, nparts = 0, fix_sets = 0, tbl_sets = 0;
-    int fix_wpw = 16, tbl_wpw = 32;
-    double pts_fix = 0, pts_tbl = 0;
-    bool any_add = false;
+  struct TblPlan : TblShape {   // task descriptors of one table-backed MSM phase whose scalars live in device memory, built once
     bool table_stream = false;   // runs beside the main stream's plans (phase 1t): its own write-only dummy slot
     bool combined = false;       // fused SameMSM rounds: wave w of a proof runs fixed-base block w and table block w (RoundDev::combine)
     bool keep_order = false;     // tasks stay in request (= proof-major) order: the fused round kernels address them by proof (round.hip)
@@ -356,13 +357,33 @@ class Engine {
   void verify_core_device(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid);
   void build_plan(TblPlan& pl, const std::vector<TblReq>& reqs, const std::vector<uint32_t>& comp_index);
   void exec_plan(const TblPlan& pl, uint8_t* d_comp_registry, bool on_table_stream = false);
+  // the launches of one table-backed phase (fixed-base kernel, table kernel, reduction, k_finalize_ranges) on stream `st` in scratch `sc`;
+  // timed = false: none of them enters the statistics
+  void launch_tbl_phase(const TblShape& sh, const TblTask* d_tt, const FixTask* d_ft, const uint32_t* d_meta, uint8_t* d_comp, hipStream_t st, MsmScratch& sc,
+                        bool timed = true);
+  // host-driven form: plans `reqs`, stages scalars, tasks and per-request arrays in ONE pinned buffer, uploads it with ONE copy and launches
+  void enqueue_tbl_phase(const std::vector<TblReq>& reqs, uint32_t dummy_dst, PinBuf<uint8_t>& stage, DevBuf<uint8_t>& blob, DevBuf<uint8_t>& comp, hipStream_t st,
+                         MsmScratch& sc, bool timed);
+  // R = a x vec_R, S = a x vec_S (and whatever further tasks side_.tasks holds) through the endomorphism bucket-list kernel on stream `st`;
+  // the first nfinal results go to their slots (side_.dst)
+  void launch_rs(size_t ntasks, size_t nfinal, int slices, bool pairs, hipStream_t st, bool timed);
+  // the verifier's accumulated check, per proof and fused (config 5), up to the device-to-host copy of the result into h_comp_
+  void launch_check(const MsmTask* d_mt, const FixTask* d_ft, size_t B, size_t NPT, int fix_wpw, int fix_parts, size_t slices);
+  void launch_check_fused(const MsmTask* d_gt, const FixTask* d_ft, size_t NT, size_t G, size_t NPT, size_t N, int fix_wpw, int fix_parts);
+  static constexpr uint8_t kCompIdentity = 0xc0;   // first byte of the compressed identity: what the accumulated check of a valid proof sums to
+  bool check_passed(size_t p) const { return h_comp_.p[p * 48] == kCompIdentity; }
+  struct Untimed {   // keeps a launch sequence out of the statistics
+    bool& on;
+    const bool was;
+    Untimed(Engine* e, bool timed) : on(e->profiling_), was(e->profiling_) { on = was && timed; }
+    ~Untimed() { on = was; }
+  };
   void prepare_device_prover();
   void batch_prove_device(const uint32_t* permutation, const uint8_t* k, const uint8_t* m_blinders, const uint8_t* rand, uint8_t* proofs_out);
 
   void run_msm_phase(const std::vector<MsmReq>& reqs, std::vector<uint8_t>* comp_out);
   void run_tbl_phase(const std::vector<TblReq>& reqs, std::vector<uint8_t>* comp_out);
-  void ensure_raw_sets(size_t nsets);
-  void reduce_sets(size_t nplain, size_t nweighted, TJac* part = nullptr);
+  void reduce_sets(hipStream_t st, MsmScratch& sc, size_t nplain, size_t nweighted, TJac* part = nullptr);
   void verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid);
   void batch_prove_tables(const uint32_t* permutation, const uint8_t* k, const uint8_t* m_blinders, const uint8_t* rand, uint8_t* proofs_out);
   // option strict_infinity = 0: `bytes` with every non-canonical infinity encoding (at `offsets` of each of the nrec records) rewritten to
@@ -439,8 +460,7 @@ class Engine {
   const TAff* ctab() const { return crs_tab_ ? crs_tab_->ctab.p : nullptr; }
   const TFix* fixtab() const { return crs_tab_ ? crs_tab_->fixtab.p : nullptr; }
   DevBuf<TAff> d_ptab_;      // per-proof tables [B][copies][NP]
-  DevBuf<uint32_t> d_raw_, d_rawslot_;   // raw lane accumulators of k_msm_tblw / k_msm_fix and their partial-sum slots
-  DevBuf<TJac> d_rawmid_;                // group sums between the two reduction launches
+  MsmScratch main_;                      // the main stream's MSM scratch: shared by the prover's phases, the verifier and the tier-0 calls
   DevBuf<uint32_t> d_digits_;            // recoded scalars of the endomorphism bucket MSM (9 words per point)
   DevBuf<Aff> d_psrc_;       // their standard-form sources [B][NP] : M | T_b | U_b
   DevBuf<TblTmp> d_tbltmp_;
@@ -474,7 +494,6 @@ class Engine {
   DevBuf<Jac> d_res_;
   DevBuf<uint32_t> d_big_idx_;   // gather list of the fused verifier's per-proof points
   DevBuf<TAff> d_conv_;            // table-form copies of the bases of a bucket-MSM phase
-  DevBuf<TJac> d_tpart_;           // partial sums of the table kernels
   DevBuf<uint32_t> d_dst_;
   DevBuf<uint8_t> d_comp_;
   PinBuf<uint8_t> h_stage_;

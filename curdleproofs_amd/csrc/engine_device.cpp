@@ -15,77 +15,25 @@
 namespace cpx {
 
 // ---------------------------------------------------------------- plans
-// Layout of a table-backed MSM phase whose requests all read device-resident scalars (TblReq::dev): the CRS segments go to
-// k_msm_fix, the per-proof segments to k_msm_tblw; k_reduce_sets turns the raw lane accumulators into partial sums,
-// k_finalize_ranges adds them per request, normalises, scatters the affine point (TblReq::dst) and writes the compressed
-// bytes to slot `comp_index[i]` of the registry.
+// Layout of a table-backed MSM phase whose requests all read device-resident scalars (TblReq::dev), by the planner of tbl_plan.hpp;
+// the launches (Engine::launch_tbl_phase) scatter the affine point (TblReq::dst) and write the compressed bytes to slot
+// `comp_index[i]` of the registry.
 void Engine::build_plan(TblPlan& pl, const std::vector<TblReq>& reqs, const std::vector<uint32_t>& comp_index) {
-  const size_t nt = reqs.size();
-  const bool fix = fix_bits_ && fixtab();
-  if (!fix) throw std::logic_error("set_crs first");
-  const TAff* c_lo = ctab();
-  const TAff* c_hi = ctab() + (size_t)copies_ * nc();
-  auto is_crs = [&](const TblSeg& sg) { return sg.n && sg.base >= c_lo && sg.base < c_hi; };
-  auto needs_tbl = [&](const TblReq& r) { return (r.seg0.n && !is_crs(r.seg0)) || (r.seg1.n && !is_crs(r.seg1)); };
-  size_t ntt = 0, nft = 0;
-  for (const TblReq& r : reqs) {
+  if (!(fix_bits_ && fixtab())) throw std::logic_error("set_crs first");
+  for (const TblReq& r : reqs)
     if (!r.dev && (r.seg0.n || r.seg1.n)) throw std::logic_error("device plan: request without device scalars");
-    ntt += needs_tbl(r) ? 1 : 0;
-    nft += (is_crs(r.seg0) ? 1 : 0) + (is_crs(r.seg1) ? 1 : 0);
-  }
-  pl.nt = nt;
-  pl.ntt = ntt;
-  pl.nft = nft;
-  pl.fix_wpw = pl.force_fix_wpw ? pl.force_fix_wpw : msm_fix_windows_per_wave(opt_, (int)nft, fix_bits_);
-  pl.tbl_wpw = pl.force_tbl_wpw ? pl.force_tbl_wpw : msm_tblw_windows_per_wave(opt_, (int)ntt);
-  const uint32_t fix_parts = (uint32_t)msm_fix_parts(fix_bits_, pl.fix_wpw), tbl_parts = (uint32_t)msm_tblw_parts(pl.tbl_wpw);
-  std::vector<TblTask> ht(ntt);
-  std::vector<FixTask> hf(nft);
-  std::vector<uint32_t> meta(7 * nt);   // pfirst | pcount | dst | comp_index | addends[3]
+  const CrsRange crs{ctab(), ctab() + (size_t)copies_ * nc()};
+  tbl_count(reqs, crs, pl);
+  pl.fix_wpw = pl.force_fix_wpw ? pl.force_fix_wpw : msm_fix_windows_per_wave(opt_, (int)pl.nft, fix_bits_);
+  pl.tbl_wpw = pl.force_tbl_wpw ? pl.force_tbl_wpw : msm_tblw_windows_per_wave(opt_, (int)pl.ntt);
+  std::vector<TblTask> ht(pl.ntt);
+  std::vector<FixTask> hf(pl.nft);
+  std::vector<uint32_t> meta(7 * pl.nt);
   // requests without a destination scatter their affine point to a write-only slot of proof 0 that NOTHING ever reads: TMP(7) for plans of the
   // main stream, TMP(5) for the plan that runs beside them on the table stream (phase 1t) — two streams never write the same slot
   const uint32_t dummy_dst = slot_index(0, SlotMap(L_).TMP(pl.table_stream ? 5 : 7));
-  const TblSeg none{nullptr, nullptr, 0, 0};
-  size_t it = 0, jf = 0, nparts = 0;
-  pl.pts_fix = pl.pts_tbl = 0;
-  pl.any_add = false;
-  for (size_t i = 0; i < nt; i++) {
-    const TblReq& r = reqs[i];
-    const bool f0 = is_crs(r.seg0), f1 = is_crs(r.seg1);
-    const uint32_t first = (uint32_t)nparts;
-    if (needs_tbl(r)) {
-      TblTask t;
-      t.seg[0] = r.seg0;
-      t.seg[1] = f1 ? none : r.seg1;
-      t.scalars = r.dev;
-      if (f0) {   // seg0 goes to the fixed-base kernel: its scalars are skipped, seg1 becomes the only segment
-        t.seg[0] = f1 ? none : r.seg1;
-        t.seg[1] = none;
-        t.scalars = r.dev + r.seg0.n;
-      }
-      t.flags = 0;
-      t.pad = (uint32_t)nparts;
-      t.digits = nullptr;
-      ht[it++] = t;
-      nparts += tbl_parts;
-    }
-    if (f0) {
-      hf[jf++] = FixTask{r.seg0.idx, r.dev, (uint32_t)(r.seg0.base - c_lo), r.seg0.n, 0, (uint32_t)nparts};
-      nparts += fix_parts;
-    }
-    if (f1) {
-      hf[jf++] = FixTask{r.seg1.idx, r.dev + r.seg0.n, (uint32_t)(r.seg1.base - c_lo), r.seg1.n, 0, (uint32_t)nparts};
-      nparts += fix_parts;
-    }
-    meta[i] = first;
-    meta[nt + i] = (uint32_t)nparts - first;
-    meta[2 * nt + i] = r.dst != ~0u ? r.dst : dummy_dst;
-    meta[3 * nt + i] = comp_index[i];
-    for (int j = 0; j < 3; j++) meta[4 * nt + 3 * i + j] = r.add[j];
-    pl.any_add |= r.add[0] != ~0u;
-    pl.pts_fix += (f0 ? r.seg0.n : 0) + (f1 ? r.seg1.n : 0);
-    pl.pts_tbl += (f0 ? 0 : r.seg0.n) + (f1 ? 0 : r.seg1.n);
-  }
+  tbl_plan(reqs, crs, (uint32_t)msm_fix_parts(fix_bits_, pl.fix_wpw), (uint32_t)msm_tblw_parts(pl.tbl_wpw), dummy_dst, nullptr, comp_index.data(), pl, ht.data(),
+           hf.data(), meta.data());
   // Long tasks first: a work-group's task is its index in these arrays, partial-sum slots travel with the task (out_first / pad).  With the
   // requests in protocol order a launch ended with the long waves of the last proofs and the GPU drained behind them (~0.8 ms of a
   // 7.6-ms k_msm_fix launch at 8192 proofs); now the one-point tasks fill the tail.
@@ -93,46 +41,20 @@ void Engine::build_plan(TblPlan& pl, const std::vector<TblReq>& reqs, const std:
     std::stable_sort(hf.begin(), hf.end(), [](const FixTask& a, const FixTask& b) { return a.n > b.n; });
     std::stable_sort(ht.begin(), ht.end(), [](const TblTask& a, const TblTask& b) { return a.seg[0].n + a.seg[1].n > b.seg[0].n + b.seg[1].n; });
   }
-  pl.nparts = nparts;
-  pl.fix_sets = nft * fix_parts;
-  pl.tbl_sets = ntt * tbl_parts;
-  pl.ttasks.ensure(std::max<size_t>(ntt, 1));
-  pl.ftasks.ensure(std::max<size_t>(nft, 1));
+  pl.ttasks.ensure(std::max<size_t>(pl.ntt, 1));
+  pl.ftasks.ensure(std::max<size_t>(pl.nft, 1));
   pl.meta.ensure(std::max<size_t>(meta.size(), 1));
-  if (ntt) CPX_HIP(hipMemcpy(pl.ttasks.p, ht.data(), ntt * sizeof(TblTask), hipMemcpyHostToDevice));
-  if (nft) CPX_HIP(hipMemcpy(pl.ftasks.p, hf.data(), nft * sizeof(FixTask), hipMemcpyHostToDevice));
-  if (nt) CPX_HIP(hipMemcpy(pl.meta.p, meta.data(), meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (pl.ntt) CPX_HIP(hipMemcpy(pl.ttasks.p, ht.data(), pl.ntt * sizeof(TblTask), hipMemcpyHostToDevice));
+  if (pl.nft) CPX_HIP(hipMemcpy(pl.ftasks.p, hf.data(), pl.nft * sizeof(FixTask), hipMemcpyHostToDevice));
+  if (pl.nt) CPX_HIP(hipMemcpy(pl.meta.p, meta.data(), meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
 }
 
 void Engine::exec_plan(const TblPlan& pl, uint8_t* d_comp_registry, bool on_table_stream) {
-  if (!pl.nt) return;
   // (a plan on the table stream works in the table stream's own scratch, sized by prepare_device_prover: it runs beside the plans
   // of the main stream)
-  const bool tl = on_table_stream && table_stream_on();
-  hipStream_t const st = tl ? tab_.dstream : stream_;
-  if (!tl) {
-    d_tpart_.ensure(std::max<size_t>(pl.nparts, 1));
-    ensure_raw_sets(pl.fix_sets + pl.tbl_sets);
-  }
-  uint32_t* const raw = tl ? tab_.raw.p : d_raw_.p;
-  uint32_t* const rawslot = tl ? tab_.rawslot.p : d_rawslot_.p;
-  TJac* const part = tl ? tab_.part.p : d_tpart_.p;
-  if (pl.nft) {
-    tick(fix_kernel_name(fix_bits_, pl.fix_wpw), 128.0 * pl.pts_fix, pl.pts_fix);
-    launch_msm_fix(pl.ftasks.p, (int)pl.nft, fixtab(), fix_bits_, pl.fix_wpw, (int)nc(), raw, rawslot, st);
-    tock();
-  }
-  if (pl.ntt) {
-    tick(tblw_kernel_name(pl.tbl_wpw), 128.0 * pl.pts_tbl, pl.pts_tbl);
-    launch_msm_tblw(pl.ttasks.p, (int)pl.ntt, pl.tbl_wpw, raw + pl.fix_sets * raw_set_words(), rawslot + pl.fix_sets, st);
-    tock();
-  }
-  if (tl) launch_reduce_sets(opt_, raw, rawslot, (int)pl.fix_sets, (int)pl.tbl_sets, tab_.mid.p, part, st, (int)B_);   // (not timed: a span is bracketed on the main stream)
-  else reduce_sets(pl.fix_sets, pl.tbl_sets);
-  const uint32_t* m = pl.meta.p;
-  tick("k_finalize_ranges", 0, (double)pl.nt);
-  launch_finalize_ranges(opt_, part, m, m + pl.nt, (int)pl.nt, d_pp_.p, m + 2 * pl.nt, d_comp_registry, st, pl.any_add ? m + 4 * pl.nt : nullptr, m + 3 * pl.nt);
-  tock();
+  if (on_table_stream && table_stream_on()) return launch_tbl_phase(pl, pl.ttasks.p, pl.ftasks.p, pl.meta.p, d_comp_registry, tab_.dstream, tab_.scr);
+  main_.ensure(pl.fix_sets + pl.tbl_sets, pl.nparts);
+  launch_tbl_phase(pl, pl.ttasks.p, pl.ftasks.p, pl.meta.p, d_comp_registry, stream_, main_);
 }
 
 // One late round: lane-per-output Straus MSMs over the materialised points, then the usual finalisation (affine, compressed bytes
@@ -152,11 +74,11 @@ void Engine::exec_late_round(const LateRound& r0, size_t comp_off, const char* w
     launch_late_fix(d_rout_.p + 3 * hm + 1, r.scal_proof_stride, lt.h_col, 1, 1, fixtab(), fix_bits_, (int)nc(), lt.extra.p + 2, 4, Bi, stream_);
   }
   tick("k_msm_tail", 0, (double)nreq);
-  launch_msm_tail(opt_, lt.part.p, d_tpart_.p, nullptr, nreq, r.slices, 128 / r.slices, stream_, ipa ? lt.extra.p : nullptr, ipa ? 1 : 0);
+  launch_msm_tail(opt_, lt.part.p, main_.part.p, nullptr, nreq, r.slices, 128 / r.slices, stream_, ipa ? lt.extra.p : nullptr, ipa ? 1 : 0);
   tock();
   const uint32_t* meta = lt.meta.p;
   tick("k_finalize_ranges", 0, (double)nreq);
-  launch_finalize_ranges(opt_, d_tpart_.p, meta, meta + 6 * B_, nreq, nullptr, nullptr, dprove_.slotcomp.p, stream_, nullptr, meta + comp_off);
+  launch_finalize_ranges(opt_, main_.part.p, meta, meta + 6 * B_, nreq, nullptr, nullptr, dprove_.slotcomp.p, stream_, nullptr, meta + comp_off);
   tock();
 }
 
@@ -197,10 +119,7 @@ void Engine::prepare_device_prover() {
   side_.conv.ensure(4 * B * ell);
   side_.ttasks.ensure(2 * B);
   side_.digits.ensure(9 * 2 * B * ell);
-  side_.raw.ensure(2 * B * 32 * raw_set_words());
-  side_.rawslot.ensure(2 * B * 32);
-  side_.mid.ensure(2 * B * 32 * reduce_mid_per_set());
-  side_.part.ensure(2 * B * 32);
+  side_.scr.ensure(2 * B * 32, 2 * B * 32);
   const std::vector<const void*> sig = {d_pp_.p,     d_ptab_.p,    d_psrc_.p,  d_bytes_.p,  d_mcomp_.p,   d_tstate_.p,   d_veca_.p,      d_rvec_.p,
                                         dp.rvec2.p,  d_rgam_.p,    d_rbeta_.p, d_rout_.p,   dp.perm.p,    dp.k.p,        dp.mbl.p,       dp.rnd.p,
                                         dp.vec.p,    dp.sc.p,      dp.slotcomp.p, dp.proofs.p, side_.tasks.p, side_.stasks.p, side_.dst.p, side_.conv.p,
@@ -331,10 +250,7 @@ void Engine::prepare_device_prover() {
   }
   dp.p1t.table_stream = true;
   build_plan(dp.p1t, reqs, ci);
-  tab_.raw.ensure(std::max<size_t>(dp.p1t.fix_sets + dp.p1t.tbl_sets, 1) * raw_set_words());
-  tab_.rawslot.ensure(std::max<size_t>(dp.p1t.fix_sets + dp.p1t.tbl_sets, 1));
-  tab_.mid.ensure(std::max<size_t>(dp.p1t.fix_sets + dp.p1t.tbl_sets, 1) * reduce_mid_per_set());
-  tab_.part.ensure(std::max<size_t>(dp.p1t.nparts, 1));
+  tab_.scr.ensure(dp.p1t.fix_sets + dp.p1t.tbl_sets, dp.p1t.nparts);
   // -- phase 1b (option p1_split): A = msm(G | Hvec, a_sigma | blinders) (curdleproofs.rs:93) alone — the one commitment of phase 1
   //    that needs vec_a; the rest of the phase then runs before the main stream waits for the transcript prefix
   reqs.clear();
@@ -570,8 +486,7 @@ void Engine::prepare_device_prover() {
       dp.rpart.ensure(max_parts);
       dp.rcount.ensure(B);
     }
-    d_tpart_.ensure(max_parts);
-    ensure_raw_sets(max_sets);
+    main_.ensure(max_sets, max_parts);
     d_tbltmp_.ensure(std::max(table_chunk_rows(B) * NP * (size_t)(copies_ / 2 - 1),   // one chunk of the table build ...
                               (3 * B * (size_t)lt.m + 63) / 64 * 64 * late_tmp_per_lane()));               // ... or the multiples of the late rounds' materialised points
   }
@@ -632,21 +547,7 @@ void Engine::enqueue_prove_device() {
   tock();
   CPX_HIP(hipEventRecord(dp.ev_b, pre));
   if (pre != side) CPX_HIP(hipStreamWaitEvent(side, dp.ev_b, 0));
-  {
-    const int nt = 2 * Bi;
-    // (R and S of a proof share the scalars vec_a: one wave per (proof, window) serves both, kernels.h launch_msm_endo_pairs)
-    tick(opt_.rs_pairs ? "k_msm_tblw_pair" : "k_msm_tblw<2, true>", 128.0 * 2 * ell * B, (double)(2 * ell * B));
-    if (opt_.rs_pairs) launch_msm_endo_pairs(side_.tasks.p, Bi, (int)ell, side_.conv.p, side_.digits.p, side_.ttasks.p, side_.raw.p, side_.rawslot.p, side);
-    else launch_msm_endo(side_.tasks.p, nt, (int)ell, side_.conv.p, side_.digits.p, side_.ttasks.p, side_.raw.p, side_.rawslot.p, side);
-    tock();
-    if (opt_.serial_streams) tick("k_reduce_sets", 0, (double)(nt * 32), true);   // (a span is bracketed on the main stream)
-    launch_reduce_sets(opt_, side_.raw.p, side_.rawslot.p, 0, nt * 32, side_.mid.p, side_.part.p, side, Bi);
-    if (opt_.serial_streams) tock();
-    tick("k_msm_tail", 0, (double)nt);
-    launch_msm_tail(opt_, side_.part.p, nullptr, side_.res.p, nt, 16, 8, side, nullptr, 0, 2);
-    tock();
-    launch_finalize(side_.res.p, nt, d_pp_.p, side_.dst.p, nullptr, side);
-  }
+  launch_rs(2 * B, 2 * B, 1, opt_.rs_pairs != 0, side, true);
   // table stream: the per-proof tables, then B_t and B_u (phase 1t) — nothing on the main stream needs a table before phase 2 (M's row)
   // nor B_t, B_u before the SameMSM transcript step
   hipStream_t const tabs = table_stream_on() ? tab_.dstream : stream_;
@@ -712,10 +613,10 @@ void Engine::enqueue_prove_device() {
     rd.next_scalars = last ? 0 : 1;
     rd.fixtab = fixtab();
     rd.nc = (int)nc();
-    rd.fraw = d_raw_.p;
-    rd.fraw_slot = d_rawslot_.p;
-    rd.traw = d_raw_.p + pl.fix_sets * raw_set_words();
-    rd.traw_slot = d_rawslot_.p + pl.fix_sets;
+    rd.fraw = main_.raw.p;
+    rd.fraw_slot = main_.rawslot.p;
+    rd.traw = main_.raw.p + pl.fix_sets * raw_set_words();
+    rd.traw_slot = main_.rawslot.p + pl.fix_sets;
     rd.part = dp.rpart.p;
     rd.meta = pl.meta.p;
     rd.comp_index = pl.meta.p + 3 * pl.nt;
@@ -987,29 +888,10 @@ void Engine::verify_core_device(const uint8_t* proofs, const uint8_t* rand, size
   exec_plan(dv.pd, dv.slotcomp.p);
   launch_vs_scalars(d, Bi, stream_);
   // -- V2: the accumulated check(s)
-  h_comp_.ensure(std::max<size_t>(B * 48, sizeof(Jac)));
   h_u32_.ensure(B);
   if (fused_partial) {
     launch_vs_crs_sum(dv.scal_crs.p, Bi, (int)n, dv.scal.p + B * NPT, stream_);
-    d_tpart_.ensure(dv.fix_parts1);
-    ensure_raw_sets(std::max<size_t>(dv.NT * 32, dv.fix_parts1));
-    launch_msm_fix(dv.ftasks.p + B, 1, fixtab(), fix_bits_, dv.fix_wpw1, (int)nc(), d_raw_.p, d_rawslot_.p, stream_);
-    reduce_sets(dv.fix_parts1, 0);
-    const size_t NT = dv.NT, NT16 = (NT + 15) / 16 * 16, N = B * NPT;
-    d_part_.ensure(NT * 32);
-    d_wsum_.ensure(NT16 + NT16 / 16);
-    d_ttasks_.ensure(NT);
-    CPX_HIP(hipMemsetAsync(d_wsum_.p, 0, (NT16 + NT16 / 16) * sizeof(TJac), stream_));   // all-zero = identity: pads the summation levels
-    tick("k_msm_tblw<2, true>", 128.0 * N, (double)N);
-    launch_msm_endo(dv.gtasks.p, (int)NT, (int)(dv.G * NPT), d_conv_.p, d_digits_.p, d_ttasks_.p, d_raw_.p, d_rawslot_.p, stream_);
-    tock();
-    reduce_sets(0, NT * 32, d_part_.p);
-    tick("k_msm_tail", 0, (double)NT, true);
-    launch_msm_tail(opt_, d_part_.p, d_wsum_.p, nullptr, (int)NT, 16, 8, stream_, nullptr, 0, 2);                               // windows of a group
-    launch_msm_tail(opt_, d_wsum_.p, d_wsum_.p + NT16, nullptr, (int)(NT16 / 16), 16, 0, stream_);                              // 16 groups each
-    launch_msm_tail(opt_, d_wsum_.p + NT16, nullptr, d_res_.p, 1, (int)(NT16 / 16), 0, stream_, d_tpart_.p, dv.fix_parts1);      // + the fixed-base part
-    tock();
-    CPX_HIP(hipMemcpyAsync(h_comp_.p, d_res_.p, sizeof(Jac), hipMemcpyDeviceToHost, stream_));
+    launch_check_fused(dv.gtasks.p, dv.ftasks.p + B, dv.NT, dv.G, NPT, B * NPT, dv.fix_wpw1, dv.fix_parts1);
     CPX_HIP(hipMemcpyAsync(h_u32_.p, dv.flags.p, B * 4, hipMemcpyDeviceToHost, stream_));
     wait_stream_blocking();
     memcpy(fused_partial, h_comp_.p, sizeof(Jac));
@@ -1019,29 +901,12 @@ void Engine::verify_core_device(const uint8_t* proofs, const uint8_t* rand, size
     flush_timers();
     return;
   }
-  d_tpart_.ensure(B * (size_t)dv.fix_parts);
-  ensure_raw_sets(B * std::max<size_t>(dv.fix_parts, 32));
-  tick(fix_kernel_name(fix_bits_, dv.fix_wpw), 128.0 * n * B, (double)(n * B));
-  launch_msm_fix(dv.ftasks.p, Bi, fixtab(), fix_bits_, dv.fix_wpw, (int)nc(), d_raw_.p, d_rawslot_.p, stream_);
-  tock();
-  reduce_sets(B * dv.fix_parts, 0);
-  tick("k_msm_tblw<2, true>", 128.0 * NPT * B, (double)(NPT * B));
-  launch_msm_endo(dv.mtasks.p, Bi, (int)NPT, d_conv_.p, d_digits_.p, d_ttasks_.p, d_raw_.p, d_rawslot_.p, stream_);
-  tock();
-  reduce_sets(0, B * 32, d_part_.p);
-  tick("k_msm_tail", 0, (double)B);
-  launch_msm_tail(opt_, d_part_.p, nullptr, d_res_.p, Bi, 16, 8, stream_, d_tpart_.p, dv.fix_parts, 2);
-  tock();
-  tick("k_finalize", 0, (double)B);
-  launch_finalize(d_res_.p, Bi, nullptr, nullptr, d_comp_.p, stream_);
-  tock();
-  CPX_HIP(hipMemcpyAsync(h_comp_.p, d_comp_.p, B * 48, hipMemcpyDeviceToHost, stream_));
+  launch_check(dv.mtasks.p, dv.ftasks.p, B, NPT, dv.fix_wpw, dv.fix_parts, 1);
   CPX_HIP(hipMemcpyAsync(h_u32_.p, dv.flags.p, B * 4, hipMemcpyDeviceToHost, stream_));
   wait_stream_blocking();
   for (size_t p = 0; p < B; p++) {
     const uint32_t f = h_u32_.p[p];
-    const bool ok = h_comp_.p[p * 48] == 0xc0;
-    verdict[p] = (f & 1u) ? CPX_ERR_DESERIALIZE : (((f & 2u) || !ok) ? CPX_ERR_VERIFY : CPX_OK);
+    verdict[p] = (f & 1u) ? CPX_ERR_DESERIALIZE : (((f & 2u) || !check_passed(p)) ? CPX_ERR_VERIFY : CPX_OK);
   }
   flush_timers();
 }
