@@ -21,6 +21,13 @@ SOURCES = ["kernels.hip", "late.hip", "protocol.hip", "round.hip", "engine.cpp",
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-ffp-contract=off",
          "-Xarch_host", "-march=x86-64-v3", "-Xarch_host", "-madx"]
 
+SELFCHECK = os.path.join(OUT_DIR, "quad_selfcheck")
+# test-only device program: every field and point operation on raw limbs, one kernel each (tests/test_gpu_field.py).  The
+# library does not depend on it: a tree without the tests' source builds libcpx.so alone.
+FIELDCHECK = os.path.join(OUT_DIR, "field_check")
+FIELDCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "field_check.hip")
+DEVICE_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-I", CSRC]   # the library's device flags
+
 
 def _hipcc():
     for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
@@ -30,10 +37,12 @@ def _hipcc():
 
 
 def _stale():
-    if not os.path.exists(LIB):
+    check = os.path.exists(FIELDCHECK_SRC)
+    outs = [LIB] + ([FIELDCHECK] if check else [])
+    if not all(os.path.exists(o) for o in outs):
         return True
-    t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__]
+    t = min(os.path.getmtime(o) for o in outs)
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else [])
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -76,6 +85,10 @@ def build(force=False, verbose=False):
                     print(" ".join(cmd))
                 procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
                 objs.append(obj)
+            tmp_check = os.path.join(work, "field_check")   # compiles beside the library's sources
+            check = os.path.exists(FIELDCHECK_SRC)
+            if check:
+                procs.append(("field_check.hip", subprocess.Popen(_fieldcheck_cmd(tmp_check), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
             for src, p in procs:
                 out, _ = p.communicate()
                 if p.returncode != 0:
@@ -86,13 +99,12 @@ def build(force=False, verbose=False):
             tmp_lib = os.path.join(work, "libcpx.so")
             subprocess.check_call([hipcc, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", tmp_lib] + objs + ["-lpthread"])
             os.replace(tmp_lib, LIB)
+            if check:
+                os.replace(tmp_check, FIELDCHECK)
         finally:
             shutil.rmtree(work, ignore_errors=True)
         build_selfcheck()
     return LIB
-
-
-SELFCHECK = os.path.join(OUT_DIR, "quad_selfcheck")
 
 
 def build_selfcheck():
@@ -102,6 +114,21 @@ def build_selfcheck():
     src = os.path.join(HERE, "..", "scripts", "micro", "quad_micro.hip")
     subprocess.check_call([_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-I", CSRC, src, "-o", SELFCHECK])
     return SELFCHECK
+
+
+def _fieldcheck_cmd(out):
+    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [FIELDCHECK_SRC, "-o", out]
+
+
+def build_fieldcheck():
+    """The device build of tests/device/field_check.hip alone (build() compiles it with the library; the host twin is compiled by
+    the tests with g++): cross-compiled here, it travels with the library."""
+    if not os.path.exists(FIELDCHECK_SRC):
+        raise RuntimeError("tests/device/field_check.hip is missing: the device field check cannot be built")
+    os.makedirs(OUT_DIR, exist_ok=True)
+    subprocess.check_call(_fieldcheck_cmd(FIELDCHECK + ".tmp"))
+    os.replace(FIELDCHECK + ".tmp", FIELDCHECK)
+    return FIELDCHECK
 
 
 if __name__ == "__main__":

@@ -11,16 +11,13 @@ import subprocess
 
 import pytest
 
+from tests.f28_vectors import P, RMOD, check_montgomery, extreme_sets, lazy_shape_sets, point_formula_sets, random_sets, value
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 EMUL = os.path.join(HERE, "host_emul", "emul.cpp")
 BODIES = os.path.join(HERE, "host_emul", "f28_redc_bodies.cpp")
-P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
-R392 = 1 << 392
-MASK = (1 << 28) - 1
-TOP38 = (38 * P) >> 364          # top limb of a value at the largest operand magnitude of the point formulas (38 p)
 SCHOOL, KARA_AB, KARA_REDC, DEFAULT = 0, 1, 2, -1
 AFF, FR = 96, 32
-RMOD = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 
 
 def _compile(src, out, defines=()):
@@ -42,19 +39,6 @@ def _bind(L):
 @pytest.fixture(scope="module")
 def bodies(tmp_path_factory):
     return _bind(_compile(BODIES, str(tmp_path_factory.mktemp("f28r") / "f28_redc_bodies.so")))
-
-
-def limbs(v):
-    """normalised limbs of an integer: 0..12 in [0, 2^28), the top limb signed"""
-    out = []
-    for _ in range(13):
-        out.append(v & MASK)
-        v >>= 28
-    return out + [v]
-
-
-def value(ls):
-    return sum(x << (28 * i) for i, x in enumerate(ls))
 
 
 def _arr(flat):
@@ -80,14 +64,6 @@ def run_sqr(L, body, regs, ops):
     out = (ctypes.c_int32 * (14 * n))()
     L.f28r_sqr(body, regs, _arr([x for ls in ops for x in ls]), out, n)
     return [list(out[14 * i:14 * i + 14]) for i in range(n)]
-
-
-def check_montgomery(t, target):
-    """t = (target + M p) / 2^392 for an integer M in [0, 2^392), with normalised limbs"""
-    assert all(0 <= x <= MASK for x in t[:13])
-    num = value(t) * R392 - target
-    assert num % P == 0
-    assert 0 <= num // P < R392
 
 
 def check_products(L, rows):
@@ -117,114 +93,44 @@ def check_squares(L, ops):
         check_montgomery(t, value(a) ** 2)
 
 
-def check_all(L, ops, rng, n2=2000, n4=2000):
-    check_squares(L, ops)
-    check_products(L, [[rng.choice(ops), rng.choice(ops)] for _ in range(n2)])
-    check_differences(L, [[rng.choice(ops) for _ in range(4)] for _ in range(n4)])
-
-
-def rand_val(rng, scale):
-    return rng.randrange(-scale * P, scale * P + 1)
-
-
-def lazy_diff(x, y):
-    """f28_sub_lazy: limb-wise difference of two normalised values, no carry pass"""
-    return [p - q for p, q in zip(limbs(x), limbs(y))]
-
-
-def cneg_lazy(x):
-    """f28_cneg_lazy of a normalised value"""
-    return [-v for v in limbs(x)]
-
-
 def test_defaults_select_the_karatsuba_reduction(bodies):
     assert bodies.f28r_defaults() == 7
 
 
 def test_random_operands_at_1_12_38_p(bodies):
-    rng = random.Random(3920)
-    for scale in (1, 12, 38):
-        ops = [limbs(rand_val(rng, scale)) for _ in range(400)]
+    for _, ops, rows2, rows4 in random_sets():
         check_squares(bodies, ops)
-        check_products(bodies, [[limbs(rand_val(rng, scale)), limbs(rand_val(rng, scale))] for _ in range(400)])
-        check_differences(bodies, [[limbs(rand_val(rng, scale)) for _ in range(4)] for _ in range(400)])
+        check_products(bodies, rows2)
+        check_differences(bodies, rows4)
 
 
 def test_extreme_limbs(bodies):
     """limbs at +-(2^28 - 1), top limb at its largest lazy value for 38 p, in every sign combination, single-limb spikes on
     either half of the split, and values whose Montgomery digits come out at 0 or 2^28 - 1 (the extremes of dm_i)"""
-    pos = [MASK] * 13 + [TOP38]
-    neg = [-MASK] * 13 + [-TOP38]
-    alt = [MASK if i % 2 else -MASK for i in range(13)] + [TOP38]
-    halves = [[MASK] * 7 + [-MASK] * 6 + [-TOP38], [-MASK] * 7 + [MASK] * 6 + [TOP38]]
-    ops = [pos, neg, alt, [-x for x in alt]] + halves + [[0] * 14, limbs(P), limbs(P - 1), limbs(1), limbs(R392 % P)]
-    for i in range(14):
-        s = [0] * 14
-        s[i] = TOP38 if i == 13 else MASK
-        ops += [s, [-x for x in s]]
-    rng = random.Random(11)
-    check_squares(bodies, ops)
-    check_products(bodies, [[a, b] for a in ops for b in ops])
-    check_differences(bodies, [[rng.choice(ops) for _ in range(4)] for _ in range(3000)])
+    e = extreme_sets()
+    check_squares(bodies, e["squares"])
+    check_products(bodies, e["pairs"])
+    check_differences(bodies, e["fours"])
     # the largest column sums of f28_mulsub_body: all four operands at the extreme of the same sign
-    check_differences(bodies, [[pos, pos, neg, pos], [neg, neg, pos, neg], [pos, neg, neg, neg], [alt, alt, [-x for x in alt], alt]])
+    check_differences(bodies, e["same_sign"])
     # products whose Montgomery digits (m = -a b p^-1 mod 2^392) are 0, all 2^28 - 1, or one half all 2^28 - 1 and the other 0:
     # dm_i = m_i - m_(7+i) and the substituted m_(k-7) dP_0 of the Karatsuba reduction at both ends of their range
-    rows = []
-    for m in (0, R392 - 1, (1 << 196) - 1, R392 - (1 << 196)):
-        target = -m * P % R392
-        for _ in range(4):
-            while True:   # a random a within 38 p and b = target / a mod 2^392, kept when b is within 38 p as well
-                a = rng.randrange(1, 38 * P) | 1
-                b = target * pow(a, -1, R392) % R392
-                b = b if b < 38 * P else b - R392
-                if abs(b) < 38 * P:
-                    break
-            assert (-(a * b) * pow(P, -1, R392)) % R392 == m
-            rows.append([limbs(a), limbs(b)])
-    check_products(bodies, rows)
-    check_differences(bodies, [r + [limbs(0), limbs(0)] for r in rows] + [r + rows[-1 - k] for k, r in enumerate(rows)])
+    check_products(bodies, e["digit_rows"])
+    check_differences(bodies, e["digit_fours"])
 
 
 def test_lazy_difference_and_negation_shapes(bodies):
     """f28_sub_lazy / f28_cneg_lazy results as operands: limbs in (-2^28, 2^28) of either sign, top limb signed"""
-    rng = random.Random(2801)
-    prod = lambda: rng.randrange(-81 * P // 100, 181 * P // 100)
-    ops = []
-    for _ in range(300):
-        ops += [lazy_diff(prod(), rand_val(rng, 6)), lazy_diff(rand_val(rng, 15), rand_val(rng, 15)), cneg_lazy(prod()),
-                cneg_lazy(rand_val(rng, 3))]
-    check_all(bodies, ops, rng)
+    ops, rows2, rows4 = lazy_shape_sets()
+    check_squares(bodies, ops)
+    check_products(bodies, rows2)
+    check_differences(bodies, rows4)
 
 
 def test_operands_of_the_point_formulas(bodies):
     """operands shaped as in xyzz28_add_mixed_t, jac28_dbl, xyzz28_dbl and xyzz28_add (g1_28.hpp): products in (-0.81 p, 1.81 p),
     stored coordinates up to 15.4 p, lazy differences of a product and a coordinate, lazily negated y, shifted values"""
-    rng = random.Random(3811)
-    prod = lambda: rng.randrange(-81 * P // 100, 181 * P // 100)
-    coord = lambda m: rng.randrange(-int(m * P), int(m * P))
-    rows2, rows4, sq = [], [], []
-    for _ in range(300):
-        # mixed addition: U2 = X2 ZZ1, S2 = (+-Y2) ZZZ1, P = U2 - X1, R = S2 - Y1 (lazy), PP = P^2, PPP = P PP, Q = X1 PP,
-        # X3 = R^2 - PPP - 2 Q, Y3 = R (Q - X3) - Y1 PPP, ZZ3 = ZZ1 PP, ZZZ3 = ZZZ1 PPP
-        x2, y2, zz1, zzz1, x1, y1 = prod(), prod(), prod(), prod(), coord(6.3), coord(2.7)
-        pp_, rr = lazy_diff(prod(), x1), lazy_diff(prod(), y1)
-        pp2, ppp, qq, x3 = prod(), prod(), prod(), coord(6.3)
-        rows2 += [[limbs(x2), limbs(zz1)], [cneg_lazy(y2), limbs(zzz1)], [limbs(zz1), limbs(pp2)], [pp_, limbs(pp2)],
-                  [limbs(x1), limbs(pp2)], [limbs(zzz1), limbs(ppp)]]
-        sq += [pp_, rr]
-        rows4 += [[rr, lazy_diff(qq, x3), limbs(y1), limbs(ppp)]]
-        # Jacobian doubling (k_table_build): A = X^2, B = Y^2, F = E^2 with E = 3 A; Y3 = E (D - X3) - (8 B) B with D = 4 X B
-        x, y = coord(15.4), coord(15.4)
-        e, d, x3d, b = 3 * prod(), 4 * prod(), coord(15.4), prod()
-        sq += [limbs(x), limbs(y), limbs(e)]
-        rows4 += [[limbs(e), lazy_diff(d, x3d), limbs(8 * b), limbs(b)]]
-        # XYZZ doubling: V = (2 Y)^2, XX = X^2, M^2 with M = 3 XX
-        sq += [limbs(2 * coord(2.7)), limbs(3 * prod())]
-        # full XYZZ addition: R = S2 - S1 (lazy, both products), Y3 = R (Q - X3) - S1 PPP
-        s1 = prod()
-        rows4 += [[lazy_diff(prod(), s1), lazy_diff(prod(), coord(8.1)), limbs(s1), limbs(prod())]]
-        rows2 += [[lazy_diff(prod(), s1), lazy_diff(prod(), prod())]]
+    sq, rows2, rows4 = point_formula_sets()
     check_products(bodies, rows2)
     check_differences(bodies, rows4)
     check_squares(bodies, sq)
