@@ -1,6 +1,7 @@
 // Host engine of the MI355X Curdleproofs core — see engine.hpp.  Product code: no CPU fallback for
 // the group arithmetic exists here; every point operation below is a kernel launch (kernels.hip).
 #include "engine.hpp"
+#include "host_verify.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -11,16 +12,11 @@
 namespace cpx {
 
 using host::S;
+using host::S_from_wire;
 using host::SVec;
 using host::Transcript;
 
 static const size_t N_BLINDERS = 4;   // /root/reference/src/lib.rs:35
-
-static inline S S_from_wire(const uint8_t* b) {
-  S s;
-  memcpy(s.f.v, b, 32);
-  return s;
-}
 
 std::atomic<int>& Engine::live_engines() {
   static std::atomic<int> n{0};
@@ -1369,7 +1365,8 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     run_tbl_phase(reqs, &comp);
     parallel_for(B, [&](size_t p) {
       ProverState& s = st[p];
-      const int order[4] = {sm.LC((int)j), sm.LD((int)j), sm.RC((int)j), sm.RD((int)j)};
+      int order[4];
+      sm.ipa_round((int)j, order);
       for (int q = 0; q < 4; q++) take(p, order[q], p * 4 + q);
       for (int q : order) s.tr.append_point_bytes("ipa_loop", &s.comp[(size_t)q * 48]);
       const S gamma = s.tr.get_and_append_challenge("ipa_gamma");
@@ -1389,7 +1386,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   // -- P6 (host only): SameScalar transcript, SameMSM step 1
   {
     std::vector<uint8_t> id_comp(48, 0);
-    id_comp[0] = 0xc0;
+    id_comp[0] = kCompIdentity;
     wait_side();   // R, S and the four T_2 commitments from the side stream
     {
       HostSpan w(this, "host_wait_device");
@@ -1404,7 +1401,8 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       memcpy(s.d_final.f.v, &h_rfin_.p[3 * p + 1], sizeof(Fr));
       const int side_slots[6] = {SL_R, SL_S, SL_CMT2, SL_CMU2, sm.CMA2(), sm.CMB2()};
       for (int q : side_slots) memcpy(&s.comp[(size_t)q * 48], side_.hcomp.p + (p * (size_t)CWN + (q - CW0)) * 48, 48);
-      const int pts[10] = {SL_R, SL_S, SL_CMT1, SL_CMT2, SL_CMU1, SL_CMU2, sm.CMA1(), sm.CMA2(), sm.CMB1(), sm.CMB2()};
+      int pts[10];
+      sm.sameexp_points(pts);
       for (int q : pts) s.tr.append_point_bytes("sameexp_points", &s.comp[(size_t)q * 48]);
       const S alpha = s.tr.get_and_append_challenge("same_scalar_alpha");
       const S kk = S_from_wire(k_in + 32 * p);
@@ -1476,7 +1474,8 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     run_tbl_phase(reqs, &comp);
     parallel_for(B, [&](size_t p) {
       ProverState& s = st[p];
-      const int order[6] = {sm.LA((int)j), sm.LT((int)j), sm.LU((int)j), sm.RA((int)j), sm.RT((int)j), sm.RU((int)j)};
+      int order[6];
+      sm.same_msm_round((int)j, order);
       for (int i = 0; i < 6; i++) take(p, order[i], p * 6 + i);
       for (int q : order) s.tr.append_point_bytes("same_msm_loop", &s.comp[(size_t)q * 48]);
       const S gamma = s.tr.get_and_append_challenge("same_msm_gamma");
@@ -1560,18 +1559,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
   }
 
   TeamScope team(this, B);   // 2 ... device_min_batch - 1 (55) proofs: the host loops on spinning helper threads
-  struct VState {
-    Transcript tr{"curdleproofs"};
-    bool bad = false;           // deserialisation failure
-    bool reject = false;        // structural rejection
-    S r_p, c_fin, d_fin, z_k, z_t, z_u, x_fin;
-    SVec vec_a;
-    S alpha_sp, beta_sp, gprod, alpha_g, beta_g, beta_g_inv, z_ip, alpha_i, beta_i, alpha_s, alpha_m;
-    SVec gam_i, gam_i_inv, gam_m, gam_m_inv;
-    const uint8_t* pb;          // proof bytes
-    SVec scal[8];
-  };
-  std::vector<VState> st(B);
+  std::vector<host::VerifyState> st(B);
 
   // -- V0: compressed instance vectors and M -> affine first (the transcript starts with their bytes: the side stream copies them
   //    to the host), then the proof points are decompressed into their slots — the host hashes (V1a) while that kernel runs
@@ -1616,43 +1604,10 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     wait_side();
   }
 
-  const uint8_t ID0 = kCompIdentity;
   std::vector<uint8_t> comp;
 
   // -- V1a: transcript up to the grand-product beta
-  parallel_for(B, [&](size_t p) {
-    VState& s = st[p];
-    s.pb = proofs + p * psz;
-    const uint8_t* pb = s.pb;
-    auto P = [&](int slot_id) { return pb + pl.point_offset(slot_id - SL_A); };
-    S* vals[ProofLayout::N_SCALARS] = {&s.r_p, &s.c_fin, &s.d_fin, &s.z_k, &s.z_t, &s.z_u, &s.x_fin};
-    for (int i = 0; i < ProofLayout::N_SCALARS; i++)
-      if (!S::from_le_bytes(pb + pl.scalar_offset(i), vals[i])) s.bad = true;
-    const uint8_t* ic = &inst_comp[p * 4 * ell * 48];
-    // curdleproofs.rs:218: the randomiser must not have wiped the ciphertexts
-    if (ic[2 * ell * 48] == ID0) s.reject = true;
-    for (int v = 0; v < 4; v++) s.tr.append_point_vec_bytes("curdleproofs_step1", ic + v * ell * 48, ell);   // curdleproofs.rs:213-222
-    s.tr.append_point_bytes("curdleproofs_step1", &mcomp[p * 48]);
-    s.vec_a = s.tr.get_and_append_challenges("curdleproofs_vec_a", ell);
-    // same_permutation_argument.rs:131-145
-    s.tr.append_point_bytes("same_perm_step1", P(SL_A));
-    s.tr.append_point_bytes("same_perm_step1", &mcomp[p * 48]);
-    s.tr.append_scalar_vec("same_perm_step1", s.vec_a);
-    s.alpha_sp = s.tr.get_and_append_challenge("same_perm_alpha");
-    s.beta_sp = s.tr.get_and_append_challenge("same_perm_beta");
-    s.gprod = S::one();
-    for (size_t i = 0; i < ell; i++) s.gprod *= s.vec_a[i] + S::from_u64(i) * s.alpha_sp + s.beta_sp;
-    // grand_product_argument.rs:200-209
-    s.tr.append_point_bytes("gprod_step1", P(SL_B));
-    s.tr.append_scalar("gprod_step1", s.gprod);
-    s.alpha_g = s.tr.get_and_append_challenge("gprod_alpha");
-    s.tr.append_point_bytes("gprod_step2", P(SL_C));
-    s.tr.append_scalar("gprod_step2", s.r_p);
-    s.beta_g = s.tr.get_and_append_challenge("gprod_beta");
-    s.beta_g_inv = s.beta_g.inverse();
-    s.scal[0] = {S::one(), -s.beta_g_inv, s.alpha_g};    // D  (grand_product_argument.rs:223)
-    s.scal[1] = {S::one(), S::one(), S::one()};          // A' (curdleproofs.rs:258)
-  });
+  parallel_for(B, [&](size_t p) { host::verify_prefix(st[p], ell, L, proofs + p * psz, &inst_comp[p * 4 * ell * 48], &mcomp[p * 48]); });
   {   // the decompressed proof points (and their verdicts) are needed from here on
     wait_stream();
     const uint8_t* status = h_status_.p;
@@ -1680,191 +1635,12 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     run_tbl_phase(reqs, &comp);
   }
 
-  // -- V1c: rest of the transcript and the scalars of the accumulated check
-  // slot-relative gather list of the "misc" MSM: CRS singles, M, every proof point
-  std::vector<uint32_t> misc_idx;
-  for (int q = SL_H; q <= SL_M; q++) misc_idx.push_back((uint32_t)q);
-  for (int q = 0; q < NPP; q++) misc_idx.push_back((uint32_t)(SL_A + q));
-  const size_t NM = misc_idx.size();
-
+  // -- V1c: rest of the transcript and the scalars of the accumulated check; its "misc" part runs over the CRS singles, M and every
+  //    proof point: the slots 0 .. NM
+  const size_t NM = (size_t)SL_A + NPP;
   parallel_for(B, [&](size_t p) {
-    VState& s = st[p];
-    const uint8_t* pb = s.pb;
-    auto P = [&](int slot_id) { return pb + pl.point_offset(slot_id - SL_A); };
-    auto factor = [&](int i) { return S_from_wire(rand + (p * rand_stride + i) * 32); };
-    const S a1 = factor(VF_SAMEPERM), a2 = factor(VF_IPA_C), a3 = factor(VF_IPA_D), a4 = factor(VF_SMSM_A), a5 = factor(VF_SMSM_T), a6 = factor(VF_SMSM_U),
-            a7 = factor(VF_R), a8 = factor(VF_S);
-    const S beta_l = s.beta_g.pow_u64(ell), beta_l1 = beta_l * s.beta_g;
-    s.z_ip = s.r_p * beta_l1 + s.gprod * beta_l - S::one();
-    // inner_product_argument.rs:283-290, 202-250
-    s.tr.append_point_bytes("ipa_step1", P(SL_C));
-    s.tr.append_point_bytes("ipa_step1", &comp[(p * 2) * 48]);   // D
-    s.tr.append_scalar("ipa_step1", s.z_ip);
-    s.tr.append_point_bytes("ipa_step1", P(SL_BC));
-    s.tr.append_point_bytes("ipa_step1", P(SL_BD));
-    s.alpha_i = s.tr.get_and_append_challenge("ipa_alpha");
-    s.beta_i = s.tr.get_and_append_challenge("ipa_beta");
-    s.gam_i.resize(L);
-    for (size_t j = 0; j < L; j++) {
-      s.tr.append_point_bytes("ipa_loop", P(sm.LC((int)j)));
-      s.tr.append_point_bytes("ipa_loop", P(sm.LD((int)j)));
-      s.tr.append_point_bytes("ipa_loop", P(sm.RC((int)j)));
-      s.tr.append_point_bytes("ipa_loop", P(sm.RD((int)j)));
-      s.gam_i[j] = s.tr.get_and_append_challenge("ipa_gamma");
-    }
-    s.gam_i_inv = s.gam_i;
-    host::batch_inverse(s.gam_i_inv);
-    // same_scalar_argument.rs:112-128
-    const int sp[10] = {SL_R, SL_S, SL_CMT1, SL_CMT2, SL_CMU1, SL_CMU2, sm.CMA1(), sm.CMA2(), sm.CMB1(), sm.CMB2()};
-    for (int q : sp) s.tr.append_point_bytes("sameexp_points", P(q));
-    s.alpha_s = s.tr.get_and_append_challenge("same_scalar_alpha");
-    // same_multiscalar_argument.rs:229-233, 167-186
-    s.tr.append_point_bytes("same_msm_step1", &comp[(p * 2 + 1) * 48]);   // A'
-    s.tr.append_point_bytes("same_msm_step1", P(SL_CMT2));
-    s.tr.append_point_bytes("same_msm_step1", P(SL_CMU2));
-    {
-      const uint8_t* ic = &inst_comp[p * 4 * ell * 48];
-      std::vector<uint8_t> vb(n * 48, 0);
-      memcpy(vb.data(), ic + 2 * ell * 48, ell * 48);
-      for (int i = 0; i < 4; i++) vb[(ell + i) * 48] = ID0;
-      memcpy(&vb[(ell + 2) * 48], crs_H_comp_, 48);
-      s.tr.append_point_vec_bytes("same_msm_step1", vb.data(), n);
-      std::fill(vb.begin() + ell * 48, vb.end(), 0);
-      memcpy(vb.data(), ic + 3 * ell * 48, ell * 48);
-      for (int i = 0; i < 4; i++) vb[(ell + i) * 48] = ID0;
-      memcpy(&vb[(ell + 3) * 48], crs_H_comp_, 48);
-      s.tr.append_point_vec_bytes("same_msm_step1", vb.data(), n);
-    }
-    s.tr.append_point_bytes("same_msm_step1", P(sm.BA()));
-    s.tr.append_point_bytes("same_msm_step1", P(sm.BT()));
-    s.tr.append_point_bytes("same_msm_step1", P(sm.BU()));
-    s.alpha_m = s.tr.get_and_append_challenge("same_msm_alpha");
-    s.gam_m.resize(L);
-    for (size_t j = 0; j < L; j++) {
-      const int six[6] = {sm.LA((int)j), sm.LT((int)j), sm.LU((int)j), sm.RA((int)j), sm.RT((int)j), sm.RU((int)j)};
-      for (int q : six) s.tr.append_point_bytes("same_msm_loop", P(q));
-      s.gam_m[j] = s.tr.get_and_append_challenge("same_msm_gamma");
-    }
-    s.gam_m_inv = s.gam_m;
-    host::batch_inverse(s.gam_m_inv);
-
-    // verification scalars s_i = prod_{j : bit (L-1-j) of i set} gamma_j  (util.rs:40-64), built by doubling
-    auto svec = [&](const SVec& g) {
-      SVec sv(n);
-      sv[0] = S::one();
-      for (size_t j = 0; j < L; j++) {          // after step j, entries < 2^(j+1) are final for the low (j+1) bits
-        const size_t w = size_t(1) << j;
-        const S gj = g[L - 1 - j];              // bit j of i  <->  round L-1-j
-        for (size_t i = 0; i < w; i++) sv[w + i] = sv[i] * gj;
-      }
-      return sv;
-    };
-    const SVec s_i = svec(s.gam_i), s_m = svec(s.gam_m);
-    SVec s_i_inv = s_i;
-    host::batch_inverse(s_i_inv);
-    // u (grand_product_argument.rs:211-219)
-    SVec u(n);
-    {
-      S pw = s.beta_g_inv;
-      for (size_t i = 0; i < ell; i++) {
-        u[i] = pw;
-        pw *= s.beta_g_inv;
-      }
-      for (size_t i = ell; i < n; i++) u[i] = pw;
-    }
-    // ---- flattened accumulated check: sum_i a_i * (lhs_i - x_i . V_i) == O  (msm_accumulator.rs:38-68) ----
-    const S a2c = a2 * s.c_fin, a3d = a3 * s.d_fin, a4x = a4 * s.x_fin, a5x = a5 * s.x_fin, a6x = a6 * s.x_fin;
-    // (1) CRS part over G | Hvec (n bases)
-    SVec& k1 = s.scal[0];
-    k1.assign(n, S::zero());
-    const S a1b = a1 * s.beta_sp;
-    for (size_t i = 0; i < n; i++) {
-      S t = a2c * s_i[i] + a3d * (s_i_inv[i] * u[i]);
-      if (i < ell) t += a1b;
-      if (i < ell + 2) t += a4x * s_m[i];       // G_b = G | Hvec[0..2) | G_t | G_u
-      k1[i] = -t;
-    }
-    // (2) instance part over R | S | T | U
-    SVec& k2 = s.scal[1];
-    k2.resize(4 * ell);
-    for (size_t i = 0; i < ell; i++) {
-      k2[i] = -(a7 * s.vec_a[i]);
-      k2[ell + i] = -(a8 * s.vec_a[i]);
-      k2[2 * ell + i] = -(a5x * s_m[i]);
-      k2[3 * ell + i] = -(a6x * s_m[i]);
-    }
-    // (3) misc part: singles, M, proof points
-    SVec& k3 = s.scal[2];
-    k3.assign(NM, S::zero());
-    auto at = [&](int slot_id) -> S& { return k3[slot_id <= SL_M ? slot_id : (SL_M + 1) + (slot_id - SL_A)]; };
-    at(SL_GT) = -(a4x * s_m[ell + 2]);
-    at(SL_GU) = -(a4x * s_m[ell + 3]);
-    at(SL_H) = a2 * (s.alpha_i * s.alpha_i * s.z_ip * s.beta_i) - a2c * s.d_fin * s.beta_i - a5x * s_m[ell + 2] - a6x * s_m[ell + 3];
-    at(SL_GSUM) = -(a3 * s.alpha_i * s.beta_g_inv);
-    at(SL_HSUM) = a3 * s.alpha_i * s.alpha_g;
-    at(SL_M) = -(a1 * s.alpha_sp);
-    at(SL_B) = a1 + a3 * s.alpha_i;
-    at(SL_A) = a4 * s.alpha_m - a1;
-    at(SL_CMT1) = a4 * s.alpha_m;
-    at(SL_CMU1) = a4 * s.alpha_m;
-    at(SL_CMT2) = a5 * s.alpha_m;
-    at(SL_CMU2) = a6 * s.alpha_m;
-    at(SL_C) = a2 * s.alpha_i;
-    at(SL_BC) = a2;
-    at(SL_BD) = a3;
-    at(sm.BA()) = a4;
-    at(sm.BT()) = a5;
-    at(sm.BU()) = a6;
-    at(SL_R) = a7;
-    at(SL_S) = a8;
-    for (size_t j = 0; j < L; j++) {
-      at(sm.LC((int)j)) = a2 * s.gam_i[j];
-      at(sm.RC((int)j)) = a2 * s.gam_i_inv[j];
-      at(sm.LD((int)j)) = a3 * s.gam_i[j];
-      at(sm.RD((int)j)) = a3 * s.gam_i_inv[j];
-      at(sm.LA((int)j)) = a4 * s.gam_m[j];
-      at(sm.RA((int)j)) = a4 * s.gam_m_inv[j];
-      at(sm.LT((int)j)) = a5 * s.gam_m[j];
-      at(sm.RT((int)j)) = a5 * s.gam_m_inv[j];
-      at(sm.LU((int)j)) = a6 * s.gam_m[j];
-      at(sm.RU((int)j)) = a6 * s.gam_m_inv[j];
-    }
-    // SameScalar equalities (same_scalar_argument.rs:127-137), each of the form "... == O":
-    //   cm_A.T_1 + alpha cm_T.T_1 - z_t G_t,   cm_A.T_2 + alpha cm_T.T_2 - z_k R - z_t H,
-    //   cm_B.T_1 + alpha cm_U.T_1 - z_u G_u,   cm_B.T_2 + alpha cm_U.T_2 - z_k S - z_u H
-    {
-      // The four equalities join the accumulated MSM with random weights of their own: factors 9..12 in fused mode;
-      // in per-proof mode the pairwise products a1 a2, a3 a4, a5 a6, a7 a8 of the caller's eight factors — the
-      // accumulated sum is then a polynomial of degree 2 in independent uniform factors whose coefficients are the
-      // individual check values, so it vanishes with probability <= 2/r unless every check holds (Schwartz-Zippel),
-      // the same argument that backs msm_accumulator.rs itself.
-      S w1, w2, w3, w4;
-      if (fused_partial) {
-        w1 = factor(VF_SS_A1);
-        w2 = factor(VF_SS_A2);
-        w3 = factor(VF_SS_B1);
-        w4 = factor(VF_SS_B2);
-      } else {
-        w1 = a1 * a2;
-        w2 = a3 * a4;
-        w3 = a5 * a6;
-        w4 = a7 * a8;
-      }
-      at(sm.CMA1()) += w1;
-      at(SL_CMT1) += w1 * s.alpha_s;
-      at(SL_GT) += -(w1 * s.z_t);
-      at(sm.CMA2()) += w2;
-      at(SL_CMT2) += w2 * s.alpha_s;
-      at(SL_R) += -(w2 * s.z_k);
-      at(SL_H) += -(w2 * s.z_t);
-      at(sm.CMB1()) += w3;
-      at(SL_CMU1) += w3 * s.alpha_s;
-      at(SL_GU) += -(w3 * s.z_u);
-      at(sm.CMB2()) += w4;
-      at(SL_CMU2) += w4 * s.alpha_s;
-      at(SL_S) += -(w4 * s.z_k);
-      at(SL_H) += -(w4 * s.z_u);
-    }
+    host::verify_scalars(st[p], ell, L, &inst_comp[p * 4 * ell * 48], crs_H_comp_, &comp[(p * 2) * 48], &comp[(p * 2 + 1) * 48], rand + p * rand_stride * 32,
+                         fused_partial != nullptr);
   });
 
   if (fused_partial) {
@@ -1891,7 +1667,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     uint32_t* hi = reinterpret_cast<uint32_t*>(h_stage_.p + b_scal);
     FixTask* hf = reinterpret_cast<FixTask*>(h_stage_.p + b_scal + b_idx);
     parallel_for(B, [&](size_t p) {
-      const VState& s = st[p];
+      const host::VerifyState& s = st[p];
       Fr* d = hs + p * NPT;
       uint32_t* x = hi + p * NPT;
       for (size_t i = 0; i < NI; i++) {
@@ -1900,7 +1676,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
       }
       for (size_t j = 0; j < NM; j++) {
         d[NI + j] = s.bad ? S::zero().f : s.scal[2][j].f;
-        x[NI + j] = slot_index(p, (int)misc_idx[j]);
+        x[NI + j] = slot_index(p, (int)j);
       }
     });
     for (size_t i = 0; i < n; i++) hs[N + i] = crs_sum[i].f;
@@ -1930,9 +1706,8 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
   {
     if (!fixtab()) throw std::logic_error("set_crs first");
     const size_t NI = 4 * ell, NPT = NI + NM;
-    std::vector<uint32_t> all_idx(NPT);   // row-relative gather list: instance vectors, then the slots of the misc part
-    for (size_t i = 0; i < NI; i++) all_idx[i] = (uint32_t)i;
-    for (size_t j = 0; j < NM; j++) all_idx[NI + j] = (uint32_t)(NI + misc_idx[j]);
+    std::vector<uint32_t> all_idx(NPT);   // row-relative gather list: the instance vectors, then the slots of the misc part — the row's first NPT points
+    for (size_t i = 0; i < NPT; i++) all_idx[i] = (uint32_t)i;
     const uint32_t* d_all = idx_list(all_idx);
     const int fix_wpw = msm_fix_windows_per_wave(opt_, (int)B, fix_bits_);
     const int fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
@@ -1947,7 +1722,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     MsmTask* hm = reinterpret_cast<MsmTask*>(h_stage_.p + b_scal);
     FixTask* hf = reinterpret_cast<FixTask*>(h_stage_.p + b_scal + b_mt);
     parallel_for(B, [&](size_t p) {
-      const VState& s = st[p];
+      const host::VerifyState& s = st[p];
       Fr* d = hs + p * (NPT + n);
       for (size_t i = 0; i < NI; i++) d[i] = s.scal[1][i].f;
       for (size_t j = 0; j < NM; j++) d[NI + j] = s.scal[2][j].f;
@@ -1961,7 +1736,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     launch_check(d_tasks_.p, d_ftasks_.p, B, NPT, fix_wpw, fix_parts, slices);
     wait_stream();
     for (size_t p = 0; p < B; p++) {
-      const VState& s = st[p];
+      const host::VerifyState& s = st[p];
       verdict[p] = s.bad ? CPX_ERR_DESERIALIZE : ((s.reject || !check_passed(p)) ? CPX_ERR_VERIFY : CPX_OK);
     }
   }

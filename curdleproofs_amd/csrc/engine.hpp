@@ -370,8 +370,7 @@ class Engine {
   // the verifier's accumulated check, per proof and fused (config 5), up to the device-to-host copy of the result into h_comp_
   void launch_check(const MsmTask* d_mt, const FixTask* d_ft, size_t B, size_t NPT, int fix_wpw, int fix_parts, size_t slices);
   void launch_check_fused(const MsmTask* d_gt, const FixTask* d_ft, size_t NT, size_t G, size_t NPT, size_t N, int fix_wpw, int fix_parts);
-  static constexpr uint8_t kCompIdentity = 0xc0;   // first byte of the compressed identity: what the accumulated check of a valid proof sums to
-  bool check_passed(size_t p) const { return h_comp_.p[p * 48] == kCompIdentity; }
+  bool check_passed(size_t p) const { return h_comp_.p[p * 48] == kCompIdentity; }   // the accumulated check of a valid proof sums to the identity
   struct Untimed {   // keeps a launch sequence out of the statistics
     bool& on;
     const bool was;

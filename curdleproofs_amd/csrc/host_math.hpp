@@ -211,6 +211,16 @@ struct S {   // a scalar in Montgomery form
   }
 };
 typedef std::vector<S> SVec;
+inline S S_from_wire(const uint8_t* b) {   // a Montgomery residue as the ABI carries it (4 x u64 LE)
+  S s;
+  memcpy(s.f.v, b, 32);
+  return s;
+}
+// the names code shared with the device calls on Fr (check_weights.hpp), on the 64-bit-limb host product
+inline S fe_mul(const S& a, const S& b) { return a * b; }
+inline S fe_add(const S& a, const S& b) { return a + b; }
+inline S fe_sub(const S& a, const S& b) { return a - b; }
+inline S fe_neg(const S& a) { return -a; }
 
 // A random factor of the accumulated check as the caller hands it over (wire form: Montgomery residue, 4 x u64 LE): it
 // must be a reduced, non-zero element — a zero factor would drop its check from the accumulated sum.

@@ -11,6 +11,9 @@ namespace cpx {
 // ---- per-proof point registry ("slots") that follows the 4*ell instance points in d_pp_ ----
 // CRS singles, M, then every proof point in serialisation order (curdleproofs.rs:300-310), then scratch.
 enum { SL_H = 0, SL_GT, SL_GU, SL_GSUM, SL_HSUM, SL_M, SL_A, SL_CMT1, SL_CMT2, SL_CMU1, SL_CMU2, SL_R, SL_S, SL_B, SL_C, SL_BC, SL_BD, SL_IPA0 };
+// The "misc" points of the verifier's accumulated check are the slots 0 .. SL_A + n_points(): slot s is misc point s.
+static_assert(SL_A == SL_M + 1, "the proof points must follow the CRS singles and M without a gap");
+static constexpr uint8_t kCompIdentity = 0xc0;   // first byte of the compressed identity (the other 47 are zero)
 struct SlotMap {
   int L;
   CPX_HD explicit SlotMap(size_t l) : L((int)l) {}
@@ -35,6 +38,20 @@ struct SlotMap {
   CPX_HD int APRIME() const { return D() + 1; }
   CPX_HD int TMP(int i) const { return D() + 2 + i; }   // 8 scratch results
   CPX_HD int count() const { return D() + 2 + 8; }
+  // the points the transcripts absorb together, in the order they are hashed (the proof-byte known answers pin it):
+  // same_scalar_argument.rs:112-118, and one round of inner_product_argument.rs:164-170 / same_multiscalar_argument.rs:114-122
+  CPX_HD void sameexp_points(int q[10]) const {
+    const int pts[10] = {SL_R, SL_S, SL_CMT1, SL_CMT2, SL_CMU1, SL_CMU2, CMA1(), CMA2(), CMB1(), CMB2()};
+    for (int i = 0; i < 10; i++) q[i] = pts[i];
+  }
+  CPX_HD void ipa_round(int j, int q[4]) const {
+    const int pts[4] = {LC(j), LD(j), RC(j), RD(j)};
+    for (int i = 0; i < 4; i++) q[i] = pts[i];
+  }
+  CPX_HD void same_msm_round(int j, int q[6]) const {
+    const int pts[6] = {LA(j), LT(j), LU(j), RA(j), RT(j), RU(j)};
+    for (int i = 0; i < 6; i++) q[i] = pts[i];
+  }
 };
 
 // ---- wire format of a proof (CurdleproofsProof::serialize, curdleproofs.rs:300-310): the proof points in slot order from SL_A,

@@ -13,6 +13,7 @@
 #include "strobe.hpp"
 #include "wave_strobe.hpp"
 #include "protocol.h"
+#include "check_weights.hpp"
 
 namespace cpx {
 
@@ -278,10 +279,9 @@ __global__ __launch_bounds__(64) void k_ps_ipa_round(const ProveDev d, int j) {
   const SlotMap sm(d.L);
   WaveStrobe t;
   t.load(v.tstate(), lane);
-  t.append_message(LBL("ipa_loop"), v.slot(sm.LC(j)), 48, scratch);
-  t.append_message(LBL("ipa_loop"), v.slot(sm.LD(j)), 48, scratch);
-  t.append_message(LBL("ipa_loop"), v.slot(sm.RC(j)), 48, scratch);
-  t.append_message(LBL("ipa_loop"), v.slot(sm.RD(j)), 48, scratch);
+  int four[4];
+  sm.ipa_round(j, four);
+  for (int q = 0; q < 4; q++) t.append_message(LBL("ipa_loop"), v.slot(four[q]), 48, scratch);
   const Fr gamma = t.challenge_scalar(LBL("ipa_gamma"), scratch);
   t.store(v.tstate());
   const Fr gi = fr_inv_divsteps(gamma);
@@ -310,7 +310,8 @@ __global__ __launch_bounds__(64) void k_ps_smsm_setup(const ProveDev d) {
   }
   WaveStrobe t;
   t.load(v.tstate(), lane);
-  const int pts[10] = {SL_R, SL_S, SL_CMT1, SL_CMT2, SL_CMU1, SL_CMU2, sm.CMA1(), sm.CMA2(), sm.CMB1(), sm.CMB2()};
+  int pts[10];
+  sm.sameexp_points(pts);
   for (int q = 0; q < 10; q++) t.append_message(LBL("sameexp_points"), v.slot(pts[q]), 48, scratch);
   const Fr alpha_s = t.challenge_scalar(LBL("same_scalar_alpha"), scratch);
   const Fr z_k = fe_add(rnd[ri.RK()], fe_mul(d.k[v.p], alpha_s));
@@ -325,7 +326,7 @@ __global__ __launch_bounds__(64) void k_ps_smsm_setup(const ProveDev d) {
     for (int i = lane; i < 4 * 48; i += 64) {
       const int s = i / 48, b = i % 48;
       const bool h = s == (which ? 3 : 2);
-      tail[i] = h ? d.crs_h_comp[b] : (b == 0 ? 0xc0 : 0);
+      tail[i] = h ? d.crs_h_comp[b] : (b == 0 ? kCompIdentity : 0);
     }
     if (lane < 8) scratch[8 + lane] = (uint8_t)((uint64_t)n >> (8 * lane));
     __syncthreads();
@@ -367,7 +368,8 @@ __global__ __launch_bounds__(64) void k_ps_smsm_round(const ProveDev d, int j) {
   const SlotMap sm(d.L);
   WaveStrobe t;
   t.load(v.tstate(), lane);
-  const int six[6] = {sm.LA(j), sm.LT(j), sm.LU(j), sm.RA(j), sm.RT(j), sm.RU(j)};
+  int six[6];
+  sm.same_msm_round(j, six);
   for (int q = 0; q < 6; q++) t.append_message(LBL("same_msm_loop"), v.slot(six[q]), 48, scratch);
   const Fr gamma = t.challenge_scalar(LBL("same_msm_gamma"), scratch);
   t.store(v.tstate());
@@ -467,7 +469,7 @@ __global__ __launch_bounds__(64) void k_vs_prefix(const VerifyDev d) {
   for (int q = lane; q < npp; q += 64) badpt |= d.status[(size_t)v.p * npp + q];
   const bool bad = !ok || __any(badpt != 0);
   const uint8_t* ic = d.inst_comp + (size_t)v.p * 4 * ell * 48;
-  const bool reject = ic[(size_t)2 * ell * 48] == 0xc0;   // curdleproofs.rs:218: the randomiser must not have wiped the ciphertexts
+  const bool reject = ic[(size_t)2 * ell * 48] == kCompIdentity;   // curdleproofs.rs:218: the randomiser must not have wiped the ciphertexts
   const Fr* veca = d.veca + (size_t)v.p * ell;
   WaveStrobe t;
   t.load(v.tstate(), lane);
@@ -549,15 +551,15 @@ __global__ __launch_bounds__(64) void k_vs_scalars(const VerifyDev d) {
   const Fr alpha_i = t.challenge_scalar(LBL("ipa_alpha"), scratch);
   const Fr beta_i = t.challenge_scalar(LBL("ipa_beta"), scratch);
   for (int j = 0; j < L; j++) {
-    t.append_message(LBL("ipa_loop"), v.P(sm.LC(j)), 48, scratch);
-    t.append_message(LBL("ipa_loop"), v.P(sm.LD(j)), 48, scratch);
-    t.append_message(LBL("ipa_loop"), v.P(sm.RC(j)), 48, scratch);
-    t.append_message(LBL("ipa_loop"), v.P(sm.RD(j)), 48, scratch);
+    int four[4];
+    sm.ipa_round(j, four);
+    for (int q = 0; q < 4; q++) t.append_message(LBL("ipa_loop"), v.P(four[q]), 48, scratch);
     const Fr g = t.challenge_scalar(LBL("ipa_gamma"), scratch);
     if (lane == 0) gam[j] = g;
   }
   {
-    const int sp[10] = {SL_R, SL_S, SL_CMT1, SL_CMT2, SL_CMU1, SL_CMU2, sm.CMA1(), sm.CMA2(), sm.CMB1(), sm.CMB2()};
+    int sp[10];
+    sm.sameexp_points(sp);
     for (int q = 0; q < 10; q++) t.append_message(LBL("sameexp_points"), v.P(sp[q]), 48, scratch);
   }
   const Fr alpha_s = t.challenge_scalar(LBL("same_scalar_alpha"), scratch);
@@ -569,7 +571,7 @@ __global__ __launch_bounds__(64) void k_vs_scalars(const VerifyDev d) {
     for (int i = lane; i < 4 * 48; i += 64) {
       const int s = i / 48, b = i % 48;
       const bool h = s == (which ? 3 : 2);
-      tail[i] = h ? d.crs_h_comp[b] : (b == 0 ? 0xc0 : 0);
+      tail[i] = h ? d.crs_h_comp[b] : (b == 0 ? kCompIdentity : 0);
     }
     if (lane < 8) scratch[8 + lane] = (uint8_t)((uint64_t)n >> (8 * lane));
     __syncthreads();
@@ -584,7 +586,8 @@ __global__ __launch_bounds__(64) void k_vs_scalars(const VerifyDev d) {
   t.append_message(LBL("same_msm_step1"), v.P(sm.BU()), 48, scratch);
   const Fr alpha_m = t.challenge_scalar(LBL("same_msm_alpha"), scratch);
   for (int j = 0; j < L; j++) {
-    const int six[6] = {sm.LA(j), sm.LT(j), sm.LU(j), sm.RA(j), sm.RT(j), sm.RU(j)};
+    int six[6];
+    sm.same_msm_round(j, six);
     for (int q = 0; q < 6; q++) t.append_message(LBL("same_msm_loop"), v.P(six[q]), 48, scratch);
     const Fr g = t.challenge_scalar(LBL("same_msm_gamma"), scratch);
     if (lane == 0) gam[L + j] = g;
@@ -594,16 +597,17 @@ __global__ __launch_bounds__(64) void k_vs_scalars(const VerifyDev d) {
   // the 2 L challenge inverses, one lane each (ark_ff::batch_inversion of the reference gives the same values)
   if (lane < 2 * L) gam[2 * L + lane] = fr_inv_divsteps(gam[lane]);
   __syncthreads();
-  const Fr *gam_i = gam, *gam_m = gam + L, *gam_i_inv = gam + 2 * L, *gam_m_inv = gam + 3 * L;
   // u_i = beta^-(i+1), i < ell; beta^-(ell+1) on the blinder positions (grand_product_argument.rs:211-219)
   for (int i = lane; i <= ell; i += 64) buf[i] = beta_g_inv;
   __syncthreads();
   scan_mul(buf, ell + 1);
   const Fr* rnd = v.rnd();
-  const Fr a1 = rnd[VF_SAMEPERM], a2 = rnd[VF_IPA_C], a3 = rnd[VF_IPA_D], a4 = rnd[VF_SMSM_A], a5 = rnd[VF_SMSM_T], a6 = rnd[VF_SMSM_U],
-           a7 = rnd[VF_R], a8 = rnd[VF_S];
-  const Fr a2c = fe_mul(a2, c_fin), a3d = fe_mul(a3, d_fin), a4x = fe_mul(a4, x_fin), a5x = fe_mul(a5, x_fin), a6x = fe_mul(a6, x_fin);
-  const Fr a1b = fe_mul(a1, beta_sp);
+  CheckTerms<Fr> w;   // the weights of the accumulated check: check_weights.hpp
+  w.alpha_sp = alpha_sp, w.beta_sp = beta_sp, w.alpha_g = alpha_g, w.beta_g_inv = beta_g_inv;
+  w.alpha_i = alpha_i, w.beta_i = beta_i, w.alpha_s = alpha_s, w.alpha_m = alpha_m;
+  w.c_fin = c_fin, w.d_fin = d_fin, w.z_k = z_k, w.z_t = z_t, w.z_u = z_u, w.x_fin = x_fin, w.z_ip = z_ip;
+  w.gam_i = gam, w.gam_m = gam + L, w.gam_i_inv = gam + 2 * L, w.gam_m_inv = gam + 3 * L;
+  w.set_factors(rnd);
   const bool bad = d.flags[v.p] & 1u;   // an undecodable proof contributes nothing to a fused batch (it is counted as invalid)
   const size_t NI = 4 * (size_t)ell, NPT = NI + d.NM;
   Fr* out = d.scal + (size_t)v.p * NPT;
@@ -617,112 +621,28 @@ __global__ __launch_bounds__(64) void k_vs_scalars(const VerifyDev d) {
   };
   Fr sm_l2 = Fr::zero(), sm_l3 = Fr::zero();   // s_m[ell + 2], s_m[ell + 3]
   for (int i = lane; i < n; i += 64) {
-    const Fr s_i = svec(gam_i, i), s_i_inv = svec(gam_i_inv, i), s_m = svec(gam_m, i);
+    const Fr s_i = svec(w.gam_i, i), s_i_inv = svec(w.gam_i_inv, i), s_m = svec(w.gam_m, i);
     const Fr u = buf[i < ell ? i : ell];
     // (1) CRS part over G | Hvec
-    Fr k1 = fe_add(fe_mul(a2c, s_i), fe_mul(a3d, fe_mul(s_i_inv, u)));
-    if (i < ell) k1 = fe_add(k1, a1b);
-    if (i < ell + 2) k1 = fe_add(k1, fe_mul(a4x, s_m));   // G_b = G | Hvec[0..2) | G_t | G_u
-    out_crs[i] = bad ? Fr::zero() : fe_neg(k1);
+    const Fr k1 = crs_weight(w, i, ell, s_i, fe_mul(s_i_inv, u), s_m);
+    out_crs[i] = bad ? Fr::zero() : k1;
     // (2) instance part over R | S | T | U
     if (i < ell) {
-      const Fr va = d.veca[(size_t)v.p * ell + i];
-      out[i] = bad ? Fr::zero() : fe_neg(fe_mul(a7, va));
-      out[ell + i] = bad ? Fr::zero() : fe_neg(fe_mul(a8, va));
-      out[2 * ell + i] = bad ? Fr::zero() : fe_neg(fe_mul(a5x, s_m));
-      out[3 * ell + i] = bad ? Fr::zero() : fe_neg(fe_mul(a6x, s_m));
+      Fr k2[4];
+      instance_weights(w, d.veca[(size_t)v.p * ell + i], s_m, k2);
+      CPX_UNROLL for (int q = 0; q < 4; q++) out[q * ell + i] = bad ? Fr::zero() : k2[q];
     }
     if (i == ell + 2) sm_l2 = s_m;
     if (i == ell + 3) sm_l3 = s_m;
   }
   // s_m at the two positions the misc part needs: owned by the lanes (ell + 2) % 64 and (ell + 3) % 64
-  {
-    Fr t2 = sm_l2, t3 = sm_l3;
-    CPX_UNROLL for (int j = 0; j < 8; j++) {
-      t2.v[j] = (uint32_t)__shfl((int)sm_l2.v[j], (ell + 2) & 63, 64);
-      t3.v[j] = (uint32_t)__shfl((int)sm_l3.v[j], (ell + 3) & 63, 64);
-    }
-    sm_l2 = t2;
-    sm_l3 = t3;
+  CPX_UNROLL for (int j = 0; j < 8; j++) {
+    w.sm_l2.v[j] = (uint32_t)__shfl((int)sm_l2.v[j], (ell + 2) & 63, 64);
+    w.sm_l3.v[j] = (uint32_t)__shfl((int)sm_l3.v[j], (ell + 3) & 63, 64);
   }
-  // (3) misc part: singles, M, proof points.  Slot s sits at misc index s (SL_A == SL_M + 1).
-  Fr w1, w2, w3, w4;   // weights of the four SameScalar equalities (same_scalar_argument.rs:127-137; include/cpx.h)
-  if (d.rand_stride >= VF_FUSED_COUNT) {
-    w1 = rnd[VF_SS_A1];
-    w2 = rnd[VF_SS_A2];
-    w3 = rnd[VF_SS_B1];
-    w4 = rnd[VF_SS_B2];
-  } else {
-    w1 = fe_mul(a1, a2);
-    w2 = fe_mul(a3, a4);
-    w3 = fe_mul(a5, a6);
-    w4 = fe_mul(a7, a8);
-  }
-  const Fr a4am = fe_mul(a4, alpha_m), a5am = fe_mul(a5, alpha_m), a6am = fe_mul(a6, alpha_m), a3ai = fe_mul(a3, alpha_i);
-  for (int s = lane; s < d.NM; s += 64) {
-    Fr k = Fr::zero();
-    if (s == SL_H) {
-      k = fe_sub(fe_sub(fe_sub(fe_mul(a2, fe_mul(fe_mul(fe_mul(alpha_i, alpha_i), z_ip), beta_i)), fe_mul(fe_mul(a2c, d_fin), beta_i)), fe_mul(a5x, sm_l2)),
-                 fe_mul(a6x, sm_l3));
-      k = fe_sub(fe_sub(k, fe_mul(w2, z_t)), fe_mul(w4, z_u));
-    } else if (s == SL_GT) {
-      k = fe_neg(fe_add(fe_mul(a4x, sm_l2), fe_mul(w1, z_t)));
-    } else if (s == SL_GU) {
-      k = fe_neg(fe_add(fe_mul(a4x, sm_l3), fe_mul(w3, z_u)));
-    } else if (s == SL_GSUM) {
-      k = fe_neg(fe_mul(a3ai, beta_g_inv));
-    } else if (s == SL_HSUM) {
-      k = fe_mul(a3ai, alpha_g);
-    } else if (s == SL_M) {
-      k = fe_neg(fe_mul(a1, alpha_sp));
-    } else if (s == SL_A) {
-      k = fe_sub(a4am, a1);
-    } else if (s == SL_CMT1) {
-      k = fe_add(a4am, fe_mul(w1, alpha_s));
-    } else if (s == SL_CMT2) {
-      k = fe_add(a5am, fe_mul(w2, alpha_s));
-    } else if (s == SL_CMU1) {
-      k = fe_add(a4am, fe_mul(w3, alpha_s));
-    } else if (s == SL_CMU2) {
-      k = fe_add(a6am, fe_mul(w4, alpha_s));
-    } else if (s == SL_R) {
-      k = fe_sub(a7, fe_mul(w2, z_k));
-    } else if (s == SL_S) {
-      k = fe_sub(a8, fe_mul(w4, z_k));
-    } else if (s == SL_B) {
-      k = fe_add(a1, a3ai);
-    } else if (s == SL_C) {
-      k = fe_mul(a2, alpha_i);
-    } else if (s == SL_BC) {
-      k = a2;
-    } else if (s == SL_BD) {
-      k = a3;
-    } else if (s < sm.CMA1()) {   // IPA cross terms: L_C | R_C | L_D | R_D, L each
-      const int q = s - SL_IPA0, blk = q / L, j = q % L;
-      const Fr g = (blk & 1) ? gam_i_inv[j] : gam_i[j];
-      k = fe_mul(blk < 2 ? a2 : a3, g);
-    } else if (s == sm.CMA1()) {
-      k = w1;
-    } else if (s == sm.CMA2()) {
-      k = w2;
-    } else if (s == sm.CMB1()) {
-      k = w3;
-    } else if (s == sm.CMB2()) {
-      k = w4;
-    } else if (s == sm.BA()) {
-      k = a4;
-    } else if (s == sm.BT()) {
-      k = a5;
-    } else if (s == sm.BU()) {
-      k = a6;
-    } else {   // SameMSM cross terms: L_A | L_T | L_U | R_A | R_T | R_U, L each
-      const int q = s - sm.LA(0), blk = q / L, j = q % L;
-      const Fr g = blk < 3 ? gam_m[j] : gam_m_inv[j];
-      const int col = blk % 3;
-      k = fe_mul(col == 0 ? a4 : (col == 1 ? a5 : a6), g);
-    }
-    out[NI + s] = bad ? Fr::zero() : k;
-  }
+  // (3) misc part: singles, M, proof points: slot s sits at misc index s
+  w.set_same_scalar_weights(rnd, d.rand_stride >= VF_FUSED_COUNT);
+  for (int s = lane; s < d.NM; s += 64) out[NI + s] = bad ? Fr::zero() : misc_weight(w, sm, s);
 }
 
 // fused batch: sum over the proofs of the CRS scalars (the shared bases G | Hvec merge in Fr; msm_accumulator.rs:47-51)

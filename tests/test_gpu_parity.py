@@ -829,12 +829,67 @@ def _proof_offsets(ell):
     return off
 
 
-def test_same_scalar_relations_are_checked(ctx, orc):
+@pytest.fixture(params=["host_driven", "device_resident"])
+def path_ctx(request, ctx):
+    """a context on which a batch of four proofs takes the named verifier path: the module's context at its default options (the
+    host drives the transcripts below `device_min_batch` proofs), or one with that option lowered (everything on the GPU)"""
+    import curdleproofs_amd as cpx
+    if request.param == "host_driven":
+        assert ctx.get_option("device_min_batch") > 4
+        yield ctx
+    else:
+        c = cpx.Context(0, options={"device_min_batch": 1})
+        yield c
+        c.close()
+
+
+def test_fused_partial_sums_agree_between_the_verifier_paths(ctx, orc):
+    """The table of the accumulated check's weights (csrc/check_weights.hpp) as both verifier paths apply it.  The partial sum of a
+    fused batch that holds wrong proofs is sum_i weight_i . point_i != O and depends on every weight, so the same batch with the same
+    twelve factors per proof must give the same point on the host-driven path and on the device-resident one."""
+    import curdleproofs_amd as cpx
+    ell = 28
+    crs = orc.generate_crs_points(ell)
+    insts = [orc.make_instance(ell, s, crs) for s in (21, 22, 23, 24)]
+    cat = lambda key: b"".join(i[key] for i in insts)
+    frand = orc.rng(919).fr(12 * len(insts))
+    identity = bytes([0xc0]) + bytes(47)
+    proofs = [i["proof"] for i in insts]
+    off = _proof_offsets(ell)
+    rng = orc.rng(929)
+    wrong = list(proofs)
+    for victim, field, repl in ((1, "z_t", orc.fr_to_canonical_bytes(rng.fr(1))), (3, "L_T", orc.g1_compress(rng.g1_affine(1)))):
+        bad = bytearray(wrong[victim])
+        bad[off[field]:off[field] + len(repl)] = repl
+        wrong[victim] = bytes(bad)
+        x = insts[victim]
+        assert orc.verify(ell, crs, x["vec_R"], x["vec_S"], x["vec_T"], x["vec_U"], x["M"], wrong[victim], x["verifier_rand"]) == 0, field
+    assert ctx.get_option("device_min_batch") > len(insts)
+    dev = cpx.Context(0, options={"device_min_batch": 1})
+    try:
+        sums = []
+        for c in (ctx, dev):
+            c.set_crs(ell, crs)
+            c.load_batch(cat("vec_R"), cat("vec_S"), cat("vec_T"), cat("vec_U"), cat("M"))
+            part, nbad = c.verify_batch_fused_partial(proofs, frand)
+            assert nbad == 0 and orc.g1_compress_jac(part) == identity
+            part, nbad = c.verify_batch_fused_partial(wrong, frand)
+            assert nbad == 0
+            sums.append(orc.g1_compress_jac(part))
+        assert sums[0] == sums[1]
+        assert sums[0] != identity
+    finally:
+        dev.close()
+
+
+def test_same_scalar_relations_are_checked(path_ctx, orc):
     """same_scalar_argument.rs:96-137.  z_k, z_t, z_u are never absorbed into the transcript, so re-encoding a proof with
     one of them replaced by another canonical scalar breaks ONLY the SameScalar equalities (every challenge and every other
     check stays as it was): the verdict must be VerificationError, as the oracle's.  Same for cm_A.T_1 / cm_B.T_2 replaced
-    by another valid point.  Both verifier forms (per proof, fused) and a fused batch with exactly one such proof."""
+    by another valid point.  Both verifier forms (per proof, fused) and a fused batch with exactly one such proof, on the host-driven
+    and on the device-resident path."""
     import curdleproofs_amd as cpx
+    ctx = path_ctx
     ell = 28
     seeds = [11, 12, 13, 14]
     crs = orc.generate_crs_points(ell)
