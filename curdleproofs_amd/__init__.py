@@ -61,6 +61,7 @@ EXPORTS = [
     "cpx_accum_new", "cpx_accum_free", "cpx_accum_check", "cpx_accum_verify",
     "cpx_batch_load", "cpx_batch_load_begin", "cpx_batch_load_end", "cpx_batch_prove", "cpx_batch_verify", "cpx_batch_verify_fused", "cpx_g1_sum_jac",
     "cpx_whisk_generate_shuffle_proof", "cpx_whisk_is_valid_shuffle_proof", "cpx_whisk_generate_tracker_proof", "cpx_whisk_is_valid_tracker_proof",
+    "cpx_whisk_generate_tracker_proofs", "cpx_whisk_verify_tracker_proofs",
     "cpx_set_profiling", "cpx_reset_stats", "cpx_get_stat", "cpx_set_host_threads", "cpx_bench_fpmul",
 ]
 
@@ -127,6 +128,8 @@ def load_library(path=None):
     L.cpx_whisk_is_valid_shuffle_proof.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(ci)]
     L.cpx_whisk_generate_tracker_proof.argtypes = [vp, vp, vp, vp, vp]
     L.cpx_whisk_is_valid_tracker_proof.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ci)]
+    L.cpx_whisk_generate_tracker_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.cpx_whisk_verify_tracker_proofs.argtypes = [vp, sz, vp, vp, vp, vp]
     L.cpx_bench_fpmul.argtypes = [vp, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
     _libs[os.path.realpath(path)] = L
     if default:
@@ -422,7 +425,7 @@ class Context:
         return dict(launches=n.value, ms=ms.value, alg_bytes=by.value, units=un.value)
 
     KERNELS = ("k_msm_tblw<32, false>", "k_reduce_sets", "k_msm_tblw<16, false>", "k_msm_tblw<8, false>", "k_msm_tblw<4, false>", "k_msm_tblw<2, false>", "k_msm_fix<19, 7>", "k_msm_fix<16, 4>", "k_msm_fix<16, 2>", "k_msm_fix<16, 16>", "k_msm_fix<16, 8>", "k_msm_fix<8, 16>", "k_msm_fix<8, 8>",
-               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
+               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
 
     def stats(self):
         return {k: self.stat(k) for k in self.KERNELS}

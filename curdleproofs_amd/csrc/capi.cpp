@@ -342,6 +342,20 @@ int cpx_whisk_is_valid_tracker_proof(cpx_ctx* ctx, const uint8_t tracker[96], co
   if (!tracker || !k_commitment || !proof || !valid) return CPX_ERR_ARG;
   return guarded(ctx, [&] { return ctx->eng->whisk_is_valid_tracker_proof(tracker, k_commitment, proof, valid); });
 }
+int cpx_whisk_generate_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* trackers, const uint8_t* k, const uint8_t* blinders, uint8_t* proofs_out, int* status) {
+  if (count && (!trackers || !k || !blinders || !proofs_out || !status)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_generate_tracker_proofs(count, trackers, k, blinders, proofs_out, status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_whisk_verify_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, int* verdict) {
+  if (count && (!trackers || !k_commitments || !proofs || !verdict)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_verify_tracker_proofs(count, trackers, k_commitments, proofs, verdict);
+    return (int)CPX_OK;
+  });
+}
 
 int cpx_set_profiling(cpx_ctx* ctx, int on) {
   if (!ctx || !ctx->eng) return CPX_ERR_ARG;

@@ -184,6 +184,10 @@ class Engine {
   int whisk_is_valid_shuffle_proof(const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proof, const uint8_t* rand, int* valid);
   int whisk_generate_tracker_proof(const uint8_t tracker[96], const uint8_t k[32], const uint8_t blinder[32], uint8_t proof_out[128]);
   int whisk_is_valid_tracker_proof(const uint8_t tracker[96], const uint8_t k_commitment[48], const uint8_t proof[128], int* valid);
+  // the two tracker-proof functions for `count` independent items per call: a constant number of launches and one stream synchronisation
+  // (tracker.hip); status / verdict per item, the loaded batch and the CRS are not touched
+  void whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k, const uint8_t* blinders, uint8_t* proofs_out, int* status);
+  void whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, int* verdict);
 
   // ---- measurement ----
   void set_profiling(bool on) { profiling_ = on; }
@@ -322,6 +326,8 @@ class Engine {
     DevBuf<uint32_t> dig;
     DevBuf<uint8_t> bytes, status;
     DevBuf<int> flag;
+    DevBuf<Aff> gen;      // copies of the generator: the base of the batched tracker prover's k G and blinder G (whisk.cpp)
+    size_t gen_n = 0;     // how many of them are filled in
   } t0_;
   static constexpr size_t kTier0Keep = (size_t)64 << 20;
   template <class T> static void tier0_trim(DevBuf<T>& b) {

@@ -277,6 +277,24 @@ struct RoundDev {
 bool round_fused_supported(int fix_wpw, int tbl_wpw, bool ipa);
 void launch_round_fused(const RoundDev& rd, const ProveDev& d, int j, bool ipa, hipStream_t s);
 
+// ---- batched Whisk tracker proofs (tracker.hip): one launch each, whatever the count ----
+// ark_bls12_381::g1::G1Affine::generator(), compressed (whisk.rs:363-368 pins these bytes)
+#define CPX_G1_GENERATOR_COMPRESSED                                                                                                                           \
+  {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f, 0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05,           \
+   0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58, 0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb}
+// verifier: d_in = trackers [count][96] | k_commitments [count][48] | proofs [count][128]; d_status: decoding verdicts of the 5 count points,
+// plane-major A | B | k_r_G | r_G | k_G.  One wave per proof hashes the six-point transcript: d_chal[p] = the challenge (canonical),
+// d_bad[p] = 1 where a point did not decode or s >= r (such a proof is not hashed)
+void launch_tracker_challenge_verify(const uint8_t* d_in, const uint8_t* d_status, int count, Fr* d_chal, uint8_t* d_bad, hipStream_t s);
+// prover: d_comp = k_G | A | B compressed, [3][count][48]; d_status: r_G | k_r_G plane-major; d_k, d_blinder Montgomery form.  Writes
+// A || B || s per proof (128 zero bytes for an undecodable tracker) and d_verdict[p] = CPX_OK / CPX_ERR_DESERIALIZE
+void launch_tracker_challenge_prove(const uint8_t* d_trackers, const uint8_t* d_comp, const uint8_t* d_status, const Fr* d_k, const Fr* d_blinder, int count,
+                                    uint8_t* d_proofs_out, int* d_verdict, hipStream_t s);
+// the 2 count relations s G + c k_G == A, s r_G + c k_r_G == B, a quad each: d_pts = the decoded points [5][count] (order of d_status),
+// d_proofs [count][128]; d_verdict[p] = CPX_OK / CPX_ERR_VERIFY, CPX_ERR_DESERIALIZE where d_bad[p]
+void launch_tracker_relations(const Aff* d_pts, const uint8_t* d_proofs, const Fr* d_chal, const uint8_t* d_bad, const Aff& gen, int count, int* d_verdict,
+                              hipStream_t s);
+
 void launch_sum_jac(const Jac* d_in, int n, Jac* d_out, int* d_flag, hipStream_t s);
 void launch_bench_fpmul(Fp* d_data, int blocks, int iters, hipStream_t s);
 void launch_bench_f28mul(Fp* d_data, int blocks, int iters, hipStream_t s);

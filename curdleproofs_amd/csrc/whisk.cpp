@@ -14,10 +14,7 @@ using host::S;
 using host::Transcript;
 
 namespace {
-// ark_bls12_381::g1::G1Affine::generator(), compressed (whisk.rs:363-368 pins these bytes)
-const uint8_t GEN_COMP[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f,
-                              0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05, 0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58,
-                              0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
+const uint8_t GEN_COMP[48] = CPX_G1_GENERATOR_COMPRESSED;   // (kernels.h)
 
 struct DeserializeError {};   // ark_serialize::SerializationError
 
@@ -173,6 +170,163 @@ int Engine::whisk_is_valid_tracker_proof(const uint8_t tracker[96], const uint8_
   normalize(reinterpret_cast<const uint8_t*>(res), 2, nullptr, got);
   *valid = (memcmp(got, comp + 4 * 48, 96) == 0) ? 1 : 0;
   return CPX_OK;
+}
+
+// ---------------------------------------------------------------- tracker proofs, `count` per call (tracker.hip)
+// Both calls: the inputs go up once, a constant number of kernels runs whatever the count, the results come down and the stream is
+// synchronised once.  (The very first call of a context also decodes the generator: Engine::generator.)  Scratch is the tier-0 set.
+namespace {
+constexpr size_t kTrackerBatchMax = (size_t)1 << 23;   // 32-bit byte offsets into the uploaded inputs (272 B per proof) and int grids
+}
+
+// encoding j < planes * count of the decoder = the point at byte plane_off[j / count] + rec * (j % count) of the uploaded inputs:
+// plane-major, so that every family of points (all r_G, all A, ...) is one dense array for the kernels behind the decoder
+static void tracker_point_offsets(size_t count, const size_t* plane_off, const size_t* plane_rec, int planes, std::vector<uint32_t>& off) {
+  off.resize((size_t)planes * count);
+  for (int pl = 0; pl < planes; pl++)
+    for (size_t i = 0; i < count; i++) off[(size_t)pl * count + i] = (uint32_t)(plane_off[pl] + plane_rec[pl] * i);
+}
+
+// whisk.rs:183-226 is_valid_whisk_tracker_proof for every (tracker, k_commitment, proof) triple
+void Engine::whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, int* verdict) {
+  for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
+  if (!count) return;
+  if (count > kTrackerBatchMax) throw ArgError("tracker proofs: at most 2^23 per call");
+  CPX_HIP(hipSetDevice(device_));
+  const Aff G = generator();
+  // strict_infinity = 0: non-canonical infinity encodings are rewritten in COPIES of the inputs (canonical_infinities)
+  std::vector<uint8_t> keep[2];
+  auto canon = [&](const uint8_t* in, size_t rec, const std::vector<size_t>& offs, std::vector<uint8_t>* store) {
+    const uint8_t* p = canonical_infinities(in, count * rec, count, rec, offs);
+    if (p == in || !store) return p;
+    store->assign(p, p + count * rec);   // (canon_bytes_ is reused by the next array)
+    return (const uint8_t*)store->data();
+  };
+  trackers = canon(trackers, 96, {0, 48}, &keep[0]);
+  k_commitments = canon(k_commitments, 48, {0}, &keep[1]);
+  proofs = canon(proofs, 128, {0, 48}, nullptr);
+  struct Trim {
+    Engine* e;
+    ~Trim() {
+      tier0_trim(e->t0_.bytes);
+      tier0_trim(e->t0_.a0);
+      tier0_trim(e->t0_.dig);
+      tier0_trim(e->t0_.status);
+      tier0_trim(e->t0_.fr);
+      tier0_trim(e->t0_.flag);
+    }
+  } trim{this};
+  const int n = (int)count;
+  DevBuf<uint8_t>&din = t0_.bytes, &dst = t0_.status;   // trackers | k_commitments | proofs; 5 count decoding verdicts | count proof flags
+  DevBuf<uint32_t>& doff = t0_.dig;
+  DevBuf<Aff>& dpts = t0_.a0;
+  DevBuf<Fr>& dchal = t0_.fr;
+  DevBuf<int>& dver = t0_.flag;
+  din.ensure(272 * count);
+  dst.ensure(6 * count);
+  doff.ensure(5 * count);
+  dpts.ensure(5 * count);
+  dchal.ensure(count);
+  dver.ensure(count);
+  uint8_t *d_trk = din.p, *d_kc = din.p + 96 * count, *d_prf = din.p + 144 * count;
+  // the five points of proof i are read where they lie: A, B inside the proof, k_r_G, r_G inside the tracker, k_G
+  const size_t plane_off[5] = {144 * count, 144 * count + 48, 48, 0, 96 * count}, plane_rec[5] = {128, 128, 96, 96, 48};
+  std::vector<uint32_t> off;
+  tracker_point_offsets(count, plane_off, plane_rec, 5, off);
+  CPX_HIP(hipMemcpyAsync(d_trk, trackers, 96 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(d_kc, k_commitments, 48 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(d_prf, proofs, 128 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemsetAsync(dver.p, 0xff, count * sizeof(int), stream_));   // (-1: not CPX_OK)
+  tick("k_decompress", 0, 5.0 * count);
+  launch_decompress(opt_, din.p, 5 * n, dpts.p, nullptr, dst.p, 1, stream_, doff.p);
+  tock();
+  tick("k_tracker_challenge", 288.0 * count, (double)count);
+  launch_tracker_challenge_verify(din.p, dst.p, n, dchal.p, dst.p + 5 * count, stream_);
+  tock();
+  tick("k_tracker_relations", 0, 2.0 * count);
+  launch_tracker_relations(dpts.p, d_prf, dchal.p, dst.p + 5 * count, G, n, dver.p, stream_);
+  tock();
+  CPX_HIP(hipMemcpyAsync(verdict, dver.p, count * sizeof(int), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipStreamSynchronize(stream_));
+  flush_timers();
+}
+
+// whisk.rs:228-263 generate_whisk_tracker_proof for every (tracker, k, blinder) triple
+void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k, const uint8_t* blinders, uint8_t* proofs_out, int* status) {
+  for (size_t i = 0; i < count; i++) status[i] = CPX_ERR_INTERNAL;
+  if (!count) return;
+  if (count > kTrackerBatchMax) throw ArgError("tracker proofs: at most 2^23 per call");
+  CPX_HIP(hipSetDevice(device_));
+  const Aff G = generator();
+  trackers = canonical_infinities(trackers, 96 * count, count, 96, {0, 48});
+  struct Trim {
+    Engine* e;
+    ~Trim() {
+      tier0_trim(e->t0_.bytes);
+      tier0_trim(e->t0_.a0);
+      tier0_trim(e->t0_.a1);
+      tier0_trim(e->t0_.dig);
+      tier0_trim(e->t0_.status);
+      tier0_trim(e->t0_.fr);
+      tier0_trim(e->t0_.flag);
+      tier0_trim(e->t0_.gen);
+      if (!e->t0_.gen.p) e->t0_.gen_n = 0;
+    }
+  } trim{this};
+  const int n = (int)count;
+  DevBuf<uint8_t>&db = t0_.bytes, &dst = t0_.status;   // trackers | k_G, A, B compressed | proofs
+  DevBuf<uint32_t>& doff = t0_.dig;
+  DevBuf<Aff>&dtr = t0_.a0, &dout = t0_.a1, &dgen = t0_.gen;   // r_G | k_r_G; k G | blinder G | blinder r_G
+  DevBuf<Fr>& dsc = t0_.fr;                                    // k | blinder
+  DevBuf<SmulTask>& dtask = t0_.stask;
+  DevBuf<int>& dver = t0_.flag;
+  db.ensure(368 * count);
+  dst.ensure(2 * count);
+  doff.ensure(2 * count);
+  dtr.ensure(2 * count);
+  dout.ensure(3 * count);
+  dsc.ensure(2 * count);
+  dtask.ensure(3);
+  dver.ensure(count);
+  if (t0_.gen_n < count) {   // grows with the largest call; filled once
+    dgen.ensure(count);
+    std::vector<Aff> g(count, G);
+    CPX_HIP(hipMemcpyAsync(dgen.p, g.data(), count * sizeof(Aff), hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipStreamSynchronize(stream_));   // (g leaves scope; only when the buffer grows)
+    t0_.gen_n = count;
+  }
+  uint8_t *d_trk = db.p, *d_comp = db.p + 96 * count, *d_prf = db.p + 240 * count;
+  const size_t plane_off[2] = {0, 48}, plane_rec[2] = {96, 96};
+  std::vector<uint32_t> off;
+  tracker_point_offsets(count, plane_off, plane_rec, 2, off);
+  const uint32_t fl = opt_.scale_any_point ? SMUL_PLAIN : 0u;   // (as Engine::scale)
+  const SmulTask tasks[3] = {{nullptr, dgen.p, dout.p, dsc.p, 1, fl},                              // k_G = k G
+                             {nullptr, dgen.p, dout.p + count, dsc.p + count, 1, fl},              // A = blinder G
+                             {nullptr, dtr.p, dout.p + 2 * count, dsc.p + count, 1, fl}};          // B = blinder r_G
+  CPX_HIP(hipMemcpyAsync(d_trk, trackers, 96 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(dsc.p, k, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(dsc.p + count, blinders, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(dtask.p, tasks, sizeof tasks, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemsetAsync(dver.p, 0xff, count * sizeof(int), stream_));
+  CPX_HIP(hipMemsetAsync(d_prf, 0, 128 * count, stream_));
+  tick("k_decompress", 0, 2.0 * count);
+  launch_decompress(opt_, db.p, 2 * n, dtr.p, nullptr, dst.p, 1, stream_, doff.p);
+  tock();
+  tick("k_smul", 224.0 * 3 * count, 3.0 * count);
+  launch_smul(dtask.p, 3, n, stream_, false, fl ? 0 : opt_.smul_quad_max);
+  tock();
+  tick("k_compress", 0, 3.0 * count);
+  launch_compress(dout.p, 3 * n, 3 * n, 1, d_comp, stream_);
+  tock();
+  tick("k_tracker_challenge", 288.0 * count, (double)count);
+  launch_tracker_challenge_prove(d_trk, d_comp, dst.p, dsc.p, dsc.p + count, n, d_prf, dver.p, stream_);
+  tock();
+  CPX_HIP(hipMemcpyAsync(proofs_out, d_prf, 128 * count, hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(status, dver.p, count * sizeof(int), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipStreamSynchronize(stream_));
+  flush_timers();
 }
 
 }  // namespace cpx

@@ -9,7 +9,7 @@ are omitted — draws them from the OS CSPRNG (`secrets`), which is what a produ
 import ctypes
 import secrets
 
-from . import AFF, FR, CPX_ERR_DESERIALIZE, CPX_OK, CpxError, _in, _out   # noqa: F401
+from . import AFF, FR, CPX_ERR_DESERIALIZE, CPX_ERR_INTERNAL, CPX_ERR_VERIFY, CPX_OK, CpxError, _in, _out   # noqa: F401
 from . import params as pr
 
 FIELD_ELEMENT_SIZE = 32        # whisk.rs:21
@@ -124,6 +124,60 @@ def is_valid_whisk_tracker_proof(ctx, tracker, k_commitment, tracker_proof):
     valid = ctypes.c_int(0)
     _check(ctx, ctx._L.cpx_whisk_is_valid_tracker_proof(ctx._h, _in(tracker.to_bytes()), _in(k_commitment), _in(tracker_proof), ctypes.byref(valid)))
     return bool(valid.value)
+
+
+# ---- many tracker proofs per call (cpx_whisk_generate_tracker_proofs / cpx_whisk_verify_tracker_proofs) ----
+def generate_whisk_tracker_proofs(ctx, trackers, ks, blinders=None):
+    """whisk.rs:228-263 for every (tracker, k, blinder) triple in ONE library call (a constant number of kernel launches).
+    ks / blinders: lists of 32-byte wire scalars; omitted blinders come from the OS CSPRNG.  Returns a list of 128-byte proofs, with
+    None where the tracker does not decode (the reference's SerializationError); nothing is raised per item."""
+    count = len(trackers)
+    blinders = [_rand_fr(1) for _ in range(count)] if blinders is None else blinders
+    if len(ks) != count or len(blinders) != count:
+        raise ValueError("one k and one blinder per tracker")
+    if any(len(x) != FR for x in ks) or any(len(x) != FR for x in blinders):
+        raise ValueError("k and blinder are 32-byte wire scalars")
+    if count == 0:
+        return []
+    out = _out(TRACKER_PROOF_SIZE * count)
+    status = (ctypes.c_int * count)(*([CPX_ERR_INTERNAL] * count))   # an entry the library does not write is never read as a proof
+    ctx._check(ctx._L.cpx_whisk_generate_tracker_proofs(ctx._h, count, _in(_cat(trackers)), _in(b"".join(ks)), _in(b"".join(blinders)), out, status))
+    blob = bytes(out)
+    res = []
+    for i, st in enumerate(status):
+        if st not in (CPX_OK, CPX_ERR_DESERIALIZE):
+            raise CpxError(st, "tracker proof %d" % i)
+        res.append(blob[TRACKER_PROOF_SIZE * i:TRACKER_PROOF_SIZE * (i + 1)] if st == CPX_OK else None)
+    return res
+
+
+def are_valid_whisk_tracker_proofs(ctx, trackers, k_commitments, proofs):
+    """whisk.rs:183-226 for every (tracker, k_commitment, proof) triple in ONE library call.  Returns a list with True / False, or a
+    SerializationError INSTANCE where the reference returns Err (undecodable point, s >= r, wrong length); nothing is raised per item."""
+    count = len(trackers)
+    if len(k_commitments) != count or len(proofs) != count:
+        raise ValueError("one k_commitment and one proof per tracker")
+    if count == 0:
+        return []
+    # a wrong length is a fixed-size array mismatch in the reference: reported per item, the library sees a well-formed dummy
+    short = [len(c) != G1POINT_SIZE or len(p) != TRACKER_PROOF_SIZE for c, p in zip(k_commitments, proofs)]
+    kc = b"".join(bytes(G1POINT_SIZE) if s else c for s, c in zip(short, k_commitments))
+    pf = b"".join(bytes(TRACKER_PROOF_SIZE) if s else p for s, p in zip(short, proofs))
+    verdict = (ctypes.c_int * count)(*([CPX_ERR_INTERNAL] * count))   # an entry the library does not write is never read as accepted
+    ctx._check(ctx._L.cpx_whisk_verify_tracker_proofs(ctx._h, count, _in(_cat(trackers)), _in(kc), _in(pf), verdict))
+    res = []
+    for i, v in enumerate(verdict):
+        if short[i]:
+            res.append(SerializationError("wrong length"))
+        elif v == CPX_OK:
+            res.append(True)
+        elif v == CPX_ERR_VERIFY:
+            res.append(False)
+        elif v == CPX_ERR_DESERIALIZE:
+            res.append(SerializationError("tracker proof %d" % i))
+        else:
+            raise CpxError(v, "tracker proof %d" % i)
+    return res
 
 
 # ---- small helpers of whisk.rs:295-345 ----

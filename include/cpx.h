@@ -196,6 +196,19 @@ int cpx_whisk_is_valid_shuffle_proof(cpx_ctx* ctx, const uint8_t* pre_trackers, 
 int cpx_whisk_generate_tracker_proof(cpx_ctx* ctx, const uint8_t tracker[96], const uint8_t k[32], const uint8_t blinder[32], uint8_t proof_out[128]);
 /* whisk.rs:183-226 `is_valid_whisk_tracker_proof(tracker, k_commitment, tracker_proof)` */
 int cpx_whisk_is_valid_tracker_proof(cpx_ctx* ctx, const uint8_t tracker[96], const uint8_t k_commitment[48], const uint8_t proof[128], int* valid);
+/* The two tracker-proof functions for `count` independent items per call: a constant number of kernel launches and ONE stream
+ * synchronisation whatever the count (the single calls above cost several synchronisations per proof).  Scalars as above: k and
+ * blinders are 32-byte Montgomery limbs, s inside a proof is 32 bytes little-endian canonical.  Both return CPX_OK whatever the
+ * per-item results are (the convention of cpx_batch_verify and cpx_g1_decompress_status); NULL pointers with count > 0 are CPX_ERR_ARG,
+ * count = 0 is a no-op.  Neither needs a CRS, neither touches the loaded batch (cpx_batch_size is unchanged).  At most 2^23 items per call. */
+/* whisk.rs:228-263 `generate_whisk_tracker_proof` for `count` independent (tracker, k, blinder) triples.
+ *   status[i]: CPX_OK, or CPX_ERR_DESERIALIZE (undecodable tracker; proofs_out[i] is then 128 zero bytes). */
+int cpx_whisk_generate_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* trackers /* count*96 */, const uint8_t* k /* count*32 */,
+                                      const uint8_t* blinders /* count*32 */, uint8_t* proofs_out /* count*128 */, int* status /* count */);
+/* whisk.rs:183-226 `is_valid_whisk_tracker_proof` for `count` independent (tracker, k_commitment, proof) triples.
+ *   verdict[i]: CPX_OK = Ok(true), CPX_ERR_VERIFY = Ok(false), CPX_ERR_DESERIALIZE = Err(SerializationError). */
+int cpx_whisk_verify_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* trackers /* count*96 */, const uint8_t* k_commitments /* count*48 */,
+                                    const uint8_t* proofs /* count*128 */, int* verdict /* count */);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 int cpx_set_profiling(cpx_ctx* ctx, int on); /* time every kernel group with HIP events on the ctx stream */

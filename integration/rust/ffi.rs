@@ -74,6 +74,11 @@ extern "C" {
                                             valid: *mut c_int) -> c_int;
     pub fn cpx_whisk_generate_tracker_proof(ctx: *mut cpx_ctx, tracker: *const u8, k: *const u8, blinder: *const u8, proof_out: *mut u8) -> c_int;
     pub fn cpx_whisk_is_valid_tracker_proof(ctx: *mut cpx_ctx, tracker: *const u8, k_commitment: *const u8, proof: *const u8, valid: *mut c_int) -> c_int;
+    // `count` tracker proofs per call: per-item status / verdict, the call itself returns CPX_OK
+    pub fn cpx_whisk_generate_tracker_proofs(ctx: *mut cpx_ctx, count: usize, trackers: *const u8, k: *const u8, blinders: *const u8, proofs_out: *mut u8,
+                                             status: *mut c_int) -> c_int;
+    pub fn cpx_whisk_verify_tracker_proofs(ctx: *mut cpx_ctx, count: usize, trackers: *const u8, k_commitments: *const u8, proofs: *const u8,
+                                           verdict: *mut c_int) -> c_int;
 }
 
 pub const AFF: usize = 96;

@@ -89,3 +89,49 @@ pub fn generate_whisk_tracker_proof<T: RngCore>(rng: &mut T, tracker: &WhiskTrac
     map_rc(unsafe { cpx_whisk_generate_tracker_proof(ctx(), t.as_ptr(), scalars_ptr(std::slice::from_ref(k)), scalars_ptr(std::slice::from_ref(&blinder)), out.as_mut_ptr()) })?;
     Ok(out)
 }
+
+/// whisk.rs:183-226 for many (tracker, k_commitment, proof) triples in one library call: one result per item, in order
+pub fn are_valid_whisk_tracker_proofs(
+    trackers: &[WhiskTracker],
+    k_commitments: &[[u8; 48]],
+    tracker_proofs: &[TrackerProofBytes],
+) -> Vec<Result<bool, SerializationError>> {
+    assert!(trackers.len() == k_commitments.len() && trackers.len() == tracker_proofs.len());
+    let count = trackers.len();
+    let kc: Vec<u8> = k_commitments.iter().flat_map(|c| c.iter().copied()).collect();
+    let pf: Vec<u8> = tracker_proofs.iter().flat_map(|p| p.iter().copied()).collect();
+    let mut verdict = vec![CPX_ERR_INTERNAL; count]; // an entry the library does not write is never read as accepted
+    let rc = unsafe { cpx_whisk_verify_tracker_proofs(ctx(), count, trackers_to_wire(trackers).as_ptr(), kc.as_ptr(), pf.as_ptr(), verdict.as_mut_ptr()) };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    verdict
+        .into_iter()
+        .map(|v| match v {
+            CPX_OK => Ok(true),
+            CPX_ERR_VERIFY => Ok(false),
+            CPX_ERR_DESERIALIZE => Err(SerializationError::InvalidData),
+            v => panic!("libcpx: {}", v),
+        })
+        .collect()
+}
+
+/// whisk.rs:228-263 for many (tracker, k) pairs in one library call; the blinders are drawn in item order (:238)
+pub fn generate_whisk_tracker_proofs<T: RngCore>(rng: &mut T, trackers: &[WhiskTracker], ks: &[Fr]) -> Vec<Result<TrackerProofBytes, SerializationError>> {
+    assert!(trackers.len() == ks.len());
+    let count = trackers.len();
+    let blinders: Vec<Fr> = (0..count).map(|_| Fr::rand(rng)).collect();
+    let mut out = vec![0u8; TRACKER_PROOF_SIZE * count];
+    let mut status = vec![CPX_ERR_INTERNAL; count];
+    let rc = unsafe {
+        cpx_whisk_generate_tracker_proofs(ctx(), count, trackers_to_wire(trackers).as_ptr(), scalars_ptr(ks), scalars_ptr(&blinders), out.as_mut_ptr(), status.as_mut_ptr())
+    };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    status
+        .iter()
+        .zip(out.chunks(TRACKER_PROOF_SIZE))
+        .map(|(st, p)| match *st {
+            CPX_OK => Ok(p.try_into().unwrap()),
+            CPX_ERR_DESERIALIZE => Err(SerializationError::InvalidData),
+            st => panic!("libcpx: {}", st),
+        })
+        .collect()
+}
