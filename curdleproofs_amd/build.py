@@ -26,6 +26,9 @@ SELFCHECK = os.path.join(OUT_DIR, "quad_selfcheck")
 # library does not depend on it: a tree without the tests' source builds libcpx.so alone.
 FIELDCHECK = os.path.join(OUT_DIR, "field_check")
 FIELDCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "field_check.hip")
+# test-only device program: the three transcript implementations at every position of the rate (tests/test_gpu_transcript.py)
+TRANSCRIPTCHECK = os.path.join(OUT_DIR, "transcript_check")
+TRANSCRIPTCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "transcript_check.hip")
 DEVICE_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-I", CSRC]   # the library's device flags
 
 
@@ -38,11 +41,12 @@ def _hipcc():
 
 def _stale():
     check = os.path.exists(FIELDCHECK_SRC)
-    outs = [LIB] + ([FIELDCHECK] if check else [])
+    tcheck = os.path.exists(TRANSCRIPTCHECK_SRC)
+    outs = [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else [])
     if not all(os.path.exists(o) for o in outs):
         return True
     t = min(os.path.getmtime(o) for o in outs)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else [])
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else [])
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -89,6 +93,10 @@ def build(force=False, verbose=False):
             check = os.path.exists(FIELDCHECK_SRC)
             if check:
                 procs.append(("field_check.hip", subprocess.Popen(_fieldcheck_cmd(tmp_check), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+            tmp_tcheck = os.path.join(work, "transcript_check")
+            tcheck = os.path.exists(TRANSCRIPTCHECK_SRC)
+            if tcheck:
+                procs.append(("transcript_check.hip", subprocess.Popen(_transcriptcheck_cmd(tmp_tcheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
             for src, p in procs:
                 out, _ = p.communicate()
                 if p.returncode != 0:
@@ -101,6 +109,8 @@ def build(force=False, verbose=False):
             os.replace(tmp_lib, LIB)
             if check:
                 os.replace(tmp_check, FIELDCHECK)
+            if tcheck:
+                os.replace(tmp_tcheck, TRANSCRIPTCHECK)
         finally:
             shutil.rmtree(work, ignore_errors=True)
         build_selfcheck()
@@ -129,6 +139,21 @@ def build_fieldcheck():
     subprocess.check_call(_fieldcheck_cmd(FIELDCHECK + ".tmp"))
     os.replace(FIELDCHECK + ".tmp", FIELDCHECK)
     return FIELDCHECK
+
+
+def _transcriptcheck_cmd(out):
+    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [TRANSCRIPTCHECK_SRC, "-o", out]
+
+
+def build_transcriptcheck():
+    """The device build of tests/device/transcript_check.hip alone (build() compiles it with the library; the host twin is compiled
+    by the tests with g++): cross-compiled here, it travels with the library."""
+    if not os.path.exists(TRANSCRIPTCHECK_SRC):
+        raise RuntimeError("tests/device/transcript_check.hip is missing: the device transcript check cannot be built")
+    os.makedirs(OUT_DIR, exist_ok=True)
+    subprocess.check_call(_transcriptcheck_cmd(TRANSCRIPTCHECK + ".tmp"))
+    os.replace(TRANSCRIPTCHECK + ".tmp", TRANSCRIPTCHECK)
+    return TRANSCRIPTCHECK
 
 
 if __name__ == "__main__":

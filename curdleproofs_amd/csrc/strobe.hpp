@@ -138,27 +138,29 @@ struct Strobe {
   // CurdleproofsTranscript::get_and_append_challenge (transcript.rs:40-60): 64 challenge bytes, Fr::from_random_bytes
   // on them (first 32 bytes, top bit cleared, must be canonical), retried until non-zero; the scalar is appended
   // back under the same label.  Output: canonical little-endian limbs (NOT Montgomery).
+  // One attempt: false when the bytes were refused (the caller retries; nothing was appended).
+  CPX_HD bool challenge_attempt_canonical(const char* label, uint32_t e[8]) {
+    uint8_t buf[64];
+    challenge_bytes(label, buf, 64);
+    buf[31] &= 0x7f;
+    bool nz = false;
+    for (int i = 0; i < 8; i++) {
+      e[i] = (uint32_t)buf[4 * i] | ((uint32_t)buf[4 * i + 1] << 8) | ((uint32_t)buf[4 * i + 2] << 16) | ((uint32_t)buf[4 * i + 3] << 24);
+      nz |= e[i] != 0;
+    }
+    bool lt = false;   // e < r ?
+    for (int i = 7; i >= 0; i--) {
+      if (e[i] != FrCfg::P[i]) {
+        lt = e[i] < FrCfg::P[i];
+        break;
+      }
+    }
+    if (!(lt && nz)) return false;
+    append_message(label, buf, 32);   // append_scalar: the canonical 32 bytes
+    return true;
+  }
   CPX_HD void challenge_scalar_canonical(const char* label, uint32_t e[8]) {
-    for (;;) {
-      uint8_t buf[64];
-      challenge_bytes(label, buf, 64);
-      buf[31] &= 0x7f;
-      bool nz = false;
-      for (int i = 0; i < 8; i++) {
-        e[i] = (uint32_t)buf[4 * i] | ((uint32_t)buf[4 * i + 1] << 8) | ((uint32_t)buf[4 * i + 2] << 16) | ((uint32_t)buf[4 * i + 3] << 24);
-        nz |= e[i] != 0;
-      }
-      bool lt = false;   // e < r ?
-      for (int i = 7; i >= 0; i--) {
-        if (e[i] != FrCfg::P[i]) {
-          lt = e[i] < FrCfg::P[i];
-          break;
-        }
-      }
-      if (lt && nz) {
-        append_message(label, buf, 32);   // append_scalar: the canonical 32 bytes
-        return;
-      }
+    while (!challenge_attempt_canonical(label, e)) {
     }
   }
 };

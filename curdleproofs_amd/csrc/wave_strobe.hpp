@@ -19,13 +19,14 @@
 //   * iota: the round constant's even / odd bits into word 0 of each half.
 // Message bytes are absorbed four per lane (the lower half owns bytes 0..3 of a word, the upper half bytes 4..7), un-shuffled into
 // even | odd bits and exchanged with the partner lane.  Same semantics as strobe.hpp (the host's code, merlin 3.0.0 as used by
-// transcript.rs:28-60 of the reference), pinned by the bit-exact proof tests and by scripts/micro/keccak_micro.hip against the host
+// transcript.rs:28-60 of the reference), pinned by tests/device/transcript_check.hip at every position of the rate, by the bit-exact proof tests and by scripts/micro/keccak_micro.hip against the host
 // permutation.  Values the callers use (challenges, pos) are uniform over the wave.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "mont32.hpp"
 #include "strobe.hpp"
+#include "bit_interleave.hpp"
 
 namespace cpx {
 
@@ -34,34 +35,6 @@ namespace cpx {
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
-}
-
-// perfect outer un-shuffle of 32 bits: even bits -> low 16, odd bits -> high 16 (Hacker's Delight 7-2), and its inverse
-CPX_HD uint32_t bits_unshuffle32(uint32_t x) {
-  uint32_t t;
-  t = (x ^ (x >> 1)) & 0x22222222u; x ^= t ^ (t << 1);
-  t = (x ^ (x >> 2)) & 0x0c0c0c0cu; x ^= t ^ (t << 2);
-  t = (x ^ (x >> 4)) & 0x00f000f0u; x ^= t ^ (t << 4);
-  t = (x ^ (x >> 8)) & 0x0000ff00u; x ^= t ^ (t << 8);
-  return x;
-}
-CPX_HD uint32_t bits_shuffle32(uint32_t x) {
-  uint32_t t;
-  t = (x ^ (x >> 8)) & 0x0000ff00u; x ^= t ^ (t << 8);
-  t = (x ^ (x >> 4)) & 0x00f000f0u; x ^= t ^ (t << 4);
-  t = (x ^ (x >> 2)) & 0x0c0c0c0cu; x ^= t ^ (t << 2);
-  t = (x ^ (x >> 1)) & 0x22222222u; x ^= t ^ (t << 1);
-  return x;
-}
-// 64-bit word <-> (even bits, odd bits)
-CPX_HD void bits_split64(uint64_t v, uint32_t& even, uint32_t& odd) {
-  const uint32_t lo = bits_unshuffle32((uint32_t)v), hi = bits_unshuffle32((uint32_t)(v >> 32));
-  even = (lo & 0xffffu) | (hi << 16);
-  odd = (lo >> 16) | (hi & 0xffff0000u);
-}
-CPX_HD uint64_t bits_join64(uint32_t even, uint32_t odd) {
-  const uint32_t lo = bits_shuffle32((even & 0xffffu) | (odd << 16)), hi = bits_shuffle32((even >> 16) | (odd & 0xffff0000u));
-  return ((uint64_t)hi << 32) | lo;
 }
 
 struct KeccakRC {   // the 24 round constants as (even bits, odd bits)
