@@ -62,6 +62,7 @@ EXPORTS = [
     "cpx_batch_load", "cpx_batch_load_begin", "cpx_batch_load_end", "cpx_batch_prove", "cpx_batch_verify", "cpx_batch_verify_fused", "cpx_g1_sum_jac",
     "cpx_whisk_generate_shuffle_proof", "cpx_whisk_is_valid_shuffle_proof", "cpx_whisk_generate_tracker_proof", "cpx_whisk_is_valid_tracker_proof",
     "cpx_whisk_generate_tracker_proofs", "cpx_whisk_verify_tracker_proofs",
+    "cpx_batch_shuffle", "cpx_whisk_generate_shuffle_proofs", "cpx_whisk_verify_shuffle_proofs",
     "cpx_set_profiling", "cpx_reset_stats", "cpx_get_stat", "cpx_set_host_threads", "cpx_bench_fpmul",
 ]
 
@@ -130,6 +131,9 @@ def load_library(path=None):
     L.cpx_whisk_is_valid_tracker_proof.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ci)]
     L.cpx_whisk_generate_tracker_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.cpx_whisk_verify_tracker_proofs.argtypes = [vp, sz, vp, vp, vp, vp]
+    L.cpx_batch_shuffle.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.cpx_whisk_generate_shuffle_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.cpx_whisk_verify_shuffle_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.cpx_bench_fpmul.argtypes = [vp, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
     _libs[os.path.realpath(path)] = L
     if default:
@@ -386,6 +390,27 @@ class Context:
         self._check(self._L.cpx_batch_verify(self._h, _in(blob), _in(rand), verdict))
         return list(verdict)
 
+    def shuffle_batch(self, vec_R, vec_S, permutations, k, vec_m_blinders):
+        """util.rs:83-106 for every instance in ONE library call (cpx_batch_shuffle): vec_R / vec_S hold count * ell affine points,
+        permutations count * ell entries, k count scalars, vec_m_blinders 4 per instance.  Returns (vec_T, vec_U, M) — affine, affine,
+        Jacobian, concatenated per instance — and leaves the count instances loaded (self.batch == count)."""
+        if self.ell is None:
+            raise CpxError(CPX_ERR_STATE, "set_crs first")
+        ell = self.ell
+        count = _len(k) // FR
+        if not isinstance(permutations, ctypes.Array):
+            if len(permutations) != count * ell:
+                raise ValueError("permutations: count * ell entries")
+            permutations = (ctypes.c_uint32 * max(count * ell, 1))(*permutations)
+        if (_len(k) != count * FR or _len(vec_R) != count * ell * AFF or _len(vec_S) != count * ell * AFF or _len(vec_m_blinders) != count * N_BLINDERS * FR
+                or ctypes.sizeof(permutations) != 4 * max(count * ell, 1)):
+            raise ValueError("shuffle_batch: per instance ell affine points in vec_R and vec_S, ell u32 permutation entries, k (32 B), 4 blinders")
+        if count == 0:
+            return b"", b"", b""
+        t, u, m = _out(count * ell * AFF), _out(count * ell * AFF), _out(count * JAC)
+        self._check(self._L.cpx_batch_shuffle(self._h, count, _in(vec_R), _in(vec_S), permutations, _in(k), _in(vec_m_blinders), t, u, m))
+        return bytes(t), bytes(u), bytes(m)
+
     # ---- measurement ----
     def verify_batch_fused_partial(self, proofs, rand):
         """BASELINE config 5: one accumulated MSM over all loaded proofs.  `rand`: 12 Fr per proof.
@@ -425,7 +450,7 @@ class Context:
         return dict(launches=n.value, ms=ms.value, alg_bytes=by.value, units=un.value)
 
     KERNELS = ("k_msm_tblw<32, false>", "k_reduce_sets", "k_msm_tblw<16, false>", "k_msm_tblw<8, false>", "k_msm_tblw<4, false>", "k_msm_tblw<2, false>", "k_msm_fix<19, 7>", "k_msm_fix<16, 4>", "k_msm_fix<16, 2>", "k_msm_fix<16, 16>", "k_msm_fix<16, 8>", "k_msm_fix<8, 16>", "k_msm_fix<8, 8>",
-               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
+               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
 
     def stats(self):
         return {k: self.stat(k) for k in self.KERNELS}

@@ -357,6 +357,31 @@ int cpx_whisk_verify_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* t
   });
 }
 
+int cpx_batch_shuffle(cpx_ctx* ctx, size_t count, const uint8_t* vec_R, const uint8_t* vec_S, const uint32_t* permutation, const uint8_t* k,
+                      const uint8_t* vec_m_blinders, uint8_t* vec_T_out, uint8_t* vec_U_out, uint8_t* M_out) {
+  if (count && (!vec_R || !vec_S || !permutation || !k || !vec_m_blinders)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->shuffle_batch(count, vec_R, vec_S, permutation, k, vec_m_blinders, vec_T_out, vec_U_out, M_out);
+    return (int)CPX_OK;
+  });
+}
+int cpx_whisk_generate_shuffle_proofs(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers, const uint32_t* permutation, const uint8_t* k,
+                                      const uint8_t* vec_m_blinders, const uint8_t* rand, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status) {
+  if (count && (!pre_trackers || !permutation || !k || !vec_m_blinders || !rand || !post_trackers_out || !proofs_out || !status)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_generate_shuffle_proofs(count, pre_trackers, permutation, k, vec_m_blinders, rand, post_trackers_out, proofs_out, status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_whisk_verify_shuffle_proofs(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs,
+                                    const uint8_t* rand, int* verdict) {
+  if (count && (!pre_trackers || !post_trackers || !proofs || !rand || !verdict)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_verify_shuffle_proofs(count, pre_trackers, post_trackers, proofs, rand, verdict);
+    return (int)CPX_OK;
+  });
+}
+
 int cpx_set_profiling(cpx_ctx* ctx, int on) {
   if (!ctx || !ctx->eng) return CPX_ERR_ARG;
   ctx->eng->set_profiling(on != 0);

@@ -24,6 +24,7 @@
 #include "host_threads.hpp"
 #include "kernels.h"
 #include "protocol.h"
+#include "shuffle_plan.hpp"
 #include "tbl_plan.hpp"
 
 namespace cpx {
@@ -188,6 +189,13 @@ class Engine {
   // (tracker.hip); status / verdict per item, the loaded batch and the CRS are not touched
   void whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k, const uint8_t* blinders, uint8_t* proofs_out, int* status);
   void whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, int* verdict);
+  // the shuffle step and the two shuffle-proof functions for `count` independent shuffles per call (shuffle.hip): compressed bytes in, compressed
+  // bytes out, nothing returns to the host between the uploads and the batch prover / verifier; the count instances become the loaded batch
+  void shuffle_batch(size_t count, const uint8_t* vec_R, const uint8_t* vec_S, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
+                     uint8_t* vec_T_out, uint8_t* vec_U_out, uint8_t* M_out);
+  void whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
+                                     const uint8_t* rand, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status);
+  void whisk_verify_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand, int* verdict);
 
   // ---- measurement ----
   void set_profiling(bool on) { profiling_ = on; }
@@ -329,6 +337,18 @@ class Engine {
     DevBuf<Aff> gen;      // copies of the generator: the base of the batched tracker prover's k G and blinder G (whisk.cpp)
     size_t gen_n = 0;     // how many of them are filled in
   } t0_;
+  // Scratch of the batched shuffle calls (whisk.cpp), kept and trimmed like the tier-0 set
+  struct ShuffleBufs {
+    DevBuf<uint8_t> bytes, status, bad;   // uploaded encodings, then the compressed post trackers; decoding verdicts; per-item flags
+    DevBuf<uint32_t> off, perm;
+    DevBuf<Aff> pts, kpts, tu, zip;       // decoded planes R | S (| T | U | M); k R | k S; T | U; (T_j, U_j) interleaved
+    DevBuf<Fr> fr;                        // k | blinders | the scalars of M
+    DevBuf<Jac> mjac;
+    DevBuf<SmulTask> stask;
+  } sh_;
+  // vec_T, vec_U and M of the plan's items from the device-resident vec_R | vec_S (sh_.pts), permutations, k and M scalars; loads the batch
+  void shuffle_device(const ShufflePlan& pl);
+  void shuffle_trim();
   static constexpr size_t kTier0Keep = (size_t)64 << 20;
   template <class T> static void tier0_trim(DevBuf<T>& b) {
     if (b.cap * sizeof(T) > kTier0Keep) b.release();

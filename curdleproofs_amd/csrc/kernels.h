@@ -295,6 +295,18 @@ void launch_tracker_challenge_prove(const uint8_t* d_trackers, const uint8_t* d_
 void launch_tracker_relations(const Aff* d_pts, const uint8_t* d_proofs, const Fr* d_chal, const uint8_t* d_bad, const Aff& gen, int count, int* d_verdict,
                               hipStream_t s);
 
+// ---- batched Whisk shuffle calls (shuffle.hip; index arithmetic in shuffle_plan.hpp): one launch each, whatever the count ----
+struct ShufflePlan;
+// d_status (nullable: nothing was decoded): the decoder's verdicts of the plan's points; d_pts: the decoded planes, the rows of an item with a
+// bad point are overwritten by `gen`; d_bad[i] = 1 for such an item.  Prover form: d_msc[i][ell + 4] = sigma_i | blinders_i in Montgomery
+// form (d_perm [count][ell], d_blinders [count][4]).  Verifier form: d_mjac[i] = the decoded M of item i.
+void launch_shuffle_status(const ShufflePlan& pl, const uint8_t* d_status, Aff* d_pts, const Aff& gen, const uint32_t* d_perm, const Fr* d_blinders, Fr* d_msc,
+                           Jac* d_mjac, uint8_t* d_bad, hipStream_t s);
+// T[i][j] = kr[i][perm[i][j]], U likewise: dense [count][ell] in d_t / d_u and interleaved [count][ell][2] in d_zipped
+void launch_shuffle_gather(const ShufflePlan& pl, const uint32_t* d_perm, const Aff* d_kr, const Aff* d_ks, Aff* d_t, Aff* d_u, Aff* d_zipped, hipStream_t s);
+// d_mjac[i] = the affine point d_pp[i * pp_stride + m_slot] as a Jacobian one
+void launch_shuffle_commit(const Aff* d_pp, size_t pp_stride, uint32_t m_slot, uint32_t count, Jac* d_mjac, hipStream_t s);
+
 void launch_sum_jac(const Jac* d_in, int n, Jac* d_out, int* d_flag, hipStream_t s);
 void launch_bench_fpmul(Fp* d_data, int blocks, int iters, hipStream_t s);
 void launch_bench_f28mul(Fp* d_data, int blocks, int iters, hipStream_t s);

@@ -4,6 +4,7 @@
 // scalar multiplications, MSMs, the batch prover / verifier, normalisation + compression); the host hashes the
 // six-point transcript of the tracker proofs and moves bytes.  Randomness stays with the caller (SURVEY 8b RNG
 // contract): every `Fr::rand(rng)` / `shuffle(rng)` the reference performs is an argument, in the reference's order.
+#include <algorithm>
 #include <cstring>
 #include <vector>
 #include "engine.hpp"
@@ -327,6 +328,243 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
   CPX_HIP(hipMemcpyAsync(status, dver.p, count * sizeof(int), hipMemcpyDeviceToHost, stream_));
   CPX_HIP(hipStreamSynchronize(stream_));
   flush_timers();
+}
+
+// ---------------------------------------------------------------- shuffle step and shuffle proofs, `count` per call (shuffle.hip)
+// All three calls: the inputs go up once; decoding, the placeholder rule, k R / k S, the gather, M and the compression are a constant number
+// of launches whatever the count, on device-resident data; the count instances become the loaded batch through load_rows (device to device)
+// and the batch prover / verifier runs on them unchanged.  The host touches bytes (offset table, task descriptors, the proof records'
+// 48-byte prefix), never points.
+namespace {
+// every row must be a permutation of 0..ell (the reference shuffles (0..ELL)): the check of the single call (capi.cpp), before anything is launched
+void check_permutations(size_t count, size_t ell, const uint32_t* permutation) {
+  std::vector<uint8_t> seen(ell);
+  for (size_t i = 0; i < count; i++) {
+    std::fill(seen.begin(), seen.end(), 0);
+    for (size_t j = 0; j < ell; j++) {
+      const uint32_t p = permutation[i * ell + j];
+      if (p >= ell || seen[p]) throw ArgError("permutation: every row must be a permutation of 0..ell");
+      seen[p] = 1;
+    }
+  }
+}
+void shuffle_point_offsets(const ShufflePlan& pl, std::vector<uint32_t>& off) {
+  off.resize(pl.points());
+  for (size_t j = 0; j < off.size(); j++) off[j] = (uint32_t)pl.src_offset(j);
+}
+}  // namespace
+
+void Engine::shuffle_trim() {
+  tier0_trim(sh_.bytes);
+  tier0_trim(sh_.status);
+  tier0_trim(sh_.off);
+  tier0_trim(sh_.perm);
+  tier0_trim(sh_.pts);
+  tier0_trim(sh_.kpts);
+  tier0_trim(sh_.tu);
+  tier0_trim(sh_.zip);
+  tier0_trim(sh_.fr);
+  tier0_trim(sh_.mjac);
+  tier0_trim(sh_.stask);
+}
+
+// util.rs:94-104 on the device.  In: sh_.pts = vec_R | vec_S (dense planes), sh_.perm, sh_.fr = k [count] | blinders [count][4] | the scalars
+// of M [count][n] (k_shuffle_status).  Out: sh_.tu = vec_T | vec_U, sh_.zip = (T_j, U_j) interleaved, the loaded batch (R, S, T, U, M) and the
+// compressed M of every item in d_comp_.  Ends synchronised: the staging buffers and the task list are free again.
+void Engine::shuffle_device(const ShufflePlan& pl) {
+  const size_t count = pl.count, ell = ell_, n = n_, pp = pl.plane_points();
+  sh_.kpts.ensure(2 * pp);
+  sh_.tu.ensure(2 * pp);
+  sh_.zip.ensure(2 * pp);
+  sh_.stask.ensure(2 * count);
+  sh_.mjac.ensure(count);
+  const Aff *d_r = sh_.pts.p + pl.point_index(SHP_R, 0, 0), *d_s = sh_.pts.p + pl.point_index(SHP_S, 0, 0);
+  // k R, k S: one task per (item, family), the item's k shared by its ell elements (scale_any_point as in Engine::scale)
+  const uint32_t fl = opt_.scale_any_point ? SMUL_PLAIN : 0u;
+  std::vector<SmulTask> tasks(2 * count);
+  for (size_t i = 0; i < count; i++) {
+    tasks[2 * i] = SmulTask{nullptr, d_r + i * ell, sh_.kpts.p + i * ell, sh_.fr.p + i, 0, fl};
+    tasks[2 * i + 1] = SmulTask{nullptr, d_s + i * ell, sh_.kpts.p + pp + i * ell, sh_.fr.p + i, 0, fl};
+  }
+  CPX_HIP(hipMemcpyAsync(sh_.stask.p, tasks.data(), tasks.size() * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemsetAsync(sh_.mjac.p, 0, count * sizeof(Jac), stream_));   // (Z = 0: the identity, until M is known)
+  tick("k_smul", 224.0 * 2 * pp, 2.0 * pp);
+  launch_smul(sh_.stask.p, (int)(2 * count), (int)ell, stream_, false, fl ? 0 : opt_.smul_quad_max);
+  tock();
+  tick("k_shuffle_gather", 6.0 * sizeof(Aff) * pp, (double)pp);
+  launch_shuffle_gather(pl, sh_.perm.p, sh_.kpts.p, sh_.kpts.p + pp, sh_.tu.p, sh_.tu.p + pp, sh_.zip.p, stream_);
+  tock();
+  load_rows(count, reinterpret_cast<const uint8_t*>(d_r), reinterpret_cast<const uint8_t*>(d_s), reinterpret_cast<const uint8_t*>(sh_.tu.p),
+            reinterpret_cast<const uint8_t*>(sh_.tu.p + pp), reinterpret_cast<const uint8_t*>(sh_.mjac.p), true);
+  // M = msm(vec_G, sigma) + msm(vec_H, blinders): vec_G | vec_H are the first n columns of the CRS tables — one fixed-base task per item
+  const TblSeg none{nullptr, nullptr, 0, 0};
+  const Fr* d_msc = sh_.fr.p + 5 * count;
+  std::vector<TblReq> reqs(count);
+  for (size_t i = 0; i < count; i++) reqs[i] = TblReq{cseg(0, (uint32_t)n), nullptr, none, nullptr, slot_index(i, SL_M), d_msc + i * n};
+  enqueue_tbl_phase(reqs, slot_index(0, SlotMap(L_).TMP(7)), h_stage_, d_blob_, d_comp_, stream_, main_, true);
+  tick("k_shuffle_commit", 0, (double)count);
+  launch_shuffle_commit(d_pp_.p, pp_stride_, (uint32_t)(4 * ell + SL_M), (uint32_t)count, d_Mjac_.p, stream_);
+  tock();
+  CPX_HIP(hipStreamSynchronize(stream_));
+}
+
+// util.rs:83-106 shuffle_permute_and_commit_input for every instance
+void Engine::shuffle_batch(size_t count, const uint8_t* vec_R, const uint8_t* vec_S, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
+                           uint8_t* vec_T_out, uint8_t* vec_U_out, uint8_t* M_out) {
+  if (!count) return;
+  if (!ell_) throw std::logic_error("set_crs first");
+  const size_t ell = ell_, n = n_;
+  const ShufflePlan pl(count, ell, false);
+  if (!pl.fits()) throw ArgError("shuffle batch: count * ell exceeds the 32-bit index range of one call");
+  check_permutations(count, ell, permutation);
+  CPX_HIP(hipSetDevice(device_));
+  struct Trim {
+    Engine* e;
+    ~Trim() { e->shuffle_trim(); }
+  } trim{this};
+  const size_t pp = pl.plane_points();
+  sh_.pts.ensure(2 * pp);
+  sh_.perm.ensure(pp);
+  sh_.fr.ensure(5 * count + count * n);
+  sh_.bad.ensure(count);
+  CPX_HIP(hipMemcpyAsync(sh_.pts.p, vec_R, pp * sizeof(Aff), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.pts.p + pp, vec_S, pp * sizeof(Aff), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.perm.p, permutation, pp * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.fr.p, k, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.fr.p + count, vec_m_blinders, 4 * count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  tick("k_shuffle_status", 0, (double)count);
+  launch_shuffle_status(pl, nullptr, sh_.pts.p, Aff::identity(), sh_.perm.p, sh_.fr.p + count, sh_.fr.p + 5 * count, nullptr, sh_.bad.p, stream_);
+  tock();
+  shuffle_device(pl);
+  if (vec_T_out) CPX_HIP(hipMemcpyAsync(vec_T_out, sh_.tu.p, pp * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
+  if (vec_U_out) CPX_HIP(hipMemcpyAsync(vec_U_out, sh_.tu.p + pp, pp * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
+  if (M_out) CPX_HIP(hipMemcpyAsync(M_out, d_Mjac_.p, count * sizeof(Jac), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipStreamSynchronize(stream_));
+  flush_timers();
+}
+
+// whisk.rs:144-179 generate_whisk_shuffle_proof for every (pre_trackers, permutation, k, blinders, draws) item
+void Engine::whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
+                                           const uint8_t* rand, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status) {
+  for (size_t i = 0; i < count; i++) status[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as a proof
+  if (!count) return;
+  if (!ell_) throw std::logic_error("set_crs first");
+  const size_t ell = ell_, n = n_, psz = proof_size(), rec = 48 + psz;
+  const ShufflePlan pl(count, ell, false);
+  if (!pl.fits()) throw ArgError("shuffle proofs: count * ell exceeds the 32-bit index range of one call");
+  check_permutations(count, ell, permutation);
+  CPX_HIP(hipSetDevice(device_));
+  const Aff G = generator();   // (before canonical_infinities: its first call decodes, and that shares canon_bytes_)
+  const size_t pp = pl.plane_points();
+  pre_trackers = canonical_infinities(pre_trackers, pp * 96, pp, 96, {0, 48});
+  struct Trim {
+    Engine* e;
+    ~Trim() { e->shuffle_trim(); }
+  } trim{this};
+  sh_.bytes.ensure(pl.upload_bytes() + 2 * pp * 48);   // pre trackers | post trackers
+  sh_.status.ensure(pl.points());
+  sh_.off.ensure(pl.points());
+  sh_.pts.ensure(pl.points());
+  sh_.perm.ensure(pp);
+  sh_.fr.ensure(5 * count + count * n);
+  sh_.bad.ensure(count);
+  std::vector<uint32_t> off;
+  shuffle_point_offsets(pl, off);
+  CPX_HIP(hipMemcpyAsync(sh_.bytes.p, pre_trackers, pl.upload_bytes(), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.perm.p, permutation, pp * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.fr.p, k, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.fr.p + count, vec_m_blinders, 4 * count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  tick("k_decompress", 0, (double)pl.points());
+  launch_decompress(opt_, sh_.bytes.p, (int)pl.points(), sh_.pts.p, nullptr, sh_.status.p, 1, stream_, sh_.off.p);
+  tock();
+  tick("k_shuffle_status", 0, (double)count);
+  launch_shuffle_status(pl, sh_.status.p, sh_.pts.p, G, sh_.perm.p, sh_.fr.p + count, sh_.fr.p + 5 * count, nullptr, sh_.bad.p, stream_);
+  tock();
+  shuffle_device(pl);
+  uint8_t* d_post = sh_.bytes.p + pl.upload_bytes();
+  tick("k_compress", 0, 2.0 * pp);
+  launch_compress(sh_.zip.p, (int)(2 * pp), (int)(2 * pp), 1, d_post, stream_);   // zip_trackers (whisk.rs:279-293)
+  tock();
+  std::vector<uint8_t> bad(count);
+  CPX_HIP(hipMemcpyAsync(post_trackers_out, d_post, 2 * pp * 48, hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpy2DAsync(proofs_out, rec, d_comp_.p, 48, 48, count, hipMemcpyDeviceToHost, stream_));   // WhiskShuffleProof::serialize: M first (whisk.rs:87-91)
+  CPX_HIP(hipMemcpyAsync(bad.data(), sh_.bad.p, count, hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipStreamSynchronize(stream_));
+  flush_timers();
+  // CurdleproofsProof::new on the loaded instances; the proofs come back dense and go behind their M
+  std::vector<uint8_t> dense(count * psz);
+  batch_prove(permutation, k, vec_m_blinders, rand, dense.data());
+  for (size_t i = 0; i < count; i++) {
+    if (bad[i]) {   // Err(SerializationError): the placeholder's proof is dropped
+      memset(post_trackers_out + i * ell * 96, 0, ell * 96);
+      memset(proofs_out + i * rec, 0, rec);
+      status[i] = CPX_ERR_DESERIALIZE;
+    } else {
+      memcpy(proofs_out + i * rec + 48, dense.data() + i * psz, psz);
+      status[i] = CPX_OK;
+    }
+  }
+}
+
+// whisk.rs:106-130 is_valid_whisk_shuffle_proof for every (pre_trackers, post_trackers, proof) triple
+void Engine::whisk_verify_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand,
+                                         int* verdict) {
+  for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
+  if (!count) return;
+  if (!ell_) throw std::logic_error("set_crs first");
+  const size_t ell = ell_, psz = proof_size(), rec = 48 + psz;
+  const ShufflePlan pl(count, ell, true);
+  if (!pl.fits()) throw ArgError("shuffle proofs: count * ell exceeds the 32-bit index range of one call");
+  CPX_HIP(hipSetDevice(device_));
+  const Aff G = generator();
+  const size_t pp = pl.plane_points(), tb = pl.tracker_bytes();
+  // strict_infinity = 0: non-canonical infinity encodings are rewritten in COPIES of the inputs (canonical_infinities; canon_bytes_ is
+  // reused by the next array, so a rewritten array is kept)
+  std::vector<uint8_t> keep[2];
+  auto canon = [&](const uint8_t* in, size_t nbytes, size_t nrec, size_t stride, const std::vector<size_t>& offs, std::vector<uint8_t>* store) {
+    const uint8_t* p = canonical_infinities(in, nbytes, nrec, stride, offs);
+    if (p == in || !store) return p;
+    store->assign(p, p + nbytes);
+    return (const uint8_t*)store->data();
+  };
+  pre_trackers = canon(pre_trackers, tb, pp, 96, {0, 48}, &keep[0]);
+  post_trackers = canon(post_trackers, tb, pp, 96, {0, 48}, &keep[1]);
+  proofs = canon(proofs, count * rec, count, rec, {0}, nullptr);   // M; the proof points behind it are batch_verify's
+  std::vector<uint8_t> dense(count * psz);                        // CurdleproofsProof::deserialize reads the bytes behind M (whisk.rs:122)
+  for (size_t i = 0; i < count; i++) memcpy(dense.data() + i * psz, proofs + i * rec + 48, psz);
+  struct Trim {
+    Engine* e;
+    ~Trim() { e->shuffle_trim(); }
+  } trim{this};
+  sh_.bytes.ensure(pl.upload_bytes());
+  sh_.status.ensure(pl.points());
+  sh_.off.ensure(pl.points());
+  sh_.pts.ensure(pl.points());
+  sh_.bad.ensure(count);
+  sh_.mjac.ensure(count);
+  std::vector<uint32_t> off;
+  shuffle_point_offsets(pl, off);
+  CPX_HIP(hipMemcpyAsync(sh_.bytes.p, pre_trackers, tb, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.bytes.p + tb, post_trackers, tb, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpy2DAsync(sh_.bytes.p + 2 * tb, 48, proofs, rec, 48, count, hipMemcpyHostToDevice, stream_));   // the M prefixes only
+  CPX_HIP(hipMemcpyAsync(sh_.off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  tick("k_decompress", 0, (double)pl.points());
+  launch_decompress(opt_, sh_.bytes.p, (int)pl.points(), sh_.pts.p, nullptr, sh_.status.p, 1, stream_, sh_.off.p);
+  tock();
+  tick("k_shuffle_status", 0, (double)count);
+  launch_shuffle_status(pl, sh_.status.p, sh_.pts.p, G, nullptr, nullptr, nullptr, sh_.mjac.p, sh_.bad.p, stream_);
+  tock();
+  const Aff* d = sh_.pts.p;
+  load_rows(count, reinterpret_cast<const uint8_t*>(d), reinterpret_cast<const uint8_t*>(d + pp), reinterpret_cast<const uint8_t*>(d + 2 * pp),
+            reinterpret_cast<const uint8_t*>(d + 3 * pp), reinterpret_cast<const uint8_t*>(sh_.mjac.p), true);
+  std::vector<uint8_t> bad(count);
+  CPX_HIP(hipMemcpyAsync(bad.data(), sh_.bad.p, count, hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipStreamSynchronize(stream_));
+  flush_timers();
+  batch_verify(dense.data(), rand, verdict);
+  for (size_t i = 0; i < count; i++)
+    if (bad[i]) verdict[i] = CPX_ERR_DESERIALIZE;   // an undecodable tracker or M: Err(SerializationError), whatever the placeholder's verdict
 }
 
 }  // namespace cpx

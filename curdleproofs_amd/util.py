@@ -59,6 +59,23 @@ def shuffle_permute_and_commit_input(ctx, crs_points, ell, vec_R, vec_S, permuta
     return vec_T, vec_U, M
 
 
+def shuffle_permute_and_commit_inputs(ctx, vec_Rs, vec_Ss, permutations, ks, vec_m_blinders):
+    """util.rs:83-106 for many instances in ONE library call (`Context.shuffle_batch`): lists of per-instance arguments as the single
+    function takes them, against the CRS loaded into ctx.  Returns a list of (vec_T, vec_U, M); the instances stay loaded in ctx."""
+    count = len(vec_Rs)
+    if len(vec_Ss) != count or len(permutations) != count or len(ks) != count or len(vec_m_blinders) != count:
+        raise ValueError("one vec_S, permutation, k and blinder set per vec_R")
+    ell = ctx.ell
+    if any(len(r) != ell * AFF or len(s) != ell * AFF or len(p) != ell or len(k) != FR or len(b) != N_BLINDERS * FR
+           for r, s, p, k, b in zip(vec_Rs, vec_Ss, permutations, ks, vec_m_blinders)):
+        raise ValueError("bad argument lengths")
+    if count == 0:
+        return []
+    t, u, m = ctx.shuffle_batch(b"".join(vec_Rs), b"".join(vec_Ss), [x for p in permutations for x in p], b"".join(ks), b"".join(vec_m_blinders))
+    w = ell * AFF
+    return [(t[w * i:w * (i + 1)], u[w * i:w * (i + 1)], m[JAC * i:JAC * (i + 1)]) for i in range(count)]
+
+
 def serialize_g1projective_vec(ctx, points_jac):
     """util.rs:126-133: compressed zcash encoding of every point, concatenated"""
     return ctx.normalize(points_jac, compressed=True)[1]

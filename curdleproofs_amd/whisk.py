@@ -126,6 +126,92 @@ def is_valid_whisk_tracker_proof(ctx, tracker, k_commitment, tracker_proof):
     return bool(valid.value)
 
 
+# ---- many shuffle proofs per call (cpx_whisk_generate_shuffle_proofs / cpx_whisk_verify_shuffle_proofs) ----
+def _random_permutation(ell):
+    permutation = list(range(ell))
+    for i in range(ell - 1, 0, -1):                          # Fisher-Yates on the CSPRNG
+        j = secrets.randbelow(i + 1)
+        permutation[i], permutation[j] = permutation[j], permutation[i]
+    return permutation
+
+
+def generate_whisk_shuffle_proofs(ctx, pre_tracker_lists, permutations=None, ks=None, vec_m_blinders=None, rands=None):
+    """whisk.rs:144-179 for every list of ell pre trackers in ONE library call.  permutations / ks / vec_m_blinders / rands: one entry per
+    list, the reference's rng draws as in generate_whisk_shuffle_proof; omitted ones come from the OS CSPRNG.  Returns a list of
+    (post_trackers, whisk_shuffle_proof_bytes), with None where a pre tracker does not decode (the reference's SerializationError);
+    nothing is raised per item.  The count instances stay loaded in ctx."""
+    count = len(pre_tracker_lists)
+    for name, arg in (("permutation", permutations), ("k", ks), ("blinder set", vec_m_blinders), ("set of draws", rands)):
+        if arg is not None and len(arg) != count:
+            raise ValueError("one %s per tracker list" % name)
+    if count == 0:
+        return []
+    ell, n = ctx.ell, ctx.n
+    if any(len(t) != ell for t in pre_tracker_lists):
+        raise ValueError("need exactly ell = %d trackers per list" % ell)
+    permutations = [_random_permutation(ell) for _ in range(count)] if permutations is None else permutations
+    ks = [_rand_fr(1) for _ in range(count)] if ks is None else ks
+    vec_m_blinders = [_rand_fr(N_BLINDERS) for _ in range(count)] if vec_m_blinders is None else vec_m_blinders
+    rands = [_rand_fr(3 * n + 9) for _ in range(count)] if rands is None else rands
+    if (any(len(p) != ell for p in permutations) or any(len(k) != FR for k in ks) or any(len(b) != N_BLINDERS * FR for b in vec_m_blinders)
+            or any(len(r) != (3 * n + 9) * FR for r in rands)):
+        raise ValueError("bad argument lengths: ell permutation entries, a 32-byte k, 4 blinders and 3n+9 draws per list")
+    rec = whisk_shuffle_proof_size(ctx)
+    post, proofs = _out(count * ell * 2 * G1POINT_SIZE), _out(count * rec)
+    perm = (ctypes.c_uint32 * (count * ell))(*[x for p in permutations for x in p])
+    status = (ctypes.c_int * count)(*([CPX_ERR_INTERNAL] * count))   # an entry the library does not write is never read as a proof
+    ctx._check(ctx._L.cpx_whisk_generate_shuffle_proofs(ctx._h, count, _in(b"".join(_cat(t) for t in pre_tracker_lists)), perm, _in(b"".join(ks)),
+                                                        _in(b"".join(vec_m_blinders)), _in(b"".join(rands)), post, proofs, status))
+    pb, fb = bytes(post), bytes(proofs)
+    res = []
+    for i, st in enumerate(status):
+        if st not in (CPX_OK, CPX_ERR_DESERIALIZE):
+            raise CpxError(st, "shuffle proof %d" % i)
+        if st != CPX_OK:
+            res.append(None)
+            continue
+        row = pb[96 * ell * i:96 * ell * (i + 1)]
+        res.append(([WhiskTracker(row[96 * j:96 * j + 48], row[96 * j + 48:96 * j + 96]) for j in range(ell)], fb[rec * i:rec * (i + 1)]))
+    return res
+
+
+def are_valid_whisk_shuffle_proofs(ctx, pre_lists, post_lists, proofs, rands=None):
+    """whisk.rs:106-130 for every (pre_trackers, post_trackers, proof) triple in ONE library call.  rands: per triple the verifier's eight
+    accumulate_check factors (CSPRNG when omitted).  Returns a list with True / False, or a SerializationError INSTANCE where the reference
+    returns Err (undecodable tracker, M or proof bytes, wrong proof length); nothing is raised per item."""
+    count = len(pre_lists)
+    if len(post_lists) != count or len(proofs) != count or (rands is not None and len(rands) != count):
+        raise ValueError("one post tracker list, one proof and one set of factors per pre tracker list")
+    if count == 0:
+        return []
+    ell = ctx.ell
+    if any(len(t) != ell for t in pre_lists) or any(len(t) != ell for t in post_lists):
+        raise ValueError("need exactly ell = %d trackers per list on both sides" % ell)
+    rands = [_rand_fr(8) for _ in range(count)] if rands is None else rands
+    if any(len(r) != 8 * FR for r in rands):
+        raise ValueError("8 random factors per proof")
+    rec = whisk_shuffle_proof_size(ctx)
+    # a wrong length is a fixed-size array mismatch in the reference: reported per item, the library sees a well-formed dummy
+    short = [len(p) != rec for p in proofs]
+    pf = b"".join(bytes(rec) if s else p for s, p in zip(short, proofs))
+    verdict = (ctypes.c_int * count)(*([CPX_ERR_INTERNAL] * count))   # an entry the library does not write is never read as accepted
+    ctx._check(ctx._L.cpx_whisk_verify_shuffle_proofs(ctx._h, count, _in(b"".join(_cat(t) for t in pre_lists)), _in(b"".join(_cat(t) for t in post_lists)),
+                                                      _in(pf), _in(b"".join(rands)), verdict))
+    res = []
+    for i, v in enumerate(verdict):
+        if short[i]:
+            res.append(SerializationError("wrong proof length"))
+        elif v == CPX_OK:
+            res.append(True)
+        elif v == CPX_ERR_VERIFY:
+            res.append(False)
+        elif v == CPX_ERR_DESERIALIZE:
+            res.append(SerializationError("shuffle proof %d" % i))
+        else:
+            raise CpxError(v, "shuffle proof %d" % i)
+    return res
+
+
 # ---- many tracker proofs per call (cpx_whisk_generate_tracker_proofs / cpx_whisk_verify_tracker_proofs) ----
 def generate_whisk_tracker_proofs(ctx, trackers, ks, blinders=None):
     """whisk.rs:228-263 for every (tracker, k, blinder) triple in ONE library call (a constant number of kernel launches).

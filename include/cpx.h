@@ -75,7 +75,7 @@ void cpx_host_free(void* p);
 int cpx_ctx_set_crs(cpx_ctx* ctx, size_t ell, const uint8_t* points, size_t n_points);
 int cpx_crs_sums(const cpx_ctx* ctx, uint8_t g_sum[96], uint8_t h_sum[96]);
 size_t cpx_proof_size(const cpx_ctx* ctx); /* 48*(18+10*log2(ell+4)) + 32*7, e.g. 4928 at ell = 252 */
-size_t cpx_batch_size(const cpx_ctx* ctx); /* instances currently loaded (cpx_batch_load, or 1 after a cpx_whisk_*_shuffle_proof call); 0 = none */
+size_t cpx_batch_size(const cpx_ctx* ctx); /* instances currently loaded (cpx_batch_load; 1 after a cpx_whisk_*_shuffle_proof call, count after the batched ones); 0 = none */
 
 /* ---- tier 0: the reference's MSM funnel and the loops that bypass it ------------------------- */
 /* util.rs:19-22 `msm(points: &[G1Affine], scalars: &[Fr]) -> G1Projective` */
@@ -210,12 +210,39 @@ int cpx_whisk_generate_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t*
 int cpx_whisk_verify_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* trackers /* count*96 */, const uint8_t* k_commitments /* count*48 */,
                                     const uint8_t* proofs /* count*128 */, int* verdict /* count */);
 
+/* The shuffle half of the byte-level API for `count` independent shuffles per call: compressed bytes in, compressed bytes out, and between
+ * the uploads and the downloads every step runs on the device in a number of kernel launches that does not depend on count — decoding, the
+ * scalar multiplications, the permutation, M (the fixed-base CRS table), normalisation and compression; the proving and verifying is
+ * cpx_batch_prove / cpx_batch_verify on the count instances, which become the loaded batch (cpx_batch_size == count).  Conventions of the batched
+ * tracker calls: CPX_OK whatever the per-item results are, count = 0 is a no-op, NULL pointers with count > 0 are CPX_ERR_ARG and nothing is
+ * written, no CRS is CPX_ERR_STATE; status / verdict are pre-filled with CPX_ERR_INTERNAL.  A row of `permutation` that is not a permutation of
+ * 0..ell makes the whole call CPX_ERR_ARG before anything is launched (the loaded batch stays).  Options "strict_infinity" and
+ * "scale_any_point" govern these calls as they govern the single ones.  An item whose points do not decode keeps its slot of the batch as a
+ * placeholder instance (every point the generator); the other items are not affected.  count * ell < 2^28 per call; beyond that what
+ * cpx_batch_load accepts at this ell. */
+/* util.rs:83-106 shuffle_permute_and_commit_input for `count` instances, device-resident:
+ * T_i = permute(k_i * R_i), U_i = permute(k_i * S_i), M_i = msm(vec_G, sigma_i) + msm(vec_H, blinders_i).
+ * The count instances (R, S, T, U, M) become the loaded batch (cpx_batch_size == count).  Either output may be NULL. */
+int cpx_batch_shuffle(cpx_ctx* ctx, size_t count, const uint8_t* vec_R /* count*ell*96 */, const uint8_t* vec_S, const uint32_t* permutation /* count*ell */,
+                      const uint8_t* k /* count*32 */, const uint8_t* vec_m_blinders /* count*4*32 */, uint8_t* vec_T_out /* count*ell*96 */,
+                      uint8_t* vec_U_out, uint8_t* M_out /* count*144 */);
+/* whisk.rs:144-179 generate_whisk_shuffle_proof for `count` independent shuffles.
+ *   status[i]: CPX_OK, or CPX_ERR_DESERIALIZE (an undecodable pre tracker; the item's post trackers and proof are then zero bytes). */
+int cpx_whisk_generate_shuffle_proofs(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers /* count*ell*96 */, const uint32_t* permutation /* count*ell */,
+                                      const uint8_t* k /* count*32 */, const uint8_t* vec_m_blinders /* count*4*32 */, const uint8_t* rand /* count*(3n+9)*32 */,
+                                      uint8_t* post_trackers_out /* count*ell*96 */, uint8_t* proofs_out /* count*(48+cpx_proof_size) */, int* status /* count */);
+/* whisk.rs:106-130 is_valid_whisk_shuffle_proof for `count` independent (pre, post, proof) triples.
+ *   verdict[i]: CPX_OK = Ok(true), CPX_ERR_VERIFY = Ok(false), CPX_ERR_DESERIALIZE = Err (an undecodable tracker on either side, an
+ *   undecodable M, a failed CurdleproofsProof::deserialize).  rand as for cpx_batch_verify (zero or >= r -> CPX_ERR_ARG for the call). */
+int cpx_whisk_verify_shuffle_proofs(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers,
+                                    const uint8_t* proofs /* count*(48+cpx_proof_size) */, const uint8_t* rand /* count*8*32 */, int* verdict /* count */);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 int cpx_set_profiling(cpx_ctx* ctx, int on); /* time every kernel group with HIP events on the ctx stream */
 int cpx_reset_stats(cpx_ctx* ctx);
 /* name = kernel name as rocprofv3 reports it, template arguments included: "k_msm_fix<16, 16>", "k_msm_tblw<32, false>",
  * "k_msm_tblw<2, true>", "k_msm_accw", "k_reduce_sets", "k_finalize_ranges", "k_table_build", "k_msm_tail", "k_smul",
- * "k_finalize", "k_compress", "k_decompress" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
+ * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
  * units = MSM points / scalar-mul elements / points; out pointers may be NULL */
 int cpx_get_stat(const cpx_ctx* ctx, const char* name, uint64_t* launches, double* total_ms, double* algorithmic_bytes, double* units);
 int cpx_set_host_threads(cpx_ctx* ctx, int threads);

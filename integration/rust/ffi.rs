@@ -79,6 +79,13 @@ extern "C" {
                                              status: *mut c_int) -> c_int;
     pub fn cpx_whisk_verify_tracker_proofs(ctx: *mut cpx_ctx, count: usize, trackers: *const u8, k_commitments: *const u8, proofs: *const u8,
                                            verdict: *mut c_int) -> c_int;
+    // `count` shuffles per call (util.rs:83-106, whisk.rs:144-179, :106-130): the instances become the loaded batch; per-item status / verdict
+    pub fn cpx_batch_shuffle(ctx: *mut cpx_ctx, count: usize, vec_r: *const u8, vec_s: *const u8, permutation: *const u32, k: *const u8, vec_m_blinders: *const u8,
+                             vec_t_out: *mut u8, vec_u_out: *mut u8, m_out: *mut u8) -> c_int;
+    pub fn cpx_whisk_generate_shuffle_proofs(ctx: *mut cpx_ctx, count: usize, pre_trackers: *const u8, permutation: *const u32, k: *const u8,
+                                             vec_m_blinders: *const u8, rand: *const u8, post_trackers_out: *mut u8, proofs_out: *mut u8, status: *mut c_int) -> c_int;
+    pub fn cpx_whisk_verify_shuffle_proofs(ctx: *mut cpx_ctx, count: usize, pre_trackers: *const u8, post_trackers: *const u8, proofs: *const u8, rand: *const u8,
+                                           verdict: *mut c_int) -> c_int;
 }
 
 pub const AFF: usize = 96;

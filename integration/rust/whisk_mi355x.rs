@@ -135,3 +135,84 @@ pub fn generate_whisk_tracker_proofs<T: RngCore>(rng: &mut T, trackers: &[WhiskT
         })
         .collect()
 }
+
+/// whisk.rs:106-130 for many (pre_trackers, post_trackers, proof) triples in one library call: one result per item, in order.  Like the
+/// rest of this file, NOT COMPILED here.
+pub fn are_valid_whisk_shuffle_proofs<T: RngCore>(
+    rng: &mut T,
+    crs: &CurdleproofsCrs,
+    pre_trackers: &[&[WhiskTracker]],
+    post_trackers: &[&[WhiskTracker]],
+    proofs: &[WhiskShuffleProofBytes],
+) -> Vec<Result<bool, SerializationError>> {
+    assert!(pre_trackers.len() == post_trackers.len() && pre_trackers.len() == proofs.len());
+    assert!(pre_trackers.iter().chain(post_trackers.iter()).all(|t| t.len() == ELL));
+    let count = proofs.len();
+    let factors = nonzero_factors(8 * count, rng); // the accumulate_check draws of every CurdleproofsProof::verify, in item order
+    let pre: Vec<u8> = pre_trackers.iter().flat_map(|t| trackers_to_wire(t)).collect();
+    let post: Vec<u8> = post_trackers.iter().flat_map(|t| trackers_to_wire(t)).collect();
+    let pf: Vec<u8> = proofs.iter().flat_map(|p| p.iter().copied()).collect();
+    let mut verdict = vec![CPX_ERR_INTERNAL; count]; // an entry the library does not write is never read as accepted
+    let rc = unsafe { cpx_whisk_verify_shuffle_proofs(ctx_with_crs(crs), count, pre.as_ptr(), post.as_ptr(), pf.as_ptr(), scalars_ptr(&factors), verdict.as_mut_ptr()) };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    verdict
+        .into_iter()
+        .map(|v| match v {
+            CPX_OK => Ok(true),
+            CPX_ERR_VERIFY => Ok(false),
+            CPX_ERR_DESERIALIZE => Err(SerializationError::InvalidData),
+            v => panic!("libcpx: {}", v),
+        })
+        .collect()
+}
+
+/// whisk.rs:144-179 for many lists of pre trackers in one library call; every item draws from `rng` in the single function's order
+/// (shuffle, k, blinders, the prover's 3n+9), item after item
+pub fn generate_whisk_shuffle_proofs<T: RngCore>(
+    rng: &mut T,
+    crs: &CurdleproofsCrs,
+    pre_trackers: &[&[WhiskTracker]],
+) -> Vec<Result<(Vec<WhiskTracker>, WhiskShuffleProofBytes), SerializationError>> {
+    assert!(pre_trackers.iter().all(|t| t.len() == ELL));
+    let count = pre_trackers.len();
+    let (mut permutation, mut k, mut blinders, mut rand) = (Vec::<u32>::new(), Vec::<Fr>::new(), Vec::<Fr>::new(), Vec::<Fr>::new());
+    for _ in 0..count {
+        let mut p: Vec<u32> = (0..ELL as u32).collect();
+        p.shuffle(rng);
+        permutation.extend(p);
+        k.push(Fr::rand(rng));
+        blinders.extend(generate_blinders(rng, N_BLINDERS));
+        rand.extend((0..3 * N + 9).map(|_| Fr::rand(rng)));
+    }
+    let pre: Vec<u8> = pre_trackers.iter().flat_map(|t| trackers_to_wire(t)).collect();
+    let mut post = vec![0u8; 96 * ELL * count];
+    let mut proofs = vec![0u8; WHISK_SHUFFLE_PROOF_SIZE * count];
+    let mut status = vec![CPX_ERR_INTERNAL; count];
+    let rc = unsafe {
+        cpx_whisk_generate_shuffle_proofs(ctx_with_crs(crs), count, pre.as_ptr(), permutation.as_ptr(), scalars_ptr(&k), scalars_ptr(&blinders), scalars_ptr(&rand),
+                                          post.as_mut_ptr(), proofs.as_mut_ptr(), status.as_mut_ptr())
+    };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    status
+        .iter()
+        .zip(post.chunks(96 * ELL).zip(proofs.chunks(WHISK_SHUFFLE_PROOF_SIZE)))
+        .map(|(st, (t, p))| match *st {
+            CPX_OK => Ok((t.chunks(96).map(|c| WhiskTracker { r_G: c[..48].try_into().unwrap(), k_r_G: c[48..].try_into().unwrap() }).collect(), p.try_into().unwrap())),
+            CPX_ERR_DESERIALIZE => Err(SerializationError::InvalidData),
+            st => panic!("libcpx: {}", st),
+        })
+        .collect()
+}
+
+/// util.rs:83-106 for many instances in one library call (wire forms of ffi.rs: affine 96 B, Jacobian 144 B); the instances stay loaded
+pub fn shuffle_permute_and_commit_inputs(crs: &CurdleproofsCrs, vec_r: &[u8], vec_s: &[u8], permutations: &[u32], k: &[Fr], vec_m_blinders: &[Fr]) -> (Vec<u8>, Vec<u8>, Vec<u8>) {
+    let count = k.len();
+    assert!(vec_r.len() == count * ELL * AFF && vec_s.len() == vec_r.len() && permutations.len() == count * ELL && vec_m_blinders.len() == count * N_BLINDERS);
+    let (mut t, mut u, mut m) = (vec![0u8; vec_r.len()], vec![0u8; vec_r.len()], vec![0u8; JAC * count]);
+    let rc = unsafe {
+        cpx_batch_shuffle(ctx_with_crs(crs), count, vec_r.as_ptr(), vec_s.as_ptr(), permutations.as_ptr(), scalars_ptr(k), scalars_ptr(vec_m_blinders), t.as_mut_ptr(),
+                          u.as_mut_ptr(), m.as_mut_ptr())
+    };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    (t, u, m)
+}
