@@ -61,7 +61,7 @@ EXPORTS = [
     "cpx_accum_new", "cpx_accum_free", "cpx_accum_check", "cpx_accum_verify",
     "cpx_batch_load", "cpx_batch_load_begin", "cpx_batch_load_end", "cpx_batch_prove", "cpx_batch_verify", "cpx_batch_verify_fused", "cpx_g1_sum_jac",
     "cpx_whisk_generate_shuffle_proof", "cpx_whisk_is_valid_shuffle_proof", "cpx_whisk_generate_tracker_proof", "cpx_whisk_is_valid_tracker_proof",
-    "cpx_whisk_generate_tracker_proofs", "cpx_whisk_verify_tracker_proofs",
+    "cpx_whisk_generate_tracker_proofs", "cpx_whisk_verify_tracker_proofs", "cpx_g1_generator_mul", "cpx_whisk_trackers_from_k_r",
     "cpx_batch_shuffle", "cpx_whisk_generate_shuffle_proofs", "cpx_whisk_verify_shuffle_proofs",
     "cpx_set_profiling", "cpx_reset_stats", "cpx_get_stat", "cpx_set_host_threads", "cpx_bench_fpmul",
 ]
@@ -131,6 +131,8 @@ def load_library(path=None):
     L.cpx_whisk_is_valid_tracker_proof.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ci)]
     L.cpx_whisk_generate_tracker_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.cpx_whisk_verify_tracker_proofs.argtypes = [vp, sz, vp, vp, vp, vp]
+    L.cpx_g1_generator_mul.argtypes = [vp, sz, vp, vp, vp]
+    L.cpx_whisk_trackers_from_k_r.argtypes = [vp, sz, vp, vp, vp, vp]
     L.cpx_batch_shuffle.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     L.cpx_whisk_generate_shuffle_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     L.cpx_whisk_verify_shuffle_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp]
@@ -298,6 +300,16 @@ class Context:
         self._check(self._L.cpx_g1_decompress(self._h, _in(comp), n, o, 1 if check_subgroup else 0))
         return bytes(o)[: AFF * n]
 
+    def generator_mul(self, scalars, compressed=False):
+        """scalars[i] * G for the G1 generator, count per call on the generator's fixed-base table (cpx_g1_generator_mul; whisk.rs:318,323
+        with g1 = generator).  scalars: count wire scalars back to back.  Returns the affine points, or (affine, compressed)."""
+        n = len(scalars) // FR
+        if len(scalars) % FR:
+            raise ValueError("generator_mul: 32 bytes per scalar")
+        a, c = _out(AFF * n), _out(48 * n)
+        self._check(self._L.cpx_g1_generator_mul(self._h, n, _in(scalars), a, c if compressed else None))
+        return (bytes(a)[: AFF * n], bytes(c)[: 48 * n]) if compressed else bytes(a)[: AFF * n]
+
     def decompress_status(self, comp, check_subgroup=True):
         """per-point form: (affine points, list of status bytes: 0 ok, 1 malformed / not on the curve, 2 not in the subgroup)"""
         n = len(comp) // 48
@@ -450,7 +462,7 @@ class Context:
         return dict(launches=n.value, ms=ms.value, alg_bytes=by.value, units=un.value)
 
     KERNELS = ("k_msm_tblw<32, false>", "k_reduce_sets", "k_msm_tblw<16, false>", "k_msm_tblw<8, false>", "k_msm_tblw<4, false>", "k_msm_tblw<2, false>", "k_msm_fix<19, 7>", "k_msm_fix<16, 4>", "k_msm_fix<16, 2>", "k_msm_fix<16, 16>", "k_msm_fix<16, 8>", "k_msm_fix<8, 16>", "k_msm_fix<8, 8>",
-               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
+               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
 
     def stats(self):
         return {k: self.stat(k) for k in self.KERNELS}

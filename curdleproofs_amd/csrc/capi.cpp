@@ -356,6 +356,20 @@ int cpx_whisk_verify_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* t
     return (int)CPX_OK;
   });
 }
+int cpx_g1_generator_mul(cpx_ctx* ctx, size_t count, const uint8_t* scalars, uint8_t* out_affine, uint8_t* out_compressed) {
+  if (count && !scalars) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->generator_mul(count, scalars, out_affine, out_compressed);
+    return (int)CPX_OK;
+  });
+}
+int cpx_whisk_trackers_from_k_r(cpx_ctx* ctx, size_t count, const uint8_t* k, const uint8_t* r, uint8_t* trackers_out, uint8_t* k_commitments_out) {
+  if (count && (!k || !r)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_trackers_from_k_r(count, k, r, trackers_out, k_commitments_out);
+    return (int)CPX_OK;
+  });
+}
 
 int cpx_batch_shuffle(cpx_ctx* ctx, size_t count, const uint8_t* vec_R, const uint8_t* vec_S, const uint32_t* permutation, const uint8_t* k,
                       const uint8_t* vec_m_blinders, uint8_t* vec_T_out, uint8_t* vec_U_out, uint8_t* M_out) {

@@ -189,6 +189,10 @@ class Engine {
   // (tracker.hip); status / verdict per item, the loaded batch and the CRS are not touched
   void whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k, const uint8_t* blinders, uint8_t* proofs_out, int* status);
   void whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, int* verdict);
+  // what those calls consume, `count` per call, as multiples of the generator on its fixed-base table (genmul.hip): out[i] = scalars[i] G, and
+  // WhiskTracker::from_k_r / get_k_commitment (whisk.rs:45-55, :370) for (k, r) pairs; either output may be null
+  void generator_mul(size_t count, const uint8_t* scalars, uint8_t* out_affine, uint8_t* out_compressed);
+  void whisk_trackers_from_k_r(size_t count, const uint8_t* k, const uint8_t* r, uint8_t* trackers_out, uint8_t* k_commitments_out);
   // the shuffle step and the two shuffle-proof functions for `count` independent shuffles per call (shuffle.hip): compressed bytes in, compressed
   // bytes out, nothing returns to the host between the uploads and the batch prover / verifier; the count instances become the loaded batch
   void shuffle_batch(size_t count, const uint8_t* vec_R, const uint8_t* vec_S, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
@@ -278,6 +282,9 @@ class Engine {
   bool unzip_trackers(const uint8_t* trackers, size_t n, std::vector<Aff>& vec_r, std::vector<Aff>& vec_s);
   Aff gen_;
   bool have_gen_ = false;
+  const TAff* generator_table();   // the fixed-base table of G (gen_table.hpp), built on the device at first use
+  DevBuf<TAff> gen_tab_;
+  bool have_gen_tab_ = false;
   std::vector<Aff> crs_host_;   // the ell + 7 CRS points (host copy: M of the Whisk shuffle is an MSM over vec_G | vec_H)
   // ---- device-resident batch prover / verifier (engine_device.cpp) ----
   struct TblPlan : TblShape {   // task descriptors of one table-backed MSM phase whose scalars live in device memory, built once

@@ -295,6 +295,18 @@ void launch_tracker_challenge_prove(const uint8_t* d_trackers, const uint8_t* d_
 void launch_tracker_relations(const Aff* d_pts, const uint8_t* d_proofs, const Fr* d_chal, const uint8_t* d_bad, const Aff& gen, int count, int* d_verdict,
                               hipStream_t s);
 
+// ---- multiples of the G1 generator on a fixed-base table (genmul.hip; layout and recoding in gen_table.hpp): one launch each ----
+size_t gen_table_entries();
+// d_tab[gen_table_entries()]: j 256^w G in the table form, built from the decoded generator
+void launch_gen_table(const Aff& gen, TAff* d_tab, hipStream_t s);
+enum : int {
+  GEN_MUL_PLAIN = 0,      // d_out[g] = d_a[g] G, g < count
+  GEN_MUL_TRACKERS = 1,   // d_a = k, d_b = r: d_out[2 i] = r_i G, d_out[2 i + 1] = (k_i r_i) G  (whisk.rs:45-55), the Fr product formed on the device
+  GEN_MUL_BOTH = 2        // ... followed by d_out[2 count + i] = k_i G  (whisk.rs:370)
+};
+// scalars in Montgomery form; results affine, standard form
+void launch_gen_mul(const Fr* d_a, const Fr* d_b, int count, int mode, const TAff* d_tab, Aff* d_out, hipStream_t s);
+
 // ---- batched Whisk shuffle calls (shuffle.hip; index arithmetic in shuffle_plan.hpp): one launch each, whatever the count ----
 struct ShufflePlan;
 // d_status (nullable: nothing was decoded): the decoder's verdicts of the plan's points; d_pts: the decoded planes, the rows of an item with a

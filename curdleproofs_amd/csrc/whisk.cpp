@@ -330,6 +330,97 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
   flush_timers();
 }
 
+// ---------------------------------------------------------------- trackers and k commitments, `count` per call (genmul.hip)
+// The objects the batched tracker calls consume: every one of them is a multiple of the generator — r G, k G and k (r G) = (k r mod r_order) G —
+// so they come from the fixed-base table of G (gen_table.hpp): the scalars go up once, ONE k_gen_mul (the Fr product k r included) and ONE
+// k_compress run whatever the count, the results come down and the stream is synchronised once.  The context's first call also decodes the
+// generator and builds the table (one launch, once per context).  Scratch is the tier-0 set.
+const TAff* Engine::generator_table() {
+  if (!have_gen_tab_) {
+    const Aff G = generator();
+    gen_tab_.ensure(gen_table_entries());
+    tick("k_gen_table", (double)(gen_table_entries() * sizeof(TAff)), (double)gen_table_entries());
+    launch_gen_table(G, gen_tab_.p, stream_);
+    tock();
+    have_gen_tab_ = true;
+  }
+  return gen_tab_.p;
+}
+
+// out[i] = scalars[i] G (whisk.rs:318, :323 with g1 = the generator)
+void Engine::generator_mul(size_t count, const uint8_t* scalars, uint8_t* out_affine, uint8_t* out_compressed) {
+  if (!count || (!out_affine && !out_compressed)) return;
+  if (count > kTrackerBatchMax) throw ArgError("generator multiples: at most 2^23 per call");
+  CPX_HIP(hipSetDevice(device_));
+  const TAff* tab = generator_table();   // (before the buffers below are taken: the first call decodes the generator in the same scratch)
+  struct Trim {
+    Engine* e;
+    ~Trim() {
+      tier0_trim(e->t0_.fr);
+      tier0_trim(e->t0_.a0);
+      tier0_trim(e->t0_.bytes);
+    }
+  } trim{this};
+  DevBuf<Fr>& dsc = t0_.fr;
+  DevBuf<Aff>& dout = t0_.a0;
+  DevBuf<uint8_t>& dcomp = t0_.bytes;
+  dsc.ensure(count);
+  dout.ensure(count);
+  if (out_compressed) dcomp.ensure(48 * count);
+  const int n = (int)count;
+  CPX_HIP(hipMemcpyAsync(dsc.p, scalars, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  tick("k_gen_mul", 128.0 * count, (double)count);
+  launch_gen_mul(dsc.p, nullptr, n, GEN_MUL_PLAIN, tab, dout.p, stream_);
+  tock();
+  if (out_compressed) {
+    tick("k_compress", 0, (double)count);
+    launch_compress(dout.p, n, n, 1, dcomp.p, stream_);
+    tock();
+    CPX_HIP(hipMemcpyAsync(out_compressed, dcomp.p, 48 * count, hipMemcpyDeviceToHost, stream_));
+  }
+  if (out_affine) CPX_HIP(hipMemcpyAsync(out_affine, dout.p, count * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipStreamSynchronize(stream_));
+  flush_timers();
+}
+
+// whisk.rs:45-55 WhiskTracker::from_k_r and whisk.rs:370 get_k_commitment for every (k, r) pair
+void Engine::whisk_trackers_from_k_r(size_t count, const uint8_t* k, const uint8_t* r, uint8_t* trackers_out, uint8_t* k_commitments_out) {
+  if (!count || (!trackers_out && !k_commitments_out)) return;
+  if (count > kTrackerBatchMax) throw ArgError("trackers: at most 2^23 per call");
+  CPX_HIP(hipSetDevice(device_));
+  const TAff* tab = generator_table();
+  struct Trim {
+    Engine* e;
+    ~Trim() {
+      tier0_trim(e->t0_.fr);
+      tier0_trim(e->t0_.a0);
+      tier0_trim(e->t0_.bytes);
+    }
+  } trim{this};
+  // points: r_0 G, k_0 r_0 G, r_1 G, ... (the trackers as they are serialised), then k_0 G, k_1 G, ...; without trackers only the latter
+  const int mode = !trackers_out ? GEN_MUL_PLAIN : k_commitments_out ? GEN_MUL_BOTH : GEN_MUL_TRACKERS;
+  const size_t points = count * (mode == GEN_MUL_PLAIN ? 1 : mode == GEN_MUL_TRACKERS ? 2 : 3);
+  DevBuf<Fr>& dsc = t0_.fr;   // k | r
+  DevBuf<Aff>& dout = t0_.a0;
+  DevBuf<uint8_t>& dcomp = t0_.bytes;
+  dsc.ensure(2 * count);
+  dout.ensure(points);
+  dcomp.ensure(48 * points);
+  const int n = (int)count, np = (int)points;
+  CPX_HIP(hipMemcpyAsync(dsc.p, k, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  if (trackers_out) CPX_HIP(hipMemcpyAsync(dsc.p + count, r, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  tick("k_gen_mul", 128.0 * points, (double)points);
+  launch_gen_mul(dsc.p, dsc.p + count, n, mode, tab, dout.p, stream_);
+  tock();
+  tick("k_compress", 0, (double)points);
+  launch_compress(dout.p, np, np, 1, dcomp.p, stream_);
+  tock();
+  if (trackers_out) CPX_HIP(hipMemcpyAsync(trackers_out, dcomp.p, 96 * count, hipMemcpyDeviceToHost, stream_));
+  if (k_commitments_out) CPX_HIP(hipMemcpyAsync(k_commitments_out, dcomp.p + (trackers_out ? 96 * count : 0), 48 * count, hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipStreamSynchronize(stream_));
+  flush_timers();
+}
+
 // ---------------------------------------------------------------- shuffle step and shuffle proofs, `count` per call (shuffle.hip)
 // All three calls: the inputs go up once; decoding, the placeholder rule, k R / k S, the gather, M and the compression are a constant number
 // of launches whatever the count, on device-resident data; the count instances become the loaded batch through load_rows (device to device)

@@ -266,6 +266,34 @@ def are_valid_whisk_tracker_proofs(ctx, trackers, k_commitments, proofs):
     return res
 
 
+# ---- many trackers and k commitments per call (cpx_whisk_trackers_from_k_r / cpx_g1_generator_mul) ----
+def trackers_from_k_r(ctx, ks, rs):
+    """whisk.rs:45-55 WhiskTracker::from_k_r and whisk.rs:370 get_k_commitment for every (k, r) pair in ONE library call, on the fixed-base
+    table of the generator.  ks / rs: lists of 32-byte wire scalars.  Returns (list of WhiskTracker, list of 48-byte k commitments)."""
+    count = len(ks)
+    if len(rs) != count:
+        raise ValueError("one r per k")
+    if any(len(x) != FR for x in ks) or any(len(x) != FR for x in rs):
+        raise ValueError("k and r are 32-byte wire scalars")
+    if count == 0:
+        return [], []
+    trk, kc = _out(2 * G1POINT_SIZE * count), _out(G1POINT_SIZE * count)
+    ctx._check(ctx._L.cpx_whisk_trackers_from_k_r(ctx._h, count, _in(b"".join(ks)), _in(b"".join(rs)), trk, kc))
+    tb, cb = bytes(trk), bytes(kc)
+    return ([WhiskTracker(tb[96 * i:96 * i + 48], tb[96 * i + 48:96 * i + 96]) for i in range(count)],
+            [cb[48 * i:48 * (i + 1)] for i in range(count)])
+
+
+def k_commitments(ctx, ks):
+    """whisk.rs:370 get_k_commitment for every k in ONE library call: the 48-byte encodings of k_i * G"""
+    if any(len(x) != FR for x in ks):
+        raise ValueError("k is a 32-byte wire scalar")
+    if not ks:
+        return []
+    cb = ctx.generator_mul(b"".join(ks), compressed=True)[1]
+    return [cb[48 * i:48 * (i + 1)] for i in range(len(ks))]
+
+
 # ---- small helpers of whisk.rs:295-345 ----
 def to_bytes_g1affine(ctx, g1):
     """whisk.rs:307-311: affine wire point (96 B) -> 48-byte compressed encoding"""

@@ -210,6 +210,22 @@ int cpx_whisk_generate_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t*
 int cpx_whisk_verify_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* trackers /* count*96 */, const uint8_t* k_commitments /* count*48 */,
                                     const uint8_t* proofs /* count*128 */, int* verdict /* count */);
 
+/* What the batched tracker calls consume, made `count` per call.  Every point below is a multiple of the BLS12-381 G1 generator G — r G, k G and
+ * k (r G) = (k r mod r_order) G — and comes from a fixed-base table of G (curdleproofs_amd/csrc/gen_table.hpp: radix 256 over the endomorphism
+ * split, 225 KB, at most 32 mixed additions per scalar and no doubling) that a context builds on the device at its first such call.  Conventions
+ * of the batched tracker calls: scalars are 32-byte Montgomery limbs; count = 0 is a no-op returning CPX_OK; a NULL input with count > 0 is
+ * CPX_ERR_ARG and nothing is written; at most 2^23 items per call; no CRS is needed and the loaded batch is untouched (cpx_batch_size is
+ * unchanged); a call costs a constant number of kernel launches and ONE stream synchronisation whatever the count.  A zero scalar gives the
+ * identity: 96 zero bytes affine, 0xc0 || 0^47 compressed.  A scalar whose limbs are not a reduced field element (>= r) is NOT rejected: as with
+ * the k of cpx_whisk_generate_tracker_proofs, the limbs are taken for the Montgomery form they are and stand for limbs / 2^256 mod r. */
+/* out[i] = scalars[i] * G for the BLS12-381 G1 generator (whisk.rs:318,323 with g1 = generator). Either output may be NULL. */
+int cpx_g1_generator_mul(cpx_ctx* ctx, size_t count, const uint8_t* scalars /* count*32 */, uint8_t* out_affine /* count*96 */,
+                         uint8_t* out_compressed /* count*48 */);
+/* whisk.rs:45-55 WhiskTracker::from_k_r and whisk.rs:370 get_k_commitment for `count` (k, r) pairs.
+ * trackers_out[i] = r_i G || k_i r_i G (compressed); k_commitments_out[i] = k_i G; either may be NULL. */
+int cpx_whisk_trackers_from_k_r(cpx_ctx* ctx, size_t count, const uint8_t* k /* count*32 */, const uint8_t* r /* count*32 */,
+                                uint8_t* trackers_out /* count*96 */, uint8_t* k_commitments_out /* count*48 */);
+
 /* The shuffle half of the byte-level API for `count` independent shuffles per call: compressed bytes in, compressed bytes out, and between
  * the uploads and the downloads every step runs on the device in a number of kernel launches that does not depend on count — decoding, the
  * scalar multiplications, the permutation, M (the fixed-base CRS table), normalisation and compression; the proving and verifying is
@@ -242,7 +258,7 @@ int cpx_set_profiling(cpx_ctx* ctx, int on); /* time every kernel group with HIP
 int cpx_reset_stats(cpx_ctx* ctx);
 /* name = kernel name as rocprofv3 reports it, template arguments included: "k_msm_fix<16, 16>", "k_msm_tblw<32, false>",
  * "k_msm_tblw<2, true>", "k_msm_accw", "k_reduce_sets", "k_finalize_ranges", "k_table_build", "k_msm_tail", "k_smul",
- * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
+ * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
  * units = MSM points / scalar-mul elements / points; out pointers may be NULL */
 int cpx_get_stat(const cpx_ctx* ctx, const char* name, uint64_t* launches, double* total_ms, double* algorithmic_bytes, double* units);
 int cpx_set_host_threads(cpx_ctx* ctx, int threads);

@@ -79,6 +79,9 @@ extern "C" {
                                              status: *mut c_int) -> c_int;
     pub fn cpx_whisk_verify_tracker_proofs(ctx: *mut cpx_ctx, count: usize, trackers: *const u8, k_commitments: *const u8, proofs: *const u8,
                                            verdict: *mut c_int) -> c_int;
+    // what those calls consume, `count` per call, as multiples of the generator on its fixed-base table (whisk.rs:45-55, :370); either output may be null
+    pub fn cpx_g1_generator_mul(ctx: *mut cpx_ctx, count: usize, scalars: *const u8, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
+    pub fn cpx_whisk_trackers_from_k_r(ctx: *mut cpx_ctx, count: usize, k: *const u8, r: *const u8, trackers_out: *mut u8, k_commitments_out: *mut u8) -> c_int;
     // `count` shuffles per call (util.rs:83-106, whisk.rs:144-179, :106-130): the instances become the loaded batch; per-item status / verdict
     pub fn cpx_batch_shuffle(ctx: *mut cpx_ctx, count: usize, vec_r: *const u8, vec_s: *const u8, permutation: *const u32, k: *const u8, vec_m_blinders: *const u8,
                              vec_t_out: *mut u8, vec_u_out: *mut u8, m_out: *mut u8) -> c_int;

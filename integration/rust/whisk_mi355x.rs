@@ -136,6 +136,27 @@ pub fn generate_whisk_tracker_proofs<T: RngCore>(rng: &mut T, trackers: &[WhiskT
         .collect()
 }
 
+/// whisk.rs:45-55 `WhiskTracker::from_k_r` and whisk.rs:370 `get_k_commitment` for many (k, r) pairs in one library call: the trackers and the
+/// 48-byte commitments k_i G, in item order (every point is a multiple of the generator: one fixed-base kernel, no per-item call)
+pub fn trackers_from_k_r(ks: &[Fr], rs: &[Fr]) -> (Vec<WhiskTracker>, Vec<[u8; 48]>) {
+    assert!(ks.len() == rs.len());
+    let count = ks.len();
+    let mut trk = vec![0u8; 96 * count];
+    let mut kc = vec![0u8; 48 * count];
+    let rc = unsafe { cpx_whisk_trackers_from_k_r(ctx(), count, scalars_ptr(ks), scalars_ptr(rs), trk.as_mut_ptr(), kc.as_mut_ptr()) };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    let trackers = trk.chunks(96).map(|c| WhiskTracker { r_G: c[..48].try_into().unwrap(), k_r_G: c[48..].try_into().unwrap() }).collect();
+    (trackers, kc.chunks(48).map(|c| c.try_into().unwrap()).collect())
+}
+
+/// whisk.rs:370 `get_k_commitment` for many k in one library call
+pub fn k_commitments(ks: &[Fr]) -> Vec<[u8; 48]> {
+    let mut kc = vec![0u8; 48 * ks.len()];
+    let rc = unsafe { cpx_g1_generator_mul(ctx(), ks.len(), scalars_ptr(ks), std::ptr::null_mut(), kc.as_mut_ptr()) };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    kc.chunks(48).map(|c| c.try_into().unwrap()).collect()
+}
+
 /// whisk.rs:106-130 for many (pre_trackers, post_trackers, proof) triples in one library call: one result per item, in order.  Like the
 /// rest of this file, NOT COMPILED here.
 pub fn are_valid_whisk_shuffle_proofs<T: RngCore>(
