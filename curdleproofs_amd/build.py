@@ -29,6 +29,9 @@ FIELDCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "field_check.hip")
 # test-only device program: the three transcript implementations at every position of the rate (tests/test_gpu_transcript.py)
 TRANSCRIPTCHECK = os.path.join(OUT_DIR, "transcript_check")
 TRANSCRIPTCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "transcript_check.hip")
+# test-only device program: every function of the scalar-side headers on raw words (tests/test_gpu_scalar.py)
+SCALARCHECK = os.path.join(OUT_DIR, "scalar_check")
+SCALARCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "scalar_check.hip")
 DEVICE_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-I", CSRC]   # the library's device flags
 
 
@@ -42,11 +45,12 @@ def _hipcc():
 def _stale():
     check = os.path.exists(FIELDCHECK_SRC)
     tcheck = os.path.exists(TRANSCRIPTCHECK_SRC)
-    outs = [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else [])
+    scheck = os.path.exists(SCALARCHECK_SRC)
+    outs = [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else []) + ([SCALARCHECK] if scheck else [])
     if not all(os.path.exists(o) for o in outs):
         return True
     t = min(os.path.getmtime(o) for o in outs)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else [])
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else []) + ([SCALARCHECK_SRC] if scheck else [])
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -97,6 +101,10 @@ def build(force=False, verbose=False):
             tcheck = os.path.exists(TRANSCRIPTCHECK_SRC)
             if tcheck:
                 procs.append(("transcript_check.hip", subprocess.Popen(_transcriptcheck_cmd(tmp_tcheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+            tmp_scheck = os.path.join(work, "scalar_check")
+            scheck = os.path.exists(SCALARCHECK_SRC)
+            if scheck:
+                procs.append(("scalar_check.hip", subprocess.Popen(_scalarcheck_cmd(tmp_scheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
             for src, p in procs:
                 out, _ = p.communicate()
                 if p.returncode != 0:
@@ -111,6 +119,8 @@ def build(force=False, verbose=False):
                 os.replace(tmp_check, FIELDCHECK)
             if tcheck:
                 os.replace(tmp_tcheck, TRANSCRIPTCHECK)
+            if scheck:
+                os.replace(tmp_scheck, SCALARCHECK)
         finally:
             shutil.rmtree(work, ignore_errors=True)
         build_selfcheck()
@@ -154,6 +164,21 @@ def build_transcriptcheck():
     subprocess.check_call(_transcriptcheck_cmd(TRANSCRIPTCHECK + ".tmp"))
     os.replace(TRANSCRIPTCHECK + ".tmp", TRANSCRIPTCHECK)
     return TRANSCRIPTCHECK
+
+
+def _scalarcheck_cmd(out):
+    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [SCALARCHECK_SRC, "-o", out]
+
+
+def build_scalarcheck():
+    """The device build of tests/device/scalar_check.hip alone (build() compiles it with the library; the host twin is compiled by
+    the tests with g++): cross-compiled here, it travels with the library."""
+    if not os.path.exists(SCALARCHECK_SRC):
+        raise RuntimeError("tests/device/scalar_check.hip is missing: the device scalar check cannot be built")
+    os.makedirs(OUT_DIR, exist_ok=True)
+    subprocess.check_call(_scalarcheck_cmd(SCALARCHECK + ".tmp"))
+    os.replace(SCALARCHECK + ".tmp", SCALARCHECK)
+    return SCALARCHECK
 
 
 if __name__ == "__main__":

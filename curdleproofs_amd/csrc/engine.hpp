@@ -427,6 +427,10 @@ class Engine {
   void tick(const char* name, double bytes, double units, bool span = false);
   bool span_ = false;
   void tock();
+  // the launch "k_smul" times ran as k_smul_quad (what launch_smul reports): counted under a name of its own, launches only
+  void count_smul_quad(bool quad) {
+    if (profiling_ && quad) stats_["k_smul_quad"].launches++;
+  }
   void flush_timers();
   template <class F> void parallel_for(size_t n, F&& f);
   std::unique_ptr<SpinTeam> team_;

@@ -118,8 +118,9 @@ CPX_HD void glv_split(const uint32_t* k, uint32_t* t_abs, uint32_t* q, uint32_t&
   }
 }
 
-// Signed radix-256 digits of a value < 2^127 (4 words): byte w of v + 0x8080...80 is d_w + 128, d_w in [-128, 127],
-// sum d_w 256^w = v; no carry leaves the top byte.
+// Signed radix-256 digits of a value v <= 0x7f7f...7f (4 words; 127 in every digit, the largest sum 16 such digits have): byte w of
+// v + 0x8080...80 is d_w + 128, d_w in [-128, 127], sum d_w 256^w = v; no carry leaves the top byte.  (Not every v < 2^127: from
+// 0x7f7f...80 on the biased sum leaves 128 bits.  The halves of glv_split are at most floor(N / 2) + 1 and r / (2 N) + 1, top byte 0x56.)
 CPX_HD void glv_biased_bytes(const uint32_t* v, uint32_t* out) {
   uint64_t c = 0;
   CPX_UNROLL for (int i = 0; i < 4; i++) {

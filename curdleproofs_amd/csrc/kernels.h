@@ -201,8 +201,8 @@ void launch_compress(const Aff* d_in, int n, int stride, int batch, uint8_t* d_o
 void launch_compress_cols(const Aff* d_in, const uint32_t* d_cols, int ncols, int stride, int batch, uint8_t* d_out, int out_stride, hipStream_t s);
 // exclusive_simd (the T_2 commitments of a small batch on the side stream, at most 16 waves): every wave claims the whole register file of its SIMD
 // quad_max > 0: launches of at most that many elements run with a QUAD per element (k_smul_quad: a third of the one-lane chain's latency, four times its lanes);
-// only for tasks without SMUL_PLAIN
-void launch_smul(const SmulTask* d_tasks, int ntasks, int cnt, hipStream_t s, bool exclusive_simd = false, long quad_max = 0);
+// only for tasks without SMUL_PLAIN.  Returns whether the quad form was launched (the profile counts it as "k_smul_quad" beside "k_smul")
+bool launch_smul(const SmulTask* d_tasks, int ntasks, int cnt, hipStream_t s, bool exclusive_simd = false, long quad_max = 0);
 // compressed bytes -> affine; status[i] = 0 ok, 1 malformed / not on curve, 2 not in the r-torsion subgroup
 // d_src_offset (optional): encoding i starts at byte d_src_offset[i] of d_in (points inside serialized proofs) instead of 48 i
 void launch_decompress(const Options& o, const uint8_t* d_in, int n, Aff* d_out, const uint32_t* d_dst_index, uint8_t* d_status, int check_subgroup, hipStream_t s,

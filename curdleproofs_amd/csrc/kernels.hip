@@ -1524,17 +1524,18 @@ void launch_compress_cols(const Aff* d_in, const uint32_t* d_cols, int ncols, in
   if (ncols <= 0 || batch <= 0) return;
   CPX_LAUNCH(k_compress_cols, dim3(batch), dim3(64), 0, s, d_in, d_cols, ncols, stride, d_out, out_stride);
 }
-void launch_smul(const SmulTask* d_tasks, int ntasks, int cnt, hipStream_t s, bool exclusive_simd, long quad_max) {
+bool launch_smul(const SmulTask* d_tasks, int ntasks, int cnt, hipStream_t s, bool exclusive_simd, long quad_max) {
   const long total = (long)ntasks * cnt;
-  if (total <= 0) return;
+  if (total <= 0) return false;
   const size_t lds = 2 * SMUL_THREADS * sizeof(TF) + 20 * SMUL_THREADS * sizeof(uint32_t);
   const unsigned groups = (unsigned)((total + SMUL_THREADS - 1) / SMUL_THREADS);
   if (quad_max > 0 && total <= quad_max) {   // a small batch's T_2 commitments: a quad per element (never with SMUL_PLAIN tasks: the side stream's only)
     CPX_LAUNCH(k_smul_quad, dim3((unsigned)((total + 15) / 16)), dim3(64), SQ_LDS, s, d_tasks, ntasks, cnt);
-    return;
+    return true;
   }
   if (exclusive_simd && groups <= 16) CPX_LAUNCH(k_smul<true>, dim3(groups), dim3(SMUL_THREADS), lds, s, d_tasks, ntasks, cnt);
   else CPX_LAUNCH(k_smul<false>, dim3(groups), dim3(SMUL_THREADS), lds, s, d_tasks, ntasks, cnt);
+  return false;
 }
 void launch_decompress(const Options& o, const uint8_t* d_in, int n, Aff* d_out, const uint32_t* d_dst_index, uint8_t* d_status, int check_subgroup, hipStream_t s,
                        const uint32_t* d_src_offset) {

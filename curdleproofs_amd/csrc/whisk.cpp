@@ -316,7 +316,7 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
   launch_decompress(opt_, db.p, 2 * n, dtr.p, nullptr, dst.p, 1, stream_, doff.p);
   tock();
   tick("k_smul", 224.0 * 3 * count, 3.0 * count);
-  launch_smul(dtask.p, 3, n, stream_, false, fl ? 0 : opt_.smul_quad_max);
+  count_smul_quad(launch_smul(dtask.p, 3, n, stream_, false, fl ? 0 : opt_.smul_quad_max));
   tock();
   tick("k_compress", 0, 3.0 * count);
   launch_compress(dout.p, 3 * n, 3 * n, 1, d_comp, stream_);
@@ -480,7 +480,7 @@ void Engine::shuffle_device(const ShufflePlan& pl) {
   CPX_HIP(hipMemcpyAsync(sh_.stask.p, tasks.data(), tasks.size() * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemsetAsync(sh_.mjac.p, 0, count * sizeof(Jac), stream_));   // (Z = 0: the identity, until M is known)
   tick("k_smul", 224.0 * 2 * pp, 2.0 * pp);
-  launch_smul(sh_.stask.p, (int)(2 * count), (int)ell, stream_, false, fl ? 0 : opt_.smul_quad_max);
+  count_smul_quad(launch_smul(sh_.stask.p, (int)(2 * count), (int)ell, stream_, false, fl ? 0 : opt_.smul_quad_max));
   tock();
   tick("k_shuffle_gather", 6.0 * sizeof(Aff) * pp, (double)pp);
   launch_shuffle_gather(pl, sh_.perm.p, sh_.kpts.p, sh_.kpts.p + pp, sh_.tu.p, sh_.tu.p + pp, sh_.zip.p, stream_);
