@@ -165,6 +165,27 @@ void Engine::wait_stream() {
 bool Engine::device_prefix(size_t B) const {
   return B >= (size_t)opt_.device_min_batch;
 }
+Engine::LateShape Engine::late_shape(size_t B) const {
+  LateShape lt;
+  const size_t n = n_;
+  lt.m = opt_.late_m ? (int)opt_.late_m : n >= 512 ? 32 : 16;
+  while (lt.m > 16 && !late_supported((int)n, lt.m)) lt.m /= 2;
+  lt.nr = 0;
+  while ((1 << lt.nr) < lt.m) lt.nr++;
+  // (late_min_batch is stated for n <= 256; larger proofs have larger grids per proof: the threshold shrinks with 256 / n)
+  const size_t late_min = n <= 256 ? (size_t)opt_.late_min_batch : std::max<size_t>(1, (size_t)opt_.late_min_batch * 256 / n);
+  lt.on = opt_.late_rounds != 0 && L_ >= (size_t)lt.nr + 1 && B >= late_min && late_supported((int)n, lt.m);
+  return lt;
+}
+bool Engine::smsm_may_fuse(size_t B) const {
+  const size_t fused_smsm_max = n_ <= 256 ? (size_t)opt_.fused_smsm_max : (size_t)opt_.fused_smsm_max * 256 / n_;
+  return !late_shape(B).on && fix_bits_ == 16 && !opt_.serial_streams && opt_.fused_smsm_max > 0 && B <= fused_smsm_max;
+}
+int Engine::tbl_segments_for(size_t B) const {
+  // option 0: two segments up to n = 256 (the A/B of profiles/r10_tbl_segments.md); larger proofs keep one until they are measured
+  const long want = opt_.tbl_segments ? opt_.tbl_segments : (n_ <= 256 ? 2 : 1);
+  return want == 2 && n_ && device_prefix(B) && !smsm_may_fuse(B) ? 2 : 1;
+}
 // hipStreamSynchronize spins on a host core; an event created with hipEventBlockingSync puts the thread to sleep instead.  With
 // one thread per engine context and per rank, and hosts that give a container a small CPU quota, that matters.
 void Engine::wait_stream_blocking() {
@@ -295,6 +316,7 @@ void Engine::launch_tbl_phase(const TblShape& sh, const TblTask* d_tt, const Fix
   if (!sh.nt) return;
   Untimed quiet(this, timed);
   uint32_t* const traw = sc.raw.p + sh.fix_sets * raw_set_words();
+  if (sh.one_launch && sh.tbl_segments != 1) throw std::logic_error("the one-launch phase of a lone proof reads one-segment tables");
   if (sh.one_launch) {   // a lone proof: both MSM kernels of the phase in one launch
     tick("k_msm_fix_tblw", 128.0 * (sh.pts_fix + sh.pts_tbl), sh.pts_fix + sh.pts_tbl);
     launch_msm_fix_tblw(d_ft, (int)sh.nft, fixtab(), (int)nc(), sc.raw.p, sc.rawslot.p, d_tt, (int)sh.ntt, sh.tbl_slices, traw, sc.rawslot.p + sh.fix_sets, st);
@@ -306,8 +328,8 @@ void Engine::launch_tbl_phase(const TblShape& sh, const TblTask* d_tt, const Fix
       tock();
     }
     if (sh.ntt) {
-      tick(tblw_kernel_name(sh.tbl_wpw), 128.0 * sh.pts_tbl, sh.pts_tbl);
-      launch_msm_tblw(d_tt, (int)sh.ntt, sh.tbl_wpw, traw, sc.rawslot.p + sh.fix_sets, st, sh.tbl_slices);
+      tick(tblw_kernel_name(sh.tbl_wpw), 128.0 * sh.pts_tbl, sh.pts_tbl);   // (the statistics keep one name per window grouping, whichever table layout)
+      launch_msm_tblw(d_tt, (int)sh.ntt, sh.tbl_wpw, traw, sc.rawslot.p + sh.fix_sets, st, sh.tbl_slices, sh.tbl_segments);
       tock();
     }
   }
@@ -843,11 +865,11 @@ void Engine::load_rows(size_t batch, const uint8_t* vec_R, const uint8_t* vec_S,
   CPX_HIP(hipMemcpyAsync(d_Mjac_.p, M, batch * sizeof(Jac), kind, stream_));
   // copy 0 of the per-proof tables: M (filled at prove time) | T || O O H O | U || O O O H  (curdleproofs.rs:141-155)
   const size_t NP = np();
-  d_ptab_.ensure(batch * (size_t)copies_ * NP);
+  d_ptab_.ensure(batch * (size_t)pcopies_for(batch) * NP);   // (a prove under other options makes sure of its own layout)
   d_psrc_.ensure(batch * NP);
   // build scratch: the 15 doubled copies of every point — of one chunk of the device prover's table build (engine_device.cpp); the host-driven
   // prover, which builds all rows at once, makes sure of its own (batch_prove_tables)
-  d_tbltmp_.ensure(table_chunk_rows(batch) * NP * (size_t)(copies_ / 2 - 1));
+  d_tbltmp_.ensure(table_chunk_rows(batch) * NP * (size_t)(pcopies_for(batch) / 2 - 1));
   const size_t spitch = NP * sizeof(Aff);
   Aff* t = d_psrc_.p;
   rows(t + 1, spitch, vec_T, vb, vb, kind);
@@ -1043,6 +1065,10 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       CPX_HIP(hipEventCreateWithFlags(&tab_.ev_m, hipEventDisableTiming));
       CPX_HIP(hipEventCreateWithFlags(&tab_.ev_done, hipEventDisableTiming));
     }
+    // (the host-driven prover reads its tables through the lone-proof and small-batch kernels: one-segment tables of copies_ copies, whatever
+    // layout batch_load sized the buffer for)
+    pcopies_ = copies_;
+    d_ptab_.ensure(B * (size_t)copies_ * NP);
     d_tbltmp_.ensure(B * NP * (size_t)(copies_ / 2 - 1));   // (all rows in two launches; load_batch sized the scratch for the device prover's chunks: a no-op below 3072 proofs)
     CPX_HIP(hipEventRecord(tab_.ev_start, stream_));
     CPX_HIP(hipStreamWaitEvent(tab_.stream, tab_.ev_start, 0));

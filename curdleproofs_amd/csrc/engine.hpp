@@ -220,6 +220,11 @@ class Engine {
       if (value) *value = crs_tab_ ? fix_bits_ : 0;
       return true;
     }
+    // "tbl_segments_effective" = the layout of the per-proof tables the loaded batch proves with (0 before the first batch_load)
+    if (key && !strcmp(key, "tbl_segments_effective")) {
+      if (value) *value = B_ ? tbl_segments_for(B_) : 0;
+      return true;
+    }
     return cpx::get_option(opt_, key, value);
   }
   hipStream_t stream() const { return stream_; }
@@ -367,7 +372,7 @@ class Engine {
   // 4096 (6.7 GB of scratch) on a cross-box comparison; the in-process A/B of round 6 (bench.py --ab table_chunks=0,1, profiles/r06_ab_table_chunks.json)
   // has all rows 0.53 % faster in six of six rounds (every chunk launch ends in a tail of long waves) — and HBM footprint is not the metric.
   size_t table_chunk_rows(size_t batch) const {
-    const size_t bytes = batch * np() * (size_t)(copies_ / 2 - 1) * sizeof(TblTmp);
+    const size_t bytes = batch * np() * (size_t)(pcopies_for(batch) / 2 - 1) * sizeof(TblTmp);
     const size_t nch = opt_.table_chunks > 0 ? std::min<size_t>((size_t)opt_.table_chunks, std::max<size_t>(1, batch))
                                              : std::max<size_t>(1, (bytes + ((size_t)16 << 30) - 1) >> 34);
     return (batch + nch - 1) / nch;
@@ -458,7 +463,7 @@ class Engine {
 
   // per-proof table row: copy-major [copies][NP]
   size_t np() const { return PtabRow(n_).count(); }   // M | T_b | U_b
-  TAff* ptab(size_t p) const { return d_ptab_.p + p * (size_t)copies_ * np(); }
+  TAff* ptab(size_t p) const { return d_ptab_.p + p * (size_t)pcopies_ * np(); }
   TblSeg pseg(size_t p, size_t off, uint32_t cnt, const uint32_t* idx = nullptr) const { return TblSeg{ptab(p) + off, idx, (uint32_t)np(), cnt}; }
   TblSeg cseg(size_t off, uint32_t cnt, const uint32_t* idx = nullptr) const { return TblSeg{ctab() + off, idx, (uint32_t)nc(), cnt}; }
   size_t nc() const { return CtabCols(n_).count(); }   // CRS table columns: G | Hvec | H | G_t | G_u | G_sum | H_sum
@@ -483,7 +488,19 @@ class Engine {
   uint8_t crs_H_comp_[48];
 
   // shifted-base tables (all-MSM prover)
-  static constexpr int copies_ = 32;   // table copies per base: 2^(8c) P and z^2 2^(8c) P, c < 16: one per radix-256 window of the split scalar
+  static constexpr int copies_ = 32;   // copies per base of the CRS table: 2^(8c) P and z^2 2^(8c) P, c < 16: one per radix-256 window of the split scalar
+  // The per-proof tables have a copy count of their own, 32 / segments (kernels.h "table-backed MSM").  Two segments where the batch's
+  // path reads them through the stand-alone bucket-list waves and k_late_uniform: the device-resident prover whose SameMSM rounds are not
+  // fused.  The fused rounds (round.hip), the lone-proof kernels and the host-driven prover keep one-segment tables.
+  struct LateShape {
+    int m, nr;
+    bool on;
+  };
+  LateShape late_shape(size_t batch) const;   // the late rounds of a device-resident batch (options late_rounds, late_m, late_min_batch)
+  bool smsm_may_fuse(size_t batch) const;     // whether the batch's SameMSM rounds may run as fused launches (options fused_smsm_max, ...)
+  int tbl_segments_for(size_t batch) const;
+  int pcopies_for(size_t batch) const { return copies_ / tbl_segments_for(batch); }
+  int pcopies_ = copies_;              // copy count of d_ptab_ as the prover in progress lays it out (set when a prove starts)
   // CRS tables are immutable once built and large (15 GB at ell = 252): engines on the same device that are
   // given the same CRS share one copy (process-wide registry in engine.cpp).
   struct CrsTables {

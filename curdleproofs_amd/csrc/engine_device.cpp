@@ -32,8 +32,15 @@ void Engine::build_plan(TblPlan& pl, const std::vector<TblReq>& reqs, const std:
   // requests without a destination scatter their affine point to a write-only slot of proof 0 that NOTHING ever reads: TMP(7) for plans of the
   // main stream, TMP(5) for the plan that runs beside them on the table stream (phase 1t) — two streams never write the same slot
   const uint32_t dummy_dst = slot_index(0, SlotMap(L_).TMP(pl.table_stream ? 5 : 7));
-  tbl_plan(reqs, crs, (uint32_t)msm_fix_parts(fix_bits_, pl.fix_wpw), (uint32_t)msm_tblw_parts(pl.tbl_wpw), dummy_dst, nullptr, comp_index.data(), pl, ht.data(),
-           hf.data(), meta.data());
+  // two-segment per-proof tables: every segment of a table task must be one (the CRS segments all went to the fixed-base kernel)
+  pl.tbl_segments = pcopies_ == copies_ ? 1 : 2;
+  const uint32_t tbl_parts = (uint32_t)msm_tblw_parts(pl.tbl_wpw, pl.tbl_segments);
+  tbl_plan(reqs, crs, (uint32_t)msm_fix_parts(fix_bits_, pl.fix_wpw), tbl_parts, dummy_dst, nullptr, comp_index.data(), pl, ht.data(), hf.data(), meta.data(), nullptr,
+           pl.tbl_segments == 2 ? tbl_parts / 2 : 0);
+  if (pl.tbl_segments == 2)
+    for (const TblTask& t : ht)
+      for (const TblSeg& sg : t.seg)
+        if (sg.n && !(sg.base >= d_ptab_.p && sg.base < d_ptab_.p + d_ptab_.cap)) throw std::logic_error("device plan: a table task outside the two-segment per-proof tables");
   // Long tasks first: a work-group's task is its index in these arrays, partial-sum slots travel with the task (out_first / pad).  With the
   // requests in protocol order a launch ended with the long waves of the last proofs and the GPU drained behind them (~0.8 ms of a
   // 7.6-ms k_msm_fix launch at 8192 proofs); now the one-point tasks fill the tail.
@@ -93,7 +100,10 @@ void Engine::prepare_device_prover() {
   const CtabCols cc(n);
   const size_t NS = sm.count(), NP = np(), nrand = ri.count();
   DevProver& dp = dprove_;
+  // the layout of the per-proof tables this batch proves with (engine.hpp): part of the plans' signature
+  pcopies_ = pcopies_for(B);
   // buffers (sizes only grow; a reallocation changes a pointer and invalidates the plans)
+  d_ptab_.ensure(B * (size_t)pcopies_ * NP);   // (batch_load sized it under the options of its time)
   d_bytes_.ensure(B * 4 * ell * 48);
   d_mcomp_.ensure(B * 48);
   d_tstate_.ensure(B * 27);
@@ -123,7 +133,8 @@ void Engine::prepare_device_prover() {
   const std::vector<const void*> sig = {d_pp_.p,     d_ptab_.p,    d_psrc_.p,  d_bytes_.p,  d_mcomp_.p,   d_tstate_.p,   d_veca_.p,      d_rvec_.p,
                                         dp.rvec2.p,  d_rgam_.p,    d_rbeta_.p, d_rout_.p,   dp.perm.p,    dp.k.p,        dp.mbl.p,       dp.rnd.p,
                                         dp.vec.p,    dp.sc.p,      dp.slotcomp.p, dp.proofs.p, side_.tasks.p, side_.stasks.p, side_.dst.p, side_.conv.p,
-                                        ctab(),      fixtab(),     (const void*)(uintptr_t)B, (const void*)(uintptr_t)ell, (const void*)(uintptr_t)fix_bits_};
+                                        ctab(),      fixtab(),     (const void*)(uintptr_t)B, (const void*)(uintptr_t)ell, (const void*)(uintptr_t)fix_bits_,
+                                        (const void*)(uintptr_t)pcopies_};
   if (sig == dp.signature) return;
   dp.signature.clear();
 
@@ -184,13 +195,10 @@ void Engine::prepare_device_prover() {
   // proofs of ell = 1020: m = 16 534.8 ms, m = 32 506.1 ms, m = 64 506.7 ms (six rounds, two k_late_uniform waves per proof: no further gain);
   // 4096 proofs of ell = 508: 500.9 / 475.8 / 495.2 ms; 8192 proofs of ell = 252: 507.4 / 511.2 ms
   DevProver::Late& lt = dp.late;
-  lt.m = opt_.late_m ? (int)opt_.late_m : n >= 512 ? 32 : 16;
-  while (lt.m > 16 && !late_supported((int)n, lt.m)) lt.m /= 2;
-  lt.nr = 0;
-  while ((1 << lt.nr) < lt.m) lt.nr++;
-  // (late_min_batch is stated for n <= 256; larger proofs have larger grids per proof: the threshold shrinks with 256 / n)
-  const size_t late_min = n <= 256 ? (size_t)opt_.late_min_batch : std::max<size_t>(1, (size_t)opt_.late_min_batch * 256 / n);
-  lt.on = opt_.late_rounds != 0 && L >= (size_t)lt.nr + 1 && B >= late_min && late_supported((int)n, lt.m);
+  const LateShape ls = late_shape(B);   // (engine.cpp: the layout of the per-proof tables depends on it, too)
+  lt.m = ls.m;
+  lt.nr = ls.nr;
+  lt.on = ls.on;
   lt.j0 = lt.on ? L - (size_t)lt.nr : L;
   // fused log rounds (round.hip): every round of both arguments is ONE launch — for the batches in which a round is a chain of latency-bound
   // kernels (below the late rounds' threshold; the 16-bit table of multiples)
@@ -199,6 +207,7 @@ void Engine::prepare_device_prover() {
   const bool fused_ok = !lt.on && fix_bits_ == 16 && !opt_.serial_streams;
   dp.fused = fused_ok && opt_.fused_rounds_max > 0 && B <= fused_max;
   dp.fused_smsm = fused_ok && opt_.fused_smsm_max > 0 && B <= fused_smsm_max;
+  if (dp.fused_smsm && pcopies_ != copies_) throw std::logic_error("fused SameMSM rounds read one-segment tables");   // (smsm_may_fuse() says the same)
   // wave shapes of the fused rounds: as many waves per proof as find a SIMD of their own (1024 SIMDs; proofs of n > 256 take n / 256 times the work)
   const size_t simd_share = 1024 * 256 / (B * std::max<size_t>(n, 256));   // SIMDs per proof
   const int f_fix_ipa = opt_.fused_fix_wpw ? (int)opt_.fused_fix_wpw : (simd_share >= 16 ? 4 : simd_share >= 8 ? 8 : 16);   // 16 / 8 / 4 waves per proof
@@ -487,7 +496,7 @@ void Engine::prepare_device_prover() {
       dp.rcount.ensure(B);
     }
     main_.ensure(max_sets, max_parts);
-    d_tbltmp_.ensure(std::max(table_chunk_rows(B) * NP * (size_t)(copies_ / 2 - 1),   // one chunk of the table build ...
+    d_tbltmp_.ensure(std::max(table_chunk_rows(B) * NP * (size_t)(pcopies_ / 2 - 1),   // one chunk of the table build ...
                               (3 * B * (size_t)lt.m + 63) / 64 * 64 * late_tmp_per_lane()));               // ... or the multiples of the late rounds' materialised points
   }
   dp.signature = sig;
@@ -558,7 +567,8 @@ void Engine::enqueue_prove_device() {
   for (size_t r0 = 0, ch = table_chunk_rows(B); r0 < B; r0 += ch) {
     const size_t rows = std::min(ch, B - r0);
     tick("k_table_build", 0, (double)(rows * NP));
-    launch_table_build(opt_, d_psrc_.p + r0 * NP, NP, d_ptab_.p + r0 * (size_t)copies_ * NP, (int)rows, (size_t)copies_ * NP, (int)NP, (int)NP, copies_, true, d_tbltmp_.p, tabs);
+    launch_table_build(opt_, d_psrc_.p + r0 * NP, NP, d_ptab_.p + r0 * (size_t)pcopies_ * NP, (int)rows, (size_t)pcopies_ * NP, (int)NP, (int)NP, pcopies_, true, d_tbltmp_.p, tabs,
+                       8);   // copy c = 2^(8c) P whatever the copy count
     tock();
   }
   CPX_HIP(hipEventRecord(dp.ev_t1, tabs));
@@ -676,8 +686,8 @@ void Engine::enqueue_prove_device() {
       // (T_b, U_b with two lanes per output fill a wave at m = 16, with one lane per output at m = 32; m = 64: two waves per proof; G_b comes
       // from the table of multiples like G and G')
       tick("k_late_uniform", 128.0 * 2 * n * B, (double)(2 * n * B));
-      launch_late_uniform(dp.rvec2.p + n, 2 * n, d_ptab_.p, (size_t)copies_ * NP, (int)NP, ctab(), (int)nc(), lt.gb_cols, (int)n, lt.m, 2, 4 * lt.m <= 64 ? 2 : 1,
-                          lt.jac.p + LATE_F_T * BM, BM, Bi, stream_);
+      launch_late_uniform(dp.rvec2.p + n, 2 * n, d_ptab_.p, (size_t)pcopies_ * NP, (int)NP, ctab(), (int)nc(), lt.gb_cols, (int)n, lt.m, 2, 4 * lt.m <= 64 ? 2 : 1,
+                          lt.jac.p + LATE_F_T * BM, BM, Bi, stream_, copies_ / pcopies_);
       tock();
       launch_late_fix(dp.rvec2.p + n, 2 * n, lt.gb_cols, (int)n, lt.m, fixtab(), fix_bits_, (int)nc(), lt.jac.p + LATE_F_GB * BM, (size_t)lt.m, Bi, stream_);
       tick("k_late_tables", 0, (double)(3 * BM));

@@ -44,6 +44,8 @@ struct Options {
   long late_slices = 8;            // lanes per cross term of a late round (1, 2, 4, 8): 15.3 k proofs/s at 8, 14.9 k at 4 and 2, 14.3 k at 1
   long rs_pairs = 1;               // 1: the prover's R and S MSMs of a proof share their waves (same scalars: one digit sort for both); 0: two separate tasks
   long table_chunks = 0;           // launches of the device prover's per-proof table build: 0 = all rows at once while the scratch stays below 16 GiB (8192 proofs of ell = 252: 13.5 GB), k = exactly k equal chunks (2: round 5's default, 6.7 GB, 0.5 % slower in the round-6 A/B)
+  long tbl_segments = 0;           // weight classes of the per-proof tables (below, "table-backed MSM"): 1 = 16 + 16 copies, 2 = 8 + 8 copies wherever the batch's path supports them
+                                   // (read-only `tbl_segments_effective`: the layout the loaded batch proves with), 0 = by the proof size
   long table_stream_max = 4096;            // up to this many proofs (n <= 256; scaled by 256 / n above) the prover's per-proof tables and B_t, B_u run on a table stream beside phase 1 (engine_device.cpp); larger batches fill the GPU with either and keep them in line
   long transcript_excl_max = 256;          // up to this many proofs a wave of k_transcript_step1 claims the whole register file of its SIMD: no wave of a concurrent kernel is placed beside it (a shared SIMD costs a lone dependent chain 1.7x)
   long transcript_lane_min_batch = 8192;   // batches of at least this many proofs (n <= 256; scaled by n / 256 above) hash the transcript prefix with one LANE per proof (k_transcript_step1_lane): a fifth of the wave instructions but a chain of 19 ms at ell = 252 — only where the table build (prover) and the decompression (verifier: 18.7 ms per 8192 proofs) hide it; +2.2 % at 2 x 8192 proofs
@@ -96,10 +98,19 @@ struct SmulTask {
 
 // ---- table-backed MSM (no doubling tails) ----
 // Tables and partial sums are in the table kernels' representation (g1_28.hpp: TAff / TJac, 28-bit limbs).
-// A table holds, for every base point P_i, 32 affine copies, copy-major (entry (c, i) at base + c*copy_stride + i):
+// A 32-copy table holds, for every base point P_i, 32 affine copies, copy-major (entry (c, i) at base + c*copy_stride + i):
 // 2^(8c) * P_i for c = 0..15 and z^2 * 2^(8(c-16)) * P_i = -phi(2^(8(c-16)) P_i) for c = 16..31.  A scalar is split as
 // k = +-(+-|t| + q z^2) (glv.hpp); every radix-256 window of |t| and of q has its own copy, so all window sums carry
-// weight 1 and no doubling is left in the MSM.
+// weight 1 and no doubling is left in the MSM.  That is the layout of the CRS table (built once) and of one-segment per-proof tables.
+//
+// TWO-SEGMENT per-proof tables (option tbl_segments; built per prove, 513 bases per proof at ell = 252) hold 16 copies: 2^(8c) P for
+// c = 0..7, then their 8 endomorphism images — 56 doublings and 7 normalised copies per base instead of 120 and 15.  Window w of a half
+// reads copy w mod 8 and belongs to weight class w div 8 (recode.hpp tbl_window): the sums of class 0 carry weight 1 among
+// themselves, those of class 1 the weight 2^64, and an MSM result is sum_class0 + 2^64 sum_class1.  The bucket waves keep the classes
+// apart (class x magnitude bins, msm_body.hpp), the class-1 partial sums of a task come FIRST in its range of partial slots, and the
+// per-request count of k_finalize_ranges carries their number in its upper 16 bits: the finalisation doubles their sum 64 times — once
+// per MSM output instead of once per base.  A launch of the two-segment kernels takes tasks whose segments ALL are such tables (the
+// device-resident prover never mixes them with CRS copies: those go to the fixed-base kernel).
 struct TblSeg {
   const TAff* base;         // copy 0
   const uint32_t* idx;      // optional gather list (indices within a copy)
@@ -121,9 +132,10 @@ struct TblTmp {   // table-build scratch: a Jacobian copy and the running produc
 // -> partial sums d_part[task.pad + j], j < 64 / wpw
 int msm_tblw_windows_per_wave(const Options& o, int ntasks);
 int msm_tblw_parts(int wpw);   // waves (= partial sums) per task
+int msm_tblw_parts(int wpw, int segments);   // two-segment tables: waves of 16 / 32 windows leave four sets; the first half of a task's partials carries the weight 2^64
 // slices > 1 (a few tasks in flight): that many waves share a task's points; a task then leaves slices * msm_tblw_parts(wpw) partial sums
 int msm_tblw_slices(const Options& o, int ntasks, int wpw, int max_n);   // max_n: points of the largest task
-void launch_msm_tblw(const TblTask* d_tasks, int ntasks, int wpw, uint32_t* d_raw, uint32_t* d_raw_slot, hipStream_t s, int slices = 1);
+void launch_msm_tblw(const TblTask* d_tasks, int ntasks, int wpw, uint32_t* d_raw, uint32_t* d_raw_slot, hipStream_t s, int slices = 1, int segments = 1);
 // The MSM waves of k_msm_tblw / k_msm_fix leave their 64 lane accumulators as "raw sets" (raw_set_words() 32-bit words
 // each; tblw: 2 sets per wave, fix: 1) plus the partial-sum slot every set belongs to; launch_reduce_sets turns them
 // into d_part[slot] (bucket sets of k_msm_tblw: weighted sums; k_msm_fix: plain sums).
@@ -179,6 +191,7 @@ void launch_fix_build(const TAff* d_shift, int nc, int cbits, TFix* d_fix_tab, T
 // output o = sum of partials [first[o], first[o] + count[o]) -> standard form, normalised + compressed (+ optional affine scatter)
 // d_addends (optional): [n][3] indices into d_aff of affine points (results of earlier phases) to add to output o; ~0u = none
 // d_comp_index (optional): output o's compressed bytes go to d_comp + 48 * d_comp_index[o] instead of d_comp + 48 * o
+// d_count[o] = partial sums of output o (lower 16 bits) | how many of them, the first ones, carry the weight 2^64 (upper 16 bits)
 void launch_finalize_ranges(const Options& o, const TJac* d_part, const uint32_t* d_first, const uint32_t* d_count, int n, Aff* d_aff, const uint32_t* d_dst_index,
                             uint8_t* d_comp, hipStream_t s, const uint32_t* d_addends = nullptr, const uint32_t* d_comp_index = nullptr);
 
@@ -243,10 +256,11 @@ bool late_supported(int n, int m);
 // out[p * ostride + i] = sum_t scal[p * sstride + t m + i] * CRS column (cols ? cols[t m + i] : t m + i),  i < m
 void launch_late_fix(const Fr* d_scal, size_t sstride, const uint32_t* d_cols, int n, int m, const TFix* d_fix_tab, int cbits, int nc, TJac* d_out, size_t ostride,
                      int nproofs, hipStream_t s);
-// out[f * fstride + p * m + i] = sum_t sm[p * sstride + t m] * F_(t m + i) for the families f < nfam: T_b, U_b (per-proof 32-copy tables,
+// out[f * fstride + p * m + i] = sum_t sm[p * sstride + t m] * F_(t m + i) for the families f < nfam: T_b, U_b (per-proof shifted tables,
 // row M | T_b | U_b, NP columns) and G_b (CRS copies d_ctab, nc columns, column map d_gb_cols)
+// segments = 2: the per-proof tables are two-segment ones (8 + 8 copies); the CRS family then reads copies 0..7 / 16..23 of its 32
 void launch_late_uniform(const Fr* d_sm, size_t sstride, const TAff* d_ptab, size_t ptab_proof_stride, int NP, const TAff* d_ctab, int nc, const uint32_t* d_gb_cols, int n,
-                         int m, int nfam, int split, TJac* d_out, size_t fstride, int nproofs, hipStream_t s);   // split: lanes per output (> 1 only while nfam * m * split <= 64); ceil(nfam * m * split / 64) waves per proof
+                         int m, int nfam, int split, TJac* d_out, size_t fstride, int nproofs, hipStream_t s, int segments = 1);   // split: lanes per output (> 1 only while nfam * m * split <= 64); ceil(nfam * m * split / 64) waves per proof
 void launch_late_tables(const TJac* d_jac, TAff* d_tab, TblTmp* d_tmp, int npoints, hipStream_t s);
 void launch_late_msm(const LateRound& r, hipStream_t s);
 void launch_late_restart(Fr* d_vec, int n, int m, int nproofs, hipStream_t s);

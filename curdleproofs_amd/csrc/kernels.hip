@@ -279,6 +279,14 @@ template <int WPW, bool PERWIN = false> __global__ __launch_bounds__(64, 2) void
   msm_tblw_body<WPW, PERWIN>(tasks, raw, raw_slot, slices, blockIdx.x);
 }
 
+// Two-segment per-proof tables (kernels.h): a wave of 16 or 32 windows serves both weight classes (msm_tblw2_body: four raw sets), a
+// narrower one lies inside one class.
+template <int WPW> __global__ __launch_bounds__(64, 2) void k_msm_tblw2(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw, uint32_t* __restrict__ raw_slot,
+                                                                        int slices) {
+  if constexpr (WPW >= 16) msm_tblw2_body<WPW>(tasks, raw, raw_slot, slices, blockIdx.x);
+  else msm_tblw_body<WPW, false, false, 2>(tasks, raw, raw_slot, slices, blockIdx.x);
+}
+
 __global__ __launch_bounds__(64, 2) void k_msm_tblw_pair(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw, uint32_t* __restrict__ raw_slot) {
   msm_tblw_body<2, true, true>(tasks, raw, raw_slot, 1, blockIdx.x);
 }
@@ -348,6 +356,11 @@ template <int CB> __global__ __launch_bounds__(64) void k_fix_build(const TAff* 
   }
 }
 
+__device__ __noinline__ TJac t_dbl_n(TJac p, int n) {
+#pragma unroll 1
+  for (int s = 0; s < n; s++) p = t_dbl(p);
+  return p;
+}
 // Thread per request: add its partial sums [first, first + count), normalise (one inversion per work-group),
 // convert to the standard form, scatter the affine point and emit the 48-byte compressed encoding.
 __global__ __launch_bounds__(64) void k_finalize_ranges(const TJac* __restrict__ part, const uint32_t* __restrict__ first, const uint32_t* __restrict__ count,
@@ -359,9 +372,13 @@ __global__ __launch_bounds__(64) void k_finalize_ranges(const TJac* __restrict__
   TJac p = TJac::identity();
   if (g < n) {
     const TJac* src = part + first[g];
-    const uint32_t c = count[g];
+    const uint32_t c = count[g] & 0xffffu, hi = count[g] >> 16;   // the first `hi` partial sums carry the weight 2^64 (two-segment tables, kernels.h)
     if (c) p = src[0];
-    for (uint32_t j = 1; j < c; j++) p = t_add(p, src[j]);
+    for (uint32_t j = 1; j < c; j++) {
+      if (j == hi) p = t_dbl_n(p, 64);
+      p = t_add(p, src[j]);
+    }
+    if (hi && hi == c) p = t_dbl_n(p, 64);
     if (addends) {   // up to three already-normalised points of out_aff (results of earlier phases) added with coefficient 1
       for (int j = 0; j < 3; j++) {
         const uint32_t a = addends[3 * g + j];
@@ -390,11 +407,11 @@ __global__ __launch_bounds__(64) void k_finalize_ranges_wave(const TJac* __restr
   TAcc* buf = reinterpret_cast<TAcc*>(smem);   // [256]: up to 255 sums + the identity (entry 255) for idle quads
   const int lane = threadIdx.x, g = blockIdx.x;
   const TJac* src = part + first[g];
-  const uint32_t c = count[g];
+  const uint32_t c = count[g] & 0xffffu, hi = count[g] >> 16;   // the first `hi` partial sums carry the weight 2^64 (two-segment tables, kernels.h)
   int m = c < 255 ? (int)c : 255;
   for (int i = lane; i < m; i += 64) {
-    TJac p = src[i];
-    for (uint32_t j = i + 255; j < c; j += 255) p = t_add(p, src[j]);   // (more partial sums than entries: never in the shipped configurations)
+    TJac p = (uint32_t)i < hi ? t_dbl_n(src[i], 64) : src[i];   // (every lane shifts its own entry: the 64 doublings are paid once in time)
+    for (uint32_t j = i + 255; j < c; j += 255) p = t_add(p, j < hi ? t_dbl_n(src[j], 64) : src[j]);   // (more partial sums than entries: never in the shipped configurations)
     buf[i] = xyzz28_from_jac(p);
   }
   if (lane == 0) {
@@ -465,9 +482,10 @@ __device__ __forceinline__ void tmp_load(const uint32_t* tmp, size_t nthreads, s
 }
 
 // Thread per base point: reads the standard-form source point, writes copy 0 in table form, then runs a chain
-// of 256 - sb doublings storing every sb-th value; the C-1 Jacobian copies are normalised with the thread's own
-// Montgomery trick plus one inversion per work-group.
-// Product body: Karatsuba through the out-of-line f28_mul / f28_sqr (its 120 doublings per base), Karatsuba reduction included;
+// of (real - 1) sb doublings storing every sb-th value (real = shifted copies: 16 for a 32-copy endomorphism row, 120 doublings; 8
+// for a two-segment per-proof row, 56 doublings, sb passed as step_bits = 8); the real - 1 Jacobian copies are normalised with the
+// thread's own Montgomery trick plus one inversion per work-group.
+// Product body: Karatsuba through the out-of-line f28_mul / f28_sqr (its 56 or 120 doublings per base), Karatsuba reduction included;
 // resources unchanged (profiles/r08_f28_redc_karatsuba.md).
 __global__ __launch_bounds__(64) void k_table_build(const Aff* __restrict__ src, size_t src_row_stride, TAff* __restrict__ table, int rows, size_t row_stride,
                                                      int npts, int copy_stride, int copies, int endo, TblTmp* __restrict__ tmp_, int step_bits) {
@@ -520,7 +538,7 @@ __global__ __launch_bounds__(64) void k_table_build(const Aff* __restrict__ src,
 }
 
 // A few rows (a lone proof): one QUAD per base point.  The chain of doublings is what the build waits for (120 of them for the
-// 16 + 16 copies of an endomorphism row): three product rounds per doubling over the quad instead of seven products of one lane;
+// 16 + 16 copies of an endomorphism row, 56 for the 8 + 8 of a two-segment one): three product rounds per doubling over the quad instead of seven products of one lane;
 // the copies are dealt to the four lanes, which normalise their four each (the work-group's one inversion as before).  The copies
 // wait in LDS instead of the scratch buffer.
 constexpr int TBQ_CHUNK = 4;   // copies per lane: real - 1 <= 16
@@ -1265,6 +1283,7 @@ const OptField kOptFields[] = {
     {"scale_any_point", &Options::scale_any_point, 0, 1},         {"strict_infinity", &Options::strict_infinity, 0, 1},
     {"fused_rounds_max", &Options::fused_rounds_max, 0, 1L << 30}, {"fused_smsm_max", &Options::fused_smsm_max, 0, 1L << 30}, {"fused_fix_wpw", &Options::fused_fix_wpw, 0, 16},
     {"smul_quad_max", &Options::smul_quad_max, 0, 1L << 30},       {"fused_tbl_wpw", &Options::fused_tbl_wpw, 8, 32},             {"fused_combine", &Options::fused_combine, -1, 1},
+    {"tbl_segments", &Options::tbl_segments, 0, 2},
 };
 bool option_value_ok(const OptField& f, long v) {
   if (v < f.lo || v > f.hi) return false;
@@ -1403,9 +1422,20 @@ int msm_tblw_slices(const Options& o, int ntasks, int wpw, int max_n) {
   while (s > 1 && max_n / s < 256) s >>= 1;
   return s;
 }
-void launch_msm_tblw(const TblTask* d_tasks, int ntasks, int wpw, uint32_t* d_raw, uint32_t* d_raw_slot, hipStream_t s, int slices) {
+int msm_tblw_parts(int wpw, int segments) { return segments == 2 && wpw >= 16 ? 128 / wpw : 64 / wpw; }
+void launch_msm_tblw(const TblTask* d_tasks, int ntasks, int wpw, uint32_t* d_raw, uint32_t* d_raw_slot, hipStream_t s, int slices, int segments) {
   if (ntasks <= 0) return;
   const dim3 grid(ntasks * (TBW_WINDOWS / wpw) * slices), block(64);
+  if (segments == 2) {
+    switch (wpw) {
+      case 32: CPX_LAUNCH(k_msm_tblw2<32>, grid, block, TBW2_LDS, s, d_tasks, d_raw, d_raw_slot, slices); break;
+      case 16: CPX_LAUNCH(k_msm_tblw2<16>, grid, block, TBW2_LDS, s, d_tasks, d_raw, d_raw_slot, slices); break;
+      case 4: CPX_LAUNCH(k_msm_tblw2<4>, grid, block, TBW_LDS, s, d_tasks, d_raw, d_raw_slot, slices); break;
+      case 2: CPX_LAUNCH(k_msm_tblw2<2>, grid, block, TBW_LDS_CACHE, s, d_tasks, d_raw, d_raw_slot, slices); break;
+      default: CPX_LAUNCH(k_msm_tblw2<8>, grid, block, TBW_LDS, s, d_tasks, d_raw, d_raw_slot, slices); break;
+    }
+    return;
+  }
   switch (wpw) {
     case 32: CPX_LAUNCH(k_msm_tblw<32>, grid, block, TBW_LDS, s, d_tasks, d_raw, d_raw_slot, slices); break;
     case 16: CPX_LAUNCH(k_msm_tblw<16>, grid, block, TBW_LDS, s, d_tasks, d_raw, d_raw_slot, slices); break;

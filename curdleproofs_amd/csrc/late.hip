@@ -10,11 +10,12 @@
 //      basis), T_b, U_b — the identity the all-MSM form rests on, evaluated once at round j0 = log2(n) - log2(m):
 //        k_late_fix      CRS families from the fixed-base table of multiples: one LANE per output walks its n/m points x 16
 //                        windows = exactly (n/m) * 16 mixed additions, no buckets, no raw sets, no reduction kernels;
-//        k_late_uniform  T_b, U_b (and G_b) from the 32-copy shifted tables: the fold coefficients S_t are the same for every
+//        k_late_uniform  T_b, U_b (and G_b) from the shifted tables (32 copies, or 16 in two weight classes: kernels.h): the fold coefficients S_t are the same for every
 //                        output i and for T, U, G_b, so ALL lanes of a wave (lane = output) share one digit sequence: the
 //                        (t, window) entries are counting-sorted by |digit| once per proof and every lane runs the same
 //                        running-sum schedule  sum_b b B_b = sum_b (sum_{b' >= b} B_b')  without bucket storage:
-//                        32 n/m mixed additions + 128 full additions per output.
+//                        32 n/m mixed additions + 128 full additions per output (two-segment tables: one such schedule per weight
+//                        class, 64 doublings between them).
 //   2. k_late_tables   small multiples 1..8 of every materialised point and their endomorphism images, affine (one inversion per
 //                      work-group): what a 4-bit signed window method needs.
 //   3. k_late_msm      every cross term of a late round is an m/2-point MSM over the materialised points: Straus interleaving over
@@ -74,7 +75,7 @@ template <int CB> __global__ __launch_bounds__(64, 2) void k_late_fix(const Fr* 
   out[(size_t)p * ostride + i] = t_acc_to_jac(acc);
 }
 
-// ------------------------------------------------------------------ 1b. T_b, U_b, G_b from the 32-copy shifted tables
+// ------------------------------------------------------------------ 1b. T_b, U_b, G_b from the shifted tables
 // `waves` waves per proof (one while nfam * m * split <= 64: m = 16 with two lanes per output, m = 32 with one; m = 64: two waves, each
 // sorting the proof's digit list for itself).  lane = family * m + i (family 0: T_b, 1: U_b, 2: G_b via the CRS copies); the n/m fold coefficients
 // S_t = sm[t m] are split (glv.hpp) and recoded once, their 32 n/m (t, copy) entries sorted by |digit| into `list`
@@ -84,15 +85,16 @@ constexpr int LU_MAX_T = 128;                       // n / m <= 128
 // r07 body, two waves per SIMD (profiles/r08_f28_redc_karatsuba.md).
 __global__ __launch_bounds__(64, 2) void k_late_uniform(const Fr* __restrict__ sm, size_t sstride, const TAff* __restrict__ ptab, size_t ptab_proof_stride, int NP,
                                                         const TAff* __restrict__ ctab, int nc, const uint32_t* __restrict__ gb_cols, int n, int m, int nfam,
-                                                        int split, int waves, TJac* __restrict__ out, size_t fstride) {
+                                                        int split, int waves, TJac* __restrict__ out, size_t fstride, int segs) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int nt = n / m, nent = 32 * nt;
   TAcc* total = reinterpret_cast<TAcc*>(smem);                                    // [64]
   uint16_t* list = reinterpret_cast<uint16_t*>(smem + 64 * sizeof(TAcc));         // [nent] (t << 6) | (copy << 1) | neg
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(list + ((nent + 1) & ~1));          // [129] entries per magnitude
-  uint32_t* cur = cnt + 132;                                                      // [129] scatter cursors
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(list + ((nent + 1) & ~1));          // [2][132] entries per (weight class, magnitude); one-segment tables: class 0 only
+  uint32_t* cur = cnt + 2 * 132;                                                  // [2][132] scatter cursors
   const int p = blockIdx.x / waves, lane = threadIdx.x, flat = (blockIdx.x % waves) * 64 + lane;   // flat: the lane's index among the proof's lanes
-  for (int b = lane; b < 132; b += 64) cnt[b] = 0;
+  const uint32_t real = segs == 2 ? 8u : 16u;   // shifted copies per endomorphism half of the per-proof tables (recode.hpp tbl_window)
+  for (int b = lane; b < 2 * 132; b += 64) cnt[b] = 0;
   __syncthreads();
   // digits of S_t (lane t; nt may exceed 64)
   for (int t0 = 0; t0 < nt; t0 += 64) {
@@ -105,17 +107,18 @@ __global__ __launch_bounds__(64, 2) void k_late_uniform(const Fr* __restrict__ s
       glv_biased_bytes(qq, bytes + 4);
       CPX_UNROLL for (int c = 0; c < 32; c++) {
         const int d = (int)((bytes[c >> 2] >> (8 * (c & 3))) & 255u) - 128;
-        if (d) atomicAdd(&cnt[d < 0 ? -d : d], 1u);
+        if (d) atomicAdd(&cnt[tbl_window((uint32_t)c, real).cls * 132 + (d < 0 ? -d : d)], 1u);
       }
     }
   }
   __syncthreads();
-  if (lane == 0) {   // offsets in descending magnitude order
+  if (lane == 0) {   // offsets: class 1 before class 0, each in descending magnitude order
     uint32_t o = 0;
-    for (int b = 128; b >= 1; b--) {
-      cur[b] = o;
-      o += cnt[b];
-    }
+    for (int cl = 1; cl >= 0; cl--)
+      for (int b = 128; b >= 1; b--) {
+        cur[cl * 132 + b] = o;
+        o += cnt[cl * 132 + b];
+      }
   }
   __syncthreads();
   for (int t0 = 0; t0 < nt; t0 += 64) {
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(64, 2) void k_late_uniform(const Fr* __restrict__ s
         const int d = (int)((bytes[c >> 2] >> (8 * (c & 3))) & 255u) - 128;
         if (d) {
           const uint32_t neg = (d < 0 ? 1u : 0u) ^ (c < 16 ? sg_lo : sg_hi);
-          list[atomicAdd(&cur[d < 0 ? -d : d], 1u)] = (uint16_t)(((uint32_t)t << 6) | ((uint32_t)c << 1) | neg);
+          list[atomicAdd(&cur[tbl_window((uint32_t)c, real).cls * 132 + (d < 0 ? -d : d)], 1u)] = (uint16_t)(((uint32_t)t << 6) | ((uint32_t)c << 1) | neg);
         }
       }
     }
@@ -156,21 +159,48 @@ __global__ __launch_bounds__(64, 2) void k_late_uniform(const Fr* __restrict__ s
       cstride = (size_t)nc;
     }
   }
-  TAcc acc = TAcc::identity();
+  // Two-segment tables: the entries of class 1 carry the weight 2^64.  Two lanes per output: lane `sub` walks class `sub` alone (every
+  // entry of it) and lane 1 doubles its total 64 times before the join.  Otherwise a lane runs the classes one after the other: class
+  // 1, 64 doublings of the total, then class 0 continuing on that total with a fresh running sum.  The G_b family reads the copies
+  // 2^(8 (w mod 8)) P of the 32-copy CRS table the same way.
+  const bool by_class = segs == 2 && split == 2;
+  const int cl_first = by_class ? sub : segs - 1, cl_last = by_class ? sub : 0;
+  const uint32_t stride = by_class ? 1u : (uint32_t)split, off = by_class ? 0u : (uint32_t)sub;
+  const uint32_t chalf = fam < 2 ? real : 16u;   // where the endomorphism images start in the lane's table
   total[lane] = TAcc::identity();
   uint32_t pos = 0;
-  for (int b = 128; b >= 1; b--) {
-    const uint32_t c = cnt[b];
-    if (live) {
-      for (uint32_t e = pos + (uint32_t)sub; e < pos + c; e += (uint32_t)split) {
-        const uint32_t en = list[e];
-        const uint32_t k = (en >> 6) * (uint32_t)m + (uint32_t)i;
-        const TAff q = base[(size_t)((en >> 1) & 31u) * cstride + (fam < 2 ? k : gb_cols[k])];
-        acc = t_acc_add_mixed_inl(acc, t_cneg_lazy(q, (en & 1u) != 0));
-      }
-      if (pos + c) total[lane] = t_acc_add(total[lane], acc);   // the running sum waits in LDS between its additions (VGPR budget)
+  if (cl_first == 0)
+    for (int b = 128; b >= 1; b--) pos += cnt[132 + b];   // class 0 follows class 1 in the list
+  for (int cl = cl_first; cl >= cl_last; cl--) {
+    TAcc acc = TAcc::identity();
+    uint32_t seen = 0;
+    if (cl != cl_first && live) {
+      TAcc t = total[lane];
+#pragma unroll 1
+      for (int d = 0; d < 64; d++) t = t_acc_dbl(t);
+      total[lane] = t;
     }
-    pos += c;
+    for (int b = 128; b >= 1; b--) {
+      const uint32_t c = cnt[cl * 132 + b];
+      if (live) {
+        for (uint32_t e = pos + off; e < pos + c; e += stride) {
+          const uint32_t en = list[e];
+          const uint32_t k = (en >> 6) * (uint32_t)m + (uint32_t)i, w = (en >> 1) & 31u;
+          const uint32_t copy = segs == 2 ? (w & 7u) + (w >= 16u ? chalf : 0u) : w;
+          const TAff q = base[(size_t)copy * cstride + (fam < 2 ? k : gb_cols[k])];
+          acc = t_acc_add_mixed_inl(acc, t_cneg_lazy(q, (en & 1u) != 0));
+        }
+        if (seen + c) total[lane] = t_acc_add(total[lane], acc);   // the running sum waits in LDS between its additions (VGPR budget)
+      }
+      pos += c;
+      seen += c;
+    }
+  }
+  if (by_class && live && sub == 1) {
+    TAcc t = total[lane];
+#pragma unroll 1
+    for (int d = 0; d < 64; d++) t = t_acc_dbl(t);
+    total[lane] = t;
   }
   __syncthreads();
   if (live && sub == 0) {
@@ -317,7 +347,7 @@ void launch_late_fix(const Fr* d_scal, size_t sstride, const uint32_t* d_cols, i
   else LATE_LAUNCH(k_late_fix<8>, dim3((total + 63) / 64), dim3(64), 0, s, d_scal, sstride, d_cols, n, m, d_fix_tab, nc, d_out, ostride, total);
 }
 void launch_late_uniform(const Fr* d_sm, size_t sstride, const TAff* d_ptab, size_t ptab_proof_stride, int NP, const TAff* d_ctab, int nc, const uint32_t* d_gb_cols, int n,
-                         int m, int nfam, int split, TJac* d_out, size_t fstride, int nproofs, hipStream_t s) {
+                         int m, int nfam, int split, TJac* d_out, size_t fstride, int nproofs, hipStream_t s, int segments) {
   if (nproofs <= 0) return;
   // (late_supported() keeps the engine away from shapes this kernel cannot take; a caller that gets here anyway must not go on with
   // uninitialised folded bases)
@@ -325,9 +355,9 @@ void launch_late_uniform(const Fr* d_sm, size_t sstride, const TAff* d_ptab, siz
   if ((split > 1 && waves > 1) || split < 1 || m <= 0 || n % m || n / m > LU_MAX_T || (n / m) > (1 << 10))
     throw std::invalid_argument("launch_late_uniform: the lanes of a split output must fit one wave and n / m the 16-bit list entries");
   const int nent = 32 * (n / m);
-  const size_t lds = 64 * sizeof(TAcc) + (size_t)((nent + 1) & ~1) * 2 + 2 * 132 * 4;
+  const size_t lds = 64 * sizeof(TAcc) + (size_t)((nent + 1) & ~1) * 2 + 4 * 132 * 4;
   LATE_LAUNCH(k_late_uniform, dim3(nproofs * waves), dim3(64), lds, s, d_sm, sstride, d_ptab, ptab_proof_stride, NP, d_ctab, nc, d_gb_cols, n, m, nfam, split, waves, d_out,
-              fstride);
+              fstride, segments);
 }
 void launch_late_tables(const TJac* d_jac, TAff* d_tab, TblTmp* d_tmp, int npoints, hipStream_t s) {
   if (npoints <= 0) return;

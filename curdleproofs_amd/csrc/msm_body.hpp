@@ -58,7 +58,8 @@ template <class JobFn> __device__ __forceinline__ void quad_exec(TAcc* buf, int 
 }
 
 // ------------------------------------------------------------------ table-backed MSM, barrier-free single-wave groups
-// 32-copy tables: every radix-256 window of a scalar has its own pre-shifted copy 2^(8c) P of the base, so ALL window
+// 32-copy tables (the CRS table, one-segment per-proof tables; the two-segment ones with 8 + 8 copies and two weight classes:
+// msm_tblw2_body below): every radix-256 window of a scalar has its own pre-shifted copy 2^(8c) P of the base, so ALL window
 // sums carry weight 1 and a bucket may collect additions from any window: one (scalar, base) pair costs 32 mixed
 // additions, the 128 bucket magnitudes of the signed digits are the only reduction.  (Radix 16 with 64 copies — the
 // previous layout — paid 60 additions per pair.)
@@ -142,10 +143,14 @@ __device__ __forceinline__ uint32_t tbw_bucket(uint32_t word, int j, uint32_t& n
 // and the same sorted bucket lists — one wave serves both, walking its lists once per task: the fixed cost of a wave (digit load,
 // histogram, ranking, scatter: as much as a dozen additions) is paid once for 16 instead of 8 additions per lane.  Four raw sets
 // per wave: [task 2 t lower | upper | task 2 t + 1 lower | upper].
-template <int WPW, bool PERWIN, bool PAIR = false> __device__ __forceinline__ void msm_tblw_body(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw,
-                                                                                               uint32_t* __restrict__ raw_slot, int slices, const uint32_t bid) {
+// SEGS = 2 (WPW <= 8, every segment of the task a two-segment per-proof table: kernels.h): the wave's windows lie inside one weight
+// class; it reads copy tbl_window(w, 8).copy and its two partial slots go to the class's half of the task's range — the class-1
+// partials come first (k_finalize_ranges doubles their sum 64 times).  Wider waves cover both classes: msm_tblw2_body below.
+template <int WPW, bool PERWIN, bool PAIR = false, int SEGS = 1> __device__ __forceinline__ void msm_tblw_body(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw,
+                                                                                                             uint32_t* __restrict__ raw_slot, int slices, const uint32_t bid) {
   static_assert(!PERWIN || WPW == 2, "one window of each half per wave");
   static_assert(!PAIR || PERWIN, "pairs only for the one-off MSMs");
+  static_assert(SEGS == 1 || (SEGS == 2 && !PERWIN && WPW <= 8), "a two-segment wave of this body stays inside one weight class");
   constexpr int NSETS = PAIR ? 4 : 2;
   constexpr int WV = PERWIN ? 16 : TBW_WINDOWS / WPW;   // waves per task
   // list entry: (point index inside the round << ESH) | (window j << 1) | sign.  PERWIN has j < 2, so 14 bits of point index fit: the
@@ -180,7 +185,11 @@ template <int WPW, bool PERWIN, bool PAIR = false> __device__ __forceinline__ vo
   const uint32_t nall = task.seg[0].n + task.seg[1].n, per = ((nall + slices - 1) / slices + 63) & ~63u;
   const uint32_t first = min(nall, (uint32_t)slice * per), ntot = min(nall, first + per);
   uint32_t* raw0 = raw + (size_t)bid * NSETS * RAW_SET_WORDS;
-  if (lane < NSETS) raw_slot[bid * NSETS + lane] = (lane < 2 ? task.pad : task2.pad) + 2 * (wv * slices + slice) + (lane & 1);   // pad = first partial slot of the task
+  if (SEGS == 2) {   // the task's range: [class 1: 16 / WPW waves x slices | class 0: likewise], two partials per wave
+    constexpr int PER8 = 8 / (WPW <= 8 ? WPW : 8);   // waves per block of 8 windows
+    const int blk = wv / PER8, idx = (blk >> 1) * PER8 + wv % PER8;
+    if (lane < 2) raw_slot[bid * 2 + lane] = task.pad + ((blk & 1) ? 0 : WV * slices) + 2 * (idx * slices + slice) + lane;
+  } else if (lane < NSETS) raw_slot[bid * NSETS + lane] = (lane < 2 ? task.pad : task2.pad) + 2 * (wv * slices + slice) + (lane & 1);   // pad = first partial slot of the task
 
   uint32_t next = first;
   bool later = false;   // a later round: the accumulators are parked in raw0 / raw1
@@ -295,7 +304,8 @@ template <int WPW, bool PERWIN, bool PAIR = false> __device__ __forceinline__ vo
           xacc = later ? raw_load(rb1, b1 & 63) : TAcc::identity();
         }
         const uint32_t e = list[k < c0 ? s0_ + k : s1_ + (k - c0)];
-        const TAff q = *tbl_point(task, next + (e >> ESH), (PERWIN ? 0u : (uint32_t)w0) + ((e >> 1) & EJM));
+        const uint32_t w = (PERWIN ? 0u : (uint32_t)w0) + ((e >> 1) & EJM);
+        const TAff q = *tbl_point(task, next + (e >> ESH), SEGS == 2 ? tbl_window(w, 8).copy : w);
         xacc = t_acc_add_mixed_inl(xacc, t_cneg_lazy(q, (e & 1u) != 0));   // products inlined: no argument moves, 231 VGPRs, no scratch
       }
       if (c1 == 0) {
@@ -346,6 +356,143 @@ template <int WPW, bool PERWIN, bool PAIR = false> __device__ __forceinline__ vo
     later = true;
   } while (next < ntot);
 }
+// ------------------------------------------------------------------ two-segment tables: one wave, both weight classes
+// The per-proof tables of a large batch hold 8 + 8 copies (kernels.h): windows 8..15 of a half read the same copies as windows 0..7 and
+// their sums carry the weight 2^64.  A wave of 16 or 32 windows serves both classes: ONE histogram over 256 bins (class x magnitude),
+// the bins ranked by size, lane l walks the lists of rank l, 127 - l, 128 + l and 255 - l (longest with shortest, twice) in one loop
+// and parks the accumulator at every boundary.  Four raw sets per wave — bin b lives in set b / 64: [class 0 lower | upper | class 1
+// lower | upper] — and four partial slots: the task's range is [class 1: two per wave | class 0: two per wave].  The list offsets are
+// not kept beside the cursors (after the scatter cur[b] - cnt[b] is where list b starts): 19 712 B of LDS, two waves per SIMD.
+constexpr int TBW2_BINS = 256;
+constexpr int TBW2_LDS = TBW_CAP * 2 + 2 * TBW2_BINS * 4 + TBW2_BINS;
+static_assert(TBW_LDS <= 20480 && TBW2_LDS <= 20480, "eight single-wave groups per CU share 160 KiB of LDS");
+template <int WPW> __device__ __forceinline__ void msm_tblw2_body(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw, uint32_t* __restrict__ raw_slot,
+                                                                  int slices, const uint32_t bid) {
+  static_assert(WPW == 16 || WPW == 32, "both classes of a half in one wave");
+  constexpr int WV = TBW_WINDOWS / WPW, NW = WPW / 4, NSEG = 4;
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint16_t* list = reinterpret_cast<uint16_t*>(smem);                 // [TBW_CAP]
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + TBW_CAP * 2);    // [256] bin sizes of the round
+  uint32_t* cur = cnt + TBW2_BINS;                                    // [256] scatter cursors
+  uint8_t* order = reinterpret_cast<uint8_t*>(cur + TBW2_BINS);       // [256] bins by size
+  const TblTask task = tasks[bid / (WV * slices)];
+  const int wv = (bid / slices) % WV, w0 = wv * WPW, slice = bid % slices;
+  const int lane = threadIdx.x;
+  const uint32_t nall = task.seg[0].n + task.seg[1].n, per = ((nall + slices - 1) / slices + 63) & ~63u;
+  const uint32_t first = min(nall, (uint32_t)slice * per), ntot = min(nall, first + per);
+  uint32_t* raw0 = raw + (size_t)bid * NSEG * RAW_SET_WORDS;
+  if (lane < NSEG) raw_slot[bid * NSEG + lane] = task.pad + ((lane >> 1) ? 0 : 2 * WV * slices) + 2 * (wv * slices + slice) + (lane & 1);
+  // bin of window j's digit: class (w0 is a multiple of 16, so the class is bit 3 of j) x magnitude, or >= 256 for a zero digit
+  auto bin_of = [](uint32_t word, int j, uint32_t& neg) {
+    const uint32_t b = tbw_bucket(word, j, neg);
+    return b < 128u ? b + 128u * (uint32_t)((j >> 3) & 1) : 256u;
+  };
+
+  uint32_t next = first;
+  bool later = false;   // a later round: the accumulators are parked in the raw sets
+  do {
+    CPX_UNROLL for (int k = 0; k < 4; k++) cnt[64 * k + lane] = 0;
+    __syncthreads();
+    uint32_t total = 0, end = next;
+    while (end < ntot && end - next + 64 <= (uint32_t)TBW_ROUND_PTS) {
+      const uint32_t i = end + lane;
+      uint32_t dg[NW], sg_lo, sg_hi;
+      int mine = 0;
+      if (i < ntot) {
+        tbw_digits<WPW, false>(task, i, w0, dg, sg_lo, sg_hi);
+        CPX_UNROLL for (int j = 0; j < WPW; j++) {
+          uint32_t neg;
+          mine += tbw_bucket(dg[j >> 2], j, neg) < 128u ? 1 : 0;
+        }
+      }
+      int ct = mine;
+      CPX_UNROLL for (int m = 32; m >= 1; m >>= 1) ct += __shfl_xor(ct, m, 64);
+      if (total && total + (uint32_t)ct > (uint32_t)TBW_CAP) break;
+      if (i < ntot) {
+        CPX_UNROLL for (int j = 0; j < WPW; j++) {
+          uint32_t neg;
+          const uint32_t b = bin_of(dg[j >> 2], j, neg);
+          if (b < 256u) atomicAdd(&cnt[b], 1u);
+        }
+      }
+      total += (uint32_t)ct;
+      end = min(end + 64, ntot);
+    }
+    __syncthreads();
+    // list offsets (lane l scans bins 4 l .. 4 l + 3) and the rank of every bin by size
+    {
+      uint32_t a[4], sum = 0;
+      CPX_UNROLL for (int k = 0; k < 4; k++) {
+        a[k] = cnt[4 * lane + k];
+        sum += a[k];
+      }
+      uint32_t incl = sum;
+      CPX_UNROLL for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)incl, d, 64);
+        if (lane >= d) incl += y;
+      }
+      uint32_t o = incl - sum;
+      CPX_UNROLL for (int k = 0; k < 4; k++) {
+        cur[4 * lane + k] = o;
+        o += a[k];
+      }
+      uint32_t r[4] = {0, 0, 0, 0};
+      for (int q = 0; q < TBW2_BINS; q++) {
+        const uint32_t c = cnt[q];
+        CPX_UNROLL for (int k = 0; k < 4; k++) r[k] += (c < a[k] || (c == a[k] && q < 4 * lane + k)) ? 1u : 0u;
+      }
+      CPX_UNROLL for (int k = 0; k < 4; k++) order[r[k]] = (uint8_t)(4 * lane + k);
+    }
+    __syncthreads();
+    for (uint32_t s0 = next; s0 < end; s0 += 64) {
+      const uint32_t i = s0 + lane;
+      if (i < end) {
+        uint32_t dg[NW], sg_lo, sg_hi;
+        tbw_digits<WPW, false>(task, i, w0, dg, sg_lo, sg_hi);
+        CPX_UNROLL for (int j = 0; j < WPW; j++) {
+          uint32_t neg;
+          const uint32_t b = bin_of(dg[j >> 2], j, neg);
+          neg ^= (w0 + j < 16) ? sg_lo : sg_hi;
+          if (b < 256u) list[atomicAdd(&cur[b], 1u)] = (uint16_t)(((i - next) << 6) | ((uint32_t)j << 1) | neg);
+        }
+      }
+    }
+    __syncthreads();
+    // ONE loop over the lane's four lists (as the pairs of msm_tblw_body walk theirs): a list that ends parks its accumulator by bin
+    // index and loads (or zeroes) the next one
+    auto seg_bin = [&](int sg) { return (uint32_t)order[sg == 0 ? lane : sg == 1 ? 127 - lane : sg == 2 ? 128 + lane : 255 - lane]; };
+    uint32_t nwalk = 0;
+    CPX_UNROLL for (int sg = 0; sg < NSEG; sg++) nwalk += cnt[seg_bin(sg)];
+    int sg = 0;
+    uint32_t bk = seg_bin(0), cs = cnt[bk], st = cur[bk] - cs, kin = 0;
+    uint32_t* rb = raw0 + (bk >> 6) * RAW_SET_WORDS;
+    TAcc xacc = later ? raw_load(rb, bk & 63) : TAcc::identity();
+    auto next_segment = [&]() {
+      raw_store(rb, bk & 63, xacc);
+      sg++;
+      bk = seg_bin(sg);
+      cs = cnt[bk];
+      st = cur[bk] - cs;
+      kin = 0;
+      rb = raw0 + (bk >> 6) * RAW_SET_WORDS;
+      xacc = later ? raw_load(rb, bk & 63) : TAcc::identity();
+    };
+#pragma unroll 1
+    for (uint32_t k = 0; k < nwalk; k++) {
+      while (kin == cs) next_segment();   // (sg stays below NSEG: entries remain)
+      const uint32_t e = list[st + kin];
+      const TAff q = *tbl_point(task, next + (e >> 6), tbl_window((uint32_t)w0 + ((e >> 1) & 31u), 8).copy);
+      xacc = t_acc_add_mixed_inl(xacc, t_cneg_lazy(q, (e & 1u) != 0));
+      kin++;
+    }
+    while (sg + 1 < NSEG) next_segment();   // the lists that were empty or remain: every bin of the round is written
+    raw_store(rb, bk & 63, xacc);
+    __syncthreads();
+    next = end;
+    later = true;
+  } while (next < ntot);
+}
+
 // ------------------------------------------------------------------ fixed-base MSM over multiples tables
 constexpr int FIX_CHUNK = 256;
 

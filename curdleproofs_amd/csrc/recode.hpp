@@ -104,6 +104,18 @@ template <int CB, int NW, class DT> CPX_HD void fix_window_digits(const uint32_t
   }
 }
 
+// ---- shifted tables (k_msm_tblw, k_late_uniform): which copy a radix-256 window reads and which weight its sum carries ----
+// Windows 0..15 are the digits of |t|, 16..31 those of q (glv.hpp).  A table with `real` shifted copies per half (16: one per
+// window; 8: the two-segment layout of the per-proof tables, kernels.h) holds 2^(8c) P for c < real followed by the `real`
+// endomorphism images: window w reads copy (w mod real) of its half, and its sum carries the weight 2^(8 real cls), cls = (w mod 16) / real.
+struct TblWindow {
+  uint32_t copy, cls;
+};
+CPX_HD TblWindow tbl_window(uint32_t w, uint32_t real) {
+  const uint32_t v = w & 15u;
+  return TblWindow{(v & (real - 1u)) + (w >= 16u ? real : 0u), v / real};
+}
+
 // ---- late rounds (k_late_msm): signed radix-16 digits in [-7, 8] of a value v < 2^127 (an endomorphism half), biased by 7 and
 // packed eight per word: v = sum_j (nibble_j - 7) 16^j, j < 32; no carry leaves nibble 31 ----
 CPX_HD void recode_signed_nibbles_biased(const uint32_t* v /*4*/, uint32_t* packed /*4*/) {

@@ -37,6 +37,7 @@ struct TblShape {
   uint32_t tbl_max_n = 0;            // points of the largest task of k_msm_tblw
   size_t nparts = 0, fix_sets = 0, tbl_sets = 0;   // partial sums; raw sets [fixed-base waves | bucket sets of the table waves]
   int fix_wpw = 16, tbl_wpw = 32, tbl_slices = 1;
+  int tbl_segments = 1;      // 2: the table tasks read two-segment per-proof tables (kernels.h) and leave their weight-2^64 partials first
   double pts_fix = 0, pts_tbl = 0;
   bool any_add = false;
   bool has_comp = false;     // the per-request arrays carry a compressed-bytes slot
@@ -65,8 +66,10 @@ inline void tbl_count(const std::vector<TblReq>& reqs, const CrsRange& crs, TblS
 // tbl_parts followed by fix_parts per fixed-base task.  The scalars of a request are at TblReq::dev or, without one, at
 // scal + soff[i] of the blob the caller uploads (soff: optional, nt offsets in Fr units, seg0 then seg1 per request).  Requests
 // without a destination scatter to dummy_dst; comp_index (optional): the compressed-bytes slot of every request.
+// tbl_hi (two-segment per-proof tables, kernels.h): how many of a table task's tbl_parts, the first ones, carry the weight 2^64 — recorded
+// in the upper 16 bits of the request's partial count.
 inline void tbl_plan(const std::vector<TblReq>& reqs, const CrsRange& crs, uint32_t fix_parts, uint32_t tbl_parts, uint32_t dummy_dst, const Fr* scal,
-                     const uint32_t* comp_index, TblShape& sh, TblTask* tt, FixTask* ft, uint32_t* meta, size_t* soff = nullptr) {
+                     const uint32_t* comp_index, TblShape& sh, TblTask* tt, FixTask* ft, uint32_t* meta, size_t* soff = nullptr, uint32_t tbl_hi = 0) {
   const size_t nt = reqs.size();
   const TblSeg none{nullptr, nullptr, 0, 0};
   sh.has_comp = comp_index != nullptr;
@@ -80,7 +83,9 @@ inline void tbl_plan(const std::vector<TblReq>& reqs, const CrsRange& crs, uint3
     if (!r.dev) off += r.seg0.n + r.seg1.n;
     const bool f0 = crs.is_crs(r.seg0), f1 = crs.is_crs(r.seg1);
     const uint32_t first = (uint32_t)nparts;
+    uint32_t hi = 0;
     if (crs.needs_tbl(r)) {
+      hi = tbl_hi;
       TblTask t;
       t.seg[0] = r.seg0;
       t.seg[1] = f1 ? none : r.seg1;
@@ -105,7 +110,7 @@ inline void tbl_plan(const std::vector<TblReq>& reqs, const CrsRange& crs, uint3
       nparts += fix_parts;
     }
     meta[i] = first;
-    meta[nt + i] = (uint32_t)nparts - first;
+    meta[nt + i] = ((uint32_t)nparts - first) | (hi << 16);
     meta[2 * nt + i] = r.dst != ~0u ? r.dst : dummy_dst;
     if (comp_index) meta[3 * nt + i] = comp_index[i];
     for (int j = 0; j < 3; j++) meta[sh.add_offset() + 3 * i + j] = r.add[j];
