@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "engine.hpp"
+#include "recode.hpp"
 
 namespace cpx {
 
@@ -36,7 +37,7 @@ void Engine::build_plan(TblPlan& pl, const std::vector<TblReq>& reqs, const std:
   pl.tbl_segments = pcopies_ == copies_ ? 1 : 2;
   const uint32_t tbl_parts = (uint32_t)msm_tblw_parts(pl.tbl_wpw, pl.tbl_segments);
   tbl_plan(reqs, crs, (uint32_t)msm_fix_parts(fix_bits_, pl.fix_wpw), tbl_parts, dummy_dst, nullptr, comp_index.data(), pl, ht.data(), hf.data(), meta.data(), nullptr,
-           pl.tbl_segments == 2 ? tbl_parts / 2 : 0);
+           tbw_parts_hi((uint32_t)pl.tbl_wpw, (uint32_t)pl.tbl_segments));   // (one slice: the class-1 partials of a task, which come first)
   if (pl.tbl_segments == 2)
     for (const TblTask& t : ht)
       for (const TblSeg& sg : t.seg)

@@ -131,8 +131,7 @@ struct TblTmp {   // table-build scratch: a Jacobian copy and the running produc
 // single-wave work-groups owning wpw (2 .. 32) windows each: 32 / wpw waves per task, two raw sets per wave
 // -> partial sums d_part[task.pad + j], j < 64 / wpw
 int msm_tblw_windows_per_wave(const Options& o, int ntasks);
-int msm_tblw_parts(int wpw);   // waves (= partial sums) per task
-int msm_tblw_parts(int wpw, int segments);   // two-segment tables: waves of 16 / 32 windows leave four sets; the first half of a task's partials carries the weight 2^64
+int msm_tblw_parts(int wpw, int segments = 1);   // partial sums (= raw sets of its waves) per task, recode.hpp tbw_parts; two-segment tables: waves of 16 / 32 windows leave four sets, the first half of a task's partials carries the weight 2^64
 // slices > 1 (a few tasks in flight): that many waves share a task's points; a task then leaves slices * msm_tblw_parts(wpw) partial sums
 int msm_tblw_slices(const Options& o, int ntasks, int wpw, int max_n);   // max_n: points of the largest task
 void launch_msm_tblw(const TblTask* d_tasks, int ntasks, int wpw, uint32_t* d_raw, uint32_t* d_raw_slot, hipStream_t s, int slices = 1, int segments = 1);

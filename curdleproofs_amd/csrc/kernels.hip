@@ -279,12 +279,11 @@ template <int WPW, bool PERWIN = false> __global__ __launch_bounds__(64, 2) void
   msm_tblw_body<WPW, PERWIN>(tasks, raw, raw_slot, slices, blockIdx.x);
 }
 
-// Two-segment per-proof tables (kernels.h): a wave of 16 or 32 windows serves both weight classes (msm_tblw2_body: four raw sets), a
-// narrower one lies inside one class.
+// Two-segment per-proof tables (kernels.h): a wave of 16 or 32 windows serves both weight classes (four raw sets), a narrower one lies
+// inside one class.
 template <int WPW> __global__ __launch_bounds__(64, 2) void k_msm_tblw2(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw, uint32_t* __restrict__ raw_slot,
                                                                         int slices) {
-  if constexpr (WPW >= 16) msm_tblw2_body<WPW>(tasks, raw, raw_slot, slices, blockIdx.x);
-  else msm_tblw_body<WPW, false, false, 2>(tasks, raw, raw_slot, slices, blockIdx.x);
+  msm_tblw_body<WPW, false, false, 2>(tasks, raw, raw_slot, slices, blockIdx.x);
 }
 
 __global__ __launch_bounds__(64, 2) void k_msm_tblw_pair(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw, uint32_t* __restrict__ raw_slot) {
@@ -1410,7 +1409,7 @@ int msm_tblw_windows_per_wave(const Options& o, int ntasks) {
   if ((long)ntasks * 8 <= lat_waves) return 4;
   return 8;
 }
-int msm_tblw_parts(int wpw) { return 64 / wpw; }
+int msm_tblw_parts(int wpw, int segments) { return (int)tbw_parts((uint32_t)wpw, (uint32_t)segments); }   // recode.hpp, shared with the waves
 int msm_tblw_slices(const Options& o, int ntasks, int wpw, int max_n) {
   // waves per task over its points: only when the GPU would otherwise stand almost empty (a lone proof: 16 waves per task) and a
   // slice keeps >= 256 points — below that the longest of a wave's 128 bucket lists no longer shrinks with the slice (a lane adds
@@ -1422,7 +1421,6 @@ int msm_tblw_slices(const Options& o, int ntasks, int wpw, int max_n) {
   while (s > 1 && max_n / s < 256) s >>= 1;
   return s;
 }
-int msm_tblw_parts(int wpw, int segments) { return segments == 2 && wpw >= 16 ? 128 / wpw : 64 / wpw; }
 void launch_msm_tblw(const TblTask* d_tasks, int ntasks, int wpw, uint32_t* d_raw, uint32_t* d_raw_slot, hipStream_t s, int slices, int segments) {
   if (ntasks <= 0) return;
   const dim3 grid(ntasks * (TBW_WINDOWS / wpw) * slices), block(64);

@@ -1,6 +1,6 @@
 // The MSM wave bodies of the gfx950 kernels and what they share with the in-wave reductions — device code included by kernels.hip (the
 // stand-alone MSM / reduction kernels) and round.hip (the fused log-round kernels: MSM waves that reduce their own accumulators and
-// whose last arriver runs the round's finalisation, transcript step and Fr folds).  Moved out of kernels.hip unchanged.
+// whose last arriver runs the round's finalisation, transcript step and Fr folds).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "g1.hpp"
@@ -58,13 +58,13 @@ template <class JobFn> __device__ __forceinline__ void quad_exec(TAcc* buf, int 
 }
 
 // ------------------------------------------------------------------ table-backed MSM, barrier-free single-wave groups
-// 32-copy tables (the CRS table, one-segment per-proof tables; the two-segment ones with 8 + 8 copies and two weight classes:
-// msm_tblw2_body below): every radix-256 window of a scalar has its own pre-shifted copy 2^(8c) P of the base, so ALL window
+// 32-copy tables (the CRS table, one-segment per-proof tables; the two-segment ones with 8 + 8 copies and two weight classes
+// further down): every radix-256 window of a scalar has its own pre-shifted copy 2^(8c) P of the base, so ALL window
 // sums carry weight 1 and a bucket may collect additions from any window: one (scalar, base) pair costs 32 mixed
 // additions, the 128 bucket magnitudes of the signed digits are the only reduction.  (Radix 16 with 64 copies — the
 // previous layout — paid 60 additions per pair.)
 // A single-wave work-group owns WPW consecutive windows of one task and all 128 buckets, two per lane.  With a hit
-// rate of 1/128 per (window, point) pair a lane cannot scan for its digits; the wave sorts instead: every lane recodes
+// rate of 1/128 per (window, point) pair a lane cannot scan for its digits; the wave sorts instead (tbw_sort): every lane recodes
 // one scalar of a 64-point slab, a histogram over the 128 magnitudes (LDS atomics) gives the list offsets, a second
 // pass scatters 16-bit (point, window, sign) entries into per-bucket lists in LDS.  The buckets are then ranked by
 // size and lane l takes rank l and rank 127 - l (longest with shortest): the lanes' totals differ by a few additions
@@ -79,9 +79,26 @@ constexpr int TBW_CAP = 8704;         // list entries per round
 constexpr int TBW_ROUND_PTS = 1024;   // a list entry holds a 10-bit point index beside a 5-bit window and the sign ...
 constexpr int TBW_ROUND_PTS_PERWIN = 4096;   // ... or, with one window per scalar half (PERWIN), a 14-bit one: a round takes TBW_CAP / 2 points
 static_assert(2 * TBW_ROUND_PTS_PERWIN <= TBW_CAP, "two entries per point of a PERWIN round");
-constexpr int TBW_LDS = TBW_CAP * 2 + 3 * 128 * 4 + 128;
-constexpr int TBW_LDS_CACHE = TBW_LDS + TBW_ROUND_PTS * 4;   // k_msm_tblw<2, false> keeps a round's recoded digits (below)
 static_assert(TBW_CAP >= 64 * TBW_WINDOWS, "one slab always fits");
+
+// The LDS of a wave's sort over NBINS bins: 128 (the bucket magnitudes) or 256 (weight class x magnitude, the two-segment tables below).
+// The list offsets are not kept beside the cursors: after the scatter list b is [cur[b] - cnt[b], cur[b]).
+template <int NBINS> struct TbwSort {
+  static constexpr int LDS = TBW_CAP * 2 + 2 * NBINS * 4 + NBINS;
+  uint16_t* list;     // [TBW_CAP]
+  uint32_t* cnt;      // [NBINS] bin sizes of the round
+  uint32_t* cur;      // [NBINS] scatter cursors
+  uint8_t* order;     // [NBINS] bins by size
+  uint32_t* dcache;   // [TBW_ROUND_PTS] a round's recoded digits, CACHE only
+  __device__ __forceinline__ explicit TbwSort(uint8_t* smem)
+      : list(reinterpret_cast<uint16_t*>(smem)), cnt(reinterpret_cast<uint32_t*>(smem + TBW_CAP * 2)), cur(cnt + NBINS),
+        order(reinterpret_cast<uint8_t*>(cur + NBINS)), dcache(reinterpret_cast<uint32_t*>(smem + LDS)) {}
+  __device__ __forceinline__ uint32_t start(uint32_t b) const { return cur[b] - cnt[b]; }
+};
+constexpr int TBW_LDS = TbwSort<128>::LDS;                   // 18 560 B
+constexpr int TBW_LDS_CACHE = TBW_LDS + TBW_ROUND_PTS * 4;   // k_msm_tblw<2, false> keeps a round's recoded digits (tbw_sort)
+constexpr int TBW2_LDS = TbwSort<256>::LDS;                  // 19 712 B
+static_assert(TBW_LDS <= 20480 && TBW2_LDS <= 20480, "eight single-wave groups per CU share 160 KiB of LDS");
 
 __device__ __forceinline__ const TAff* tbl_point(const TblTask& t, uint32_t g, uint32_t copy) {
   const uint32_t n0 = t.seg[0].n;
@@ -135,6 +152,153 @@ __device__ __forceinline__ uint32_t tbw_bucket(uint32_t word, int j, uint32_t& n
   neg = d < 0 ? 1u : 0u;
   return (uint32_t)((d < 0 ? -d : d) - 1);   // digit 0 -> 0xffffffff
 }
+// bin of window j's digit, or >= NBINS for a zero digit: the bucket, or with 256 bins weight class x bucket (a wave of both classes
+// starts at a multiple of 16 windows, so the class of window w0 + j is bit 3 of j)
+template <int NBINS> __device__ __forceinline__ uint32_t tbw_bin(uint32_t word, int j, uint32_t& neg) {
+  const uint32_t b = tbw_bucket(word, j, neg);
+  if constexpr (NBINS == 128) return b;
+  else return b < 128u ? b + 128u * (uint32_t)((j >> 3) & 1) : (uint32_t)NBINS;
+}
+// list entry: (point index inside the round << ESH) | (window j << 1) | sign.  PERWIN has j < 2, so 14 bits of point index fit: the
+// verifier's 1112 points per proof are ONE round instead of 1024 + 88 (the short second round cost a tenth of the kernel: its lists of
+// 0 - 6 entries wait for the longest, and the histogram, ranking and parking are paid again)
+template <bool PERWIN> struct TbwEntry {
+  static constexpr int ESH = PERWIN ? 2 : 6;
+  static constexpr uint32_t EJM = PERWIN ? 1u : 31u;
+  static constexpr uint32_t ROUND_PTS = PERWIN ? (uint32_t)TBW_ROUND_PTS_PERWIN : (uint32_t)TBW_ROUND_PTS;
+};
+
+// The sort of one round, by the whole wave: the points [next, end) of the task — as many 64-point slabs from `next` on as fit the
+// list — with their digits of windows [w0, w0 + WPW) sorted into the NBINS lists of ts.  On return (behind a barrier) cnt[b] is the
+// size of list b, ts.start(b) its offset, and order[] holds the bins by size.  Returns end.
+// CACHE (the latency form: two windows per wave, a lone proof): the split + recoding of a scalar (~700 instructions) is done in the
+// histogram pass and kept for the scatter pass (one word per point); the other forms recompute it (2 x per 4-32 windows: < 1 %
+// of their additions, and 4 KB more LDS per wave would cost them the second wave per SIMD).
+template <int WPW, bool PERWIN, int NBINS, bool CACHE>
+__device__ __forceinline__ uint32_t tbw_sort(const TbwSort<NBINS>& ts, const TblTask& task, int w0, uint32_t next, uint32_t ntot) {
+  constexpr int NW = (WPW + 3) / 4, K = NBINS / 64;   // K bins per lane
+  typedef TbwEntry<PERWIN> E;
+  const int lane = threadIdx.x;
+  CPX_UNROLL for (int k = 0; k < K; k++) ts.cnt[64 * k + lane] = 0;
+  __syncthreads();
+  // histogram over as many 64-point slabs as fit the list
+  uint32_t total = 0, end = next;
+  while (end < ntot && end - next + 64 <= E::ROUND_PTS) {
+    const uint32_t i = end + lane;
+    uint32_t dg[NW], sg_lo, sg_hi;
+    int mine = 0;
+    if (i < ntot) {
+      tbw_digits<WPW, PERWIN>(task, i, w0, dg, sg_lo, sg_hi);
+      if (CACHE) ts.dcache[i - next] = (dg[0] & 0xffffu) | (sg_lo << 16) | (sg_hi << 17);
+      CPX_UNROLL for (int j = 0; j < WPW; j++) {
+        uint32_t neg;
+        mine += tbw_bucket(dg[j >> 2], j, neg) < 128u ? 1 : 0;
+      }
+    }
+    int ct = mine;
+    CPX_UNROLL for (int m = 32; m >= 1; m >>= 1) ct += __shfl_xor(ct, m, 64);
+    if (total && total + (uint32_t)ct > (uint32_t)TBW_CAP) break;
+    if (i < ntot) {
+      CPX_UNROLL for (int j = 0; j < WPW; j++) {
+        uint32_t neg;
+        const uint32_t b = tbw_bin<NBINS>(dg[j >> 2], j, neg);
+        if (b < (uint32_t)NBINS) atomicAdd(&ts.cnt[b], 1u);
+      }
+    }
+    total += (uint32_t)ct;
+    end = min(end + 64, ntot);
+  }
+  __syncthreads();
+  // list offsets: exclusive scan of the bin sizes over the wave (lane l scans bins K l .. K l + K - 1)
+  {
+    uint32_t a[K], sum = 0;
+    CPX_UNROLL for (int k = 0; k < K; k++) {
+      a[k] = ts.cnt[K * lane + k];
+      sum += a[k];
+    }
+    uint32_t incl = sum;
+    CPX_UNROLL for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t y = (uint32_t)__shfl_up((int)incl, d, 64);
+      if (lane >= d) incl += y;
+    }
+    uint32_t o = incl - sum;
+    CPX_UNROLL for (int k = 0; k < K; k++) {
+      ts.cur[K * lane + k] = o;
+      o += a[k];
+    }
+    // the bins ranked by size: a lane adds up rank l and rank 127 - l of them (longest with shortest), so the lanes' totals differ
+    // by a few additions instead of +-30 %
+    uint32_t r[K];
+    CPX_UNROLL for (int k = 0; k < K; k++) r[k] = 0;
+    for (int q = 0; q < NBINS; q++) {
+      const uint32_t c = ts.cnt[q];
+      CPX_UNROLL for (int k = 0; k < K; k++) r[k] += (c < a[k] || (c == a[k] && q < K * lane + k)) ? 1u : 0u;
+    }
+    CPX_UNROLL for (int k = 0; k < K; k++) ts.order[r[k]] = (uint8_t)(K * lane + k);
+  }
+  __syncthreads();
+  for (uint32_t s0 = next; s0 < end; s0 += 64) {
+    const uint32_t i = s0 + lane;
+    if (i < end) {
+      uint32_t dg[NW], sg_lo, sg_hi;
+      if (CACHE) {
+        const uint32_t v = ts.dcache[i - next];
+        dg[0] = v & 0xffffu;
+        sg_lo = (v >> 16) & 1u;
+        sg_hi = (v >> 17) & 1u;
+      } else {
+        tbw_digits<WPW, PERWIN>(task, i, w0, dg, sg_lo, sg_hi);
+      }
+      CPX_UNROLL for (int j = 0; j < WPW; j++) {
+        uint32_t neg;
+        const uint32_t b = tbw_bin<NBINS>(dg[j >> 2], j, neg);
+        neg ^= (PERWIN ? j == 0 : w0 + j < 16) ? sg_lo : sg_hi;
+        if (b < (uint32_t)NBINS) ts.list[atomicAdd(&ts.cur[b], 1u)] = (uint16_t)(((i - next) << E::ESH) | ((uint32_t)j << 1) | neg);
+      }
+    }
+  }
+  __syncthreads();
+  return end;
+}
+
+// ONE loop over the lane's NSEG lists: a wave runs a loop until its slowest lane is through, so only inside one loop do a lane's long
+// and short lists add up (two loops, one per task of a pair, each waited for the longest pair of buckets of the wave, whoever walked
+// it; the same loop in the one-task kernels measured 0.4 % slower than the two-list loop of msm_tblw_body).  Segment sg walks list
+// bin(sg) into the accumulator at position bin % 64 of raw set set(sg, bin), reading the point src(sg, entry) for every entry; a
+// segment that ends parks its accumulator and loads (or, in the first round of a task, zeroes) the next one.
+template <int NSEG, int NBINS, class BinFn, class SetFn, class SrcFn>
+__device__ __forceinline__ void tbw_walk_lists(const TbwSort<NBINS>& ts, uint32_t* __restrict__ raw0, bool later, BinFn bin, SetFn set, SrcFn src) {
+  uint32_t nwalk = 0;   // entries of all the lane's lists
+  CPX_UNROLL for (int s = 0; s < NSEG; s++) nwalk += ts.cnt[bin(s)];
+  int sg = 0;
+  uint32_t bk, cs, st, kin;
+  uint32_t* rb;
+  TAcc xacc;
+  auto enter = [&]() {
+    bk = bin(sg);
+    cs = ts.cnt[bk];
+    st = ts.start(bk);
+    kin = 0;
+    rb = raw0 + set(sg, bk) * RAW_SET_WORDS;
+    xacc = later ? raw_load(rb, bk & 63) : TAcc::identity();
+  };
+  auto next_segment = [&]() {
+    raw_store(rb, bk & 63, xacc);
+    sg++;
+    enter();
+  };
+  enter();
+#pragma unroll 1
+  for (uint32_t k = 0; k < nwalk; k++) {
+    while (kin == cs) next_segment();   // (sg stays below NSEG: entries remain)
+    const uint32_t e = ts.list[st + kin];
+    const TAff q = *src(sg, e);
+    xacc = t_acc_add_mixed_inl(xacc, t_cneg_lazy(q, (e & 1u) != 0));   // products inlined: no argument moves, no scratch
+    kin++;
+  }
+  while (sg + 1 < NSEG) next_segment();   // the lists that were empty or remain: every bin of the round is written
+  raw_store(rb, bk & 63, xacc);
+}
 
 // PERWIN (k_msm_tblw<2, true>): the same wave over bases WITHOUT shifted copies (the verifier's per-proof points, used once):
 // the "table" has two copies, P and -phi(P) (k_to_table_endo), wave w of a task takes digit w of |t| and of q, and the
@@ -143,34 +307,24 @@ __device__ __forceinline__ uint32_t tbw_bucket(uint32_t word, int j, uint32_t& n
 // and the same sorted bucket lists — one wave serves both, walking its lists once per task: the fixed cost of a wave (digit load,
 // histogram, ranking, scatter: as much as a dozen additions) is paid once for 16 instead of 8 additions per lane.  Four raw sets
 // per wave: [task 2 t lower | upper | task 2 t + 1 lower | upper].
-// SEGS = 2 (WPW <= 8, every segment of the task a two-segment per-proof table: kernels.h): the wave's windows lie inside one weight
-// class; it reads copy tbl_window(w, 8).copy and its two partial slots go to the class's half of the task's range — the class-1
-// partials come first (k_finalize_ranges doubles their sum 64 times).  Wider waves cover both classes: msm_tblw2_body below.
+// SEGS = 2 (every segment of the task a two-segment per-proof table: kernels.h): the tables hold 8 + 8 copies, windows 8..15 of a half
+// read the same copies as windows 0..7 (tbl_window(w, 8).copy) and their sums carry the weight 2^64.  A wave of up to 8 windows lies
+// inside one weight class and differs from the one-segment wave only in the copy it reads and in its partial slots.  A wave of 16 or 32
+// windows serves BOTH classes: ONE histogram over 256 bins (class x magnitude), the bins ranked by size, lane l walks the lists of rank
+// l, 127 - l, 128 + l and 255 - l (longest with shortest, twice) in one loop.  Four raw sets per wave — bin b lives in set b / 64:
+// [class 0 lower | upper | class 1 lower | upper].  The partial slots of either (recode.hpp tbw_part_slot): class 1 first.
 template <int WPW, bool PERWIN, bool PAIR = false, int SEGS = 1> __device__ __forceinline__ void msm_tblw_body(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw,
                                                                                                              uint32_t* __restrict__ raw_slot, int slices, const uint32_t bid) {
   static_assert(!PERWIN || WPW == 2, "one window of each half per wave");
   static_assert(!PAIR || PERWIN, "pairs only for the one-off MSMs");
-  static_assert(SEGS == 1 || (SEGS == 2 && !PERWIN && WPW <= 8), "a two-segment wave of this body stays inside one weight class");
-  constexpr int NSETS = PAIR ? 4 : 2;
+  static_assert(SEGS == 1 || (SEGS == 2 && !PERWIN), "two-segment tables have shifted copies");
+  constexpr bool BOTH = SEGS == 2 && WPW >= 16;   // both weight classes in one wave
+  constexpr int NBINS = BOTH ? 256 : 128;
+  constexpr int NSETS = (PAIR || BOTH) ? 4 : 2;
   constexpr int WV = PERWIN ? 16 : TBW_WINDOWS / WPW;   // waves per task
-  // list entry: (point index inside the round << ESH) | (window j << 1) | sign.  PERWIN has j < 2, so 14 bits of point index fit: the
-  // verifier's 1112 points per proof are ONE round instead of 1024 + 88 (the short second round cost a tenth of the kernel: its lists of
-  // 0 - 6 entries wait for the longest, and the histogram, ranking and parking are paid again)
-  constexpr int ESH = PERWIN ? 2 : 6;
-  constexpr uint32_t EJM = PERWIN ? 1u : 31u;
-  constexpr uint32_t ROUND_PTS = PERWIN ? (uint32_t)TBW_ROUND_PTS_PERWIN : (uint32_t)TBW_ROUND_PTS;
-  constexpr int NW = (WPW + 3) / 4;
+  typedef TbwEntry<PERWIN> E;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint16_t* list = reinterpret_cast<uint16_t*>(smem);                 // [TBW_CAP]
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + TBW_CAP * 2);    // [128] bucket sizes of the round
-  uint32_t* cur = cnt + 128;                                          // [128] scatter cursors
-  uint32_t* start = cur + 128;                                        // [128] list offsets
-  uint8_t* order = reinterpret_cast<uint8_t*>(start + 128);           // [128] buckets by size
-  // the latency form (two windows per wave, a lone proof): the split + recoding of a scalar (~700 instructions) is done in the
-  // histogram pass and kept for the scatter pass (one word per point); the other forms recompute it (2 x per 4-32 windows: < 1 %
-  // of their additions, and 4 KB more LDS per wave would cost them the second wave per SIMD)
-  constexpr bool CACHE = WPW == 2 && !PERWIN;
-  uint32_t* dcache = reinterpret_cast<uint32_t*>(smem + TBW_LDS);      // [TBW_ROUND_PTS], CACHE only
+  const TbwSort<NBINS> ts(smem);
   // a few tasks in flight (latency matters): `slices` waves share a task's points (each its own 64-aligned range and raw sets), so
   // that a lane's chain of additions is a quarter as long; slices = 1 otherwise
   const uint32_t tidx = (PAIR ? 2u : 1u) * (bid / (WV * slices));
@@ -185,115 +339,49 @@ template <int WPW, bool PERWIN, bool PAIR = false, int SEGS = 1> __device__ __fo
   const uint32_t nall = task.seg[0].n + task.seg[1].n, per = ((nall + slices - 1) / slices + 63) & ~63u;
   const uint32_t first = min(nall, (uint32_t)slice * per), ntot = min(nall, first + per);
   uint32_t* raw0 = raw + (size_t)bid * NSETS * RAW_SET_WORDS;
-  if (SEGS == 2) {   // the task's range: [class 1: 16 / WPW waves x slices | class 0: likewise], two partials per wave
-    constexpr int PER8 = 8 / (WPW <= 8 ? WPW : 8);   // waves per block of 8 windows
-    const int blk = wv / PER8, idx = (blk >> 1) * PER8 + wv % PER8;
-    if (lane < 2) raw_slot[bid * 2 + lane] = task.pad + ((blk & 1) ? 0 : WV * slices) + 2 * (idx * slices + slice) + lane;
-  } else if (lane < NSETS) raw_slot[bid * NSETS + lane] = (lane < 2 ? task.pad : task2.pad) + 2 * (wv * slices + slice) + (lane & 1);   // pad = first partial slot of the task
+  if (lane < NSETS)   // pad = first partial slot of the task; a pair's sets 2, 3 are sets 0, 1 of its second task
+    raw_slot[bid * NSETS + lane] = ((PAIR && lane >= 2) ? task2.pad : task.pad) + tbw_part_slot(WPW, SEGS, WV, slices, wv, slice, PAIR ? lane & 1 : lane);
+  // the table copy that entry e reads
+  auto copy_of = [&](uint32_t e) {
+    const uint32_t w = (PERWIN ? 0u : (uint32_t)w0) + ((e >> 1) & E::EJM);
+    return SEGS == 2 ? tbl_window(w, 8).copy : w;
+  };
 
   uint32_t next = first;
-  bool later = false;   // a later round: the accumulators are parked in raw0 / raw1
+  bool later = false;   // a later round: the accumulators are parked in the raw sets
   do {
-    cnt[lane] = 0;
-    cnt[64 + lane] = 0;
-    __syncthreads();
-    // histogram over as many 64-point slabs as fit the list
-    uint32_t total = 0, end = next;
-    while (end < ntot && end - next + 64 <= ROUND_PTS) {
-      const uint32_t i = end + lane;
-      uint32_t dg[NW], sg_lo, sg_hi;
-      int mine = 0;
-      if (i < ntot) {
-        tbw_digits<WPW, PERWIN>(task, i, w0, dg, sg_lo, sg_hi);
-        if (CACHE) dcache[i - next] = (dg[0] & 0xffffu) | (sg_lo << 16) | (sg_hi << 17);
-        CPX_UNROLL for (int j = 0; j < WPW; j++) {
-          uint32_t neg;
-          mine += tbw_bucket(dg[j >> 2], j, neg) < 128u ? 1 : 0;
-        }
-      }
-      int ct = mine;
-      CPX_UNROLL for (int m = 32; m >= 1; m >>= 1) ct += __shfl_xor(ct, m, 64);
-      if (total && total + (uint32_t)ct > (uint32_t)TBW_CAP) break;
-      if (i < ntot) {
-        CPX_UNROLL for (int j = 0; j < WPW; j++) {
-          uint32_t neg;
-          const uint32_t b = tbw_bucket(dg[j >> 2], j, neg);
-          if (b < 128u) atomicAdd(&cnt[b], 1u);
-        }
-      }
-      total += (uint32_t)ct;
-      end = min(end + 64, ntot);
-    }
-    __syncthreads();
-    // list offsets: exclusive scan of the 128 bucket sizes over the wave (lane l scans buckets 2l, 2l + 1)
-    {
-      const uint32_t a0 = cnt[2 * lane], a1 = cnt[2 * lane + 1];
-      uint32_t incl = a0 + a1;
-      CPX_UNROLL for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)incl, d, 64);
-        if (lane >= d) incl += y;
-      }
-      const uint32_t o = incl - (a0 + a1);
-      start[2 * lane] = o;
-      start[2 * lane + 1] = o + a0;
-      cur[2 * lane] = o;
-      cur[2 * lane + 1] = o + a0;
-      // which two buckets this lane adds up: the 128 buckets ranked by size, lane l takes rank l and rank 127 - l
-      // (longest with shortest), so the lanes' totals differ by a few additions instead of +-30 %
-      uint32_t r0 = 0, r1 = 0;
-      for (int q = 0; q < 128; q++) {
-        const uint32_t c = cnt[q];
-        r0 += (c < a0 || (c == a0 && q < 2 * lane)) ? 1u : 0u;
-        r1 += (c < a1 || (c == a1 && q < 2 * lane + 1)) ? 1u : 0u;
-      }
-      order[r0] = (uint8_t)(2 * lane);
-      order[r1] = (uint8_t)(2 * lane + 1);
-    }
-    __syncthreads();
-    const uint32_t b0 = order[lane];
-    const uint32_t c0 = cnt[b0], c1 = cnt[order[127 - lane]], s0_ = start[b0];
-    // PAIR: both tasks have the same lists, so a lane that walked its own bucket pair twice carried twice its imbalance (252 points: the
-    // longest pair 10.2 entries against a mean of 7.8).  The second task's walk takes the bucket pair of ANOTHER lane instead: the lanes are
-    // ranked by the size of their pair and lane of rank r takes the pair of rank 63 - r (the buckets are parked by bucket index, whoever adds
-    // them up): the two walks of a lane sum to about twice the mean
-    int partner = lane;
-    if (PAIR) {
-      const uint32_t mine = c0 + c1;
+    const uint32_t end = tbw_sort<WPW, PERWIN, NBINS, WPW == 2 && !PERWIN>(ts, task, w0, next, ntot);
+    if constexpr (BOTH) {
+      tbw_walk_lists<4>(
+          ts, raw0, later, [&](int sg) { return (uint32_t)ts.order[sg == 0 ? lane : sg == 1 ? 127 - lane : sg == 2 ? 128 + lane : 255 - lane]; },
+          [&](int, uint32_t bin) { return bin >> 6; }, [&](int, uint32_t e) { return tbl_point(task, next + (e >> E::ESH), copy_of(e)); });
+    } else if constexpr (PAIR) {
+      // both tasks have the same lists, so a lane that walked its own bucket pair twice carried twice its imbalance (252 points: the
+      // longest pair 10.2 entries against a mean of 7.8).  The second task's walk takes the bucket pair of ANOTHER lane instead: the lanes are
+      // ranked by the size of their pair and lane of rank r takes the pair of rank 63 - r (the buckets are parked by bucket index, whoever adds
+      // them up): the two walks of a lane sum to about twice the mean
+      const uint32_t mine = ts.cnt[ts.order[lane]] + ts.cnt[ts.order[127 - lane]];
       uint32_t rk = 0;
       for (int q = 0; q < 64; q++) {
         const uint32_t o = (uint32_t)__shfl((int)mine, q, 64);
         rk += (o < mine || (o == mine && q < lane)) ? 1u : 0u;
       }
       // lane of rank 63 - rk: every lane publishes its rank, the partner is found by a second sweep
+      int partner = lane;
       for (int q = 0; q < 64; q++) {
         const uint32_t o = (uint32_t)__shfl((int)rk, q, 64);
         if (o == 63u - rk) partner = q;
       }
-    }
-    for (uint32_t s0 = next; s0 < end; s0 += 64) {
-      const uint32_t i = s0 + lane;
-      if (i < end) {
-        uint32_t dg[NW], sg_lo, sg_hi;
-        if (CACHE) {
-          const uint32_t v = dcache[i - next];
-          dg[0] = v & 0xffffu;
-          sg_lo = (v >> 16) & 1u;
-          sg_hi = (v >> 17) & 1u;
-        } else {
-          tbw_digits<WPW, PERWIN>(task, i, w0, dg, sg_lo, sg_hi);
-        }
-        CPX_UNROLL for (int j = 0; j < WPW; j++) {
-          uint32_t neg;
-          const uint32_t b = tbw_bucket(dg[j >> 2], j, neg);
-          neg ^= (PERWIN ? j == 0 : w0 + j < 16) ? sg_lo : sg_hi;
-          if (b < 128u) list[atomicAdd(&cur[b], 1u)] = (uint16_t)(((i - next) << ESH) | ((uint32_t)j << 1) | neg);
-        }
-      }
-    }
-    __syncthreads();
-    if constexpr (!PAIR) {
+      const ptrdiff_t base2 = task2.seg[0].base - task.seg[0].base;   // (a pair's tasks differ in their bases only)
+      // own, own, partner, partner; bucket b lives in set b / 64 (+ 2 for the second task) at position b % 64
+      tbw_walk_lists<4>(
+          ts, raw0, later, [&](int sg) { return (uint32_t)ts.order[(sg & 1) ? 127 - (sg >= 2 ? partner : lane) : (sg >= 2 ? partner : lane)]; },
+          [&](int sg, uint32_t bin) { return 2 * (uint32_t)(sg >> 1) + (bin >> 6); },
+          [&](int sg, uint32_t e) { return tbl_point(task, next + (e >> E::ESH), copy_of(e)) + (sg >= 2 ? base2 : 0); });
+    } else {
       // every lane walks its two lists in one loop; at the boundary it parks the first accumulator (by bucket index)
-      const uint32_t b1 = order[127 - lane], s1_ = start[b1];
+      const uint32_t b0 = ts.order[lane], b1 = ts.order[127 - lane];
+      const uint32_t c0 = ts.cnt[b0], c1 = ts.cnt[b1], s0_ = ts.start(b0), s1_ = ts.start(b1);
       uint32_t* const rb0 = raw0 + (b0 >> 6) * RAW_SET_WORDS;   // bucket b lives in set b / 64 at position b % 64
       uint32_t* const rb1 = raw0 + (b1 >> 6) * RAW_SET_WORDS;
       TAcc xacc = later ? raw_load(rb0, b0 & 63) : TAcc::identity();
@@ -303,190 +391,16 @@ template <int WPW, bool PERWIN, bool PAIR = false, int SEGS = 1> __device__ __fo
           raw_store(rb0, b0 & 63, xacc);
           xacc = later ? raw_load(rb1, b1 & 63) : TAcc::identity();
         }
-        const uint32_t e = list[k < c0 ? s0_ + k : s1_ + (k - c0)];
-        const uint32_t w = (PERWIN ? 0u : (uint32_t)w0) + ((e >> 1) & EJM);
-        const TAff q = *tbl_point(task, next + (e >> ESH), SEGS == 2 ? tbl_window(w, 8).copy : w);
-        xacc = t_acc_add_mixed_inl(xacc, t_cneg_lazy(q, (e & 1u) != 0));   // products inlined: no argument moves, 231 VGPRs, no scratch
+        const uint32_t e = ts.list[k < c0 ? s0_ + k : s1_ + (k - c0)];
+        const TAff q = *tbl_point(task, next + (e >> E::ESH), copy_of(e));
+        xacc = t_acc_add_mixed_inl(xacc, t_cneg_lazy(q, (e & 1u) != 0));   // products inlined: no argument moves, no scratch (profiles/r11_bucket_wave.md)
       }
       if (c1 == 0) {
         raw_store(rb0, b0 & 63, xacc);
         xacc = later ? raw_load(rb1, b1 & 63) : TAcc::identity();
       }
       raw_store(rb1, b1 & 63, xacc);
-    } else {
-      // ONE loop over the lane's four bucket lists — its own two for the first task, the two of its partner lane for the second: a wave runs a
-      // loop until its slowest lane is through, so only inside one loop do a lane's long and short lists add up (two loops, one per task,
-      // each waited for the longest pair of buckets of the wave, whoever walked it; the same loop in the one-task kernels measured 0.4 % slower
-      // than the two-list loop above).  Segment sg: bucket, list, raw set and task; a segment that ends parks its accumulator by bucket index
-      // and loads (or zeroes) the next one.
-      constexpr int NSEG = PAIR ? 4 : 2;
-      auto seg_bucket = [&](int sg) { return (uint32_t)order[(sg & 1) ? 127 - ((PAIR && sg >= 2) ? partner : lane) : ((PAIR && sg >= 2) ? partner : lane)]; };
-      uint32_t nwalk = c0 + c1;   // entries of all the lane's lists
-      if (PAIR) nwalk += cnt[seg_bucket(2)] + cnt[seg_bucket(3)];
-      const ptrdiff_t base2 = PAIR ? task2.seg[0].base - task.seg[0].base : 0;   // (a pair's tasks differ in their bases only)
-      int sg = 0;
-      uint32_t bk = b0, cs = c0, st = s0_, kin = 0;
-      uint32_t* rb = raw0 + (bk >> 6) * RAW_SET_WORDS;   // bucket b lives in set b / 64 (+ 2 for the second task of a pair) at position b % 64
-      TAcc xacc = later ? raw_load(rb, bk & 63) : TAcc::identity();
-      auto next_segment = [&]() {
-        raw_store(rb, bk & 63, xacc);
-        sg++;
-        bk = seg_bucket(sg);
-        cs = cnt[bk];
-        st = start[bk];
-        kin = 0;
-        rb = raw0 + (2 * (sg >> 1) + (bk >> 6)) * RAW_SET_WORDS;
-        xacc = later ? raw_load(rb, bk & 63) : TAcc::identity();
-      };
-#pragma unroll 1
-      for (uint32_t k = 0; k < nwalk; k++) {
-        while (kin == cs) next_segment();   // (sg stays below NSEG: entries remain)
-        const uint32_t e = list[st + kin];
-        const TAff* src = tbl_point(task, next + (e >> ESH), (PERWIN ? 0u : (uint32_t)w0) + ((e >> 1) & EJM));
-        if (PAIR && sg >= 2) src += base2;
-        const TAff q = *src;
-        xacc = t_acc_add_mixed_inl(xacc, t_cneg_lazy(q, (e & 1u) != 0));   // products inlined: no argument moves, no scratch
-        kin++;
-      }
-      while (sg + 1 < NSEG) next_segment();   // the lists that were empty or remain: every bucket of the round is written
-      raw_store(rb, bk & 63, xacc);
     }
-    __syncthreads();
-    next = end;
-    later = true;
-  } while (next < ntot);
-}
-// ------------------------------------------------------------------ two-segment tables: one wave, both weight classes
-// The per-proof tables of a large batch hold 8 + 8 copies (kernels.h): windows 8..15 of a half read the same copies as windows 0..7 and
-// their sums carry the weight 2^64.  A wave of 16 or 32 windows serves both classes: ONE histogram over 256 bins (class x magnitude),
-// the bins ranked by size, lane l walks the lists of rank l, 127 - l, 128 + l and 255 - l (longest with shortest, twice) in one loop
-// and parks the accumulator at every boundary.  Four raw sets per wave — bin b lives in set b / 64: [class 0 lower | upper | class 1
-// lower | upper] — and four partial slots: the task's range is [class 1: two per wave | class 0: two per wave].  The list offsets are
-// not kept beside the cursors (after the scatter cur[b] - cnt[b] is where list b starts): 19 712 B of LDS, two waves per SIMD.
-constexpr int TBW2_BINS = 256;
-constexpr int TBW2_LDS = TBW_CAP * 2 + 2 * TBW2_BINS * 4 + TBW2_BINS;
-static_assert(TBW_LDS <= 20480 && TBW2_LDS <= 20480, "eight single-wave groups per CU share 160 KiB of LDS");
-template <int WPW> __device__ __forceinline__ void msm_tblw2_body(const TblTask* __restrict__ tasks, uint32_t* __restrict__ raw, uint32_t* __restrict__ raw_slot,
-                                                                  int slices, const uint32_t bid) {
-  static_assert(WPW == 16 || WPW == 32, "both classes of a half in one wave");
-  constexpr int WV = TBW_WINDOWS / WPW, NW = WPW / 4, NSEG = 4;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint16_t* list = reinterpret_cast<uint16_t*>(smem);                 // [TBW_CAP]
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + TBW_CAP * 2);    // [256] bin sizes of the round
-  uint32_t* cur = cnt + TBW2_BINS;                                    // [256] scatter cursors
-  uint8_t* order = reinterpret_cast<uint8_t*>(cur + TBW2_BINS);       // [256] bins by size
-  const TblTask task = tasks[bid / (WV * slices)];
-  const int wv = (bid / slices) % WV, w0 = wv * WPW, slice = bid % slices;
-  const int lane = threadIdx.x;
-  const uint32_t nall = task.seg[0].n + task.seg[1].n, per = ((nall + slices - 1) / slices + 63) & ~63u;
-  const uint32_t first = min(nall, (uint32_t)slice * per), ntot = min(nall, first + per);
-  uint32_t* raw0 = raw + (size_t)bid * NSEG * RAW_SET_WORDS;
-  if (lane < NSEG) raw_slot[bid * NSEG + lane] = task.pad + ((lane >> 1) ? 0 : 2 * WV * slices) + 2 * (wv * slices + slice) + (lane & 1);
-  // bin of window j's digit: class (w0 is a multiple of 16, so the class is bit 3 of j) x magnitude, or >= 256 for a zero digit
-  auto bin_of = [](uint32_t word, int j, uint32_t& neg) {
-    const uint32_t b = tbw_bucket(word, j, neg);
-    return b < 128u ? b + 128u * (uint32_t)((j >> 3) & 1) : 256u;
-  };
-
-  uint32_t next = first;
-  bool later = false;   // a later round: the accumulators are parked in the raw sets
-  do {
-    CPX_UNROLL for (int k = 0; k < 4; k++) cnt[64 * k + lane] = 0;
-    __syncthreads();
-    uint32_t total = 0, end = next;
-    while (end < ntot && end - next + 64 <= (uint32_t)TBW_ROUND_PTS) {
-      const uint32_t i = end + lane;
-      uint32_t dg[NW], sg_lo, sg_hi;
-      int mine = 0;
-      if (i < ntot) {
-        tbw_digits<WPW, false>(task, i, w0, dg, sg_lo, sg_hi);
-        CPX_UNROLL for (int j = 0; j < WPW; j++) {
-          uint32_t neg;
-          mine += tbw_bucket(dg[j >> 2], j, neg) < 128u ? 1 : 0;
-        }
-      }
-      int ct = mine;
-      CPX_UNROLL for (int m = 32; m >= 1; m >>= 1) ct += __shfl_xor(ct, m, 64);
-      if (total && total + (uint32_t)ct > (uint32_t)TBW_CAP) break;
-      if (i < ntot) {
-        CPX_UNROLL for (int j = 0; j < WPW; j++) {
-          uint32_t neg;
-          const uint32_t b = bin_of(dg[j >> 2], j, neg);
-          if (b < 256u) atomicAdd(&cnt[b], 1u);
-        }
-      }
-      total += (uint32_t)ct;
-      end = min(end + 64, ntot);
-    }
-    __syncthreads();
-    // list offsets (lane l scans bins 4 l .. 4 l + 3) and the rank of every bin by size
-    {
-      uint32_t a[4], sum = 0;
-      CPX_UNROLL for (int k = 0; k < 4; k++) {
-        a[k] = cnt[4 * lane + k];
-        sum += a[k];
-      }
-      uint32_t incl = sum;
-      CPX_UNROLL for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)incl, d, 64);
-        if (lane >= d) incl += y;
-      }
-      uint32_t o = incl - sum;
-      CPX_UNROLL for (int k = 0; k < 4; k++) {
-        cur[4 * lane + k] = o;
-        o += a[k];
-      }
-      uint32_t r[4] = {0, 0, 0, 0};
-      for (int q = 0; q < TBW2_BINS; q++) {
-        const uint32_t c = cnt[q];
-        CPX_UNROLL for (int k = 0; k < 4; k++) r[k] += (c < a[k] || (c == a[k] && q < 4 * lane + k)) ? 1u : 0u;
-      }
-      CPX_UNROLL for (int k = 0; k < 4; k++) order[r[k]] = (uint8_t)(4 * lane + k);
-    }
-    __syncthreads();
-    for (uint32_t s0 = next; s0 < end; s0 += 64) {
-      const uint32_t i = s0 + lane;
-      if (i < end) {
-        uint32_t dg[NW], sg_lo, sg_hi;
-        tbw_digits<WPW, false>(task, i, w0, dg, sg_lo, sg_hi);
-        CPX_UNROLL for (int j = 0; j < WPW; j++) {
-          uint32_t neg;
-          const uint32_t b = bin_of(dg[j >> 2], j, neg);
-          neg ^= (w0 + j < 16) ? sg_lo : sg_hi;
-          if (b < 256u) list[atomicAdd(&cur[b], 1u)] = (uint16_t)(((i - next) << 6) | ((uint32_t)j << 1) | neg);
-        }
-      }
-    }
-    __syncthreads();
-    // ONE loop over the lane's four lists (as the pairs of msm_tblw_body walk theirs): a list that ends parks its accumulator by bin
-    // index and loads (or zeroes) the next one
-    auto seg_bin = [&](int sg) { return (uint32_t)order[sg == 0 ? lane : sg == 1 ? 127 - lane : sg == 2 ? 128 + lane : 255 - lane]; };
-    uint32_t nwalk = 0;
-    CPX_UNROLL for (int sg = 0; sg < NSEG; sg++) nwalk += cnt[seg_bin(sg)];
-    int sg = 0;
-    uint32_t bk = seg_bin(0), cs = cnt[bk], st = cur[bk] - cs, kin = 0;
-    uint32_t* rb = raw0 + (bk >> 6) * RAW_SET_WORDS;
-    TAcc xacc = later ? raw_load(rb, bk & 63) : TAcc::identity();
-    auto next_segment = [&]() {
-      raw_store(rb, bk & 63, xacc);
-      sg++;
-      bk = seg_bin(sg);
-      cs = cnt[bk];
-      st = cur[bk] - cs;
-      kin = 0;
-      rb = raw0 + (bk >> 6) * RAW_SET_WORDS;
-      xacc = later ? raw_load(rb, bk & 63) : TAcc::identity();
-    };
-#pragma unroll 1
-    for (uint32_t k = 0; k < nwalk; k++) {
-      while (kin == cs) next_segment();   // (sg stays below NSEG: entries remain)
-      const uint32_t e = list[st + kin];
-      const TAff q = *tbl_point(task, next + (e >> 6), tbl_window((uint32_t)w0 + ((e >> 1) & 31u), 8).copy);
-      xacc = t_acc_add_mixed_inl(xacc, t_cneg_lazy(q, (e & 1u) != 0));
-      kin++;
-    }
-    while (sg + 1 < NSEG) next_segment();   // the lists that were empty or remain: every bin of the round is written
-    raw_store(rb, bk & 63, xacc);
     __syncthreads();
     next = end;
     later = true;

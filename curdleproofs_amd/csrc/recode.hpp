@@ -115,6 +115,26 @@ CPX_HD TblWindow tbl_window(uint32_t w, uint32_t real) {
   const uint32_t v = w & 15u;
   return TblWindow{(v & (real - 1u)) + (w >= 16u ? real : 0u), v / real};
 }
+// Where a bucket-list wave (msm_body.hpp msm_tblw_body) leaves its partial sums, one per raw set — the one statement of it for the wave
+// that writes the slots and the planner that tells k_finalize_ranges what they weigh.  A task of `waves` waves of wpw windows, its
+// points shared by `slices` waves per window group, owns slices * tbw_parts slots from TblTask::pad on; a wave leaves the lower and
+// the upper magnitudes of its buckets at adjacent slots 2k, 2k + 1.  One-segment tables (segs = 1, and the waves without shifted
+// copies): waves in order.  Two-segment tables (segs = 2): the slots of weight class 1, slices * tbw_parts_hi of them, come FIRST
+// (k_finalize_ranges doubles their sum 64 times), then those of class 0; a wave of up to 8 windows lies inside one class (its sets
+// 0, 1), a wave of 16 or 32 windows serves both and leaves four sets, set / 2 the class.
+CPX_HD uint32_t tbw_parts(uint32_t wpw, uint32_t segs) { return (segs == 2 && wpw >= 16 ? 128u : 64u) / wpw; }   // per task and slice
+CPX_HD uint32_t tbw_parts_hi(uint32_t wpw, uint32_t segs) { return segs == 2 ? tbw_parts(wpw, segs) / 2 : 0u; }   // those of class 1
+CPX_HD uint32_t tbw_part_slot(uint32_t wpw, uint32_t segs, uint32_t waves, uint32_t slices, uint32_t wv, uint32_t slice, uint32_t set) {
+  if (segs != 2) return 2 * (wv * slices + slice) + set;
+  uint32_t cls = set >> 1, k = wv, per_cls = 2 * waves * slices;   // the set's class, the wave's rank among those of the class, slots per class
+  if (wpw < 16) {   // blocks of 8 windows alternate between the classes: 0, 1 (the |t| half), 0, 1 (the q half)
+    const uint32_t per8 = 8 / wpw, blk = wv / per8;
+    cls = blk & 1;
+    k = (blk >> 1) * per8 + wv % per8;
+    per_cls = waves * slices;
+  }
+  return (cls ? 0u : per_cls) + 2 * (k * slices + slice) + (set & 1u);
+}
 
 // ---- late rounds (k_late_msm): signed radix-16 digits in [-7, 8] of a value v < 2^127 (an endomorphism half), biased by 7 and
 // packed eight per word: v = sum_j (nibble_j - 7) 16^j, j < 32; no carry leaves nibble 31 ----

@@ -245,7 +245,7 @@ template <int FW, int TW, bool IPA, bool COMBINE = false> __global__ __launch_bo
       const uint32_t ntw = (uint32_t)rd.nt * TWV, bt = p * ntw + (COMBINE ? w : w - nfw);
       msm_tblw_body<TW, false>(rd.ttasks, rd.traw, rd.traw_slot, 1, bt);
       tail_sync();
-      const uint32_t slot = rd.ttasks[bt / TWV].pad + 2 * (bt % TWV);
+      const uint32_t slot = rd.ttasks[bt / TWV].pad + tbw_part_slot(TW, 1, TWV, 1, bt % TWV, 0, 0);   // the wave's two sets: slot, slot + 1
       reduce_set_inwave(rd.traw + (size_t)bt * 2 * RAW_SET_WORDS, 1, buf, rd.part + slot);
       reduce_set_inwave(rd.traw + ((size_t)bt * 2 + 1) * RAW_SET_WORDS, 2, buf, rd.part + slot + 1);
     }

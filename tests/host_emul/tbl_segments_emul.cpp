@@ -1,6 +1,7 @@
 // TEST-ONLY: the host side of the shifted-table recoding compiled for the CPU — the endomorphism split (glv.hpp), the signed radix-256
 // digits of a half (glv_biased_bytes) and the window -> (copy, weight class) map of the one- and two-segment tables (recode.hpp
-// tbl_window), exactly as k_msm_tblw and k_late_uniform use them.
+// tbl_window), exactly as k_msm_tblw and k_late_uniform use them, and the partial-slot layout of the bucket-list waves (tbw_parts,
+// tbw_part_slot), as the waves and the planner of a table phase use it.
 #include <cstdint>
 #include "../../curdleproofs_amd/csrc/recode.hpp"
 
@@ -24,4 +25,10 @@ extern "C" void emul_scalar_windows(const uint32_t* k, uint32_t real, uint32_t* 
   glv_split(k, t_abs, q, neg[0], neg[1]);   // neg[0]: k was negated, neg[1]: t is negative
   emul_half_windows(t_abs, real, 0, digits, copy, cls);
   emul_half_windows(q, real, 16, digits + 16, copy + 16, cls + 16);
+}
+
+extern "C" uint32_t emul_tbw_parts(uint32_t wpw, uint32_t segs) { return tbw_parts(wpw, segs); }
+extern "C" uint32_t emul_tbw_parts_hi(uint32_t wpw, uint32_t segs) { return tbw_parts_hi(wpw, segs); }
+extern "C" uint32_t emul_tbw_part_slot(uint32_t wpw, uint32_t segs, uint32_t waves, uint32_t slices, uint32_t wv, uint32_t slice, uint32_t set) {
+  return tbw_part_slot(wpw, segs, waves, slices, wv, slice, set);
 }

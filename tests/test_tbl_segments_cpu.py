@@ -8,7 +8,11 @@ compiler by tests/host_emul/tbl_segments_emul.cpp.  For the one-segment layout (
 A half of sixteen 0x80 bytes is outside the domain of the recoding (glv.hpp: a half is at most 0x7f7f...7f, the halves of a split
 scalar have a top byte of at most 0x56; the carry of the top window would leave the 128 bits), so the "carry through every window"
 case keeps the top byte below that bound: fifteen 0x80 bytes under a top byte of 0x00 and of 0x56 — every window carries into the
-next one, the top one included as a receiver."""
+next one, the top one included as a receiver.
+
+The partial-slot layout of the bucket-list waves (recode.hpp tbw_parts, tbw_part_slot) is checked for every window grouping, both
+table layouts and the wave without shifted copies: the contract between the wave that writes a slot and the planner that tells the
+finalisation how many of a task's partials, the first ones, carry the weight 2^64."""
 import ctypes
 import os
 import random
@@ -100,3 +104,43 @@ def test_random_scalars(emul, real):
     rnd = random.Random(20240)
     for _ in range(1000):
         _scalar(emul, rnd.randrange(R), real)
+
+
+def _tbw_shapes():
+    """(wpw, segs, waves per task, sets per wave, windows summed by set `s` of wave `wv`)"""
+    for segs in (1, 2):
+        for wpw in (2, 4, 8, 16, 32):
+            both = segs == 2 and wpw >= 16   # a wave of both weight classes: four sets, set // 2 the class (bit 3 of the window)
+            def windows(wv, s, wpw=wpw, both=both):
+                return [w for w in range(wv * wpw, (wv + 1) * wpw) if not both or (w >> 3) & 1 == s >> 1]
+            yield wpw, segs, 32 // wpw, 4 if both else 2, windows
+    yield 2, 1, 16, 2, lambda wv, s: [wv, 16 + wv]   # one window of each half per wave, no shifted copies (k_msm_tblw<2, true>)
+
+
+@pytest.mark.parametrize("slices", [1, 2, 4])
+def test_partial_slots_of_the_bucket_waves(emul, slices):
+    for wpw, segs, waves, nsets, windows in _tbw_shapes():
+        parts = emul.emul_tbw_parts(wpw, segs)
+        assert parts == waves * nsets
+        slot = {(wv, sl, s): emul.emul_tbw_part_slot(wpw, segs, waves, slices, wv, sl, s) for wv in range(waves) for sl in range(slices) for s in range(nsets)}
+        # (a) a bijection onto the task's range of partial slots
+        assert sorted(slot.values()) == list(range(slices * parts)), (wpw, segs)
+        cls_of = []   # tbl_window(w, 8).cls of the 32 windows
+        for first in (0, 16):
+            d, copy, c = (ctypes.c_int32 * 16)(), (ctypes.c_uint32 * 16)(), (ctypes.c_uint32 * 16)()
+            emul.emul_half_windows(_words(0, 4), 8, first, d, copy, c)
+            cls_of += list(c)
+        hi = 0
+        for (wv, sl, s), v in slot.items():
+            ws = windows(wv, s)
+            assert ws and set(ws) <= set(range(32))
+            if segs == 1:
+                assert v == 2 * (wv * slices + sl) + s                                # (b) waves in order
+            else:
+                cls = {cls_of[w] for w in ws}
+                assert len(cls) == 1, "a set sums windows of both weight classes"
+                assert (v < slices * parts // 2) == (cls == {1}), (wpw, wv, sl, s)    # (c) class 1 first
+                hi += cls == {1}
+            # (d) the lower and the upper magnitudes of one (wave, class) side by side
+            assert s % 2 == 0 or (v % 2 == 1 and slot[(wv, sl, s - 1)] == v - 1)
+        assert hi == slices * emul.emul_tbw_parts_hi(wpw, segs)                       # what the planner records as tbl_hi
