@@ -392,6 +392,44 @@ void Engine::run_tbl_phase(const std::vector<TblReq>& reqs, std::vector<uint8_t>
   }
 }
 
+// The requests of a phase as prove_reqs.hpp describes them, for every loaded proof: the gather lists of the list are resolved once, the
+// rest per proof.  The ONE place where a request of the protocol becomes a TblReq.
+std::vector<TblReq> Engine::make_reqs(const ReqList& list, const ScalAt& scal_at, std::vector<uint32_t>* comp_index) {
+  const SlotMap sm(L_);
+  const uint32_t* idx[ReqList::MAX][2];
+  std::vector<uint32_t> g(n_ + 1);
+  for (int i = 0; i < list.n; i++)
+    for (int h = 0; h < 2; h++) {
+      const ReqSeg& sg = h ? list.r[i].seg1 : list.r[i].seg0;
+      const int cnt = gather_list((int)n_, sg.gather, sg.arg, g.data());
+      idx[i][h] = cnt ? idx_list(std::vector<uint32_t>(g.begin(), g.begin() + cnt)) : nullptr;
+    }
+  auto seg = [&](size_t p, const ReqSeg& sg, const uint32_t* ix) {
+    return sg.kind == SEG_CRS ? cseg((size_t)sg.off, (uint32_t)sg.n, ix) : sg.kind == SEG_PTAB ? pseg(p, (size_t)sg.off, (uint32_t)sg.n, ix) : TblSeg{nullptr, nullptr, 0, 0};
+  };
+  std::vector<TblReq> reqs;
+  reqs.reserve(B_ * (size_t)list.n);
+  for (size_t p = 0; p < B_; p++)
+    for (int i = 0; i < list.n; i++) {
+      const ReqDesc& d = list.r[i];
+      TblReq r{seg(p, d.seg0, idx[i][0]), nullptr, seg(p, d.seg1, idx[i][1]), nullptr};
+      if (d.keep >= 0) r.dst = slot_index(p, d.keep);
+      for (int j = 0; j < 3; j++)
+        if (d.add[j] >= 0) r.add[j] = slot_index(p, d.add[j]);
+      if (d.scal.kind == SCAL_ROUND) r.dev = d_rout_.p + p * (size_t)list.round_stride + d.scal.at;
+      else if (d.scal.kind != SCAL_NONE) {
+        const ScalAddr a = scal_at(p, d.scal);
+        r.s0 = a.host;
+        r.s1 = a.host ? a.host + d.seg0.n : nullptr;
+        r.dev = a.dev;
+      }
+      reqs.push_back(r);
+      // (a request without an output: its compressed bytes go to TMP(6), which nobody reads)
+      if (comp_index) comp_index->push_back((uint32_t)(p * sm.count() + (d.out >= 0 ? d.out : sm.TMP(6))));
+    }
+  return reqs;
+}
+
 // R = a x vec_R, S = a x vec_S (curdleproofs.rs:112-113) and whatever further tasks over the same points side_.tasks holds: the
 // endomorphism bucket-list kernel (pairs: R and S of a proof share the scalars vec_a — one wave per (proof, window) serves both,
 // kernels.h launch_msm_endo_pairs), reduction and Horner tail in the side scratch on stream `st`; the first nfinal results go to
@@ -935,18 +973,15 @@ void Engine::batch_load_end() {
 namespace {
 struct ProverState {
   Transcript tr{"curdleproofs"};
-  SVec vec_a, a_perm, x;            // x: SameMSM witness vector
-  SVec c, d;                        // IPA vectors
-  SVec factors;
-  S alpha_sp, beta_sp, gprod, alpha_g, beta_g, beta_g_inv, r_p, z_ip, alpha_i, beta_i, alpha_m;
-  SVec vec_c_blinders, rb_plus_alpha, u;
-  SVec SG, SGp, SM;                 // all-MSM prover: per-original-base fold coefficients (IPA G, IPA G' incl. u, SameMSM)
-  SVec scal[8];                     // scalar vectors handed to the device for the current phase
-  S gam[2];
+  // the scalars under the names the device-resident prover keeps them by (protocol.h, layout.hpp): the RandIdx row, the vectors V_*
+  // (V_FACT: its first ell entries — the host-driven B is a sum of points, not the commitment form that reads the blinder entries),
+  // the small scalars SC_*
+  SVec rnd;
+  SVec vec[V_COUNT];
+  S sc[SC_COUNT];
+  S k;
+  SVec vec_a, rb_plus_alpha;
   std::vector<uint8_t> comp;        // compressed bytes of every slot (count * 48)
-  S r_p_out, c_final, d_final, z_k, z_t, z_u, x_final;
-  const uint8_t* rnd;               // 3n+9 Fr draws, wire form
-  S draw(size_t i) const { return S_from_wire(rnd + 32 * i); }
 };
 }  // namespace
 
@@ -1025,19 +1060,24 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   const SlotMap sm(L);
   const RandIdx ri((int)n);
   const PtabRow row(n);
-  const CtabCols cc(n);
   const size_t nrand = ri.count();
   const int NS = sm.count();
   const size_t NP = np();
   std::vector<ProverState> st(B);
   std::vector<uint8_t> comp;
-  const uint32_t* iH = idx_list({(uint32_t)cc.H()});
-  const uint32_t* iGt = idx_list({(uint32_t)cc.G_t()});
-  const uint32_t* iGu = idx_list({(uint32_t)cc.G_u()});
-  std::vector<uint32_t> gb(n);
-  cc.same_msm_basis(gb.data());
-  const uint32_t* iGb = idx_list(gb);
-  const TblSeg none{nullptr, nullptr, 0, 0};
+  const int ni = (int)n, Li = (int)L;
+  // where a request's scalars are staged from: the proof's host state (make_reqs points the round phases at d_rout_ itself)
+  const ScalAt scal = [&](size_t p, const ReqScal& sc) {
+    const ProverState& s = st[p];
+    return ScalAddr{sc.kind == SCAL_RAND ? &s.rnd[(size_t)sc.at] : sc.kind == SCAL_VEC ? s.vec[sc.at].data() : &s.sc[sc.at], nullptr};
+  };
+  // the compressed results of a phase (request order, in `src`) into the slots its requests name
+  auto take = [&](size_t p, const ReqList& l, const uint8_t* src) {
+    for (int i = 0; i < l.n; i++)
+      if (l.r[i].out >= 0) memcpy(&st[p].comp[(size_t)l.r[i].out * 48], src + (p * (size_t)l.n + i) * 48, 48);
+  };
+  int side_slots[6];   // R, S and the four T_2 commitments: the side stream's
+  side_stream_slots(Li, side_slots);
 
   // -- P0: compressed instance vectors, M -> affine (into table slot 0), then the per-proof tables.  The transcript
   //    prefix (instance + M absorbed, vec_a drawn) is hashed on the side stream while the tables are built.
@@ -1080,7 +1120,9 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     wait_side();
     parallel_for(B, [&](size_t p) {
       ProverState& s = st[p];
-      s.rnd = rand + p * nrand * 32;
+      s.rnd.resize(nrand);
+      for (size_t i = 0; i < nrand; i++) s.rnd[i] = S_from_wire(rand + (p * nrand + i) * 32);
+      s.k = S_from_wire(k_in + 32 * p);
       s.comp.assign((size_t)NS * 48, 0);
       memcpy(&s.comp[SL_M * 48], &mcomp[p * 48], 48);
       {   // curdleproofs.rs:78-83
@@ -1089,27 +1131,14 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
         s.tr.append_point_bytes("curdleproofs_step1", &s.comp[SL_M * 48]);
         s.vec_a = s.tr.get_and_append_challenges("curdleproofs_vec_a", ell);
       }
+      // the scalars of A: vec_a permuted, then the two vec_a_blinders and two zeros (curdleproofs.rs:85-93)
       const uint32_t* perm = permutation + p * ell;
-      s.a_perm.resize(ell);
-      for (size_t i = 0; i < ell; i++) s.a_perm[i] = s.vec_a[perm[i]];
-      const S kk = S_from_wire(k_in + 32 * p), r_k = s.draw(ri.RK());
-      // scalar vectors of phase 1
-      s.scal[0] = s.a_perm;                                   // A (and the head of A') over G | Hvec
-      s.scal[0].push_back(s.draw(ri.AB()));
-      s.scal[0].push_back(s.draw(ri.AB() + 1));
-      s.scal[0].push_back(S::zero());
-      s.scal[0].push_back(S::zero());
-      s.scal[0].push_back(s.draw(ri.RT()));                   // ... then r_t on G_t, r_u on G_u for A' (curdleproofs.rs:134)
-      s.scal[0].push_back(s.draw(ri.RU()));
-      s.scal[1].resize(n);                                    // vec_r of SameMSM: B_a, B_t, B_u
-      for (size_t i = 0; i < n; i++) s.scal[1][i] = s.draw(ri.VR() + i);
-      s.scal[2] = {s.draw(ri.RT()), s.draw(ri.RU()), s.draw(ri.RA()), s.draw(ri.RB())};
-      s.scal[3] = {kk, r_k};                                   // scalars of the four T_2 scalar multiplications
-      s.scal[4].resize(n);                                     // r_c of the IPA (inner_product_argument.rs:46): B_c = msm(G | Hvec, r_c)
-      for (size_t i = 0; i < n; i++) s.scal[4][i] = s.draw(ri.IR() + i);
+      SVec& ap = s.vec[V_APERM];
+      ap.resize(n);
+      for (size_t i = 0; i < ell; i++) ap[i] = s.vec_a[perm[i]];
+      for (size_t i = 0; i < N_BLINDERS; i++) ap[ell + i] = i < 2 ? s.rnd[ri.AB() + i] : S::zero();
     });
   }
-  auto take = [&](size_t p, int slot_id, size_t req_index) { memcpy(&st[p].comp[(size_t)slot_id * 48], &comp[req_index * 48], 48); };
 
   // -- side stream: R = a x vec_R and S = a x vec_S (curdleproofs.rs:112-113).  The instance points R_i, S_i are
   //    used by exactly these MSMs, so they get no table: the endomorphism bucket-list kernel (the verifier's) + tails off the
@@ -1133,19 +1162,18 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     MsmTask* ht = reinterpret_cast<MsmTask*>(side_.stage.p + o_tasks);
     uint32_t* hd = reinterpret_cast<uint32_t*>(side_.stage.p + o_dst);   // [nt] destination slots, [nt] addend slots
     parallel_for(B, [&](size_t p) {
-      const S kk = st[p].scal[3][0], r_k = st[p].scal[3][1];
+      const S kk = st[p].k, r_k = st[p].rnd[ri.RK()];
       for (size_t i = 0; i < ell; i++) {
         hs[p * ell + i] = st[p].vec_a[i].f;
         hs[total + p * ell + i] = (st[p].vec_a[i] * kk).f;
         hs[2 * total + p * ell + i] = (st[p].vec_a[i] * r_k).f;
       }
       // tasks [0, 2B): R, S; tasks [2B, 6B): k R, k S, r_k R, r_k S (finalised later, on top of the r H points of phase 1)
-      const int dsts[6] = {SL_R, SL_S, SL_CMT2, SL_CMU2, sm.CMA2(), sm.CMB2()};
       for (int j = 0; j < 6; j++) {
         const size_t t = j < 2 ? 2 * p + j : 2 * B + 4 * p + (j - 2);
         const Fr* sc = side_.scal.p + (size_t)(j / 2) * total + p * ell;
         ht[t] = MsmTask{pp(p) + (j & 1) * ell, nullptr, sc, (uint32_t)ell, 0, (uint32_t)(t * ell)};
-        hd[t] = slot_index(p, dsts[j]);
+        hd[t] = slot_index(p, side_slots[j]);
         hd[nt + t] = j < 2 ? ~0u : slot_index(p, sm.TMP(j - 2));
       }
     });
@@ -1161,14 +1189,10 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   }
 
   // -- table stream: B_t = msm(T_b, vec_r), B_u = msm(U_b, vec_r) (same_multiscalar_argument.rs:81-82) right behind the tables of T and U
+  const ReqList p1t = prove_phase1t(ni, Li);
   {
-    const size_t nt = 2 * B;
-    std::vector<TblReq> reqs;
-    for (size_t p = 0; p < B; p++) {
-      reqs.push_back({pseg(p, row.T(), (uint32_t)n), st[p].scal[1].data(), none, nullptr});
-      reqs.push_back({pseg(p, row.U(), (uint32_t)n), st[p].scal[1].data(), none, nullptr});
-    }
-    enqueue_tbl_phase(reqs, slot_index(0, sm.TMP(7)), tab_.stage, tab_.blob, tab_.comp, tab_.stream, tab_.scr, false);
+    const size_t nt = p1t.n * B;
+    enqueue_tbl_phase(make_reqs(p1t, scal), slot_index(0, sm.TMP(7)), tab_.stage, tab_.blob, tab_.comp, tab_.stream, tab_.scr, false);
     tab_.hcomp.ensure(nt * 48);
     CPX_HIP(hipMemcpyAsync(tab_.hcomp.p, tab_.comp.p, nt * 48, hipMemcpyDeviceToHost, tab_.stream));
     CPX_HIP(hipEventRecord(tab_.ev_done, tab_.stream));
@@ -1176,55 +1200,30 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
 
   // -- P1: everything that depends only on vec_a and the prover's randomness
   {
-    std::vector<TblReq> reqs;
-    for (size_t p = 0; p < B; p++) {
-      ProverState& s = st[p];
-      const S* rt = &s.scal[2][0];
-      const S* ru = &s.scal[2][1];
-      const S* ra = &s.scal[2][2];
-      const S* rb = &s.scal[2][3];
-      reqs.push_back({cseg(0, (uint32_t)n), s.scal[0].data(), none, nullptr, slot_index(p, SL_A)});  // A (kept as a point: B and A' add it)
-      reqs.push_back({cseg(0, (uint32_t)n, iGb), s.scal[1].data(), none, nullptr});                   // B_a (same_multiscalar_argument.rs:80)
-      reqs.push_back({cseg(0, 1, iGt), rt, none, nullptr, slot_index(p, SL_CMT1)});                   // cm_T.T_1 = r_t G_t
-      reqs.push_back({cseg(0, 1, iGu), ru, none, nullptr, slot_index(p, SL_CMU1)});                   // cm_U.T_1
-      reqs.push_back({cseg(0, 1, iGt), ra, none, nullptr});                                           // cm_A.T_1
-      reqs.push_back({cseg(0, 1, iGu), rb, none, nullptr});                                           // cm_B.T_1
-      // r * H halves of the four T_2 commitments, kept as affine points for the side-stream scalar multiplications
-      reqs.push_back({cseg(0, 1, iH), rt, none, nullptr, slot_index(p, sm.TMP(0))});
-      reqs.push_back({cseg(0, 1, iH), ru, none, nullptr, slot_index(p, sm.TMP(1))});
-      reqs.push_back({cseg(0, 1, iH), ra, none, nullptr, slot_index(p, sm.TMP(2))});
-      reqs.push_back({cseg(0, 1, iH), rb, none, nullptr, slot_index(p, sm.TMP(3))});
-      reqs.push_back({cseg(0, (uint32_t)n), s.scal[4].data(), none, nullptr});                        // B_c: depends on the randomness only
-    }
-    run_tbl_phase(reqs, &comp);
+    const ReqList p1 = prove_phase1b(ni, Li).then(prove_phase1(ni, Li));   // A, then what depends on the randomness only
+    run_tbl_phase(make_reqs(p1, scal), &comp);
     parallel_for(B, [&](size_t p) {
       ProverState& s = st[p];
-      const int ids[11] = {SL_A, sm.BA(), SL_CMT1, SL_CMU1, sm.CMA1(), sm.CMB1(), -1, -1, -1, -1, SL_BC};
-      for (int i = 0; i < 11; i++)
-        if (ids[i] >= 0) take(p, ids[i], p * 11 + i);
+      take(p, p1, comp.data());
       // same_permutation_argument.rs:60-83
       s.tr.append_point_bytes("same_perm_step1", &s.comp[SL_A * 48]);
       s.tr.append_point_bytes("same_perm_step1", &s.comp[SL_M * 48]);
       s.tr.append_scalar_vec("same_perm_step1", s.vec_a);
-      s.alpha_sp = s.tr.get_and_append_challenge("same_perm_alpha");
-      s.beta_sp = s.tr.get_and_append_challenge("same_perm_beta");
+      s.sc[SC_ALPHA_SP] = s.tr.get_and_append_challenge("same_perm_alpha");
+      s.sc[SC_BETA_SP] = s.tr.get_and_append_challenge("same_perm_beta");
       const uint32_t* perm = permutation + p * ell;
-      s.factors.resize(ell);
-      s.gprod = S::one();
+      s.vec[V_FACT].resize(ell);
+      s.sc[SC_GPROD] = S::one();
       for (size_t i = 0; i < ell; i++) {
-        s.factors[i] = s.a_perm[i] + S::from_u64(perm[i]) * s.alpha_sp + s.beta_sp;
-        s.gprod *= s.factors[i];
+        s.vec[V_FACT][i] = s.vec[V_APERM][i] + S::from_u64(perm[i]) * s.sc[SC_ALPHA_SP] + s.sc[SC_BETA_SP];
+        s.sc[SC_GPROD] *= s.vec[V_FACT][i];
       }
-      // B = A + alpha M + beta * sum(G) (same_permutation_argument.rs:75-76): the point A of phase 1 plus two
-      // single-point terms (G_sum sits in the CRS tables)
-      s.scal[5] = {s.beta_sp};
-      s.scal[6] = {s.alpha_sp};
+      // (B = A + alpha M + beta * sum(G) (same_permutation_argument.rs:75-76): the point A of phase 1 plus two single-point terms
+      // with the scalars beta, alpha — G_sum sits in the CRS tables)
       // the partial products c (grand_product_argument.rs:66-75) need the factors only, so C joins the phase of B and A'
-      s.c.assign(1, S::one());
-      for (size_t i = 0; i + 1 < ell; i++) s.c.push_back(s.c[i] * s.factors[i]);
-      s.vec_c_blinders.resize(N_BLINDERS);
-      for (size_t i = 0; i < N_BLINDERS; i++) s.vec_c_blinders[i] = s.draw(ri.CB() + i);
-      s.c.insert(s.c.end(), s.vec_c_blinders.begin(), s.vec_c_blinders.end());
+      s.vec[V_C].assign(1, S::one());
+      for (size_t i = 0; i + 1 < ell; i++) s.vec[V_C].push_back(s.vec[V_C][i] * s.vec[V_FACT][i]);
+      s.vec[V_C].insert(s.vec[V_C].end(), &s.rnd[ri.CB()], &s.rnd[ri.CB()] + N_BLINDERS);   // vec_c_blinders
     });
   }
 
@@ -1242,72 +1241,58 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   // -- P2: B, A' = A + cm_T.T_1 + cm_U.T_1 (curdleproofs.rs:134) as a sum of three points of phase 1, and C = msm(G | Hvec, c)
   //    (grand_product_argument.rs:76).  The transcript takes B, draws alpha, then takes C: an order of hashing, not of computing.
   {
-    std::vector<TblReq> reqs;
-    for (size_t p = 0; p < B; p++) {
-      TblReq rb{cseg(cc.G_sum(), 1), st[p].scal[5].data(), pseg(p, row.M(), 1), st[p].scal[6].data(), slot_index(p, SL_B)};
-      rb.add[0] = slot_index(p, SL_A);
-      TblReq ra{none, nullptr, none, nullptr};
-      ra.add[0] = slot_index(p, SL_A);
-      ra.add[1] = slot_index(p, SL_CMT1);
-      ra.add[2] = slot_index(p, SL_CMU1);
-      reqs.push_back(rb);
-      reqs.push_back(ra);
-      reqs.push_back({cseg(0, (uint32_t)n), st[p].c.data(), none, nullptr});
-    }
+    const ReqList p2 = prove_phase2(ni, Li, false);
     CPX_HIP(hipStreamWaitEvent(stream_, tab_.ev_m, 0));   // M's table row (table stream)
-    run_tbl_phase(reqs, &comp);
+    run_tbl_phase(make_reqs(p2, scal), &comp);
     parallel_for(B, [&](size_t p) {
       ProverState& s = st[p];
-      take(p, SL_B, p * 3);
-      take(p, sm.APRIME(), p * 3 + 1);
-      take(p, SL_C, p * 3 + 2);
+      take(p, p2, comp.data());
       s.tr.append_point_bytes("gprod_step1", &s.comp[SL_B * 48]);
-      s.tr.append_scalar("gprod_step1", s.gprod);
-      s.alpha_g = s.tr.get_and_append_challenge("gprod_alpha");
+      s.tr.append_scalar("gprod_step1", s.sc[SC_GPROD]);
+      s.sc[SC_ALPHA_G] = s.tr.get_and_append_challenge("gprod_alpha");
       const S mb[4] = {S_from_wire(m_blinders + (p * 4 + 0) * 32), S_from_wire(m_blinders + (p * 4 + 1) * 32),
                        S_from_wire(m_blinders + (p * 4 + 2) * 32), S_from_wire(m_blinders + (p * 4 + 3) * 32)};
-      const S ab[4] = {s.draw(ri.AB()), s.draw(ri.AB() + 1), S::zero(), S::zero()};
+      const S* ab = &s.vec[V_APERM][ell];   // vec_a_blinders | 0 0
       s.rb_plus_alpha.resize(N_BLINDERS);
-      for (size_t i = 0; i < N_BLINDERS; i++) s.rb_plus_alpha[i] = (ab[i] + s.alpha_sp * mb[i]) + s.alpha_g;
-      s.r_p = host::inner_product(s.rb_plus_alpha.data(), s.vec_c_blinders.data(), N_BLINDERS);
+      for (size_t i = 0; i < N_BLINDERS; i++) s.rb_plus_alpha[i] = (ab[i] + s.sc[SC_ALPHA_SP] * mb[i]) + s.sc[SC_ALPHA_G];
+      s.sc[SC_RP] = host::inner_product(s.rb_plus_alpha.data(), &s.rnd[ri.CB()], N_BLINDERS);
       s.tr.append_point_bytes("gprod_step2", &s.comp[SL_C * 48]);
-      s.tr.append_scalar("gprod_step2", s.r_p);
-      s.beta_g = s.tr.get_and_append_challenge("gprod_beta");
-      s.beta_g_inv = s.beta_g.inverse();
-      s.u.resize(n);
-      S pw = s.beta_g_inv;
+      s.tr.append_scalar("gprod_step2", s.sc[SC_RP]);
+      s.sc[SC_BETA_G] = s.tr.get_and_append_challenge("gprod_beta");
+      s.sc[SC_BETA_G_INV] = s.sc[SC_BETA_G].inverse();
+      s.vec[V_U].resize(n);
+      S pw = s.sc[SC_BETA_G_INV];
       for (size_t i = 0; i < ell; i++) {
-        s.u[i] = pw;
-        pw *= s.beta_g_inv;
+        s.vec[V_U][i] = pw;
+        pw *= s.sc[SC_BETA_G_INV];
       }
-      for (size_t i = ell; i < n; i++) s.u[i] = pw;
-      s.d.resize(n);
-      S pb = s.beta_g, pbm = S::one();
+      for (size_t i = ell; i < n; i++) s.vec[V_U][i] = pw;
+      s.vec[V_D].resize(n);
+      S pb = s.sc[SC_BETA_G], pbm = S::one();
       for (size_t i = 0; i < ell; i++) {
-        s.d[i] = s.factors[i] * pb - pbm;
+        s.vec[V_D][i] = s.vec[V_FACT][i] * pb - pbm;
         pbm = pb;
-        pb *= s.beta_g;
+        pb *= s.sc[SC_BETA_G];
       }
-      const S beta_l1 = pbm * s.beta_g, beta_l = pbm;
-      for (size_t i = 0; i < N_BLINDERS; i++) s.d[ell + i] = beta_l1 * s.rb_plus_alpha[i];
-      s.z_ip = s.r_p * beta_l1 + s.gprod * beta_l - S::one();
+      const S beta_l1 = pbm * s.sc[SC_BETA_G], beta_l = pbm;
+      for (size_t i = 0; i < N_BLINDERS; i++) s.vec[V_D][ell + i] = beta_l1 * s.rb_plus_alpha[i];
+      s.sc[SC_ZIP] = s.sc[SC_RP] * beta_l1 + s.sc[SC_GPROD] * beta_l - S::one();
       // D = B - beta^-1 sum(G) + alpha sum(Hvec) (grand_product_argument.rs:132): the point B plus two single-point terms
-      s.scal[0] = {-s.beta_g_inv, s.alpha_g};
+      s.sc[SC_NEG_BETA_G_INV] = -s.sc[SC_BETA_G_INV];
       // generate_ipa_blinders (inner_product_argument.rs:42-82)
-      SVec r(n), zz(n);
-      for (size_t i = 0; i < n; i++) r[i] = s.draw(ri.IR() + i);
-      for (size_t i = 0; i + 2 < n; i++) zz[i] = s.draw(ri.IZ() + i);
-      const S omega = host::inner_product(r.data(), s.d.data(), n) + host::inner_product(zz.data(), s.c.data(), n - 2);
-      const S delta = host::inner_product(r.data(), zz.data(), n - 2);
-      const S inv_c = s.c[n - 2].inverse();
-      const S last_z = (r[n - 2] * inv_c * omega - delta) * ((-r[n - 2]) * inv_c * s.c[n - 1] + r[n - 1]).inverse();
-      const S pen_z = (-inv_c) * (last_z * s.c[n - 1] + omega);
+      const S* r = &s.rnd[ri.IR()];
+      SVec& zz = s.vec[V_ZZ];
+      zz.assign(&s.rnd[ri.IZ()], &s.rnd[ri.IZ()] + n - 2);
+      zz.resize(n);   // (the last two entries are solved for)
+      const S omega = host::inner_product(r, s.vec[V_D].data(), n) + host::inner_product(zz.data(), s.vec[V_C].data(), n - 2);
+      const S delta = host::inner_product(r, zz.data(), n - 2);
+      const S inv_c = s.vec[V_C][n - 2].inverse();
+      const S last_z = (r[n - 2] * inv_c * omega - delta) * ((-r[n - 2]) * inv_c * s.vec[V_C][n - 1] + r[n - 1]).inverse();
+      const S pen_z = (-inv_c) * (last_z * s.vec[V_C][n - 1] + omega);
       zz[n - 2] = pen_z;
       zz[n - 1] = last_z;
-      s.scal[1] = r;                                      // r_c -> B_c over G
-      s.scal[2] = zz;                                     // r_d
-      s.scal[3].resize(n);                                // B_d = msm(G', r_d) = msm(G, r_d o u)
-      for (size_t i = 0; i < n; i++) s.scal[3][i] = zz[i] * s.u[i];
+      s.vec[V_ZZU].resize(n);                             // B_d = msm(G', r_d) = msm(G, r_d o u)
+      for (size_t i = 0; i < n; i++) s.vec[V_ZZU][i] = zz[i] * s.vec[V_U][i];
     });
   }
 
@@ -1320,41 +1305,28 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   d_rbeta_.ensure(B);
   d_rout_.ensure(B * (2 * n + 2));
   {
-    std::vector<TblReq> reqs;
-    for (size_t p = 0; p < B; p++) {
-      ProverState& s = st[p];
-      TblReq rd{cseg(cc.G_sum(), 2), s.scal[0].data(), none, nullptr};   // G_sum, H_sum: adjacent columns of the CRS tables
-      rd.add[0] = slot_index(p, SL_B);
-      reqs.push_back(rd);
-      reqs.push_back({cseg(0, (uint32_t)n), s.scal[3].data(), none, nullptr});
-    }
-    run_tbl_phase(reqs, &comp);
+    const ReqList p3 = prove_phase3(ni, Li);
+    run_tbl_phase(make_reqs(p3, scal), &comp);
     parallel_for(B, [&](size_t p) {
       ProverState& s = st[p];
-      take(p, sm.D(), p * 2);
-      take(p, SL_BD, p * 2 + 1);
+      take(p, p3, comp.data());
       s.tr.append_point_bytes("ipa_step1", &s.comp[SL_C * 48]);
       s.tr.append_point_bytes("ipa_step1", &s.comp[sm.D() * 48]);
-      s.tr.append_scalar("ipa_step1", s.z_ip);
+      s.tr.append_scalar("ipa_step1", s.sc[SC_ZIP]);
       s.tr.append_point_bytes("ipa_step1", &s.comp[SL_BC * 48]);
       s.tr.append_point_bytes("ipa_step1", &s.comp[SL_BD * 48]);
-      s.alpha_i = s.tr.get_and_append_challenge("ipa_alpha");
-      s.beta_i = s.tr.get_and_append_challenge("ipa_beta");
-      for (size_t i = 0; i < n; i++) {
-        s.c[i] = s.scal[1][i] + s.alpha_i * s.c[i];
-        s.d[i] = s.scal[2][i] + s.alpha_i * s.d[i];
-      }
-      s.SG.assign(n, S::one());
-      s.SGp = s.u;
-      // the round vectors live on the device from here on: c | d | SG | SGp
+      s.sc[SC_ALPHA_I] = s.tr.get_and_append_challenge("ipa_alpha");
+      s.sc[SC_BETA_I] = s.tr.get_and_append_challenge("ipa_beta");
+      // the round vectors live on the device from here on: c | d | S_G | S_G' (inner_product_argument.rs:129-148; the fold coefficients
+      // start at 1 and at u)
       Fr* v = h_rvec_.p + p * 4 * n;
       for (size_t i = 0; i < n; i++) {
-        v[i] = s.c[i].f;
-        v[n + i] = s.d[i].f;
-        v[2 * n + i] = s.SG[i].f;
-        v[3 * n + i] = s.SGp[i].f;
+        v[i] = (s.rnd[ri.IR() + i] + s.sc[SC_ALPHA_I] * s.vec[V_C][i]).f;
+        v[n + i] = (s.vec[V_ZZ][i] + s.sc[SC_ALPHA_I] * s.vec[V_D][i]).f;
+        v[2 * n + i] = S::one().f;
+        v[3 * n + i] = s.vec[V_U][i].f;
       }
-      h_rgam_.p[p] = s.beta_i.f;
+      h_rgam_.p[p] = s.sc[SC_BETA_I].f;
     });
     CPX_HIP(hipMemcpyAsync(d_rvec_.p, h_rvec_.p, B * 4 * n * sizeof(Fr), hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(d_rbeta_.p, h_rgam_.p, B * sizeof(Fr), hipMemcpyHostToDevice, stream_));
@@ -1366,34 +1338,14 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   //    host hashes the four points of the round and returns gamma, gamma^-1.
   for (size_t j = 0; j < L; j++) {
     const size_t half = n >> (j + 1);
-    std::vector<uint32_t> hi, lo;
-    for (size_t k = 0; k < n; k++) ((k & half) ? hi : lo).push_back((uint32_t)k);
-    const uint32_t* d_hi = idx_list(hi);
-    const uint32_t* d_lo = idx_list(lo);
-    const size_t hn = n / 2, per = 4 * hn + 2;
+    const ReqList rd = prove_ipa_round(ni, Li, (int)j, false);
     launch_ipa_round_scalars(d_rvec_.p, (int)B, (int)n, (int)half, d_rbeta_.p, d_rout_.p, stream_);
-    std::vector<TblReq> reqs;
-    for (size_t p = 0; p < B; p++) {
-      const Fr* o = d_rout_.p + p * per;   // [L_C (hn), beta<c_L,d_R> | L_D (hn) | R_C (hn), beta<c_R,d_L> | R_D (hn)]
-      TblReq r0{cseg(0, (uint32_t)hn, d_hi), nullptr, cseg(0, 1, iH), nullptr};
-      r0.dev = o;
-      TblReq r1{cseg(0, (uint32_t)hn, d_lo), nullptr, none, nullptr};
-      r1.dev = o + hn + 1;
-      TblReq r2{cseg(0, (uint32_t)hn, d_lo), nullptr, cseg(0, 1, iH), nullptr};
-      r2.dev = o + 2 * hn + 1;
-      TblReq r3{cseg(0, (uint32_t)hn, d_hi), nullptr, none, nullptr};
-      r3.dev = o + 3 * hn + 2;
-      reqs.push_back(r0);
-      reqs.push_back(r1);
-      reqs.push_back(r2);
-      reqs.push_back(r3);
-    }
-    run_tbl_phase(reqs, &comp);
+    run_tbl_phase(make_reqs(rd, scal), &comp);
     parallel_for(B, [&](size_t p) {
       ProverState& s = st[p];
+      take(p, rd, comp.data());
       int order[4];
       sm.ipa_round((int)j, order);
-      for (int q = 0; q < 4; q++) take(p, order[q], p * 4 + q);
       for (int q : order) s.tr.append_point_bytes("ipa_loop", &s.comp[(size_t)q * 48]);
       const S gamma = s.tr.get_and_append_challenge("ipa_gamma");
       h_rgam_.p[2 * p] = gamma.f;
@@ -1421,20 +1373,17 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     CPX_HIP(hipStreamWaitEvent(stream_, tab_.ev_done, 0));
     parallel_for(B, [&](size_t p) {
       ProverState& s = st[p];
-      memcpy(&s.comp[(size_t)sm.BT() * 48], tab_.hcomp.p + (2 * p) * 48, 48);
-      memcpy(&s.comp[(size_t)sm.BU() * 48], tab_.hcomp.p + (2 * p + 1) * 48, 48);
-      memcpy(s.c_final.f.v, &h_rfin_.p[3 * p], sizeof(Fr));       // c[0], d[0] after the last fold (device-resident vectors)
-      memcpy(s.d_final.f.v, &h_rfin_.p[3 * p + 1], sizeof(Fr));
-      const int side_slots[6] = {SL_R, SL_S, SL_CMT2, SL_CMU2, sm.CMA2(), sm.CMB2()};
+      take(p, p1t, tab_.hcomp.p);   // B_t, B_u
+      memcpy(s.sc[SC_CFIN].f.v, &h_rfin_.p[3 * p], sizeof(Fr));       // c[0], d[0] after the last fold (device-resident vectors)
+      memcpy(s.sc[SC_DFIN].f.v, &h_rfin_.p[3 * p + 1], sizeof(Fr));
       for (int q : side_slots) memcpy(&s.comp[(size_t)q * 48], side_.hcomp.p + (p * (size_t)CWN + (q - CW0)) * 48, 48);
       int pts[10];
       sm.sameexp_points(pts);
       for (int q : pts) s.tr.append_point_bytes("sameexp_points", &s.comp[(size_t)q * 48]);
-      const S alpha = s.tr.get_and_append_challenge("same_scalar_alpha");
-      const S kk = S_from_wire(k_in + 32 * p);
-      s.z_k = s.draw(ri.RK()) + kk * alpha;
-      s.z_t = s.draw(ri.RA()) + s.draw(ri.RT()) * alpha;
-      s.z_u = s.draw(ri.RB()) + s.draw(ri.RU()) * alpha;
+      const S alpha = s.sc[SC_ALPHA_S] = s.tr.get_and_append_challenge("same_scalar_alpha");
+      s.sc[SC_ZK] = s.rnd[ri.RK()] + s.k * alpha;
+      s.sc[SC_ZT] = s.rnd[ri.RA()] + s.rnd[ri.RT()] * alpha;
+      s.sc[SC_ZU] = s.rnd[ri.RB()] + s.rnd[ri.RU()] * alpha;
       s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.APRIME() * 48]);
       s.tr.append_point_bytes("same_msm_step1", &s.comp[SL_CMT2 * 48]);
       s.tr.append_point_bytes("same_msm_step1", &s.comp[SL_CMU2 * 48]);
@@ -1451,18 +1400,14 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
       s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.BA() * 48]);
       s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.BT() * 48]);
       s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.BU() * 48]);
-      s.alpha_m = s.tr.get_and_append_challenge("same_msm_alpha");
-      s.x.resize(n);
-      for (size_t i = 0; i < ell; i++) s.x[i] = s.draw(ri.VR() + i) + s.alpha_m * s.a_perm[i];
-      s.x[ell] = s.draw(ri.VR() + ell) + s.alpha_m * s.draw(ri.AB());
-      s.x[ell + 1] = s.draw(ri.VR() + ell + 1) + s.alpha_m * s.draw(ri.AB() + 1);
-      s.x[ell + 2] = s.draw(ri.VR() + ell + 2) + s.alpha_m * s.draw(ri.RT());
-      s.x[ell + 3] = s.draw(ri.VR() + ell + 3) + s.alpha_m * s.draw(ri.RU());
-      s.SM.assign(n, S::one());
-      Fr* v = h_rvec_.p + p * 2 * n;   // device-resident round vectors: x | SM
+      s.sc[SC_ALPHA_M] = s.tr.get_and_append_challenge("same_msm_alpha");
+      // device-resident round vectors: the witness x = vec_r + alpha (a_sigma | a_blinders 0 0) with r_t, r_u on the last two bases
+      // (same_multiscalar_argument.rs:93-95, curdleproofs.rs:136-143) | the fold coefficients S_M, which start at 1
+      Fr* v = h_rvec_.p + p * 2 * n;
       for (size_t i = 0; i < n; i++) {
-        v[i] = s.x[i].f;
-        v[n + i] = s.SM[i].f;
+        const S& w = i + 2 < n ? s.vec[V_APERM][i] : s.rnd[i + 2 == n ? ri.RT() : ri.RU()];
+        v[i] = (s.rnd[ri.VR() + i] + s.sc[SC_ALPHA_M] * w).f;
+        v[n + i] = S::one().f;
       }
     });
     CPX_HIP(hipMemcpyAsync(d_rvec_.p, h_rvec_.p, B * 2 * n * sizeof(Fr), hipMemcpyHostToDevice, stream_));
@@ -1471,38 +1416,14 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   // -- P7: SameMSM rounds; the Fr side (cross-term scalars, fold of x, fold-coefficient update) on the device
   for (size_t j = 0; j < L; j++) {
     const size_t half = n >> (j + 1);
-    std::vector<uint32_t> hi, lo, ghi, glo;
-    for (size_t k = 0; k < n; k++) {
-      ((k & half) ? hi : lo).push_back((uint32_t)k);
-      ((k & half) ? ghi : glo).push_back(gb[k]);
-    }
-    const uint32_t* d_hi = idx_list(hi);
-    const uint32_t* d_lo = idx_list(lo);
-    const uint32_t* d_ghi = idx_list(ghi);
-    const uint32_t* d_glo = idx_list(glo);
-    const size_t hn = n / 2;
+    const ReqList rd = prove_smsm_round(ni, Li, (int)j);
     launch_smsm_round_scalars(d_rvec_.p, (int)B, (int)n, (int)half, d_rout_.p, stream_);
-    std::vector<TblReq> reqs;
-    for (size_t p = 0; p < B; p++) {
-      const Fr* oL = d_rout_.p + p * 2 * hn;   // [L_* scalars (hn) | R_* scalars (hn)]
-      const Fr* oR = oL + hn;
-      TblReq r[6] = {{cseg(0, (uint32_t)hn, d_ghi), nullptr, none, nullptr},       // L_A
-                     {pseg(p, row.T(), (uint32_t)hn, d_hi), nullptr, none, nullptr},   // L_T
-                     {pseg(p, row.U(), (uint32_t)hn, d_hi), nullptr, none, nullptr},   // L_U
-                     {cseg(0, (uint32_t)hn, d_glo), nullptr, none, nullptr},       // R_A
-                     {pseg(p, row.T(), (uint32_t)hn, d_lo), nullptr, none, nullptr},   // R_T
-                     {pseg(p, row.U(), (uint32_t)hn, d_lo), nullptr, none, nullptr}};  // R_U
-      for (int q = 0; q < 6; q++) {
-        r[q].dev = q < 3 ? oL : oR;
-        reqs.push_back(r[q]);
-      }
-    }
-    run_tbl_phase(reqs, &comp);
+    run_tbl_phase(make_reqs(rd, scal), &comp);
     parallel_for(B, [&](size_t p) {
       ProverState& s = st[p];
+      take(p, rd, comp.data());
       int order[6];
       sm.same_msm_round((int)j, order);
-      for (int i = 0; i < 6; i++) take(p, order[i], p * 6 + i);
       for (int q : order) s.tr.append_point_bytes("same_msm_loop", &s.comp[(size_t)q * 48]);
       const S gamma = s.tr.get_and_append_challenge("same_msm_gamma");
       h_rgam_.p[2 * p] = gamma.f;
@@ -1518,23 +1439,23 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
 
   if (opt_.trace) {
     const ProverState& s = st[0];
-    trace_scalar("beta_sp", s.beta_sp.f);
-    trace_scalar("alpha_sp", s.alpha_sp.f);
-    trace_scalar("-beta_g_inv", (-s.beta_g_inv).f);
-    trace_scalar("alpha_g", s.alpha_g.f);
-    trace_scalar("gprod", s.gprod.f);
-    trace_scalar("beta_g", s.beta_g.f);
-    trace_scalar("beta_g_inv", s.beta_g_inv.f);
-    trace_scalar("r_p", s.r_p.f);
-    trace_scalar("z_ip", s.z_ip.f);
-    trace_scalar("alpha_i", s.alpha_i.f);
-    trace_scalar("beta_i", s.beta_i.f);
-    trace_scalar("alpha_m", s.alpha_m.f);
-    trace_scalar("z_k", s.z_k.f);
-    trace_scalar("z_t", s.z_t.f);
-    trace_scalar("z_u", s.z_u.f);
-    trace_scalar("c_final", s.c_final.f);
-    trace_scalar("d_final", s.d_final.f);
+    trace_scalar("beta_sp", s.sc[SC_BETA_SP].f);
+    trace_scalar("alpha_sp", s.sc[SC_ALPHA_SP].f);
+    trace_scalar("-beta_g_inv", (-s.sc[SC_BETA_G_INV]).f);
+    trace_scalar("alpha_g", s.sc[SC_ALPHA_G].f);
+    trace_scalar("gprod", s.sc[SC_GPROD].f);
+    trace_scalar("beta_g", s.sc[SC_BETA_G].f);
+    trace_scalar("beta_g_inv", s.sc[SC_BETA_G_INV].f);
+    trace_scalar("r_p", s.sc[SC_RP].f);
+    trace_scalar("z_ip", s.sc[SC_ZIP].f);
+    trace_scalar("alpha_i", s.sc[SC_ALPHA_I].f);
+    trace_scalar("beta_i", s.sc[SC_BETA_I].f);
+    trace_scalar("alpha_m", s.sc[SC_ALPHA_M].f);
+    trace_scalar("z_k", s.sc[SC_ZK].f);
+    trace_scalar("z_t", s.sc[SC_ZT].f);
+    trace_scalar("z_u", s.sc[SC_ZU].f);
+    trace_scalar("c_final", s.sc[SC_CFIN].f);
+    trace_scalar("d_final", s.sc[SC_DFIN].f);
   }
   // -- serialise
   const ProofLayout pl(L);
@@ -1545,7 +1466,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     for (int q = 0; q < pl.n_points(); q++) memcpy(o + pl.point_offset(q), &s.comp[(size_t)(SL_A + q) * 48], 48);
     S xf;   // x[0] after the last fold (device-resident vector)
     memcpy(xf.f.v, &h_rfin_.p[3 * p + 2], sizeof(Fr));
-    const S* vals[ProofLayout::N_SCALARS] = {&s.r_p, &s.c_final, &s.d_final, &s.z_k, &s.z_t, &s.z_u, &xf};
+    const S* vals[ProofLayout::N_SCALARS] = {&s.sc[SC_RP], &s.sc[SC_CFIN], &s.sc[SC_DFIN], &s.sc[SC_ZK], &s.sc[SC_ZT], &s.sc[SC_ZU], &xf};
     for (int i = 0; i < ProofLayout::N_SCALARS; i++) vals[i]->to_le_bytes(o + pl.scalar_offset(i));
   });
   flush_timers();
@@ -1631,6 +1552,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
   }
 
   std::vector<uint8_t> comp;
+  const ReqList vreqs = verify_requests((int)n, (int)L);   // D, A'
 
   // -- V1a: transcript up to the grand-product beta
   parallel_for(B, [&](size_t p) { host::verify_prefix(st[p], ell, L, proofs + p * psz, &inst_comp[p * 4 * ell * 48], &mcomp[p * 48]); });
@@ -1646,26 +1568,20 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
   //    (curdleproofs.rs:258) are hashed into the transcript, so they are needed as bytes: sums of decompressed proof
   //    points plus two fixed-base terms (G_sum, H_sum are columns of the CRS tables)
   {
-    const TblSeg none{nullptr, nullptr, 0, 0};
-    std::vector<TblReq> reqs;
-    for (size_t p = 0; p < B; p++) {
-      TblReq rd{cseg(CtabCols(n).G_sum(), 2), st[p].scal[0].data() + 1, none, nullptr, slot_index(p, sm.D())};
-      rd.add[0] = slot_index(p, SL_B);
-      TblReq ra{none, nullptr, none, nullptr, slot_index(p, sm.APRIME())};
-      ra.add[0] = slot_index(p, SL_A);
-      ra.add[1] = slot_index(p, SL_CMT1);
-      ra.add[2] = slot_index(p, SL_CMU1);
-      reqs.push_back(rd);
-      reqs.push_back(ra);
-    }
-    run_tbl_phase(reqs, &comp);
+    // (after verify_prefix scal[0] holds the coefficients of D's three terms, 1 for the addend B first)
+    run_tbl_phase(make_reqs(vreqs, [&](size_t p, const ReqScal&) { return ScalAddr{st[p].scal[0].data() + 1, nullptr}; }), &comp);
   }
 
   // -- V1c: rest of the transcript and the scalars of the accumulated check; its "misc" part runs over the CRS singles, M and every
   //    proof point: the slots 0 .. NM
   const size_t NM = (size_t)SL_A + NPP;
+  auto comp_of = [&](size_t p, int slot) -> const uint8_t* {   // the bytes of the request whose output is `slot`
+    for (int i = 0; i < vreqs.n; i++)
+      if (vreqs.r[i].out == slot) return &comp[(p * (size_t)vreqs.n + i) * 48];
+    throw std::logic_error("no verifier request writes this slot");
+  };
   parallel_for(B, [&](size_t p) {
-    host::verify_scalars(st[p], ell, L, &inst_comp[p * 4 * ell * 48], crs_H_comp_, &comp[(p * 2) * 48], &comp[(p * 2 + 1) * 48], rand + p * rand_stride * 32,
+    host::verify_scalars(st[p], ell, L, &inst_comp[p * 4 * ell * 48], crs_H_comp_, comp_of(p, sm.D()), comp_of(p, sm.APRIME()), rand + p * rand_stride * 32,
                          fused_partial != nullptr);
   });
 

@@ -24,6 +24,7 @@
 #include "host_threads.hpp"
 #include "kernels.h"
 #include "protocol.h"
+#include "prove_reqs.hpp"
 #include "shuffle_plan.hpp"
 #include "tbl_plan.hpp"
 
@@ -393,7 +394,17 @@ class Engine {
   DevVerifier dverify_;
   void prepare_device_verifier(size_t rand_stride);
   void verify_core_device(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid);
-  void build_plan(TblPlan& pl, const std::vector<TblReq>& reqs, const std::vector<uint32_t>& comp_index);
+  // Where the scalars of a request are: the ONE thing the host-driven and the device-resident path answer differently (prove_reqs.hpp).
+  // Staged host scalars (uploaded with the phase) or device memory; the rows of round scalars are d_rout_ on both paths (make_reqs).
+  struct ScalAddr {
+    const host::S* host = nullptr;
+    const Fr* dev = nullptr;
+  };
+  using ScalAt = std::function<ScalAddr(size_t p, const ReqScal& sc)>;
+  // the requests of `list` for every loaded proof, proof by proof: segments, kept point, addends and scalars resolved to addresses;
+  // comp_index (optional): the slot of the registry [B][SlotMap::count()] that receives a request's compressed bytes
+  std::vector<TblReq> make_reqs(const ReqList& list, const ScalAt& scal_at, std::vector<uint32_t>* comp_index = nullptr);
+  void build_plan(TblPlan& pl, const ReqList& list, const ScalAt& scal_at);
   void exec_plan(const TblPlan& pl, uint8_t* d_comp_registry, bool on_table_stream = false);
   // the launches of one table-backed phase (fixed-base kernel, table kernel, reduction, k_finalize_ranges) on stream `st` in scratch `sc`;
   // timed = false: none of them enters the statistics

@@ -16,11 +16,13 @@
 namespace cpx {
 
 // ---------------------------------------------------------------- plans
-// Layout of a table-backed MSM phase whose requests all read device-resident scalars (TblReq::dev), by the planner of tbl_plan.hpp;
-// the launches (Engine::launch_tbl_phase) scatter the affine point (TblReq::dst) and write the compressed bytes to slot
-// `comp_index[i]` of the registry.
-void Engine::build_plan(TblPlan& pl, const std::vector<TblReq>& reqs, const std::vector<uint32_t>& comp_index) {
+// Layout of a table-backed MSM phase — the requests of `list` (prove_reqs.hpp) for every proof — whose requests all read device-resident
+// scalars (TblReq::dev), by the planner of tbl_plan.hpp; the launches (Engine::launch_tbl_phase) scatter the affine point (TblReq::dst)
+// and write the compressed bytes to the request's slot of the registry.
+void Engine::build_plan(TblPlan& pl, const ReqList& list, const ScalAt& scal_at) {
   if (!(fix_bits_ && fixtab())) throw std::logic_error("set_crs first");
+  std::vector<uint32_t> comp_index;
+  const std::vector<TblReq> reqs = make_reqs(list, scal_at, &comp_index);
   for (const TblReq& r : reqs)
     if (!r.dev && (r.seg0.n || r.seg1.n)) throw std::logic_error("device plan: request without device scalars");
   const CrsRange crs{ctab(), ctab() + (size_t)copies_ * nc()};
@@ -164,23 +166,13 @@ void Engine::prepare_device_prover() {
   memcpy(d.crs_h_comp, crs_H_comp_, 48);
 
   auto rnd = [&](size_t p, int i) { return dp.rnd.p + p * nrand + i; };
-  auto vec = [&](size_t p, int v) { return dp.vec.p + (p * V_COUNT + v) * n; };
-  auto sc = [&](size_t p, int i) { return dp.sc.p + p * SC_COUNT + i; };
-  auto cidx = [&](size_t p, int slot) { return (uint32_t)(p * NS + slot); };
-  const uint32_t* iH = idx_list({(uint32_t)cc.H()});
-  const uint32_t* iGt = idx_list({(uint32_t)cc.G_t()});
-  const uint32_t* iGu = idx_list({(uint32_t)cc.G_u()});
-  std::vector<uint32_t> gb(n);
-  cc.same_msm_basis(gb.data());
-  const uint32_t* iGb = idx_list(gb);
-  const TblSeg none{nullptr, nullptr, 0, 0};
-  auto req = [&](TblSeg s0, TblSeg s1, const Fr* dev, uint32_t dst = ~0u) {
-    TblReq r{s0, nullptr, s1, nullptr, dst};
-    r.dev = dev;
-    return r;
+  // where the prover's kernels (protocol.hip) leave the scalars of a request
+  const ScalAt scal = [&](size_t p, const ReqScal& sc) {
+    const Fr* at = sc.kind == SCAL_RAND ? rnd(p, sc.at) : sc.kind == SCAL_VEC ? dp.vec.p + (p * V_COUNT + sc.at) * n : dp.sc.p + p * SC_COUNT + sc.at;
+    return ScalAddr{nullptr, at};
   };
-  std::vector<TblReq> reqs;
-  std::vector<uint32_t> ci;
+  auto cidx = [&](size_t p, int slot) { return (uint32_t)(p * NS + slot); };
+  const int ni = (int)n, Li = (int)L;
 
   // mdst: where the affine M of proof p goes (table source slot 0)
   {
@@ -189,7 +181,6 @@ void Engine::prepare_device_prover() {
     CPX_HIP(hipMemcpy(dp.mdst.p, md.data(), B * 4, hipMemcpyHostToDevice));
   }
   // (decided before the plans are laid out: the phases of a small batch differ, too)
-  const size_t hn = n / 2, per = 4 * hn + 2;
   // the last log2(m) rounds of a large batch work on m materialised folded bases per family instead (late.hip): m = 16 (four rounds) up to
   // n = 256; an all-MSM round of n = 512 / 1024 costs two / four times as much, while materialising costs the same whatever m (every base
   // is visited once) and a late round 32 x (4 + m) operations per cross term: m = 32 (five rounds) pays there — measured per pass of 2048
@@ -222,91 +213,26 @@ void Engine::prepare_device_prover() {
   dp.fused_smsm = dp.fused_smsm && round_fused_supported(f_fix_smsm, f_tbl_smsm, false);
   // -- phase 1: everything that depends only on vec_a and the prover's randomness (curdleproofs.rs:93,110-116,
   //    same_multiscalar_argument.rs:80 (B_a; B_t and B_u are phase 1t), inner_product_argument.rs:126, same_scalar_argument.rs:60-61).
-  for (size_t p = 0; p < B; p++) {
-    const int TMPX = sm.TMP(6);   // compressed bytes nobody reads
-    if (!opt_.p1_split) {
-      reqs.push_back(req(cseg(0, (uint32_t)n), none, vec(p, V_APERM), slot_index(p, SL_A)));          // A
-      ci.push_back(cidx(p, SL_A));
-    }
-    reqs.push_back(req(cseg(0, (uint32_t)n, iGb), none, rnd(p, ri.VR())));                            // B_a
-    ci.push_back(cidx(p, sm.BA()));
-    reqs.push_back(req(cseg(0, (uint32_t)n), none, rnd(p, ri.IR())));                                 // B_c = msm(G | Hvec, r_c)
-    ci.push_back(cidx(p, SL_BC));
-    reqs.push_back(req(cseg(0, 1, iGt), none, rnd(p, ri.RT()), slot_index(p, SL_CMT1)));              // cm_T.T_1 = r_t G_t
-    ci.push_back(cidx(p, SL_CMT1));
-    reqs.push_back(req(cseg(0, 1, iGu), none, rnd(p, ri.RU()), slot_index(p, SL_CMU1)));              // cm_U.T_1
-    ci.push_back(cidx(p, SL_CMU1));
-    reqs.push_back(req(cseg(0, 1, iGt), none, rnd(p, ri.RA())));                                      // cm_A.T_1
-    ci.push_back(cidx(p, sm.CMA1()));
-    reqs.push_back(req(cseg(0, 1, iGu), none, rnd(p, ri.RB())));                                      // cm_B.T_1
-    ci.push_back(cidx(p, sm.CMB1()));
-    const int rs[4] = {ri.RT(), ri.RU(), ri.RA(), ri.RB()};                                           // r * H halves of the four T_2 commitments
-    for (int q = 0; q < 4; q++) {
-      reqs.push_back(req(cseg(0, 1, iH), none, rnd(p, rs[q]), slot_index(p, sm.TMP(q))));
-      ci.push_back(cidx(p, TMPX));
-    }
-  }
-  build_plan(dp.p1, reqs, ci);
+  //    Without the option p1_split, A (phase 1b) leads the phase.
+  build_plan(dp.p1, opt_.p1_split ? prove_phase1(ni, Li) : prove_phase1b(ni, Li).then(prove_phase1(ni, Li)), scal);
   // -- phase 1t: B_t = msm(T_b, r), B_u = msm(U_b, r) (same_multiscalar_argument.rs:81-82) — the two commitments of phase 1 over the
   //    per-proof tables.  Nothing reads them before the SameMSM transcript step: they follow the table build on the table stream, and
   //    the main stream goes on with the CRS-only commitments at once
-  reqs.clear();
-  ci.clear();
-  for (size_t p = 0; p < B; p++) {
-    reqs.push_back(req(pseg(p, row.T(), (uint32_t)n), none, rnd(p, ri.VR())));
-    ci.push_back(cidx(p, sm.BT()));
-    reqs.push_back(req(pseg(p, row.U(), (uint32_t)n), none, rnd(p, ri.VR())));
-    ci.push_back(cidx(p, sm.BU()));
-  }
   dp.p1t.table_stream = true;
-  build_plan(dp.p1t, reqs, ci);
+  build_plan(dp.p1t, prove_phase1t(ni, Li), scal);
   tab_.scr.ensure(dp.p1t.fix_sets + dp.p1t.tbl_sets, dp.p1t.nparts);
   // -- phase 1b (option p1_split): A = msm(G | Hvec, a_sigma | blinders) (curdleproofs.rs:93) alone — the one commitment of phase 1
   //    that needs vec_a; the rest of the phase then runs before the main stream waits for the transcript prefix
-  reqs.clear();
-  ci.clear();
-  if (opt_.p1_split)
-    for (size_t p = 0; p < B; p++) {
-      reqs.push_back(req(cseg(0, (uint32_t)n), none, vec(p, V_APERM), slot_index(p, SL_A)));
-      ci.push_back(cidx(p, SL_A));
-    }
-  build_plan(dp.p1b, reqs, ci);
+  build_plan(dp.p1b, opt_.p1_split ? prove_phase1b(ni, Li) : ReqList(), scal);
   // -- phase 2: B = A + alpha M + beta sum(G) (same_permutation_argument.rs:75-76), A' = A + cm_T.T_1 + cm_U.T_1
-  //    (curdleproofs.rs:134), C = msm(G | Hvec, c) (grand_product_argument.rs:76)
-  reqs.clear();
-  ci.clear();
-  for (size_t p = 0; p < B; p++) {
-    // B.  Large batches: A + alpha M + beta sum(G) — two points and an addend.  Fused / small batches: the commitment the reference computes,
-    // msm(G | Hvec, a_sigma + alpha sigma + beta | a_blinders + alpha m_blinders) (same_permutation_argument.rs:75-76; the scalars are the
-    // grand-product factors k_ps_sameperm leaves in V_FACT) — a 256-point task of the fixed-base kernel like C beside it, instead of a
-    // one-point task of the bucket-list kernel whose 32 bucket sets per proof cost the phase 0.5 ms of reductions at 128 proofs
-    TblReq rb = dp.fused_smsm ? req(cseg(0, (uint32_t)n), none, vec(p, V_FACT), slot_index(p, SL_B))
-                         : req(cseg(cc.G_sum(), 1), pseg(p, row.M(), 1), sc(p, SC_BETA_SP), slot_index(p, SL_B));
-    if (!dp.fused_smsm) rb.add[0] = slot_index(p, SL_A);
-    reqs.push_back(rb);
-    ci.push_back(cidx(p, SL_B));
-    TblReq ra = req(none, none, nullptr);
-    ra.add[0] = slot_index(p, SL_A);
-    ra.add[1] = slot_index(p, SL_CMT1);
-    ra.add[2] = slot_index(p, SL_CMU1);
-    reqs.push_back(ra);
-    ci.push_back(cidx(p, sm.APRIME()));
-    reqs.push_back(req(cseg(0, (uint32_t)n), none, vec(p, V_C)));
-    ci.push_back(cidx(p, SL_C));
-  }
-  build_plan(dp.p2, reqs, ci);
+  //    (curdleproofs.rs:134), C = msm(G | Hvec, c) (grand_product_argument.rs:76).
+  //    B.  Large batches: A + alpha M + beta sum(G) — two points and an addend.  Fused / small batches: the commitment the reference computes,
+  //    msm(G | Hvec, a_sigma + alpha sigma + beta | a_blinders + alpha m_blinders) (same_permutation_argument.rs:75-76; the scalars are the
+  //    grand-product factors k_ps_sameperm leaves in V_FACT) — a 256-point task of the fixed-base kernel like C beside it, instead of a
+  //    one-point task of the bucket-list kernel whose 32 bucket sets per proof cost the phase 0.5 ms of reductions at 128 proofs
+  build_plan(dp.p2, prove_phase2(ni, Li, dp.fused_smsm), scal);
   // -- phase 3: D = B - beta^-1 sum(G) + alpha sum(H) (grand_product_argument.rs:132), B_d = msm(G', r_d) = msm(G, r_d o u)
-  reqs.clear();
-  ci.clear();
-  for (size_t p = 0; p < B; p++) {
-    TblReq rd = req(cseg(cc.G_sum(), 2), none, sc(p, SC_NEG_BETA_G_INV));
-    rd.add[0] = slot_index(p, SL_B);
-    reqs.push_back(rd);
-    ci.push_back(cidx(p, sm.D()));
-    reqs.push_back(req(cseg(0, (uint32_t)n), none, vec(p, V_ZZU)));
-    ci.push_back(cidx(p, SL_BD));
-  }
-  build_plan(dp.p3, reqs, ci);
+  build_plan(dp.p3, prove_phase3(ni, Li), scal);
   // -- IPA rounds as MSMs over the original bases; scalars from k_ipa_round_scalars
   dp.ipa.clear();
   dp.smsm.clear();
@@ -316,62 +242,14 @@ void Engine::prepare_device_prover() {
       dp.smsm.emplace_back(nullptr);
       continue;
     }
-    const size_t half = n >> (j + 1);
-    std::vector<uint32_t> hi, lo, ghi, glo;
-    for (size_t k = 0; k < n; k++) {
-      ((k & half) ? hi : lo).push_back((uint32_t)k);
-      ((k & half) ? ghi : glo).push_back(gb[k]);
-    }
-    const uint32_t *d_hi = idx_list(hi), *d_lo = idx_list(lo), *d_ghi = idx_list(ghi), *d_glo = idx_list(glo);
     // (fused rounds: the H term of L_C / R_C rides in the same fixed-base task as the n/2 bases — one more column of the gather list, the
     // scalar beta <c, d> follows the n/2 cross-term scalars in memory anyway — instead of a one-point task of its own: 4 tasks per proof)
-    const uint32_t *d_hiH = nullptr, *d_loH = nullptr;
-    if (dp.fused) {
-      std::vector<uint32_t> hiH(hi), loH(lo);
-      hiH.push_back((uint32_t)cc.H());
-      loH.push_back((uint32_t)cc.H());
-      d_hiH = idx_list(hiH);
-      d_loH = idx_list(loH);
-    }
-    reqs.clear();
-    ci.clear();
-    for (size_t p = 0; p < B; p++) {
-      const Fr* o = d_rout_.p + p * per;   // [L_C (hn), beta<c_L,d_R> | L_D (hn) | R_C (hn), beta<c_R,d_L> | R_D (hn)]
-      if (dp.fused) reqs.push_back(req(cseg(0, (uint32_t)hn + 1, d_hiH), none, o));
-      else reqs.push_back(req(cseg(0, (uint32_t)hn, d_hi), cseg(0, 1, iH), o));
-      ci.push_back(cidx(p, sm.LC((int)j)));
-      reqs.push_back(req(cseg(0, (uint32_t)hn, d_lo), none, o + hn + 1));
-      ci.push_back(cidx(p, sm.LD((int)j)));
-      if (dp.fused) reqs.push_back(req(cseg(0, (uint32_t)hn + 1, d_loH), none, o + 2 * hn + 1));
-      else reqs.push_back(req(cseg(0, (uint32_t)hn, d_lo), cseg(0, 1, iH), o + 2 * hn + 1));
-      ci.push_back(cidx(p, sm.RC((int)j)));
-      reqs.push_back(req(cseg(0, (uint32_t)hn, d_hi), none, o + 3 * hn + 2));
-      ci.push_back(cidx(p, sm.RD((int)j)));
-    }
     dp.ipa.emplace_back(new TblPlan());
     if (dp.fused) {
       dp.ipa.back()->keep_order = true;
       dp.ipa.back()->force_fix_wpw = f_fix_ipa;
     }
-    build_plan(*dp.ipa.back(), reqs, ci);
-    reqs.clear();
-    ci.clear();
-    for (size_t p = 0; p < B; p++) {
-      const Fr* oL = d_rout_.p + p * 2 * hn;   // [L_* scalars (hn) | R_* scalars (hn)]
-      const Fr* oR = oL + hn;
-      reqs.push_back(req(cseg(0, (uint32_t)hn, d_ghi), none, oL));
-      ci.push_back(cidx(p, sm.LA((int)j)));
-      reqs.push_back(req(pseg(p, row.T(), (uint32_t)hn, d_hi), none, oL));
-      ci.push_back(cidx(p, sm.LT((int)j)));
-      reqs.push_back(req(pseg(p, row.U(), (uint32_t)hn, d_hi), none, oL));
-      ci.push_back(cidx(p, sm.LU((int)j)));
-      reqs.push_back(req(cseg(0, (uint32_t)hn, d_glo), none, oR));
-      ci.push_back(cidx(p, sm.RA((int)j)));
-      reqs.push_back(req(pseg(p, row.T(), (uint32_t)hn, d_lo), none, oR));
-      ci.push_back(cidx(p, sm.RT((int)j)));
-      reqs.push_back(req(pseg(p, row.U(), (uint32_t)hn, d_lo), none, oR));
-      ci.push_back(cidx(p, sm.RU((int)j)));
-    }
+    build_plan(*dp.ipa.back(), prove_ipa_round(ni, Li, (int)j, dp.fused), scal);
     dp.smsm.emplace_back(new TblPlan());
     if (dp.fused_smsm) {
       dp.smsm.back()->keep_order = true;
@@ -379,15 +257,17 @@ void Engine::prepare_device_prover() {
       dp.smsm.back()->force_fix_wpw = f_fix_smsm;
       dp.smsm.back()->force_tbl_wpw = f_tbl_smsm;
     }
-    build_plan(*dp.smsm.back(), reqs, ci);
+    build_plan(*dp.smsm.back(), prove_smsm_round(ni, Li, (int)j), scal);
   }
   if (lt.on) {
     const int m = lt.m, hm = m / 2;
     const size_t BM = B * (size_t)m, ent = late_tab_entries();
     lt.jac.ensure((size_t)LATE_FAMILIES * BM);
     lt.tab.ensure((size_t)LATE_FAMILIES * BM * ent);
-    lt.gb_cols = iGb;
-    lt.h_col = iH;
+    std::vector<uint32_t> gb(n);
+    cc.same_msm_basis(gb.data());
+    lt.gb_cols = idx_list(gb);
+    lt.h_col = idx_list({(uint32_t)cc.H()});
     lt.part.ensure(6 * B * (size_t)opt_.late_slices);
     lt.extra.ensure(4 * B);
     CPX_HIP(hipMemsetAsync(lt.extra.p, 0, 4 * B * sizeof(TJac), stream_));   // all-zero = the identity: the outputs without a CRS term keep it (ordered before the prove's launches on this stream)
@@ -460,7 +340,9 @@ void Engine::prepare_device_prover() {
     CPX_HIP(hipMemcpy(side_.tasks.p, mt.data(), mt.size() * sizeof(MsmTask), hipMemcpyHostToDevice));
     CPX_HIP(hipMemcpy(side_.dst.p, md.data(), md.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     CPX_HIP(hipMemcpy(side_.stasks.p, st.data(), st.size() * sizeof(SmulTask), hipMemcpyHostToDevice));
-    dp.side_cols = idx_list({(uint32_t)SL_R, (uint32_t)SL_S, (uint32_t)SL_CMT2, (uint32_t)SL_CMU2, (uint32_t)sm.CMA2(), (uint32_t)sm.CMB2()});
+    int side[6];
+    side_stream_slots(Li, side);
+    dp.side_cols = idx_list(std::vector<uint32_t>(side, side + 6));
   }
   if (!tab_.dstream) CPX_HIP(hipStreamCreateWithFlags(&tab_.dstream, hipStreamNonBlocking));
   if (!dp.ev_t1) {
@@ -808,25 +690,7 @@ void Engine::prepare_device_verifier(size_t rand_stride) {
   CPX_HIP(hipMemcpy(dv.mdst.p, md.data(), md.size() * 4, hipMemcpyHostToDevice));
   // D = B - beta^-1 sum(G) + alpha sum(H) (grand_product_argument.rs:223) and A' = A + cm_T.T_1 + cm_U.T_1 (curdleproofs.rs:258)
   // are hashed into the transcript, so they are needed as bytes
-  {
-    const TblSeg none{nullptr, nullptr, 0, 0};
-    std::vector<TblReq> reqs;
-    std::vector<uint32_t> ci;
-    for (size_t p = 0; p < B; p++) {
-      TblReq rd{cseg(CtabCols(n).G_sum(), 2), nullptr, none, nullptr, slot_index(p, sm.D())};
-      rd.dev = dv.vsc.p + p * VSC_COUNT + VSC_NEG_BETA_G_INV;
-      rd.add[0] = slot_index(p, SL_B);
-      TblReq ra{none, nullptr, none, nullptr, slot_index(p, sm.APRIME())};
-      ra.add[0] = slot_index(p, SL_A);
-      ra.add[1] = slot_index(p, SL_CMT1);
-      ra.add[2] = slot_index(p, SL_CMU1);
-      reqs.push_back(rd);
-      ci.push_back((uint32_t)(p * NS + sm.D()));
-      reqs.push_back(ra);
-      ci.push_back((uint32_t)(p * NS + sm.APRIME()));
-    }
-    build_plan(dv.pd, reqs, ci);
-  }
+  build_plan(dv.pd, verify_requests((int)n, (int)L), [&](size_t p, const ReqScal& sc) { return ScalAddr{nullptr, dv.vsc.p + p * VSC_COUNT + sc.at}; });
   // the accumulated check: per proof one fixed-base task over G | Hvec and one bucket MSM over R | S | T | U and the misc slots
   std::vector<uint32_t> all_idx(NPT);   // row-relative gather list
   for (size_t i = 0; i < NI; i++) all_idx[i] = (uint32_t)i;

@@ -1,6 +1,7 @@
 // Index layouts shared by the host-driven protocol (engine.cpp), the device-resident one (engine_device.cpp, protocol.hip) and
 // the host-only test build: the per-proof point registry, the wire format of a proof, the prover's random draws, the row of a
 // proof's point table, the columns of the CRS tables and the verifier's random factors.  Plain index arithmetic, no HIP.
+// prove_reqs.hpp states the protocol's MSM requests in these names.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,7 +1,8 @@
 // Planner of a table-backed MSM phase — host code without a HIP call: turns a list of requests into the task descriptors of
 // k_msm_fix (CRS segments) and k_msm_tblw (per-proof segments) and the per-request ranges k_finalize_ranges adds up.  One definition
 // for the host-driven phases (Engine::run_tbl_phase, the table stream of batch_prove_tables) and the device-resident plans
-// (Engine::build_plan); tests/test_tbl_plan_cpu.py compiles it for the CPU.
+// (Engine::build_plan); tests/test_tbl_plan_cpu.py compiles it for the CPU.  WHICH requests the protocol makes is written down in
+// prove_reqs.hpp; Engine::make_reqs turns those descriptors into the TblReq below.
 #pragma once
 #include <algorithm>
 #include <vector>
