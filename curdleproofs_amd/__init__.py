@@ -57,7 +57,7 @@ _libs = {}   # realpath -> loaded library (the default one and build variants fo
 
 EXPORTS = [
     "cpx_host_alloc", "cpx_host_free", "cpx_ctx_create", "cpx_ctx_destroy", "cpx_last_error", "cpx_device_count", "cpx_ctx_set_option", "cpx_ctx_get_option", "cpx_ctx_set_crs", "cpx_crs_sums", "cpx_proof_size", "cpx_batch_size",
-    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_normalize", "cpx_g1_decompress", "cpx_g1_decompress_status",
+    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_g1_normalize", "cpx_g1_decompress", "cpx_g1_decompress_status",
     "cpx_accum_new", "cpx_accum_free", "cpx_accum_check", "cpx_accum_verify",
     "cpx_batch_load", "cpx_batch_load_begin", "cpx_batch_load_end", "cpx_batch_prove", "cpx_batch_verify", "cpx_batch_verify_fused", "cpx_g1_sum_jac",
     "cpx_whisk_generate_shuffle_proof", "cpx_whisk_is_valid_shuffle_proof", "cpx_whisk_generate_tracker_proof", "cpx_whisk_is_valid_tracker_proof",
@@ -105,6 +105,8 @@ def load_library(path=None):
     L.cpx_g1_msm_jac.argtypes = [vp, vp, vp, sz, vp]
     L.cpx_g1_fold.argtypes = [vp, vp, vp, vp, sz]
     L.cpx_g1_scale.argtypes = [vp, vp, vp, sz, sz, vp]
+    L.cpx_g1_msm_many.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.cpx_g1_fold_many.argtypes = [vp, sz, sz, vp, vp, vp]
     L.cpx_g1_normalize.argtypes = [vp, vp, sz, vp, vp]
     L.cpx_g1_decompress.argtypes = [vp, vp, sz, vp, ci]
     L.cpx_g1_decompress_status.argtypes = [vp, vp, sz, vp, ci, vp]
@@ -287,6 +289,49 @@ class Context:
         o = _out(AFF * n)
         self._check(self._L.cpx_g1_scale(self._h, _in(P), _in(scalars), stride, n, o))
         return bytes(o)[: AFF * n]
+
+    def msm_many(self, bases_list, scalars_list, compressed=False):
+        """util.rs:19-22 for every (bases, scalars) pair of the lists in ONE call (cpx_g1_msm_many: the cross terms of a log round,
+        inner_product_argument.rs:158-161, same_multiscalar_argument.rs:107-112); the lengths may differ, an empty pair gives the identity.
+        Returns the list of 144-byte Jacobian results, or (that list, the list of 48-byte encodings)."""
+        if len(bases_list) != len(scalars_list):
+            raise ValueError("msm_many: one scalar vector per base vector")
+        lens = []
+        for b, s in zip(bases_list, scalars_list):
+            n = len(s) // FR
+            if len(b) != AFF * n or len(s) != FR * n:
+                raise ValueError("number of points != number of scalars")
+            lens.append(n)
+        count = len(lens)
+        if not count:
+            return ([], []) if compressed else []
+        la = (ctypes.c_uint32 * count)(*lens)
+        o, c = _out(JAC * count), _out(48 * count)
+        self._check(self._L.cpx_g1_msm_many(self._h, count, la, _in(b"".join(bytes(b) for b in bases_list)), _in(b"".join(bytes(s) for s in scalars_list)),
+                                            o, c if compressed else None))
+        jac = [bytes(o)[JAC * i: JAC * (i + 1)] for i in range(count)]
+        return (jac, [bytes(c)[48 * i: 48 * (i + 1)] for i in range(count)]) if compressed else jac
+
+    def fold_many(self, PL_list, PR_list, gammas):
+        """PL[f][i] + gammas[f] * PR[f][i], affine, for every family f in ONE call (cpx_g1_fold_many: the basis folds of a log round,
+        inner_product_argument.rs:177-178, same_multiscalar_argument.rs:128-130).  Every vector holds the same number of points;
+        gammas: one 32-byte scalar per family (a list, or the scalars back to back).  Returns the list of folded vectors."""
+        if not isinstance(gammas, (bytes, bytearray)):
+            if any(len(g) != FR for g in gammas):
+                raise ValueError("fold_many: 32 bytes per gamma")
+            gammas = b"".join(bytes(g) for g in gammas)
+        families = len(PL_list)
+        if len(PR_list) != families or len(gammas) != FR * families:
+            raise ValueError("fold_many: one PR vector and one gamma per PL vector")
+        if not families:
+            return []
+        size = len(PL_list[0])
+        if size % AFF or any(len(v) != size for v in PL_list) or any(len(v) != size for v in PR_list):
+            raise ValueError("fold_many: every vector must hold the same number of affine points")
+        half = size // AFF
+        b = _in(b"".join(bytes(v) for v in PL_list))
+        self._check(self._L.cpx_g1_fold_many(self._h, families, half, b, _in(b"".join(bytes(v) for v in PR_list)), _in(gammas)))
+        return [bytes(b)[size * f: size * (f + 1)] for f in range(families)]
 
     def normalize(self, jac, compressed=False):
         n = len(jac) // JAC

@@ -193,6 +193,20 @@ int cpx_g1_scale(cpx_ctx* ctx, const uint8_t* P, const uint8_t* scalars, size_t 
     return CPX_OK;
   });
 }
+int cpx_g1_msm_many(cpx_ctx* ctx, size_t count, const uint32_t* lens, const uint8_t* bases, const uint8_t* scalars, uint8_t* out_jac, uint8_t* out_compressed) {
+  if (count && (!lens || !bases || !scalars)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->msm_many(count, lens, bases, scalars, out_jac, out_compressed);
+    return (int)CPX_OK;
+  });
+}
+int cpx_g1_fold_many(cpx_ctx* ctx, size_t families, size_t half, uint8_t* PL, const uint8_t* PR, const uint8_t* gammas) {
+  if (families && half && (!PL || !PR || !gammas)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->fold_many(families, half, PL, PR, gammas);
+    return (int)CPX_OK;
+  });
+}
 int cpx_g1_normalize(cpx_ctx* ctx, const uint8_t* jac, size_t n, uint8_t* out_affine, uint8_t* out_compressed) {
   if (n && !jac) return CPX_ERR_ARG;
   return guarded(ctx, [&] {

@@ -2,6 +2,7 @@
 // the group arithmetic exists here; every point operation below is a kernel launch (kernels.hip).
 #include "engine.hpp"
 #include "host_verify.hpp"
+#include "tier0_plan.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -790,6 +791,113 @@ void Engine::scale(const uint8_t* P, const uint8_t* scalars, size_t scalar_strid
   tier0_trim(dp);
   tier0_trim(dout);
   tier0_trim(dsc);
+}
+// The cross terms of one log round (inner_product_argument.rs:158-161: 4, same_multiscalar_argument.rs:107-112: 6) as ONE call: `count`
+// independent MSMs of ragged lengths, all of them tasks of the endomorphism bucket-list path in one launch each — k_to_table_endo +
+// k_msm_tblw<2, true> over count tasks, k_reduce_sets over their count * 32 * slices bucket sets, k_msm_tail with one output per task,
+// k_finalize for the compressed form — between one upload and one download, with one stream synchronisation whatever the count.  Where
+// every task lives in the scratch is written down in tier0_plan.hpp; option msm_endo_min is not consulted (the windowed accumulation
+// has no place in a call whose point is the shared launch).
+void Engine::msm_many(size_t count, const uint32_t* lens, const uint8_t* bases, const uint8_t* scalars, uint8_t* out_jac, uint8_t* out_comp) {
+  if (!count) return;
+  Tier0MsmPlan pl;
+  if (!tier0_msm_plan(count, lens, pl)) throw ArgError("cpx_g1_msm_many: at most 2^16 MSMs and 2^24 points per call");
+  if (!out_jac && !out_comp) return;
+  CPX_HIP(hipSetDevice(device_));
+  pl.slices = msm_tblw_slices(opt_, (int)count, 2, (int)pl.max_n);   // one value for every task of the call
+  DevBuf<Aff>&db = t0_.a0, &daff = t0_.a1;
+  DevBuf<Fr>& ds = t0_.fr;
+  DevBuf<MsmTask>& dt = t0_.mtask;
+  DevBuf<TblTask>& tt = t0_.ttask;
+  DevBuf<TAff>& conv = t0_.conv;
+  DevBuf<uint32_t>& dig = t0_.dig;
+  DevBuf<TJac>& part = t0_.part;
+  DevBuf<Jac>& res = t0_.res;
+  DevBuf<uint8_t>& dcomp = t0_.bytes;
+  struct Trim {
+    Engine* e;
+    ~Trim() {
+      tier0_trim(e->t0_.a0);
+      tier0_trim(e->t0_.a1);
+      tier0_trim(e->t0_.fr);
+      tier0_trim(e->t0_.conv);
+      tier0_trim(e->t0_.dig);
+      tier0_trim(e->t0_.part);
+      tier0_trim(e->t0_.bytes);
+    }
+  } trim{this};
+  const size_t np = pl.points;
+  db.ensure(std::max<size_t>(np, 1));
+  ds.ensure(std::max<size_t>(np, 1));
+  dt.ensure(count);
+  tt.ensure(count);
+  conv.ensure(std::max<size_t>(pl.conv_entries(), 1));
+  dig.ensure(std::max<size_t>(pl.digit_words(), 1));
+  part.ensure(pl.sets());
+  res.ensure(count);
+  main_.ensure(pl.sets(), 0);
+  std::vector<MsmTask> tasks(count);   // (alive until the synchronisation below)
+  for (size_t i = 0; i < count; i++) tasks[i] = MsmTask{db.p + pl.conv_off[i], nullptr, ds.p + pl.conv_off[i], lens[i], 0, pl.conv_off[i]};
+  if (np) {
+    CPX_HIP(hipMemcpyAsync(db.p, bases, np * sizeof(Aff), hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(ds.p, scalars, np * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  }
+  CPX_HIP(hipMemcpyAsync(dt.p, tasks.data(), count * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+  tick("k_msm_tblw<2, true>", 128.0 * np, (double)np);
+  launch_msm_endo(dt.p, (int)count, (int)pl.max_n, conv.p, dig.p, tt.p, main_.raw.p, main_.rawslot.p, stream_, pl.slices);
+  tock();
+  reduce_sets(stream_, main_, 0, pl.sets(), part.p);
+  tick("k_msm_tail", 0, (double)count);
+  launch_msm_tail(opt_, part.p, nullptr, res.p, (int)count, 16, 8, stream_, nullptr, 0, pl.tail_dup());
+  tock();
+  if (out_jac) CPX_HIP(hipMemcpyAsync(out_jac, res.p, count * sizeof(Jac), hipMemcpyDeviceToHost, stream_));
+  if (out_comp) {
+    daff.ensure(count);
+    dcomp.ensure(count * 48);
+    tick("k_finalize", 0, (double)count);
+    launch_finalize(res.p, (int)count, daff.p, nullptr, dcomp.p, stream_);
+    tock();
+    CPX_HIP(hipMemcpyAsync(out_comp, dcomp.p, count * 48, hipMemcpyDeviceToHost, stream_));
+  }
+  CPX_HIP(hipStreamSynchronize(stream_));   // the results are in the caller's buffers; the scratch may be reused by the next call
+  flush_timers();
+}
+// The basis folds of one log round (inner_product_argument.rs:177-178: 2 families, same_multiscalar_argument.rs:128-130: 3) as ONE call:
+// a SmulTask per family, each with its own gamma shared by its `half` elements, in one launch_smul.  A round's folds are small (3 x 128
+// elements at ell = 252), so up to option fold_quad_max elements the launch takes the quad-per-element form (tier0_plan.hpp).
+void Engine::fold_many(size_t families, size_t half, uint8_t* PL, const uint8_t* PR, const uint8_t* gammas) {
+  if (!families || !half) return;
+  if (!tier0_fold_fits(families, half)) throw ArgError("cpx_g1_fold_many: at most 2^24 elements per call");
+  CPX_HIP(hipSetDevice(device_));
+  const size_t total = families * half;
+  DevBuf<Aff>&dl = t0_.a0, &dr = t0_.a1;
+  DevBuf<Fr>& dg = t0_.fr;
+  DevBuf<SmulTask>& dt = t0_.stask;
+  struct Trim {
+    Engine* e;
+    ~Trim() {
+      tier0_trim(e->t0_.a0);
+      tier0_trim(e->t0_.a1);
+      tier0_trim(e->t0_.fr);
+    }
+  } trim{this};
+  dl.ensure(total);
+  dr.ensure(total);
+  dg.ensure(families);
+  dt.ensure(families);
+  const bool plain = opt_.scale_any_point != 0;
+  std::vector<SmulTask> tasks(families);   // (alive until the synchronisation below)
+  for (size_t f = 0; f < families; f++) tasks[f] = SmulTask{dl.p + f * half, dr.p + f * half, dl.p + f * half, dg.p + f, 0, plain ? SMUL_PLAIN : 0u};
+  CPX_HIP(hipMemcpyAsync(dl.p, PL, total * sizeof(Aff), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(dr.p, PR, total * sizeof(Aff), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(dg.p, gammas, families * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(dt.p, tasks.data(), families * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
+  tick("k_smul", 288.0 * total, (double)total);
+  count_smul_quad(launch_smul(dt.p, (int)families, (int)half, stream_, false, tier0_fold_quad_max(total, opt_.fold_quad_max, plain)));
+  tock();
+  CPX_HIP(hipMemcpyAsync(PL, dl.p, total * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipStreamSynchronize(stream_));
+  flush_timers();
 }
 // Encodings with the infinity flag set (include/cpx.h, option strict_infinity).  ark-bls12-381 ^0.4's `read_g1_compressed` — the
 // deserialiser behind `G1Affine::deserialize_compressed`, whisk.rs:313-320 — returns the identity as soon as the compression and the

@@ -162,6 +162,9 @@ class Engine {
   void msm_jac(const uint8_t* bases_jac, const uint8_t* scalars, size_t n, uint8_t* out_jac);          // util.rs:25-29
   void fold(uint8_t* PL, const uint8_t* PR, const uint8_t* gamma, size_t half);                        // IPA / SameMSM folds
   void scale(const uint8_t* P, const uint8_t* scalars, size_t scalar_stride, size_t n, uint8_t* out);  // G' rescale / k*R
+  // the calls of one log round, many per call (tier0_plan.hpp): ONE upload, kernel chain, download and stream synchronisation each
+  void msm_many(size_t count, const uint32_t* lens, const uint8_t* bases, const uint8_t* scalars, uint8_t* out_jac, uint8_t* out_comp);   // the cross terms: inner_product_argument.rs:158-161, same_multiscalar_argument.rs:107-112
+  void fold_many(size_t families, size_t half, uint8_t* PL, const uint8_t* PR, const uint8_t* gammas);                                      // the basis folds: inner_product_argument.rs:177-178, same_multiscalar_argument.rs:128-130
   void normalize(const uint8_t* jac, size_t n, uint8_t* out_aff, uint8_t* out_comp);                   // normalize_batch (+compress)
   int decompress(const uint8_t* comp, size_t n, uint8_t* out_aff, int check_subgroup, uint8_t* status_out = nullptr);   // whisk.rs:318-320
 

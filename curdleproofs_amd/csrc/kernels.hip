@@ -42,6 +42,7 @@
 #include "kernels.h"
 #include "block_inverse.hpp"
 #include "msm_body.hpp"
+#include "tier0_plan.hpp"
 
 namespace cpx {
 
@@ -1282,7 +1283,7 @@ const OptField kOptFields[] = {
     {"scale_any_point", &Options::scale_any_point, 0, 1},         {"strict_infinity", &Options::strict_infinity, 0, 1},
     {"fused_rounds_max", &Options::fused_rounds_max, 0, 1L << 30}, {"fused_smsm_max", &Options::fused_smsm_max, 0, 1L << 30}, {"fused_fix_wpw", &Options::fused_fix_wpw, 0, 16},
     {"smul_quad_max", &Options::smul_quad_max, 0, 1L << 30},       {"fused_tbl_wpw", &Options::fused_tbl_wpw, 8, 32},             {"fused_combine", &Options::fused_combine, -1, 1},
-    {"tbl_segments", &Options::tbl_segments, 0, 2},
+    {"tbl_segments", &Options::tbl_segments, 0, 2},                {"fold_quad_max", &Options::fold_quad_max, 0, 1L << 30},
 };
 bool option_value_ok(const OptField& f, long v) {
   if (v < f.lo || v > f.hi) return false;
@@ -1414,12 +1415,7 @@ int msm_tblw_slices(const Options& o, int ntasks, int wpw, int max_n) {
   // waves per task over its points: only when the GPU would otherwise stand almost empty (a lone proof: 16 waves per task) and a
   // slice keeps >= 256 points — below that the longest of a wave's 128 bucket lists no longer shrinks with the slice (a lane adds
   // max, not mean, and 64 points leave lists of 0..6), while every slice costs two more sets to reduce
-  if (o.tbw_slices) return (int)o.tbw_slices;   // 1|2|4 pins it
-  if (wpw != 2) return 1;
-  const long waves = (long)ntasks * 16;
-  int s = waves * 4 <= 1024 ? 4 : waves * 2 <= 1024 ? 2 : 1;
-  while (s > 1 && max_n / s < 256) s >>= 1;
-  return s;
+  return tbw_slices_rule(o.tbw_slices, ntasks, wpw, max_n);   // tier0_plan.hpp: the rule, where a host program can check it
 }
 void launch_msm_tblw(const TblTask* d_tasks, int ntasks, int wpw, uint32_t* d_raw, uint32_t* d_raw_slot, hipStream_t s, int slices, int segments) {
   if (ntasks <= 0) return;

@@ -54,7 +54,7 @@ int cpx_device_count(void);
 
 /* Per-context tunables (kernel selection thresholds, radix of the fixed-base table, batch size from which the protocol runs on the
  * device, ...): key = one of the names listed in curdleproofs_amd/csrc/kernels.h `struct Options` ("fix_bits", "device_min_batch",
- * "tbw_wpw", "reduce_wave_max", ...).  A new context starts from the built-in defaults, overridden by CPX_<KEY> environment
+ * "tbw_wpw", "reduce_wave_max", "fold_quad_max", ...).  A new context starts from the built-in defaults, overridden by CPX_<KEY> environment
  * variables read once per process; everything after that goes through these calls and concerns this context only.  Results never
  * depend on an option (tests/test_gpu_parity.py::test_engine_variants_stay_bit_exact), only speed does.  "fix_bits" takes effect at
  * the next cpx_ctx_set_crs.  Unknown key / value out of range -> CPX_ERR_ARG.  cpx_ctx_get_option also answers the read-only key
@@ -94,6 +94,33 @@ int cpx_g1_fold(cpx_ctx* ctx, uint8_t* PL /* half*96 */, const uint8_t* PR /* ha
  * E(Fp) outside it a scalar >= z^2 / 2 gives a wrong result.  Context option "scale_any_point" = 1 selects the plain 257-step
  * double-and-add for both calls, valid on all of E(Fp) (the cofactor multiplication of the hash-to-curve CRS, tests/crs.rs:38). */
 int cpx_g1_scale(cpx_ctx* ctx, const uint8_t* P /* n*96 */, const uint8_t* scalars, size_t scalar_stride, size_t n, uint8_t* out /* n*96 */);
+/* The calls of ONE log round in two calls.  Within a round the cross terms do not depend on each other, nor do the basis folds; only the
+ * challenge stands between the two groups.  cpx_g1_msm_many takes the cross terms, cpx_g1_fold_many the folds: each is one upload, one chain of
+ * kernel launches whose length does not depend on the count, one download and ONE stream synchronisation, so a round costs two calls and two
+ * synchronisations instead of 4 + 2 (IPA) or 6 + 3 (SameMSM).  Conventions of the batched tracker calls: scalars are 32-byte Montgomery limbs;
+ * count = 0 (families = 0, half = 0) is a no-op returning CPX_OK; a NULL input with work to do is CPX_ERR_ARG and nothing is written; no CRS is
+ * needed and the loaded batch is untouched (cpx_batch_size is unchanged).  Same subgroup precondition as the single calls' default paths.
+ * COST.  Every tier-0 call above is its own upload, kernel chain, download and synchronisation: by the library's own figures
+ * (curdleproofs_amd/csrc/kernels.h, kernels.hip) a cpx_g1_msm of 1 - 63 points takes 0.72 - 0.77 ms and the one-lane scalar multiplication
+ * behind cpx_g1_fold is a chain of 4.6 ms, which at 8 + 8 rounds (ell = 252: about 94 MSM calls and 41 fold / scale calls per proof) comes to
+ * well over 200 ms per proof.  What a round costs through the two calls below is measured by scripts/tier0_round_timing.py and recorded in
+ * INTEGRATION.md section 3. */
+/* util.rs:19-22 `msm` for `count` independent (points, scalars) pairs: the cross terms of one log round —
+ * inner_product_argument.rs:158-161, same_multiscalar_argument.rs:107-112.
+ *   lens     count lengths, ragged on purpose (L_C = msm(G_R, c_L) + <c_L, d_R> H is one task of n/2 + 1 points beside L_D of n/2);
+ *            a task of length 0 gives the identity: Z == 0 in out_jac, 0xc0 || 0^47 in out_compressed
+ *   bases, scalars  the tasks' points and scalars back to back, task after task
+ * Every task takes the endomorphism bucket-list path whatever its length (option "msm_endo_min" is not consulted).  Either output may be
+ * NULL.  At most 2^16 tasks and 2^24 points per call: more is CPX_ERR_ARG before anything else is read. */
+int cpx_g1_msm_many(cpx_ctx* ctx, size_t count, const uint32_t* lens /* count */, const uint8_t* bases /* sum(lens)*96, task after task */,
+                    const uint8_t* scalars /* sum(lens)*32 */, uint8_t* out_jac /* count*144 */, uint8_t* out_compressed /* count*48 */);
+/* inner_product_argument.rs:177-178, same_multiscalar_argument.rs:128-130 for `families` vectors of `half` elements:
+ *   PL[f][i] <- (PL[f][i] + PR[f][i] * gammas[f]).into_affine(), in place
+ * Option "fold_quad_max" (default 1536): a call of at most that many elements (families * half) runs with a quad of lanes per element
+ * (k_smul_quad, a third of the one-lane chain's latency); above it, at 0, or with "scale_any_point" = 1 it runs as the one-lane k_smul that
+ * cpx_g1_fold always takes.  At most 2^24 elements per call (CPX_ERR_ARG, PL untouched). */
+int cpx_g1_fold_many(cpx_ctx* ctx, size_t families, size_t half, uint8_t* PL /* families*half*96 */, const uint8_t* PR /* families*half*96 */,
+                     const uint8_t* gammas /* families*32 */);
 /* ark_ec `CurveGroup::normalize_batch` (+ optional `serialize_compressed`); either output may be NULL */
 int cpx_g1_normalize(cpx_ctx* ctx, const uint8_t* jac /* n*144 */, size_t n, uint8_t* out_affine /* n*96 */, uint8_t* out_compressed /* n*48 */);
 /* whisk.rs:318-320 `from_bytes_g1affine` = deserialize_compressed with on-curve + subgroup validation */

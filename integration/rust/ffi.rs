@@ -50,6 +50,9 @@ extern "C" {
     pub fn cpx_g1_msm_jac(ctx: *mut cpx_ctx, bases: *const u8, scalars: *const u8, n: usize, out: *mut u8) -> c_int;
     pub fn cpx_g1_fold(ctx: *mut cpx_ctx, pl: *mut u8, pr: *const u8, gamma: *const u8, half: usize) -> c_int;
     pub fn cpx_g1_scale(ctx: *mut cpx_ctx, p: *const u8, scalars: *const u8, scalar_stride: usize, n: usize, out: *mut u8) -> c_int;
+    // one log round in two calls: the cross terms (inner_product_argument.rs:158-161, same_multiscalar_argument.rs:107-112), then the basis folds (:177-178, :128-130)
+    pub fn cpx_g1_msm_many(ctx: *mut cpx_ctx, count: usize, lens: *const u32, bases: *const u8, scalars: *const u8, out_jac: *mut u8, out_compressed: *mut u8) -> c_int;
+    pub fn cpx_g1_fold_many(ctx: *mut cpx_ctx, families: usize, half: usize, pl: *mut u8, pr: *const u8, gammas: *const u8) -> c_int;
     pub fn cpx_g1_normalize(ctx: *mut cpx_ctx, jac: *const u8, n: usize, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
     pub fn cpx_g1_decompress(ctx: *mut cpx_ctx, compressed: *const u8, n: usize, out_affine: *mut u8, check_subgroup: c_int) -> c_int;
     // one verdict per point (0 ok, 1 malformed / not on the curve, 2 outside the subgroup): the square root behind tests/crs.rs:13-52

@@ -40,6 +40,40 @@ pub fn fold_bases(vec_L: &mut [G1Affine], vec_R: &[G1Affine], gamma: &Fr) {
     vec_L.copy_from_slice(&affine_from_wire(&l));
 }
 
+/// The cross terms of one log round in ONE call (inner_product_argument.rs:158-161: `&[(G_R, c_L + [<c_L, d_R>]), (G_prime_L, d_R), ...]`
+/// with H appended to the bases of L_C / R_C; same_multiscalar_argument.rs:107-112: six pairs of n points): `msm` for every pair.
+pub fn msm_many(pairs: &[(&[G1Affine], &[Fr])]) -> Vec<G1Projective> {
+    let lens: Vec<u32> = pairs.iter().map(|(p, s)| { assert_eq!(p.len(), s.len()); p.len() as u32 }).collect();
+    let mut bases = Vec::new();
+    let mut scalars: Vec<Fr> = Vec::new();
+    for (p, s) in pairs {
+        bases.extend_from_slice(&affine_to_wire(p));
+        scalars.extend_from_slice(s);
+    }
+    let mut out = vec![0u8; JAC * pairs.len()];
+    let rc = unsafe { cpx_g1_msm_many(ctx(), pairs.len(), lens.as_ptr(), bases.as_ptr(), scalars_ptr(&scalars), out.as_mut_ptr(), std::ptr::null_mut()) };
+    assert_eq!(rc, CPX_OK, "cpx_g1_msm_many");
+    out.chunks(JAC).map(projective_from_wire).collect()
+}
+
+/// The basis folds of one log round in ONE call (inner_product_argument.rs:177-178: G with gamma, G_prime with gamma_inv;
+/// same_multiscalar_argument.rs:128-130: T, U, G with gamma): `fold_bases` for every (vec_L, vec_R, gamma) of equal length.
+pub fn fold_bases_many(families: &mut [(&mut [G1Affine], &[G1Affine], Fr)]) {
+    let half = families.first().map_or(0, |f| f.0.len());
+    let (mut l, mut r, mut gammas) = (Vec::new(), Vec::new(), Vec::new());
+    for (vec_L, vec_R, gamma) in families.iter() {
+        assert!(vec_L.len() == half && vec_R.len() == half);
+        l.extend_from_slice(&affine_to_wire(vec_L));
+        r.extend_from_slice(&affine_to_wire(vec_R));
+        gammas.push(*gamma);
+    }
+    let rc = unsafe { cpx_g1_fold_many(ctx(), families.len(), half, l.as_mut_ptr(), r.as_ptr(), scalars_ptr(&gammas)) };
+    assert_eq!(rc, CPX_OK, "cpx_g1_fold_many");
+    for (f, (vec_L, _, _)) in families.iter_mut().enumerate() {
+        vec_L.copy_from_slice(&affine_from_wire(&l[AFF * half * f..AFF * half * (f + 1)]));
+    }
+}
+
 /// grand_product_argument.rs:90-102 (one scalar per point) and util.rs:94-95 (one shared scalar):
 /// `points[i].mul(scalars[i]).into_affine()`
 pub fn scale_points(points: &[G1Affine], scalars: &[Fr]) -> Vec<G1Affine> {
