@@ -59,10 +59,10 @@ EXPORTS = [
     "cpx_host_alloc", "cpx_host_free", "cpx_ctx_create", "cpx_ctx_destroy", "cpx_last_error", "cpx_device_count", "cpx_ctx_set_option", "cpx_ctx_get_option", "cpx_ctx_set_crs", "cpx_crs_sums", "cpx_proof_size", "cpx_batch_size",
     "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_g1_normalize", "cpx_g1_decompress", "cpx_g1_decompress_status",
     "cpx_accum_new", "cpx_accum_free", "cpx_accum_check", "cpx_accum_verify",
-    "cpx_batch_load", "cpx_batch_load_begin", "cpx_batch_load_end", "cpx_batch_prove", "cpx_batch_verify", "cpx_batch_verify_fused", "cpx_g1_sum_jac",
+    "cpx_batch_load", "cpx_batch_load_begin", "cpx_batch_load_end", "cpx_batch_prove", "cpx_batch_verify", "cpx_batch_verify_fused", "cpx_batch_verify_grouped", "cpx_g1_sum_jac",
     "cpx_whisk_generate_shuffle_proof", "cpx_whisk_is_valid_shuffle_proof", "cpx_whisk_generate_tracker_proof", "cpx_whisk_is_valid_tracker_proof",
     "cpx_whisk_generate_tracker_proofs", "cpx_whisk_verify_tracker_proofs", "cpx_g1_generator_mul", "cpx_whisk_trackers_from_k_r",
-    "cpx_batch_shuffle", "cpx_whisk_generate_shuffle_proofs", "cpx_whisk_verify_shuffle_proofs",
+    "cpx_batch_shuffle", "cpx_whisk_generate_shuffle_proofs", "cpx_whisk_verify_shuffle_proofs", "cpx_whisk_verify_shuffle_proofs_grouped",
     "cpx_set_profiling", "cpx_reset_stats", "cpx_get_stat", "cpx_set_host_threads", "cpx_bench_fpmul",
 ]
 
@@ -125,6 +125,7 @@ def load_library(path=None):
     L.cpx_get_stat.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double),
                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     L.cpx_batch_verify_fused.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ci)]
+    L.cpx_batch_verify_grouped.argtypes = [vp, vp, vp, vp, ctypes.POINTER(sz)]
     L.cpx_g1_sum_jac.argtypes = [vp, vp, sz, vp, ctypes.POINTER(ci)]
     L.cpx_set_host_threads.argtypes = [vp, ci]
     L.cpx_whisk_generate_shuffle_proof.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
@@ -138,6 +139,7 @@ def load_library(path=None):
     L.cpx_batch_shuffle.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     L.cpx_whisk_generate_shuffle_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     L.cpx_whisk_verify_shuffle_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.cpx_whisk_verify_shuffle_proofs_grouped.argtypes = [vp, sz, vp, vp, vp, vp, vp, ctypes.POINTER(sz)]
     L.cpx_bench_fpmul.argtypes = [vp, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
     _libs[os.path.realpath(path)] = L
     if default:
@@ -447,6 +449,21 @@ class Context:
         self._check(self._L.cpx_batch_verify(self._h, _in(blob), _in(rand), verdict))
         return list(verdict)
 
+    def verify_batch_grouped(self, proofs, rand):
+        """CurdleproofsProof::verify for every loaded instance through the grouped form of the accumulated check
+        (cpx_batch_verify_grouped): the batch is cut into at most `locate_groups_max` groups, every group's accumulated sum is tested,
+        and only the proofs of a failing group get a check of their own.  `rand`: 12 Fr per proof, as for verify_batch_fused.
+        Returns (list of CPX_* verdicts, n_rechecked)."""
+        B = self.batch
+        psz = self.proof_size
+        blob = proofs if isinstance(proofs, ctypes.Array) else b"".join(proofs)
+        if _len(blob) != B * psz or _len(rand) != B * 12 * FR:
+            raise ValueError("verify_batch_grouped: batch * proof_size proof bytes and 12 random factors per proof")
+        verdict = (ctypes.c_int * max(B, 1))(*([CPX_ERR_INTERNAL] * max(B, 1)))   # an entry the library does not write is never read as "accepted"
+        rechecked = ctypes.c_size_t(0)
+        self._check(self._L.cpx_batch_verify_grouped(self._h, _in(blob), _in(rand), verdict, ctypes.byref(rechecked)))
+        return list(verdict)[:B], rechecked.value
+
     def shuffle_batch(self, vec_R, vec_S, permutations, k, vec_m_blinders):
         """util.rs:83-106 for every instance in ONE library call (cpx_batch_shuffle): vec_R / vec_S hold count * ell affine points,
         permutations count * ell entries, k count scalars, vec_m_blinders 4 per instance.  Returns (vec_T, vec_U, M) — affine, affine,
@@ -507,7 +524,7 @@ class Context:
         return dict(launches=n.value, ms=ms.value, alg_bytes=by.value, units=un.value)
 
     KERNELS = ("k_msm_tblw<32, false>", "k_reduce_sets", "k_msm_tblw<16, false>", "k_msm_tblw<8, false>", "k_msm_tblw<4, false>", "k_msm_tblw<2, false>", "k_msm_fix<19, 7>", "k_msm_fix<16, 4>", "k_msm_fix<16, 2>", "k_msm_fix<16, 16>", "k_msm_fix<16, 8>", "k_msm_fix<8, 16>", "k_msm_fix<8, 8>",
-               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
+               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_vs_crs_sum_groups", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
 
     def stats(self):
         return {k: self.stat(k) for k in self.KERNELS}

@@ -322,6 +322,13 @@ int cpx_batch_verify_fused(cpx_ctx* ctx, const uint8_t* proofs, const uint8_t* r
     return CPX_OK;
   });
 }
+int cpx_batch_verify_grouped(cpx_ctx* ctx, const uint8_t* proofs, const uint8_t* rand, int* verdict, size_t* n_rechecked) {
+  if (!proofs || !rand || !verdict) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->batch_verify_grouped(proofs, rand, verdict, n_rechecked);
+    return CPX_OK;
+  });
+}
 int cpx_g1_sum_jac(cpx_ctx* ctx, const uint8_t* points_jac, size_t n, uint8_t* out_jac, int* is_identity) {
   if ((n && !points_jac) || !out_jac || !is_identity) return CPX_ERR_ARG;
   return guarded(ctx, [&] {
@@ -406,6 +413,15 @@ int cpx_whisk_verify_shuffle_proofs(cpx_ctx* ctx, size_t count, const uint8_t* p
   if (count && (!pre_trackers || !post_trackers || !proofs || !rand || !verdict)) return CPX_ERR_ARG;
   return guarded(ctx, [&] {
     ctx->eng->whisk_verify_shuffle_proofs(count, pre_trackers, post_trackers, proofs, rand, verdict);
+    return (int)CPX_OK;
+  });
+}
+
+int cpx_whisk_verify_shuffle_proofs_grouped(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs,
+                                            const uint8_t* rand, int* verdict, size_t* n_rechecked) {
+  if (count && (!pre_trackers || !post_trackers || !proofs || !rand || !verdict)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_verify_shuffle_proofs_grouped(count, pre_trackers, post_trackers, proofs, rand, verdict, n_rechecked);
     return (int)CPX_OK;
   });
 }

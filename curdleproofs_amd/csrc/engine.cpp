@@ -1586,11 +1586,19 @@ void Engine::batch_verify_fused(const uint8_t* proofs, const uint8_t* rand, uint
   verify_core(proofs, rand, VF_FUSED_COUNT, nullptr, partial_jac, n_invalid);
 }
 
+void Engine::batch_verify_grouped(const uint8_t* proofs, const uint8_t* rand, int* verdict, size_t* n_rechecked) {
+  size_t rechecked = 0;
+  verify_core(proofs, rand, VF_FUSED_COUNT, verdict, nullptr, nullptr, &rechecked);
+  if (n_rechecked) *n_rechecked = rechecked;
+}
+
 // Shared body.  Per-proof mode (verdict != nullptr, 8 random factors per proof): curdleproofs.rs:197.  Fused mode
 // (fused_partial != nullptr, 12 factors per proof): BASELINE config 5 — every check of every proof goes into ONE
 // accumulated MSM (the reference's MsmAccumulator shared by all verify calls); the result is this
 // engine's partial sum, which must add up to the identity over all engines / GPUs.
-void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid) {
+// Grouped mode (grouped != nullptr, verdict != nullptr, 12 factors per proof): the fused check stopped one level earlier — every group's sum is
+// tested, and the proofs of the failing groups get their own check from the same scalars (locate_plan.hpp); *grouped = proofs rechecked.
+void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid, size_t* grouped) {
   HostSpan wall(this, "host_verify_wall");
   if (!B_) throw std::logic_error("batch_load first");
   CPX_HIP(hipSetDevice(device_));
@@ -1609,7 +1617,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
     proofs = canonical_infinities(proofs, B * psz, B, psz, offs);
   }
   if (device_prefix(B)) {   // the whole verifier on the GPU (engine_device.cpp); a few proofs: host-driven Fiat-Shamir below
-    verify_core_device(proofs, rand, rand_stride, verdict, fused_partial, fused_invalid);
+    verify_core_device(proofs, rand, rand_stride, verdict, fused_partial, fused_invalid, grouped);
     return;
   }
 
@@ -1690,8 +1698,94 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
   };
   parallel_for(B, [&](size_t p) {
     host::verify_scalars(st[p], ell, L, &inst_comp[p * 4 * ell * 48], crs_H_comp_, comp_of(p, sm.D()), comp_of(p, sm.APRIME()), rand + p * rand_stride * 32,
-                         fused_partial != nullptr);
+                         fused_partial != nullptr || grouped != nullptr);
   });
+
+  if (grouped) {
+    // ---- the grouped check (locate_plan.hpp): stage 1 = one task per group, staged as the fused branch stages its groups; stage 2 = one
+    //      task per suspect proof over the scalars already on the device ----
+    if (!fixtab()) throw std::logic_error("set_crs first");
+    const size_t NI = 4 * ell, NPT = NI + NM, N = B * NPT;
+    const LocatePlan lp = locate_plan(B, opt_.locate_groups_max);
+    const size_t NT = lp.NT;
+    std::vector<uint32_t> flags(B);
+    for (size_t p = 0; p < B; p++) flags[p] = (st[p].bad ? kLocateFlagDecode : 0u) | (st[p].reject ? kLocateFlagStruct : 0u);
+    // device scalars: [ per-proof points' scalars (N) | per-proof CRS scalars (B n) | per-group CRS sums (NT n) ]
+    const size_t o_crs = N, o_sum = N + B * n, total = o_sum + lp.s1_crs_scalars(n);
+    const int fix_wpw = msm_fix_windows_per_wave(opt_, (int)NT, fix_bits_);
+    const int fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
+    const size_t slices = (size_t)msm_tblw_slices(opt_, (int)NT, 2, (int)lp.s1_max_n(NPT));
+    d_scal_.ensure(total);
+    d_big_idx_.ensure(N);
+    d_tasks_.ensure(NT + B);     // stage 1's tasks, then stage 2's
+    d_ftasks_.ensure(NT + B);
+    const size_t b_scal = total * sizeof(Fr), b_mt = NT * sizeof(MsmTask), b_ft = NT * sizeof(FixTask), b_idx = N * sizeof(uint32_t);
+    h_stage_.ensure(b_scal + b_mt + b_ft + b_idx);
+    Fr* hs = reinterpret_cast<Fr*>(h_stage_.p);
+    MsmTask* hm = reinterpret_cast<MsmTask*>(h_stage_.p + b_scal);
+    FixTask* hf = reinterpret_cast<FixTask*>(h_stage_.p + b_scal + b_mt);
+    uint32_t* hi = reinterpret_cast<uint32_t*>(h_stage_.p + b_scal + b_mt + b_ft);
+    parallel_for(B, [&](size_t p) {
+      const host::VerifyState& s = st[p];
+      Fr* d = hs + p * NPT;
+      Fr* c = hs + o_crs + p * n;
+      uint32_t* x = hi + p * NPT;
+      for (size_t i = 0; i < NI; i++) {
+        d[i] = s.bad ? S::zero().f : s.scal[1][i].f;   // an undecodable proof contributes nothing to its group
+        x[i] = (uint32_t)(p * pp_stride_ + i);
+      }
+      for (size_t j = 0; j < NM; j++) {
+        d[NI + j] = s.bad ? S::zero().f : s.scal[2][j].f;
+        x[NI + j] = slot_index(p, (int)j);
+      }
+      for (size_t i = 0; i < n; i++) c[i] = s.bad ? S::zero().f : s.scal[0][i].f;
+    });
+    parallel_for(n, [&](size_t i) {   // the CRS scalars summed per group
+      for (size_t g = 0; g < NT; g++) {
+        S t = S::zero();
+        for (size_t p = lp.group_first(g), e = p + lp.group_count(g); p < e; p++)
+          if (!st[p].bad) t += st[p].scal[0][i];
+        hs[o_sum + g * n + i] = t.f;
+      }
+    });
+    for (size_t g = 0; g < NT; g++) {
+      const size_t off = lp.s1_task_off(g, NPT);
+      hm[g] = MsmTask{d_pp_.p, d_big_idx_.p + off, d_scal_.p + off, (uint32_t)lp.s1_task_n(g, NPT), 0, (uint32_t)off};
+      hf[g] = FixTask{nullptr, d_scal_.p + o_sum + g * n, 0, (uint32_t)n, 0, (uint32_t)lp.s1_out_first(g, (size_t)fix_parts)};
+    }
+    CPX_HIP(hipMemcpyAsync(d_scal_.p, hs, b_scal, hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(d_tasks_.p, hm, b_mt, hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(d_ftasks_.p, hf, b_ft, hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(d_big_idx_.p, hi, b_idx, hipMemcpyHostToDevice, stream_));
+    launch_check(d_tasks_.p, d_ftasks_.p, NT, lp.s1_max_n(NPT), fix_wpw, fix_parts, slices);
+    wait_stream();
+    std::vector<uint8_t> group_ok(NT), recheck_ok;
+    for (size_t g = 0; g < NT; g++) group_ok[g] = check_passed(g) ? 1 : 0;   // (before stage 2 overwrites h_comp_)
+    std::vector<uint32_t> list;
+    locate_stage2(lp, group_ok.data(), flags.data(), list);   // empty with one proof per group: stage 1 was the per-proof check
+    const size_t nS = list.size();
+    if (nS) {
+      const int fix_wpw2 = msm_fix_windows_per_wave(opt_, (int)nS, fix_bits_), fix_parts2 = msm_fix_parts(fix_bits_, fix_wpw2);
+      const size_t slices2 = (size_t)msm_tblw_slices(opt_, (int)nS, 2, (int)NPT);
+      std::vector<MsmTask> mt(nS);   // (copied asynchronously: alive until the wait below)
+      std::vector<FixTask> ft(nS);
+      for (size_t s = 0; s < nS; s++) {
+        const size_t p = list[s];
+        mt[s] = MsmTask{d_pp_.p, d_big_idx_.p + p * NPT, d_scal_.p + p * NPT, (uint32_t)NPT, 0, (uint32_t)LocatePlan::s2_conv_off(s, NPT)};
+        ft[s] = FixTask{nullptr, d_scal_.p + o_crs + p * n, 0, (uint32_t)n, 0, (uint32_t)LocatePlan::s2_out_first(s, (size_t)fix_parts2)};
+      }
+      CPX_HIP(hipMemcpyAsync(d_tasks_.p + NT, mt.data(), nS * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(d_ftasks_.p + NT, ft.data(), nS * sizeof(FixTask), hipMemcpyHostToDevice, stream_));
+      launch_check(d_tasks_.p + NT, d_ftasks_.p + NT, nS, NPT, fix_wpw2, fix_parts2, slices2);
+      wait_stream();
+      recheck_ok.resize(nS);
+      for (size_t s = 0; s < nS; s++) recheck_ok[s] = check_passed(s) ? 1 : 0;
+    }
+    locate_verdicts(lp, group_ok.data(), flags.data(), list, recheck_ok.data(), verdict);
+    *grouped = nS;
+    flush_timers();
+    return;
+  }
 
   if (fused_partial) {
     // ---- one MSM over the CRS (scalars summed over the proofs, fixed-base table) and B * (4 ell + NM) per-proof points ----

@@ -23,6 +23,7 @@
 #include "host_math.hpp"
 #include "host_threads.hpp"
 #include "kernels.h"
+#include "locate_plan.hpp"
 #include "protocol.h"
 #include "prove_reqs.hpp"
 #include "shuffle_plan.hpp"
@@ -181,6 +182,9 @@ class Engine {
   // BASELINE config 5: all proofs of the batch in one accumulated MSM; 12 random factors per proof; output = this
   // engine's partial sum (Jacobian, standard form) and the number of structurally invalid proofs
   void batch_verify_fused(const uint8_t* proofs, const uint8_t* rand, uint8_t* partial_jac, int* n_invalid);
+  // The grouped form of the accumulated check (locate_plan.hpp; include/cpx.h cpx_batch_verify_grouped): 12 factors per proof as for the fused
+  // call, one verdict per proof; n_rechecked (nullable) = the proofs that went through the second stage
+  void batch_verify_grouped(const uint8_t* proofs, const uint8_t* rand, int* verdict, size_t* n_rechecked);
   size_t batch() const { return B_; }
 
   // ---- Whisk byte-level API (whisk.rs; whisk.cpp) ----
@@ -204,6 +208,9 @@ class Engine {
   void whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
                                      const uint8_t* rand, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status);
   void whisk_verify_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand, int* verdict);
+  // ... with 12 factors per item and the grouped check behind it
+  void whisk_verify_shuffle_proofs_grouped(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand, int* verdict,
+                                           size_t* n_rechecked);
 
   // ---- measurement ----
   void set_profiling(bool on) { profiling_ = on; }
@@ -392,11 +399,18 @@ class Engine {
     TblPlan pd;                                  // D and A'
     int fix_wpw = 16, fix_parts = 1, fix_wpw1 = 2, fix_parts1 = 8;
     size_t G = 1, NT = 1;                        // fused batch: proofs per group, groups
+    // grouped verifier (locate_plan.hpp): its own group tasks for option locate_groups_max, one fixed-base task per group over the group's
+    // summed CRS scalars (lsum), and room for the task lists of the second stage, which the host writes per call
+    LocatePlan lplan;
+    DevBuf<MsmTask> ltasks, l2tasks;
+    DevBuf<FixTask> lftasks, l2ftasks;
+    DevBuf<Fr> lsum;
+    int lfix_wpw = 16, lfix_parts = 1;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
   };
   DevVerifier dverify_;
   void prepare_device_verifier(size_t rand_stride);
-  void verify_core_device(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid);
+  void verify_core_device(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid, size_t* grouped);
   // Where the scalars of a request are: the ONE thing the host-driven and the device-resident path answer differently (prove_reqs.hpp).
   // Staged host scalars (uploaded with the phase) or device memory; the rows of round scalars are d_rout_ on both paths (make_reqs).
   struct ScalAddr {
@@ -435,7 +449,10 @@ class Engine {
   void run_msm_phase(const std::vector<MsmReq>& reqs, std::vector<uint8_t>* comp_out);
   void run_tbl_phase(const std::vector<TblReq>& reqs, std::vector<uint8_t>* comp_out);
   void reduce_sets(hipStream_t st, MsmScratch& sc, size_t nplain, size_t nweighted, TJac* part = nullptr);
-  void verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid);
+  void verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid, size_t* grouped = nullptr);
+  // the shared body of the two many-per-call shuffle verifiers: everything up to the dense proofs of the loaded batch, then `verify` on them
+  void whisk_verify_shuffle_proofs_with(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, int* verdict,
+                                        const std::function<void(const uint8_t* dense, int* verdict)>& verify);
   void batch_prove_tables(const uint32_t* permutation, const uint8_t* k, const uint8_t* m_blinders, const uint8_t* rand, uint8_t* proofs_out);
   // option strict_infinity = 0: `bytes` with every non-canonical infinity encoding (at `offsets` of each of the nrec records) rewritten to
   // the canonical one, in canon_bytes_ (valid until the next call); `bytes` itself when there is none or the option is set

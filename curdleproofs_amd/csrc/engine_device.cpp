@@ -650,9 +650,17 @@ void Engine::prepare_device_verifier(size_t rand_stride) {
   d_part_.ensure(B * 32);
   d_res_.ensure(B);
   d_comp_.ensure(B * 48);
+  // grouped verifier: the plan for option locate_groups_max and the buffers its task lists point into
+  const LocatePlan lp = locate_plan(B, opt_.locate_groups_max);
+  dv.lsum.ensure(lp.s1_crs_scalars(n));
+  dv.ltasks.ensure(lp.NT);
+  dv.lftasks.ensure(lp.NT);
+  dv.l2tasks.ensure(B);
+  dv.l2ftasks.ensure(B);
   const std::vector<const void*> sig = {d_pp_.p,       d_bytes_.p,  d_mcomp_.p,     d_tstate_.p, d_veca_.p,  dv.proofs.p, dv.rnd.p,    dv.vsc.p, dv.slotcomp.p,
                                         dv.status.p,   dv.scal.p,   dv.scal_crs.p,  dv.flags.p,  dv.mtasks.p, dv.ftasks.p, dv.gidx.p,  ctab(),   fixtab(),
-                                        (const void*)(uintptr_t)B, (const void*)(uintptr_t)ell, (const void*)(uintptr_t)fix_bits_};
+                                        (const void*)(uintptr_t)B, (const void*)(uintptr_t)ell, (const void*)(uintptr_t)fix_bits_,
+                                        dv.lsum.p,     dv.ltasks.p, dv.lftasks.p,   (const void*)(uintptr_t)lp.G, (const void*)(uintptr_t)lp.NT};
   dv.dev.rand_stride = (int)rand_stride;
   if (sig == dv.signature) return;
   dv.signature.clear();
@@ -722,6 +730,19 @@ void Engine::prepare_device_verifier(size_t rand_stride) {
     gt[g] = MsmTask{d_pp_.p, dv.gidx.p + off, dv.scal.p + off, (uint32_t)np_, 0, (uint32_t)off};
   }
   CPX_HIP(hipMemcpy(dv.gtasks.p, gt.data(), dv.NT * sizeof(MsmTask), hipMemcpyHostToDevice));
+  // grouped verifier, stage 1: the same layout for ITS group size, and per group a fixed-base task over the group's summed CRS scalars
+  dv.lplan = lp;
+  dv.lfix_wpw = msm_fix_windows_per_wave(opt_, (int)lp.NT, fix_bits_);
+  dv.lfix_parts = msm_fix_parts(fix_bits_, dv.lfix_wpw);
+  std::vector<MsmTask> lt(lp.NT);
+  std::vector<FixTask> lf(lp.NT);
+  for (size_t g = 0; g < lp.NT; g++) {
+    const size_t off = lp.s1_task_off(g, NPT);
+    lt[g] = MsmTask{d_pp_.p, dv.gidx.p + off, dv.scal.p + off, (uint32_t)lp.s1_task_n(g, NPT), 0, (uint32_t)off};
+    lf[g] = FixTask{nullptr, dv.lsum.p + g * n, 0, (uint32_t)n, 0, (uint32_t)lp.s1_out_first(g, (size_t)dv.lfix_parts)};
+  }
+  CPX_HIP(hipMemcpy(dv.ltasks.p, lt.data(), lp.NT * sizeof(MsmTask), hipMemcpyHostToDevice));
+  CPX_HIP(hipMemcpy(dv.lftasks.p, lf.data(), lp.NT * sizeof(FixTask), hipMemcpyHostToDevice));
   if (!dv.ev_a) {
     CPX_HIP(hipEventCreateWithFlags(&dv.ev_a, hipEventDisableTiming));
     CPX_HIP(hipEventCreateWithFlags(&dv.ev_b, hipEventDisableTiming));
@@ -731,7 +752,8 @@ void Engine::prepare_device_verifier(size_t rand_stride) {
 
 // curdleproofs.rs:197 for every loaded instance (verdict != nullptr) or BASELINE config 5 (fused_partial != nullptr), all on the
 // device: the host uploads proofs and random factors, enqueues, and reads back 48 bytes + a flag word per proof (or one point).
-void Engine::verify_core_device(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid) {
+void Engine::verify_core_device(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid,
+                                size_t* grouped) {
   CPX_HIP(hipSetDevice(device_));
   const size_t B = B_, ell = ell_, n = n_, L = L_;
   const ProofLayout pl(L);
@@ -773,6 +795,43 @@ void Engine::verify_core_device(const uint8_t* proofs, const uint8_t* rand, size
     int invalid = 0;
     for (size_t p = 0; p < B; p++) invalid += h_u32_.p[p] ? 1 : 0;
     if (fused_invalid) *fused_invalid = invalid;
+    flush_timers();
+    return;
+  }
+  if (grouped) {
+    // ---- the grouped check (locate_plan.hpp).  Stage 1: every group's sum — its CRS scalars added up in Fr, its points in one bucket
+    //      MSM — tested for the identity; the compressed sums and the flag words arrive behind ONE wait
+    const LocatePlan& lp = dv.lplan;
+    tick("k_vs_crs_sum_groups", 32.0 * B * n, (double)(B * n));
+    launch_vs_crs_sum_groups(dv.scal_crs.p, Bi, (int)n, (int)lp.G, (int)lp.NT, dv.lsum.p, stream_);
+    tock();
+    launch_check(dv.ltasks.p, dv.lftasks.p, lp.NT, lp.s1_max_n(NPT), dv.lfix_wpw, dv.lfix_parts, 1);
+    CPX_HIP(hipMemcpyAsync(h_u32_.p, dv.flags.p, B * 4, hipMemcpyDeviceToHost, stream_));
+    wait_stream_blocking();
+    std::vector<uint8_t> group_ok(lp.NT), recheck_ok;
+    for (size_t g = 0; g < lp.NT; g++) group_ok[g] = check_passed(g) ? 1 : 0;   // (before stage 2 overwrites h_comp_)
+    std::vector<uint32_t> list;
+    locate_stage2(lp, group_ok.data(), h_u32_.p, list);
+    // ---- stage 2: the suspects' own checks from the scalars stage 1 left in place; nothing when every group passed
+    const size_t S = list.size();
+    if (S) {
+      const int fix_wpw = msm_fix_windows_per_wave(opt_, (int)S, fix_bits_), fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
+      std::vector<MsmTask> mt(S);   // (copied asynchronously: alive until the wait below)
+      std::vector<FixTask> ft(S);
+      for (size_t s = 0; s < S; s++) {
+        const size_t p = list[s];
+        mt[s] = MsmTask{d_pp_.p, dv.gidx.p + p * NPT, dv.scal.p + p * NPT, (uint32_t)NPT, 0, (uint32_t)LocatePlan::s2_conv_off(s, NPT)};
+        ft[s] = FixTask{nullptr, dv.scal_crs.p + p * n, 0, (uint32_t)n, 0, (uint32_t)LocatePlan::s2_out_first(s, (size_t)fix_parts)};
+      }
+      CPX_HIP(hipMemcpyAsync(dv.l2tasks.p, mt.data(), S * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(dv.l2ftasks.p, ft.data(), S * sizeof(FixTask), hipMemcpyHostToDevice, stream_));
+      launch_check(dv.l2tasks.p, dv.l2ftasks.p, S, NPT, fix_wpw, fix_parts, 1);
+      wait_stream_blocking();
+      recheck_ok.resize(S);
+      for (size_t s = 0; s < S; s++) recheck_ok[s] = check_passed(s) ? 1 : 0;
+    }
+    locate_verdicts(lp, group_ok.data(), h_u32_.p, list, recheck_ok.data(), verdict);
+    *grouped = S;
     flush_timers();
     return;
   }

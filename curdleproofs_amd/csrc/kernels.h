@@ -64,6 +64,7 @@ struct Options {
   long strict_infinity = 0;        // point encodings with the infinity flag set: 0 = the identity whatever the other 382 bits say (ark-bls12-381 ^0.4 `read_g1_compressed`, as recalled: include/cpx.h), 1 = only 0xc0 || 0^47 (the zcash specification's wording; ark-bls12-381 0.5)
   long msm_endo_min = 1;           // cpx_g1_msm / cpx_g1_msm_jac: from this many points on the endomorphism bucket-list path (k_to_table_endo + k_msm_tblw<2, true>), below it the plain windowed accumulation (k_msm_accw: three dependent launches with doubling chains, 1.35 - 1.5 ms per call at 1 - 63 points against 0.72 - 0.77 on the bucket-list path; the default was 64 until round 6)
   long fold_quad_max = 1536;       // cpx_g1_fold_many: a call of at most this many elements (families x half) runs with a quad per element (k_smul_quad), above it, at 0 and with scale_any_point = 1 as the one-lane k_smul; 3 x 128 elements 1.22 against 2.19 ms per call, 3 x 512 (the largest size measured) 1.24 against 2.20 (profiles/r13_tier0_rounds.md); cpx_g1_fold keeps the one-lane kernel
+  long locate_groups_max = 256;    // cpx_batch_verify_grouped / cpx_whisk_verify_shuffle_proofs_grouped: the batch is cut into at most this many groups (1 .. 256; locate_plan.hpp); the fewer the groups, the more proofs one wrong proof sends to the second stage.  The grouping of cpx_batch_verify_fused stays at 256
   long scale_any_point = 0;        // 1: cpx_g1_scale / cpx_g1_fold take ANY point of E(Fp) (plain 257-step double-and-add, SMUL_PLAIN); 0: points of the order-r subgroup (endomorphism split, 129 steps)
 };
 const Options& default_options();                               // built-in defaults overridden by CPX_<NAME> environment variables

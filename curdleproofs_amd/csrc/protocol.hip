@@ -13,6 +13,7 @@
 #include "strobe.hpp"
 #include "wave_strobe.hpp"
 #include "protocol.h"
+#include "kernels.h"   // take_launch_events: the profiling hook of the launchers
 #include "check_weights.hpp"
 
 namespace cpx {
@@ -654,6 +655,17 @@ __global__ __launch_bounds__(64) void k_vs_crs_sum(const Fr* __restrict__ scal_c
   out[i] = t;
 }
 
+// grouped verifier: the same sum per GROUP of G consecutive proofs, out[g * n + i] for group g = blockIdx.y.  Consecutive lanes take
+// consecutive i: a wave reads 64 neighbouring 32-byte elements of one proof's row per step, and every scalar of the batch is read once.
+__global__ __launch_bounds__(64) void k_vs_crs_sum_groups(const Fr* __restrict__ scal_crs, int B, int n, int G, Fr* __restrict__ out) {
+  const int i = blockIdx.x * 64 + threadIdx.x, g = blockIdx.y;
+  if (i >= n) return;
+  const int p0 = g * G, p1 = min(p0 + G, B);   // the last group may be short
+  Fr t = Fr::zero();
+  for (int p = p0; p < p1; p++) t = fe_add(t, scal_crs[(size_t)p * n + i]);
+  out[(size_t)g * n + i] = t;
+}
+
 // ------------------------------------------------------------------ launchers
 static inline size_t lds_vec(const ProveDev& d) { return (size_t)d.n * 32 + 64; }
 #define PS_LAUNCH(kern, B, lds, s, ...) hipLaunchKernelGGL(kern, dim3(B), dim3(64), lds, s, __VA_ARGS__)
@@ -669,6 +681,13 @@ void launch_vs_prefix(const VerifyDev& d, int B, hipStream_t s) { PS_LAUNCH(k_vs
 void launch_vs_scalars(const VerifyDev& d, int B, hipStream_t s) { PS_LAUNCH(k_vs_scalars, B, (size_t)d.n * 32 + (size_t)4 * d.L * 32 + 64 + 4 * 48, s, d); }
 void launch_vs_crs_sum(const Fr* d_scal_crs, int B, int n, Fr* d_out, hipStream_t s) {
   hipLaunchKernelGGL(k_vs_crs_sum, dim3((n + 63) / 64), dim3(64), 0, s, d_scal_crs, B, n, d_out);
+}
+void launch_vs_crs_sum_groups(const Fr* d_scal_crs, int B, int n, int G, int NT, Fr* d_out, hipStream_t s) {
+  if (NT <= 0 || n <= 0) return;
+  hipEvent_t a = nullptr, b = nullptr;
+  take_launch_events(&a, &b);   // profiling: the pending events of Engine::tick belong to this dispatch
+  if (a || b) hipExtLaunchKernelGGL(k_vs_crs_sum_groups, dim3((n + 63) / 64, NT), dim3(64), 0, s, a, b, 0, d_scal_crs, B, n, G, d_out);
+  else hipLaunchKernelGGL(k_vs_crs_sum_groups, dim3((n + 63) / 64, NT), dim3(64), 0, s, d_scal_crs, B, n, G, d_out);
 }
 
 }  // namespace cpx

@@ -601,6 +601,18 @@ void Engine::whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trac
 // whisk.rs:106-130 is_valid_whisk_shuffle_proof for every (pre_trackers, post_trackers, proof) triple
 void Engine::whisk_verify_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand,
                                          int* verdict) {
+  whisk_verify_shuffle_proofs_with(count, pre_trackers, post_trackers, proofs, verdict, [&](const uint8_t* dense, int* v) { batch_verify(dense, rand, v); });
+}
+// ... with 12 factors per item, through the grouped form of the accumulated check (locate_plan.hpp)
+void Engine::whisk_verify_shuffle_proofs_grouped(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand,
+                                                 int* verdict, size_t* n_rechecked) {
+  if (n_rechecked) *n_rechecked = 0;
+  whisk_verify_shuffle_proofs_with(count, pre_trackers, post_trackers, proofs, verdict,
+                                   [&](const uint8_t* dense, int* v) { batch_verify_grouped(dense, rand, v, n_rechecked); });
+}
+// The shared body: decode the trackers and M, load the count instances, hand the dense proofs to `verify`, override the undecodable items
+void Engine::whisk_verify_shuffle_proofs_with(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, int* verdict,
+                                              const std::function<void(const uint8_t* dense, int* verdict)>& verify) {
   for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
   if (!count) return;
   if (!ell_) throw std::logic_error("set_crs first");
@@ -653,7 +665,7 @@ void Engine::whisk_verify_shuffle_proofs(size_t count, const uint8_t* pre_tracke
   CPX_HIP(hipMemcpyAsync(bad.data(), sh_.bad.p, count, hipMemcpyDeviceToHost, stream_));
   CPX_HIP(hipStreamSynchronize(stream_));
   flush_timers();
-  batch_verify(dense.data(), rand, verdict);
+  verify(dense.data(), verdict);
   for (size_t i = 0; i < count; i++)
     if (bad[i]) verdict[i] = CPX_ERR_DESERIALIZE;   // an undecodable tracker or M: Err(SerializationError), whatever the placeholder's verdict
 }

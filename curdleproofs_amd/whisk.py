@@ -179,24 +179,41 @@ def are_valid_whisk_shuffle_proofs(ctx, pre_lists, post_lists, proofs, rands=Non
     """whisk.rs:106-130 for every (pre_trackers, post_trackers, proof) triple in ONE library call.  rands: per triple the verifier's eight
     accumulate_check factors (CSPRNG when omitted).  Returns a list with True / False, or a SerializationError INSTANCE where the reference
     returns Err (undecodable tracker, M or proof bytes, wrong proof length); nothing is raised per item."""
+    return _verify_whisk_shuffle_proofs(ctx, pre_lists, post_lists, proofs, rands, 8)[0]
+
+
+def are_valid_whisk_shuffle_proofs_grouped(ctx, pre_lists, post_lists, proofs, rands=None):
+    """The same through the grouped form of the accumulated check (cpx_whisk_verify_shuffle_proofs_grouped): close to the rate of the
+    all-or-nothing fused check while few items are wrong.  rands: per triple TWELVE factors (the eight accumulate_check factors, then
+    four weights for the SameScalar equalities).  Returns (results as above, n_rechecked): n_rechecked items went through a check of
+    their own because the sum of their group was not the identity (context option "locate_groups_max")."""
+    return _verify_whisk_shuffle_proofs(ctx, pre_lists, post_lists, proofs, rands, 12)
+
+
+def _verify_whisk_shuffle_proofs(ctx, pre_lists, post_lists, proofs, rands, nf):
+    """nf = 8: cpx_whisk_verify_shuffle_proofs, nf = 12: its grouped form.  Returns (results, n_rechecked)."""
     count = len(pre_lists)
     if len(post_lists) != count or len(proofs) != count or (rands is not None and len(rands) != count):
         raise ValueError("one post tracker list, one proof and one set of factors per pre tracker list")
     if count == 0:
-        return []
+        return [], 0
     ell = ctx.ell
     if any(len(t) != ell for t in pre_lists) or any(len(t) != ell for t in post_lists):
         raise ValueError("need exactly ell = %d trackers per list on both sides" % ell)
-    rands = [_rand_fr(8) for _ in range(count)] if rands is None else rands
-    if any(len(r) != 8 * FR for r in rands):
-        raise ValueError("8 random factors per proof")
+    rands = [_rand_fr(nf) for _ in range(count)] if rands is None else rands
+    if any(len(r) != nf * FR for r in rands):
+        raise ValueError("%d random factors per proof" % nf)
     rec = whisk_shuffle_proof_size(ctx)
     # a wrong length is a fixed-size array mismatch in the reference: reported per item, the library sees a well-formed dummy
     short = [len(p) != rec for p in proofs]
     pf = b"".join(bytes(rec) if s else p for s, p in zip(short, proofs))
     verdict = (ctypes.c_int * count)(*([CPX_ERR_INTERNAL] * count))   # an entry the library does not write is never read as accepted
-    ctx._check(ctx._L.cpx_whisk_verify_shuffle_proofs(ctx._h, count, _in(b"".join(_cat(t) for t in pre_lists)), _in(b"".join(_cat(t) for t in post_lists)),
-                                                      _in(pf), _in(b"".join(rands)), verdict))
+    pre, post = _in(b"".join(_cat(t) for t in pre_lists)), _in(b"".join(_cat(t) for t in post_lists))
+    rechecked = ctypes.c_size_t(0)
+    if nf == 8:
+        ctx._check(ctx._L.cpx_whisk_verify_shuffle_proofs(ctx._h, count, pre, post, _in(pf), _in(b"".join(rands)), verdict))
+    else:
+        ctx._check(ctx._L.cpx_whisk_verify_shuffle_proofs_grouped(ctx._h, count, pre, post, _in(pf), _in(b"".join(rands)), verdict, ctypes.byref(rechecked)))
     res = []
     for i, v in enumerate(verdict):
         if short[i]:
@@ -209,7 +226,7 @@ def are_valid_whisk_shuffle_proofs(ctx, pre_lists, post_lists, proofs, rands=Non
             res.append(SerializationError("shuffle proof %d" % i))
         else:
             raise CpxError(v, "shuffle proof %d" % i)
-    return res
+    return res, rechecked.value
 
 
 # ---- many tracker proofs per call (cpx_whisk_generate_tracker_proofs / cpx_whisk_verify_tracker_proofs) ----

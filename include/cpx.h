@@ -198,8 +198,32 @@ int cpx_batch_verify(cpx_ctx* ctx, const uint8_t* proofs, const uint8_t* rand, i
  *                The batch is accepted iff the partial sums of all contexts / GPUs add up to the identity
  *                (all-gather the 144-byte partials, add them with cpx_g1_sum_jac) and no context reports invalid proofs.
  *   n_invalid    number of loaded proofs that failed deserialisation or the structural checks (curdleproofs.rs:218)
- * All-or-nothing: a rejected batch does not say which proof is wrong (re-run cpx_batch_verify for that). */
+ * All-or-nothing: a rejected batch does not say which proof is wrong (cpx_batch_verify_grouped below names the wrong proofs at close to this
+ * call's cost). */
 int cpx_batch_verify_fused(cpx_ctx* ctx, const uint8_t* proofs, const uint8_t* rand, uint8_t* partial_jac, int* n_invalid);
+/* curdleproofs.rs:197 `verify` for every loaded instance, one verdict per proof, through the grouped form of the accumulated check
+ * (msm_accumulator.rs:22-68 shared by the proofs of a group).
+ *   rand         batch*12*32, as for cpx_batch_verify_fused (zero or >= r -> CPX_ERR_ARG)
+ *   verdict      batch ints: CPX_OK, CPX_ERR_VERIFY or CPX_ERR_DESERIALIZE; the call returns CPX_OK whatever they are
+ *   n_rechecked  (may be NULL) the number of proofs that went through stage 2; deterministic given the inputs and the option below
+ * The batch is cut into NT groups of G consecutive proofs, G = ceil(batch / locate_groups_max), NT = ceil(batch / G); the last group may be
+ * short.  Context option "locate_groups_max" (default 256, 1 .. 256) concerns the grouped calls only: cpx_batch_verify_fused keeps its 256
+ * groups.  Results never depend on it, only n_rechecked and speed do.
+ *   Stage 1  every group's accumulated sum — the fused check restricted to that group — is computed and tested for the identity.
+ *   Stage 2  every flag-free proof of a group whose sum is not the identity gets its own accumulated check, from the scalars stage 1
+ *            computed (nothing is hashed or decoded again).  With G = 1 stage 1 already is that check and there is no stage 2.
+ * Verdicts: a proof that does not decode is CPX_ERR_DESERIALIZE; one with the structural flag (vec_T[0] is zero, curdleproofs.rs:218) is
+ * CPX_ERR_VERIFY; a flag-free proof of a passing group is CPX_OK; any other proof has the verdict of its own check.  An undecodable proof
+ * contributes nothing to its group, so it does not send its neighbours to stage 2.  A structurally rejected proof keeps its scalars (as in
+ * the fused call) and therefore DOES drag its group into stage 2: its neighbours are rechecked and counted in n_rechecked.
+ * Soundness.  A group's sum is a polynomial of total degree 2 in the independent factors of its proofs whose coefficients are the individual
+ * check values, so a group that contains a false relation passes stage 1 with probability <= 2/r — the bound cpx_batch_verify already rests
+ * on (Schwartz-Zippel).  Stage 2 reuses a proof's own 12 factors: a valid proof's check is identically zero, an invalid one survives with
+ * probability <= 2/r over its own factors.  The per-proof verdicts therefore equal cpx_batch_verify's except with probability < 2^-252.
+ * strict_infinity applies as for cpx_batch_verify.  Without a loaded batch: CPX_ERR_STATE.  NULL proofs, rand or verdict: CPX_ERR_ARG and
+ * nothing is written.  What the call costs beside the other two is measured by scripts/grouped_verify_rate.py (profiles/grouped_verify.md). */
+int cpx_batch_verify_grouped(cpx_ctx* ctx, const uint8_t* proofs, const uint8_t* rand /* batch*12*32, as cpx_batch_verify_fused */,
+                             int* verdict /* batch: CPX_OK / CPX_ERR_VERIFY / CPX_ERR_DESERIALIZE */, size_t* n_rechecked /* may be NULL */);
 /* sum of n Jacobian points (n*144 B) -> out (144 B); *is_identity = 1 iff the sum is the point at infinity */
 int cpx_g1_sum_jac(cpx_ctx* ctx, const uint8_t* points_jac, size_t n, uint8_t* out_jac, int* is_identity);
 
@@ -281,13 +305,20 @@ int cpx_whisk_generate_shuffle_proofs(cpx_ctx* ctx, size_t count, const uint8_t*
  *   undecodable M, a failed CurdleproofsProof::deserialize).  rand as for cpx_batch_verify (zero or >= r -> CPX_ERR_ARG for the call). */
 int cpx_whisk_verify_shuffle_proofs(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers,
                                     const uint8_t* proofs /* count*(48+cpx_proof_size) */, const uint8_t* rand /* count*8*32 */, int* verdict /* count */);
+/* whisk.rs:106-130 for `count` triples: cpx_whisk_verify_shuffle_proofs with 12 factors per item and the grouped check behind it
+ * (cpx_batch_verify_grouped: stages, verdicts, soundness, option "locate_groups_max").  Everything else is cpx_whisk_verify_shuffle_proofs:
+ * verdict is pre-filled with CPX_ERR_INTERNAL, an item whose trackers or M do not decode keeps its slot as a placeholder instance and is
+ * CPX_ERR_DESERIALIZE whatever the placeholder's verdict (the placeholder fails its group's sum, so the items beside it are rechecked and
+ * counted).  n_rechecked may be NULL. */
+int cpx_whisk_verify_shuffle_proofs_grouped(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers,
+                                            const uint8_t* proofs, const uint8_t* rand /* count*12*32 */, int* verdict, size_t* n_rechecked);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 int cpx_set_profiling(cpx_ctx* ctx, int on); /* time every kernel group with HIP events on the ctx stream */
 int cpx_reset_stats(cpx_ctx* ctx);
 /* name = kernel name as rocprofv3 reports it, template arguments included: "k_msm_fix<16, 16>", "k_msm_tblw<32, false>",
  * "k_msm_tblw<2, true>", "k_msm_accw", "k_reduce_sets", "k_finalize_ranges", "k_table_build", "k_msm_tail", "k_smul",
- * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
+ * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_vs_crs_sum_groups" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
  * "k_smul" times the one-lane and the quad form alike; "k_smul_quad" counts (launches only) those of them that ran as k_smul_quad;
  * units = MSM points / scalar-mul elements / points; out pointers may be NULL */
 int cpx_get_stat(const cpx_ctx* ctx, const char* name, uint64_t* launches, double* total_ms, double* algorithmic_bytes, double* units);

@@ -69,6 +69,8 @@ extern "C" {
     pub fn cpx_batch_prove(ctx: *mut cpx_ctx, permutation: *const u32, k: *const u8, vec_m_blinders: *const u8, rand: *const u8, proofs_out: *mut u8) -> c_int;
     pub fn cpx_batch_verify(ctx: *mut cpx_ctx, proofs: *const u8, rand: *const u8, verdict: *mut c_int) -> c_int;
     pub fn cpx_batch_verify_fused(ctx: *mut cpx_ctx, proofs: *const u8, rand: *const u8, partial_jac: *mut u8, n_invalid: *mut c_int) -> c_int;
+    // the grouped form of the accumulated check: one verdict per proof, 12 factors per proof; n_rechecked may be null
+    pub fn cpx_batch_verify_grouped(ctx: *mut cpx_ctx, proofs: *const u8, rand: *const u8, verdict: *mut c_int, n_rechecked: *mut usize) -> c_int;
     pub fn cpx_g1_sum_jac(ctx: *mut cpx_ctx, points_jac: *const u8, n: usize, out_jac: *mut u8, is_identity: *mut c_int) -> c_int;
     // whisk.rs byte-level API
     pub fn cpx_whisk_generate_shuffle_proof(ctx: *mut cpx_ctx, pre_trackers: *const u8, permutation: *const u32, k: *const u8, vec_m_blinders: *const u8,
@@ -92,6 +94,8 @@ extern "C" {
                                              vec_m_blinders: *const u8, rand: *const u8, post_trackers_out: *mut u8, proofs_out: *mut u8, status: *mut c_int) -> c_int;
     pub fn cpx_whisk_verify_shuffle_proofs(ctx: *mut cpx_ctx, count: usize, pre_trackers: *const u8, post_trackers: *const u8, proofs: *const u8, rand: *const u8,
                                            verdict: *mut c_int) -> c_int;
+    pub fn cpx_whisk_verify_shuffle_proofs_grouped(ctx: *mut cpx_ctx, count: usize, pre_trackers: *const u8, post_trackers: *const u8, proofs: *const u8,
+                                                   rand: *const u8, verdict: *mut c_int, n_rechecked: *mut usize) -> c_int;
 }
 
 pub const AFF: usize = 96;
