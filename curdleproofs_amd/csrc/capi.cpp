@@ -7,6 +7,7 @@
 #include <vector>
 #include <cstdlib>
 #include "engine.hpp"
+#include "find_plan.hpp"
 
 using namespace cpx;
 
@@ -388,6 +389,14 @@ int cpx_whisk_trackers_from_k_r(cpx_ctx* ctx, size_t count, const uint8_t* k, co
   if (count && (!k || !r)) return CPX_ERR_ARG;
   return guarded(ctx, [&] {
     ctx->eng->whisk_trackers_from_k_r(count, k, r, trackers_out, k_commitments_out);
+    return (int)CPX_OK;
+  });
+}
+int cpx_whisk_find_trackers(cpx_ctx* ctx, size_t n_trackers, const uint8_t* trackers, size_t n_keys, const uint8_t* k, uint32_t* owner, int* status) {
+  if (!find_fits(n_trackers, n_keys)) return CPX_ERR_ARG;   // before anything is read
+  if (n_trackers && (!trackers || !owner || !status || (n_keys && !k))) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_find_trackers(n_trackers, trackers, n_keys, k, owner, status);
     return (int)CPX_OK;
   });
 }

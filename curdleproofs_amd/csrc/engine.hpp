@@ -200,6 +200,8 @@ class Engine {
   // what those calls consume, `count` per call, as multiples of the generator on its fixed-base table (genmul.hip): out[i] = scalars[i] G, and
   // WhiskTracker::from_k_r / get_k_commitment (whisk.rs:45-55, :370) for (k, r) pairs; either output may be null
   void generator_mul(size_t count, const uint8_t* scalars, uint8_t* out_affine, uint8_t* out_compressed);
+  // which key opens which tracker, k_j * r_G_i == k_r_G_i for every pair (find.hip, find_plan.hpp): owner[i] = the smallest such j or CPX_NO_OWNER
+  void whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, size_t n_keys, const uint8_t* k, uint32_t* owner, int* status);
   void whisk_trackers_from_k_r(size_t count, const uint8_t* k, const uint8_t* r, uint8_t* trackers_out, uint8_t* k_commitments_out);
   // the shuffle step and the two shuffle-proof functions for `count` independent shuffles per call (shuffle.hip): compressed bytes in, compressed
   // bytes out, nothing returns to the host between the uploads and the batch prover / verifier; the count instances become the loaded batch

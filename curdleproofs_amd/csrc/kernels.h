@@ -65,6 +65,8 @@ struct Options {
   long msm_endo_min = 1;           // cpx_g1_msm / cpx_g1_msm_jac: from this many points on the endomorphism bucket-list path (k_to_table_endo + k_msm_tblw<2, true>), below it the plain windowed accumulation (k_msm_accw: three dependent launches with doubling chains, 1.35 - 1.5 ms per call at 1 - 63 points against 0.72 - 0.77 on the bucket-list path; the default was 64 until round 6)
   long fold_quad_max = 1536;       // cpx_g1_fold_many: a call of at most this many elements (families x half) runs with a quad per element (k_smul_quad), above it, at 0 and with scale_any_point = 1 as the one-lane k_smul; 3 x 128 elements 1.22 against 2.19 ms per call, 3 x 512 (the largest size measured) 1.24 against 2.20 (profiles/r13_tier0_rounds.md); cpx_g1_fold keeps the one-lane kernel
   long locate_groups_max = 256;    // cpx_batch_verify_grouped / cpx_whisk_verify_shuffle_proofs_grouped: the batch is cut into at most this many groups (1 .. 256; locate_plan.hpp); the fewer the groups, the more proofs one wrong proof sends to the second stage.  The grouping of cpx_batch_verify_fused stays at 256
+  long find_table_min_keys = 256;  // cpx_whisk_find_trackers: from this many keys on the call builds a per-tracker table of multiples and scans it (k_find_scan), below it one k_smul element per (tracker, key) pair (1 .. 2^20 + 1: 1 = always the table, 2^20 + 1 = never; find_plan.hpp).  Measured at 8192 trackers (profiles/find_trackers.md): the table path costs 34 ms before the first pair (k_table_build + k_fix_build) and is level with the ladder at 128 keys (37.4 against 36.1 ms), ahead at 256 (41.5 against 69.2) — the smallest measured power of two with the table ahead.  The operation counts alone said 64 (break-even near 57 keys); they leave out that the table build runs at a fraction of the scan's product rate
+  long find_table_mb = 1024;       // ... and the trackers are processed in chunks whose table and build scratch stay within this many MiB (1 .. 65536; 0.56 MiB per tracker)
   long scale_any_point = 0;        // 1: cpx_g1_scale / cpx_g1_fold take ANY point of E(Fp) (plain 257-step double-and-add, SMUL_PLAIN); 0: points of the order-r subgroup (endomorphism split, 129 steps)
 };
 const Options& default_options();                               // built-in defaults overridden by CPX_<NAME> environment variables
@@ -333,6 +335,16 @@ void launch_shuffle_status(const ShufflePlan& pl, const uint8_t* d_status, Aff* 
 void launch_shuffle_gather(const ShufflePlan& pl, const uint32_t* d_perm, const Aff* d_kr, const Aff* d_ks, Aff* d_t, Aff* d_u, Aff* d_zipped, hipStream_t s);
 // d_mjac[i] = the affine point d_pp[i * pp_stride + m_slot] as a Jacobian one
 void launch_shuffle_commit(const Aff* d_pp, size_t pp_stride, uint32_t m_slot, uint32_t count, Jac* d_mjac, hipStream_t s);
+
+// ---- which trackers a set of keys opens (find.hip; plan and per-pair body in find_plan.hpp) ----
+struct FindPlan;
+// table path, one chunk: d_tab = the chunk's table of multiples (launch_table_build with 32 plain copies, step_bits 8, then launch_fix_build at
+// cbits 8) of the nc trackers from col_first on; d_keys: n_keys scalars in Montgomery form; d_claimed: the decoded k_r_G of all trackers;
+// d_status: the decoder's verdicts, r_G plane | k_r_G plane; d_owner[i] = min(d_owner[i], j) for every key j that opens tracker i
+void launch_find_scan(const FindPlan& pl, const TFix* d_tab, size_t nc, size_t col_first, const Fr* d_keys, const Aff* d_claimed, const uint8_t* d_status,
+                      uint32_t* d_owner, hipStream_t s);
+// ladder path: d_prod[j * n_trackers + i] = k_j r_G_i (launch_smul, one task per key); d_owner[i] = the smallest such j equal to k_r_G_i, or CPX_NO_OWNER
+void launch_find_compare(const Aff* d_prod, const Aff* d_claimed, const uint8_t* d_status, size_t n_trackers, size_t n_keys, uint32_t* d_owner, hipStream_t s);
 
 void launch_sum_jac(const Jac* d_in, int n, Jac* d_out, int* d_flag, hipStream_t s);
 void launch_bench_fpmul(Fp* d_data, int blocks, int iters, hipStream_t s);

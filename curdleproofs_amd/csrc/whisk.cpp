@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 #include "engine.hpp"
+#include "find_plan.hpp"
 
 namespace cpx {
 
@@ -328,6 +329,105 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
   CPX_HIP(hipMemcpyAsync(status, dver.p, count * sizeof(int), hipMemcpyDeviceToHost, stream_));
   CPX_HIP(hipStreamSynchronize(stream_));
   flush_timers();
+}
+
+// ---------------------------------------------------------------- which trackers a set of keys opens (find.hip, find_plan.hpp)
+// k_j * r_G_i == k_r_G_i (whisk.rs:36-55, the multiplication of whisk.rs:323) for every (tracker, key) pair: the trackers and the keys go up once,
+// every point is decoded once, and either ONE k_smul + ONE k_find_compare run (few keys), or per chunk of trackers k_table_build + k_fix_build +
+// k_find_scan (many keys) — the number of launches never depends on n_keys.  The owners and the decoding verdicts come down and the stream is
+// synchronised once.  Scratch is the tier-0 set; the table and its build scratch live for the call only.
+void Engine::whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, size_t n_keys, const uint8_t* k, uint32_t* owner, int* status) {
+  for (size_t i = 0; i < n_trackers; i++) {   // an entry the device never wrote is never read as an owner
+    status[i] = CPX_ERR_INTERNAL;
+    owner[i] = CPX_NO_OWNER;
+  }
+  if (!n_trackers) return;
+  if (!find_fits(n_trackers, n_keys)) throw ArgError("find trackers: at most 2^23 trackers, 2^20 keys and 2^32 pairs per call");
+  CPX_HIP(hipSetDevice(device_));
+  trackers = canonical_infinities(trackers, 96 * n_trackers, n_trackers, 96, {0, 48});
+  struct Trim {
+    Engine* e;
+    ~Trim() {
+      tier0_trim(e->t0_.bytes);
+      tier0_trim(e->t0_.a0);
+      tier0_trim(e->t0_.a1);
+      tier0_trim(e->t0_.dig);
+      tier0_trim(e->t0_.status);
+      tier0_trim(e->t0_.fr);
+      tier0_trim(e->t0_.stask);
+    }
+  } trim{this};
+  const FindPlan pl = find_plan(n_trackers, n_keys, opt_.find_table_min_keys, opt_.find_table_mb);
+  const size_t n = n_trackers;
+  DevBuf<uint8_t>&din = t0_.bytes, &dst = t0_.status;   // the trackers; decoding verdicts r_G plane | k_r_G plane
+  DevBuf<uint32_t>& dwords = t0_.dig;                   // 2 n byte offsets of the encodings | n owners
+  DevBuf<Aff>&dpts = t0_.a0, &dprod = t0_.a1;           // r_G | k_r_G decoded; ladder path: k_j r_G_i, key-major
+  DevBuf<Fr>& dkeys = t0_.fr;
+  DevBuf<SmulTask>& dtask = t0_.stask;
+  din.ensure(96 * n);
+  dst.ensure(2 * n);
+  dwords.ensure(3 * n);
+  dpts.ensure(2 * n);
+  dkeys.ensure(std::max<size_t>(n_keys, 1));
+  uint32_t* d_owner = dwords.p + 2 * n;
+  const Aff *d_r = dpts.p, *d_claimed = dpts.p + n;
+  const size_t plane_off[2] = {0, 48}, plane_rec[2] = {96, 96};
+  std::vector<uint32_t> off;
+  tracker_point_offsets(n, plane_off, plane_rec, 2, off);
+  CPX_HIP(hipMemcpyAsync(din.p, trackers, 96 * n, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(dwords.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  if (n_keys) CPX_HIP(hipMemcpyAsync(dkeys.p, k, n_keys * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemsetAsync(d_owner, 0xff, n * sizeof(uint32_t), stream_));   // CPX_NO_OWNER
+  tick("k_decompress", 0, 2.0 * n);
+  launch_decompress(opt_, din.p, (int)(2 * n), dpts.p, nullptr, dst.p, 1, stream_, dwords.p);
+  tock();
+  DevBuf<TFix> tab;   // table path: one chunk's table, its shifted copies and the build scratch; released when the call ends
+  DevBuf<TAff> shift;
+  DevBuf<TblTmp> tmp;
+  std::vector<SmulTask> tasks;
+  if (pl.table) {
+    tab.ensure(FindPlan::table_entries(pl.chunk_cols));
+    shift.ensure(FindPlan::shift_entries(pl.chunk_cols));
+    tmp.ensure(FindPlan::tmp_entries(pl.chunk_cols, pl.fix_chunk));
+    for (size_t c = 0; c < pl.n_chunks; c++) {
+      const size_t first = pl.chunk_first(c), nc = pl.chunk_size(c);
+      // copy w = 256^w r_G for the nc trackers of the chunk, then the multiples m 256^w r_G: the CRS table at fix_bits = 8, a tracker per column
+      tick("k_table_build", 0, (double)nc);
+      launch_table_build(opt_, d_r + first, 0, shift.p, 1, 0, (int)nc, (int)nc, FIND_WINDOWS, false, tmp.p, stream_, 8);
+      tock();
+      tick("k_fix_build", (double)(FindPlan::table_entries(nc) * sizeof(TFix)), (double)FindPlan::table_entries(nc));
+      launch_fix_build(shift.p, (int)nc, 8, tab.p, tmp.p, pl.fix_chunk, stream_);
+      tock();
+      tick("k_find_scan", 32.0 * sizeof(TFix) * nc * n_keys, (double)nc * n_keys);
+      launch_find_scan(pl, tab.p, nc, first, dkeys.p, d_claimed, dst.p, d_owner, stream_);
+      tock();
+    }
+  } else if (n_keys) {
+    dprod.ensure(n * n_keys);
+    dtask.ensure(n_keys);
+    // one task per key, the key shared by its n elements; the subgroup-checked decoding is what makes k_smul's endomorphism split valid
+    // (scale_any_point as in Engine::scale)
+    const uint32_t fl = opt_.scale_any_point ? SMUL_PLAIN : 0u;
+    tasks.resize(n_keys);
+    for (size_t j = 0; j < n_keys; j++) tasks[j] = SmulTask{nullptr, d_r, dprod.p + j * n, dkeys.p + j, 0, fl};
+    CPX_HIP(hipMemcpyAsync(dtask.p, tasks.data(), tasks.size() * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
+    tick("k_smul", 224.0 * n * n_keys, (double)n * n_keys);
+    count_smul_quad(launch_smul(dtask.p, (int)n_keys, (int)n, stream_, false, fl ? 0 : opt_.smul_quad_max));
+    tock();
+    tick("k_find_compare", (double)sizeof(Aff) * n * n_keys, (double)n * n_keys);
+    launch_find_compare(dprod.p, d_claimed, dst.p, n, n_keys, d_owner, stream_);
+    tock();
+  }
+  std::vector<uint8_t> st(2 * n);
+  CPX_HIP(hipMemcpyAsync(owner, d_owner, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(st.data(), dst.p, 2 * n, hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipStreamSynchronize(stream_));
+  flush_timers();
+  for (size_t i = 0; i < n; i++) {
+    const bool bad = st[i] != 0 || st[n + i] != 0;
+    status[i] = bad ? CPX_ERR_DESERIALIZE : CPX_OK;
+    if (bad) owner[i] = CPX_NO_OWNER;   // (the kernels mask by the verdicts; an identity left by a failed decode never matches)
+  }
 }
 
 // ---------------------------------------------------------------- trackers and k commitments, `count` per call (genmul.hip)

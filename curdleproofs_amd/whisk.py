@@ -9,7 +9,7 @@ are omitted — draws them from the OS CSPRNG (`secrets`), which is what a produ
 import ctypes
 import secrets
 
-from . import AFF, FR, CPX_ERR_DESERIALIZE, CPX_ERR_INTERNAL, CPX_ERR_VERIFY, CPX_OK, CpxError, _in, _out   # noqa: F401
+from . import AFF, FR, CPX_ERR_DESERIALIZE, CPX_ERR_INTERNAL, CPX_ERR_VERIFY, CPX_NO_OWNER, CPX_OK, CpxError, _in, _out   # noqa: F401
 from . import params as pr
 
 FIELD_ELEMENT_SIZE = 32        # whisk.rs:21
@@ -309,6 +309,31 @@ def k_commitments(ctx, ks):
         return []
     cb = ctx.generator_mul(b"".join(ks), compressed=True)[1]
     return [cb[48 * i:48 * (i + 1)] for i in range(len(ks))]
+
+
+# ---- which trackers a set of keys opens (cpx_whisk_find_trackers) ----
+def find_trackers(ctx, trackers, ks):
+    """The relation of whisk.rs:36-55, k * r_G == k_r_G, for every (tracker, key) pair in ONE library call.  ks: list of 32-byte wire scalars.
+    Returns (owners, status): owners[i] is the smallest index j whose key opens tracker i (an int) or None; status[i] is True, or a
+    SerializationError INSTANCE where a half of the tracker does not decode (its owner is None); nothing is raised per item.  A tracker
+    whose two halves are the identity is opened by every key (owner 0); of duplicate keys the smaller index is reported."""
+    if any(len(x) != FR for x in ks):
+        raise ValueError("k is a 32-byte wire scalar")
+    n, nk = len(trackers), len(ks)
+    if n > 1 << 23 or nk > 1 << 20 or n * nk > 1 << 32:
+        raise ValueError("at most 2^23 trackers, 2^20 keys and 2^32 pairs per call")
+    if n == 0:
+        return [], []
+    owner = (ctypes.c_uint32 * n)(*([CPX_NO_OWNER] * n))
+    status = (ctypes.c_int * n)(*([CPX_ERR_INTERNAL] * n))   # an entry the library does not write is never read as an owner
+    ctx._check(ctx._L.cpx_whisk_find_trackers(ctx._h, n, _in(_cat(trackers)), nk, _in(b"".join(ks)) if nk else None, owner, status))
+    owners, res = [], []
+    for i, st in enumerate(status):
+        if st not in (CPX_OK, CPX_ERR_DESERIALIZE):
+            raise CpxError(st, "tracker %d" % i)
+        res.append(True if st == CPX_OK else SerializationError("tracker %d" % i))
+        owners.append(int(owner[i]) if st == CPX_OK and owner[i] != CPX_NO_OWNER else None)
+    return owners, res
 
 
 # ---- small helpers of whisk.rs:295-345 ----

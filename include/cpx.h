@@ -279,6 +279,30 @@ int cpx_g1_generator_mul(cpx_ctx* ctx, size_t count, const uint8_t* scalars /* c
 int cpx_whisk_trackers_from_k_r(cpx_ctx* ctx, size_t count, const uint8_t* k /* count*32 */, const uint8_t* r /* count*32 */,
                                 uint8_t* trackers_out /* count*96 */, uint8_t* k_commitments_out /* count*48 */);
 
+/* Which trackers belong to a set of keys: the defining relation of a tracker, k * r_G == k_r_G, tested for every (tracker, key) pair in one call.
+ * A validator tests the shuffled trackers against its k; an operator tests them against all of its keys — n_trackers * n_keys independent scalar
+ * multiplications.  With fewer than option "find_table_min_keys" keys (default 256) every pair is one element of the scalar-multiplication kernel
+ * (k_smul) and one kernel compares; from that many keys on the trackers are processed in chunks: per chunk a table of the multiples
+ * m * 256^w * r_G (m = 1..128, 32 windows, 0.56 MiB per tracker; a chunk's table and build scratch stay within option "find_table_mb", default
+ * 1024 MiB) is built on the device and scanned with at most 32 mixed additions per pair, no doubling and no inversion (k_find_scan; plan in
+ * curdleproofs_amd/csrc/find_plan.hpp, measurements in profiles/find_trackers.md).  The answers do not depend on the path.
+ *   owner[i]   the smallest j with k_j * r_G_i == k_r_G_i, or CPX_NO_OWNER if no key opens tracker i
+ *   status[i]  CPX_OK, or CPX_ERR_DESERIALIZE when either half does not decode (on the curve, in the subgroup, option "strict_infinity" governing
+ *              infinity encodings as in the tracker calls); such a tracker has owner[i] = CPX_NO_OWNER
+ * Two consequences of the relation: a tracker whose r_G is the identity is opened by EVERY key iff its k_r_G is the identity too (its owner is then 0,
+ * provided n_keys > 0), and of duplicate keys the smaller index is reported.  Conventions of the batched tracker calls: CPX_OK whatever the items say;
+ * status is pre-filled with CPX_ERR_INTERNAL and owner with CPX_NO_OWNER; n_trackers = 0 is a no-op; with n_keys = 0 the trackers are still decoded and
+ * none has an owner (k may then be NULL); a NULL pointer with work to do is CPX_ERR_ARG and nothing is written; no CRS is needed and the loaded batch is
+ * untouched.  Keys are 32-byte Montgomery limbs; limbs >= r are NOT rejected and stand for limbs / 2^256 mod r, as k does in the other calls.
+ * Limits: n_trackers <= 2^23, n_keys <= 2^20, n_trackers * n_keys <= 2^32; beyond them the call is CPX_ERR_ARG before anything is read.  The ladder
+ * path holds all n_trackers * n_keys products (96 B each) on the device.  ONE stream synchronisation per call; the number of kernel launches depends
+ * on the number of table chunks only, never on n_keys. */
+#define CPX_NO_OWNER 0xffffffffu
+/* whisk.rs:36-55 (a tracker is r_G || k_r_G with k_r_G = k * r_G) and whisk.rs:323 for every (tracker, key) pair */
+int cpx_whisk_find_trackers(cpx_ctx* ctx, size_t n_trackers, const uint8_t* trackers /* n_trackers*96 */,
+                            size_t n_keys, const uint8_t* k /* n_keys*32, Montgomery limbs */,
+                            uint32_t* owner /* n_trackers */, int* status /* n_trackers */);
+
 /* The shuffle half of the byte-level API for `count` independent shuffles per call: compressed bytes in, compressed bytes out, and between
  * the uploads and the downloads every step runs on the device in a number of kernel launches that does not depend on count — decoding, the
  * scalar multiplications, the permutation, M (the fixed-base CRS table), normalisation and compression; the proving and verifying is
@@ -318,7 +342,7 @@ int cpx_set_profiling(cpx_ctx* ctx, int on); /* time every kernel group with HIP
 int cpx_reset_stats(cpx_ctx* ctx);
 /* name = kernel name as rocprofv3 reports it, template arguments included: "k_msm_fix<16, 16>", "k_msm_tblw<32, false>",
  * "k_msm_tblw<2, true>", "k_msm_accw", "k_reduce_sets", "k_finalize_ranges", "k_table_build", "k_msm_tail", "k_smul",
- * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_vs_crs_sum_groups" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
+ * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_vs_crs_sum_groups" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
  * "k_smul" times the one-lane and the quad form alike; "k_smul_quad" counts (launches only) those of them that ran as k_smul_quad;
  * units = MSM points / scalar-mul elements / points; out pointers may be NULL */
 int cpx_get_stat(const cpx_ctx* ctx, const char* name, uint64_t* launches, double* total_ms, double* algorithmic_bytes, double* units);

@@ -29,6 +29,7 @@ pub const CPX_ERR_HIP: c_int = -3;
 pub const CPX_ERR_VERIFY: c_int = -4;
 pub const CPX_ERR_DESERIALIZE: c_int = -5;
 pub const CPX_ERR_STATE: c_int = -6;
+pub const CPX_NO_OWNER: u32 = 0xffff_ffff;
 pub const CPX_ERR_INTERNAL: c_int = -7;
 
 extern "C" {
@@ -87,6 +88,9 @@ extern "C" {
     // what those calls consume, `count` per call, as multiples of the generator on its fixed-base table (whisk.rs:45-55, :370); either output may be null
     pub fn cpx_g1_generator_mul(ctx: *mut cpx_ctx, count: usize, scalars: *const u8, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
     pub fn cpx_whisk_trackers_from_k_r(ctx: *mut cpx_ctx, count: usize, k: *const u8, r: *const u8, trackers_out: *mut u8, k_commitments_out: *mut u8) -> c_int;
+    // which key opens which tracker, k_j * r_G_i == k_r_G_i (whisk.rs:36-55, :323) for every pair: owner[i] = the smallest such j or CPX_NO_OWNER,
+    // status[i] = CPX_OK / CPX_ERR_DESERIALIZE; k may be null with n_keys = 0
+    pub fn cpx_whisk_find_trackers(ctx: *mut cpx_ctx, n_trackers: usize, trackers: *const u8, n_keys: usize, k: *const u8, owner: *mut u32, status: *mut c_int) -> c_int;
     // `count` shuffles per call (util.rs:83-106, whisk.rs:144-179, :106-130): the instances become the loaded batch; per-item status / verdict
     pub fn cpx_batch_shuffle(ctx: *mut cpx_ctx, count: usize, vec_r: *const u8, vec_s: *const u8, permutation: *const u32, k: *const u8, vec_m_blinders: *const u8,
                              vec_t_out: *mut u8, vec_u_out: *mut u8, m_out: *mut u8) -> c_int;

@@ -149,6 +149,26 @@ pub fn trackers_from_k_r(ks: &[Fr], rs: &[Fr]) -> (Vec<WhiskTracker>, Vec<[u8; 4
     (trackers, kc.chunks(48).map(|c| c.try_into().unwrap()).collect())
 }
 
+/// Which of `ks` opens each tracker: the relation of whisk.rs:36-55, `k * r_G == k_r_G`, for every (tracker, key) pair in one library call.
+/// Per tracker `Ok(Some(j))` with the smallest such j, `Ok(None)` when no key opens it, `Err` when one of its halves does not decode.
+pub fn find_whisk_trackers(trackers: &[WhiskTracker], ks: &[Fr]) -> Vec<Result<Option<usize>, SerializationError>> {
+    let n = trackers.len();
+    let wire = trackers_to_wire(trackers);
+    let mut owner = vec![CPX_NO_OWNER; n];
+    let mut status = vec![CPX_ERR_INTERNAL; n]; // an entry the library does not write is never read as an owner
+    let rc = unsafe { cpx_whisk_find_trackers(ctx(), n, wire.as_ptr(), ks.len(), scalars_ptr(ks), owner.as_mut_ptr(), status.as_mut_ptr()) };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    owner
+        .iter()
+        .zip(status.iter())
+        .map(|(&o, &st)| match st {
+            CPX_OK => Ok(if o == CPX_NO_OWNER { None } else { Some(o as usize) }),
+            CPX_ERR_DESERIALIZE => Err(SerializationError::InvalidData),
+            other => panic!("libcpx: {}", other),
+        })
+        .collect()
+}
+
 /// whisk.rs:370 `get_k_commitment` for many k in one library call
 pub fn k_commitments(ks: &[Fr]) -> Vec<[u8; 48]> {
     let mut kc = vec![0u8; 48 * ks.len()];
