@@ -2,12 +2,12 @@
 // the group arithmetic exists here; every point operation below is a kernel launch (kernels.hip).
 #include "engine.hpp"
 #include "host_verify.hpp"
-#include "tier0_plan.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <exception>
 #include <thread>
 
 namespace cpx {
@@ -646,67 +646,78 @@ void Engine::crs_sums(uint8_t* g_sum, uint8_t* h_sum) const {
 }
 
 // ---------------------------------------------------------------- tier 0
+Engine::CallScope::CallScope(Engine* e) : e_(e), uncaught_(std::uncaught_exceptions()) {
+  if (e->in_call_) throw std::logic_error("a tier-0 call inside a tier-0 call: their scratch scopes do not nest");
+  CPX_HIP(hipSetDevice(e->device_));
+  e->in_call_ = true;
+}
+void Engine::CallScope::finish() {
+  CPX_HIP(hipStreamSynchronize(e_->stream_));   // the results are in the caller's buffers; the scratch may be reused by the next call
+  e_->flush_timers();
+}
+Engine::CallScope::~CallScope() {
+  if (std::uncaught_exceptions() != uncaught_) {   // the call threw: nothing it enqueued may outlive it, none of its timings is read
+    (void)hipStreamSynchronize(e_->stream_);
+    set_launch_events(nullptr, nullptr);
+    e_->span_ = false;
+    for (auto& t : e_->pending_) {
+      (void)hipEventDestroy(t.a);
+      (void)hipEventDestroy(t.b);
+    }
+    e_->pending_.clear();
+  }
+  const auto trim = [](auto& b) {
+    if (b.bytes() > kTier0Keep) b.release();
+  };
+  Tier0::each(e_->t0_, trim);
+  ShuffleBufs::each(e_->sh_, trim);
+  if (!e_->t0_.gen.p) e_->t0_.gen_n = 0;
+  e_->in_call_ = false;
+}
+
 void Engine::msm(const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t* out_jac) {
-  CPX_HIP(hipSetDevice(device_));
+  if ((long)n >= opt_.msm_endo_min && n) {   // endomorphism split + radix-256 bucket lists (the verifier's kernel): 32 additions per point
+    const uint32_t len = (uint32_t)n;
+    Tier0MsmPlan pl;   // msm_many's plan of one task, without its limits
+    pl.count = 1;
+    pl.points = n;
+    pl.max_n = len;
+    pl.conv_off.assign(1, 0);
+    msm_lists(pl, &len, bases, scalars, out_jac, nullptr);
+    return;
+  }
+  MsmTask t;
+  CallScope call(this);
   DevBuf<Aff>& db = t0_.a0;   // (tier-0 scratch of the engine, engine.hpp: no allocation on the call path once warm)
   DevBuf<Fr>& ds = t0_.fr;
   DevBuf<MsmTask>& dt = t0_.mtask;
   DevBuf<TJac>&w = t0_.w, &pt = t0_.pt;
   DevBuf<Jac>& res = t0_.res;
-  struct Trim {
-    Engine* e;
-    ~Trim() {
-      tier0_trim(e->t0_.a0);
-      tier0_trim(e->t0_.fr);
-      tier0_trim(e->t0_.conv);
-      tier0_trim(e->t0_.dig);
-    }
-  } trim{this};
+  DevBuf<TAff>& conv = t0_.conv;
   db.ensure(std::max<size_t>(n, 1));
   ds.ensure(std::max<size_t>(n, 1));
   dt.ensure(1);
   w.ensure(64);
   pt.ensure(8);
   res.ensure(1);
+  conv.ensure(2 * std::max<size_t>(n, 1));
   if (n) {
     CPX_HIP(hipMemcpyAsync(db.p, bases, n * sizeof(Aff), hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(ds.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   }
-  MsmTask t{db.p, nullptr, ds.p, (uint32_t)n, 0, 0};
+  t = MsmTask{db.p, nullptr, ds.p, (uint32_t)n, 0, 0};
   CPX_HIP(hipMemcpyAsync(dt.p, &t, sizeof t, hipMemcpyHostToDevice, stream_));
-  DevBuf<TAff>& conv = t0_.conv;
-  conv.ensure(2 * std::max<size_t>(n, 1));
-  if ((long)n >= opt_.msm_endo_min && n) {   // endomorphism split + radix-256 bucket lists (the verifier's kernel): 32 additions per point
-    DevBuf<TblTask>& tt = t0_.ttask;
-    DevBuf<TJac>& part = t0_.part;
-    DevBuf<uint32_t>& dig = t0_.dig;
-    const int slices = msm_tblw_slices(opt_, 1, 2, (int)n);
-    tt.ensure(1);
-    part.ensure(32 * (size_t)slices);
-    dig.ensure(9 * n);
-    main_.ensure(32 * (size_t)slices, 0);
-    tick("k_msm_tblw<2, true>", 128.0 * n, (double)n);
-    launch_msm_endo(dt.p, 1, (int)n, conv.p, dig.p, tt.p, main_.raw.p, main_.rawslot.p, stream_, slices);
-    tock();
-    reduce_sets(stream_, main_, 0, 32 * (size_t)slices, part.p);
-    launch_msm_tail(opt_, part.p, nullptr, res.p, 1, 16, 8, stream_, nullptr, 0, 2 * slices);
-    CPX_HIP(hipMemcpyAsync(out_jac, res.p, sizeof(Jac), hipMemcpyDeviceToHost, stream_));
-    CPX_HIP(hipStreamSynchronize(stream_));   // the result is in out_jac; the scratch may be reused by the next call
-    flush_timers();
-    return;
-  }
   tick("k_msm_accw", 128.0 * n, (double)n);
   launch_msm_accum(dt.p, 1, (int)n, conv.p, w.p, stream_);
   tock();
   launch_msm_tail(opt_, w.p, pt.p, nullptr, 8, 8, 4, stream_);
   launch_msm_tail(opt_, pt.p, nullptr, res.p, 1, 8, 32, stream_);
   CPX_HIP(hipMemcpyAsync(out_jac, res.p, sizeof(Jac), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
 }
 void Engine::normalize(const uint8_t* jac, size_t n, uint8_t* out_aff, uint8_t* out_comp) {
-  CPX_HIP(hipSetDevice(device_));
   if (!n) return;
+  CallScope call(this);
   DevBuf<Jac>& dj = t0_.jin;
   DevBuf<Aff>& da = t0_.a0;
   DevBuf<uint8_t>& dc = t0_.bytes;
@@ -717,13 +728,11 @@ void Engine::normalize(const uint8_t* jac, size_t n, uint8_t* out_aff, uint8_t* 
   launch_finalize(dj.p, (int)n, da.p, nullptr, dc.p, stream_);
   if (out_aff) CPX_HIP(hipMemcpyAsync(out_aff, da.p, n * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
   if (out_comp) CPX_HIP(hipMemcpyAsync(out_comp, dc.p, n * 48, hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  tier0_trim(dj);
-  tier0_trim(da);
-  tier0_trim(dc);
+  call.finish();
 }
 bool Engine::sum_jac(const uint8_t* points_jac, size_t n, uint8_t* out_jac) {
-  CPX_HIP(hipSetDevice(device_));
+  int flag = 0;
+  CallScope call(this);
   DevBuf<Jac>&din = t0_.jin, &dout = t0_.res;
   DevBuf<int>& dflag = t0_.flag;
   din.ensure(std::max<size_t>(n, 1));
@@ -731,45 +740,23 @@ bool Engine::sum_jac(const uint8_t* points_jac, size_t n, uint8_t* out_jac) {
   dflag.ensure(1);
   if (n) CPX_HIP(hipMemcpyAsync(din.p, points_jac, n * sizeof(Jac), hipMemcpyHostToDevice, stream_));
   launch_sum_jac(din.p, (int)n, dout.p, dflag.p, stream_);
-  int flag = 0;
   CPX_HIP(hipMemcpyAsync(out_jac, dout.p, sizeof(Jac), hipMemcpyDeviceToHost, stream_));
   CPX_HIP(hipMemcpyAsync(&flag, dflag.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  tier0_trim(din);
+  call.finish();
   return flag != 0;
 }
-void Engine::msm_jac(const uint8_t* bases_jac, const uint8_t* scalars, size_t n, uint8_t* out_jac) {
+void Engine::msm_jac(const uint8_t* bases_jac, const uint8_t* scalars, size_t n, uint8_t* out_jac) {   // (two calls, one scope after the other)
   std::vector<uint8_t> aff(std::max<size_t>(n, 1) * sizeof(Aff));
   normalize(bases_jac, n, aff.data(), nullptr);
   msm(aff.data(), scalars, n, out_jac);
 }
 void Engine::fold(uint8_t* PL, const uint8_t* PR, const uint8_t* gamma, size_t half) {
-  CPX_HIP(hipSetDevice(device_));
-  if (!half) return;
-  DevBuf<Aff>&dl = t0_.a0, &dr = t0_.a1;
-  DevBuf<Fr>& dg = t0_.fr;
-  DevBuf<SmulTask>& dt = t0_.stask;
-  dl.ensure(half);
-  dr.ensure(half);
-  dg.ensure(1);
-  dt.ensure(1);
-  CPX_HIP(hipMemcpyAsync(dl.p, PL, half * sizeof(Aff), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(dr.p, PR, half * sizeof(Aff), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(dg.p, gamma, sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  SmulTask t{dl.p, dr.p, dl.p, dg.p, 0, opt_.scale_any_point ? SMUL_PLAIN : 0u};
-  CPX_HIP(hipMemcpyAsync(dt.p, &t, sizeof t, hipMemcpyHostToDevice, stream_));
-  tick("k_smul", 288.0 * half, (double)half);
-  launch_smul(dt.p, 1, (int)half, stream_);
-  tock();
-  CPX_HIP(hipMemcpyAsync(PL, dl.p, half * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
-  tier0_trim(dl);
-  tier0_trim(dr);
+  if (half) fold_lanes(1, half, PL, PR, gamma, 0);   // quad_max 0: cpx_g1_fold keeps the one-lane k_smul (kernels.h, option fold_quad_max)
 }
 void Engine::scale(const uint8_t* P, const uint8_t* scalars, size_t scalar_stride, size_t n, uint8_t* out) {
-  CPX_HIP(hipSetDevice(device_));
   if (!n) return;
+  SmulTask t;
+  CallScope call(this);
   DevBuf<Aff>&dp = t0_.a0, &dout = t0_.a1;
   DevBuf<Fr>& dsc = t0_.fr;
   DevBuf<SmulTask>& dt = t0_.stask;
@@ -780,17 +767,13 @@ void Engine::scale(const uint8_t* P, const uint8_t* scalars, size_t scalar_strid
   dt.ensure(1);
   CPX_HIP(hipMemcpyAsync(dp.p, P, n * sizeof(Aff), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dsc.p, scalars, ns * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  SmulTask t{nullptr, dp.p, dout.p, dsc.p, scalar_stride ? 1u : 0u, opt_.scale_any_point ? SMUL_PLAIN : 0u};
+  t = SmulTask{nullptr, dp.p, dout.p, dsc.p, scalar_stride ? 1u : 0u, opt_.scale_any_point ? SMUL_PLAIN : 0u};
   CPX_HIP(hipMemcpyAsync(dt.p, &t, sizeof t, hipMemcpyHostToDevice, stream_));
   tick("k_smul", 224.0 * n, (double)n);
   launch_smul(dt.p, 1, (int)n, stream_);
   tock();
   CPX_HIP(hipMemcpyAsync(out, dout.p, n * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
-  tier0_trim(dp);
-  tier0_trim(dout);
-  tier0_trim(dsc);
+  call.finish();
 }
 // The cross terms of one log round (inner_product_argument.rs:158-161: 4, same_multiscalar_argument.rs:107-112: 6) as ONE call: `count`
 // independent MSMs of ragged lengths, all of them tasks of the endomorphism bucket-list path in one launch each — k_to_table_endo +
@@ -803,7 +786,13 @@ void Engine::msm_many(size_t count, const uint32_t* lens, const uint8_t* bases, 
   Tier0MsmPlan pl;
   if (!tier0_msm_plan(count, lens, pl)) throw ArgError("cpx_g1_msm_many: at most 2^16 MSMs and 2^24 points per call");
   if (!out_jac && !out_comp) return;
-  CPX_HIP(hipSetDevice(device_));
+  msm_lists(pl, lens, bases, scalars, out_jac, out_comp);
+}
+// ... and its body, which cpx_g1_msm takes with a plan of one task
+void Engine::msm_lists(Tier0MsmPlan& pl, const uint32_t* lens, const uint8_t* bases, const uint8_t* scalars, uint8_t* out_jac, uint8_t* out_comp) {
+  const size_t count = pl.count, np = pl.points;
+  std::vector<MsmTask> tasks;
+  CallScope call(this);
   pl.slices = msm_tblw_slices(opt_, (int)count, 2, (int)pl.max_n);   // one value for every task of the call
   DevBuf<Aff>&db = t0_.a0, &daff = t0_.a1;
   DevBuf<Fr>& ds = t0_.fr;
@@ -814,19 +803,6 @@ void Engine::msm_many(size_t count, const uint32_t* lens, const uint8_t* bases, 
   DevBuf<TJac>& part = t0_.part;
   DevBuf<Jac>& res = t0_.res;
   DevBuf<uint8_t>& dcomp = t0_.bytes;
-  struct Trim {
-    Engine* e;
-    ~Trim() {
-      tier0_trim(e->t0_.a0);
-      tier0_trim(e->t0_.a1);
-      tier0_trim(e->t0_.fr);
-      tier0_trim(e->t0_.conv);
-      tier0_trim(e->t0_.dig);
-      tier0_trim(e->t0_.part);
-      tier0_trim(e->t0_.bytes);
-    }
-  } trim{this};
-  const size_t np = pl.points;
   db.ensure(std::max<size_t>(np, 1));
   ds.ensure(std::max<size_t>(np, 1));
   dt.ensure(count);
@@ -836,7 +812,7 @@ void Engine::msm_many(size_t count, const uint32_t* lens, const uint8_t* bases, 
   part.ensure(pl.sets());
   res.ensure(count);
   main_.ensure(pl.sets(), 0);
-  std::vector<MsmTask> tasks(count);   // (alive until the synchronisation below)
+  tasks.resize(count);
   for (size_t i = 0; i < count; i++) tasks[i] = MsmTask{db.p + pl.conv_off[i], nullptr, ds.p + pl.conv_off[i], lens[i], 0, pl.conv_off[i]};
   if (np) {
     CPX_HIP(hipMemcpyAsync(db.p, bases, np * sizeof(Aff), hipMemcpyHostToDevice, stream_));
@@ -859,8 +835,7 @@ void Engine::msm_many(size_t count, const uint32_t* lens, const uint8_t* bases, 
     tock();
     CPX_HIP(hipMemcpyAsync(out_comp, dcomp.p, count * 48, hipMemcpyDeviceToHost, stream_));
   }
-  CPX_HIP(hipStreamSynchronize(stream_));   // the results are in the caller's buffers; the scratch may be reused by the next call
-  flush_timers();
+  call.finish();
 }
 // The basis folds of one log round (inner_product_argument.rs:177-178: 2 families, same_multiscalar_argument.rs:128-130: 3) as ONE call:
 // a SmulTask per family, each with its own gamma shared by its `half` elements, in one launch_smul.  A round's folds are small (3 x 128
@@ -868,36 +843,32 @@ void Engine::msm_many(size_t count, const uint32_t* lens, const uint8_t* bases, 
 void Engine::fold_many(size_t families, size_t half, uint8_t* PL, const uint8_t* PR, const uint8_t* gammas) {
   if (!families || !half) return;
   if (!tier0_fold_fits(families, half)) throw ArgError("cpx_g1_fold_many: at most 2^24 elements per call");
-  CPX_HIP(hipSetDevice(device_));
+  fold_lanes(families, half, PL, PR, gammas, tier0_fold_quad_max(families * half, opt_.fold_quad_max, opt_.scale_any_point != 0));
+}
+// ... and its body, which cpx_g1_fold takes with one family
+void Engine::fold_lanes(size_t families, size_t half, uint8_t* PL, const uint8_t* PR, const uint8_t* gammas, long quad_max) {
   const size_t total = families * half;
+  std::vector<SmulTask> tasks;
+  CallScope call(this);
   DevBuf<Aff>&dl = t0_.a0, &dr = t0_.a1;
   DevBuf<Fr>& dg = t0_.fr;
   DevBuf<SmulTask>& dt = t0_.stask;
-  struct Trim {
-    Engine* e;
-    ~Trim() {
-      tier0_trim(e->t0_.a0);
-      tier0_trim(e->t0_.a1);
-      tier0_trim(e->t0_.fr);
-    }
-  } trim{this};
   dl.ensure(total);
   dr.ensure(total);
   dg.ensure(families);
   dt.ensure(families);
-  const bool plain = opt_.scale_any_point != 0;
-  std::vector<SmulTask> tasks(families);   // (alive until the synchronisation below)
-  for (size_t f = 0; f < families; f++) tasks[f] = SmulTask{dl.p + f * half, dr.p + f * half, dl.p + f * half, dg.p + f, 0, plain ? SMUL_PLAIN : 0u};
+  const uint32_t fl = opt_.scale_any_point ? SMUL_PLAIN : 0u;
+  tasks.resize(families);
+  for (size_t f = 0; f < families; f++) tasks[f] = SmulTask{dl.p + f * half, dr.p + f * half, dl.p + f * half, dg.p + f, 0, fl};
   CPX_HIP(hipMemcpyAsync(dl.p, PL, total * sizeof(Aff), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dr.p, PR, total * sizeof(Aff), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dg.p, gammas, families * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dt.p, tasks.data(), families * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
   tick("k_smul", 288.0 * total, (double)total);
-  count_smul_quad(launch_smul(dt.p, (int)families, (int)half, stream_, false, tier0_fold_quad_max(total, opt_.fold_quad_max, plain)));
+  count_smul_quad(launch_smul(dt.p, (int)families, (int)half, stream_, false, quad_max));
   tock();
   CPX_HIP(hipMemcpyAsync(PL, dl.p, total * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
 }
 // Encodings with the infinity flag set (include/cpx.h, option strict_infinity).  ark-bls12-381 ^0.4's `read_g1_compressed` — the
 // deserialiser behind `G1Affine::deserialize_compressed`, whisk.rs:313-320 — returns the identity as soon as the compression and the
@@ -932,9 +903,10 @@ const uint8_t* Engine::canonical_infinities(const uint8_t* bytes, size_t nbytes,
 }
 
 int Engine::decompress(const uint8_t* comp, size_t n, uint8_t* out_aff, int check_subgroup, uint8_t* status_out) {
-  CPX_HIP(hipSetDevice(device_));
   if (!n) return CPX_OK;
   comp = canonical_infinities(comp, n * 48, n, 48, {0});
+  std::vector<uint8_t> st;
+  CallScope call(this);
   DevBuf<uint8_t>&dc = t0_.bytes, &dst = t0_.status;
   DevBuf<Aff>& da = t0_.a0;
   dc.ensure(n * 48);
@@ -942,10 +914,10 @@ int Engine::decompress(const uint8_t* comp, size_t n, uint8_t* out_aff, int chec
   da.ensure(n);
   CPX_HIP(hipMemcpyAsync(dc.p, comp, n * 48, hipMemcpyHostToDevice, stream_));
   launch_decompress(opt_, dc.p, (int)n, da.p, nullptr, dst.p, check_subgroup, stream_);
-  std::vector<uint8_t> st(n);
+  st.resize(n);
   CPX_HIP(hipMemcpyAsync(out_aff, da.p, n * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
   CPX_HIP(hipMemcpyAsync(st.data(), dst.p, n, hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
+  call.finish();
   if (status_out) {   // per-point verdicts: the call itself succeeds
     memcpy(status_out, st.data(), n);
     return CPX_OK;

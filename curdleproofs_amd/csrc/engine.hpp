@@ -28,6 +28,7 @@
 #include "prove_reqs.hpp"
 #include "shuffle_plan.hpp"
 #include "tbl_plan.hpp"
+#include "tier0_plan.hpp"
 
 namespace cpx {
 
@@ -69,6 +70,7 @@ inline char g_pinned_memory_sync = 0;
 template <class T> struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
+  size_t bytes() const { return cap * sizeof(T); }
   void ensure(size_t n) {
     if (n <= cap) return;
     if (p) CPX_HIP(hipFree(p));
@@ -85,6 +87,9 @@ template <class T> struct DevBuf {
     if (p) (void)hipFree(p);
   }
 };
+template <class F, class... B> void each_buf(F&& f, B&... b) {   // f on every buffer of a list, whatever their element types
+  (f(b), ...);
+}
 template <class T> struct PinBuf {
   T* p = nullptr;
   size_t cap = 0;
@@ -238,6 +243,15 @@ class Engine {
       if (value) *value = B_ ? tbl_segments_for(B_) : 0;
       return true;
     }
+    // "tier0_scratch_bytes" = the device memory the tier-0 and batched Whisk scratch holds between calls (Tier0, ShuffleBufs below)
+    if (key && !strcmp(key, "tier0_scratch_bytes")) {
+      size_t sum = 0;
+      const auto add = [&](const auto& b) { sum += b.bytes(); };
+      Tier0::each(t0_, add);
+      ShuffleBufs::each(sh_, add);
+      if (value) *value = (long)sum;
+      return true;
+    }
     return cpx::get_option(opt_, key, value);
   }
   hipStream_t stream() const { return stream_; }
@@ -345,8 +359,9 @@ class Engine {
   };
   DevProver dprove_;
   // Scratch of the tier-0 calls (msm, fold, scale, normalize, decompress, sum_jac): kept between calls — a call used to allocate and free up to ten
-  // device buffers of its own (hipMalloc + hipFree: 1.9 ms per 256-point cpx_g1_msm, most of it the allocator); a buffer that has grown beyond
-  // kTier0Keep bytes for one large call is given back at the end of that call.
+  // device buffers of its own (hipMalloc + hipFree: 1.9 ms per 256-point cpx_g1_msm, most of it the allocator).  The contract: every buffer of
+  // this set and of ShuffleBufs that has grown beyond kTier0Keep bytes for one large call is given back at the end of that call, on every exit
+  // path — CallScope does it, through each(), which is the one place besides its declaration where a buffer is named.
   struct Tier0 {
     DevBuf<Aff> a0, a1;
     DevBuf<Fr> fr;
@@ -361,6 +376,9 @@ class Engine {
     DevBuf<int> flag;
     DevBuf<Aff> gen;      // copies of the generator: the base of the batched tracker prover's k G and blinder G (whisk.cpp)
     size_t gen_n = 0;     // how many of them are filled in
+    template <class Self, class F> static void each(Self& s, F&& f) {   // (Self: Tier0 or const Tier0)
+      each_buf(f, s.a0, s.a1, s.fr, s.mtask, s.stask, s.w, s.pt, s.part, s.res, s.jin, s.conv, s.ttask, s.dig, s.bytes, s.status, s.flag, s.gen);
+    }
   } t0_;
   // Scratch of the batched shuffle calls (whisk.cpp), kept and trimmed like the tier-0 set
   struct ShuffleBufs {
@@ -370,14 +388,32 @@ class Engine {
     DevBuf<Fr> fr;                        // k | blinders | the scalars of M
     DevBuf<Jac> mjac;
     DevBuf<SmulTask> stask;
+    template <class Self, class F> static void each(Self& s, F&& f) {
+      each_buf(f, s.bytes, s.status, s.bad, s.off, s.perm, s.pts, s.kpts, s.tu, s.zip, s.fr, s.mjac, s.stask);
+    }
   } sh_;
   // vec_T, vec_U and M of the plan's items from the device-resident vec_R | vec_S (sh_.pts), permutations, k and M scalars; loads the batch
-  void shuffle_device(const ShufflePlan& pl);
-  void shuffle_trim();
+  void shuffle_device(const ShufflePlan& pl, std::vector<SmulTask>& tasks);
   static constexpr size_t kTier0Keep = (size_t)64 << 20;
-  template <class T> static void tier0_trim(DevBuf<T>& b) {
-    if (b.cap * sizeof(T) > kTier0Keep) b.release();
-  }
+  // One tier-0 or batched Whisk call's hold on the two scratch sets, opened after the argument checks and before the first ensure.  The
+  // constructor selects the device; finish() ends the call's device work (stream synchronisation + flush_timers: both can throw, so it is not
+  // the destructor); the destructor never throws and keeps the contract above on every exit path.  Left by an exception, it first waits for
+  // the stream (best effort) and drops the profiling state of the call: the bound launch events and the events of pending_, unread.
+  // Scopes do not nest (std::logic_error): an inner scope's trim would release buffers the outer call still holds pointers into.
+  // Host memory that an enqueued copy reads or writes (task lists, offset tables, downloaded verdicts) is declared ABOVE the scope object,
+  // empty, and sized where it is needed: it must outlive the destructor's wait.
+  struct CallScope {
+    explicit CallScope(Engine* e);
+    void finish();
+    ~CallScope();
+    CallScope(const CallScope&) = delete;
+    Engine* e_;
+    const int uncaught_;
+  };
+  bool in_call_ = false;
+  // the bucket-list form of msm / msm_many and the body of fold / fold_many (engine.cpp): the single calls are the many-calls of one task
+  void msm_lists(Tier0MsmPlan& pl, const uint32_t* lens, const uint8_t* bases, const uint8_t* scalars, uint8_t* out_jac, uint8_t* out_comp);
+  void fold_lanes(size_t families, size_t half, uint8_t* PL, const uint8_t* PR, const uint8_t* gammas, long quad_max);
   void enqueue_prove_device();
   void exec_late_round(const LateRound& r, size_t comp_off, const char* what);
   // proofs per launch of the device prover's table build (option table_chunks).  Default: ALL rows in one launch while its scratch (15 doubled

@@ -194,8 +194,7 @@ void Engine::whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, 
   for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
   if (!count) return;
   if (count > kTrackerBatchMax) throw ArgError("tracker proofs: at most 2^23 per call");
-  CPX_HIP(hipSetDevice(device_));
-  const Aff G = generator();
+  const Aff G = generator();   // (before the scope: the first call decodes the generator, a tier-0 call of its own)
   // strict_infinity = 0: non-canonical infinity encodings are rewritten in COPIES of the inputs (canonical_infinities)
   std::vector<uint8_t> keep[2];
   auto canon = [&](const uint8_t* in, size_t rec, const std::vector<size_t>& offs, std::vector<uint8_t>* store) {
@@ -207,17 +206,8 @@ void Engine::whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, 
   trackers = canon(trackers, 96, {0, 48}, &keep[0]);
   k_commitments = canon(k_commitments, 48, {0}, &keep[1]);
   proofs = canon(proofs, 128, {0, 48}, nullptr);
-  struct Trim {
-    Engine* e;
-    ~Trim() {
-      tier0_trim(e->t0_.bytes);
-      tier0_trim(e->t0_.a0);
-      tier0_trim(e->t0_.dig);
-      tier0_trim(e->t0_.status);
-      tier0_trim(e->t0_.fr);
-      tier0_trim(e->t0_.flag);
-    }
-  } trim{this};
+  std::vector<uint32_t> off;
+  CallScope call(this);
   const int n = (int)count;
   DevBuf<uint8_t>&din = t0_.bytes, &dst = t0_.status;   // trackers | k_commitments | proofs; 5 count decoding verdicts | count proof flags
   DevBuf<uint32_t>& doff = t0_.dig;
@@ -233,7 +223,6 @@ void Engine::whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, 
   uint8_t *d_trk = din.p, *d_kc = din.p + 96 * count, *d_prf = din.p + 144 * count;
   // the five points of proof i are read where they lie: A, B inside the proof, k_r_G, r_G inside the tracker, k_G
   const size_t plane_off[5] = {144 * count, 144 * count + 48, 48, 0, 96 * count}, plane_rec[5] = {128, 128, 96, 96, 48};
-  std::vector<uint32_t> off;
   tracker_point_offsets(count, plane_off, plane_rec, 5, off);
   CPX_HIP(hipMemcpyAsync(d_trk, trackers, 96 * count, hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(d_kc, k_commitments, 48 * count, hipMemcpyHostToDevice, stream_));
@@ -250,8 +239,7 @@ void Engine::whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, 
   launch_tracker_relations(dpts.p, d_prf, dchal.p, dst.p + 5 * count, G, n, dver.p, stream_);
   tock();
   CPX_HIP(hipMemcpyAsync(verdict, dver.p, count * sizeof(int), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
 }
 
 // whisk.rs:228-263 generate_whisk_tracker_proof for every (tracker, k, blinder) triple
@@ -259,23 +247,12 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
   for (size_t i = 0; i < count; i++) status[i] = CPX_ERR_INTERNAL;
   if (!count) return;
   if (count > kTrackerBatchMax) throw ArgError("tracker proofs: at most 2^23 per call");
-  CPX_HIP(hipSetDevice(device_));
-  const Aff G = generator();
+  const Aff G = generator();   // (before the scope, as above)
   trackers = canonical_infinities(trackers, 96 * count, count, 96, {0, 48});
-  struct Trim {
-    Engine* e;
-    ~Trim() {
-      tier0_trim(e->t0_.bytes);
-      tier0_trim(e->t0_.a0);
-      tier0_trim(e->t0_.a1);
-      tier0_trim(e->t0_.dig);
-      tier0_trim(e->t0_.status);
-      tier0_trim(e->t0_.fr);
-      tier0_trim(e->t0_.flag);
-      tier0_trim(e->t0_.gen);
-      if (!e->t0_.gen.p) e->t0_.gen_n = 0;
-    }
-  } trim{this};
+  std::vector<Aff> g;
+  std::vector<uint32_t> off;
+  SmulTask tasks[3];
+  CallScope call(this);
   const int n = (int)count;
   DevBuf<uint8_t>&db = t0_.bytes, &dst = t0_.status;   // trackers | k_G, A, B compressed | proofs
   DevBuf<uint32_t>& doff = t0_.dig;
@@ -293,19 +270,18 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
   dver.ensure(count);
   if (t0_.gen_n < count) {   // grows with the largest call; filled once
     dgen.ensure(count);
-    std::vector<Aff> g(count, G);
+    g.assign(count, G);
     CPX_HIP(hipMemcpyAsync(dgen.p, g.data(), count * sizeof(Aff), hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipStreamSynchronize(stream_));   // (g leaves scope; only when the buffer grows)
+    CPX_HIP(hipStreamSynchronize(stream_));   // (gen_n counts copies that have arrived; only when the buffer grows)
     t0_.gen_n = count;
   }
   uint8_t *d_trk = db.p, *d_comp = db.p + 96 * count, *d_prf = db.p + 240 * count;
   const size_t plane_off[2] = {0, 48}, plane_rec[2] = {96, 96};
-  std::vector<uint32_t> off;
   tracker_point_offsets(count, plane_off, plane_rec, 2, off);
   const uint32_t fl = opt_.scale_any_point ? SMUL_PLAIN : 0u;   // (as Engine::scale)
-  const SmulTask tasks[3] = {{nullptr, dgen.p, dout.p, dsc.p, 1, fl},                              // k_G = k G
-                             {nullptr, dgen.p, dout.p + count, dsc.p + count, 1, fl},              // A = blinder G
-                             {nullptr, dtr.p, dout.p + 2 * count, dsc.p + count, 1, fl}};          // B = blinder r_G
+  tasks[0] = SmulTask{nullptr, dgen.p, dout.p, dsc.p, 1, fl};                              // k_G = k G
+  tasks[1] = SmulTask{nullptr, dgen.p, dout.p + count, dsc.p + count, 1, fl};              // A = blinder G
+  tasks[2] = SmulTask{nullptr, dtr.p, dout.p + 2 * count, dsc.p + count, 1, fl};           // B = blinder r_G
   CPX_HIP(hipMemcpyAsync(d_trk, trackers, 96 * count, hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dsc.p, k, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dsc.p + count, blinders, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
@@ -327,8 +303,7 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
   tock();
   CPX_HIP(hipMemcpyAsync(proofs_out, d_prf, 128 * count, hipMemcpyDeviceToHost, stream_));
   CPX_HIP(hipMemcpyAsync(status, dver.p, count * sizeof(int), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
 }
 
 // ---------------------------------------------------------------- which trackers a set of keys opens (find.hip, find_plan.hpp)
@@ -343,20 +318,11 @@ void Engine::whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, siz
   }
   if (!n_trackers) return;
   if (!find_fits(n_trackers, n_keys)) throw ArgError("find trackers: at most 2^23 trackers, 2^20 keys and 2^32 pairs per call");
-  CPX_HIP(hipSetDevice(device_));
   trackers = canonical_infinities(trackers, 96 * n_trackers, n_trackers, 96, {0, 48});
-  struct Trim {
-    Engine* e;
-    ~Trim() {
-      tier0_trim(e->t0_.bytes);
-      tier0_trim(e->t0_.a0);
-      tier0_trim(e->t0_.a1);
-      tier0_trim(e->t0_.dig);
-      tier0_trim(e->t0_.status);
-      tier0_trim(e->t0_.fr);
-      tier0_trim(e->t0_.stask);
-    }
-  } trim{this};
+  std::vector<uint32_t> off;
+  std::vector<SmulTask> tasks;
+  std::vector<uint8_t> st;
+  CallScope call(this);
   const FindPlan pl = find_plan(n_trackers, n_keys, opt_.find_table_min_keys, opt_.find_table_mb);
   const size_t n = n_trackers;
   DevBuf<uint8_t>&din = t0_.bytes, &dst = t0_.status;   // the trackers; decoding verdicts r_G plane | k_r_G plane
@@ -372,7 +338,6 @@ void Engine::whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, siz
   uint32_t* d_owner = dwords.p + 2 * n;
   const Aff *d_r = dpts.p, *d_claimed = dpts.p + n;
   const size_t plane_off[2] = {0, 48}, plane_rec[2] = {96, 96};
-  std::vector<uint32_t> off;
   tracker_point_offsets(n, plane_off, plane_rec, 2, off);
   CPX_HIP(hipMemcpyAsync(din.p, trackers, 96 * n, hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dwords.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
@@ -384,7 +349,6 @@ void Engine::whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, siz
   DevBuf<TFix> tab;   // table path: one chunk's table, its shifted copies and the build scratch; released when the call ends
   DevBuf<TAff> shift;
   DevBuf<TblTmp> tmp;
-  std::vector<SmulTask> tasks;
   if (pl.table) {
     tab.ensure(FindPlan::table_entries(pl.chunk_cols));
     shift.ensure(FindPlan::shift_entries(pl.chunk_cols));
@@ -418,11 +382,10 @@ void Engine::whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, siz
     launch_find_compare(dprod.p, d_claimed, dst.p, n, n_keys, d_owner, stream_);
     tock();
   }
-  std::vector<uint8_t> st(2 * n);
+  st.resize(2 * n);
   CPX_HIP(hipMemcpyAsync(owner, d_owner, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
   CPX_HIP(hipMemcpyAsync(st.data(), dst.p, 2 * n, hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
   for (size_t i = 0; i < n; i++) {
     const bool bad = st[i] != 0 || st[n + i] != 0;
     status[i] = bad ? CPX_ERR_DESERIALIZE : CPX_OK;
@@ -438,6 +401,7 @@ void Engine::whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, siz
 const TAff* Engine::generator_table() {
   if (!have_gen_tab_) {
     const Aff G = generator();
+    CallScope call(this);   // (selects the device; the launch stays enqueued for the caller's own scope to wait for)
     gen_tab_.ensure(gen_table_entries());
     tick("k_gen_table", (double)(gen_table_entries() * sizeof(TAff)), (double)gen_table_entries());
     launch_gen_table(G, gen_tab_.p, stream_);
@@ -451,16 +415,8 @@ const TAff* Engine::generator_table() {
 void Engine::generator_mul(size_t count, const uint8_t* scalars, uint8_t* out_affine, uint8_t* out_compressed) {
   if (!count || (!out_affine && !out_compressed)) return;
   if (count > kTrackerBatchMax) throw ArgError("generator multiples: at most 2^23 per call");
-  CPX_HIP(hipSetDevice(device_));
-  const TAff* tab = generator_table();   // (before the buffers below are taken: the first call decodes the generator in the same scratch)
-  struct Trim {
-    Engine* e;
-    ~Trim() {
-      tier0_trim(e->t0_.fr);
-      tier0_trim(e->t0_.a0);
-      tier0_trim(e->t0_.bytes);
-    }
-  } trim{this};
+  const TAff* tab = generator_table();   // (before the scope and the buffers below: the first call decodes the generator in the same scratch)
+  CallScope call(this);
   DevBuf<Fr>& dsc = t0_.fr;
   DevBuf<Aff>& dout = t0_.a0;
   DevBuf<uint8_t>& dcomp = t0_.bytes;
@@ -479,24 +435,15 @@ void Engine::generator_mul(size_t count, const uint8_t* scalars, uint8_t* out_af
     CPX_HIP(hipMemcpyAsync(out_compressed, dcomp.p, 48 * count, hipMemcpyDeviceToHost, stream_));
   }
   if (out_affine) CPX_HIP(hipMemcpyAsync(out_affine, dout.p, count * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
 }
 
 // whisk.rs:45-55 WhiskTracker::from_k_r and whisk.rs:370 get_k_commitment for every (k, r) pair
 void Engine::whisk_trackers_from_k_r(size_t count, const uint8_t* k, const uint8_t* r, uint8_t* trackers_out, uint8_t* k_commitments_out) {
   if (!count || (!trackers_out && !k_commitments_out)) return;
   if (count > kTrackerBatchMax) throw ArgError("trackers: at most 2^23 per call");
-  CPX_HIP(hipSetDevice(device_));
   const TAff* tab = generator_table();
-  struct Trim {
-    Engine* e;
-    ~Trim() {
-      tier0_trim(e->t0_.fr);
-      tier0_trim(e->t0_.a0);
-      tier0_trim(e->t0_.bytes);
-    }
-  } trim{this};
+  CallScope call(this);
   // points: r_0 G, k_0 r_0 G, r_1 G, ... (the trackers as they are serialised), then k_0 G, k_1 G, ...; without trackers only the latter
   const int mode = !trackers_out ? GEN_MUL_PLAIN : k_commitments_out ? GEN_MUL_BOTH : GEN_MUL_TRACKERS;
   const size_t points = count * (mode == GEN_MUL_PLAIN ? 1 : mode == GEN_MUL_TRACKERS ? 2 : 3);
@@ -517,8 +464,7 @@ void Engine::whisk_trackers_from_k_r(size_t count, const uint8_t* k, const uint8
   tock();
   if (trackers_out) CPX_HIP(hipMemcpyAsync(trackers_out, dcomp.p, 96 * count, hipMemcpyDeviceToHost, stream_));
   if (k_commitments_out) CPX_HIP(hipMemcpyAsync(k_commitments_out, dcomp.p + (trackers_out ? 96 * count : 0), 48 * count, hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
 }
 
 // ---------------------------------------------------------------- shuffle step and shuffle proofs, `count` per call (shuffle.hip)
@@ -545,24 +491,11 @@ void shuffle_point_offsets(const ShufflePlan& pl, std::vector<uint32_t>& off) {
 }
 }  // namespace
 
-void Engine::shuffle_trim() {
-  tier0_trim(sh_.bytes);
-  tier0_trim(sh_.status);
-  tier0_trim(sh_.off);
-  tier0_trim(sh_.perm);
-  tier0_trim(sh_.pts);
-  tier0_trim(sh_.kpts);
-  tier0_trim(sh_.tu);
-  tier0_trim(sh_.zip);
-  tier0_trim(sh_.fr);
-  tier0_trim(sh_.mjac);
-  tier0_trim(sh_.stask);
-}
-
 // util.rs:94-104 on the device.  In: sh_.pts = vec_R | vec_S (dense planes), sh_.perm, sh_.fr = k [count] | blinders [count][4] | the scalars
 // of M [count][n] (k_shuffle_status).  Out: sh_.tu = vec_T | vec_U, sh_.zip = (T_j, U_j) interleaved, the loaded batch (R, S, T, U, M) and the
-// compressed M of every item in d_comp_.  Ends synchronised: the staging buffers and the task list are free again.
-void Engine::shuffle_device(const ShufflePlan& pl) {
+// compressed M of every item in d_comp_.  Ends synchronised: the staging buffers and the task list (`tasks`: the caller's, declared above
+// its scope) are free again.
+void Engine::shuffle_device(const ShufflePlan& pl, std::vector<SmulTask>& tasks) {
   const size_t count = pl.count, ell = ell_, n = n_, pp = pl.plane_points();
   sh_.kpts.ensure(2 * pp);
   sh_.tu.ensure(2 * pp);
@@ -572,7 +505,7 @@ void Engine::shuffle_device(const ShufflePlan& pl) {
   const Aff *d_r = sh_.pts.p + pl.point_index(SHP_R, 0, 0), *d_s = sh_.pts.p + pl.point_index(SHP_S, 0, 0);
   // k R, k S: one task per (item, family), the item's k shared by its ell elements (scale_any_point as in Engine::scale)
   const uint32_t fl = opt_.scale_any_point ? SMUL_PLAIN : 0u;
-  std::vector<SmulTask> tasks(2 * count);
+  tasks.resize(2 * count);
   for (size_t i = 0; i < count; i++) {
     tasks[2 * i] = SmulTask{nullptr, d_r + i * ell, sh_.kpts.p + i * ell, sh_.fr.p + i, 0, fl};
     tasks[2 * i + 1] = SmulTask{nullptr, d_s + i * ell, sh_.kpts.p + pp + i * ell, sh_.fr.p + i, 0, fl};
@@ -608,11 +541,8 @@ void Engine::shuffle_batch(size_t count, const uint8_t* vec_R, const uint8_t* ve
   const ShufflePlan pl(count, ell, false);
   if (!pl.fits()) throw ArgError("shuffle batch: count * ell exceeds the 32-bit index range of one call");
   check_permutations(count, ell, permutation);
-  CPX_HIP(hipSetDevice(device_));
-  struct Trim {
-    Engine* e;
-    ~Trim() { e->shuffle_trim(); }
-  } trim{this};
+  std::vector<SmulTask> tasks;
+  CallScope call(this);
   const size_t pp = pl.plane_points();
   sh_.pts.ensure(2 * pp);
   sh_.perm.ensure(pp);
@@ -626,12 +556,11 @@ void Engine::shuffle_batch(size_t count, const uint8_t* vec_R, const uint8_t* ve
   tick("k_shuffle_status", 0, (double)count);
   launch_shuffle_status(pl, nullptr, sh_.pts.p, Aff::identity(), sh_.perm.p, sh_.fr.p + count, sh_.fr.p + 5 * count, nullptr, sh_.bad.p, stream_);
   tock();
-  shuffle_device(pl);
+  shuffle_device(pl, tasks);
   if (vec_T_out) CPX_HIP(hipMemcpyAsync(vec_T_out, sh_.tu.p, pp * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
   if (vec_U_out) CPX_HIP(hipMemcpyAsync(vec_U_out, sh_.tu.p + pp, pp * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
   if (M_out) CPX_HIP(hipMemcpyAsync(M_out, d_Mjac_.p, count * sizeof(Jac), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
 }
 
 // whisk.rs:144-179 generate_whisk_shuffle_proof for every (pre_trackers, permutation, k, blinders, draws) item
@@ -644,14 +573,13 @@ void Engine::whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trac
   const ShufflePlan pl(count, ell, false);
   if (!pl.fits()) throw ArgError("shuffle proofs: count * ell exceeds the 32-bit index range of one call");
   check_permutations(count, ell, permutation);
-  CPX_HIP(hipSetDevice(device_));
-  const Aff G = generator();   // (before canonical_infinities: its first call decodes, and that shares canon_bytes_)
+  const Aff G = generator();   // (before canonical_infinities: its first call decodes, and that shares canon_bytes_; before the scope for the same reason)
   const size_t pp = pl.plane_points();
   pre_trackers = canonical_infinities(pre_trackers, pp * 96, pp, 96, {0, 48});
-  struct Trim {
-    Engine* e;
-    ~Trim() { e->shuffle_trim(); }
-  } trim{this};
+  std::vector<uint32_t> off;
+  std::vector<uint8_t> bad, dense;
+  std::vector<SmulTask> tasks;
+  CallScope call(this);
   sh_.bytes.ensure(pl.upload_bytes() + 2 * pp * 48);   // pre trackers | post trackers
   sh_.status.ensure(pl.points());
   sh_.off.ensure(pl.points());
@@ -659,7 +587,6 @@ void Engine::whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trac
   sh_.perm.ensure(pp);
   sh_.fr.ensure(5 * count + count * n);
   sh_.bad.ensure(count);
-  std::vector<uint32_t> off;
   shuffle_point_offsets(pl, off);
   CPX_HIP(hipMemcpyAsync(sh_.bytes.p, pre_trackers, pl.upload_bytes(), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(sh_.off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
@@ -672,19 +599,18 @@ void Engine::whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trac
   tick("k_shuffle_status", 0, (double)count);
   launch_shuffle_status(pl, sh_.status.p, sh_.pts.p, G, sh_.perm.p, sh_.fr.p + count, sh_.fr.p + 5 * count, nullptr, sh_.bad.p, stream_);
   tock();
-  shuffle_device(pl);
+  shuffle_device(pl, tasks);
   uint8_t* d_post = sh_.bytes.p + pl.upload_bytes();
   tick("k_compress", 0, 2.0 * pp);
   launch_compress(sh_.zip.p, (int)(2 * pp), (int)(2 * pp), 1, d_post, stream_);   // zip_trackers (whisk.rs:279-293)
   tock();
-  std::vector<uint8_t> bad(count);
+  bad.resize(count);
   CPX_HIP(hipMemcpyAsync(post_trackers_out, d_post, 2 * pp * 48, hipMemcpyDeviceToHost, stream_));
   CPX_HIP(hipMemcpy2DAsync(proofs_out, rec, d_comp_.p, 48, 48, count, hipMemcpyDeviceToHost, stream_));   // WhiskShuffleProof::serialize: M first (whisk.rs:87-91)
   CPX_HIP(hipMemcpyAsync(bad.data(), sh_.bad.p, count, hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
   // CurdleproofsProof::new on the loaded instances; the proofs come back dense and go behind their M
-  std::vector<uint8_t> dense(count * psz);
+  dense.resize(count * psz);
   batch_prove(permutation, k, vec_m_blinders, rand, dense.data());
   for (size_t i = 0; i < count; i++) {
     if (bad[i]) {   // Err(SerializationError): the placeholder's proof is dropped
@@ -719,8 +645,7 @@ void Engine::whisk_verify_shuffle_proofs_with(size_t count, const uint8_t* pre_t
   const size_t ell = ell_, psz = proof_size(), rec = 48 + psz;
   const ShufflePlan pl(count, ell, true);
   if (!pl.fits()) throw ArgError("shuffle proofs: count * ell exceeds the 32-bit index range of one call");
-  CPX_HIP(hipSetDevice(device_));
-  const Aff G = generator();
+  const Aff G = generator();   // (before the scope, as above)
   const size_t pp = pl.plane_points(), tb = pl.tracker_bytes();
   // strict_infinity = 0: non-canonical infinity encodings are rewritten in COPIES of the inputs (canonical_infinities; canon_bytes_ is
   // reused by the next array, so a rewritten array is kept)
@@ -736,17 +661,15 @@ void Engine::whisk_verify_shuffle_proofs_with(size_t count, const uint8_t* pre_t
   proofs = canon(proofs, count * rec, count, rec, {0}, nullptr);   // M; the proof points behind it are batch_verify's
   std::vector<uint8_t> dense(count * psz);                        // CurdleproofsProof::deserialize reads the bytes behind M (whisk.rs:122)
   for (size_t i = 0; i < count; i++) memcpy(dense.data() + i * psz, proofs + i * rec + 48, psz);
-  struct Trim {
-    Engine* e;
-    ~Trim() { e->shuffle_trim(); }
-  } trim{this};
+  std::vector<uint32_t> off;
+  std::vector<uint8_t> bad;
+  CallScope call(this);
   sh_.bytes.ensure(pl.upload_bytes());
   sh_.status.ensure(pl.points());
   sh_.off.ensure(pl.points());
   sh_.pts.ensure(pl.points());
   sh_.bad.ensure(count);
   sh_.mjac.ensure(count);
-  std::vector<uint32_t> off;
   shuffle_point_offsets(pl, off);
   CPX_HIP(hipMemcpyAsync(sh_.bytes.p, pre_trackers, tb, hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(sh_.bytes.p + tb, post_trackers, tb, hipMemcpyHostToDevice, stream_));
@@ -761,10 +684,9 @@ void Engine::whisk_verify_shuffle_proofs_with(size_t count, const uint8_t* pre_t
   const Aff* d = sh_.pts.p;
   load_rows(count, reinterpret_cast<const uint8_t*>(d), reinterpret_cast<const uint8_t*>(d + pp), reinterpret_cast<const uint8_t*>(d + 2 * pp),
             reinterpret_cast<const uint8_t*>(d + 3 * pp), reinterpret_cast<const uint8_t*>(sh_.mjac.p), true);
-  std::vector<uint8_t> bad(count);
+  bad.resize(count);
   CPX_HIP(hipMemcpyAsync(bad.data(), sh_.bad.p, count, hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipStreamSynchronize(stream_));
-  flush_timers();
+  call.finish();
   verify(dense.data(), verdict);
   for (size_t i = 0; i < count; i++)
     if (bad[i]) verdict[i] = CPX_ERR_DESERIALIZE;   // an undecodable tracker or M: Err(SerializationError), whatever the placeholder's verdict

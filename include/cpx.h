@@ -59,8 +59,10 @@ int cpx_device_count(void);
  * depend on an option (tests/test_gpu_parity.py::test_engine_variants_stay_bit_exact), only speed does.  "fix_bits" takes effect at
  * the next cpx_ctx_set_crs.  Unknown key / value out of range -> CPX_ERR_ARG.  cpx_ctx_get_option also answers the read-only key
  * "fix_bits_effective": the radix of the fixed-base table this context actually uses (the fallback of cpx_ctx_set_crs; 0 = no CRS),
- * and "tbl_segments_effective": the layout of the per-proof tables the loaded batch proves with (1 = 16 + 16 shifted copies per
- * base, 2 = 8 + 8; option "tbl_segments"; 0 = no batch loaded). */
+ * "tbl_segments_effective": the layout of the per-proof tables the loaded batch proves with (1 = 16 + 16 shifted copies per
+ * base, 2 = 8 + 8; option "tbl_segments"; 0 = no batch loaded), and "tier0_scratch_bytes": the device memory the context keeps between
+ * calls as scratch of the cpx_g1_* and the many-per-call cpx_whisk_* functions (0 on a new context; a buffer that one large call grew
+ * beyond 64 MiB is given back when that call ends, however it ends, so the value stays below 64 MiB per buffer). */
 int cpx_ctx_set_option(cpx_ctx* ctx, const char* key, long long value);
 int cpx_ctx_get_option(const cpx_ctx* ctx, const char* key, long long* value);
 
