@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(OUT_DIR, "libcpx.so")
 ARCH = "gfx950"
-SOURCES = ["kernels.hip", "late.hip", "protocol.hip", "round.hip", "tracker.hip", "shuffle.hip", "genmul.hip", "find.hip", "engine.cpp", "engine_device.cpp", "whisk.cpp", "capi.cpp"]
+SOURCES = ["kernels.hip", "late.hip", "protocol.hip", "round.hip", "tracker.hip", "shuffle.hip", "genmul.hip", "find.hip", "rng.hip", "engine.cpp", "engine_device.cpp", "whisk.cpp", "capi.cpp"]
 # host side: x86-64-v3 + ADX (BMI2 mulx / andn / rorx: the Keccak permutation of the transcripts runs 1.7x faster, the
 # 64-bit-limb Fr products use mulx); every host of an MI355X (EPYC 9005) has them
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-ffp-contract=off",
@@ -32,6 +32,9 @@ TRANSCRIPTCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "transcript_ch
 # test-only device program: every function of the scalar-side headers on raw words (tests/test_gpu_scalar.py)
 SCALARCHECK = os.path.join(OUT_DIR, "scalar_check")
 SCALARCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "scalar_check.hip")
+# test-only device program: every function of rng.hpp on raw words (tests/test_gpu_rng.py)
+RNGCHECK = os.path.join(OUT_DIR, "rng_check")
+RNGCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "rng_check.hip")
 DEVICE_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-I", CSRC]   # the library's device flags
 
 
@@ -46,11 +49,12 @@ def _stale():
     check = os.path.exists(FIELDCHECK_SRC)
     tcheck = os.path.exists(TRANSCRIPTCHECK_SRC)
     scheck = os.path.exists(SCALARCHECK_SRC)
-    outs = [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else []) + ([SCALARCHECK] if scheck else [])
+    rcheck = os.path.exists(RNGCHECK_SRC)
+    outs = [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else []) + ([SCALARCHECK] if scheck else []) + ([RNGCHECK] if rcheck else [])
     if not all(os.path.exists(o) for o in outs):
         return True
     t = min(os.path.getmtime(o) for o in outs)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else []) + ([SCALARCHECK_SRC] if scheck else [])
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else []) + ([SCALARCHECK_SRC] if scheck else []) + ([RNGCHECK_SRC] if rcheck else [])
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -105,6 +109,10 @@ def build(force=False, verbose=False):
             scheck = os.path.exists(SCALARCHECK_SRC)
             if scheck:
                 procs.append(("scalar_check.hip", subprocess.Popen(_scalarcheck_cmd(tmp_scheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+            tmp_rcheck = os.path.join(work, "rng_check")
+            rcheck = os.path.exists(RNGCHECK_SRC)
+            if rcheck:
+                procs.append(("rng_check.hip", subprocess.Popen(_rngcheck_cmd(tmp_rcheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
             for src, p in procs:
                 out, _ = p.communicate()
                 if p.returncode != 0:
@@ -121,6 +129,8 @@ def build(force=False, verbose=False):
                 os.replace(tmp_tcheck, TRANSCRIPTCHECK)
             if scheck:
                 os.replace(tmp_scheck, SCALARCHECK)
+            if rcheck:
+                os.replace(tmp_rcheck, RNGCHECK)
         finally:
             shutil.rmtree(work, ignore_errors=True)
         build_selfcheck()
@@ -179,6 +189,21 @@ def build_scalarcheck():
     subprocess.check_call(_scalarcheck_cmd(SCALARCHECK + ".tmp"))
     os.replace(SCALARCHECK + ".tmp", SCALARCHECK)
     return SCALARCHECK
+
+
+def _rngcheck_cmd(out):
+    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [RNGCHECK_SRC, "-o", out]
+
+
+def build_rngcheck():
+    """The device build of tests/device/rng_check.hip alone (build() compiles it with the library; the host twin is compiled by the
+    tests with g++): cross-compiled here, it travels with the library."""
+    if not os.path.exists(RNGCHECK_SRC):
+        raise RuntimeError("tests/device/rng_check.hip is missing: the device rng check cannot be built")
+    os.makedirs(OUT_DIR, exist_ok=True)
+    subprocess.check_call(_rngcheck_cmd(RNGCHECK + ".tmp"))
+    os.replace(RNGCHECK + ".tmp", RNGCHECK)
+    return RNGCHECK
 
 
 if __name__ == "__main__":

@@ -435,6 +435,67 @@ int cpx_whisk_verify_shuffle_proofs_grouped(cpx_ctx* ctx, size_t count, const ui
   });
 }
 
+// ---- the reference's `rng: &mut T` as ChaCha12 states (rng.hpp) ----
+namespace {
+RngState rng_state_from_bytes(const uint8_t b[40]) {
+  uint32_t w[10];
+  memcpy(w, b, sizeof w);
+  return rng_state_from_words(w);
+}
+void rng_state_to_bytes(const RngState& s, uint8_t b[40]) {
+  uint32_t w[10];
+  rng_state_to_words(s, w);
+  memcpy(b, w, sizeof w);
+}
+}  // namespace
+int cpx_rng_from_u64(uint64_t seed, uint8_t state_out[40]) {
+  if (!state_out) return CPX_ERR_ARG;
+  rng_state_to_bytes(rng_seed_from_u64(seed), state_out);
+  return CPX_OK;
+}
+int cpx_rng_split(uint8_t parent[40], size_t count, uint8_t* states_out) {
+  if (!count) return CPX_OK;
+  if (!parent || !states_out) return CPX_ERR_ARG;
+  RngStream p(rng_state_from_bytes(parent));
+  // (8 words per child: the position stays valid iff it does with every child drawn)
+  if (!rng_pos_valid(p.st.word_pos) || count > ((size_t)1 << 28) || !rng_pos_valid(p.st.word_pos + 8 * (uint64_t)count)) return CPX_ERR_ARG;
+  for (size_t i = 0; i < count; i++) rng_state_to_bytes(rng_split(p), states_out + i * RNG_STATE_BYTES);
+  rng_state_to_bytes(p.st, parent);
+  return CPX_OK;
+}
+int cpx_rng_fr(cpx_ctx* ctx, size_t count, uint8_t* states, size_t n_each, uint8_t* out) {
+  if (count && n_each && (!states || !out)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->rng_fr(count, states, n_each, out);
+    return (int)CPX_OK;
+  });
+}
+int cpx_rng_shuffle_draws(cpx_ctx* ctx, size_t count, uint8_t* states, uint32_t* permutation_out, uint8_t* k_out, uint8_t* blinders_out, uint8_t* rand_out) {
+  if (count && !states) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->rng_shuffle_draws(count, states, permutation_out, k_out, blinders_out, rand_out);
+    return (int)CPX_OK;
+  });
+}
+int cpx_whisk_generate_shuffle_proofs_rng(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers, uint8_t* states, uint8_t* post_trackers_out, uint8_t* proofs_out,
+                                          int* status) {
+  if (count && (!pre_trackers || !states || !post_trackers_out || !proofs_out || !status)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_generate_shuffle_proofs_rng(count, pre_trackers, states, post_trackers_out, proofs_out, status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_batch_prove_rng(cpx_ctx* ctx, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders, uint8_t* states, uint8_t* proofs_out) {
+  if (!permutation || !k || !vec_m_blinders || !states || !proofs_out) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    const size_t B = ctx->eng->batch(), ell = ctx->eng->ell();
+    for (size_t i = 0; i < B * ell; i++)
+      if (permutation[i] >= ell) return (int)CPX_ERR_ARG;
+    ctx->eng->batch_prove_rng(permutation, k, vec_m_blinders, states, proofs_out);
+    return (int)CPX_OK;
+  });
+}
+
 int cpx_set_profiling(cpx_ctx* ctx, int on) {
   if (!ctx || !ctx->eng) return CPX_ERR_ARG;
   ctx->eng->set_profiling(on != 0);

@@ -1067,7 +1067,7 @@ struct ProverState {
 
 void Engine::batch_prove(const uint32_t* permutation, const uint8_t* k_in, const uint8_t* m_blinders, const uint8_t* rand, uint8_t* proofs_out) {
   if (!B_) throw std::logic_error("batch_load first");
-  if (device_prefix(B_)) batch_prove_device(permutation, k_in, m_blinders, rand, proofs_out);   // the whole protocol on the GPU (engine_device.cpp)
+  if (device_prefix(B_)) batch_prove_device(ProveDraws{permutation, k_in, m_blinders, hipMemcpyHostToDevice, rand, nullptr, nullptr}, proofs_out);   // the whole protocol on the GPU (engine_device.cpp)
   else batch_prove_tables(permutation, k_in, m_blinders, rand, proofs_out);                  // a few proofs: host-driven Fiat-Shamir
 }
 

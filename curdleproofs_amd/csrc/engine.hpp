@@ -26,6 +26,7 @@
 #include "locate_plan.hpp"
 #include "protocol.h"
 #include "prove_reqs.hpp"
+#include "rng.hpp"
 #include "shuffle_plan.hpp"
 #include "tbl_plan.hpp"
 #include "tier0_plan.hpp"
@@ -215,6 +216,16 @@ class Engine {
   void whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
                                      const uint8_t* rand, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status);
   void whisk_verify_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand, int* verdict);
+  // ---- the reference's `rng: &mut T` as ChaCha12 states (rng.hpp), the draws made on the device by k_rng_draw (rng.hip; whisk.cpp) ----
+  // states: count x 40 bytes, in/out; a call that throws leaves them as they were
+  void rng_fr(size_t count, uint8_t* states, size_t n_each, uint8_t* out);
+  // the draws of one generate_whisk_shuffle_proof per stream (shuffle, k, 4 blinders, 3n + 9), downloaded; any output may be null.
+  // states_after_k (nullable): every stream's state as it stands after the shuffle and k (whisk.rs:150-157 returns Err there)
+  void rng_shuffle_draws(size_t count, uint8_t* states, uint32_t* permutation_out, uint8_t* k_out, uint8_t* blinders_out, uint8_t* rand_out,
+                         uint8_t* states_after_k = nullptr);
+  void whisk_generate_shuffle_proofs_rng(size_t count, const uint8_t* pre_trackers, uint8_t* states, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status);
+  // batch_prove with the 3n + 9 draws of every loaded instance taken from its stream
+  void batch_prove_rng(const uint32_t* permutation, const uint8_t* k, const uint8_t* m_blinders, uint8_t* states, uint8_t* proofs_out);
   // ... with 12 factors per item and the grouped check behind it
   void whisk_verify_shuffle_proofs_grouped(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand, int* verdict,
                                            size_t* n_rechecked);
@@ -482,7 +493,29 @@ class Engine {
     ~Untimed() { on = was; }
   };
   void prepare_device_prover();
-  void batch_prove_device(const uint32_t* permutation, const uint8_t* k, const uint8_t* m_blinders, const uint8_t* rand, uint8_t* proofs_out);
+  // Where the device-resident prover finds its witnesses and draws.  kind: the side of perm / k / mbl (host: uploaded, device: copied on the
+  // device).  rand: the 3n + 9 draws per proof on the host, or null: k_rng_draw makes them in dp.rnd from the states in rng_.states, which
+  // states_in (host, nullable: they are there already) fills first and states_out (host) receives, advanced, when the prove has ended.
+  struct ProveDraws {
+    const uint32_t* perm;
+    const uint8_t *k, *mbl;
+    hipMemcpyKind kind;
+    const uint8_t* rand;
+    const uint8_t* states_in;
+    uint8_t* states_out;
+  };
+  void batch_prove_device(const ProveDraws& dr, uint8_t* proofs_out);
+  // Device memory that outlives the scratch scope of a `_rng` shuffle call: the states, and the witnesses the shuffle step consumed, until the
+  // prover that follows has copied them.  Trimmed like the scratch sets when the call ends (trim_rng).
+  struct RngBufs {
+    DevBuf<uint8_t> states, mid;
+    DevBuf<uint32_t> perm;
+    DevBuf<Fr> kb;   // k [count] | blinders [count][4]
+  } rng_;
+  void trim_rng();
+  // the body of the two many-per-call shuffle provers; states != null: the draws come from k_rng_draw and never leave the device
+  void whisk_generate_shuffle_proofs_with(size_t count, const uint8_t* pre_trackers, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
+                                          const uint8_t* rand, uint8_t* states, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status);
 
   void run_msm_phase(const std::vector<MsmReq>& reqs, std::vector<uint8_t>* comp_out);
   void run_tbl_phase(const std::vector<TblReq>& reqs, std::vector<uint8_t>* comp_out);

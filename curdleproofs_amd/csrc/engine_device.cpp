@@ -592,23 +592,42 @@ void Engine::enqueue_prove_device() {
   launch_ps_serialize(d, Bi, stream_);
 }
 
-void Engine::batch_prove_device(const uint32_t* permutation, const uint8_t* k_in, const uint8_t* m_blinders, const uint8_t* rand, uint8_t* proofs_out) {
+void Engine::batch_prove_device(const ProveDraws& dr, uint8_t* proofs_out) {
   HostSpan wall(this, "host_prove_wall");
   CPX_HIP(hipSetDevice(device_));
   const size_t B = B_, ell = ell_, n = n_, nrand = 3 * n + 9;
   prepare_device_prover();
   DevProver& dp = dprove_;
 
-  // witnesses and the prover's random draws: the only host -> device traffic of a prove
-  CPX_HIP(hipMemcpyAsync(dp.perm.p, permutation, B * ell * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(dp.k.p, k_in, B * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(dp.mbl.p, m_blinders, B * 4 * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(dp.rnd.p, rand, B * nrand * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  // witnesses and the prover's random draws: the only host -> device traffic of a prove (with states: 40 bytes of randomness per proof)
+  CPX_HIP(hipMemcpyAsync(dp.perm.p, dr.perm, B * ell * sizeof(uint32_t), dr.kind, stream_));
+  CPX_HIP(hipMemcpyAsync(dp.k.p, dr.k, B * sizeof(Fr), dr.kind, stream_));
+  CPX_HIP(hipMemcpyAsync(dp.mbl.p, dr.mbl, B * 4 * sizeof(Fr), dr.kind, stream_));
+  if (dr.rand) {
+    CPX_HIP(hipMemcpyAsync(dp.rnd.p, dr.rand, B * nrand * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  } else {
+    if (dr.states_in) {
+      rng_.states.ensure(B * RNG_STATE_BYTES);
+      CPX_HIP(hipMemcpyAsync(rng_.states.p, dr.states_in, B * RNG_STATE_BYTES, hipMemcpyHostToDevice, stream_));
+    }
+    RngDrawArgs a{};
+    a.states = rng_.states.p;
+    a.mid_phase = -1;
+    a.count = (uint32_t)B;
+    a.nfr = 1;
+    a.fr_cnt[0] = (uint32_t)nrand;
+    a.fr_out[0] = dp.rnd.p;
+    tick("k_rng_draw", (double)(B * nrand * sizeof(Fr)), (double)(B * nrand));
+    launch_rng_draw(a, stream_);
+    tock();
+  }
 
   enqueue_prove_device();
   CPX_HIP(hipMemcpyAsync(proofs_out, dp.proofs.p, B * proof_size(), hipMemcpyDeviceToHost, stream_));
   wait_stream_blocking();
   flush_timers();
+  // the advanced states: read once the prove has ended, so that a prove that throws leaves the caller's states alone
+  if (!dr.rand && dr.states_out) CPX_HIP(hipMemcpy(dr.states_out, rng_.states.p, B * RNG_STATE_BYTES, hipMemcpyDeviceToHost));
   if (opt_.trace) {   // debugging aid: the challenges and responses of proof 0, same format as the host-driven prover prints
     std::vector<Fr> sc(SC_COUNT);
     CPX_HIP(hipMemcpy(sc.data(), dp.sc.p, SC_COUNT * sizeof(Fr), hipMemcpyDeviceToHost));

@@ -346,6 +346,25 @@ void launch_find_scan(const FindPlan& pl, const TFix* d_tab, size_t nc, size_t c
 // ladder path: d_prod[j * n_trackers + i] = k_j r_G_i (launch_smul, one task per key); d_owner[i] = the smallest such j equal to k_r_G_i, or CPX_NO_OWNER
 void launch_find_compare(const Aff* d_prod, const Aff* d_claimed, const uint8_t* d_status, size_t n_trackers, size_t n_keys, uint32_t* d_owner, hipStream_t s);
 
+// ---- the prover's random draws from ChaCha12 states (rng.hip; the stream and the samplers in rng.hpp) ----
+// One wave per stream: an optional shuffle of 0..shuffle_len, then nfr phases of fr_cnt[ph] Fr::rand draws, in that order, each continuing
+// where the one before stopped.  states [count][40] (key || word_pos) are advanced in place; states_mid (nullable) receives the state as it
+// stands after Fr phase mid_phase.  perm [count][shuffle_len]; fr_out[ph] [count][fr_cnt[ph]] in Montgomery form.
+constexpr int RNG_MAX_FR_PHASES = 3;
+struct RngDrawArgs {
+  uint8_t* states;
+  uint8_t* states_mid;
+  int mid_phase;
+  uint32_t count;
+  uint32_t shuffle_len;
+  uint32_t* perm;
+  int nfr;
+  uint32_t fr_cnt[RNG_MAX_FR_PHASES];
+  Fr* fr_out[RNG_MAX_FR_PHASES];
+};
+size_t rng_draw_max_shuffle();   // the longest permutation a wave holds in LDS
+void launch_rng_draw(const RngDrawArgs& a, hipStream_t s);
+
 void launch_sum_jac(const Jac* d_in, int n, Jac* d_out, int* d_flag, hipStream_t s);
 void launch_bench_fpmul(Fp* d_data, int blocks, int iters, hipStream_t s);
 void launch_bench_f28mul(Fp* d_data, int blocks, int iters, hipStream_t s);

@@ -566,18 +566,25 @@ void Engine::shuffle_batch(size_t count, const uint8_t* vec_R, const uint8_t* ve
 // whisk.rs:144-179 generate_whisk_shuffle_proof for every (pre_trackers, permutation, k, blinders, draws) item
 void Engine::whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trackers, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
                                            const uint8_t* rand, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status) {
+  whisk_generate_shuffle_proofs_with(count, pre_trackers, permutation, k, vec_m_blinders, rand, nullptr, post_trackers_out, proofs_out, status);
+}
+// The body.  states == null: the caller's draws are uploaded.  states != null (a batch the device-resident prover takes): k_rng_draw makes
+// the permutation, k and the blinders where the shuffle step reads them, the prover that follows draws its 3n + 9 the same way, and only the
+// 40-byte states cross the bus; an undecodable item gets its state as it stood after the shuffle and k (whisk.rs:150-157).
+void Engine::whisk_generate_shuffle_proofs_with(size_t count, const uint8_t* pre_trackers, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders,
+                                                const uint8_t* rand, uint8_t* states, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status) {
   for (size_t i = 0; i < count; i++) status[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as a proof
   if (!count) return;
   if (!ell_) throw std::logic_error("set_crs first");
   const size_t ell = ell_, n = n_, psz = proof_size(), rec = 48 + psz;
   const ShufflePlan pl(count, ell, false);
   if (!pl.fits()) throw ArgError("shuffle proofs: count * ell exceeds the 32-bit index range of one call");
-  check_permutations(count, ell, permutation);
+  if (!states) check_permutations(count, ell, permutation);   // (a row k_rng_draw shuffled from 0..ell is one)
   const Aff G = generator();   // (before canonical_infinities: its first call decodes, and that shares canon_bytes_; before the scope for the same reason)
   const size_t pp = pl.plane_points();
   pre_trackers = canonical_infinities(pre_trackers, pp * 96, pp, 96, {0, 48});
   std::vector<uint32_t> off;
-  std::vector<uint8_t> bad, dense;
+  std::vector<uint8_t> bad, dense, mid, end;
   std::vector<SmulTask> tasks;
   CallScope call(this);
   sh_.bytes.ensure(pl.upload_bytes() + 2 * pp * 48);   // pre trackers | post trackers
@@ -590,9 +597,37 @@ void Engine::whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trac
   shuffle_point_offsets(pl, off);
   CPX_HIP(hipMemcpyAsync(sh_.bytes.p, pre_trackers, pl.upload_bytes(), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(sh_.off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(sh_.perm.p, permutation, pp * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(sh_.fr.p, k, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(sh_.fr.p + count, vec_m_blinders, 4 * count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  if (states) {
+    rng_.states.ensure(count * RNG_STATE_BYTES);
+    rng_.mid.ensure(count * RNG_STATE_BYTES);
+    rng_.perm.ensure(pp);
+    rng_.kb.ensure(5 * count);
+    mid.resize(count * RNG_STATE_BYTES);
+    CPX_HIP(hipMemcpyAsync(rng_.states.p, states, count * RNG_STATE_BYTES, hipMemcpyHostToDevice, stream_));
+    RngDrawArgs a{};
+    a.states = rng_.states.p;
+    a.states_mid = rng_.mid.p;
+    a.mid_phase = 0;
+    a.count = (uint32_t)count;
+    a.shuffle_len = (uint32_t)ell;
+    a.perm = sh_.perm.p;
+    a.nfr = 2;
+    a.fr_cnt[0] = 1;
+    a.fr_out[0] = sh_.fr.p;
+    a.fr_cnt[1] = 4;
+    a.fr_out[1] = sh_.fr.p + count;
+    tick("k_rng_draw", (double)(pp * sizeof(uint32_t) + 5 * count * sizeof(Fr)), (double)(5 * count));
+    launch_rng_draw(a, stream_);
+    tock();
+    // the prover behind this scope reads them again: out of the scratch set, which the scope's end may trim
+    CPX_HIP(hipMemcpyAsync(rng_.perm.p, sh_.perm.p, pp * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(rng_.kb.p, sh_.fr.p, 5 * count * sizeof(Fr), hipMemcpyDeviceToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(mid.data(), rng_.mid.p, mid.size(), hipMemcpyDeviceToHost, stream_));
+  } else {
+    CPX_HIP(hipMemcpyAsync(sh_.perm.p, permutation, pp * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(sh_.fr.p, k, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(sh_.fr.p + count, vec_m_blinders, 4 * count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  }
   tick("k_decompress", 0, (double)pl.points());
   launch_decompress(opt_, sh_.bytes.p, (int)pl.points(), sh_.pts.p, nullptr, sh_.status.p, 1, stream_, sh_.off.p);
   tock();
@@ -611,7 +646,15 @@ void Engine::whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trac
   call.finish();
   // CurdleproofsProof::new on the loaded instances; the proofs come back dense and go behind their M
   dense.resize(count * psz);
-  batch_prove(permutation, k, vec_m_blinders, rand, dense.data());
+  if (states) {
+    end.resize(count * RNG_STATE_BYTES);
+    batch_prove_device(ProveDraws{rng_.perm.p, reinterpret_cast<const uint8_t*>(rng_.kb.p), reinterpret_cast<const uint8_t*>(rng_.kb.p + count), hipMemcpyDeviceToDevice,
+                                  nullptr, nullptr, end.data()},
+                       dense.data());
+    for (size_t i = 0; i < count; i++) memcpy(states + i * RNG_STATE_BYTES, (bad[i] ? mid.data() : end.data()) + i * RNG_STATE_BYTES, RNG_STATE_BYTES);
+  } else {
+    batch_prove(permutation, k, vec_m_blinders, rand, dense.data());
+  }
   for (size_t i = 0; i < count; i++) {
     if (bad[i]) {   // Err(SerializationError): the placeholder's proof is dropped
       memset(post_trackers_out + i * ell * 96, 0, ell * 96);
@@ -622,6 +665,141 @@ void Engine::whisk_generate_shuffle_proofs(size_t count, const uint8_t* pre_trac
       status[i] = CPX_OK;
     }
   }
+}
+
+// ---------------------------------------------------------------- draws from ChaCha12 states (rng.hip, rng.hpp)
+// The reference hands every prover `rng: &mut T`; here a stream's state goes up (40 bytes), k_rng_draw makes the draws where their consumer
+// reads them, and the advanced state comes back.  A caller's states are written only when the call has succeeded.
+namespace {
+constexpr size_t kRngFrEachMax = (size_t)1 << 20, kRngFrTotalMax = (size_t)1 << 26;
+void check_rng_states(size_t count, const uint8_t* states) {
+  for (size_t i = 0; i < count; i++) {
+    uint64_t pos;
+    memcpy(&pos, states + i * RNG_STATE_BYTES + 32, 8);
+    if (!rng_pos_valid(pos)) throw ArgError("rng state: word_pos within 2^32 words of 2^64");
+  }
+}
+}  // namespace
+void Engine::trim_rng() {
+  const auto trim = [](auto& b) {
+    if (b.bytes() > kTier0Keep) b.release();
+  };
+  each_buf(trim, rng_.states, rng_.mid, rng_.perm, rng_.kb);
+}
+
+// Fr::rand n_each times per stream
+void Engine::rng_fr(size_t count, uint8_t* states, size_t n_each, uint8_t* out) {
+  if (count > kTrackerBatchMax || n_each > kRngFrEachMax) throw ArgError("rng draws: at most 2^23 streams and 2^20 draws each per call");
+  if (!count || !n_each) return;
+  if (count * n_each > kRngFrTotalMax) throw ArgError("rng draws: at most 2^26 draws per call");
+  check_rng_states(count, states);
+  std::vector<uint8_t> st;
+  CallScope call(this);
+  DevBuf<uint8_t>& dst = t0_.bytes;
+  DevBuf<Fr>& dfr = t0_.fr;
+  dst.ensure(count * RNG_STATE_BYTES);
+  dfr.ensure(count * n_each);
+  st.resize(count * RNG_STATE_BYTES);
+  CPX_HIP(hipMemcpyAsync(dst.p, states, st.size(), hipMemcpyHostToDevice, stream_));
+  RngDrawArgs a{};
+  a.states = dst.p;
+  a.mid_phase = -1;
+  a.count = (uint32_t)count;
+  a.nfr = 1;
+  a.fr_cnt[0] = (uint32_t)n_each;
+  a.fr_out[0] = dfr.p;
+  tick("k_rng_draw", (double)(count * n_each * sizeof(Fr)), (double)(count * n_each));
+  launch_rng_draw(a, stream_);
+  tock();
+  CPX_HIP(hipMemcpyAsync(out, dfr.p, count * n_each * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(st.data(), dst.p, st.size(), hipMemcpyDeviceToHost, stream_));
+  call.finish();
+  memcpy(states, st.data(), st.size());
+}
+
+// whisk.rs:144-179: the draws of one generate_whisk_shuffle_proof per stream — shuffle, k, 4 blinders, 3n + 9 — downloaded
+void Engine::rng_shuffle_draws(size_t count, uint8_t* states, uint32_t* permutation_out, uint8_t* k_out, uint8_t* blinders_out, uint8_t* rand_out, uint8_t* states_after_k) {
+  if (!count) return;
+  if (!ell_) throw std::logic_error("set_crs first");
+  const size_t ell = ell_, nrand = 3 * n_ + 9;
+  if (count > kTrackerBatchMax || !ShufflePlan(count, ell, false).fits() || count * nrand > kRngFrTotalMax) throw ArgError("rng shuffle draws: too many streams for one call");
+  if (ell > rng_draw_max_shuffle()) throw ArgError("rng shuffle draws: ell exceeds the permutation a wave holds");
+  check_rng_states(count, states);
+  std::vector<uint8_t> st, mid;
+  CallScope call(this);
+  DevBuf<uint8_t>& dst = t0_.bytes;   // states | states after k
+  DevBuf<Fr>& dfr = t0_.fr;           // k | blinders | rand
+  dst.ensure(2 * count * RNG_STATE_BYTES);
+  dfr.ensure(count * (5 + nrand));
+  sh_.perm.ensure(count * ell);
+  st.resize(count * RNG_STATE_BYTES);
+  mid.resize(count * RNG_STATE_BYTES);
+  CPX_HIP(hipMemcpyAsync(dst.p, states, st.size(), hipMemcpyHostToDevice, stream_));
+  RngDrawArgs a{};
+  a.states = dst.p;
+  a.states_mid = dst.p + st.size();
+  a.mid_phase = 0;
+  a.count = (uint32_t)count;
+  a.shuffle_len = (uint32_t)ell;
+  a.perm = sh_.perm.p;
+  a.nfr = 3;
+  a.fr_cnt[0] = 1;
+  a.fr_out[0] = dfr.p;
+  a.fr_cnt[1] = 4;
+  a.fr_out[1] = dfr.p + count;
+  a.fr_cnt[2] = (uint32_t)nrand;
+  a.fr_out[2] = dfr.p + 5 * count;
+  tick("k_rng_draw", (double)(count * (ell * sizeof(uint32_t) + (5 + nrand) * sizeof(Fr))), (double)(count * (5 + nrand)));
+  launch_rng_draw(a, stream_);
+  tock();
+  if (permutation_out) CPX_HIP(hipMemcpyAsync(permutation_out, sh_.perm.p, count * ell * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+  if (k_out) CPX_HIP(hipMemcpyAsync(k_out, dfr.p, count * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
+  if (blinders_out) CPX_HIP(hipMemcpyAsync(blinders_out, dfr.p + count, 4 * count * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
+  if (rand_out) CPX_HIP(hipMemcpyAsync(rand_out, dfr.p + 5 * count, count * nrand * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(st.data(), dst.p, st.size(), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(mid.data(), dst.p + st.size(), mid.size(), hipMemcpyDeviceToHost, stream_));
+  call.finish();
+  memcpy(states, st.data(), st.size());
+  if (states_after_k) memcpy(states_after_k, mid.data(), mid.size());
+}
+
+// whisk.rs:144-179 for every (pre_trackers, stream) item with the draws made on the device
+void Engine::whisk_generate_shuffle_proofs_rng(size_t count, const uint8_t* pre_trackers, uint8_t* states, uint8_t* post_trackers_out, uint8_t* proofs_out, int* status) {
+  if (!count) return;
+  if (!ell_) throw std::logic_error("set_crs first");
+  if (ell_ > rng_draw_max_shuffle()) throw ArgError("rng shuffle draws: ell exceeds the permutation a wave holds");
+  check_rng_states(count, states);
+  if (device_prefix(count)) {   // nothing but the states crosses the bus
+    struct Trim {
+      Engine* e;
+      ~Trim() { e->trim_rng(); }
+    } trim{this};
+    whisk_generate_shuffle_proofs_with(count, pre_trackers, nullptr, nullptr, nullptr, nullptr, states, post_trackers_out, proofs_out, status);
+    return;
+  }
+  // a few proofs, driven from the host: the draws come down and go through the explicit-draw call
+  const size_t nrand = 3 * n_ + 9;
+  std::vector<uint8_t> end(states, states + count * RNG_STATE_BYTES), mid(count * RNG_STATE_BYTES), k(count * 32), mbl(count * 4 * 32), rnd(count * nrand * 32);
+  std::vector<uint32_t> perm(count * ell_);
+  rng_shuffle_draws(count, end.data(), perm.data(), k.data(), mbl.data(), rnd.data(), mid.data());
+  whisk_generate_shuffle_proofs(count, pre_trackers, perm.data(), k.data(), mbl.data(), rnd.data(), post_trackers_out, proofs_out, status);
+  for (size_t i = 0; i < count; i++)
+    memcpy(states + i * RNG_STATE_BYTES, (status[i] == CPX_ERR_DESERIALIZE ? mid.data() : end.data()) + i * RNG_STATE_BYTES, RNG_STATE_BYTES);
+}
+
+// CurdleproofsProof::new on the loaded instances, the 3n + 9 draws of each taken from its stream
+void Engine::batch_prove_rng(const uint32_t* permutation, const uint8_t* k, const uint8_t* m_blinders, uint8_t* states, uint8_t* proofs_out) {
+  if (!B_) throw std::logic_error("batch_load first");
+  check_rng_states(B_, states);
+  if (device_prefix(B_)) {
+    batch_prove_device(ProveDraws{permutation, k, m_blinders, hipMemcpyHostToDevice, nullptr, states, states}, proofs_out);
+    return;
+  }
+  const size_t nrand = 3 * n_ + 9;
+  std::vector<uint8_t> st(states, states + B_ * RNG_STATE_BYTES), rnd(B_ * nrand * 32);
+  rng_fr(B_, st.data(), nrand, rnd.data());
+  batch_prove_tables(permutation, k, m_blinders, rnd.data(), proofs_out);
+  memcpy(states, st.data(), st.size());
 }
 
 // whisk.rs:106-130 is_valid_whisk_shuffle_proof for every (pre_trackers, post_trackers, proof) triple

@@ -66,13 +66,22 @@ def whisk_shuffle_proof_size(ctx):
     return G1POINT_SIZE + ctx.proof_size
 
 
-def generate_whisk_shuffle_proof(ctx, pre_trackers, permutation=None, k=None, vec_m_blinders=None, rand=None):
+def generate_whisk_shuffle_proof(ctx, pre_trackers, permutation=None, k=None, vec_m_blinders=None, rand=None, rng=None):
     """whisk.rs:144-179.  Returns (post_trackers, whisk_shuffle_proof_bytes).  ctx must hold the CRS (`Context.set_crs`).
     permutation / k / vec_m_blinders / rand are the reference's rng draws (shuffle of 0..ell, Fr::rand, 4 blinders, the
-    3n+9 draws of CurdleproofsProof::new); omitted values come from the OS CSPRNG."""
+    3n+9 draws of CurdleproofsProof::new); omitted values come from the OS CSPRNG.
+    rng (a curdleproofs_amd.rng.StdRng, instead of the four): the draws are made on the device from its state, in the reference's order,
+    and rng advances as the crate's would — by the shuffle and k only when a pre tracker does not decode (whisk.rs:150-157)."""
     ell, n = ctx.ell, ctx.n
     if len(pre_trackers) != ell:
         raise ValueError("need exactly ell = %d trackers" % ell)
+    if rng is not None:
+        if not (permutation is None and k is None and vec_m_blinders is None and rand is None):
+            raise ValueError("either rng or explicit draws")
+        res = generate_whisk_shuffle_proofs(ctx, [pre_trackers], rngs=[rng])[0]
+        if res is None:
+            raise SerializationError("undecodable pre tracker")
+        return res
     if permutation is None:
         permutation = list(range(ell))
         for i in range(ell - 1, 0, -1):                      # Fisher-Yates on the CSPRNG
@@ -135,12 +144,21 @@ def _random_permutation(ell):
     return permutation
 
 
-def generate_whisk_shuffle_proofs(ctx, pre_tracker_lists, permutations=None, ks=None, vec_m_blinders=None, rands=None):
+def generate_whisk_shuffle_proofs(ctx, pre_tracker_lists, permutations=None, ks=None, vec_m_blinders=None, rands=None, rngs=None):
     """whisk.rs:144-179 for every list of ell pre trackers in ONE library call.  permutations / ks / vec_m_blinders / rands: one entry per
     list, the reference's rng draws as in generate_whisk_shuffle_proof; omitted ones come from the OS CSPRNG.  Returns a list of
     (post_trackers, whisk_shuffle_proof_bytes), with None where a pre tracker does not decode (the reference's SerializationError);
-    nothing is raised per item.  The count instances stay loaded in ctx."""
+    nothing is raised per item.  The count instances stay loaded in ctx.
+    rngs (one curdleproofs_amd.rng.StdRng per list, DISTINCT streams — StdRng.split — instead of the four): every item's draws are made on
+    the device from its own stream (cpx_whisk_generate_shuffle_proofs_rng) and every stream advances as the crate's rng would."""
     count = len(pre_tracker_lists)
+    if rngs is not None:
+        if not (permutations is None and ks is None and vec_m_blinders is None and rands is None):
+            raise ValueError("either rngs or explicit draws")
+        if len(rngs) != count:
+            raise ValueError("one rng per tracker list")
+        if len({r.state for r in rngs}) != count:
+            raise ValueError("rngs: identical states draw identical witnesses; derive the streams with StdRng.split")
     for name, arg in (("permutation", permutations), ("k", ks), ("blinder set", vec_m_blinders), ("set of draws", rands)):
         if arg is not None and len(arg) != count:
             raise ValueError("one %s per tracker list" % name)
@@ -149,19 +167,26 @@ def generate_whisk_shuffle_proofs(ctx, pre_tracker_lists, permutations=None, ks=
     ell, n = ctx.ell, ctx.n
     if any(len(t) != ell for t in pre_tracker_lists):
         raise ValueError("need exactly ell = %d trackers per list" % ell)
-    permutations = [_random_permutation(ell) for _ in range(count)] if permutations is None else permutations
-    ks = [_rand_fr(1) for _ in range(count)] if ks is None else ks
-    vec_m_blinders = [_rand_fr(N_BLINDERS) for _ in range(count)] if vec_m_blinders is None else vec_m_blinders
-    rands = [_rand_fr(3 * n + 9) for _ in range(count)] if rands is None else rands
-    if (any(len(p) != ell for p in permutations) or any(len(k) != FR for k in ks) or any(len(b) != N_BLINDERS * FR for b in vec_m_blinders)
-            or any(len(r) != (3 * n + 9) * FR for r in rands)):
-        raise ValueError("bad argument lengths: ell permutation entries, a 32-byte k, 4 blinders and 3n+9 draws per list")
+    if rngs is None:
+        permutations = [_random_permutation(ell) for _ in range(count)] if permutations is None else permutations
+        ks = [_rand_fr(1) for _ in range(count)] if ks is None else ks
+        vec_m_blinders = [_rand_fr(N_BLINDERS) for _ in range(count)] if vec_m_blinders is None else vec_m_blinders
+        rands = [_rand_fr(3 * n + 9) for _ in range(count)] if rands is None else rands
+        if (any(len(p) != ell for p in permutations) or any(len(k) != FR for k in ks) or any(len(b) != N_BLINDERS * FR for b in vec_m_blinders)
+                or any(len(r) != (3 * n + 9) * FR for r in rands)):
+            raise ValueError("bad argument lengths: ell permutation entries, a 32-byte k, 4 blinders and 3n+9 draws per list")
     rec = whisk_shuffle_proof_size(ctx)
     post, proofs = _out(count * ell * 2 * G1POINT_SIZE), _out(count * rec)
-    perm = (ctypes.c_uint32 * (count * ell))(*[x for p in permutations for x in p])
     status = (ctypes.c_int * count)(*([CPX_ERR_INTERNAL] * count))   # an entry the library does not write is never read as a proof
-    ctx._check(ctx._L.cpx_whisk_generate_shuffle_proofs(ctx._h, count, _in(b"".join(_cat(t) for t in pre_tracker_lists)), perm, _in(b"".join(ks)),
-                                                        _in(b"".join(vec_m_blinders)), _in(b"".join(rands)), post, proofs, status))
+    if rngs is not None:
+        from . import rng as _rng
+        states = _rng.load_states(rngs)
+        ctx._check(ctx._L.cpx_whisk_generate_shuffle_proofs_rng(ctx._h, count, _in(b"".join(_cat(t) for t in pre_tracker_lists)), states, post, proofs, status))
+        _rng.store_states(rngs, states)
+    else:
+        perm = (ctypes.c_uint32 * (count * ell))(*[x for p in permutations for x in p])
+        ctx._check(ctx._L.cpx_whisk_generate_shuffle_proofs(ctx._h, count, _in(b"".join(_cat(t) for t in pre_tracker_lists)), perm, _in(b"".join(ks)),
+                                                            _in(b"".join(vec_m_blinders)), _in(b"".join(rands)), post, proofs, status))
     pb, fb = bytes(post), bytes(proofs)
     res = []
     for i, st in enumerate(status):

@@ -233,7 +233,8 @@ int cpx_g1_sum_jac(cpx_ctx* ctx, const uint8_t* points_jac, size_t n, uint8_t* o
  * A tracker is 96 bytes: r_G (48, compressed) || k_r_G (48)  (`WhiskTracker`, whisk.rs:36-42).  ell is the CRS's ell
  * (the reference hard-codes N = 128, ell = 124, whisk.rs:27-28; any power-of-two ell + 4 works here).  A bad point or
  * scalar encoding anywhere is the reference's `Err(SerializationError)` -> CPX_ERR_DESERIALIZE.  The RNG stays with the
- * caller: every draw the reference makes from `rng` is an argument, in the reference's order. */
+ * caller: every draw the reference makes from `rng` is an argument, in the reference's order.  (A caller whose rng is a ChaCha12Rng can
+ * hand over its state instead and have the draws made on the device: the cpx_rng_* and *_rng calls further down.) */
 /* whisk.rs:144-179 `generate_whisk_shuffle_proof(rng, crs, pre_trackers)`.
  *   permutation     ell u32: `(0..ELL).collect().shuffle(rng)` (:152-155)      k  `Fr::rand(rng)` (:156)
  *   vec_m_blinders  4*32: `generate_blinders(rng, N_BLINDERS)` inside shuffle_permute_and_commit_input (util.rs:91)
@@ -339,12 +340,60 @@ int cpx_whisk_verify_shuffle_proofs(cpx_ctx* ctx, size_t count, const uint8_t* p
 int cpx_whisk_verify_shuffle_proofs_grouped(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers,
                                             const uint8_t* proofs, const uint8_t* rand /* count*12*32 */, int* verdict, size_t* n_rechecked);
 
+/* ---- the reference's `rng: &mut T` as a ChaCha12 state, the draws made on the device ------------------------------
+ * Every proving function of the reference takes `rng: &mut T`; its tests and README use `StdRng::seed_from_u64(0)` (rand 0.8: StdRng =
+ * ChaCha12Rng).  The calls above keep the RNG with the caller and take every draw as an argument.  The calls below take the STATE of a
+ * ChaCha12Rng instead, make the draws on the device word for word as the reference makes them (curdleproofs_amd/csrc/rng.hpp: the block
+ * function, the word stream, Fr::rand's rejection sampling, rand 0.8's SliceRandom::shuffle with UniformInt<u32>::sample_single; kernel
+ * k_rng_draw), consume them where they lie and return the advanced state: a service hands over a seed as it would hand the crate an rng and
+ * gets the crate's bytes back (whisk.rs:416-456 from the number 0 alone: tests/test_gpu_rng.py).  The explicit-draw calls stay the route for
+ * callers with an RNG of their own.
+ *   state   40 bytes per stream: key[32] || word_pos (u64 little-endian) = ChaCha12Rng::get_seed() and the low 64 bits of get_word_pos();
+ *           on return set_word_pos(word_pos) continues the Rust object where the library stopped.  A state whose word_pos is >= 2^64 - 2^32 is
+ *           CPX_ERR_ARG for the call, before anything else is read.  `states` arguments are in/out, count x 40 bytes, and are written only
+ *           when the call returns CPX_OK.
+ * SECRECY AND REUSE.  A state is the prover's secret randomness.  Two streams with IDENTICAL states draw identical permutations, k and
+ * blinders: the witnesses repeat and zero knowledge is gone.  Never pass one state twice, and never copy one state into several slots of a
+ * call: derive the `count` states of a batch from one parent with cpx_rng_split, which advances the parent.
+ * Word consumption as recalled from rand_core 0.6 / rand_chacha 0.3 (the crates are not in the build image; the infinity-flag note of
+ * cpx_batch_verify is written the same way): BlockRng::next_u32 takes one word of the stream, next_u64 two (low word first, also across a
+ * block boundary), fill_bytes of 32 bytes eight; SeedableRng::from_rng fills the 32-byte seed with fill_bytes; seed_from_u64 expands the
+ * u64 with PCG32 into the key.  The two known-answer tests of whisk.rs pin all of it but from_rng, which nothing in the reference calls.
+ * Conventions of the batched tracker calls: count = 0 is a no-op returning CPX_OK; NULL with work to do is CPX_ERR_ARG and nothing is
+ * written. */
+/* StdRng::seed_from_u64(seed).  Host only: no context, no GPU. */
+int cpx_rng_from_u64(uint64_t seed, uint8_t state_out[40]);
+/* `count` times ChaCha12Rng::from_rng(&mut parent): child i's key is the parent's next eight words, its word_pos 0; the parent is advanced by
+ * 8 * count words.  THE way to get the states of a batch from one stream.  Host only.  At most 2^28 children per call. */
+int cpx_rng_split(uint8_t parent[40] /* in/out */, size_t count, uint8_t* states_out /* count*40 */);
+/* Fr::rand(rng) n_each times per stream, Montgomery limbs as every scalar argument of this header: the verifier's 8 / 12 factors per proof,
+ * tracker blinders, the k and r of WhiskTracker::from_rand.  Needs no CRS, leaves the loaded batch untouched.  count <= 2^23, n_each <= 2^20,
+ * count * n_each <= 2^26; n_each = 0 is a no-op. */
+int cpx_rng_fr(cpx_ctx* ctx, size_t count, uint8_t* states /* count*40, in/out */, size_t n_each, uint8_t* out /* count*n_each*32 */);
+/* The draws of ONE whisk.rs:144-179 generate_whisk_shuffle_proof per stream at the context's ell, in the reference's order — the shuffle of
+ * 0..ell (:152-155), k (:156), the 4 blinders (util.rs:91), the 3n + 9 of CurdleproofsProof::new — downloaded: the bridge to the explicit-draw
+ * calls (feed them to cpx_whisk_generate_shuffle_proofs and get what the _rng call gives).  Any output may be NULL; the states advance by the
+ * whole set whatever is downloaded.  Needs a CRS (for ell: CPX_ERR_STATE without), leaves the loaded batch untouched.  ell <= 12288. */
+int cpx_rng_shuffle_draws(cpx_ctx* ctx, size_t count, uint8_t* states /* count*40, in/out */, uint32_t* permutation_out /* count*ell */,
+                          uint8_t* k_out /* count*32 */, uint8_t* blinders_out /* count*4*32 */, uint8_t* rand_out /* count*(3n+9)*32 */);
+/* cpx_whisk_generate_shuffle_proofs with the draws of item i made on the device from states[i].  From option "device_min_batch" items on no
+ * draw crosses the bus in either direction: 40 bytes of randomness go up per proof instead of (3n + 9 + 5) * 32 + 4 ell.  Below it the draws
+ * are downloaded and the explicit-draw call runs; the bytes are the same.  The reference returns Err from unzip_trackers AFTER it has drawn
+ * the permutation and k and BEFORE the blinders (whisk.rs:150-157): an item with status CPX_ERR_DESERIALIZE gets its state back advanced by
+ * those two draws only, every other item by the full set. */
+int cpx_whisk_generate_shuffle_proofs_rng(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers /* count*ell*96 */, uint8_t* states /* count*40, in/out */,
+                                          uint8_t* post_trackers_out /* count*ell*96 */, uint8_t* proofs_out /* count*(48+cpx_proof_size) */, int* status /* count */);
+/* cpx_batch_prove on the loaded instances with `rand` replaced by one state per instance: only the 3n + 9 draws of CurdleproofsProof::new
+ * are taken from each stream; the witnesses stay arguments. */
+int cpx_batch_prove_rng(cpx_ctx* ctx, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders, uint8_t* states /* batch*40, in/out */,
+                        uint8_t* proofs_out);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 int cpx_set_profiling(cpx_ctx* ctx, int on); /* time every kernel group with HIP events on the ctx stream */
 int cpx_reset_stats(cpx_ctx* ctx);
 /* name = kernel name as rocprofv3 reports it, template arguments included: "k_msm_fix<16, 16>", "k_msm_tblw<32, false>",
  * "k_msm_tblw<2, true>", "k_msm_accw", "k_reduce_sets", "k_finalize_ranges", "k_table_build", "k_msm_tail", "k_smul",
- * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_vs_crs_sum_groups" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
+ * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_vs_crs_sum_groups", "k_rng_draw" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
  * "k_smul" times the one-lane and the quad form alike; "k_smul_quad" counts (launches only) those of them that ran as k_smul_quad;
  * units = MSM points / scalar-mul elements / points; out pointers may be NULL */
 int cpx_get_stat(const cpx_ctx* ctx, const char* name, uint64_t* launches, double* total_ms, double* algorithmic_bytes, double* units);

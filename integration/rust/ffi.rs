@@ -100,6 +100,29 @@ extern "C" {
                                            verdict: *mut c_int) -> c_int;
     pub fn cpx_whisk_verify_shuffle_proofs_grouped(ctx: *mut cpx_ctx, count: usize, pre_trackers: *const u8, post_trackers: *const u8, proofs: *const u8,
                                                    rand: *const u8, verdict: *mut c_int, n_rechecked: *mut usize) -> c_int;
+    // the caller's `rng` as ChaCha12 states (40 bytes per stream: get_seed() || get_word_pos() as u64 LE), the draws made on the device
+    pub fn cpx_rng_from_u64(seed: u64, state_out: *mut u8) -> c_int;
+    pub fn cpx_rng_split(parent: *mut u8, count: usize, states_out: *mut u8) -> c_int;
+    pub fn cpx_rng_fr(ctx: *mut cpx_ctx, count: usize, states: *mut u8, n_each: usize, out: *mut u8) -> c_int;
+    pub fn cpx_rng_shuffle_draws(ctx: *mut cpx_ctx, count: usize, states: *mut u8, permutation_out: *mut u32, k_out: *mut u8, blinders_out: *mut u8,
+                                 rand_out: *mut u8) -> c_int;
+    pub fn cpx_whisk_generate_shuffle_proofs_rng(ctx: *mut cpx_ctx, count: usize, pre_trackers: *const u8, states: *mut u8, post_trackers_out: *mut u8,
+                                                 proofs_out: *mut u8, status: *mut c_int) -> c_int;
+    pub fn cpx_batch_prove_rng(ctx: *mut cpx_ctx, permutation: *const u32, k: *const u8, vec_m_blinders: *const u8, states: *mut u8, proofs_out: *mut u8) -> c_int;
+}
+
+pub const RNG_STATE: usize = 40;
+/// The wire state of a `ChaCha12Rng` (= rand 0.8 `StdRng`): `get_seed()` and the low 64 bits of `get_word_pos()`.
+pub fn rng_state(rng: &rand_chacha::ChaCha12Rng) -> [u8; RNG_STATE] {
+    let mut s = [0u8; RNG_STATE];
+    s[..32].copy_from_slice(&rng.get_seed());
+    s[32..].copy_from_slice(&(rng.get_word_pos() as u64).to_le_bytes());
+    s
+}
+/// Continues `rng` where the library stopped.
+pub fn rng_resume(rng: &mut rand_chacha::ChaCha12Rng, state: &[u8]) {
+    debug_assert_eq!(&state[..32], &rng.get_seed()[..]);
+    rng.set_word_pos(u64::from_le_bytes(state[32..40].try_into().unwrap()) as u128);
 }
 
 pub const AFF: usize = 96;

@@ -291,3 +291,49 @@ pub fn shuffle_permute_and_commit_inputs(crs: &CurdleproofsCrs, vec_r: &[u8], ve
     assert!(rc == CPX_OK, "libcpx: {}", rc);
     (t, u, m)
 }
+
+/// whisk.rs:144-179 for many lists of pre trackers with the draws made ON THE DEVICE (cpx_whisk_generate_shuffle_proofs_rng): `rng` is a
+/// `ChaCha12Rng` (rand 0.8 `StdRng` is one), every item gets a stream of its own split off it (`ChaCha12Rng::from_rng`, done by
+/// cpx_rng_split), and 40 bytes per item cross the bus instead of the draws.  With ONE item and its state taken from `rng` itself
+/// (`rng_state` / `rng_resume` of ffi.rs instead of the split) the bytes are those of the crate's function on the same `rng`.
+/// Never hand two items the same state: identical states draw identical witnesses.  Like the rest of this file, NOT COMPILED here.
+pub fn generate_whisk_shuffle_proofs_on_device(
+    rng: &mut rand_chacha::ChaCha12Rng,
+    crs: &CurdleproofsCrs,
+    pre_trackers: &[&[WhiskTracker]],
+) -> Vec<Result<(Vec<WhiskTracker>, WhiskShuffleProofBytes), SerializationError>> {
+    assert!(pre_trackers.iter().all(|t| t.len() == ELL));
+    let count = pre_trackers.len();
+    let mut parent = rng_state(rng);
+    let mut states = vec![0u8; RNG_STATE * count];
+    let rc = unsafe { cpx_rng_split(parent.as_mut_ptr(), count, states.as_mut_ptr()) };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    rng_resume(rng, &parent);
+    let pre: Vec<u8> = pre_trackers.iter().flat_map(|t| trackers_to_wire(t)).collect();
+    let mut post = vec![0u8; 96 * ELL * count];
+    let mut proofs = vec![0u8; WHISK_SHUFFLE_PROOF_SIZE * count];
+    let mut status = vec![CPX_ERR_INTERNAL; count];
+    let rc = unsafe {
+        cpx_whisk_generate_shuffle_proofs_rng(ctx_with_crs(crs), count, pre.as_ptr(), states.as_mut_ptr(), post.as_mut_ptr(), proofs.as_mut_ptr(), status.as_mut_ptr())
+    };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    status
+        .iter()
+        .zip(post.chunks(96 * ELL).zip(proofs.chunks(WHISK_SHUFFLE_PROOF_SIZE)))
+        .map(|(st, (t, p))| match *st {
+            CPX_OK => Ok((t.chunks(96).map(|c| WhiskTracker { r_G: c[..48].try_into().unwrap(), k_r_G: c[48..].try_into().unwrap() }).collect(), p.try_into().unwrap())),
+            CPX_ERR_DESERIALIZE => Err(SerializationError::InvalidData),
+            st => panic!("libcpx: {}", st),
+        })
+        .collect()
+}
+
+/// `Fr::rand(rng)` n times on the device, `rng` advanced as the crate would have advanced it: the verifier's factors, tracker blinders
+pub fn fr_rand_on_device(rng: &mut rand_chacha::ChaCha12Rng, n: usize) -> Vec<Fr> {
+    let mut state = rng_state(rng);
+    let mut out = vec![Fr::from(0u64); n];
+    let rc = unsafe { cpx_rng_fr(ctx(), 1, state.as_mut_ptr(), n, out.as_mut_ptr() as *mut u8) };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    rng_resume(rng, &state);
+    out
+}
