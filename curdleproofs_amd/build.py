@@ -35,6 +35,10 @@ SCALARCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "scalar_check.hip"
 # test-only device program: every function of rng.hpp on raw words (tests/test_gpu_rng.py)
 RNGCHECK = os.path.join(OUT_DIR, "rng_check")
 RNGCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "rng_check.hip")
+# test-only device program: the MSM wave bodies of msm_body.hpp bucket by bucket and the library's own reducers on crafted sets
+# (tests/test_gpu_msm_waves.py); it calls the launchers of kernels.h, so it is linked against the finished libcpx.so beside it
+MSMCHECK = os.path.join(OUT_DIR, "msm_check")
+MSMCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "msm_check.hip")
 DEVICE_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-I", CSRC]   # the library's device flags
 
 
@@ -50,11 +54,12 @@ def _stale():
     tcheck = os.path.exists(TRANSCRIPTCHECK_SRC)
     scheck = os.path.exists(SCALARCHECK_SRC)
     rcheck = os.path.exists(RNGCHECK_SRC)
-    outs = [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else []) + ([SCALARCHECK] if scheck else []) + ([RNGCHECK] if rcheck else [])
+    mcheck = os.path.exists(MSMCHECK_SRC)
+    outs = [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else []) + ([SCALARCHECK] if scheck else []) + ([RNGCHECK] if rcheck else []) + ([MSMCHECK] if mcheck else [])
     if not all(os.path.exists(o) for o in outs):
         return True
     t = min(os.path.getmtime(o) for o in outs)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else []) + ([SCALARCHECK_SRC] if scheck else []) + ([RNGCHECK_SRC] if rcheck else [])
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else []) + ([SCALARCHECK_SRC] if scheck else []) + ([RNGCHECK_SRC] if rcheck else []) + ([MSMCHECK_SRC] if mcheck else [])
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -113,6 +118,10 @@ def build(force=False, verbose=False):
             rcheck = os.path.exists(RNGCHECK_SRC)
             if rcheck:
                 procs.append(("rng_check.hip", subprocess.Popen(_rngcheck_cmd(tmp_rcheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+            tmp_mobj, tmp_mcheck = os.path.join(work, "msm_check.o"), os.path.join(work, "msm_check")
+            mcheck = os.path.exists(MSMCHECK_SRC)
+            if mcheck:
+                procs.append(("msm_check.hip", subprocess.Popen(_msmcheck_compile_cmd(tmp_mobj), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
             for src, p in procs:
                 out, _ = p.communicate()
                 if p.returncode != 0:
@@ -122,7 +131,11 @@ def build(force=False, verbose=False):
                     print(out.decode())
             tmp_lib = os.path.join(work, "libcpx.so")
             subprocess.check_call([hipcc, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", tmp_lib] + objs + ["-lpthread"])
+            if mcheck:
+                subprocess.check_call(_msmcheck_link_cmd(tmp_mobj, work, tmp_mcheck))
             os.replace(tmp_lib, LIB)
+            if mcheck:
+                os.replace(tmp_mcheck, MSMCHECK)
             if check:
                 os.replace(tmp_check, FIELDCHECK)
             if tcheck:
@@ -204,6 +217,33 @@ def build_rngcheck():
     subprocess.check_call(_rngcheck_cmd(RNGCHECK + ".tmp"))
     os.replace(RNGCHECK + ".tmp", RNGCHECK)
     return RNGCHECK
+
+
+def _msmcheck_compile_cmd(obj):
+    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + ["-c", MSMCHECK_SRC, "-o", obj]
+
+
+def _msmcheck_link_cmd(obj, lib_dir, out):
+    # libcpx.so carries no soname: the program records the bare file name and finds the library in its own directory
+    return [_hipcc(), "--offload-arch=" + ARCH, obj, "-L", lib_dir, "-lcpx", "-Wl,-rpath,$ORIGIN", "-o", out]
+
+
+def build_msmcheck():
+    """The device build of tests/device/msm_check.hip alone (build() compiles it with the library): cross-compiled here and linked
+    against the libcpx.so beside it, it travels with the library."""
+    if not os.path.exists(MSMCHECK_SRC):
+        raise RuntimeError("tests/device/msm_check.hip is missing: the device MSM check cannot be built")
+    if not os.path.exists(LIB):
+        raise RuntimeError("libcpx.so is missing: build the library first")
+    obj = MSMCHECK + ".tmp.o"
+    try:
+        subprocess.check_call(_msmcheck_compile_cmd(obj))
+        subprocess.check_call(_msmcheck_link_cmd(obj, OUT_DIR, MSMCHECK + ".tmp"))
+    finally:
+        if os.path.exists(obj):
+            os.remove(obj)
+    os.replace(MSMCHECK + ".tmp", MSMCHECK)
+    return MSMCHECK
 
 
 if __name__ == "__main__":
