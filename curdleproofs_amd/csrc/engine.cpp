@@ -508,6 +508,34 @@ void Engine::launch_check_fused(const MsmTask* d_gt, const FixTask* d_ft, size_t
   CPX_HIP(hipMemcpyAsync(h_comp_.p, d_res_.p, sizeof(Jac), hipMemcpyDeviceToHost, stream_));
 }
 
+size_t Engine::located_check(const CheckPlan& cp, const LocatePlan& lp, const LocateTasks& t, const uint32_t* flags, bool resident, int* verdict) {
+  auto slices = [&](size_t tasks, size_t max_n) { return resident ? (size_t)1 : (size_t)msm_tblw_slices(opt_, (int)tasks, 2, (int)max_n); };
+  auto wait = [&] { resident ? wait_stream_blocking() : wait_stream(); };
+  // ---- stage 1: every group's sum tested for the identity
+  launch_check(t.mt1, t.ft1, lp.NT, lp.s1_max_n(cp.NPT), t.fix_wpw, t.fix_parts, slices(lp.NT, lp.s1_max_n(cp.NPT)));
+  wait();
+  std::vector<uint8_t> group_ok(lp.NT), recheck_ok;
+  for (size_t g = 0; g < lp.NT; g++) group_ok[g] = check_passed(g) ? 1 : 0;   // (before stage 2 overwrites h_comp_)
+  std::vector<uint32_t> list;
+  locate_stage2(lp, group_ok.data(), flags, list);   // empty with one proof per group: stage 1 was the per-proof check
+  // ---- stage 2: the suspects' own checks from the scalars stage 1 left in place; nothing when every group passed
+  const size_t S = list.size();
+  if (S) {
+    const int fix_wpw = msm_fix_windows_per_wave(opt_, (int)S, fix_bits_), fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
+    std::vector<MsmTask> mt(S);   // (copied asynchronously: alive until the wait below)
+    std::vector<FixTask> ft(S);
+    cp.suspect_tasks(list, (size_t)fix_parts, mt.data(), ft.data());
+    CPX_HIP(hipMemcpyAsync(t.mt2, mt.data(), S * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(t.ft2, ft.data(), S * sizeof(FixTask), hipMemcpyHostToDevice, stream_));
+    launch_check(t.mt2, t.ft2, S, cp.NPT, fix_wpw, fix_parts, slices(S, cp.NPT));
+    wait();
+    recheck_ok.resize(S);
+    for (size_t s = 0; s < S; s++) recheck_ok[s] = check_passed(s) ? 1 : 0;
+  }
+  locate_verdicts(lp, group_ok.data(), flags, list, recheck_ok.data(), verdict);
+  return S;
+}
+
 // ---------------------------------------------------------------- CRS
 void Engine::set_crs(size_t ell, const uint8_t* points) {
   const size_t n = ell + N_BLINDERS;
@@ -1564,6 +1592,23 @@ void Engine::batch_verify_grouped(const uint8_t* proofs, const uint8_t* rand, in
   if (n_rechecked) *n_rechecked = rechecked;
 }
 
+// One proof's scalars of the accumulated check (host_verify.hpp verify_scalars) into the staging copy of the layout of check_plan.hpp.  An
+// undecodable proof contributes nothing to a sum it is part of; in every mode its verdict comes from its flag.
+static void stage_check_scalars(const host::VerifyState& s, size_t p, const CheckPlan& cp, const CheckScalars<Fr>& at) {
+  Fr* d = at.of_proof(p);
+  Fr* c = at.crs_of(p);
+  for (size_t i = 0; i < cp.NI; i++) d[i] = s.bad ? S::zero().f : s.scal[1][i].f;
+  for (size_t j = 0; j < cp.NM; j++) d[cp.NI + j] = s.bad ? S::zero().f : s.scal[2][j].f;
+  for (size_t i = 0; i < cp.n; i++) c[i] = s.bad ? S::zero().f : s.scal[0][i].f;
+}
+// CRS scalar i summed over the proofs [first, first + count) (the shared bases G | Hvec merge in Fr; msm_accumulator.rs:47-51)
+static S crs_sum(const std::vector<host::VerifyState>& st, size_t i, size_t first, size_t count) {
+  S t = S::zero();
+  for (size_t p = first; p < first + count; p++)
+    if (!st[p].bad) t += st[p].scal[0][i];
+  return t;
+}
+
 // Shared body.  Per-proof mode (verdict != nullptr, 8 random factors per proof): curdleproofs.rs:197.  Fused mode
 // (fused_partial != nullptr, 12 factors per proof): BASELINE config 5 — every check of every proof goes into ONE
 // accumulated MSM (the reference's MsmAccumulator shared by all verify calls); the result is this
@@ -1661,8 +1706,7 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
   }
 
   // -- V1c: rest of the transcript and the scalars of the accumulated check; its "misc" part runs over the CRS singles, M and every
-  //    proof point: the slots 0 .. NM
-  const size_t NM = (size_t)SL_A + NPP;
+  //    proof point: the slots 0 .. NM (check_plan.hpp)
   auto comp_of = [&](size_t p, int slot) -> const uint8_t* {   // the bytes of the request whose output is `slot`
     for (int i = 0; i < vreqs.n; i++)
       if (vreqs.r[i].out == slot) return &comp[(p * (size_t)vreqs.n + i) * 48];
@@ -1673,188 +1717,67 @@ void Engine::verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand
                          fused_partial != nullptr || grouped != nullptr);
   });
 
-  if (grouped) {
-    // ---- the grouped check (locate_plan.hpp): stage 1 = one task per group, staged as the fused branch stages its groups; stage 2 = one
-    //      task per suspect proof over the scalars already on the device ----
-    if (!fixtab()) throw std::logic_error("set_crs first");
-    const size_t NI = 4 * ell, NPT = NI + NM, N = B * NPT;
-    const LocatePlan lp = locate_plan(B, opt_.locate_groups_max);
-    const size_t NT = lp.NT;
-    std::vector<uint32_t> flags(B);
-    for (size_t p = 0; p < B; p++) flags[p] = (st[p].bad ? kLocateFlagDecode : 0u) | (st[p].reject ? kLocateFlagStruct : 0u);
-    // device scalars: [ per-proof points' scalars (N) | per-proof CRS scalars (B n) | per-group CRS sums (NT n) ]
-    const size_t o_crs = N, o_sum = N + B * n, total = o_sum + lp.s1_crs_scalars(n);
-    const int fix_wpw = msm_fix_windows_per_wave(opt_, (int)NT, fix_bits_);
-    const int fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
-    const size_t slices = (size_t)msm_tblw_slices(opt_, (int)NT, 2, (int)lp.s1_max_n(NPT));
-    d_scal_.ensure(total);
-    d_big_idx_.ensure(N);
-    d_tasks_.ensure(NT + B);     // stage 1's tasks, then stage 2's
-    d_ftasks_.ensure(NT + B);
-    const size_t b_scal = total * sizeof(Fr), b_mt = NT * sizeof(MsmTask), b_ft = NT * sizeof(FixTask), b_idx = N * sizeof(uint32_t);
-    h_stage_.ensure(b_scal + b_mt + b_ft + b_idx);
-    Fr* hs = reinterpret_cast<Fr*>(h_stage_.p);
-    MsmTask* hm = reinterpret_cast<MsmTask*>(h_stage_.p + b_scal);
-    FixTask* hf = reinterpret_cast<FixTask*>(h_stage_.p + b_scal + b_mt);
-    uint32_t* hi = reinterpret_cast<uint32_t*>(h_stage_.p + b_scal + b_mt + b_ft);
-    parallel_for(B, [&](size_t p) {
-      const host::VerifyState& s = st[p];
-      Fr* d = hs + p * NPT;
-      Fr* c = hs + o_crs + p * n;
-      uint32_t* x = hi + p * NPT;
-      for (size_t i = 0; i < NI; i++) {
-        d[i] = s.bad ? S::zero().f : s.scal[1][i].f;   // an undecodable proof contributes nothing to its group
-        x[i] = (uint32_t)(p * pp_stride_ + i);
-      }
-      for (size_t j = 0; j < NM; j++) {
-        d[NI + j] = s.bad ? S::zero().f : s.scal[2][j].f;
-        x[NI + j] = slot_index(p, (int)j);
-      }
-      for (size_t i = 0; i < n; i++) c[i] = s.bad ? S::zero().f : s.scal[0][i].f;
-    });
-    parallel_for(n, [&](size_t i) {   // the CRS scalars summed per group
-      for (size_t g = 0; g < NT; g++) {
-        S t = S::zero();
-        for (size_t p = lp.group_first(g), e = p + lp.group_count(g); p < e; p++)
-          if (!st[p].bad) t += st[p].scal[0][i];
-        hs[o_sum + g * n + i] = t.f;
-      }
-    });
-    for (size_t g = 0; g < NT; g++) {
-      const size_t off = lp.s1_task_off(g, NPT);
-      hm[g] = MsmTask{d_pp_.p, d_big_idx_.p + off, d_scal_.p + off, (uint32_t)lp.s1_task_n(g, NPT), 0, (uint32_t)off};
-      hf[g] = FixTask{nullptr, d_scal_.p + o_sum + g * n, 0, (uint32_t)n, 0, (uint32_t)lp.s1_out_first(g, (size_t)fix_parts)};
-    }
-    CPX_HIP(hipMemcpyAsync(d_scal_.p, hs, b_scal, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(d_tasks_.p, hm, b_mt, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(d_ftasks_.p, hf, b_ft, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(d_big_idx_.p, hi, b_idx, hipMemcpyHostToDevice, stream_));
-    launch_check(d_tasks_.p, d_ftasks_.p, NT, lp.s1_max_n(NPT), fix_wpw, fix_parts, slices);
-    wait_stream();
-    std::vector<uint8_t> group_ok(NT), recheck_ok;
-    for (size_t g = 0; g < NT; g++) group_ok[g] = check_passed(g) ? 1 : 0;   // (before stage 2 overwrites h_comp_)
-    std::vector<uint32_t> list;
-    locate_stage2(lp, group_ok.data(), flags.data(), list);   // empty with one proof per group: stage 1 was the per-proof check
-    const size_t nS = list.size();
-    if (nS) {
-      const int fix_wpw2 = msm_fix_windows_per_wave(opt_, (int)nS, fix_bits_), fix_parts2 = msm_fix_parts(fix_bits_, fix_wpw2);
-      const size_t slices2 = (size_t)msm_tblw_slices(opt_, (int)nS, 2, (int)NPT);
-      std::vector<MsmTask> mt(nS);   // (copied asynchronously: alive until the wait below)
-      std::vector<FixTask> ft(nS);
-      for (size_t s = 0; s < nS; s++) {
-        const size_t p = list[s];
-        mt[s] = MsmTask{d_pp_.p, d_big_idx_.p + p * NPT, d_scal_.p + p * NPT, (uint32_t)NPT, 0, (uint32_t)LocatePlan::s2_conv_off(s, NPT)};
-        ft[s] = FixTask{nullptr, d_scal_.p + o_crs + p * n, 0, (uint32_t)n, 0, (uint32_t)LocatePlan::s2_out_first(s, (size_t)fix_parts2)};
-      }
-      CPX_HIP(hipMemcpyAsync(d_tasks_.p + NT, mt.data(), nS * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(d_ftasks_.p + NT, ft.data(), nS * sizeof(FixTask), hipMemcpyHostToDevice, stream_));
-      launch_check(d_tasks_.p + NT, d_ftasks_.p + NT, nS, NPT, fix_wpw2, fix_parts2, slices2);
-      wait_stream();
-      recheck_ok.resize(nS);
-      for (size_t s = 0; s < nS; s++) recheck_ok[s] = check_passed(s) ? 1 : 0;
-    }
-    locate_verdicts(lp, group_ok.data(), flags.data(), list, recheck_ok.data(), verdict);
-    *grouped = nS;
-    flush_timers();
-    return;
-  }
-
-  if (fused_partial) {
-    // ---- one MSM over the CRS (scalars summed over the proofs, fixed-base table) and B * (4 ell + NM) per-proof points ----
-    if (!fixtab()) throw std::logic_error("set_crs first");
-    const size_t NI = 4 * ell, NPT = NI + NM, N = B * NPT;
-    int invalid = 0;
-    for (size_t p = 0; p < B; p++) invalid += (st[p].bad || st[p].reject) ? 1 : 0;
-    SVec crs_sum(n, S::zero());
+  // -- V2: the accumulated check (check_plan.hpp) — the CRS part on the fixed-base table (k_msm_fix), the per-proof points (R | S | T | U
+  //    and the slots) in bucket MSMs (k_msm_tblw<2, true>); the Horner tail adds the two.  Per proof: one task pair per proof.  Fused: ONE
+  //    sum, the CRS scalars summed over the proofs, the points in up to 256 groups.  Grouped: stage 1 = one task pair per group, the CRS
+  //    scalars summed per group; stage 2 = one task pair per suspect proof over the scalars already on the device (located_check).
+  if (!fixtab()) throw std::logic_error("set_crs first");
+  const bool fused = fused_partial != nullptr, global = fused || grouped;   // global: tasks over ranges of the batch's points (gather list)
+  std::vector<uint32_t> flags(B);
+  for (size_t p = 0; p < B; p++) flags[p] = (st[p].bad ? kLocateFlagDecode : 0u) | (st[p].reject ? kLocateFlagStruct : 0u);
+  CheckPlan cp(B, ell, L, n);
+  const size_t NPT = cp.NPT, N = cp.n_points();
+  const LocatePlan lp = grouped ? locate_plan(B, opt_.locate_groups_max) : CheckPlan::fused_plan(B);   // (per proof: unused)
+  const size_t NT = global ? lp.NT : B;                     // stage 1's bucket MSM tasks
+  const size_t NF = fused ? 1 : NT;                         // ... and fixed-base tasks
+  const size_t rows = grouped ? lp.NT : fused ? 1 : 0;      // rows of summed CRS scalars
+  const size_t n2 = grouped ? B : 0;                        // room for stage 2's tasks behind stage 1's
+  // device scalars: [ per-proof points' scalars (N) | per-proof CRS scalars (B n) | summed CRS scalars (rows n) ]
+  const size_t o_crs = N, o_sum = N + B * n, total = o_sum + rows * n;
+  const int fix_wpw = msm_fix_windows_per_wave(opt_, (int)NF, fix_bits_);
+  const int fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
+  d_scal_.ensure(total);
+  d_tasks_.ensure(NT + n2);
+  d_ftasks_.ensure(NF + n2);
+  if (global) d_big_idx_.ensure(N);
+  const size_t b_scal = total * sizeof(Fr), b_mt = NT * sizeof(MsmTask), b_ft = NF * sizeof(FixTask), b_idx = global ? N * sizeof(uint32_t) : 0;
+  h_stage_.ensure(b_scal + b_mt + b_ft + b_idx);
+  Fr* hs = reinterpret_cast<Fr*>(h_stage_.p);
+  MsmTask* hm = reinterpret_cast<MsmTask*>(h_stage_.p + b_scal);
+  FixTask* hf = reinterpret_cast<FixTask*>(h_stage_.p + b_scal + b_mt);
+  uint32_t* hi = reinterpret_cast<uint32_t*>(h_stage_.p + b_scal + b_mt + b_ft);
+  std::vector<uint32_t> all_idx(global ? 0 : NPT);   // per proof: the row-relative gather list — the instance vectors, then the slots of the misc part
+  for (size_t i = 0; i < all_idx.size(); i++) all_idx[i] = (uint32_t)i;
+  cp.place(d_pp_.p, pp_stride_, global ? nullptr : idx_list(all_idx), d_big_idx_.p, d_scal_.p, d_scal_.p + o_crs, d_scal_.p + o_sum);
+  const CheckScalars<Fr> at{hs, hs + o_crs, hs + o_sum, NPT, n};   // the staging copy
+  parallel_for(B, [&](size_t p) {
+    stage_check_scalars(st[p], p, cp, at);
+    if (global) cp.gather_proof(p, hi);
+  });
+  if (rows)   // the CRS scalars summed over all proofs (fused) / per group
     parallel_for(n, [&](size_t i) {
-      S t = S::zero();
-      for (size_t p = 0; p < B; p++)
-        if (!st[p].bad) t += st[p].scal[0][i];
-      crs_sum[i] = t;
+      for (size_t r = 0; r < rows; r++) at.sum_row(r)[i] = crs_sum(st, i, grouped ? lp.group_first(r) : 0, grouped ? lp.group_count(r) : B).f;
     });
-    const int fix_wpw = msm_fix_windows_per_wave(opt_, 1, fix_bits_);
-    const int fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
-    d_scal_.ensure(N + n);
-    d_big_idx_.ensure(N);
-    d_ftasks_.ensure(1);
-    const size_t b_scal = (N + n) * sizeof(Fr), b_idx = N * sizeof(uint32_t);
-    h_stage_.ensure(b_scal + b_idx + sizeof(FixTask));
-    Fr* hs = reinterpret_cast<Fr*>(h_stage_.p);
-    uint32_t* hi = reinterpret_cast<uint32_t*>(h_stage_.p + b_scal);
-    FixTask* hf = reinterpret_cast<FixTask*>(h_stage_.p + b_scal + b_idx);
-    parallel_for(B, [&](size_t p) {
-      const host::VerifyState& s = st[p];
-      Fr* d = hs + p * NPT;
-      uint32_t* x = hi + p * NPT;
-      for (size_t i = 0; i < NI; i++) {
-        d[i] = s.bad ? S::zero().f : s.scal[1][i].f;   // an undecodable proof contributes nothing (and is counted as invalid)
-        x[i] = (uint32_t)(p * pp_stride_ + i);
-      }
-      for (size_t j = 0; j < NM; j++) {
-        d[NI + j] = s.bad ? S::zero().f : s.scal[2][j].f;
-        x[NI + j] = slot_index(p, (int)j);
-      }
-    });
-    for (size_t i = 0; i < n; i++) hs[N + i] = crs_sum[i].f;
-    *hf = FixTask{nullptr, d_scal_.p + N, 0, (uint32_t)n, 0, 0};
-    CPX_HIP(hipMemcpyAsync(d_scal_.p, hs, b_scal, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(d_big_idx_.p, hi, b_idx, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(d_ftasks_.p, hf, sizeof(FixTask), hipMemcpyHostToDevice, stream_));
-    // the per-proof points in up to 256 groups of proofs, every group one task of the endomorphism bucket-list kernel
-    const size_t G = (B + 255) / 256, NT = (B + G - 1) / G;
-    d_tasks_.ensure(NT);
-    std::vector<MsmTask> mt(NT);   // (copied asynchronously: alive until the wait below)
-    for (size_t g = 0; g < NT; g++) {
-      const size_t off = g * G * NPT, np = std::min(G, B - g * G) * NPT;
-      mt[g] = MsmTask{d_pp_.p, d_big_idx_.p + off, d_scal_.p + off, (uint32_t)np, 0, (uint32_t)off};
-    }
-    CPX_HIP(hipMemcpyAsync(d_tasks_.p, mt.data(), NT * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
-    launch_check_fused(d_tasks_.p, d_ftasks_.p, NT, G, NPT, N, fix_wpw, fix_parts);
+  if (grouped) cp.group_tasks(lp, (size_t)fix_parts, hm, hf);
+  else if (fused) cp.fused_tasks(hm, hf);
+  else cp.proof_tasks((size_t)fix_parts, hm, hf);
+  CPX_HIP(hipMemcpyAsync(d_scal_.p, hs, b_scal, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(d_tasks_.p, hm, b_mt, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(d_ftasks_.p, hf, b_ft, hipMemcpyHostToDevice, stream_));
+  if (global) CPX_HIP(hipMemcpyAsync(d_big_idx_.p, hi, b_idx, hipMemcpyHostToDevice, stream_));
+  if (grouped) {
+    *grouped = located_check(cp, lp, LocateTasks{d_tasks_.p, d_ftasks_.p, fix_wpw, fix_parts, d_tasks_.p + NT, d_ftasks_.p + NT}, flags.data(), false, verdict);
+  } else if (fused) {
+    launch_check_fused(d_tasks_.p, d_ftasks_.p, lp.NT, lp.G, NPT, N, fix_wpw, fix_parts);
     wait_stream();
     memcpy(fused_partial, h_comp_.p, sizeof(Jac));
+    int invalid = 0;
+    for (size_t p = 0; p < B; p++) invalid += flags[p] ? 1 : 0;
     if (fused_invalid) *fused_invalid = invalid;
-    flush_timers();
-    return;
-  }
-
-  // -- V2: the accumulated check of every proof as ONE sum: the CRS part on the fixed-base table (k_msm_fix), all the
-  //    per-proof points (R | S | T | U and the slots) in one bucket MSM (k_msm_accw); the Horner tail adds the two.
-  {
-    if (!fixtab()) throw std::logic_error("set_crs first");
-    const size_t NI = 4 * ell, NPT = NI + NM;
-    std::vector<uint32_t> all_idx(NPT);   // row-relative gather list: the instance vectors, then the slots of the misc part — the row's first NPT points
-    for (size_t i = 0; i < NPT; i++) all_idx[i] = (uint32_t)i;
-    const uint32_t* d_all = idx_list(all_idx);
-    const int fix_wpw = msm_fix_windows_per_wave(opt_, (int)B, fix_bits_);
-    const int fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
-    const size_t slices = (size_t)msm_tblw_slices(opt_, (int)B, 2, (int)NPT);   // a lone proof: several waves per window of the per-proof MSM
-    const size_t total = B * (NPT + n);
-    d_scal_.ensure(total);
-    d_tasks_.ensure(B);
-    d_ftasks_.ensure(B);
-    const size_t b_scal = total * sizeof(Fr), b_mt = B * sizeof(MsmTask), b_ft = B * sizeof(FixTask);
-    h_stage_.ensure(b_scal + b_mt + b_ft);
-    Fr* hs = reinterpret_cast<Fr*>(h_stage_.p);
-    MsmTask* hm = reinterpret_cast<MsmTask*>(h_stage_.p + b_scal);
-    FixTask* hf = reinterpret_cast<FixTask*>(h_stage_.p + b_scal + b_mt);
-    parallel_for(B, [&](size_t p) {
-      const host::VerifyState& s = st[p];
-      Fr* d = hs + p * (NPT + n);
-      for (size_t i = 0; i < NI; i++) d[i] = s.scal[1][i].f;
-      for (size_t j = 0; j < NM; j++) d[NI + j] = s.scal[2][j].f;
-      for (size_t i = 0; i < n; i++) d[NPT + i] = s.scal[0][i].f;
-      hm[p] = MsmTask{pp(p), d_all, d_scal_.p + p * (NPT + n), (uint32_t)NPT, 0, (uint32_t)(p * NPT)};
-      hf[p] = FixTask{nullptr, d_scal_.p + p * (NPT + n) + NPT, 0, (uint32_t)n, 0, (uint32_t)(p * fix_parts)};
-    });
-    CPX_HIP(hipMemcpyAsync(d_scal_.p, hs, b_scal, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(d_tasks_.p, hm, b_mt, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(d_ftasks_.p, hf, b_ft, hipMemcpyHostToDevice, stream_));
-    launch_check(d_tasks_.p, d_ftasks_.p, B, NPT, fix_wpw, fix_parts, slices);
+  } else {
+    launch_check(d_tasks_.p, d_ftasks_.p, B, NPT, fix_wpw, fix_parts, (size_t)msm_tblw_slices(opt_, (int)B, 2, (int)NPT));   // a lone proof: several waves per window
     wait_stream();
-    for (size_t p = 0; p < B; p++) {
-      const host::VerifyState& s = st[p];
-      verdict[p] = s.bad ? CPX_ERR_DESERIALIZE : ((s.reject || !check_passed(p)) ? CPX_ERR_VERIFY : CPX_OK);
-    }
+    for (size_t p = 0; p < B; p++) verdict[p] = check_verdict(flags[p], check_passed(p));
   }
   flush_timers();
 }

@@ -23,6 +23,7 @@
 #include "host_math.hpp"
 #include "host_threads.hpp"
 #include "kernels.h"
+#include "check_plan.hpp"
 #include "locate_plan.hpp"
 #include "protocol.h"
 #include "prove_reqs.hpp"
@@ -189,7 +190,8 @@ class Engine {
   // engine's partial sum (Jacobian, standard form) and the number of structurally invalid proofs
   void batch_verify_fused(const uint8_t* proofs, const uint8_t* rand, uint8_t* partial_jac, int* n_invalid);
   // The grouped form of the accumulated check (locate_plan.hpp; include/cpx.h cpx_batch_verify_grouped): 12 factors per proof as for the fused
-  // call, one verdict per proof; n_rechecked (nullable) = the proofs that went through the second stage
+  // call, one verdict per proof; n_rechecked (nullable) = the proofs that went through the second stage.  All three modes lay out their scalars,
+  // gather list and tasks by check_plan.hpp on both paths: verify_core stages them from the host, prepare_device_verifier builds them once per shape
   void batch_verify_grouped(const uint8_t* proofs, const uint8_t* rand, int* verdict, size_t* n_rechecked);
   size_t batch() const { return B_; }
 
@@ -447,9 +449,12 @@ class Engine {
     DevBuf<FixTask> ftasks;
     TblPlan pd;                                  // D and A'
     int fix_wpw = 16, fix_parts = 1, fix_wpw1 = 2, fix_parts1 = 8;
-    size_t G = 1, NT = 1;                        // fused batch: proofs per group, groups
+    // the accumulated check (check_plan.hpp): the builders of its task lists over scal | scal_crs | lsum.  mtasks / ftasks[0 .. B): per proof;
+    // gtasks / ftasks[B]: fused, its summed CRS scalars behind the point scalars in `scal`
+    CheckPlan cplan;
+    LocatePlan fplan;                            // fused batch: its groups
     // grouped verifier (locate_plan.hpp): its own group tasks for option locate_groups_max, one fixed-base task per group over the group's
-    // summed CRS scalars (lsum), and room for the task lists of the second stage, which the host writes per call
+    // summed CRS scalars (lsum), and room for the task lists of the second stage, which located_check writes per call
     LocatePlan lplan;
     DevBuf<MsmTask> ltasks, l2tasks;
     DevBuf<FixTask> lftasks, l2ftasks;
@@ -486,6 +491,18 @@ class Engine {
   void launch_check(const MsmTask* d_mt, const FixTask* d_ft, size_t B, size_t NPT, int fix_wpw, int fix_parts, size_t slices);
   void launch_check_fused(const MsmTask* d_gt, const FixTask* d_ft, size_t NT, size_t G, size_t NPT, size_t N, int fix_wpw, int fix_parts);
   bool check_passed(size_t p) const { return h_comp_.p[p * 48] == kCompIdentity; }   // the accumulated check of a valid proof sums to the identity
+  // The grouped check (locate_plan.hpp) from its staged scalars on, for both paths: stage 1 (the uploaded lists mt1 / ft1 of lp.NT group tasks,
+  // fix_wpw / fix_parts as ft1 was built) -> wait -> the failing groups' flag-free proofs -> their own tasks, written to mt2 / ft2 (room for
+  // lp.B) -> wait -> verdict[lp.B].  flags: the proofs' flag words on the host, valid at the latest behind the first wait.  resident: the
+  // device-resident path (one wave per window, sleeping waits); otherwise msm_tblw_slices decides and the waits spin.  Returns the proofs rechecked.
+  struct LocateTasks {
+    const MsmTask* mt1;
+    const FixTask* ft1;
+    int fix_wpw, fix_parts;
+    MsmTask* mt2;
+    FixTask* ft2;
+  };
+  size_t located_check(const CheckPlan& cp, const LocatePlan& lp, const LocateTasks& t, const uint32_t* flags, bool resident, int* verdict);
   struct Untimed {   // keeps a launch sequence out of the statistics
     bool& on;
     const bool was;

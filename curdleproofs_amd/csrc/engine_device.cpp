@@ -643,7 +643,8 @@ void Engine::prepare_device_verifier(size_t rand_stride) {
   const size_t B = B_, ell = ell_, n = n_, L = L_;
   const SlotMap sm(L);
   const ProofLayout pl(L);
-  const size_t NS = sm.count(), NPP = pl.n_points(), NM = 6 + NPP, NI = 4 * ell, NPT = NI + NM, psz = pl.size();
+  CheckPlan cp(B, ell, L, n);
+  const size_t NS = sm.count(), NPP = pl.n_points(), NM = cp.NM, NPT = cp.NPT, psz = pl.size();
   DevVerifier& dv = dverify_;
   d_bytes_.ensure(B * 4 * ell * 48);
   d_mcomp_.ensure(B * 48);
@@ -719,47 +720,39 @@ void Engine::prepare_device_verifier(size_t rand_stride) {
   // are hashed into the transcript, so they are needed as bytes
   build_plan(dv.pd, verify_requests((int)n, (int)L), [&](size_t p, const ReqScal& sc) { return ScalAddr{nullptr, dv.vsc.p + p * VSC_COUNT + sc.at}; });
   // the accumulated check: per proof one fixed-base task over G | Hvec and one bucket MSM over R | S | T | U and the misc slots
-  std::vector<uint32_t> all_idx(NPT);   // row-relative gather list
-  for (size_t i = 0; i < NI; i++) all_idx[i] = (uint32_t)i;
-  for (size_t j = 0; j < NM; j++) all_idx[NI + j] = (uint32_t)(NI + j);   // misc index j == slot j (SL_H .. SL_M, then the proof points)
-  const uint32_t* d_all = idx_list(all_idx);
+  //   (check_plan.hpp: k_vs_scalars fills scal | scal_crs, k_vs_crs_sum_groups the summed rows)
+  std::vector<uint32_t> all_idx(NPT);   // row-relative gather list: misc index j == slot j (SL_H .. SL_M, then the proof points)
+  for (size_t i = 0; i < NPT; i++) all_idx[i] = (uint32_t)i;
+  cp.place(d_pp_.p, pp_stride_, idx_list(all_idx), dv.gidx.p, dv.scal.p, dv.scal_crs.p, dv.lsum.p);
+  dv.cplan = cp;
   dv.fix_wpw = msm_fix_windows_per_wave(opt_, (int)B, fix_bits_);
   dv.fix_parts = msm_fix_parts(fix_bits_, dv.fix_wpw);
   dv.fix_wpw1 = msm_fix_windows_per_wave(opt_, 1, fix_bits_);
   dv.fix_parts1 = msm_fix_parts(fix_bits_, dv.fix_wpw1);
   std::vector<MsmTask> mt(B);
   std::vector<FixTask> ft(B + 1);
-  std::vector<uint32_t> gi(B * NPT);
-  for (size_t p = 0; p < B; p++) {
-    mt[p] = MsmTask{pp(p), d_all, dv.scal.p + p * NPT, (uint32_t)NPT, 0, (uint32_t)(p * NPT)};
-    ft[p] = FixTask{nullptr, dv.scal_crs.p + p * n, 0, (uint32_t)n, 0, (uint32_t)(p * dv.fix_parts)};
-    for (size_t i = 0; i < NPT; i++) gi[p * NPT + i] = (uint32_t)(p * pp_stride_ + i);
-  }
-  ft[B] = FixTask{nullptr, dv.scal.p + B * NPT, 0, (uint32_t)n, 0, 0};   // fused batch: the CRS scalars summed over the proofs
-  CPX_HIP(hipMemcpy(dv.mtasks.p, mt.data(), B * sizeof(MsmTask), hipMemcpyHostToDevice));
-  CPX_HIP(hipMemcpy(dv.ftasks.p, ft.data(), (B + 1) * sizeof(FixTask), hipMemcpyHostToDevice));
-  CPX_HIP(hipMemcpy(dv.gidx.p, gi.data(), gi.size() * 4, hipMemcpyHostToDevice));
-  // fused batch: the proofs in up to 256 groups, every group one task of the endomorphism bucket-list kernel
-  dv.G = (B + 255) / 256;
-  dv.NT = (B + dv.G - 1) / dv.G;
-  dv.gtasks.ensure(dv.NT);
-  std::vector<MsmTask> gt(dv.NT);
-  for (size_t g = 0; g < dv.NT; g++) {
-    const size_t off = g * dv.G * NPT, np_ = std::min(dv.G, B - g * dv.G) * NPT;
-    gt[g] = MsmTask{d_pp_.p, dv.gidx.p + off, dv.scal.p + off, (uint32_t)np_, 0, (uint32_t)off};
-  }
-  CPX_HIP(hipMemcpy(dv.gtasks.p, gt.data(), dv.NT * sizeof(MsmTask), hipMemcpyHostToDevice));
+  std::vector<uint32_t> gi(cp.n_points());
+  cp.proof_tasks((size_t)dv.fix_parts, mt.data(), ft.data());
+  cp.gather(gi.data());
+  // fused batch: the proofs in up to 256 groups, every group one task of the endomorphism bucket-list kernel; the CRS scalars summed
+  // over the proofs sit behind the point scalars
+  dv.fplan = CheckPlan::fused_plan(B);
+  dv.gtasks.ensure(dv.fplan.NT);
+  std::vector<MsmTask> gt(dv.fplan.NT);
+  CheckPlan fcp = cp;
+  fcp.at.sums = dv.scal.p + cp.n_points();
+  fcp.fused_tasks(gt.data(), &ft[B]);
   // grouped verifier, stage 1: the same layout for ITS group size, and per group a fixed-base task over the group's summed CRS scalars
   dv.lplan = lp;
   dv.lfix_wpw = msm_fix_windows_per_wave(opt_, (int)lp.NT, fix_bits_);
   dv.lfix_parts = msm_fix_parts(fix_bits_, dv.lfix_wpw);
   std::vector<MsmTask> lt(lp.NT);
   std::vector<FixTask> lf(lp.NT);
-  for (size_t g = 0; g < lp.NT; g++) {
-    const size_t off = lp.s1_task_off(g, NPT);
-    lt[g] = MsmTask{d_pp_.p, dv.gidx.p + off, dv.scal.p + off, (uint32_t)lp.s1_task_n(g, NPT), 0, (uint32_t)off};
-    lf[g] = FixTask{nullptr, dv.lsum.p + g * n, 0, (uint32_t)n, 0, (uint32_t)lp.s1_out_first(g, (size_t)dv.lfix_parts)};
-  }
+  cp.group_tasks(lp, (size_t)dv.lfix_parts, lt.data(), lf.data());
+  CPX_HIP(hipMemcpy(dv.mtasks.p, mt.data(), B * sizeof(MsmTask), hipMemcpyHostToDevice));
+  CPX_HIP(hipMemcpy(dv.ftasks.p, ft.data(), (B + 1) * sizeof(FixTask), hipMemcpyHostToDevice));
+  CPX_HIP(hipMemcpy(dv.gidx.p, gi.data(), gi.size() * 4, hipMemcpyHostToDevice));
+  CPX_HIP(hipMemcpy(dv.gtasks.p, gt.data(), gt.size() * sizeof(MsmTask), hipMemcpyHostToDevice));
   CPX_HIP(hipMemcpy(dv.ltasks.p, lt.data(), lp.NT * sizeof(MsmTask), hipMemcpyHostToDevice));
   CPX_HIP(hipMemcpy(dv.lftasks.p, lf.data(), lp.NT * sizeof(FixTask), hipMemcpyHostToDevice));
   if (!dv.ev_a) {
@@ -776,10 +769,11 @@ void Engine::verify_core_device(const uint8_t* proofs, const uint8_t* rand, size
   CPX_HIP(hipSetDevice(device_));
   const size_t B = B_, ell = ell_, n = n_, L = L_;
   const ProofLayout pl(L);
-  const size_t NPP = pl.n_points(), NM = 6 + NPP, NPT = 4 * ell + NM, psz = pl.size();
+  const size_t NPP = pl.n_points(), psz = pl.size();
   prepare_device_verifier(rand_stride);
   DevVerifier& dv = dverify_;
   const VerifyDev& d = dv.dev;
+  const size_t NPT = dv.cplan.NPT;
   const int Bi = (int)B;
   CPX_HIP(hipMemcpyAsync(dv.proofs.p, proofs, B * psz, hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dv.rnd.p, rand, B * rand_stride * sizeof(Fr), hipMemcpyHostToDevice, stream_));
@@ -804,62 +798,32 @@ void Engine::verify_core_device(const uint8_t* proofs, const uint8_t* rand, size
   exec_plan(dv.pd, dv.slotcomp.p);
   launch_vs_scalars(d, Bi, stream_);
   // -- V2: the accumulated check(s)
+  //    (check_plan.hpp); the flag words arrive behind the same wait as the first sums — copied behind the check's launches where the mode
+  //    allows it (a copy between the kernels of a pass cost the four-context fused bench 1 - 2 %)
   h_u32_.ensure(B);
-  if (fused_partial) {
-    launch_vs_crs_sum(dv.scal_crs.p, Bi, (int)n, dv.scal.p + B * NPT, stream_);
-    launch_check_fused(dv.gtasks.p, dv.ftasks.p + B, dv.NT, dv.G, NPT, B * NPT, dv.fix_wpw1, dv.fix_parts1);
-    CPX_HIP(hipMemcpyAsync(h_u32_.p, dv.flags.p, B * 4, hipMemcpyDeviceToHost, stream_));
+  const uint32_t* flags = h_u32_.p;
+  auto fetch_flags = [&] { CPX_HIP(hipMemcpyAsync(h_u32_.p, dv.flags.p, B * 4, hipMemcpyDeviceToHost, stream_)); };
+  if (fused_partial) {   // the CRS scalars summed over all proofs: one group of B
+    launch_vs_crs_sum_groups(dv.scal_crs.p, Bi, (int)n, Bi, 1, dv.scal.p + B * NPT, stream_);
+    launch_check_fused(dv.gtasks.p, dv.ftasks.p + B, dv.fplan.NT, dv.fplan.G, NPT, B * NPT, dv.fix_wpw1, dv.fix_parts1);
+    fetch_flags();
     wait_stream_blocking();
     memcpy(fused_partial, h_comp_.p, sizeof(Jac));
     int invalid = 0;
-    for (size_t p = 0; p < B; p++) invalid += h_u32_.p[p] ? 1 : 0;
+    for (size_t p = 0; p < B; p++) invalid += flags[p] ? 1 : 0;
     if (fused_invalid) *fused_invalid = invalid;
-    flush_timers();
-    return;
-  }
-  if (grouped) {
-    // ---- the grouped check (locate_plan.hpp).  Stage 1: every group's sum — its CRS scalars added up in Fr, its points in one bucket
-    //      MSM — tested for the identity; the compressed sums and the flag words arrive behind ONE wait
+  } else if (grouped) {   // the grouped check (locate_plan.hpp): every group's CRS scalars added up in Fr, then the two stages
     const LocatePlan& lp = dv.lplan;
     tick("k_vs_crs_sum_groups", 32.0 * B * n, (double)(B * n));
     launch_vs_crs_sum_groups(dv.scal_crs.p, Bi, (int)n, (int)lp.G, (int)lp.NT, dv.lsum.p, stream_);
     tock();
-    launch_check(dv.ltasks.p, dv.lftasks.p, lp.NT, lp.s1_max_n(NPT), dv.lfix_wpw, dv.lfix_parts, 1);
-    CPX_HIP(hipMemcpyAsync(h_u32_.p, dv.flags.p, B * 4, hipMemcpyDeviceToHost, stream_));
+    fetch_flags();   // (located_check reads them behind stage 1's wait)
+    *grouped = located_check(dv.cplan, lp, LocateTasks{dv.ltasks.p, dv.lftasks.p, dv.lfix_wpw, dv.lfix_parts, dv.l2tasks.p, dv.l2ftasks.p}, flags, true, verdict);
+  } else {
+    launch_check(dv.mtasks.p, dv.ftasks.p, B, NPT, dv.fix_wpw, dv.fix_parts, 1);
+    fetch_flags();
     wait_stream_blocking();
-    std::vector<uint8_t> group_ok(lp.NT), recheck_ok;
-    for (size_t g = 0; g < lp.NT; g++) group_ok[g] = check_passed(g) ? 1 : 0;   // (before stage 2 overwrites h_comp_)
-    std::vector<uint32_t> list;
-    locate_stage2(lp, group_ok.data(), h_u32_.p, list);
-    // ---- stage 2: the suspects' own checks from the scalars stage 1 left in place; nothing when every group passed
-    const size_t S = list.size();
-    if (S) {
-      const int fix_wpw = msm_fix_windows_per_wave(opt_, (int)S, fix_bits_), fix_parts = msm_fix_parts(fix_bits_, fix_wpw);
-      std::vector<MsmTask> mt(S);   // (copied asynchronously: alive until the wait below)
-      std::vector<FixTask> ft(S);
-      for (size_t s = 0; s < S; s++) {
-        const size_t p = list[s];
-        mt[s] = MsmTask{d_pp_.p, dv.gidx.p + p * NPT, dv.scal.p + p * NPT, (uint32_t)NPT, 0, (uint32_t)LocatePlan::s2_conv_off(s, NPT)};
-        ft[s] = FixTask{nullptr, dv.scal_crs.p + p * n, 0, (uint32_t)n, 0, (uint32_t)LocatePlan::s2_out_first(s, (size_t)fix_parts)};
-      }
-      CPX_HIP(hipMemcpyAsync(dv.l2tasks.p, mt.data(), S * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(dv.l2ftasks.p, ft.data(), S * sizeof(FixTask), hipMemcpyHostToDevice, stream_));
-      launch_check(dv.l2tasks.p, dv.l2ftasks.p, S, NPT, fix_wpw, fix_parts, 1);
-      wait_stream_blocking();
-      recheck_ok.resize(S);
-      for (size_t s = 0; s < S; s++) recheck_ok[s] = check_passed(s) ? 1 : 0;
-    }
-    locate_verdicts(lp, group_ok.data(), h_u32_.p, list, recheck_ok.data(), verdict);
-    *grouped = S;
-    flush_timers();
-    return;
-  }
-  launch_check(dv.mtasks.p, dv.ftasks.p, B, NPT, dv.fix_wpw, dv.fix_parts, 1);
-  CPX_HIP(hipMemcpyAsync(h_u32_.p, dv.flags.p, B * 4, hipMemcpyDeviceToHost, stream_));
-  wait_stream_blocking();
-  for (size_t p = 0; p < B; p++) {
-    const uint32_t f = h_u32_.p[p];
-    verdict[p] = (f & 1u) ? CPX_ERR_DESERIALIZE : (((f & 2u) || !check_passed(p)) ? CPX_ERR_VERIFY : CPX_OK);
+    for (size_t p = 0; p < B; p++) verdict[p] = check_verdict(flags[p], check_passed(p));
   }
   flush_timers();
 }

@@ -1,6 +1,7 @@
 // The host-driven verifier's per-proof work that needs no GPU: deserialising the proof's scalars, the Fiat-Shamir transcript and the
-// scalars of the accumulated check.  Engine::verify_core (engine.cpp) stages, launches and waits around these two steps; the
-// device-resident path does the same work in k_vs_prefix / k_vs_scalars (protocol.hip).  No HIP: the tests compile this for the CPU.
+// scalars of the accumulated check.  Engine::verify_core (engine.cpp) launches and waits around these two steps and stages the scalars
+// (VerifyState::scal) in the layout of check_plan.hpp, the same for every mode of the check; the device-resident path does the same
+// work in k_vs_prefix / k_vs_scalars (protocol.hip).  No HIP: the tests compile this for the CPU.
 #pragma once
 #include "check_weights.hpp"
 #include "host_math.hpp"

@@ -1,8 +1,10 @@
 // Planner of the grouped verifier (cpx_batch_verify_grouped, include/cpx.h) — host code without a HIP call: how a batch of B proofs is cut
 // into groups, which proofs the second stage rechecks given the groups' results and the proofs' flag words, what every proof's verdict
-// is, and how much of each scratch buffer either stage needs.  One definition for the device-resident path (engine_device.cpp), the
-// host-driven path (engine.cpp verify_core) and tests/host_emul/locate_plan_emul.cpp, which compiles it for the CPU
-// (tests/test_verify_grouped_cpu.py).
+// is, and how much of each scratch buffer either stage needs.  One definition for both verifier paths — Engine::located_check (engine.cpp)
+// runs the two stages for the host-driven and the device-resident one — and tests/host_emul/locate_plan_emul.cpp, which compiles it for the
+// CPU (tests/test_verify_grouped_cpu.py).  check_plan.hpp turns the offsets below into the task lists of either stage and of the fused
+// check, whose grouping is this plan for kLocateGroupsMax groups; who fills the scalars is the paths' business (the host's staging in
+// verify_core, k_vs_scalars and k_vs_crs_sum_groups on the device).
 //
 // Stage 1: NT group tasks through Engine::launch_check — group g is ONE bucket MSM over the points of its proofs (up to G * NPT points,
 // the fused check's task) and ONE fixed-base task over the CRS scalars summed over its proofs.  Stage 2: the S suspect proofs through

@@ -81,9 +81,8 @@ void launch_ps_smsm_round(const ProveDev& d, int B, int j, hipStream_t s);
 void launch_ps_serialize(const ProveDev& d, int B, hipStream_t s);
 void launch_vs_prefix(const VerifyDev& d, int B, hipStream_t s);
 void launch_vs_scalars(const VerifyDev& d, int B, hipStream_t s);
-// out[i] = sum_p scal_crs[p * n + i], i < n  (the CRS scalars of a fused batch)
-void launch_vs_crs_sum(const Fr* d_scal_crs, int B, int n, Fr* d_out, hipStream_t s);
-// grouped verifier (locate_plan.hpp): d_out[g * n + i] = sum over the proofs p of group g of d_scal_crs[p * n + i]; NT groups of G proofs, the last one ragged
+// d_out[g * n + i] = sum over the proofs p of group g of d_scal_crs[p * n + i]; NT groups of G proofs, the last one ragged: the groups of the
+// grouped verifier (locate_plan.hpp), or G = B, NT = 1 for the CRS scalars of a fused batch
 void launch_vs_crs_sum_groups(const Fr* d_scal_crs, int B, int n, int G, int NT, Fr* d_out, hipStream_t s);
 
 }  // namespace cpx

@@ -646,17 +646,10 @@ __global__ __launch_bounds__(64) void k_vs_scalars(const VerifyDev d) {
   for (int s = lane; s < d.NM; s += 64) out[NI + s] = bad ? Fr::zero() : misc_weight(w, sm, s);
 }
 
-// fused batch: sum over the proofs of the CRS scalars (the shared bases G | Hvec merge in Fr; msm_accumulator.rs:47-51)
-__global__ __launch_bounds__(64) void k_vs_crs_sum(const Fr* __restrict__ scal_crs, int B, int n, Fr* __restrict__ out) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= n) return;
-  Fr t = Fr::zero();
-  for (int p = 0; p < B; p++) t = fe_add(t, scal_crs[(size_t)p * n + i]);
-  out[i] = t;
-}
-
-// grouped verifier: the same sum per GROUP of G consecutive proofs, out[g * n + i] for group g = blockIdx.y.  Consecutive lanes take
-// consecutive i: a wave reads 64 neighbouring 32-byte elements of one proof's row per step, and every scalar of the batch is read once.
+// The CRS scalars summed over the proofs of a check (the shared bases G | Hvec merge in Fr; msm_accumulator.rs:47-51): per GROUP of G
+// consecutive proofs, out[g * n + i] for group g = blockIdx.y — the grouped verifier's groups, or ONE group of all B proofs for the fused
+// batch.  Consecutive lanes take consecutive i: a wave reads 64 neighbouring 32-byte elements of one proof's row per step, and every
+// scalar of the batch is read once.
 __global__ __launch_bounds__(64) void k_vs_crs_sum_groups(const Fr* __restrict__ scal_crs, int B, int n, int G, Fr* __restrict__ out) {
   const int i = blockIdx.x * 64 + threadIdx.x, g = blockIdx.y;
   if (i >= n) return;
@@ -679,9 +672,6 @@ void launch_ps_smsm_round(const ProveDev& d, int B, int j, hipStream_t s) { PS_L
 void launch_ps_serialize(const ProveDev& d, int B, hipStream_t s) { PS_LAUNCH(k_ps_serialize, B, 0, s, d); }
 void launch_vs_prefix(const VerifyDev& d, int B, hipStream_t s) { PS_LAUNCH(k_vs_prefix, B, (size_t)d.n * 32 + 64, s, d); }
 void launch_vs_scalars(const VerifyDev& d, int B, hipStream_t s) { PS_LAUNCH(k_vs_scalars, B, (size_t)d.n * 32 + (size_t)4 * d.L * 32 + 64 + 4 * 48, s, d); }
-void launch_vs_crs_sum(const Fr* d_scal_crs, int B, int n, Fr* d_out, hipStream_t s) {
-  hipLaunchKernelGGL(k_vs_crs_sum, dim3((n + 63) / 64), dim3(64), 0, s, d_scal_crs, B, n, d_out);
-}
 void launch_vs_crs_sum_groups(const Fr* d_scal_crs, int B, int n, int G, int NT, Fr* d_out, hipStream_t s) {
   if (NT <= 0 || n <= 0) return;
   hipEvent_t a = nullptr, b = nullptr;

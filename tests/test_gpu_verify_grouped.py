@@ -221,6 +221,35 @@ def test_fused_partial_sum_is_unchanged_by_a_grouped_call(c, orc, base):
     assert before == after and before[1] == 0 and orc.g1_compress_jac(before[0])[0] != 0xc0
 
 
+# ---- 7b. what the shared staging of the accumulated check (check_plan.hpp) decides for every mode ----
+def test_an_undecodable_proof_contributes_nothing_in_any_mode_on_either_path(contexts, orc, base):
+    import curdleproofs_amd as cpx
+    OK, VER, DES = cpx.CPX_OK, cpx.CPX_ERR_VERIFY, cpx.CPX_ERR_DESERIALIZE
+    identity = bytes([0xc0]) + bytes(47)
+    broken = lambda proof: bytes([proof[0] ^ 0x80]) + proof[1:]
+    frand = orc.rng(18).fr(12 * B10)
+    sums = {}
+    for name in ("host_driven", "device_resident"):
+        c = contexts(name)
+        base.load(c, B10)
+        c.set_option("locate_groups_max", 4)
+        # proof 4 undecodable, the rest valid: the fused sum is the identity and the proof is counted; the per-proof call names it
+        proofs = base.proofs(B10)
+        proofs[4] = broken(proofs[4])
+        jac, invalid = c.verify_batch_fused_partial(proofs, frand)
+        assert invalid == 1 and bytes(orc.g1_compress_jac(jac)) == identity, name
+        assert c.verify_batch(proofs, base.vrand(B10)) == [DES if p == 4 else OK for p in range(B10)], name
+        # ... beside a wrong proof: only the undecodable one is counted, and the wrong one's sum is the same on both paths
+        proofs = base.proofs(B10, {3: "z_k"})
+        proofs[4] = broken(proofs[4])
+        jac, invalid = c.verify_batch_fused_partial(proofs, frand)
+        sums[name] = bytes(orc.g1_compress_jac(jac))
+        print("%s: n_invalid %d, partial sum %s" % (name, invalid, sums[name].hex()))
+        assert invalid == 1 and sums[name] != identity, name
+        assert c.verify_batch(proofs, base.vrand(B10)) == [VER if p == 3 else DES if p == 4 else OK for p in range(B10)], name
+    assert sums["host_driven"] == sums["device_resident"]
+
+
 # ---- 8. arguments ----
 def test_arguments(c, orc, base):
     import curdleproofs_amd as cpx
