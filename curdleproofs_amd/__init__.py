@@ -65,6 +65,7 @@ EXPORTS = [
     "cpx_whisk_generate_tracker_proofs", "cpx_whisk_verify_tracker_proofs", "cpx_g1_generator_mul", "cpx_whisk_trackers_from_k_r", "cpx_whisk_find_trackers",
     "cpx_batch_shuffle", "cpx_whisk_generate_shuffle_proofs", "cpx_whisk_verify_shuffle_proofs", "cpx_whisk_verify_shuffle_proofs_grouped",
     "cpx_rng_from_u64", "cpx_rng_split", "cpx_rng_fr", "cpx_rng_shuffle_draws", "cpx_whisk_generate_shuffle_proofs_rng", "cpx_batch_prove_rng",
+    "cpx_rng_g1", "cpx_rng_instance_draws", "cpx_crs_generate", "cpx_g1_clear_cofactor",
     "cpx_set_profiling", "cpx_reset_stats", "cpx_get_stat", "cpx_set_host_threads", "cpx_bench_fpmul",
 ]
 
@@ -150,6 +151,10 @@ def load_library(path=None):
     L.cpx_rng_shuffle_draws.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.cpx_whisk_generate_shuffle_proofs_rng.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.cpx_batch_prove_rng.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.cpx_rng_g1.argtypes = [vp, sz, vp, sz, vp, vp]
+    L.cpx_rng_instance_draws.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.cpx_crs_generate.argtypes = [vp, sz, vp, vp]
+    L.cpx_g1_clear_cofactor.argtypes = [vp, vp, sz, vp]
     _libs[os.path.realpath(path)] = L
     if default:
         _lib = L
@@ -356,6 +361,17 @@ class Context:
         self._check(self._L.cpx_g1_decompress(self._h, _in(comp), n, o, 1 if check_subgroup else 0))
         return bytes(o)[: AFF * n]
 
+    def clear_cofactor(self, points):
+        """[h] P for every point of `points` — ANY points of E(Fp), 96 bytes each — with the full cofactor h = |E(Fp)| / r (ark-ec
+        `mul_by_cofactor`; cpx_g1_clear_cofactor: a compiled-in addition chain, whatever option scale_any_point says).  Returns the affine
+        points, the identity as 96 zero bytes."""
+        n = len(points) // AFF
+        if len(points) % AFF:
+            raise ValueError("clear_cofactor: 96 bytes per affine point")
+        o = _out(AFF * n)
+        self._check(self._L.cpx_g1_clear_cofactor(self._h, _in(points), n, o))
+        return bytes(o)[: AFF * n]
+
     def generator_mul(self, scalars, compressed=False):
         """scalars[i] * G for the G1 generator, count per call on the generator's fixed-base table (cpx_g1_generator_mul; whisk.rs:318,323
         with g1 = generator).  scalars: count wire scalars back to back.  Returns the affine points, or (affine, compressed)."""
@@ -533,7 +549,7 @@ class Context:
         return dict(launches=n.value, ms=ms.value, alg_bytes=by.value, units=un.value)
 
     KERNELS = ("k_msm_tblw<32, false>", "k_reduce_sets", "k_msm_tblw<16, false>", "k_msm_tblw<8, false>", "k_msm_tblw<4, false>", "k_msm_tblw<2, false>", "k_msm_fix<19, 7>", "k_msm_fix<16, 4>", "k_msm_fix<16, 2>", "k_msm_fix<16, 16>", "k_msm_fix<16, 8>", "k_msm_fix<8, 16>", "k_msm_fix<8, 8>",
-               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_vs_crs_sum_groups", "k_rng_draw", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
+               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
 
     def stats(self):
         return {k: self.stat(k) for k in self.KERNELS}

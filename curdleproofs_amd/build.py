@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(OUT_DIR, "libcpx.so")
 ARCH = "gfx950"
-SOURCES = ["kernels.hip", "late.hip", "protocol.hip", "round.hip", "tracker.hip", "shuffle.hip", "genmul.hip", "find.hip", "rng.hip", "engine.cpp", "engine_device.cpp", "whisk.cpp", "capi.cpp"]
+SOURCES = ["kernels.hip", "late.hip", "protocol.hip", "round.hip", "tracker.hip", "shuffle.hip", "genmul.hip", "find.hip", "rng.hip", "rng_g1.hip", "engine.cpp", "engine_device.cpp", "whisk.cpp", "capi.cpp"]
 # host side: x86-64-v3 + ADX (BMI2 mulx / andn / rorx: the Keccak permutation of the transcripts runs 1.7x faster, the
 # 64-bit-limb Fr products use mulx); every host of an MI355X (EPYC 9005) has them
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-ffp-contract=off",
@@ -35,6 +35,9 @@ SCALARCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "scalar_check.hip"
 # test-only device program: every function of rng.hpp on raw words (tests/test_gpu_rng.py)
 RNGCHECK = os.path.join(OUT_DIR, "rng_check")
 RNGCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "rng_check.hip")
+# test-only device program: the pieces of G1::rand on raw words (tests/test_gpu_rng_g1.py)
+RNGG1CHECK = os.path.join(OUT_DIR, "rng_g1_check")
+RNGG1CHECK_SRC = os.path.join(HERE, "..", "tests", "device", "rng_g1_check.hip")
 # test-only device program: the MSM wave bodies of msm_body.hpp bucket by bucket and the library's own reducers on crafted sets
 # (tests/test_gpu_msm_waves.py); it calls the launchers of kernels.h, so it is linked against the finished libcpx.so beside it
 MSMCHECK = os.path.join(OUT_DIR, "msm_check")
@@ -55,11 +58,12 @@ def _stale():
     scheck = os.path.exists(SCALARCHECK_SRC)
     rcheck = os.path.exists(RNGCHECK_SRC)
     mcheck = os.path.exists(MSMCHECK_SRC)
-    outs = [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else []) + ([SCALARCHECK] if scheck else []) + ([RNGCHECK] if rcheck else []) + ([MSMCHECK] if mcheck else [])
+    gcheck = os.path.exists(RNGG1CHECK_SRC)
+    outs = ([RNGG1CHECK] if gcheck else []) + [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else []) + ([SCALARCHECK] if scheck else []) + ([RNGCHECK] if rcheck else []) + ([MSMCHECK] if mcheck else [])
     if not all(os.path.exists(o) for o in outs):
         return True
     t = min(os.path.getmtime(o) for o in outs)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else []) + ([SCALARCHECK_SRC] if scheck else []) + ([RNGCHECK_SRC] if rcheck else []) + ([MSMCHECK_SRC] if mcheck else [])
+    deps = ([RNGG1CHECK_SRC] if gcheck else []) + [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else []) + ([SCALARCHECK_SRC] if scheck else []) + ([RNGCHECK_SRC] if rcheck else []) + ([MSMCHECK_SRC] if mcheck else [])
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -118,6 +122,10 @@ def build(force=False, verbose=False):
             rcheck = os.path.exists(RNGCHECK_SRC)
             if rcheck:
                 procs.append(("rng_check.hip", subprocess.Popen(_rngcheck_cmd(tmp_rcheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+            tmp_gcheck = os.path.join(work, "rng_g1_check")
+            gcheck = os.path.exists(RNGG1CHECK_SRC)
+            if gcheck:
+                procs.append(("rng_g1_check.hip", subprocess.Popen(_rngg1check_cmd(tmp_gcheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
             tmp_mobj, tmp_mcheck = os.path.join(work, "msm_check.o"), os.path.join(work, "msm_check")
             mcheck = os.path.exists(MSMCHECK_SRC)
             if mcheck:
@@ -144,6 +152,8 @@ def build(force=False, verbose=False):
                 os.replace(tmp_scheck, SCALARCHECK)
             if rcheck:
                 os.replace(tmp_rcheck, RNGCHECK)
+            if gcheck:
+                os.replace(tmp_gcheck, RNGG1CHECK)
         finally:
             shutil.rmtree(work, ignore_errors=True)
         build_selfcheck()
@@ -217,6 +227,21 @@ def build_rngcheck():
     subprocess.check_call(_rngcheck_cmd(RNGCHECK + ".tmp"))
     os.replace(RNGCHECK + ".tmp", RNGCHECK)
     return RNGCHECK
+
+
+def _rngg1check_cmd(out):
+    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [RNGG1CHECK_SRC, "-o", out]
+
+
+def build_rngg1check():
+    """The device build of tests/device/rng_g1_check.hip alone (build() compiles it with the library; the host twin is compiled by the
+    tests with g++): cross-compiled here, it travels with the library."""
+    if not os.path.exists(RNGG1CHECK_SRC):
+        raise RuntimeError("tests/device/rng_g1_check.hip is missing: the device G1 rng check cannot be built")
+    os.makedirs(OUT_DIR, exist_ok=True)
+    subprocess.check_call(_rngg1check_cmd(RNGG1CHECK + ".tmp"))
+    os.replace(RNGG1CHECK + ".tmp", RNGG1CHECK)
+    return RNGG1CHECK
 
 
 def _msmcheck_compile_cmd(obj):

@@ -65,6 +65,23 @@ def crs_from_json(ctx, text):
     return crs_from_hex(ctx, json.loads(text))
 
 
+# ---- the crate's generate_crs (src/crs.rs:61-69) ------------------------------------------------------------------------
+def generate_crs(ctx, ell, rng=None):
+    """`generate_crs(ell)`: ell + 7 `G1Projective::rand` draws from `rng` — default `StdRng::seed_from_u64(0)`, as crs.rs:63 — made on the
+    device and loaded like `Context.set_crs` (cpx_crs_generate).  `rng` advances.  Returns the ell + 7 affine points."""
+    import ctypes
+    from .rng import STATE_BYTES, StdRng
+    rng = StdRng.seed_from_u64(0) if rng is None else rng
+    state = (ctypes.c_uint8 * STATE_BYTES).from_buffer_copy(rng.state)
+    pts = (ctypes.c_uint8 * (AFF * (ell + 7)))()
+    ctx._check(ctx._L.cpx_crs_generate(ctx._h, ell, state, pts))
+    rng.state = bytes(state)
+    ctx.ell = ell
+    ctx.n = ell + N_BLINDERS
+    ctx.crs_points = bytes(pts)
+    return ctx.crs_points
+
+
 # ---- hash-to-curve CRS: /root/reference/tests/crs.rs:13-52 `generate_random_points` -------------------------------------
 COFACTOR = 0x396c8c005555e1568c00aaab0000aaab   # |E(Fp)| / r: `mul_by_cofactor` multiplies by the full cofactor (not h_eff)
 CRS_EXTRA_POINTS = 3                             # crs.rs: H, G_t, G_u

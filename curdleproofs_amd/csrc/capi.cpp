@@ -470,6 +470,34 @@ int cpx_rng_fr(cpx_ctx* ctx, size_t count, uint8_t* states, size_t n_each, uint8
     return (int)CPX_OK;
   });
 }
+int cpx_rng_g1(cpx_ctx* ctx, size_t count, uint8_t* states, size_t n_each, uint8_t* out_affine, uint8_t* out_compressed) {
+  if (count && n_each && (!states || !out_affine)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->rng_g1(count, states, n_each, out_affine, out_compressed);
+    return (int)CPX_OK;
+  });
+}
+int cpx_rng_instance_draws(cpx_ctx* ctx, size_t count, uint8_t* states, uint32_t* permutation_out, uint8_t* k_out, uint8_t* vec_R_out, uint8_t* vec_S_out) {
+  if (count && !states) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->rng_instance_draws(count, states, permutation_out, k_out, vec_R_out, vec_S_out);
+    return (int)CPX_OK;
+  });
+}
+int cpx_crs_generate(cpx_ctx* ctx, size_t ell, uint8_t state[40], uint8_t* points_out) {
+  if (!state) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->crs_generate(ell, state, points_out);
+    return (int)CPX_OK;
+  });
+}
+int cpx_g1_clear_cofactor(cpx_ctx* ctx, const uint8_t* points, size_t n, uint8_t* out_affine) {
+  if (n && (!points || !out_affine)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->clear_cofactor(points, n, out_affine);
+    return (int)CPX_OK;
+  });
+}
 int cpx_rng_shuffle_draws(cpx_ctx* ctx, size_t count, uint8_t* states, uint32_t* permutation_out, uint8_t* k_out, uint8_t* blinders_out, uint8_t* rand_out) {
   if (count && !states) return CPX_ERR_ARG;
   return guarded(ctx, [&] {

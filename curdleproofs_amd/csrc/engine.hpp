@@ -28,6 +28,7 @@
 #include "protocol.h"
 #include "prove_reqs.hpp"
 #include "rng.hpp"
+#include "rng_g1_plan.hpp"
 #include "shuffle_plan.hpp"
 #include "tbl_plan.hpp"
 #include "tier0_plan.hpp"
@@ -221,6 +222,14 @@ class Engine {
   // ---- the reference's `rng: &mut T` as ChaCha12 states (rng.hpp), the draws made on the device by k_rng_draw (rng.hip; whisk.cpp) ----
   // states: count x 40 bytes, in/out; a call that throws leaves them as they were
   void rng_fr(size_t count, uint8_t* states, size_t n_each, uint8_t* out);
+  // G1Projective::rand(rng).into_affine() n_each times per stream (rng_g1.hip); either output may be null.  Needs no CRS, leaves the batch alone
+  void rng_g1(size_t count, uint8_t* states, size_t n_each, uint8_t* out_affine, uint8_t* out_compressed);
+  // README.md:85-95 per stream at the loaded ell: shuffle of 0..ell, k, vec_R, vec_S; any output may be null, the states advance by the whole set
+  void rng_instance_draws(size_t count, uint8_t* states, uint32_t* permutation_out, uint8_t* k_out, uint8_t* vec_R_out, uint8_t* vec_S_out);
+  // crs.rs:61-69 generate_crs(ell) from the caller's stream: ell + 7 draws, then set_crs; points_out (nullable) receives them
+  void crs_generate(size_t ell, uint8_t* state, uint8_t* points_out);
+  // mul_by_cofactor for n points of E(Fp) (k_clear_cofactor), independent of option scale_any_point
+  void clear_cofactor(const uint8_t* points, size_t n, uint8_t* out_affine);
   // the draws of one generate_whisk_shuffle_proof per stream (shuffle, k, 4 blinders, 3n + 9), downloaded; any output may be null.
   // states_after_k (nullable): every stream's state as it stands after the shuffle and k (whisk.rs:150-157 returns Err there)
   void rng_shuffle_draws(size_t count, uint8_t* states, uint32_t* permutation_out, uint8_t* k_out, uint8_t* blinders_out, uint8_t* rand_out,
@@ -263,6 +272,11 @@ class Engine {
       Tier0::each(t0_, add);
       ShuffleBufs::each(sh_, add);
       if (value) *value = (long)sum;
+      return true;
+    }
+    // "rng_g1_last_rounds" = the rounds the last G1 draw call took (the most over its chunks of streams; rng_g1_plan.hpp)
+    if (key && !strcmp(key, "rng_g1_last_rounds")) {
+      if (value) *value = (long)rng_g1_rounds_;
       return true;
     }
     return cpx::get_option(opt_, key, value);
@@ -424,6 +438,7 @@ class Engine {
     const int uncaught_;
   };
   bool in_call_ = false;
+  size_t rng_g1_rounds_ = 0;
   // the bucket-list form of msm / msm_many and the body of fold / fold_many (engine.cpp): the single calls are the many-calls of one task
   void msm_lists(Tier0MsmPlan& pl, const uint32_t* lens, const uint8_t* bases, const uint8_t* scalars, uint8_t* out_jac, uint8_t* out_comp);
   void fold_lanes(size_t families, size_t half, uint8_t* PL, const uint8_t* PR, const uint8_t* gammas, long quad_max);

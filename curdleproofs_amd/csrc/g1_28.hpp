@@ -298,6 +298,45 @@ CPX_HD bool g1_28_in_subgroup(const Aff28& P) {
   return f28_eq(lhs_x, q.x) && f28_eq(lhs_y, f28_neg(q.y));
 }
 
+// ark-ec `get_point_from_x_unchecked(x, greatest)` on y^2 = x^3 + 4: false where x^3 + 4 is not a square; otherwise *out = (x, y) with y
+// the root whose canonical integer is the larger of (y, p - y) iff `greatest` — the rule k_decompress applies for the sort flag.
+// `sqrt`: f28_sqrt_candidate, or a kernel's out-of-line wrapper of it.
+template <class Sqrt> CPX_HD bool g1_28_point_from_x_with(const F28& x, bool greatest, Aff28* out, Sqrt&& sqrt) {
+  const F28 rhs = f28_add(f28_mul(f28_sqr(x), x), f28_const(F28Cfg::FOUR));
+  const F28 y = sqrt(rhs);
+  if (!f28_eq(f28_sqr(y), rhs)) return false;
+  const Fp ys = f28_to_std(y), nys = fe_neg(ys);
+  const bool y_larger = fe_raw_gt(fe_from_mont(ys), fe_from_mont(nys));
+  out->x = x;
+  out->y = f28_cneg(y, y_larger != greatest);
+  return true;
+}
+CPX_HD bool g1_28_point_from_x(const F28& x, bool greatest, Aff28* out) {
+  return g1_28_point_from_x_with(x, greatest, out, [](const F28& a) { return f28_sqrt_candidate(a); });
+}
+
+// [h] P for the full cofactor h = |E(Fp)| / r = 0x396c8c005555e1568c00aaab0000aaab (ark-ec `mul_by_cofactor` of bls12_381::g1, not h_eff),
+// for ANY point of E(Fp): the inputs are not in the subgroup, and points of small order send the chain through P + P, P + (-P) and the
+// identity, so every step is one of the complete formulas above (|E(Fp)| is odd: no doubling meets y = 0).
+// h = m3 * m with m = |z - 1| = 0xd201000000010001 and m3 = m / 3 = 0x460055555555aaab.  The chain is compiled in — both exponents are
+// constants, no lane recodes anything and every `if` on a bit below is the same in all lanes: [m3] P by 62 doublings and 27 MIXED
+// additions of P (the Hamming weight of m3 less one), then [m] of that by 63 doublings and 6 full additions: 125 doublings and 33
+// additions, 7 * 125 + 11 * 27 + 16 * 6 = 1268 field products.
+CPX_HD Jac28 g1_28_clear_cofactor(const Aff28& P) {
+  const uint64_t M3 = 0x460055555555aaabull, M = 0xd201000000010001ull;
+  Jac28 q = Jac28::from_affine(P);
+  for (int b = 61; b >= 0; b--) {   // bit 62 is the leading one
+    q = jac28_dbl(q);
+    if ((M3 >> b) & 1) q = jac28_add_mixed(q, P);
+  }
+  const Jac28 q1 = q;
+  for (int b = 62; b >= 0; b--) {   // bit 63 is the leading one
+    q = jac28_dbl(q);
+    if ((M >> b) & 1) q = jac28_add(q, q1);
+  }
+  return q;
+}
+
 }  // namespace cpx
 
 // ------------------------------------------------------------------ kernel-facing names

@@ -67,6 +67,7 @@ struct Options {
   long locate_groups_max = 256;    // cpx_batch_verify_grouped / cpx_whisk_verify_shuffle_proofs_grouped: the batch is cut into at most this many groups (1 .. 256; locate_plan.hpp); the fewer the groups, the more proofs one wrong proof sends to the second stage.  The grouping of cpx_batch_verify_fused stays at 256
   long find_table_min_keys = 256;  // cpx_whisk_find_trackers: from this many keys on the call builds a per-tracker table of multiples and scans it (k_find_scan), below it one k_smul element per (tracker, key) pair (1 .. 2^20 + 1: 1 = always the table, 2^20 + 1 = never; find_plan.hpp).  Measured at 8192 trackers (profiles/find_trackers.md): the table path costs 34 ms before the first pair (k_table_build + k_fix_build) and is level with the ladder at 128 keys (37.4 against 36.1 ms), ahead at 256 (41.5 against 69.2) — the smallest measured power of two with the table ahead.  The operation counts alone said 64 (break-even near 57 keys); they leave out that the table build runs at a fraction of the scan's product rate
   long find_table_mb = 1024;       // ... and the trackers are processed in chunks whose table and build scratch stay within this many MiB (1 .. 65536; 0.56 MiB per tracker)
+  long rng_g1_round_cap = 0;       // cpx_rng_g1 and the calls on top of it: 0 = a stream emits 2 need + 8 ceil(sqrt(need)) + 16 candidates per round (rng_g1_plan.hpp: one round is the expected case), k > 0 = at most k — the later rounds on demand, for the tests
   long scale_any_point = 0;        // 1: cpx_g1_scale / cpx_g1_fold take ANY point of E(Fp) (plain 257-step double-and-add, SMUL_PLAIN); 0: points of the order-r subgroup (endomorphism split, 129 steps)
 };
 const Options& default_options();                               // built-in defaults overridden by CPX_<NAME> environment variables
@@ -364,6 +365,29 @@ struct RngDrawArgs {
 };
 size_t rng_draw_max_shuffle();   // the longest permutation a wave holds in LDS
 void launch_rng_draw(const RngDrawArgs& a, hipStream_t s);
+
+// ---- G1::rand from ChaCha12 states and the cofactor multiplication (rng_g1.hip; the rounds and the scratch records in rng_g1_plan.hpp) ----
+struct RngG1Stream;
+struct RngG1Cand;
+// One chunk of streams: states [nstreams][40] (read for the keys only), streams [nstreams] (position, points done, shortfall: in/out),
+// cand / pts [nstreams][cap] (the round's candidates and the points of those with a root), sel [nstreams][n_each] (output slot -> candidate
+// index or RNG_G1_NONE, rewritten every round), shortfall [nstreams] (what the host reads between the rounds)
+struct RngG1Args {
+  const uint8_t* states;
+  RngG1Stream* streams;
+  RngG1Cand* cand;
+  Aff28* pts;
+  uint32_t* sel;
+  uint32_t* shortfall;
+  uint32_t nstreams, cap, n_each;
+  uint32_t round_cap;   // option rng_g1_round_cap (0: the formula alone)
+};
+void launch_rng_g1_scan(const RngG1Args& a, hipStream_t s);
+void launch_rng_g1_sqrt(const RngG1Args& a, hipStream_t s);
+void launch_rng_g1_select(const RngG1Args& a, hipStream_t s);
+// d_out[g] = affine([h] P_g), standard form, the identity as x = y = 0, g < n.  d_sel != null: P_g = d_pts[d_sel[g]], slots whose entry is
+// RNG_G1_NONE are left as they are; d_sel == null: P_g = d_std_in[g], any point of E(Fp)
+void launch_clear_cofactor(const uint32_t* d_sel, const Aff28* d_pts, const Aff* d_std_in, size_t n, Aff* d_out, hipStream_t s);
 
 void launch_sum_jac(const Jac* d_in, int n, Jac* d_out, int* d_flag, hipStream_t s);
 void launch_bench_fpmul(Fp* d_data, int blocks, int iters, hipStream_t s);

@@ -11,6 +11,12 @@
 //   gen_range  rand 0.8 `UniformInt<u32>::sample_single(0, range)`: widening multiply of one u32 by the range, accepted when the low
 //              half is <= zone = (range << clz(range)) - 1
 //   shuffle    rand 0.8 `SliceRandom::shuffle`: i from len - 1 down to 1, j = gen_range(0..i + 1), swap(i, j)
+//   G1::rand   ark-ec 0.4 `Projective::rand` (recalled; the reference's known-answer test pins it through the oracle): a loop over TOKENS.
+//              A candidate is six u64 least significant limb first, the top three bits cleared (381-bit modulus); a value >= p is
+//              rejected and nothing else is drawn for it.  An accepted candidate — its limbs ARE the Montgomery form of x — is followed
+//              by ONE word whose top bit is `greatest` (rand's `Standard` for bool), whether or not x^3 + 4 is a square; where it is, the
+//              draw is [h](x, y) with y the larger of (y, p - y) iff `greatest` and h the full cofactor (g1_28.hpp).  Where a token ends
+//              depends on the compare with p alone: rng_g1_candidate walks tokens, the square roots are somebody else's work
 //   seed       rand_core 0.6 `SeedableRng::seed_from_u64`: eight PCG32 outputs are the key, word_pos = 0
 //   split      `ChaCha12Rng::from_rng(&mut parent)`: the child's key is the next eight words of the parent, its word_pos is 0
 //
@@ -29,6 +35,7 @@ namespace cpx {
 constexpr int RNG_STATE_BYTES = 40;
 constexpr int RNG_BLOCK_WORDS = 16;
 constexpr int RNG_FR_WORDS = 8;   // u32 words of one Fr::rand candidate
+constexpr int RNG_FP_WORDS = 12;  // u32 words of one Fp::rand candidate (the x of a G1::rand token)
 
 CPX_HD bool rng_pos_valid(uint64_t word_pos) { return word_pos < 0xffffffff00000000ull; }
 
@@ -131,6 +138,27 @@ template <class W> CPX_HD void rng_fr(W& w, uint32_t out[RNG_FR_WORDS]) {
     for (int i = 0; i < RNG_FR_WORDS; i++) out[i] = w.next_u32();   // four next_u64, low word first
     if (rng_fr_accept(out)) return;
   }
+}
+
+// One Fp::rand candidate: the twelve words as they come off the stream.  Clears the top three bits in place; true iff the value is below p.
+CPX_HD bool rng_fp_accept(uint32_t limbs[RNG_FP_WORDS]) {
+  limbs[11] &= 0x1fffffffu;
+  bool lt = false, decided = false;
+  for (int i = 11; i >= 0; i--) {
+    const uint32_t p = FpCfg::P[i];
+    const bool ne = limbs[i] != p;
+    if (!decided && ne) lt = limbs[i] < p;
+    decided = decided || ne;
+  }
+  return lt;   // equal to p: rejected
+}
+// One accepted token of G1::rand: x (Montgomery limbs) and the bool drawn behind it; rejected candidates are walked over
+template <class W> CPX_HD void rng_g1_candidate(W& w, uint32_t x[RNG_FP_WORDS], bool& greatest) {
+  for (;;) {
+    for (int i = 0; i < RNG_FP_WORDS; i++) x[i] = w.next_u32();   // six next_u64, low word first
+    if (rng_fp_accept(x)) break;
+  }
+  greatest = (w.next_u32() >> 31) != 0;   // rand 0.8 Standard for bool: the most significant bit of one u32
 }
 
 // sample_single(0, range), range >= 1

@@ -717,6 +717,157 @@ void Engine::rng_fr(size_t count, uint8_t* states, size_t n_each, uint8_t* out) 
   memcpy(states, st.data(), st.size());
 }
 
+// G1Projective::rand(rng).into_affine() n_each times per stream (rng_g1.hip; the rounds in rng_g1_plan.hpp).  Rounds run per chunk of
+// streams until no stream of the chunk owes a point; between two rounds the host reads the chunk's shortfall counts and nothing else.
+// The scratch is one carved block of the tier-0 set: the call's scope gives back what grew beyond kTier0Keep.
+void Engine::rng_g1(size_t count, uint8_t* states, size_t n_each, uint8_t* out_affine, uint8_t* out_compressed) {
+  if (!RngG1Plan::fits(count, n_each)) throw ArgError("rng G1 draws: at most 2^20 streams, 2^16 points each and 2^22 points per call");
+  if (!count || !n_each) return;
+  check_rng_states(count, states);
+  const RngG1Plan pl(count, n_each, opt_.rng_g1_round_cap);
+  const size_t total = count * n_each;
+  std::vector<RngG1Stream> hs(count);
+  std::vector<uint32_t> owed(pl.chunk);
+  for (size_t i = 0; i < count; i++) {
+    uint64_t pos;
+    memcpy(&pos, states + i * RNG_STATE_BYTES + 32, 8);
+    hs[i] = RngG1Stream{pos, pos, 0, (uint32_t)n_each, 0, 0};
+  }
+  CallScope call(this);
+  DevBuf<Aff>& dout = t0_.a0;
+  DevBuf<uint8_t>&dcomp = sh_.bytes, &blob = t0_.bytes;
+  const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_states = 0, o_streams = o_states + up(pl.chunk * RNG_STATE_BYTES), o_owed = o_streams + up(pl.chunk * sizeof(RngG1Stream)),
+               o_sel = o_owed + up(pl.chunk * sizeof(uint32_t)), o_cand = o_sel + up(pl.chunk * n_each * sizeof(uint32_t)),
+               o_pts = o_cand + up(pl.chunk * pl.cap * sizeof(RngG1Cand)), o_end = o_pts + up(pl.chunk * pl.cap * sizeof(Aff28));
+  dout.ensure(total);
+  if (out_compressed) dcomp.ensure(total * 48);
+  blob.ensure(o_end);
+  RngG1Args a{};
+  a.states = blob.p + o_states;
+  a.streams = reinterpret_cast<RngG1Stream*>(blob.p + o_streams);
+  a.shortfall = reinterpret_cast<uint32_t*>(blob.p + o_owed);
+  a.sel = reinterpret_cast<uint32_t*>(blob.p + o_sel);
+  a.cand = reinterpret_cast<RngG1Cand*>(blob.p + o_cand);
+  a.pts = reinterpret_cast<Aff28*>(blob.p + o_pts);
+  a.cap = (uint32_t)pl.cap;
+  a.n_each = (uint32_t)n_each;
+  a.round_cap = (uint32_t)opt_.rng_g1_round_cap;
+  const size_t round_limit = 4096 + 64 * n_each;   // (a candidate has a root with probability 1/2: a stream that gets nowhere in this many rounds is a bug, not bad luck)
+  rng_g1_rounds_ = 0;
+  for (size_t c = 0; c < pl.chunks(); c++) {
+    const size_t first = c * pl.chunk, n = pl.chunk_streams(c);
+    a.nstreams = (uint32_t)n;
+    CPX_HIP(hipMemcpyAsync(blob.p + o_states, states + first * RNG_STATE_BYTES, n * RNG_STATE_BYTES, hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(a.streams, hs.data() + first, n * sizeof(RngG1Stream), hipMemcpyHostToDevice, stream_));
+    for (size_t round = 1;; round++) {
+      if (round > round_limit) throw std::runtime_error("rng G1 draws: a stream made no progress");
+      tick("k_rng_g1_scan", 0, (double)n);
+      launch_rng_g1_scan(a, stream_);
+      tock();
+      tick("k_rng_g1_sqrt", 0, (double)(n * pl.cap));
+      launch_rng_g1_sqrt(a, stream_);
+      tock();
+      tick("k_rng_g1_select", 0, (double)n);
+      launch_rng_g1_select(a, stream_);
+      tock();
+      tick("k_clear_cofactor", 192.0 * (n * n_each), (double)(n * n_each));
+      launch_clear_cofactor(a.sel, a.pts, nullptr, n * n_each, dout.p + first * n_each, stream_);
+      tock();
+      CPX_HIP(hipMemcpyAsync(owed.data(), a.shortfall, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+      CPX_HIP(hipStreamSynchronize(stream_));
+      rng_g1_rounds_ = std::max(rng_g1_rounds_, round);
+      bool more = false;
+      for (size_t i = 0; i < n; i++) more = more || owed[i] != 0;
+      if (!more) break;
+    }
+    CPX_HIP(hipMemcpyAsync(hs.data() + first, a.streams, n * sizeof(RngG1Stream), hipMemcpyDeviceToHost, stream_));   // the positions (the next chunk reuses the block)
+  }
+  if (out_compressed) {
+    tick("k_compress", 144.0 * total, (double)total);
+    launch_compress(dout.p, (int)total, (int)total, 1, dcomp.p, stream_);
+    tock();
+    CPX_HIP(hipMemcpyAsync(out_compressed, dcomp.p, total * 48, hipMemcpyDeviceToHost, stream_));
+  }
+  if (out_affine) CPX_HIP(hipMemcpyAsync(out_affine, dout.p, total * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
+  call.finish();
+  for (size_t i = 0; i < count; i++) memcpy(states + i * RNG_STATE_BYTES + 32, &hs[i].pos, 8);
+}
+
+// [h] P for n points of E(Fp), whatever option scale_any_point says
+void Engine::clear_cofactor(const uint8_t* points, size_t n, uint8_t* out_affine) {
+  if (n > ((size_t)1 << 24)) throw ArgError("cpx_g1_clear_cofactor: at most 2^24 points per call");
+  if (!n) return;
+  CallScope call(this);
+  DevBuf<Aff>&din = t0_.a0, &dout = t0_.a1;
+  din.ensure(n);
+  dout.ensure(n);
+  CPX_HIP(hipMemcpyAsync(din.p, points, n * sizeof(Aff), hipMemcpyHostToDevice, stream_));
+  tick("k_clear_cofactor", 192.0 * n, (double)n);
+  launch_clear_cofactor(nullptr, nullptr, din.p, n, dout.p, stream_);
+  tock();
+  CPX_HIP(hipMemcpyAsync(out_affine, dout.p, n * sizeof(Aff), hipMemcpyDeviceToHost, stream_));
+  call.finish();
+}
+
+// crs.rs:61-69 generate_crs on the caller's stream: ell + 7 draws, then from_points.  Refusals of set_crs come before the first word
+void Engine::crs_generate(size_t ell, uint8_t* state, uint8_t* points_out) {
+  const size_t n = ell + 4;   // (Engine::set_crs: ell + N_BLINDERS)
+  if (ell == 0 || (n & (n - 1))) throw std::invalid_argument("ell + 4 must be a power of two");
+  if (ell + 7 > kRngG1EachMax) throw ArgError("cpx_crs_generate: ell + 7 exceeds the points one stream draws per call");
+  std::vector<uint8_t> st(state, state + RNG_STATE_BYTES), pts((ell + 7) * sizeof(Aff));
+  rng_g1(1, st.data(), ell + 7, pts.data(), nullptr);
+  set_crs(ell, pts.data());
+  memcpy(state, st.data(), st.size());
+  if (points_out) memcpy(points_out, pts.data(), pts.size());
+}
+
+// README.md:85-95 per stream at the context's ell: the shuffle of 0..ell, k, vec_R, vec_S — one k_rng_draw program, then 2 ell G1 draws
+void Engine::rng_instance_draws(size_t count, uint8_t* states, uint32_t* permutation_out, uint8_t* k_out, uint8_t* vec_R_out, uint8_t* vec_S_out) {
+  if (!count) return;
+  if (!ell_) throw std::logic_error("set_crs first");
+  const size_t ell = ell_;
+  if (!RngG1Plan::fits(count, 2 * ell) || !ShufflePlan(count, ell, false).fits()) throw ArgError("rng instance draws: too many streams for one call");
+  if (ell > rng_draw_max_shuffle()) throw ArgError("rng shuffle draws: ell exceeds the permutation a wave holds");
+  check_rng_states(count, states);
+  std::vector<uint8_t> st(states, states + count * RNG_STATE_BYTES), k(count * sizeof(Fr)), pts(count * 2 * ell * sizeof(Aff));
+  std::vector<uint32_t> perm(count * ell);
+  {
+    CallScope call(this);
+    DevBuf<uint8_t>& dst = t0_.bytes;
+    DevBuf<Fr>& dfr = t0_.fr;
+    dst.ensure(count * RNG_STATE_BYTES);
+    dfr.ensure(count);
+    sh_.perm.ensure(count * ell);
+    CPX_HIP(hipMemcpyAsync(dst.p, st.data(), st.size(), hipMemcpyHostToDevice, stream_));
+    RngDrawArgs a{};
+    a.states = dst.p;
+    a.mid_phase = -1;
+    a.count = (uint32_t)count;
+    a.shuffle_len = (uint32_t)ell;
+    a.perm = sh_.perm.p;
+    a.nfr = 1;
+    a.fr_cnt[0] = 1;
+    a.fr_out[0] = dfr.p;
+    tick("k_rng_draw", (double)(count * (ell * sizeof(uint32_t) + sizeof(Fr))), (double)count);
+    launch_rng_draw(a, stream_);
+    tock();
+    CPX_HIP(hipMemcpyAsync(perm.data(), sh_.perm.p, perm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+    CPX_HIP(hipMemcpyAsync(k.data(), dfr.p, k.size(), hipMemcpyDeviceToHost, stream_));
+    CPX_HIP(hipMemcpyAsync(st.data(), dst.p, st.size(), hipMemcpyDeviceToHost, stream_));
+    call.finish();
+  }
+  rng_g1(count, st.data(), 2 * ell, pts.data(), nullptr);
+  const size_t row = ell * sizeof(Aff);
+  if (permutation_out) memcpy(permutation_out, perm.data(), perm.size() * sizeof(uint32_t));
+  if (k_out) memcpy(k_out, k.data(), k.size());
+  for (size_t i = 0; i < count; i++) {
+    if (vec_R_out) memcpy(vec_R_out + i * row, pts.data() + 2 * i * row, row);
+    if (vec_S_out) memcpy(vec_S_out + i * row, pts.data() + (2 * i + 1) * row, row);
+  }
+  memcpy(states, st.data(), st.size());
+}
+
 // whisk.rs:144-179: the draws of one generate_whisk_shuffle_proof per stream — shuffle, k, 4 blinders, 3n + 9 — downloaded
 void Engine::rng_shuffle_draws(size_t count, uint8_t* states, uint32_t* permutation_out, uint8_t* k_out, uint8_t* blinders_out, uint8_t* rand_out, uint8_t* states_after_k) {
   if (!count) return;

@@ -89,6 +89,18 @@ pub fn generate_random_points(num_points: usize, seed: &str) -> (Vec<G1Affine>, 
     (points, increment)
 }
 
+/// src/crs.rs:61-69 `generate_crs(ell)`: the ell + 7 `G1Projective::rand` draws made on the device from the rng's state
+/// (`cpx_crs_generate`, which also loads the CRS into the thread's context), `rng` continued where the library stopped.  The crate's own
+/// function is this one on `StdRng::seed_from_u64(0)`.
+pub fn generate_crs(ell: usize, rng: &mut rand_chacha::ChaCha12Rng) -> CurdleproofsCrs {
+    let mut state = rng_state(rng);
+    let mut wire = vec![0u8; AFF * (ell + 7)];
+    let rc = unsafe { cpx_crs_generate(ctx(), ell, state.as_mut_ptr(), wire.as_mut_ptr()) };
+    assert_eq!(rc, CPX_OK, "cpx_crs_generate");
+    rng_resume(rng, &state);
+    CurdleproofsCrs::from_points(ell, &affine_from_wire(&wire)).unwrap()
+}
+
 /// tests/crs.rs:54-66 `ethereum_crs_128_seed`: the CRS of `n` = ell + N_BLINDERS generators from a seed string
 pub fn crs_from_seed(ell: usize, seed: &str) -> (CurdleproofsCrs, u64) {
     let (points, attempts) = generate_random_points(ell + N_BLINDERS + CRS_EXTRA_POINTS, seed);

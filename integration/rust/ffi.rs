@@ -109,6 +109,11 @@ extern "C" {
     pub fn cpx_whisk_generate_shuffle_proofs_rng(ctx: *mut cpx_ctx, count: usize, pre_trackers: *const u8, states: *mut u8, post_trackers_out: *mut u8,
                                                  proofs_out: *mut u8, status: *mut c_int) -> c_int;
     pub fn cpx_batch_prove_rng(ctx: *mut cpx_ctx, permutation: *const u32, k: *const u8, vec_m_blinders: *const u8, states: *mut u8, proofs_out: *mut u8) -> c_int;
+    pub fn cpx_rng_g1(ctx: *mut cpx_ctx, count: usize, states: *mut u8, n_each: usize, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
+    pub fn cpx_rng_instance_draws(ctx: *mut cpx_ctx, count: usize, states: *mut u8, permutation_out: *mut u32, k_out: *mut u8, vec_R_out: *mut u8,
+                                  vec_S_out: *mut u8) -> c_int;
+    pub fn cpx_crs_generate(ctx: *mut cpx_ctx, ell: usize, state: *mut u8, points_out: *mut u8) -> c_int;
+    pub fn cpx_g1_clear_cofactor(ctx: *mut cpx_ctx, points: *const u8, n: usize, out_affine: *mut u8) -> c_int;
 }
 
 pub const RNG_STATE: usize = 40;
