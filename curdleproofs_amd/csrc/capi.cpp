@@ -378,6 +378,24 @@ int cpx_whisk_verify_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* t
     return (int)CPX_OK;
   });
 }
+int cpx_whisk_verify_tracker_proofs_fused(cpx_ctx* ctx, size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, const uint8_t* rand,
+                                          uint8_t* partial_jac, int* n_invalid) {
+  if (!tracker_check_fits(count)) return CPX_ERR_ARG;   // before anything is read
+  if (!partial_jac || !n_invalid || (count && (!trackers || !k_commitments || !proofs || !rand))) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_verify_tracker_proofs_fused(count, trackers, k_commitments, proofs, rand, partial_jac, n_invalid);
+    return (int)CPX_OK;
+  });
+}
+int cpx_whisk_verify_tracker_proofs_grouped(cpx_ctx* ctx, size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, const uint8_t* rand,
+                                            int* verdict, size_t* n_rechecked) {
+  if (!tracker_check_fits(count)) return CPX_ERR_ARG;   // before anything is read
+  if (count && (!trackers || !k_commitments || !proofs || !rand || !verdict)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_verify_tracker_proofs_grouped(count, trackers, k_commitments, proofs, rand, verdict, n_rechecked);
+    return (int)CPX_OK;
+  });
+}
 int cpx_g1_generator_mul(cpx_ctx* ctx, size_t count, const uint8_t* scalars, uint8_t* out_affine, uint8_t* out_compressed) {
   if (count && !scalars) return CPX_ERR_ARG;
   return guarded(ctx, [&] {

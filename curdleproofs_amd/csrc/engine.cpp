@@ -816,7 +816,7 @@ void Engine::msm_many(size_t count, const uint32_t* lens, const uint8_t* bases, 
   if (!out_jac && !out_comp) return;
   msm_lists(pl, lens, bases, scalars, out_jac, out_comp);
 }
-// ... and its body, which cpx_g1_msm takes with a plan of one task
+// ... and its body, which cpx_g1_msm takes with a plan of one task: the upload, the device chain below, the download
 void Engine::msm_lists(Tier0MsmPlan& pl, const uint32_t* lens, const uint8_t* bases, const uint8_t* scalars, uint8_t* out_jac, uint8_t* out_comp) {
   const size_t count = pl.count, np = pl.points;
   std::vector<MsmTask> tasks;
@@ -824,36 +824,17 @@ void Engine::msm_lists(Tier0MsmPlan& pl, const uint32_t* lens, const uint8_t* ba
   pl.slices = msm_tblw_slices(opt_, (int)count, 2, (int)pl.max_n);   // one value for every task of the call
   DevBuf<Aff>&db = t0_.a0, &daff = t0_.a1;
   DevBuf<Fr>& ds = t0_.fr;
-  DevBuf<MsmTask>& dt = t0_.mtask;
-  DevBuf<TblTask>& tt = t0_.ttask;
-  DevBuf<TAff>& conv = t0_.conv;
-  DevBuf<uint32_t>& dig = t0_.dig;
-  DevBuf<TJac>& part = t0_.part;
   DevBuf<Jac>& res = t0_.res;
   DevBuf<uint8_t>& dcomp = t0_.bytes;
   db.ensure(std::max<size_t>(np, 1));
   ds.ensure(std::max<size_t>(np, 1));
-  dt.ensure(count);
-  tt.ensure(count);
-  conv.ensure(std::max<size_t>(pl.conv_entries(), 1));
-  dig.ensure(std::max<size_t>(pl.digit_words(), 1));
-  part.ensure(pl.sets());
   res.ensure(count);
-  main_.ensure(pl.sets(), 0);
-  tasks.resize(count);
-  for (size_t i = 0; i < count; i++) tasks[i] = MsmTask{db.p + pl.conv_off[i], nullptr, ds.p + pl.conv_off[i], lens[i], 0, pl.conv_off[i]};
+  msm_chain_reserve(pl);
   if (np) {
     CPX_HIP(hipMemcpyAsync(db.p, bases, np * sizeof(Aff), hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(ds.p, scalars, np * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   }
-  CPX_HIP(hipMemcpyAsync(dt.p, tasks.data(), count * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
-  tick("k_msm_tblw<2, true>", 128.0 * np, (double)np);
-  launch_msm_endo(dt.p, (int)count, (int)pl.max_n, conv.p, dig.p, tt.p, main_.raw.p, main_.rawslot.p, stream_, pl.slices);
-  tock();
-  reduce_sets(stream_, main_, 0, pl.sets(), part.p);
-  tick("k_msm_tail", 0, (double)count);
-  launch_msm_tail(opt_, part.p, nullptr, res.p, (int)count, 16, 8, stream_, nullptr, 0, pl.tail_dup());
-  tock();
+  msm_chain(pl, lens, db.p, ds.p, res.p, tasks);
   if (out_jac) CPX_HIP(hipMemcpyAsync(out_jac, res.p, count * sizeof(Jac), hipMemcpyDeviceToHost, stream_));
   if (out_comp) {
     daff.ensure(count);
@@ -864,6 +845,32 @@ void Engine::msm_lists(Tier0MsmPlan& pl, const uint32_t* lens, const uint8_t* ba
     CPX_HIP(hipMemcpyAsync(out_comp, dcomp.p, count * 48, hipMemcpyDeviceToHost, stream_));
   }
   call.finish();
+}
+// The device half of the bucket-list MSM for a plan whose slices are set, inside the caller's scope: the scratch every task of the plan
+// needs beside its bases, scalars and results (reserved before the call's first launch: ensure() may free a buffer) ...
+void Engine::msm_chain_reserve(const Tier0MsmPlan& pl) {
+  t0_.mtask.ensure(pl.count);
+  t0_.ttask.ensure(pl.count);
+  t0_.conv.ensure(std::max<size_t>(pl.conv_entries(), 1));
+  t0_.dig.ensure(std::max<size_t>(pl.digit_words(), 1));
+  t0_.part.ensure(pl.sets());
+  main_.ensure(pl.sets(), 0);
+}
+// ... and the chain launch_msm_endo -> reduce_sets -> launch_msm_tail on bases and scalars that are on the device already, task i of lens[i]
+// points at offset pl.conv_off[i] of both; d_res receives pl.count sums in Jacobian standard form.  `tasks` is the caller's, declared above
+// its scope (an enqueued copy reads it).
+void Engine::msm_chain(const Tier0MsmPlan& pl, const uint32_t* lens, const Aff* d_bases, const Fr* d_scalars, Jac* d_res, std::vector<MsmTask>& tasks) {
+  const size_t count = pl.count, np = pl.points;
+  tasks.resize(count);
+  for (size_t i = 0; i < count; i++) tasks[i] = MsmTask{d_bases + pl.conv_off[i], nullptr, d_scalars + pl.conv_off[i], lens[i], 0, pl.conv_off[i]};
+  CPX_HIP(hipMemcpyAsync(t0_.mtask.p, tasks.data(), count * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+  tick("k_msm_tblw<2, true>", 128.0 * np, (double)np);
+  launch_msm_endo(t0_.mtask.p, (int)count, (int)pl.max_n, t0_.conv.p, t0_.dig.p, t0_.ttask.p, main_.raw.p, main_.rawslot.p, stream_, pl.slices);
+  tock();
+  reduce_sets(stream_, main_, 0, pl.sets(), t0_.part.p);
+  tick("k_msm_tail", 0, (double)count);
+  launch_msm_tail(opt_, t0_.part.p, nullptr, d_res, (int)count, 16, 8, stream_, nullptr, 0, pl.tail_dup());
+  tock();
 }
 // The basis folds of one log round (inner_product_argument.rs:177-178: 2 families, same_multiscalar_argument.rs:128-130: 3) as ONE call:
 // a SmulTask per family, each with its own gamma shared by its `half` elements, in one launch_smul.  A round's folds are small (3 x 128

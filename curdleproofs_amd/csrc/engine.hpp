@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "check_plan.hpp"
 #include "locate_plan.hpp"
+#include "tracker_check_plan.hpp"
 #include "protocol.h"
 #include "prove_reqs.hpp"
 #include "rng.hpp"
@@ -206,6 +207,13 @@ class Engine {
   // (tracker.hip); status / verdict per item, the loaded batch and the CRS are not touched
   void whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k, const uint8_t* blinders, uint8_t* proofs_out, int* status);
   void whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, int* verdict);
+  // the same two relations weighted by two caller-drawn factors per item and summed per group: ONE bucket MSM of 1 + 5 G points per group
+  // (tracker_check_plan.hpp).  grouped: one verdict per item, the items of a failing group rechecked by the per-item relations; fused: the
+  // sum over all items as a 144-byte partial and the number of undecodable items
+  void whisk_verify_tracker_proofs_grouped(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, const uint8_t* rand, int* verdict,
+                                           size_t* n_rechecked);
+  void whisk_verify_tracker_proofs_fused(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, const uint8_t* rand,
+                                         uint8_t* partial_jac, int* n_invalid);
   // what those calls consume, `count` per call, as multiples of the generator on its fixed-base table (genmul.hip): out[i] = scalars[i] G, and
   // WhiskTracker::from_k_r / get_k_commitment (whisk.rs:45-55, :370) for (k, r) pairs; either output may be null
   void generator_mul(size_t count, const uint8_t* scalars, uint8_t* out_affine, uint8_t* out_compressed);
@@ -403,8 +411,13 @@ class Engine {
     DevBuf<int> flag;
     DevBuf<Aff> gen;      // copies of the generator: the base of the batched tracker prover's k G and blinder G (whisk.cpp)
     size_t gen_n = 0;     // how many of them are filled in
+    // the group tasks of the tracker check (tracker_check_plan.hpp): their bases, scalars and sums live beside the verifier's own buffers
+    // above, which the MSM chain would otherwise take; tw: the weights, then stage 2's dense challenges
+    DevBuf<Aff> tbase;
+    DevBuf<Fr> tscal, tw;
+    DevBuf<Jac> tres;
     template <class Self, class F> static void each(Self& s, F&& f) {   // (Self: Tier0 or const Tier0)
-      each_buf(f, s.a0, s.a1, s.fr, s.mtask, s.stask, s.w, s.pt, s.part, s.res, s.jin, s.conv, s.ttask, s.dig, s.bytes, s.status, s.flag, s.gen);
+      each_buf(f, s.a0, s.a1, s.fr, s.mtask, s.stask, s.w, s.pt, s.part, s.res, s.jin, s.conv, s.ttask, s.dig, s.bytes, s.status, s.flag, s.gen, s.tbase, s.tscal, s.tw, s.tres);
     }
   } t0_;
   // Scratch of the batched shuffle calls (whisk.cpp), kept and trimmed like the tier-0 set
@@ -442,6 +455,13 @@ class Engine {
   // the bucket-list form of msm / msm_many and the body of fold / fold_many (engine.cpp): the single calls are the many-calls of one task
   void msm_lists(Tier0MsmPlan& pl, const uint32_t* lens, const uint8_t* bases, const uint8_t* scalars, uint8_t* out_jac, uint8_t* out_comp);
   void fold_lanes(size_t families, size_t half, uint8_t* PL, const uint8_t* PR, const uint8_t* gammas, long quad_max);
+  // msm_lists without its upload and download (engine.cpp): the chain's own scratch, then launch_msm_endo -> reduce_sets -> launch_msm_tail on
+  // device-resident bases and scalars, inside the caller's scope
+  void msm_chain_reserve(const Tier0MsmPlan& pl);
+  void msm_chain(const Tier0MsmPlan& pl, const uint32_t* lens, const Aff* d_bases, const Fr* d_scalars, Jac* d_res, std::vector<MsmTask>& tasks);
+  // the grouped / fused check of tracker proofs (tracker_check_plan.hpp, whisk.cpp): verdict != null = grouped, else partial_jac + n_invalid
+  void tracker_check(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, const uint8_t* rand, int* verdict, size_t* n_rechecked,
+                     uint8_t* partial_jac, int* n_invalid);
   void enqueue_prove_device();
   void exec_late_round(const LateRound& r, size_t comp_off, const char* what);
   // proofs per launch of the device prover's table build (option table_chunks).  Default: ALL rows in one launch while its scratch (15 doubled

@@ -312,6 +312,15 @@ void launch_tracker_challenge_prove(const uint8_t* d_trackers, const uint8_t* d_
 // d_proofs [count][128]; d_verdict[p] = CPX_OK / CPX_ERR_VERIFY, CPX_ERR_DESERIALIZE where d_bad[p]
 void launch_tracker_relations(const Aff* d_pts, const uint8_t* d_proofs, const Fr* d_chal, const uint8_t* d_bad, const Aff& gen, int count, int* d_verdict,
                               hipStream_t s);
+// the grouped / fused check (tracker_check_plan.hpp): the bases and Montgomery scalars of every group task of the plan of `count` items in
+// groups of `group` — a work-group per task; d_weights = a_i, b_i per item; a flagged item and an identity point become (generator, 0);
+// the generator scalar of a group is its items' a s added up in a fixed order
+void launch_tracker_check_scalars(const Aff* d_pts, const uint8_t* d_proofs, const Fr* d_chal, const uint8_t* d_bad, const Fr* d_weights, const Aff& gen, int count,
+                                  int group, int ntasks, Aff* d_bases, Fr* d_scalars, hipStream_t s);
+// stage 2's compaction: suspect s = item d_list[s] of `count`; its five decoded points, proof bytes and challenge go to slot s of the
+// dense arrays of n_suspects items (the points plane-major again) and d_bad_out[s] = 0 — launch_tracker_relations runs on them unchanged
+void launch_tracker_gather(const uint32_t* d_list, int n_suspects, int count, const Aff* d_pts, const uint8_t* d_proofs, const Fr* d_chal, Aff* d_pts_out,
+                           uint8_t* d_proofs_out, Fr* d_chal_out, uint8_t* d_bad_out, hipStream_t s);
 
 // ---- multiples of the G1 generator on a fixed-base table (genmul.hip; layout and recoding in gen_table.hpp): one launch each ----
 size_t gen_table_entries();

@@ -7,6 +7,10 @@
 //                        16 relations per wave, a two-base joint ladder over the schedule of tracker_ladder.hpp on the quad-cooperative
 //                        XYZZ formulas (g1_28_quad.hpp), built like k_smul_quad.  The claimed point is subtracted at the end and the
 //                        accumulator tested for the identity: no inversion, normalisation or compression anywhere in the verifier.
+//  k_tracker_check_scalars   the grouped / fused check (tracker_check_plan.hpp): both relations weighted by the caller's a, b and summed per
+//                        group of items are ONE MSM — this kernel writes every group task's bases and scalars, a work-group per task; the
+//                        bucket MSM behind it is the tier-0 chain (k_to_table_endo + k_msm_tblw<2, true> + k_reduce_sets + k_msm_tail).
+//  k_tracker_gather      the compaction in front of k_tracker_relations when a group's sum is not the identity: the suspects, dense.
 // Decoding, the prover's scalar multiplications and its compression are the existing kernels (k_decompress / k_decompress_quad, k_smul /
 // k_smul_quad, k_compress).
 #include <hip/hip_runtime.h>
@@ -20,6 +24,7 @@
 #include "recode.hpp"
 #include "glv.hpp"
 #include "tracker_ladder.hpp"
+#include "tracker_check_plan.hpp"
 #include "kernels.h"
 
 namespace cpx {
@@ -200,7 +205,75 @@ __global__ __launch_bounds__(64) void k_tracker_relations(const Aff* __restrict_
   if (in_range && j == 0 && sub == 0) verdict[p] = is_bad ? CPX_ERR_DESERIALIZE : (ok && ok_other) ? CPX_OK : CPX_ERR_VERIFY;
 }
 
-#define TRK_LAUNCH(kern, grid, block, lds, stream, ...)                                             \
+// ---- the grouped / fused check (tracker_check_plan.hpp) ----
+// k_tracker_check_scalars: a work-group of TCS_THREADS lanes per group task of the plan, a lane per item (the group's items in strides of
+// the work-group).  Item p of the group gets its five bases and Montgomery scalars at the plan's slots; a flagged item, and an identity
+// point of a live one, is written as (generator, 0).  Every lane adds up the a s of its items in batch order, the lanes' sums are added
+// in a fixed binary tree through LDS (Fr addition is exact: the tree only fixes the order of execution), lane 0 writes the generator term.
+constexpr int TCS_THREADS = 256;
+__global__ __launch_bounds__(TCS_THREADS) void k_tracker_check_scalars(const Aff* __restrict__ pts, const uint8_t* __restrict__ proofs, const Fr* __restrict__ chal,
+                                                                       const uint8_t* __restrict__ bad, const Fr* __restrict__ weights, Aff gen, int count, int group,
+                                                                       Aff* __restrict__ bases, Fr* __restrict__ scalars) {
+  __shared__ Fr red[TCS_THREADS];
+  const int t = threadIdx.x;
+  const size_t cnt = (size_t)count, g = blockIdx.x, first = g * (size_t)group;
+  const size_t n = first >= cnt ? 0 : (cnt - first < (size_t)group ? cnt - first : (size_t)group);   // LocatePlan::group_count
+  const size_t off = g + TCK_TERMS * first;                                                           // TrackerCheckPlan::task_off
+  Fr acc = Fr::zero();
+  for (size_t i = t; i < n; i += TCS_THREADS) {
+    const size_t p = first + i;
+    const bool live = bad[p] == 0;
+    TrackerCheckScalars sc{};
+    if (live) {
+      Fr s;
+      (void)load_canonical_fr(proofs + 128 * p + 96, s);
+      sc = tracker_check_scalars(weights[2 * p], weights[2 * p + 1], fe_to_mont(s), fe_to_mont(chal[p]));
+      acc = fe_add(acc, sc.gen);
+    }
+    for (int j = 0; j < TCK_TERMS; j++) {
+      const size_t slot = off + 1 + TCK_TERMS * i + (size_t)j;
+      Aff P = gen;
+      bool use = false;
+      if (live) {
+        const Aff Q = pts[(size_t)tck_plane(j) * cnt + p];
+        if (!Q.is_identity()) {
+          P = Q;
+          use = true;
+        }
+      }
+      bases[slot] = P;
+      scalars[slot] = use ? sc.term[j] : Fr::zero();
+    }
+  }
+  red[t] = acc;
+  __syncthreads();
+  for (int w = TCS_THREADS / 2; w > 0; w >>= 1) {
+    if (t < w) red[t] = fe_add(red[t], red[t + w]);
+    __syncthreads();
+  }
+  if (t == 0) {
+    bases[off] = gen;
+    scalars[off] = red[0];
+  }
+}
+
+// k_tracker_gather: a lane per suspect
+__global__ __launch_bounds__(64) void k_tracker_gather(const uint32_t* __restrict__ list, int n_suspects, int count, const Aff* __restrict__ pts,
+                                                       const uint8_t* __restrict__ proofs, const Fr* __restrict__ chal, Aff* __restrict__ pts_out,
+                                                       uint8_t* __restrict__ proofs_out, Fr* __restrict__ chal_out, uint8_t* __restrict__ bad_out) {
+  const size_t s = (size_t)blockIdx.x * 64 + threadIdx.x, S = (size_t)n_suspects, cnt = (size_t)count;
+  if (s >= S) return;
+  const size_t p = list[s];
+  if (p >= cnt) return;   // (never: the list holds items of the batch)
+  for (int pl = 0; pl < TCK_TERMS; pl++) pts_out[(size_t)pl * S + s] = pts[(size_t)pl * cnt + p];
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(proofs + 128 * p);   // (4-byte aligned: the proofs start at a multiple of 16)
+  uint32_t* dst = reinterpret_cast<uint32_t*>(proofs_out + 128 * s);
+  for (int w = 0; w < 32; w++) dst[w] = src[w];
+  chal_out[s] = chal[p];
+  bad_out[s] = 0;
+}
+
+#define TRK_LAUNCH(kern, grid, block, lds, stream, ...)                                            \
   do {                                                                                                \
     hipEvent_t _a = nullptr, _b = nullptr;                                                            \
     take_launch_events(&_a, &_b);                                                                     \
@@ -224,6 +297,17 @@ void launch_tracker_relations(const Aff* d_pts, const uint8_t* d_proofs, const F
   if (count <= 0) return;
   const unsigned waves = (unsigned)((2L * count + 15) / 16);
   TRK_LAUNCH(k_tracker_relations, dim3(waves), dim3(64), TR_LDS, s, d_pts, d_proofs, d_chal, d_bad, gen, count, d_verdict);
+}
+void launch_tracker_check_scalars(const Aff* d_pts, const uint8_t* d_proofs, const Fr* d_chal, const uint8_t* d_bad, const Fr* d_weights, const Aff& gen, int count,
+                                  int group, int ntasks, Aff* d_bases, Fr* d_scalars, hipStream_t s) {
+  if (count <= 0 || ntasks <= 0) return;
+  TRK_LAUNCH(k_tracker_check_scalars, dim3(ntasks), dim3(TCS_THREADS), 0, s, d_pts, d_proofs, d_chal, d_bad, d_weights, gen, count, group, d_bases, d_scalars);
+}
+void launch_tracker_gather(const uint32_t* d_list, int n_suspects, int count, const Aff* d_pts, const uint8_t* d_proofs, const Fr* d_chal, Aff* d_pts_out,
+                           uint8_t* d_proofs_out, Fr* d_chal_out, uint8_t* d_bad_out, hipStream_t s) {
+  if (n_suspects <= 0) return;
+  TRK_LAUNCH(k_tracker_gather, dim3((n_suspects + 63) / 64), dim3(64), 0, s, d_list, n_suspects, count, d_pts, d_proofs, d_chal, d_pts_out, d_proofs_out, d_chal_out,
+             d_bad_out);
 }
 
 }  // namespace cpx

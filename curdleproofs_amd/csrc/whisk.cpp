@@ -306,6 +306,160 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
   call.finish();
 }
 
+// ---------------------------------------------------------------- tracker proofs, grouped and fused: one MSM (tracker_check_plan.hpp)
+// The verifier's two relations weighted by the caller's a_i, b_i and summed per group of items: after the decoding and the transcripts of
+// the per-item call, k_tracker_check_scalars writes every group's task (the generator, then five points per item) and the device half of
+// the tier-0 bucket MSM (msm_chain) leaves one sum per group.  Grouped: the sums come down with the flags — ONE synchronisation when every
+// group sums to the identity; otherwise k_tracker_gather compacts the unflagged items of the failing groups and the per-item relations
+// (launch_tracker_relations, unchanged) run on them: a second synchronisation.  Fused: k_sum_jac adds the sums and one point comes down.
+// The number of launches never depends on the count.  Scratch is the tier-0 set.
+void Engine::whisk_verify_tracker_proofs_grouped(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, const uint8_t* rand,
+                                                 int* verdict, size_t* n_rechecked) {
+  if (!count) {
+    if (n_rechecked) *n_rechecked = 0;
+    return;
+  }
+  tracker_check(count, trackers, k_commitments, proofs, rand, verdict, n_rechecked, nullptr, nullptr);
+}
+void Engine::whisk_verify_tracker_proofs_fused(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, const uint8_t* rand,
+                                               uint8_t* partial_jac, int* n_invalid) {
+  if (!count) {
+    const Jac id = Jac::identity();
+    memcpy(partial_jac, &id, sizeof id);
+    *n_invalid = 0;
+    return;
+  }
+  tracker_check(count, trackers, k_commitments, proofs, rand, nullptr, nullptr, partial_jac, n_invalid);
+}
+void Engine::tracker_check(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, const uint8_t* rand, int* verdict,
+                           size_t* n_rechecked, uint8_t* partial_jac, int* n_invalid) {
+  if (!tracker_check_fits(count)) throw ArgError("tracker proofs, grouped / fused: at most 2^21 per call");
+  for (size_t i = 0; i < 2 * count; i++)
+    if (!host::is_valid_factor(rand + 32 * i)) throw ArgError("tracker check weights must be non-zero reduced field elements");
+  const bool grouped = verdict != nullptr;
+  if (grouped) {
+    for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
+    if (n_rechecked) *n_rechecked = 0;
+  }
+  const Aff G = generator();   // (before the scope: the first call decodes the generator, a tier-0 call of its own)
+  std::vector<uint8_t> keep[2];
+  auto canon = [&](const uint8_t* in, size_t rec, const std::vector<size_t>& offs, std::vector<uint8_t>* store) {
+    const uint8_t* p = canonical_infinities(in, count * rec, count, rec, offs);
+    if (p == in || !store) return p;
+    store->assign(p, p + count * rec);   // (canon_bytes_ is reused by the next array)
+    return (const uint8_t*)store->data();
+  };
+  trackers = canon(trackers, 96, {0, 48}, &keep[0]);
+  k_commitments = canon(k_commitments, 48, {0}, &keep[1]);
+  proofs = canon(proofs, 128, {0, 48}, nullptr);
+  // the fused sum keeps the grouping of cpx_batch_verify_fused; the groups only shape the MSM there
+  const TrackerCheckPlan tp = tracker_check_plan(count, grouped ? opt_.locate_groups_max : kLocateGroupsMax);
+  const LocatePlan& lp = tp.lp;
+  const size_t NT = tp.tasks();
+  Tier0MsmPlan pl;
+  pl.count = NT;
+  pl.points = tp.points();
+  pl.max_n = (uint32_t)tp.max_n();
+  pl.conv_off.resize(NT);
+  std::vector<uint32_t> lens(NT), off, list, flags;
+  for (size_t g = 0; g < NT; g++) {
+    pl.conv_off[g] = (uint32_t)tp.task_off(g);
+    lens[g] = (uint32_t)tp.task_n(g);
+  }
+  std::vector<MsmTask> tasks;
+  std::vector<uint8_t> bad, group_ok, recheck_ok;
+  std::vector<Jac> sums;
+  std::vector<int> ver2;
+  Jac total;
+  int total_is_identity = 0;
+  CallScope call(this);
+  pl.slices = msm_tblw_slices(opt_, (int)NT, 2, (int)pl.max_n);
+  const int n = (int)count;
+  DevBuf<uint8_t>&din = t0_.bytes, &dst = t0_.status;   // trackers | k_commitments | proofs; 5 count decoding verdicts | count proof flags
+  DevBuf<uint32_t>& doff = t0_.dig;                     // the decoder's offsets, then the chain's digits, then stage 2's list
+  DevBuf<Aff>&dpts = t0_.a0, &dbase = t0_.tbase;
+  DevBuf<Fr>&dchal = t0_.fr, &dscal = t0_.tscal, &dw = t0_.tw;
+  DevBuf<Jac>&dsum = t0_.tres, &dtot = t0_.res;
+  DevBuf<int>& dver = t0_.flag;
+  msm_chain_reserve(pl);   // (first: ensure() may free a buffer, and the digits outgrow the 5 count offsets)
+  din.ensure(tp.input_bytes());
+  dst.ensure(6 * count);
+  doff.ensure(5 * count);
+  dpts.ensure(5 * count);
+  dchal.ensure(count);
+  dver.ensure(count);
+  dbase.ensure(tp.points());
+  dscal.ensure(tp.points());
+  dw.ensure(tp.weight_scalars());
+  dsum.ensure(tp.result_points());
+  dtot.ensure(1);
+  uint8_t *d_trk = din.p, *d_kc = din.p + 96 * count, *d_prf = din.p + 144 * count, *d_bad = dst.p + 5 * count;
+  const size_t plane_off[5] = {144 * count, 144 * count + 48, 48, 0, 96 * count}, plane_rec[5] = {128, 128, 96, 96, 48};
+  tracker_point_offsets(count, plane_off, plane_rec, 5, off);
+  CPX_HIP(hipMemcpyAsync(d_trk, trackers, 96 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(d_kc, k_commitments, 48 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(d_prf, proofs, 128 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(dw.p, rand, 2 * count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  tick("k_decompress", 0, 5.0 * count);
+  launch_decompress(opt_, din.p, 5 * n, dpts.p, nullptr, dst.p, 1, stream_, doff.p);
+  tock();
+  tick("k_tracker_challenge", 288.0 * count, (double)count);
+  launch_tracker_challenge_verify(din.p, dst.p, n, dchal.p, d_bad, stream_);
+  tock();
+  tick("k_tracker_check_scalars", (double)(tp.points() * (sizeof(Aff) + sizeof(Fr))), (double)count);
+  launch_tracker_check_scalars(dpts.p, d_prf, dchal.p, d_bad, dw.p, G, n, (int)lp.G, (int)NT, dbase.p, dscal.p, stream_);
+  tock();
+  msm_chain(pl, lens.data(), dbase.p, dscal.p, dsum.p, tasks);
+  bad.resize(count);
+  CPX_HIP(hipMemcpyAsync(bad.data(), d_bad, count, hipMemcpyDeviceToHost, stream_));
+  if (!grouped) {
+    launch_sum_jac(dsum.p, (int)NT, dtot.p, dver.p, stream_);
+    CPX_HIP(hipMemcpyAsync(&total, dtot.p, sizeof(Jac), hipMemcpyDeviceToHost, stream_));
+    CPX_HIP(hipMemcpyAsync(&total_is_identity, dver.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
+    call.finish();
+    int inv = 0;
+    for (size_t i = 0; i < count; i++) inv += bad[i] ? 1 : 0;
+    if (total_is_identity) total = Jac::identity();   // (one encoding of the identity whatever the chain left in X and Y)
+    memcpy(partial_jac, &total, sizeof(Jac));
+    *n_invalid = inv;
+    return;
+  }
+  sums.resize(NT);
+  CPX_HIP(hipMemcpyAsync(sums.data(), dsum.p, NT * sizeof(Jac), hipMemcpyDeviceToHost, stream_));
+  call.finish();   // the one synchronisation of a batch whose groups all pass
+  group_ok.resize(NT);
+  flags.resize(count);
+  for (size_t g = 0; g < NT; g++) group_ok[g] = sums[g].is_identity() ? 1 : 0;
+  for (size_t i = 0; i < count; i++) flags[i] = bad[i] ? kLocateFlagDecode : 0u;
+  locate_stage2(lp, group_ok.data(), flags.data(), list);   // empty with one item per group: stage 1 was the per-item check
+  const size_t S = list.size();
+  if (S) {
+    // the buffers of stage 1 that are dead by now take the dense arrays (the stream is idle: ensure() may free)
+    DevBuf<Aff>& dpts2 = t0_.a1;
+    dpts2.ensure(TrackerCheckPlan::s2_points(S));
+    dst.ensure(TrackerCheckPlan::s2_proof_bytes(S) + S);
+    uint32_t* d_list = doff.p;                                    // (9 points() words: S fits)
+    uint8_t *d_prf2 = dst.p, *d_bad2 = dst.p + TrackerCheckPlan::s2_proof_bytes(S);
+    Fr* d_chal2 = dw.p;                                           // (2 count scalars: S fit)
+    CPX_HIP(hipMemcpyAsync(d_list, list.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemsetAsync(dver.p, 0xff, S * sizeof(int), stream_));   // (-1: not CPX_OK)
+    tick("k_tracker_gather", (double)(S * (5 * sizeof(Aff) + 128 + sizeof(Fr))), (double)S);
+    launch_tracker_gather(d_list, (int)S, n, dpts.p, d_prf, dchal.p, dpts2.p, d_prf2, d_chal2, d_bad2, stream_);
+    tock();
+    tick("k_tracker_relations", 0, 2.0 * S);
+    launch_tracker_relations(dpts2.p, d_prf2, d_chal2, d_bad2, G, (int)S, dver.p, stream_);
+    tock();
+    ver2.resize(S);
+    CPX_HIP(hipMemcpyAsync(ver2.data(), dver.p, S * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    call.finish();
+    recheck_ok.resize(S);
+    for (size_t s = 0; s < S; s++) recheck_ok[s] = ver2[s] == CPX_OK ? 1 : 0;
+  }
+  locate_verdicts(lp, group_ok.data(), flags.data(), list, recheck_ok.data(), verdict);
+  if (n_rechecked) *n_rechecked = S;
+}
+
 // ---------------------------------------------------------------- which trackers a set of keys opens (find.hip, find_plan.hpp)
 // k_j * r_G_i == k_r_G_i (whisk.rs:36-55, the multiplication of whisk.rs:323) for every (tracker, key) pair: the trackers and the keys go up once,
 // every point is decoded once, and either ONE k_smul + ONE k_find_compare run (few keys), or per chunk of trackers k_table_build + k_fix_build +

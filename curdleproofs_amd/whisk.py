@@ -308,6 +308,67 @@ def are_valid_whisk_tracker_proofs(ctx, trackers, k_commitments, proofs):
     return res
 
 
+# ---- the same as ONE multi-scalar multiplication (cpx_whisk_verify_tracker_proofs_grouped / _fused) ----
+def _tracker_check_inputs(trackers, k_commitments, proofs, rands):
+    """Length checks and marshalling shared by the grouped and the fused call: (count, short, trackers, kc, proofs, rands) as bytes.  An
+    item of wrong length is reported per item; the library is handed a dummy that does not decode (zero bytes lack the compression
+    flag), so it contributes nothing to any sum and counts as invalid."""
+    count = len(trackers)
+    if len(k_commitments) != count or len(proofs) != count or (rands is not None and len(rands) != count):
+        raise ValueError("one k_commitment, one proof and one pair of weights per tracker")
+    rands = [_rand_fr(2) for _ in range(count)] if rands is None else rands
+    if any(len(r) != 2 * FR for r in rands):
+        raise ValueError("two 32-byte weights per item")
+    short = [len(c) != G1POINT_SIZE or len(p) != TRACKER_PROOF_SIZE for c, p in zip(k_commitments, proofs)]
+    kc = b"".join(bytes(G1POINT_SIZE) if s else c for s, c in zip(short, k_commitments))
+    pf = b"".join(bytes(TRACKER_PROOF_SIZE) if s else p for s, p in zip(short, proofs))
+    return count, short, _cat(trackers), kc, pf, b"".join(rands)
+
+
+def are_valid_whisk_tracker_proofs_grouped(ctx, trackers, k_commitments, proofs, rands=None):
+    """are_valid_whisk_tracker_proofs through the grouped check (cpx_whisk_verify_tracker_proofs_grouped): every group of items is one MSM of
+    five points per item, and only the items of a group whose sum is not the identity get the per-item relations.  rands: one 64-byte
+    pair of weights (a_i || b_i, wire scalars, non-zero) per item, from the OS CSPRNG when omitted.  Returns (results as
+    are_valid_whisk_tracker_proofs, n_rechecked); context option "locate_groups_max" sets the grouping."""
+    count, short, tr, kc, pf, rnd = _tracker_check_inputs(trackers, k_commitments, proofs, rands)
+    if count == 0:
+        return [], 0
+    verdict = (ctypes.c_int * count)(*([CPX_ERR_INTERNAL] * count))   # an entry the library does not write is never read as accepted
+    rechecked = ctypes.c_size_t(0)
+    ctx._check(ctx._L.cpx_whisk_verify_tracker_proofs_grouped(ctx._h, count, _in(tr), _in(kc), _in(pf), _in(rnd), verdict, ctypes.byref(rechecked)))
+    res = []
+    for i, v in enumerate(verdict):
+        if short[i]:
+            res.append(SerializationError("wrong length"))
+        elif v == CPX_OK:
+            res.append(True)
+        elif v == CPX_ERR_VERIFY:
+            res.append(False)
+        elif v == CPX_ERR_DESERIALIZE:
+            res.append(SerializationError("tracker proof %d" % i))
+        else:
+            raise CpxError(v, "tracker proof %d" % i)
+    return res, rechecked.value
+
+
+def whisk_tracker_proofs_partial(ctx, trackers, k_commitments, proofs, rands=None):
+    """cpx_whisk_verify_tracker_proofs_fused: (partial_jac, n_invalid) — the 144-byte Jacobian sum of the weighted relations of all items that
+    decode, and the number of items that do not (wrong lengths included).  The batch is accepted iff n_invalid == 0 and the partials of
+    all calls, contexts and GPUs — the shuffle proofs' among them — add up to the identity (Context.sum_jac)."""
+    count, short, tr, kc, pf, rnd = _tracker_check_inputs(trackers, k_commitments, proofs, rands)
+    from . import JAC
+    partial = _out(JAC)
+    n_invalid = ctypes.c_int(0)
+    ctx._check(ctx._L.cpx_whisk_verify_tracker_proofs_fused(ctx._h, count, _in(tr), _in(kc), _in(pf), _in(rnd), partial, ctypes.byref(n_invalid)))
+    return bytes(partial), n_invalid.value
+
+
+def are_all_valid_whisk_tracker_proofs(ctx, trackers, k_commitments, proofs, rands=None):
+    """All-or-nothing: True iff every item decodes and the weighted sum of all relations is the identity"""
+    partial, n_invalid = whisk_tracker_proofs_partial(ctx, trackers, k_commitments, proofs, rands)
+    return n_invalid == 0 and bool(ctx.sum_jac(partial)[1])
+
+
 # ---- many trackers and k commitments per call (cpx_whisk_trackers_from_k_r / cpx_g1_generator_mul) ----
 def trackers_from_k_r(ctx, ks, rs):
     """whisk.rs:45-55 WhiskTracker::from_k_r and whisk.rs:370 get_k_commitment for every (k, r) pair in ONE library call, on the fixed-base

@@ -265,6 +265,36 @@ int cpx_whisk_generate_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t*
  *   verdict[i]: CPX_OK = Ok(true), CPX_ERR_VERIFY = Ok(false), CPX_ERR_DESERIALIZE = Err(SerializationError). */
 int cpx_whisk_verify_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* trackers /* count*96 */, const uint8_t* k_commitments /* count*48 */,
                                     const uint8_t* proofs /* count*128 */, int* verdict /* count */);
+/* whisk.rs:183-226 for `count` triples as ONE multi-scalar multiplication: the fused and the grouped form of the call above, as
+ * cpx_batch_verify_fused / cpx_batch_verify_grouped are of cpx_batch_verify.  rand holds two weights per item, a_i then b_i, Montgomery limbs
+ * as every scalar of this header; they must be independent, uniform, non-zero and reduced — a zero or a value >= r anywhere is CPX_ERR_ARG for
+ * the call before anything is written (the rule of cpx_batch_verify).  With c_i the challenge of whisk.rs:205-220 and s_i the proof's response,
+ * item i stands for
+ *     a_i (s_i G + c_i k_G_i - A_i) + b_i (s_i r_G_i + c_i k_r_G_i - B_i)
+ * and a group of items is one MSM: the generator with sum a_i s_i, and per item k_G (a c), A (-a), r_G (b s), k_r_G (b c), B (-b) — 5 points
+ * per item on the radix-256 endomorphism bucket path of cpx_g1_msm_many instead of two 129-step ladders (layout and scalar rules in
+ * curdleproofs_amd/csrc/tracker_check_plan.hpp).  SOUNDNESS: the sum is linear in the independent factors, so a group that contains a false
+ * relation sums to the identity with probability <= 1 / r over the caller's draws; weights an adversary can predict or influence void that.
+ * An item is FLAGGED when a point does not decode or lies outside the subgroup, or s >= r (option "strict_infinity" governs infinity encodings
+ * as in the per-item call).  A flagged item contributes nothing to any sum.
+ * Conventions of the batched tracker calls: count = 0 is a no-op returning CPX_OK; NULL with work to do is CPX_ERR_ARG and nothing is written;
+ * no CRS is needed and the loaded batch is untouched; the number of kernel launches does not depend on count.  At most 2^21 items per call
+ * (5 count + 256 points within the 2^24 of cpx_g1_msm_many); more is CPX_ERR_ARG before anything is read.  Scratch is the tier-0 set and is
+ * trimmed on every exit path: "tier0_scratch_bytes" stays within 33 buffers x 64 MiB afterwards (21 of the tier-0 set, 12 of the shuffle set).  Measurements: profiles/tracker_proofs_grouped.md. */
+/* Fused: partial_jac = the sum over all unflagged items (Jacobian, standard form; Z = 0 for the identity), *n_invalid = the flagged items.  The
+ * batch is accepted iff n_invalid == 0 and the partials of all calls / contexts / GPUs — these and those of cpx_batch_verify_fused — add up to
+ * the identity (cpx_g1_sum_jac).  count = 0: the identity and n_invalid = 0 (both outputs are always required).  ONE stream synchronisation. */
+int cpx_whisk_verify_tracker_proofs_fused(cpx_ctx* ctx, size_t count, const uint8_t* trackers /* count*96 */, const uint8_t* k_commitments /* count*48 */,
+                                          const uint8_t* proofs /* count*128 */, const uint8_t* rand /* count*2*32 */, uint8_t partial_jac[144], int* n_invalid);
+/* Grouped: the items are cut into groups exactly as cpx_batch_verify_grouped cuts proofs (option "locate_groups_max", decode flag only).  Stage 1
+ * tests every group's sum for the identity; stage 2 runs only when a group fails: every unflagged item of a failing group gets the per-item
+ * relations of cpx_whisk_verify_tracker_proofs.  verdict[i]: CPX_OK, CPX_ERR_VERIFY, or CPX_ERR_DESERIALIZE for a flagged item; pre-filled with
+ * CPX_ERR_INTERNAL; the call returns CPX_OK whatever the items say.  *n_rechecked (may be NULL) = the items stage 2 looked at, deterministic given
+ * the inputs and the option.  With one item per group (count <= locate_groups_max) stage 1 is the per-item check and there is no stage 2.  ONE
+ * stream synchronisation when every group passes, two when stage 2 runs. */
+int cpx_whisk_verify_tracker_proofs_grouped(cpx_ctx* ctx, size_t count, const uint8_t* trackers /* count*96 */, const uint8_t* k_commitments /* count*48 */,
+                                            const uint8_t* proofs /* count*128 */, const uint8_t* rand /* count*2*32 */, int* verdict /* count */,
+                                            size_t* n_rechecked /* may be NULL */);
 
 /* What the batched tracker calls consume, made `count` per call.  Every point below is a multiple of the BLS12-381 G1 generator G — r G, k G and
  * k (r G) = (k r mod r_order) G — and comes from a fixed-base table of G (curdleproofs_amd/csrc/gen_table.hpp: radix 256 over the endomorphism
@@ -431,7 +461,7 @@ int cpx_set_profiling(cpx_ctx* ctx, int on); /* time every kernel group with HIP
 int cpx_reset_stats(cpx_ctx* ctx);
 /* name = kernel name as rocprofv3 reports it, template arguments included: "k_msm_fix<16, 16>", "k_msm_tblw<32, false>",
  * "k_msm_tblw<2, true>", "k_msm_accw", "k_reduce_sets", "k_finalize_ranges", "k_table_build", "k_msm_tail", "k_smul",
- * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
+ * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
  * "k_smul" times the one-lane and the quad form alike; "k_smul_quad" counts (launches only) those of them that ran as k_smul_quad;
  * units = MSM points / scalar-mul elements / points; out pointers may be NULL */
 int cpx_get_stat(const cpx_ctx* ctx, const char* name, uint64_t* launches, double* total_ms, double* algorithmic_bytes, double* units);

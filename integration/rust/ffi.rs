@@ -85,6 +85,12 @@ extern "C" {
                                              status: *mut c_int) -> c_int;
     pub fn cpx_whisk_verify_tracker_proofs(ctx: *mut cpx_ctx, count: usize, trackers: *const u8, k_commitments: *const u8, proofs: *const u8,
                                            verdict: *mut c_int) -> c_int;
+    // the verifier as ONE multi-scalar multiplication: rand = two non-zero reduced weights per item (a_i, b_i; Montgomery limbs); fused = the 144-byte
+    // partial sum and the number of undecodable items, grouped = one verdict per item and the number of items the second stage rechecked
+    pub fn cpx_whisk_verify_tracker_proofs_fused(ctx: *mut cpx_ctx, count: usize, trackers: *const u8, k_commitments: *const u8, proofs: *const u8,
+                                                 rand: *const u8, partial_jac: *mut u8, n_invalid: *mut c_int) -> c_int;
+    pub fn cpx_whisk_verify_tracker_proofs_grouped(ctx: *mut cpx_ctx, count: usize, trackers: *const u8, k_commitments: *const u8, proofs: *const u8,
+                                                   rand: *const u8, verdict: *mut c_int, n_rechecked: *mut usize) -> c_int;
     // what those calls consume, `count` per call, as multiples of the generator on its fixed-base table (whisk.rs:45-55, :370); either output may be null
     pub fn cpx_g1_generator_mul(ctx: *mut cpx_ctx, count: usize, scalars: *const u8, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
     pub fn cpx_whisk_trackers_from_k_r(ctx: *mut cpx_ctx, count: usize, k: *const u8, r: *const u8, trackers_out: *mut u8, k_commitments_out: *mut u8) -> c_int;

@@ -114,6 +114,59 @@ pub fn are_valid_whisk_tracker_proofs(
         .collect()
 }
 
+/// The same through the grouped check: two weights per item drawn from `rng` (a_i, b_i, in item order), every group of items one MSM,
+/// the per-item relations only for the items of a group whose sum is not the identity.  Returns the results and the number rechecked.
+pub fn are_valid_whisk_tracker_proofs_grouped<T: RngCore>(
+    rng: &mut T,
+    trackers: &[WhiskTracker],
+    k_commitments: &[[u8; 48]],
+    tracker_proofs: &[TrackerProofBytes],
+) -> (Vec<Result<bool, SerializationError>>, usize) {
+    assert!(trackers.len() == k_commitments.len() && trackers.len() == tracker_proofs.len());
+    let count = trackers.len();
+    let kc: Vec<u8> = k_commitments.iter().flat_map(|c| c.iter().copied()).collect();
+    let pf: Vec<u8> = tracker_proofs.iter().flat_map(|p| p.iter().copied()).collect();
+    let weights: Vec<Fr> = (0..2 * count).map(|_| loop { let w = Fr::rand(rng); if w != Fr::from(0u64) { break w; } }).collect();
+    let mut verdict = vec![CPX_ERR_INTERNAL; count];
+    let mut rechecked = 0usize;
+    let rc = unsafe {
+        cpx_whisk_verify_tracker_proofs_grouped(ctx(), count, trackers_to_wire(trackers).as_ptr(), kc.as_ptr(), pf.as_ptr(), scalars_ptr(&weights), verdict.as_mut_ptr(), &mut rechecked)
+    };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    let res = verdict
+        .into_iter()
+        .map(|v| match v {
+            CPX_OK => Ok(true),
+            CPX_ERR_VERIFY => Ok(false),
+            CPX_ERR_DESERIALIZE => Err(SerializationError::InvalidData),
+            v => panic!("libcpx: {}", v),
+        })
+        .collect();
+    (res, rechecked)
+}
+
+/// The fused form: this call's 144-byte partial sum and the number of undecodable items.  A batch is accepted iff no call reports an invalid
+/// item and all partials — those of the shuffle proofs and of other GPUs included — add up to the identity (cpx_g1_sum_jac).
+pub fn whisk_tracker_proofs_partial<T: RngCore>(
+    rng: &mut T,
+    trackers: &[WhiskTracker],
+    k_commitments: &[[u8; 48]],
+    tracker_proofs: &[TrackerProofBytes],
+) -> ([u8; 144], usize) {
+    assert!(trackers.len() == k_commitments.len() && trackers.len() == tracker_proofs.len());
+    let count = trackers.len();
+    let kc: Vec<u8> = k_commitments.iter().flat_map(|c| c.iter().copied()).collect();
+    let pf: Vec<u8> = tracker_proofs.iter().flat_map(|p| p.iter().copied()).collect();
+    let weights: Vec<Fr> = (0..2 * count).map(|_| loop { let w = Fr::rand(rng); if w != Fr::from(0u64) { break w; } }).collect();
+    let mut partial = [0u8; 144];
+    let mut n_invalid: std::os::raw::c_int = 0;
+    let rc = unsafe {
+        cpx_whisk_verify_tracker_proofs_fused(ctx(), count, trackers_to_wire(trackers).as_ptr(), kc.as_ptr(), pf.as_ptr(), scalars_ptr(&weights), partial.as_mut_ptr(), &mut n_invalid)
+    };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    (partial, n_invalid as usize)
+}
+
 /// whisk.rs:228-263 for many (tracker, k) pairs in one library call; the blinders are drawn in item order (:238)
 pub fn generate_whisk_tracker_proofs<T: RngCore>(rng: &mut T, trackers: &[WhiskTracker], ks: &[Fr]) -> Vec<Result<TrackerProofBytes, SerializationError>> {
     assert!(trackers.len() == ks.len());
