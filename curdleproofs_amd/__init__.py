@@ -64,6 +64,7 @@ EXPORTS = [
     "cpx_whisk_generate_shuffle_proof", "cpx_whisk_is_valid_shuffle_proof", "cpx_whisk_generate_tracker_proof", "cpx_whisk_is_valid_tracker_proof",
     "cpx_whisk_generate_tracker_proofs", "cpx_whisk_verify_tracker_proofs", "cpx_whisk_verify_tracker_proofs_fused", "cpx_whisk_verify_tracker_proofs_grouped", "cpx_g1_generator_mul", "cpx_whisk_trackers_from_k_r", "cpx_whisk_find_trackers",
     "cpx_batch_shuffle", "cpx_whisk_generate_shuffle_proofs", "cpx_whisk_verify_shuffle_proofs", "cpx_whisk_verify_shuffle_proofs_grouped",
+    "cpx_whisk_candidates_load", "cpx_whisk_candidates_size", "cpx_whisk_candidates_read", "cpx_whisk_verify_shuffle_run", "cpx_whisk_verify_shuffle_run_grouped",
     "cpx_rng_from_u64", "cpx_rng_split", "cpx_rng_fr", "cpx_rng_shuffle_draws", "cpx_whisk_generate_shuffle_proofs_rng", "cpx_batch_prove_rng",
     "cpx_rng_g1", "cpx_rng_instance_draws", "cpx_crs_generate", "cpx_g1_clear_cofactor",
     "cpx_set_profiling", "cpx_reset_stats", "cpx_get_stat", "cpx_set_host_threads", "cpx_bench_fpmul",
@@ -146,6 +147,12 @@ def load_library(path=None):
     L.cpx_whisk_generate_shuffle_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     L.cpx_whisk_verify_shuffle_proofs.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.cpx_whisk_verify_shuffle_proofs_grouped.argtypes = [vp, sz, vp, vp, vp, vp, vp, ctypes.POINTER(sz)]
+    L.cpx_whisk_candidates_load.argtypes = [vp, sz, vp, vp]
+    L.cpx_whisk_candidates_size.argtypes = [vp]
+    L.cpx_whisk_candidates_size.restype = sz
+    L.cpx_whisk_candidates_read.argtypes = [vp, sz, sz, vp]
+    L.cpx_whisk_verify_shuffle_run.argtypes = [vp, sz, vp, vp, vp, vp, vp, ctypes.POINTER(sz)]
+    L.cpx_whisk_verify_shuffle_run_grouped.argtypes = [vp, sz, vp, vp, vp, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     L.cpx_bench_fpmul.argtypes = [vp, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
     L.cpx_rng_from_u64.argtypes = [ctypes.c_uint64, vp]
     L.cpx_rng_split.argtypes = [vp, sz, vp]
@@ -551,7 +558,7 @@ class Context:
         return dict(launches=n.value, ms=ms.value, alg_bytes=by.value, units=un.value)
 
     KERNELS = ("k_msm_tblw<32, false>", "k_reduce_sets", "k_msm_tblw<16, false>", "k_msm_tblw<8, false>", "k_msm_tblw<4, false>", "k_msm_tblw<2, false>", "k_msm_fix<19, 7>", "k_msm_fix<16, 4>", "k_msm_fix<16, 2>", "k_msm_fix<16, 16>", "k_msm_fix<16, 8>", "k_msm_fix<8, 16>", "k_msm_fix<8, 8>",
-               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
+               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_run_gather", "k_run_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
 
     def stats(self):
         return {k: self.stat(k) for k in self.KERNELS}

@@ -453,6 +453,39 @@ int cpx_whisk_verify_shuffle_proofs_grouped(cpx_ctx* ctx, size_t count, const ui
   });
 }
 
+// ---- the resident candidate tracker list and a run of shuffles against it (run_plan.hpp, run.hip) ----
+int cpx_whisk_candidates_load(cpx_ctx* ctx, size_t n, const uint8_t* trackers, uint8_t* status) {
+  if (n && !trackers) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_candidates_load(n, trackers, status);
+    return (int)CPX_OK;
+  });
+}
+size_t cpx_whisk_candidates_size(cpx_ctx* ctx) { return ctx && ctx->eng ? ctx->eng->whisk_candidates_size() : 0; }
+int cpx_whisk_candidates_read(cpx_ctx* ctx, size_t first, size_t count, uint8_t* trackers_out) {
+  if (count && !trackers_out) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_candidates_read(first, count, trackers_out);
+    return (int)CPX_OK;
+  });
+}
+int cpx_whisk_verify_shuffle_run(cpx_ctx* ctx, size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand,
+                                 int* verdict, size_t* n_applied) {
+  if (count && (!indices || !post_trackers || !proofs || !rand || !verdict)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_verify_shuffle_run(count, indices, post_trackers, proofs, rand, verdict, n_applied);
+    return (int)CPX_OK;
+  });
+}
+int cpx_whisk_verify_shuffle_run_grouped(cpx_ctx* ctx, size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand,
+                                         int* verdict, size_t* n_applied, size_t* n_rechecked) {
+  if (count && (!indices || !post_trackers || !proofs || !rand || !verdict)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->whisk_verify_shuffle_run_grouped(count, indices, post_trackers, proofs, rand, verdict, n_applied, n_rechecked);
+    return (int)CPX_OK;
+  });
+}
+
 // ---- the reference's `rng: &mut T` as ChaCha12 states (rng.hpp) ----
 namespace {
 RngState rng_state_from_bytes(const uint8_t b[40]) {

@@ -248,6 +248,18 @@ class Engine {
   // ... with 12 factors per item and the grouped check behind it
   void whisk_verify_shuffle_proofs_grouped(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand, int* verdict,
                                            size_t* n_rechecked);
+  // ---- the resident candidate tracker list and a run of shuffles against it (run.hip, run_plan.hpp; whisk.cpp) ----
+  // decodes the 2n points once (subgroup-checked) and keeps points, status and bytes until the next load or the end of the engine;
+  // status (nullable): per candidate the decoder's code of r_G if non-zero, else of k_r_G
+  void whisk_candidates_load(size_t n, const uint8_t* trackers, uint8_t* status);
+  size_t whisk_candidates_size() const { return cand_.n; }
+  void whisk_candidates_read(size_t first, size_t count, uint8_t* trackers_out) const;
+  // whisk.rs:106-130 for a run of items whose pre trackers are the candidates at indices[b][0..ell) of the list as it stands after items
+  // 0..b-1 were written back; the leading accepted items are written back to the resident list when n_applied is not null (a dry run otherwise)
+  void whisk_verify_shuffle_run(size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand, int* verdict,
+                                size_t* n_applied);
+  void whisk_verify_shuffle_run_grouped(size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand, int* verdict,
+                                        size_t* n_applied, size_t* n_rechecked);
 
   // ---- measurement ----
   void set_profiling(bool on) { profiling_ = on; }
@@ -576,6 +588,17 @@ class Engine {
   // the shared body of the two many-per-call shuffle verifiers: everything up to the dense proofs of the loaded batch, then `verify` on them
   void whisk_verify_shuffle_proofs_with(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, int* verdict,
                                         const std::function<void(const uint8_t* dense, int* verdict)>& verify);
+  // The resident candidate list: outside the scratch sets (no call trims it), replaced by the next load only
+  struct Candidates {
+    size_t n = 0;
+    long strict = 0;                // option strict_infinity at load: a run under another value would read the bytes differently
+    DevBuf<Aff> pts;                // cand_R | cand_S, n points each
+    DevBuf<uint8_t> status;         // the decoder's codes, same layout
+    std::vector<uint8_t> bytes;     // n * 96, exactly as given / as the applied items spelt their post trackers
+  } cand_;
+  // the run body beside whisk_verify_shuffle_proofs_with: the same `verify` functor for the plain and the grouped form
+  void whisk_verify_shuffle_run_with(size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, int* verdict, size_t* n_applied,
+                                     const std::function<void(const uint8_t* dense, int* verdict)>& verify);
   void batch_prove_tables(const uint32_t* permutation, const uint8_t* k, const uint8_t* m_blinders, const uint8_t* rand, uint8_t* proofs_out);
   // option strict_infinity = 0: `bytes` with every non-canonical infinity encoding (at `offsets` of each of the nrec records) rewritten to
   // the canonical one, in canon_bytes_ (valid until the next call); `bytes` itself when there is none or the option is set

@@ -346,6 +346,14 @@ void launch_shuffle_gather(const ShufflePlan& pl, const uint32_t* d_perm, const 
 // d_mjac[i] = the affine point d_pp[i * pp_stride + m_slot] as a Jacobian one
 void launch_shuffle_commit(const Aff* d_pp, size_t pp_stride, uint32_t m_slot, uint32_t count, Jac* d_mjac, hipStream_t s);
 
+// ---- a run of shuffles against the resident candidate list (run.hip; lists and lane layout in run_plan.hpp): one launch each ----
+// d_pts / d_status: the planes R | S | T | U of pp points each (shuffle_plan.hpp), T and U decoded; d_cand / d_cand_status: cand_R | cand_S of
+// n points each.  R, S and their status bytes are filled through the source list d_src [pp] (RunPlan::resolve)
+void launch_run_gather(uint32_t pp, uint32_t n, const uint32_t* d_src, const Aff* d_cand, const uint8_t* d_cand_status, Aff* d_pts, uint8_t* d_status, hipStream_t s);
+// candidate d_dst[t] = post tracker d_pos[t] of the planes T | U, points and status, t < len (RunPlan::commit_list: every destination once)
+void launch_run_commit(uint32_t len, uint32_t pp, uint32_t n, const uint32_t* d_dst, const uint32_t* d_pos, const Aff* d_pts, const uint8_t* d_status, Aff* d_cand,
+                       uint8_t* d_cand_status, hipStream_t s);
+
 // ---- which trackers a set of keys opens (find.hip; plan and per-pair body in find_plan.hpp) ----
 struct FindPlan;
 // table path, one chunk: d_tab = the chunk's table of multiples (launch_table_build with 32 plain copies, step_bits 8, then launch_fix_build at

@@ -9,6 +9,7 @@
 #include <vector>
 #include "engine.hpp"
 #include "find_plan.hpp"
+#include "run_plan.hpp"
 
 namespace cpx {
 
@@ -1173,6 +1174,153 @@ void Engine::whisk_verify_shuffle_proofs_with(size_t count, const uint8_t* pre_t
   verify(dense.data(), verdict);
   for (size_t i = 0; i < count; i++)
     if (bad[i]) verdict[i] = CPX_ERR_DESERIALIZE;   // an undecodable tracker or M: Err(SerializationError), whatever the placeholder's verdict
+}
+
+// ---------------------------------------------------------------- a run of shuffles against the resident candidate list (run.hip, run_plan.hpp)
+// The list: decoded once, kept as two planes cand_R | cand_S with the decoder's status per point and the bytes as given.  An undecodable
+// candidate is no error here: whisk.rs fails in unzip_trackers only, so it fails the items that read it.
+void Engine::whisk_candidates_load(size_t n, const uint8_t* trackers, uint8_t* status) {
+  if (n > RUN_MAX_CANDIDATES) throw ArgError("candidate list: more than 2^24 trackers");
+  if (!n) {
+    cand_.pts.release();
+    cand_.status.release();
+    cand_.bytes.clear();
+    cand_.n = 0;
+    return;
+  }
+  const uint8_t* given = trackers;
+  trackers = canonical_infinities(trackers, n * 96, n, 96, {0, 48});
+  std::vector<uint32_t> off(2 * n);
+  for (size_t i = 0; i < n; i++) {   // plane-major, as the run's own planes: every r_G, then every k_r_G
+    off[i] = (uint32_t)(i * 96);
+    off[n + i] = (uint32_t)(i * 96 + 48);
+  }
+  std::vector<uint8_t> st;
+  std::vector<uint8_t> mirror(given, given + n * 96);
+  DevBuf<Aff> pts;   // the new list replaces the old one only once it is complete
+  DevBuf<uint8_t> dst;
+  {
+    CallScope call(this);
+    pts.ensure(2 * n);
+    dst.ensure(2 * n);
+    sh_.bytes.ensure(n * 96);
+    sh_.off.ensure(2 * n);
+    CPX_HIP(hipMemcpyAsync(sh_.bytes.p, trackers, n * 96, hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(sh_.off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    tick("k_decompress", 0, (double)(2 * n));
+    launch_decompress(opt_, sh_.bytes.p, (int)(2 * n), pts.p, nullptr, dst.p, 1, stream_, sh_.off.p);
+    tock();
+    st.resize(2 * n);
+    CPX_HIP(hipMemcpyAsync(st.data(), dst.p, 2 * n, hipMemcpyDeviceToHost, stream_));
+    call.finish();
+  }
+  std::swap(cand_.pts.p, pts.p);
+  std::swap(cand_.pts.cap, pts.cap);
+  std::swap(cand_.status.p, dst.p);
+  std::swap(cand_.status.cap, dst.cap);
+  cand_.bytes.swap(mirror);
+  cand_.n = n;
+  cand_.strict = opt_.strict_infinity;
+  if (status)
+    for (size_t i = 0; i < n; i++) status[i] = st[i] ? st[i] : st[n + i];
+}
+
+void Engine::whisk_candidates_read(size_t first, size_t count, uint8_t* trackers_out) const {
+  if (first > cand_.n || count > cand_.n - first) throw ArgError("candidate list: the range is outside the list");
+  if (count) memcpy(trackers_out, cand_.bytes.data() + first * 96, count * 96);
+}
+
+// whisk.rs:106-130 is_valid_whisk_shuffle_proof for a run of items over the resident list
+void Engine::whisk_verify_shuffle_run(size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand, int* verdict,
+                                      size_t* n_applied) {
+  whisk_verify_shuffle_run_with(count, indices, post_trackers, proofs, verdict, n_applied, [&](const uint8_t* dense, int* v) { batch_verify(dense, rand, v); });
+}
+// ... with 12 factors per item, through the grouped form of the accumulated check (locate_plan.hpp)
+void Engine::whisk_verify_shuffle_run_grouped(size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, const uint8_t* rand,
+                                              int* verdict, size_t* n_applied, size_t* n_rechecked) {
+  if (n_rechecked) *n_rechecked = 0;
+  whisk_verify_shuffle_run_with(count, indices, post_trackers, proofs, verdict, n_applied,
+                                [&](const uint8_t* dense, int* v) { batch_verify_grouped(dense, rand, v, n_rechecked); });
+}
+// The shared body.  As whisk_verify_shuffle_proofs_with, except that only the post side and M are uploaded and decoded (planes T | U and the
+// M slots); the planes R | S are gathered from the candidate planes and from T | U through the source list, and the accepted prefix is
+// written back through the commit list as the last step.
+void Engine::whisk_verify_shuffle_run_with(size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, int* verdict, size_t* n_applied,
+                                           const std::function<void(const uint8_t* dense, int* verdict)>& verify) {
+  for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
+  if (n_applied) *n_applied = 0;
+  if (!count) return;
+  if (!ell_) throw std::logic_error("set_crs first");
+  if (!cand_.n) throw std::logic_error("cpx_whisk_candidates_load first");
+  if (cand_.strict != opt_.strict_infinity) throw std::logic_error("option strict_infinity changed since the candidate list was loaded");
+  const size_t ell = ell_, psz = proof_size(), rec = 48 + psz, n = cand_.n;
+  const ShufflePlan pl(count, ell, true);
+  if (!pl.fits()) throw ArgError("shuffle run: count * ell exceeds the 32-bit index range of one call");
+  const RunPlan rp(count, ell, n);
+  if (!rp.indices_valid(indices)) throw ArgError("shuffle run: an index is outside the candidate list");
+  const Aff G = generator();   // (before canonical_infinities and the scope, as above)
+  const size_t pp = pl.plane_points(), tb = pl.tracker_bytes(), npts = 2 * pp + count;
+  const uint8_t* post_given = post_trackers;   // the list keeps the bytes as the items spelt them
+  std::vector<uint8_t> keep;
+  post_trackers = canonical_infinities(post_trackers, tb, pp, 96, {0, 48});
+  if (post_trackers != post_given) {   // (canon_bytes_ is reused by the next array)
+    keep.assign(post_trackers, post_trackers + tb);
+    post_trackers = keep.data();
+  }
+  proofs = canonical_infinities(proofs, count * rec, count, rec, {0});   // M; the proof points behind it are batch_verify's
+  std::vector<uint8_t> dense(count * psz);
+  for (size_t i = 0; i < count; i++) memcpy(dense.data() + i * psz, proofs + i * rec + 48, psz);
+  std::vector<uint32_t> off(npts), lists(3 * pp), last(n);
+  std::vector<uint8_t> bad;
+  for (size_t j = 0; j < npts; j++) off[j] = (uint32_t)(pl.src_offset(2 * pp + j) - tb);   // the upload holds post | M: the pre side's bytes are not there
+  rp.resolve(indices, lists.data(), last.data());
+  CallScope call(this);
+  sh_.bytes.ensure(tb + count * 48);
+  sh_.status.ensure(pl.points());
+  sh_.off.ensure(npts);
+  sh_.perm.ensure(3 * pp);   // the source list | the commit list's destinations | its positions
+  sh_.pts.ensure(pl.points());
+  sh_.bad.ensure(count);
+  sh_.mjac.ensure(count);
+  CPX_HIP(hipMemcpyAsync(sh_.bytes.p, post_trackers, tb, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpy2DAsync(sh_.bytes.p + tb, 48, proofs, rec, 48, count, hipMemcpyHostToDevice, stream_));   // the M prefixes only
+  CPX_HIP(hipMemcpyAsync(sh_.off.p, off.data(), npts * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(sh_.perm.p, lists.data(), pp * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  tick("k_decompress", 0, (double)npts);
+  launch_decompress(opt_, sh_.bytes.p, (int)npts, sh_.pts.p + 2 * pp, nullptr, sh_.status.p + 2 * pp, 1, stream_, sh_.off.p);
+  tock();
+  tick("k_run_gather", (double)pp * (4 * sizeof(Aff) + 4 + sizeof(uint32_t)), (double)pp);   // two points and two status bytes read and written, one list entry
+  launch_run_gather((uint32_t)pp, (uint32_t)n, sh_.perm.p, cand_.pts.p, cand_.status.p, sh_.pts.p, sh_.status.p, stream_);
+  tock();
+  tick("k_shuffle_status", 0, (double)count);
+  launch_shuffle_status(pl, sh_.status.p, sh_.pts.p, G, nullptr, nullptr, nullptr, sh_.mjac.p, sh_.bad.p, stream_);
+  tock();
+  const Aff* d = sh_.pts.p;
+  load_rows(count, reinterpret_cast<const uint8_t*>(d), reinterpret_cast<const uint8_t*>(d + pp), reinterpret_cast<const uint8_t*>(d + 2 * pp),
+            reinterpret_cast<const uint8_t*>(d + 3 * pp), reinterpret_cast<const uint8_t*>(sh_.mjac.p), true);
+  bad.resize(count);
+  CPX_HIP(hipMemcpyAsync(bad.data(), sh_.bad.p, count, hipMemcpyDeviceToHost, stream_));
+  call.finish();
+  verify(dense.data(), verdict);
+  for (size_t i = 0; i < count; i++)
+    if (bad[i]) verdict[i] = CPX_ERR_DESERIALIZE;   // an undecodable tracker or M: Err(SerializationError), whatever the placeholder's verdict
+  if (!n_applied) return;   // a dry run
+  size_t lead = 0;
+  while (lead < count && verdict[lead] == CPX_OK) lead++;
+  // The write-back, last: the planes T | U of the scratch still hold the decoded post trackers of every accepted item (k_shuffle_status
+  // rewrites the rows of undecodable items only, and none of those is in the prefix)
+  uint32_t *dst = lists.data() + pp, *pos = lists.data() + 2 * pp;
+  const size_t len = rp.commit_list(indices, (uint32_t)lead, dst, pos, last.data());
+  if (len) {
+    CPX_HIP(hipMemcpyAsync(sh_.perm.p + pp, dst, len * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(sh_.perm.p + 2 * pp, pos, len * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    tick("k_run_commit", (double)len * (4 * sizeof(Aff) + 4 + 2 * sizeof(uint32_t)), (double)len);
+    launch_run_commit((uint32_t)len, (uint32_t)pp, (uint32_t)n, sh_.perm.p + pp, sh_.perm.p + 2 * pp, sh_.pts.p, sh_.status.p, cand_.pts.p, cand_.status.p, stream_);
+    tock();
+    call.finish();
+    for (size_t t = 0; t < len; t++) memcpy(cand_.bytes.data() + (size_t)dst[t] * 96, post_given + (size_t)pos[t] * 96, 96);
+  }
+  *n_applied = lead;
 }
 
 }  // namespace cpx

@@ -254,6 +254,84 @@ def _verify_whisk_shuffle_proofs(ctx, pre_lists, post_lists, proofs, rands, nf):
     return res, rechecked.value
 
 
+# ---- a run of shuffles against the resident candidate list (cpx_whisk_candidates_* / cpx_whisk_verify_shuffle_run) ----
+def load_candidate_trackers(ctx, trackers):
+    """Makes `trackers` (WhiskTracker list, or their bytes back to back) THE candidate list of ctx, decoded once on the device; an empty list
+    drops it.  Returns one decoder status per candidate (0 = both points decode and lie in the subgroup; cpx_g1_decompress_status codes).
+    An undecodable candidate is not an error here: every item of a run that reads it is a SerializationError, as in the reference."""
+    raw = bytes(trackers) if isinstance(trackers, (bytes, bytearray)) else _cat(trackers)
+    if len(raw) % (2 * G1POINT_SIZE):
+        raise ValueError("a tracker is two 48-byte compressed G1 points")
+    n = len(raw) // (2 * G1POINT_SIZE)
+    status = _out(n)
+    ctx._check(ctx._L.cpx_whisk_candidates_load(ctx._h, n, _in(raw) if n else None, status))
+    return list(status[:n])
+
+
+def candidate_trackers(ctx, first=0, count=None):
+    """Candidates first .. first+count-1 of the resident list (count = None: to its end), byte for byte as loaded or as the post trackers
+    of an applied item spelt them."""
+    if first < 0 or (count is not None and count < 0):
+        raise ValueError("first and count are not negative")
+    size = ctx._L.cpx_whisk_candidates_size(ctx._h)
+    count = max(size - first, 0) if count is None else count
+    out = _out(count * 2 * G1POINT_SIZE)
+    ctx._check(ctx._L.cpx_whisk_candidates_read(ctx._h, first, count, out))
+    ob = bytes(out)
+    return [WhiskTracker(ob[96 * i:96 * i + 48], ob[96 * i + 48:96 * i + 96]) for i in range(count)]
+
+
+def verify_whisk_shuffle_run(ctx, indices_lists, post_lists, proofs, rands=None, grouped=False, apply=True):
+    """whisk.rs:106-130 for a run of shuffles over the candidate list of ctx (load_candidate_trackers) in ONE library call.  Item b reads
+    the candidates at indices_lists[b] (ell indices) of the list as it stands after items 0..b-1 were written back, whatever their
+    results, and post_lists[b] are the trackers it puts there.  rands: per item the verifier's eight factors, twelve when grouped
+    (CSPRNG when omitted).  Returns (results, n_applied), or (results, n_applied, n_rechecked) when grouped: results as
+    are_valid_whisk_shuffle_proofs (True / False / a SerializationError instance, a wrong proof length among them); the n_applied leading
+    accepted items, and no others, have been written back to the resident list.  apply=False is a dry run: the list stays as it was and
+    n_applied is None."""
+    count = len(indices_lists)
+    nf = 12 if grouped else 8
+    if len(post_lists) != count or len(proofs) != count or (rands is not None and len(rands) != count):
+        raise ValueError("one post tracker list, one proof and one set of factors per index list")
+    if count == 0:
+        return ([], None if not apply else 0, 0) if grouped else ([], None if not apply else 0)
+    ell = ctx.ell
+    if any(len(ix) != ell for ix in indices_lists) or any(len(t) != ell for t in post_lists):
+        raise ValueError("need exactly ell = %d indices and ell post trackers per item" % ell)
+    if any(not 0 <= i < 1 << 32 for ix in indices_lists for i in ix):
+        raise ValueError("candidate indices are unsigned 32-bit numbers")
+    rands = [_rand_fr(nf) for _ in range(count)] if rands is None else rands
+    if any(len(r) != nf * FR for r in rands):
+        raise ValueError("%d random factors per proof" % nf)
+    rec = whisk_shuffle_proof_size(ctx)
+    # a wrong length is a fixed-size array mismatch in the reference: reported per item; the library sees zero bytes, whose M does not decode
+    short = [len(p) != rec for p in proofs]
+    pf = b"".join(bytes(rec) if s else p for s, p in zip(short, proofs))
+    verdict = (ctypes.c_int * count)(*([CPX_ERR_INTERNAL] * count))   # an entry the library does not write is never read as accepted
+    idx = (ctypes.c_uint32 * (count * ell))(*[i for ix in indices_lists for i in ix])
+    post = _in(b"".join(_cat(t) for t in post_lists))
+    applied, rechecked = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    p_applied = ctypes.byref(applied) if apply else None
+    if grouped:
+        ctx._check(ctx._L.cpx_whisk_verify_shuffle_run_grouped(ctx._h, count, idx, post, _in(pf), _in(b"".join(rands)), verdict, p_applied, ctypes.byref(rechecked)))
+    else:
+        ctx._check(ctx._L.cpx_whisk_verify_shuffle_run(ctx._h, count, idx, post, _in(pf), _in(b"".join(rands)), verdict, p_applied))
+    res = []
+    for i, v in enumerate(verdict):
+        if short[i]:
+            res.append(SerializationError("wrong proof length"))
+        elif v == CPX_OK:
+            res.append(True)
+        elif v == CPX_ERR_VERIFY:
+            res.append(False)
+        elif v == CPX_ERR_DESERIALIZE:
+            res.append(SerializationError("shuffle proof %d" % i))
+        else:
+            raise CpxError(v, "shuffle proof %d" % i)
+    n_applied = applied.value if apply else None
+    return (res, n_applied, rechecked.value) if grouped else (res, n_applied)
+
+
 # ---- many tracker proofs per call (cpx_whisk_generate_tracker_proofs / cpx_whisk_verify_tracker_proofs) ----
 def generate_whisk_tracker_proofs(ctx, trackers, ks, blinders=None):
     """whisk.rs:228-263 for every (tracker, k, blinder) triple in ONE library call (a constant number of kernel launches).

@@ -370,6 +370,43 @@ int cpx_whisk_verify_shuffle_proofs(cpx_ctx* ctx, size_t count, const uint8_t* p
 int cpx_whisk_verify_shuffle_proofs_grouped(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers,
                                             const uint8_t* proofs, const uint8_t* rand /* count*12*32 */, int* verdict, size_t* n_rechecked);
 
+/* ---- a run of shuffles against a resident candidate list ----------------------------------------------------------
+ * A node holds ONE list of candidate trackers; every block's shuffle reads the trackers at ell indices of it and the shuffled trackers go
+ * back to the same indices.  The list lives in the context, decoded once; a run of such blocks is verified in one call that uploads and
+ * decodes the post side only.  Trackers are 96 bytes (r_G then k_r_G, compressed) as in the calls above, whose conventions hold: CPX_OK
+ * whatever the per-item results, count = 0 is a no-op, NULL data pointers with count > 0 are CPX_ERR_ARG (checked before the context is
+ * looked at), verdict is pre-filled with CPX_ERR_INTERNAL. */
+/* Loads n <= 2^24 candidates, replacing any earlier list (n = 0 drops it).  The 2n points are decoded on the device, subgroup-checked,
+ * under option "strict_infinity"; the context keeps the decoded points, a status per point and the bytes exactly as given.
+ *   status (may be NULL) [i]: the code of cpx_g1_decompress_status for r_G if that is non-zero, else the one for k_r_G.
+ * An undecodable candidate is no error of the load: it makes every item that reads it CPX_ERR_DESERIALIZE (the reference fails in
+ * unzip_trackers only, whisk.rs:106-130).  The list survives cpx_ctx_set_crs, batch loads and every other call, and goes with the context. */
+int cpx_whisk_candidates_load(cpx_ctx* ctx, size_t n, const uint8_t* trackers /* n*96 */, uint8_t* status /* n, may be NULL */);
+/* the length of the resident list (0: none) */
+size_t cpx_whisk_candidates_size(cpx_ctx* ctx);
+/* The bytes of candidates first .. first+count-1, verbatim: as loaded, or as the post trackers of an applied item spelt them.  A range
+ * outside the list is CPX_ERR_ARG. */
+int cpx_whisk_candidates_read(cpx_ctx* ctx, size_t first, size_t count, uint8_t* trackers_out /* count*96 */);
+/* whisk.rs:106-130 is_valid_whisk_shuffle_proof for a run of `count` items over the resident list.
+ *   Item b's pre tracker j is candidate indices[b][j] of the list AS IT STANDS AFTER ITEMS 0..b-1 HAVE ALL BEEN WRITTEN BACK, whatever their
+ *   verdicts.  Writing item b back is list[indices[b][j]] = post[b][j] for j = 0..ell-1 in that order: an index may repeat inside an item,
+ *   the item then reads the same tracker twice and the highest slot wins the write.
+ *   verdict[b]: exactly what cpx_whisk_verify_shuffle_proofs returns for that explicit (pre, post, proof, rand), the same three codes.
+ *   *n_applied: the number of leading items with CPX_OK.  Those items, and no others, are written back to the resident list.  The verdicts
+ *   behind the first failure stay defined by the as-if list above, NOT by the list the call leaves: they say what each later item would be
+ *   worth had every earlier one been applied.  n_applied == NULL is a dry run: verdicts only, the list stays as it was.
+ * An index >= cpx_whisk_candidates_size is CPX_ERR_ARG before anything is launched.  No list or no CRS is CPX_ERR_STATE, and so is a
+ * "strict_infinity" value other than the one the list was loaded under.  Any return other than CPX_OK leaves the list untouched: the
+ * write-back is the call's last step.  The count instances become the loaded batch, as with cpx_whisk_verify_shuffle_proofs; count * ell
+ * < 2^28 per call as there. */
+int cpx_whisk_verify_shuffle_run(cpx_ctx* ctx, size_t count, const uint32_t* indices /* count*ell */, const uint8_t* post_trackers /* count*ell*96 */,
+                                 const uint8_t* proofs /* count*(48+cpx_proof_size) */, const uint8_t* rand /* count*8*32 */, int* verdict /* count */,
+                                 size_t* n_applied /* may be NULL */);
+/* whisk.rs:106-130 for a run: cpx_whisk_verify_shuffle_run with 12 factors per item and the grouped check behind it, as
+ * cpx_whisk_verify_shuffle_proofs_grouped sits on cpx_whisk_verify_shuffle_proofs.  n_rechecked may be NULL. */
+int cpx_whisk_verify_shuffle_run_grouped(cpx_ctx* ctx, size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs,
+                                         const uint8_t* rand /* count*12*32 */, int* verdict, size_t* n_applied /* may be NULL */, size_t* n_rechecked);
+
 /* ---- the reference's `rng: &mut T` as a ChaCha12 state, the draws made on the device ------------------------------
  * Every proving function of the reference takes `rng: &mut T`; its tests and README use `StdRng::seed_from_u64(0)` (rand 0.8: StdRng =
  * ChaCha12Rng).  The calls above keep the RNG with the caller and take every draw as an argument.  The calls below take the STATE of a
@@ -461,7 +498,7 @@ int cpx_set_profiling(cpx_ctx* ctx, int on); /* time every kernel group with HIP
 int cpx_reset_stats(cpx_ctx* ctx);
 /* name = kernel name as rocprofv3 reports it, template arguments included: "k_msm_fix<16, 16>", "k_msm_tblw<32, false>",
  * "k_msm_tblw<2, true>", "k_msm_accw", "k_reduce_sets", "k_finalize_ranges", "k_table_build", "k_msm_tail", "k_smul",
- * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
+ * "k_finalize", "k_compress", "k_decompress", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_run_gather", "k_run_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor" (+ the host spans "host_prove_wall", "host_verify_wall", ...);
  * "k_smul" times the one-lane and the quad form alike; "k_smul_quad" counts (launches only) those of them that ran as k_smul_quad;
  * units = MSM points / scalar-mul elements / points; out pointers may be NULL */
 int cpx_get_stat(const cpx_ctx* ctx, const char* name, uint64_t* launches, double* total_ms, double* algorithmic_bytes, double* units);

@@ -106,6 +106,16 @@ extern "C" {
                                            verdict: *mut c_int) -> c_int;
     pub fn cpx_whisk_verify_shuffle_proofs_grouped(ctx: *mut cpx_ctx, count: usize, pre_trackers: *const u8, post_trackers: *const u8, proofs: *const u8,
                                                    rand: *const u8, verdict: *mut c_int, n_rechecked: *mut usize) -> c_int;
+    // the resident candidate tracker list (96 bytes per tracker; status: one decoder code per candidate, may be null) and whisk.rs:106-130 for a
+    // run of shuffles over it: item b reads candidates indices[b][..] of the list as it stands after items 0..b-1 were written back; the
+    // *n_applied leading accepted items are written back (n_applied null: a dry run)
+    pub fn cpx_whisk_candidates_load(ctx: *mut cpx_ctx, n: usize, trackers: *const u8, status: *mut u8) -> c_int;
+    pub fn cpx_whisk_candidates_size(ctx: *mut cpx_ctx) -> usize;
+    pub fn cpx_whisk_candidates_read(ctx: *mut cpx_ctx, first: usize, count: usize, trackers_out: *mut u8) -> c_int;
+    pub fn cpx_whisk_verify_shuffle_run(ctx: *mut cpx_ctx, count: usize, indices: *const u32, post_trackers: *const u8, proofs: *const u8, rand: *const u8,
+                                        verdict: *mut c_int, n_applied: *mut usize) -> c_int;
+    pub fn cpx_whisk_verify_shuffle_run_grouped(ctx: *mut cpx_ctx, count: usize, indices: *const u32, post_trackers: *const u8, proofs: *const u8,
+                                                rand: *const u8, verdict: *mut c_int, n_applied: *mut usize, n_rechecked: *mut usize) -> c_int;
     // the caller's `rng` as ChaCha12 states (40 bytes per stream: get_seed() || get_word_pos() as u64 LE), the draws made on the device
     pub fn cpx_rng_from_u64(seed: u64, state_out: *mut u8) -> c_int;
     pub fn cpx_rng_split(parent: *mut u8, count: usize, states_out: *mut u8) -> c_int;

@@ -294,6 +294,51 @@ pub fn are_valid_whisk_shuffle_proofs_grouped<T: RngCore>(
     (res, rechecked)
 }
 
+/// Makes `candidates` the resident candidate list of the context (decoded once on the device); one decoder status per candidate, 0 = fine.
+/// An undecodable candidate is no error here: every item of a run that reads it is Err(SerializationError), as in whisk.rs:106-130.
+pub fn load_candidate_trackers(crs: &CurdleproofsCrs, candidates: &[WhiskTracker]) -> Vec<u8> {
+    let wire = trackers_to_wire(candidates);
+    let mut status = vec![0u8; candidates.len()];
+    let rc = unsafe { cpx_whisk_candidates_load(ctx_with_crs(crs), candidates.len(), wire.as_ptr(), status.as_mut_ptr()) };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    status
+}
+
+/// whisk.rs:106-130 for a run of shuffles over the resident list in one library call: item b reads the candidates at `indices[b]` of the
+/// list as it stands after items 0..b-1 were written back (whatever their results) and `post_trackers[b]` go back to the same indices.
+/// Returns one result per item and n_applied: the leading accepted items, and no others, have been written back to the resident list.
+pub fn verify_whisk_shuffle_run<T: RngCore>(
+    rng: &mut T,
+    crs: &CurdleproofsCrs,
+    indices: &[&[u32]],
+    post_trackers: &[&[WhiskTracker]],
+    proofs: &[WhiskShuffleProofBytes],
+) -> (Vec<Result<bool, SerializationError>>, usize) {
+    assert!(indices.len() == post_trackers.len() && indices.len() == proofs.len());
+    assert!(indices.iter().all(|t| t.len() == ELL) && post_trackers.iter().all(|t| t.len() == ELL));
+    let count = proofs.len();
+    let factors = nonzero_factors(8 * count, rng);
+    let idx: Vec<u32> = indices.iter().flat_map(|t| t.iter().copied()).collect();
+    let post: Vec<u8> = post_trackers.iter().flat_map(|t| trackers_to_wire(t)).collect();
+    let pf: Vec<u8> = proofs.iter().flat_map(|p| p.iter().copied()).collect();
+    let mut verdict = vec![CPX_ERR_INTERNAL; count];
+    let mut applied: usize = 0;
+    let rc = unsafe {
+        cpx_whisk_verify_shuffle_run(ctx_with_crs(crs), count, idx.as_ptr(), post.as_ptr(), pf.as_ptr(), scalars_ptr(&factors), verdict.as_mut_ptr(), &mut applied)
+    };
+    assert!(rc == CPX_OK, "libcpx: {}", rc);
+    let res = verdict
+        .into_iter()
+        .map(|v| match v {
+            CPX_OK => Ok(true),
+            CPX_ERR_VERIFY => Ok(false),
+            CPX_ERR_DESERIALIZE => Err(SerializationError::InvalidData),
+            v => panic!("libcpx: {}", v),
+        })
+        .collect();
+    (res, applied)
+}
+
 /// whisk.rs:144-179 for many lists of pre trackers in one library call; every item draws from `rng` in the single function's order
 /// (shuffle, k, blinders, the prover's 3n+9), item after item
 pub fn generate_whisk_shuffle_proofs<T: RngCore>(

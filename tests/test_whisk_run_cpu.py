@@ -1,0 +1,217 @@
+"""CPU checks of the Whisk shuffle run against the resident candidate list (cpx_whisk_candidates_load / _size / _read,
+cpx_whisk_verify_shuffle_run and its grouped form): the boundary — header, export list, library, Rust declarations, argument checks that
+need no device, the Python mirrors' shape errors — and the bookkeeping host and kernels share (curdleproofs_amd/csrc/run_plan.hpp),
+run on the CPU by tests/host_emul/run_plan_emul.cpp, once plain and once with -fsanitize=address,undefined, and compared with a plain
+Python replay of the list."""
+import ctypes
+import os
+import random
+import re
+import subprocess
+import types
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+NAMES = ("cpx_whisk_candidates_load", "cpx_whisk_candidates_size", "cpx_whisk_candidates_read", "cpx_whisk_verify_shuffle_run",
+         "cpx_whisk_verify_shuffle_run_grouped")
+CITED = ("cpx_whisk_candidates_load", "cpx_whisk_verify_shuffle_run", "cpx_whisk_verify_shuffle_run_grouped")
+KERNELS = ("k_run_gather", "k_run_commit")
+POST = 0x80000000
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from curdleproofs_amd.build import build
+    build()
+    import curdleproofs_amd as cpx
+    return cpx.load_library()
+
+
+# ---- boundary ----
+def test_header_declares_the_calls_beside_their_reference_lines():
+    hdr = open(os.path.join(ROOT, "include", "cpx.h")).read()
+    for name in NAMES:
+        assert re.search(r"^(int|size_t) %s\(" % name, hdr, re.M), name
+    for name in CITED:
+        at = hdr.index("int %s(" % name)
+        comment = hdr[hdr.rindex("/*", 0, at):at]      # the comment block that ends right above the declaration
+        assert "whisk.rs:106-130" in comment, "%s: whisk.rs:106-130 is not cited beside the declaration" % name
+        assert comment.rstrip().endswith("*/")
+    at = hdr.index("int cpx_whisk_verify_shuffle_run(")
+    assert "as-if list" in hdr[hdr.rindex("/*", 0, at):at]      # the verdicts behind the first failure: the header says what defines them
+
+
+def test_names_are_exported_everywhere(lib):
+    import curdleproofs_amd as cpx
+    ffi = open(os.path.join(ROOT, "integration", "rust", "ffi.rs")).read()
+    hdr = open(os.path.join(ROOT, "include", "cpx.h")).read()
+    for name in NAMES:
+        assert name in cpx.EXPORTS
+        assert hasattr(lib, name), "libcpx.so does not export %s" % name
+        assert re.search(r"pub fn %s\(" % name, ffi), "integration/rust/ffi.rs lacks %s" % name
+    for k in KERNELS:
+        assert k in cpx.Context.KERNELS and '"%s"' % k in hdr
+        assert not k.startswith(("k_msm_fix", "k_msm_tblw", "k_msm_accw"))      # the prefixes bench.py prices
+
+
+def test_null_arguments_and_count_zero_without_a_device(lib):
+    import curdleproofs_amd as cpx
+    buf = (ctypes.c_uint8 * 8192)(*([0xaa] * 8192))
+    idx = (ctypes.c_uint32 * 64)()
+    st = (ctypes.c_int * 1)(7)
+    applied = ctypes.c_size_t(9)
+    # NULL data pointers with count > 0 (checked before the context is looked at), and a NULL context
+    assert lib.cpx_whisk_candidates_load(None, 1, None, None) == cpx.CPX_ERR_ARG
+    assert lib.cpx_whisk_candidates_load(None, 1, buf, None) == cpx.CPX_ERR_ARG
+    assert lib.cpx_whisk_candidates_load(None, 0, None, None) == cpx.CPX_ERR_ARG
+    assert lib.cpx_whisk_candidates_size(None) == 0
+    assert lib.cpx_whisk_candidates_read(None, 0, 1, None) == cpx.CPX_ERR_ARG
+    assert lib.cpx_whisk_candidates_read(None, 0, 1, buf) == cpx.CPX_ERR_ARG
+    run, grouped = lib.cpx_whisk_verify_shuffle_run, lib.cpx_whisk_verify_shuffle_run_grouped
+    assert run(None, 1, None, None, None, None, None, None) == cpx.CPX_ERR_ARG
+    assert run(None, 1, idx, buf, None, buf, st, ctypes.byref(applied)) == cpx.CPX_ERR_ARG
+    assert run(None, 1, None, buf, buf, buf, st, ctypes.byref(applied)) == cpx.CPX_ERR_ARG
+    assert run(None, 1, idx, buf, buf, buf, st, ctypes.byref(applied)) == cpx.CPX_ERR_ARG
+    assert grouped(None, 1, idx, buf, buf, None, st, ctypes.byref(applied), None) == cpx.CPX_ERR_ARG
+    assert grouped(None, 1, idx, buf, buf, buf, st, ctypes.byref(applied), None) == cpx.CPX_ERR_ARG
+    # count = 0 touches no buffer (without a context there is nothing to run on: still CPX_ERR_ARG, and still nothing written)
+    assert run(None, 0, None, None, None, None, None, None) == cpx.CPX_ERR_ARG
+    assert grouped(None, 0, None, None, None, None, None, None, None) == cpx.CPX_ERR_ARG
+    assert st[0] == 7 and applied.value == 9 and bytes(buf) == b"\xaa" * 8192
+
+
+def test_python_mirrors_check_shapes_before_touching_the_library():
+    from curdleproofs_amd import whisk
+    ell = 4
+    ctx = types.SimpleNamespace(ell=ell, n=ell + 4)        # any use of the library would raise AttributeError, not ValueError
+    t = whisk.WhiskTracker(b"\x01" * 48, b"\x02" * 48)
+    one, ix = [t] * ell, list(range(ell))
+    with pytest.raises(ValueError):                        # one post list per index list
+        whisk.verify_whisk_shuffle_run(ctx, [ix, ix], [one], [b"", b""])
+    with pytest.raises(ValueError):                        # one proof per index list
+        whisk.verify_whisk_shuffle_run(ctx, [ix], [one], [])
+    with pytest.raises(ValueError):                        # ell indices per item
+        whisk.verify_whisk_shuffle_run(ctx, [ix[:-1]], [one], [b""])
+    with pytest.raises(ValueError):                        # ell post trackers per item
+        whisk.verify_whisk_shuffle_run(ctx, [ix], [one + one], [b""])
+    with pytest.raises(ValueError):                        # an index is an unsigned 32-bit number
+        whisk.verify_whisk_shuffle_run(ctx, [[0, 1, 2, -1]], [one], [b""])
+    with pytest.raises(ValueError):
+        whisk.verify_whisk_shuffle_run(ctx, [[0, 1, 2, 1 << 32]], [one], [b""])
+    with pytest.raises(ValueError):                        # 8 factors, 12 when grouped
+        whisk.verify_whisk_shuffle_run(ctx, [ix], [one], [b""], rands=[bytes(32 * 12)])
+    with pytest.raises(ValueError):
+        whisk.verify_whisk_shuffle_run(ctx, [ix], [one], [b""], rands=[bytes(32 * 8)], grouped=True)
+    with pytest.raises(ValueError):                        # whole trackers
+        whisk.load_candidate_trackers(ctx, bytes(95))
+    with pytest.raises(ValueError):
+        whisk.candidate_trackers(ctx, first=-1)
+    with pytest.raises(ValueError):
+        whisk.candidate_trackers(ctx, count=-1)
+    assert whisk.verify_whisk_shuffle_run(None, [], [], []) == ([], 0)
+    assert whisk.verify_whisk_shuffle_run(None, [], [], [], grouped=True) == ([], 0, 0)
+    assert whisk.verify_whisk_shuffle_run(None, [], [], [], apply=False) == ([], None)
+
+
+# ---- run_plan.hpp against a Python replay of the list ----
+def replay(n, ell, table, n_applied):
+    """A list entry is ("c", i): candidate i as loaded, or ("p", g): post tracker g = b * ell + j of the call.  Returns the entry every
+    (b, j) reads, in order, when ALL earlier items have been written back, and the list after the first n_applied items alone."""
+    lst = [("c", i) for i in range(n)]
+    reads = []
+    for b, row in enumerate(table):
+        reads += [lst[i] for i in row]                     # an item reads before it writes
+        for j, i in enumerate(row):                        # rising j: the highest slot wins
+            lst[i] = ("p", b * ell + j)
+    applied = [("c", i) for i in range(n)]
+    for b, row in enumerate(table[:n_applied]):
+        for j, i in enumerate(row):
+            applied[i] = ("p", b * ell + j)
+    return reads, applied
+
+
+@pytest.fixture(scope="module", params=["plain", "sanitized"])
+def emul(request):
+    src = os.path.join(HERE, "host_emul", "run_plan_emul.cpp")
+    san = request.param == "sanitized"
+    exe = os.path.join(HERE, "host_emul", "_run_plan_san" if san else "_run_plan")
+    csrc = os.path.join(ROOT, "curdleproofs_amd", "csrc")
+    deps = [src] + [os.path.join(csrc, f) for f in ("run_plan.hpp", "mont32.hpp")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags + ["-o", exe, src])
+
+    def run(n, ell, table, n_applied):
+        text = "%d %d %d %d\n%s\n" % (len(table), ell, n, n_applied, " ".join(str(i) for row in table for i in row))
+        out = subprocess.run([exe], input=text, check=True, capture_output=True, text=True).stdout      # a sanitizer report is a non-zero exit
+        res = {}
+        for line in out.splitlines():
+            key, *vals = line.split()
+            res[key] = [int(v) for v in vals]
+        return res
+    return run
+
+
+def check_against_replay(emul, n, ell, table, n_applied):
+    got = emul(n, ell, table, n_applied)
+    assert got["valid"] == [1] and got["lanes"] == [1]
+    reads, applied = replay(n, ell, table, n_applied)
+    assert [("p", s - POST) if s & POST else ("c", s) for s in got["src"]] == reads
+    dst, pos = got["dst"], got["pos"]
+    assert got["commit"] == [len(dst)] and len(dst) == len(pos)
+    assert len(set(dst)) == len(dst)                           # no two lanes of the write-back on one candidate
+    lst = [("c", i) for i in range(n)]
+    for d, p in zip(dst, pos):
+        lst[d] = ("p", p)
+    assert lst == applied
+    assert len(dst) == sum(1 for e in applied if e[0] == "p")  # the touched indices, and nothing else
+    return reads, applied
+
+
+@pytest.mark.parametrize("ell", (4, 28, 124))
+@pytest.mark.parametrize("count", (0, 1, 3, 65))
+def test_plan_equals_the_replay_on_seeded_tables(emul, count, ell):
+    for n in (ell, ell + 1, 3 * ell):
+        rnd = random.Random(100000 * count + 100 * ell + n)
+        distinct = [rnd.sample(range(n), ell) for _ in range(count)]                       # what a shuffle does: ell different indices
+        repeats = [[rnd.randrange(n) for _ in range(ell)] for _ in range(count)]          # what the interface allows
+        for table in (distinct, repeats):
+            for n_applied in sorted({0, count // 2, count}):
+                check_against_replay(emul, n, ell, table, n_applied)
+
+
+def test_crafted_table_reaches_every_case(emul):
+    ell, n = 4, 12
+    table = [[0, 1, 2, 3],
+             [0, 4, 5, 5],        # 0: written by the item directly before; 5 twice
+             [0, 6, 7, 8],
+             [0, 9, 10, 11],
+             [0, 1, 5, 6]]        # 1: written four items back, untouched since; 5: the higher of item 1's two writes
+    for n_applied in (0, 2, len(table)):
+        reads, applied = check_against_replay(emul, n, ell, table, n_applied)
+        at = lambda b, j: reads[b * ell + j]
+        assert at(0, 2) == ("c", 2) and at(1, 1) == ("c", 4)                       # a source in the list
+        assert at(1, 0) == ("p", 0)                                                # a source in the item directly before
+        assert at(4, 1) == ("p", 1) and all(1 not in row for row in table[1:4])    # several items back, untouched items between
+        assert at(1, 2) == at(1, 3) == ("c", 5)                                    # the same index twice: both reads get the same source
+        assert at(4, 2) == ("p", 1 * ell + 3)                                      # ... and the higher slot won the write
+        assert all(row[0] == 0 for row in table) and [at(b, 0) for b in range(1, 5)] == [("p", (b - 1) * ell) for b in range(1, 5)]
+        if n_applied == 0:
+            assert applied == [("c", i) for i in range(n)]
+        if n_applied == 2:
+            assert applied[0] == ("p", ell) and applied[5] == ("p", ell + 3) and applied[1] == ("p", 1) and applied[6] == ("c", 6)
+        if n_applied == len(table):
+            assert applied[0] == ("p", 4 * ell) and applied[1] == ("p", 4 * ell + 1) and applied[5] == ("p", 4 * ell + 2)
+
+
+def test_an_index_equal_to_n_is_refused(emul):
+    ell, n = 4, 12
+    good = [[0, 1, 2, 3], [4, 5, 6, 11]]
+    assert emul(n, ell, good, 0)["valid"] == [1]
+    for b, j in ((0, 0), (1, 3)):
+        bad = [list(r) for r in good]
+        bad[b][j] = n
+        assert emul(n, ell, bad, 0) == {"valid": [0]}
+    assert emul(n, ell, [[0, 1, 2, 0xffffffff]], 0) == {"valid": [0]}
