@@ -471,6 +471,21 @@ class Engine {
   // device-resident bases and scalars, inside the caller's scope
   void msm_chain_reserve(const Tier0MsmPlan& pl);
   void msm_chain(const Tier0MsmPlan& pl, const uint32_t* lens, const Aff* d_bases, const Fr* d_scalars, Jac* d_res, std::vector<MsmTask>& tasks);
+  // n trackers -> the planes r_G | k_r_G: upload + k_decompress of the tracker prover, find-trackers and the candidate list (whisk.cpp)
+  void decode_tracker_planes(size_t n, const uint8_t* trackers, std::vector<uint8_t>& canon, std::vector<uint32_t>& off, uint8_t* d_bytes, uint32_t* d_off, Aff* d_pts,
+                             uint8_t* d_status);
+  // What the batched tracker verifiers begin with (whisk.cpp), inside the caller's scope: upload, k_decompress, k_tracker_challenge.  The host
+  // side (rewritten copies of the three inputs, the offset table) is the caller's, declared above its scope; the pointers are into the scratch
+  struct TrackerFrontHost {
+    std::vector<uint8_t> canon[3];
+    std::vector<uint32_t> off;
+  };
+  struct TrackerFront {
+    const uint8_t *d_prf, *d_bad;   // the proofs as uploaded; per item: 0 = every point decoded and s is reduced
+    const Aff* pts;                 // planes A | B | k_r_G | r_G | k_G
+    const Fr* chal;
+  };
+  TrackerFront tracker_front(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, TrackerFrontHost& h);
   // the grouped / fused check of tracker proofs (tracker_check_plan.hpp, whisk.cpp): verdict != null = grouped, else partial_jac + n_invalid
   void tracker_check(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, const uint8_t* rand, int* verdict, size_t* n_rechecked,
                      uint8_t* partial_jac, int* n_invalid);
@@ -585,9 +600,18 @@ class Engine {
   void run_tbl_phase(const std::vector<TblReq>& reqs, std::vector<uint8_t>* comp_out);
   void reduce_sets(hipStream_t st, MsmScratch& sc, size_t nplain, size_t nweighted, TJac* part = nullptr);
   void verify_core(const uint8_t* proofs, const uint8_t* rand, size_t rand_stride, int* verdict, uint8_t* fused_partial, int* fused_invalid, size_t* grouped = nullptr);
-  // the shared body of the two many-per-call shuffle verifiers: everything up to the dense proofs of the loaded batch, then `verify` on them
+  // The many-per-call shuffle verifiers (whisk.cpp): one body for the explicit pre side and the run's, `verify` on the dense proofs of the
+  // loaded batch (plain or grouped).  Host memory of the body: the caller's, declared above its scope
+  using ShuffleVerifyFn = std::function<void(const uint8_t* dense, int* verdict)>;
+  struct ShuffleVerifyHost {
+    std::vector<uint8_t> canon[3], dense, bad;
+    std::vector<uint32_t> off;
+  };
+  bool shuffle_verify_begin(size_t count, int* verdict);
+  void shuffle_verify_body(CallScope& call, ShuffleVerifyHost& h, const ShufflePlan& pl, const Aff& G, const uint8_t* pre_trackers, const uint32_t* src,
+                           const uint8_t* post_trackers, const uint8_t* proofs, int* verdict, const ShuffleVerifyFn& verify);
   void whisk_verify_shuffle_proofs_with(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, int* verdict,
-                                        const std::function<void(const uint8_t* dense, int* verdict)>& verify);
+                                        const ShuffleVerifyFn& verify);
   // The resident candidate list: outside the scratch sets (no call trims it), replaced by the next load only
   struct Candidates {
     size_t n = 0;
@@ -596,14 +620,15 @@ class Engine {
     DevBuf<uint8_t> status;         // the decoder's codes, same layout
     std::vector<uint8_t> bytes;     // n * 96, exactly as given / as the applied items spelt their post trackers
   } cand_;
-  // the run body beside whisk_verify_shuffle_proofs_with: the same `verify` functor for the plain and the grouped form
+  // the run beside whisk_verify_shuffle_proofs_with: the same body with the pre side from the list, then the write-back
   void whisk_verify_shuffle_run_with(size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, int* verdict, size_t* n_applied,
-                                     const std::function<void(const uint8_t* dense, int* verdict)>& verify);
+                                     const ShuffleVerifyFn& verify);
   void batch_prove_tables(const uint32_t* permutation, const uint8_t* k, const uint8_t* m_blinders, const uint8_t* rand, uint8_t* proofs_out);
   // option strict_infinity = 0: `bytes` with every non-canonical infinity encoding (at `offsets` of each of the nrec records) rewritten to
-  // the canonical one, in canon_bytes_ (valid until the next call); `bytes` itself when there is none or the option is set
-  const uint8_t* canonical_infinities(const uint8_t* bytes, size_t nbytes, size_t nrec, size_t rec_stride, const std::vector<size_t>& offsets);
-  std::vector<uint8_t> canon_bytes_;
+  // the canonical one, in the caller's `store` (canon_infinity.hpp; declared above the caller's CallScope: an enqueued copy reads it); `bytes`
+  // itself, with `store` left alone, when there is none or the option is set
+  const uint8_t* canonical_infinities(const uint8_t* bytes, size_t nbytes, size_t nrec, size_t rec_stride, const std::vector<size_t>& offsets,
+                                      std::vector<uint8_t>& store) const;
   void run_smul(const std::vector<SmulTask>& tasks, int cnt, const host::S* scalars, size_t nscalars, double alg_bytes);
   const uint32_t* idx_list(const std::vector<uint32_t>& v);
   void tick(const char* name, double bytes, double units, bool span = false);
@@ -612,6 +637,14 @@ class Engine {
   // the launch "k_smul" times ran as k_smul_quad (what launch_smul reports): counted under a name of its own, launches only
   void count_smul_quad(bool quad) {
     if (profiling_ && quad) stats_["k_smul_quad"].launches++;
+  }
+  // One k_smul over ntasks uploaded tasks of `each` elements (whisk.cpp: the tracker prover, find-trackers, the shuffle step): the tasks
+  // carry smul_flag(), option scale_any_point as in Engine::scale, and the quad form is off under it
+  uint32_t smul_flag() const { return opt_.scale_any_point ? SMUL_PLAIN : 0u; }
+  void smul_tasks(const SmulTask* d_tasks, size_t ntasks, size_t each, double units) {
+    tick("k_smul", 224.0 * units, units);
+    count_smul_quad(launch_smul(d_tasks, (int)ntasks, (int)each, stream_, false, smul_flag() ? 0 : opt_.smul_quad_max));
+    tock();
   }
   void flush_timers();
   template <class F> void parallel_for(size_t n, F&& f);

@@ -610,15 +610,8 @@ void Engine::batch_prove_device(const ProveDraws& dr, uint8_t* proofs_out) {
       rng_.states.ensure(B * RNG_STATE_BYTES);
       CPX_HIP(hipMemcpyAsync(rng_.states.p, dr.states_in, B * RNG_STATE_BYTES, hipMemcpyHostToDevice, stream_));
     }
-    RngDrawArgs a{};
-    a.states = rng_.states.p;
-    a.mid_phase = -1;
-    a.count = (uint32_t)B;
-    a.nfr = 1;
-    a.fr_cnt[0] = (uint32_t)nrand;
-    a.fr_out[0] = dp.rnd.p;
     tick("k_rng_draw", (double)(B * nrand * sizeof(Fr)), (double)(B * nrand));
-    launch_rng_draw(a, stream_);
+    launch_rng_draw(rng_draw_args(rng_.states.p, nullptr, B, 0, nullptr, {{nrand, dp.rnd.p}}), stream_);
     tock();
   }
 

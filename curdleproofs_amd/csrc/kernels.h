@@ -1,6 +1,7 @@
 // Task descriptors and launchers of the gfx950 kernels (kernels.hip) — shared with the host engine.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include "g1.hpp"
 #include "g1_28.hpp"
 
@@ -380,6 +381,25 @@ struct RngDrawArgs {
   uint32_t fr_cnt[RNG_MAX_FR_PHASES];
   Fr* fr_out[RNG_MAX_FR_PHASES];
 };
+// the arguments of one launch: states_mid (nullable) is taken after the first Fr group; no shuffle: shuffle_len 0, perm null
+struct RngFrGroup {
+  size_t count;
+  Fr* out;
+};
+inline RngDrawArgs rng_draw_args(uint8_t* states, uint8_t* states_mid, size_t count, size_t shuffle_len, uint32_t* perm, std::initializer_list<RngFrGroup> fr) {
+  RngDrawArgs a{};
+  a.states = states;
+  a.states_mid = states_mid;
+  a.mid_phase = states_mid ? 0 : -1;
+  a.count = (uint32_t)count;
+  a.shuffle_len = (uint32_t)shuffle_len;
+  a.perm = perm;
+  for (const RngFrGroup& g : fr) {   // (at most RNG_MAX_FR_PHASES)
+    a.fr_cnt[a.nfr] = (uint32_t)g.count;
+    a.fr_out[a.nfr++] = g.out;
+  }
+  return a;
+}
 size_t rng_draw_max_shuffle();   // the longest permutation a wave holds in LDS
 void launch_rng_draw(const RngDrawArgs& a, hipStream_t s);
 

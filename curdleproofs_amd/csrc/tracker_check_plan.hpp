@@ -28,6 +28,19 @@ enum : int { TCK_K_G = 0, TCK_A = 1, TCK_R_G = 2, TCK_K_R_G = 3, TCK_B = 4 };
 // the plane of k_decompress's output that holds term j (the batched verifier decodes A, B, k_r_G, r_G, k_G plane-major: whisk.cpp)
 CPX_HD int tck_plane(int j) { return j == TCK_K_G ? 4 : j == TCK_A ? 0 : j == TCK_R_G ? 3 : j == TCK_K_R_G ? 2 : 1; }
 
+// The inputs of `count` items as both batched verifiers upload them: trackers (96 B each) | k_commitments (48 B) | proofs (128 B), and where
+// the decoder reads the five points of item i from: plane_off[pl] + plane_rec[pl] * i, planes A, B (inside the proof), k_r_G, r_G (inside
+// the tracker), k_G — the order tck_plane() names.
+constexpr int TCK_PLANES = 5;
+struct TrackerInputLayout {
+  size_t trackers, k_commitments, proofs, bytes;   // the three arrays' offsets and the size of the whole
+  size_t plane_off[TCK_PLANES], plane_rec[TCK_PLANES];
+};
+inline TrackerInputLayout tracker_input_layout(size_t count) {
+  const size_t kc = 96 * count, prf = 144 * count;
+  return TrackerInputLayout{0, kc, prf, 272 * count, {prf, prf + 48, 48, 0, kc}, {128, 128, 96, 96, 48}};
+}
+
 struct TrackerCheckPlan {
   LocatePlan lp;
   size_t count() const { return lp.B; }
@@ -43,7 +56,7 @@ struct TrackerCheckPlan {
     return task_off(g) + 1 + TCK_TERMS * (p - lp.group_first(g)) + (size_t)j;
   }
   // ---- scratch of a call (beside the tier-0 MSM scratch for tasks() tasks of points() points: tier0_plan.hpp) ----
-  size_t input_bytes() const { return 272 * lp.B; }    // trackers | k_commitments | proofs
+  size_t input_bytes() const { return tracker_input_layout(lp.B).bytes; }
   size_t weight_scalars() const { return 2 * lp.B; }   // a_i, b_i
   size_t result_points() const { return lp.NT; }       // the group sums, Jacobian standard form
   // stage 2: S suspects, dense — five decoded planes of S points, S proofs, S challenges, S clear flags, S verdicts

@@ -189,55 +189,68 @@ static void tracker_point_offsets(size_t count, const size_t* plane_off, const s
   for (int pl = 0; pl < planes; pl++)
     for (size_t i = 0; i < count; i++) off[(size_t)pl * count + i] = (uint32_t)(plane_off[pl] + plane_rec[pl] * i);
 }
+// n trackers (r_G || k_r_G, 96 bytes each) -> d_pts = every r_G, then every k_r_G, with the decoder's verdict per point in d_status: the
+// upload (strict_infinity = 0 applied) and ONE k_decompress, inside the caller's scope.  `canon`, `off`: the caller's, declared above it
+void Engine::decode_tracker_planes(size_t n, const uint8_t* trackers, std::vector<uint8_t>& canon, std::vector<uint32_t>& off, uint8_t* d_bytes, uint32_t* d_off,
+                                   Aff* d_pts, uint8_t* d_status) {
+  trackers = canonical_infinities(trackers, 96 * n, n, 96, {0, 48}, canon);
+  const size_t plane_off[2] = {0, 48}, plane_rec[2] = {96, 96};
+  tracker_point_offsets(n, plane_off, plane_rec, 2, off);
+  CPX_HIP(hipMemcpyAsync(d_bytes, trackers, 96 * n, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  tick("k_decompress", 0, 2.0 * n);
+  launch_decompress(opt_, d_bytes, (int)(2 * n), d_pts, nullptr, d_status, 1, stream_, d_off);
+  tock();
+}
+
+// What every batched tracker verifier begins with, inside the caller's scope (`h`: the caller's, declared above it): the inputs with
+// strict_infinity = 0 applied go up as tracker_input_layout (tracker_check_plan.hpp) says, k_decompress leaves the five planes A, B, k_r_G,
+// r_G, k_G and k_tracker_challenge every item's challenge and clear flag.  t0_.dig holds the decoder's offsets (5 count words).
+Engine::TrackerFront Engine::tracker_front(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, TrackerFrontHost& h) {
+  trackers = canonical_infinities(trackers, 96 * count, count, 96, {0, 48}, h.canon[0]);
+  k_commitments = canonical_infinities(k_commitments, 48 * count, count, 48, {0}, h.canon[1]);
+  proofs = canonical_infinities(proofs, 128 * count, count, 128, {0, 48}, h.canon[2]);
+  const int n = (int)count;
+  const TrackerInputLayout in = tracker_input_layout(count);
+  DevBuf<uint8_t>&din = t0_.bytes, &dst = t0_.status;   // trackers | k_commitments | proofs; 5 count decoding verdicts | count proof flags
+  DevBuf<uint32_t>& doff = t0_.dig;
+  DevBuf<Aff>& dpts = t0_.a0;
+  DevBuf<Fr>& dchal = t0_.fr;
+  din.ensure(in.bytes);
+  dst.ensure(6 * count);
+  doff.ensure(TCK_PLANES * count);
+  dpts.ensure(TCK_PLANES * count);
+  dchal.ensure(count);
+  // the five points of proof i are read where they lie: A, B inside the proof, k_r_G, r_G inside the tracker, k_G
+  tracker_point_offsets(count, in.plane_off, in.plane_rec, TCK_PLANES, h.off);
+  CPX_HIP(hipMemcpyAsync(din.p + in.trackers, trackers, 96 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(din.p + in.k_commitments, k_commitments, 48 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(din.p + in.proofs, proofs, 128 * count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(doff.p, h.off.data(), h.off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  uint8_t* d_bad = dst.p + TCK_PLANES * count;
+  tick("k_decompress", 0, 5.0 * count);
+  launch_decompress(opt_, din.p, TCK_PLANES * n, dpts.p, nullptr, dst.p, 1, stream_, doff.p);
+  tock();
+  tick("k_tracker_challenge", 288.0 * count, (double)count);
+  launch_tracker_challenge_verify(din.p, dst.p, n, dchal.p, d_bad, stream_);
+  tock();
+  return TrackerFront{din.p + in.proofs, d_bad, dpts.p, dchal.p};
+}
 
 // whisk.rs:183-226 is_valid_whisk_tracker_proof for every (tracker, k_commitment, proof) triple
 void Engine::whisk_verify_tracker_proofs(size_t count, const uint8_t* trackers, const uint8_t* k_commitments, const uint8_t* proofs, int* verdict) {
   for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
   if (!count) return;
   if (count > kTrackerBatchMax) throw ArgError("tracker proofs: at most 2^23 per call");
-  const Aff G = generator();   // (before the scope: the first call decodes the generator, a tier-0 call of its own)
-  // strict_infinity = 0: non-canonical infinity encodings are rewritten in COPIES of the inputs (canonical_infinities)
-  std::vector<uint8_t> keep[2];
-  auto canon = [&](const uint8_t* in, size_t rec, const std::vector<size_t>& offs, std::vector<uint8_t>* store) {
-    const uint8_t* p = canonical_infinities(in, count * rec, count, rec, offs);
-    if (p == in || !store) return p;
-    store->assign(p, p + count * rec);   // (canon_bytes_ is reused by the next array)
-    return (const uint8_t*)store->data();
-  };
-  trackers = canon(trackers, 96, {0, 48}, &keep[0]);
-  k_commitments = canon(k_commitments, 48, {0}, &keep[1]);
-  proofs = canon(proofs, 128, {0, 48}, nullptr);
-  std::vector<uint32_t> off;
+  const Aff G = generator();   // (before the scope: the first call decodes the generator, a tier-0 call of its own, and scopes do not nest)
+  TrackerFrontHost host;
   CallScope call(this);
-  const int n = (int)count;
-  DevBuf<uint8_t>&din = t0_.bytes, &dst = t0_.status;   // trackers | k_commitments | proofs; 5 count decoding verdicts | count proof flags
-  DevBuf<uint32_t>& doff = t0_.dig;
-  DevBuf<Aff>& dpts = t0_.a0;
-  DevBuf<Fr>& dchal = t0_.fr;
   DevBuf<int>& dver = t0_.flag;
-  din.ensure(272 * count);
-  dst.ensure(6 * count);
-  doff.ensure(5 * count);
-  dpts.ensure(5 * count);
-  dchal.ensure(count);
   dver.ensure(count);
-  uint8_t *d_trk = din.p, *d_kc = din.p + 96 * count, *d_prf = din.p + 144 * count;
-  // the five points of proof i are read where they lie: A, B inside the proof, k_r_G, r_G inside the tracker, k_G
-  const size_t plane_off[5] = {144 * count, 144 * count + 48, 48, 0, 96 * count}, plane_rec[5] = {128, 128, 96, 96, 48};
-  tracker_point_offsets(count, plane_off, plane_rec, 5, off);
-  CPX_HIP(hipMemcpyAsync(d_trk, trackers, 96 * count, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(d_kc, k_commitments, 48 * count, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(d_prf, proofs, 128 * count, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemsetAsync(dver.p, 0xff, count * sizeof(int), stream_));   // (-1: not CPX_OK)
-  tick("k_decompress", 0, 5.0 * count);
-  launch_decompress(opt_, din.p, 5 * n, dpts.p, nullptr, dst.p, 1, stream_, doff.p);
-  tock();
-  tick("k_tracker_challenge", 288.0 * count, (double)count);
-  launch_tracker_challenge_verify(din.p, dst.p, n, dchal.p, dst.p + 5 * count, stream_);
-  tock();
+  const TrackerFront f = tracker_front(count, trackers, k_commitments, proofs, host);
   tick("k_tracker_relations", 0, 2.0 * count);
-  launch_tracker_relations(dpts.p, d_prf, dchal.p, dst.p + 5 * count, G, n, dver.p, stream_);
+  launch_tracker_relations(f.pts, f.d_prf, f.chal, f.d_bad, G, (int)count, dver.p, stream_);
   tock();
   CPX_HIP(hipMemcpyAsync(verdict, dver.p, count * sizeof(int), hipMemcpyDeviceToHost, stream_));
   call.finish();
@@ -249,7 +262,7 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
   if (!count) return;
   if (count > kTrackerBatchMax) throw ArgError("tracker proofs: at most 2^23 per call");
   const Aff G = generator();   // (before the scope, as above)
-  trackers = canonical_infinities(trackers, 96 * count, count, 96, {0, 48});
+  std::vector<uint8_t> canon;
   std::vector<Aff> g;
   std::vector<uint32_t> off;
   SmulTask tasks[3];
@@ -277,25 +290,17 @@ void Engine::whisk_generate_tracker_proofs(size_t count, const uint8_t* trackers
     t0_.gen_n = count;
   }
   uint8_t *d_trk = db.p, *d_comp = db.p + 96 * count, *d_prf = db.p + 240 * count;
-  const size_t plane_off[2] = {0, 48}, plane_rec[2] = {96, 96};
-  tracker_point_offsets(count, plane_off, plane_rec, 2, off);
-  const uint32_t fl = opt_.scale_any_point ? SMUL_PLAIN : 0u;   // (as Engine::scale)
+  const uint32_t fl = smul_flag();
   tasks[0] = SmulTask{nullptr, dgen.p, dout.p, dsc.p, 1, fl};                              // k_G = k G
   tasks[1] = SmulTask{nullptr, dgen.p, dout.p + count, dsc.p + count, 1, fl};              // A = blinder G
   tasks[2] = SmulTask{nullptr, dtr.p, dout.p + 2 * count, dsc.p + count, 1, fl};           // B = blinder r_G
-  CPX_HIP(hipMemcpyAsync(d_trk, trackers, 96 * count, hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dsc.p, k, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dsc.p + count, blinders, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dtask.p, tasks, sizeof tasks, hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemsetAsync(dver.p, 0xff, count * sizeof(int), stream_));
   CPX_HIP(hipMemsetAsync(d_prf, 0, 128 * count, stream_));
-  tick("k_decompress", 0, 2.0 * count);
-  launch_decompress(opt_, db.p, 2 * n, dtr.p, nullptr, dst.p, 1, stream_, doff.p);
-  tock();
-  tick("k_smul", 224.0 * 3 * count, 3.0 * count);
-  count_smul_quad(launch_smul(dtask.p, 3, n, stream_, false, fl ? 0 : opt_.smul_quad_max));
-  tock();
+  decode_tracker_planes(count, trackers, canon, off, d_trk, doff.p, dtr.p, dst.p);
+  smul_tasks(dtask.p, 3, count, 3.0 * count);
   tick("k_compress", 0, 3.0 * count);
   launch_compress(dout.p, 3 * n, 3 * n, 1, d_comp, stream_);
   tock();
@@ -342,17 +347,7 @@ void Engine::tracker_check(size_t count, const uint8_t* trackers, const uint8_t*
     for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
     if (n_rechecked) *n_rechecked = 0;
   }
-  const Aff G = generator();   // (before the scope: the first call decodes the generator, a tier-0 call of its own)
-  std::vector<uint8_t> keep[2];
-  auto canon = [&](const uint8_t* in, size_t rec, const std::vector<size_t>& offs, std::vector<uint8_t>* store) {
-    const uint8_t* p = canonical_infinities(in, count * rec, count, rec, offs);
-    if (p == in || !store) return p;
-    store->assign(p, p + count * rec);   // (canon_bytes_ is reused by the next array)
-    return (const uint8_t*)store->data();
-  };
-  trackers = canon(trackers, 96, {0, 48}, &keep[0]);
-  k_commitments = canon(k_commitments, 48, {0}, &keep[1]);
-  proofs = canon(proofs, 128, {0, 48}, nullptr);
+  const Aff G = generator();   // (before the scope, as above)
   // the fused sum keeps the grouping of cpx_batch_verify_fused; the groups only shape the MSM there
   const TrackerCheckPlan tp = tracker_check_plan(count, grouped ? opt_.locate_groups_max : kLocateGroupsMax);
   const LocatePlan& lp = tp.lp;
@@ -362,7 +357,8 @@ void Engine::tracker_check(size_t count, const uint8_t* trackers, const uint8_t*
   pl.points = tp.points();
   pl.max_n = (uint32_t)tp.max_n();
   pl.conv_off.resize(NT);
-  std::vector<uint32_t> lens(NT), off, list, flags;
+  std::vector<uint32_t> lens(NT), list, flags;
+  TrackerFrontHost host;
   for (size_t g = 0; g < NT; g++) {
     pl.conv_off[g] = (uint32_t)tp.task_off(g);
     lens[g] = (uint32_t)tp.task_n(g);
@@ -376,40 +372,24 @@ void Engine::tracker_check(size_t count, const uint8_t* trackers, const uint8_t*
   CallScope call(this);
   pl.slices = msm_tblw_slices(opt_, (int)NT, 2, (int)pl.max_n);
   const int n = (int)count;
-  DevBuf<uint8_t>&din = t0_.bytes, &dst = t0_.status;   // trackers | k_commitments | proofs; 5 count decoding verdicts | count proof flags
-  DevBuf<uint32_t>& doff = t0_.dig;                     // the decoder's offsets, then the chain's digits, then stage 2's list
-  DevBuf<Aff>&dpts = t0_.a0, &dbase = t0_.tbase;
-  DevBuf<Fr>&dchal = t0_.fr, &dscal = t0_.tscal, &dw = t0_.tw;
+  DevBuf<uint8_t>& dst = t0_.status;      // (the front's; stage 2 reuses it)
+  DevBuf<uint32_t>& doff = t0_.dig;       // the decoder's offsets, then the chain's digits, then stage 2's list
+  DevBuf<Aff>& dbase = t0_.tbase;
+  DevBuf<Fr>&dscal = t0_.tscal, &dw = t0_.tw;
   DevBuf<Jac>&dsum = t0_.tres, &dtot = t0_.res;
   DevBuf<int>& dver = t0_.flag;
-  msm_chain_reserve(pl);   // (first: ensure() may free a buffer, and the digits outgrow the 5 count offsets)
-  din.ensure(tp.input_bytes());
-  dst.ensure(6 * count);
-  doff.ensure(5 * count);
-  dpts.ensure(5 * count);
-  dchal.ensure(count);
+  msm_chain_reserve(pl);   // (first: ensure() may free a buffer, and the digits outgrow the front's 5 count offsets)
   dver.ensure(count);
   dbase.ensure(tp.points());
   dscal.ensure(tp.points());
   dw.ensure(tp.weight_scalars());
   dsum.ensure(tp.result_points());
   dtot.ensure(1);
-  uint8_t *d_trk = din.p, *d_kc = din.p + 96 * count, *d_prf = din.p + 144 * count, *d_bad = dst.p + 5 * count;
-  const size_t plane_off[5] = {144 * count, 144 * count + 48, 48, 0, 96 * count}, plane_rec[5] = {128, 128, 96, 96, 48};
-  tracker_point_offsets(count, plane_off, plane_rec, 5, off);
-  CPX_HIP(hipMemcpyAsync(d_trk, trackers, 96 * count, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(d_kc, k_commitments, 48 * count, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(d_prf, proofs, 128 * count, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(doff.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(dw.p, rand, 2 * count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  tick("k_decompress", 0, 5.0 * count);
-  launch_decompress(opt_, din.p, 5 * n, dpts.p, nullptr, dst.p, 1, stream_, doff.p);
-  tock();
-  tick("k_tracker_challenge", 288.0 * count, (double)count);
-  launch_tracker_challenge_verify(din.p, dst.p, n, dchal.p, d_bad, stream_);
-  tock();
+  const TrackerFront f = tracker_front(count, trackers, k_commitments, proofs, host);
+  const uint8_t *d_prf = f.d_prf, *d_bad = f.d_bad;
   tick("k_tracker_check_scalars", (double)(tp.points() * (sizeof(Aff) + sizeof(Fr))), (double)count);
-  launch_tracker_check_scalars(dpts.p, d_prf, dchal.p, d_bad, dw.p, G, n, (int)lp.G, (int)NT, dbase.p, dscal.p, stream_);
+  launch_tracker_check_scalars(f.pts, d_prf, f.chal, d_bad, dw.p, G, n, (int)lp.G, (int)NT, dbase.p, dscal.p, stream_);
   tock();
   msm_chain(pl, lens.data(), dbase.p, dscal.p, dsum.p, tasks);
   bad.resize(count);
@@ -446,7 +426,7 @@ void Engine::tracker_check(size_t count, const uint8_t* trackers, const uint8_t*
     CPX_HIP(hipMemcpyAsync(d_list, list.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemsetAsync(dver.p, 0xff, S * sizeof(int), stream_));   // (-1: not CPX_OK)
     tick("k_tracker_gather", (double)(S * (5 * sizeof(Aff) + 128 + sizeof(Fr))), (double)S);
-    launch_tracker_gather(d_list, (int)S, n, dpts.p, d_prf, dchal.p, dpts2.p, d_prf2, d_chal2, d_bad2, stream_);
+    launch_tracker_gather(d_list, (int)S, n, f.pts, d_prf, f.chal, dpts2.p, d_prf2, d_chal2, d_bad2, stream_);
     tock();
     tick("k_tracker_relations", 0, 2.0 * S);
     launch_tracker_relations(dpts2.p, d_prf2, d_chal2, d_bad2, G, (int)S, dver.p, stream_);
@@ -473,10 +453,9 @@ void Engine::whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, siz
   }
   if (!n_trackers) return;
   if (!find_fits(n_trackers, n_keys)) throw ArgError("find trackers: at most 2^23 trackers, 2^20 keys and 2^32 pairs per call");
-  trackers = canonical_infinities(trackers, 96 * n_trackers, n_trackers, 96, {0, 48});
   std::vector<uint32_t> off;
   std::vector<SmulTask> tasks;
-  std::vector<uint8_t> st;
+  std::vector<uint8_t> st, canon;
   CallScope call(this);
   const FindPlan pl = find_plan(n_trackers, n_keys, opt_.find_table_min_keys, opt_.find_table_mb);
   const size_t n = n_trackers;
@@ -492,15 +471,9 @@ void Engine::whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, siz
   dkeys.ensure(std::max<size_t>(n_keys, 1));
   uint32_t* d_owner = dwords.p + 2 * n;
   const Aff *d_r = dpts.p, *d_claimed = dpts.p + n;
-  const size_t plane_off[2] = {0, 48}, plane_rec[2] = {96, 96};
-  tracker_point_offsets(n, plane_off, plane_rec, 2, off);
-  CPX_HIP(hipMemcpyAsync(din.p, trackers, 96 * n, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(dwords.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
   if (n_keys) CPX_HIP(hipMemcpyAsync(dkeys.p, k, n_keys * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemsetAsync(d_owner, 0xff, n * sizeof(uint32_t), stream_));   // CPX_NO_OWNER
-  tick("k_decompress", 0, 2.0 * n);
-  launch_decompress(opt_, din.p, (int)(2 * n), dpts.p, nullptr, dst.p, 1, stream_, dwords.p);
-  tock();
+  decode_tracker_planes(n, trackers, canon, off, din.p, dwords.p, dpts.p, dst.p);
   DevBuf<TFix> tab;   // table path: one chunk's table, its shifted copies and the build scratch; released when the call ends
   DevBuf<TAff> shift;
   DevBuf<TblTmp> tmp;
@@ -525,14 +498,11 @@ void Engine::whisk_find_trackers(size_t n_trackers, const uint8_t* trackers, siz
     dprod.ensure(n * n_keys);
     dtask.ensure(n_keys);
     // one task per key, the key shared by its n elements; the subgroup-checked decoding is what makes k_smul's endomorphism split valid
-    // (scale_any_point as in Engine::scale)
-    const uint32_t fl = opt_.scale_any_point ? SMUL_PLAIN : 0u;
+    const uint32_t fl = smul_flag();
     tasks.resize(n_keys);
     for (size_t j = 0; j < n_keys; j++) tasks[j] = SmulTask{nullptr, d_r, dprod.p + j * n, dkeys.p + j, 0, fl};
     CPX_HIP(hipMemcpyAsync(dtask.p, tasks.data(), tasks.size() * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
-    tick("k_smul", 224.0 * n * n_keys, (double)n * n_keys);
-    count_smul_quad(launch_smul(dtask.p, (int)n_keys, (int)n, stream_, false, fl ? 0 : opt_.smul_quad_max));
-    tock();
+    smul_tasks(dtask.p, n_keys, n, (double)n * n_keys);
     tick("k_find_compare", (double)sizeof(Aff) * n * n_keys, (double)n * n_keys);
     launch_find_compare(dprod.p, d_claimed, dst.p, n, n_keys, d_owner, stream_);
     tock();
@@ -658,8 +628,8 @@ void Engine::shuffle_device(const ShufflePlan& pl, std::vector<SmulTask>& tasks)
   sh_.stask.ensure(2 * count);
   sh_.mjac.ensure(count);
   const Aff *d_r = sh_.pts.p + pl.point_index(SHP_R, 0, 0), *d_s = sh_.pts.p + pl.point_index(SHP_S, 0, 0);
-  // k R, k S: one task per (item, family), the item's k shared by its ell elements (scale_any_point as in Engine::scale)
-  const uint32_t fl = opt_.scale_any_point ? SMUL_PLAIN : 0u;
+  // k R, k S: one task per (item, family), the item's k shared by its ell elements
+  const uint32_t fl = smul_flag();
   tasks.resize(2 * count);
   for (size_t i = 0; i < count; i++) {
     tasks[2 * i] = SmulTask{nullptr, d_r + i * ell, sh_.kpts.p + i * ell, sh_.fr.p + i, 0, fl};
@@ -667,9 +637,7 @@ void Engine::shuffle_device(const ShufflePlan& pl, std::vector<SmulTask>& tasks)
   }
   CPX_HIP(hipMemcpyAsync(sh_.stask.p, tasks.data(), tasks.size() * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemsetAsync(sh_.mjac.p, 0, count * sizeof(Jac), stream_));   // (Z = 0: the identity, until M is known)
-  tick("k_smul", 224.0 * 2 * pp, 2.0 * pp);
-  count_smul_quad(launch_smul(sh_.stask.p, (int)(2 * count), (int)ell, stream_, false, fl ? 0 : opt_.smul_quad_max));
-  tock();
+  smul_tasks(sh_.stask.p, 2 * count, ell, 2.0 * pp);
   tick("k_shuffle_gather", 6.0 * sizeof(Aff) * pp, (double)pp);
   launch_shuffle_gather(pl, sh_.perm.p, sh_.kpts.p, sh_.kpts.p + pp, sh_.tu.p, sh_.tu.p + pp, sh_.zip.p, stream_);
   tock();
@@ -735,11 +703,11 @@ void Engine::whisk_generate_shuffle_proofs_with(size_t count, const uint8_t* pre
   const ShufflePlan pl(count, ell, false);
   if (!pl.fits()) throw ArgError("shuffle proofs: count * ell exceeds the 32-bit index range of one call");
   if (!states) check_permutations(count, ell, permutation);   // (a row k_rng_draw shuffled from 0..ell is one)
-  const Aff G = generator();   // (before canonical_infinities: its first call decodes, and that shares canon_bytes_; before the scope for the same reason)
+  const Aff G = generator();   // (before the scope, as above)
   const size_t pp = pl.plane_points();
-  pre_trackers = canonical_infinities(pre_trackers, pp * 96, pp, 96, {0, 48});
   std::vector<uint32_t> off;
-  std::vector<uint8_t> bad, dense, mid, end;
+  std::vector<uint8_t> bad, dense, mid, end, canon;
+  pre_trackers = canonical_infinities(pre_trackers, pp * 96, pp, 96, {0, 48}, canon);
   std::vector<SmulTask> tasks;
   CallScope call(this);
   sh_.bytes.ensure(pl.upload_bytes() + 2 * pp * 48);   // pre trackers | post trackers
@@ -759,20 +727,8 @@ void Engine::whisk_generate_shuffle_proofs_with(size_t count, const uint8_t* pre
     rng_.kb.ensure(5 * count);
     mid.resize(count * RNG_STATE_BYTES);
     CPX_HIP(hipMemcpyAsync(rng_.states.p, states, count * RNG_STATE_BYTES, hipMemcpyHostToDevice, stream_));
-    RngDrawArgs a{};
-    a.states = rng_.states.p;
-    a.states_mid = rng_.mid.p;
-    a.mid_phase = 0;
-    a.count = (uint32_t)count;
-    a.shuffle_len = (uint32_t)ell;
-    a.perm = sh_.perm.p;
-    a.nfr = 2;
-    a.fr_cnt[0] = 1;
-    a.fr_out[0] = sh_.fr.p;
-    a.fr_cnt[1] = 4;
-    a.fr_out[1] = sh_.fr.p + count;
     tick("k_rng_draw", (double)(pp * sizeof(uint32_t) + 5 * count * sizeof(Fr)), (double)(5 * count));
-    launch_rng_draw(a, stream_);
+    launch_rng_draw(rng_draw_args(rng_.states.p, rng_.mid.p, count, ell, sh_.perm.p, {{1, sh_.fr.p}, {4, sh_.fr.p + count}}), stream_);
     tock();
     // the prover behind this scope reads them again: out of the scratch set, which the scope's end may trim
     CPX_HIP(hipMemcpyAsync(rng_.perm.p, sh_.perm.p, pp * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream_));
@@ -856,15 +812,8 @@ void Engine::rng_fr(size_t count, uint8_t* states, size_t n_each, uint8_t* out) 
   dfr.ensure(count * n_each);
   st.resize(count * RNG_STATE_BYTES);
   CPX_HIP(hipMemcpyAsync(dst.p, states, st.size(), hipMemcpyHostToDevice, stream_));
-  RngDrawArgs a{};
-  a.states = dst.p;
-  a.mid_phase = -1;
-  a.count = (uint32_t)count;
-  a.nfr = 1;
-  a.fr_cnt[0] = (uint32_t)n_each;
-  a.fr_out[0] = dfr.p;
   tick("k_rng_draw", (double)(count * n_each * sizeof(Fr)), (double)(count * n_each));
-  launch_rng_draw(a, stream_);
+  launch_rng_draw(rng_draw_args(dst.p, nullptr, count, 0, nullptr, {{n_each, dfr.p}}), stream_);
   tock();
   CPX_HIP(hipMemcpyAsync(out, dfr.p, count * n_each * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
   CPX_HIP(hipMemcpyAsync(st.data(), dst.p, st.size(), hipMemcpyDeviceToHost, stream_));
@@ -995,17 +944,8 @@ void Engine::rng_instance_draws(size_t count, uint8_t* states, uint32_t* permuta
     dfr.ensure(count);
     sh_.perm.ensure(count * ell);
     CPX_HIP(hipMemcpyAsync(dst.p, st.data(), st.size(), hipMemcpyHostToDevice, stream_));
-    RngDrawArgs a{};
-    a.states = dst.p;
-    a.mid_phase = -1;
-    a.count = (uint32_t)count;
-    a.shuffle_len = (uint32_t)ell;
-    a.perm = sh_.perm.p;
-    a.nfr = 1;
-    a.fr_cnt[0] = 1;
-    a.fr_out[0] = dfr.p;
     tick("k_rng_draw", (double)(count * (ell * sizeof(uint32_t) + sizeof(Fr))), (double)count);
-    launch_rng_draw(a, stream_);
+    launch_rng_draw(rng_draw_args(dst.p, nullptr, count, ell, sh_.perm.p, {{1, dfr.p}}), stream_);
     tock();
     CPX_HIP(hipMemcpyAsync(perm.data(), sh_.perm.p, perm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
     CPX_HIP(hipMemcpyAsync(k.data(), dfr.p, k.size(), hipMemcpyDeviceToHost, stream_));
@@ -1041,22 +981,8 @@ void Engine::rng_shuffle_draws(size_t count, uint8_t* states, uint32_t* permutat
   st.resize(count * RNG_STATE_BYTES);
   mid.resize(count * RNG_STATE_BYTES);
   CPX_HIP(hipMemcpyAsync(dst.p, states, st.size(), hipMemcpyHostToDevice, stream_));
-  RngDrawArgs a{};
-  a.states = dst.p;
-  a.states_mid = dst.p + st.size();
-  a.mid_phase = 0;
-  a.count = (uint32_t)count;
-  a.shuffle_len = (uint32_t)ell;
-  a.perm = sh_.perm.p;
-  a.nfr = 3;
-  a.fr_cnt[0] = 1;
-  a.fr_out[0] = dfr.p;
-  a.fr_cnt[1] = 4;
-  a.fr_out[1] = dfr.p + count;
-  a.fr_cnt[2] = (uint32_t)nrand;
-  a.fr_out[2] = dfr.p + 5 * count;
   tick("k_rng_draw", (double)(count * (ell * sizeof(uint32_t) + (5 + nrand) * sizeof(Fr))), (double)(count * (5 + nrand)));
-  launch_rng_draw(a, stream_);
+  launch_rng_draw(rng_draw_args(dst.p, dst.p + st.size(), count, ell, sh_.perm.p, {{1, dfr.p}, {4, dfr.p + count}, {nrand, dfr.p + 5 * count}}), stream_);
   tock();
   if (permutation_out) CPX_HIP(hipMemcpyAsync(permutation_out, sh_.perm.p, count * ell * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
   if (k_out) CPX_HIP(hipMemcpyAsync(k_out, dfr.p, count * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
@@ -1120,60 +1046,73 @@ void Engine::whisk_verify_shuffle_proofs_grouped(size_t count, const uint8_t* pr
   whisk_verify_shuffle_proofs_with(count, pre_trackers, post_trackers, proofs, verdict,
                                    [&](const uint8_t* dense, int* v) { batch_verify_grouped(dense, rand, v, n_rechecked); });
 }
-// The shared body: decode the trackers and M, load the count instances, hand the dense proofs to `verify`, override the undecodable items
+// The explicit pre side: its bytes are uploaded and decoded with the rest
 void Engine::whisk_verify_shuffle_proofs_with(size_t count, const uint8_t* pre_trackers, const uint8_t* post_trackers, const uint8_t* proofs, int* verdict,
-                                              const std::function<void(const uint8_t* dense, int* verdict)>& verify) {
-  for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
-  if (!count) return;
-  if (!ell_) throw std::logic_error("set_crs first");
-  const size_t ell = ell_, psz = proof_size(), rec = 48 + psz;
-  const ShufflePlan pl(count, ell, true);
+                                              const ShuffleVerifyFn& verify) {
+  if (!shuffle_verify_begin(count, verdict)) return;
+  const ShufflePlan pl(count, ell_, true);
   if (!pl.fits()) throw ArgError("shuffle proofs: count * ell exceeds the 32-bit index range of one call");
   const Aff G = generator();   // (before the scope, as above)
-  const size_t pp = pl.plane_points(), tb = pl.tracker_bytes();
-  // strict_infinity = 0: non-canonical infinity encodings are rewritten in COPIES of the inputs (canonical_infinities; canon_bytes_ is
-  // reused by the next array, so a rewritten array is kept)
-  std::vector<uint8_t> keep[2];
-  auto canon = [&](const uint8_t* in, size_t nbytes, size_t nrec, size_t stride, const std::vector<size_t>& offs, std::vector<uint8_t>* store) {
-    const uint8_t* p = canonical_infinities(in, nbytes, nrec, stride, offs);
-    if (p == in || !store) return p;
-    store->assign(p, p + nbytes);
-    return (const uint8_t*)store->data();
-  };
-  pre_trackers = canon(pre_trackers, tb, pp, 96, {0, 48}, &keep[0]);
-  post_trackers = canon(post_trackers, tb, pp, 96, {0, 48}, &keep[1]);
-  proofs = canon(proofs, count * rec, count, rec, {0}, nullptr);   // M; the proof points behind it are batch_verify's
-  std::vector<uint8_t> dense(count * psz);                        // CurdleproofsProof::deserialize reads the bytes behind M (whisk.rs:122)
-  for (size_t i = 0; i < count; i++) memcpy(dense.data() + i * psz, proofs + i * rec + 48, psz);
-  std::vector<uint32_t> off;
-  std::vector<uint8_t> bad;
+  ShuffleVerifyHost host;
   CallScope call(this);
-  sh_.bytes.ensure(pl.upload_bytes());
+  shuffle_verify_body(call, host, pl, G, pre_trackers, nullptr, post_trackers, proofs, verdict, verify);
+}
+// What both bodies begin with: the verdict preset and the refusal that needs nothing but the context; false: nothing to verify
+bool Engine::shuffle_verify_begin(size_t count, int* verdict) {
+  for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
+  if (count && !ell_) throw std::logic_error("set_crs first");
+  return count != 0;
+}
+// The shared body, inside the caller's scope (`h`: the caller's, declared above it): decode the trackers and M, load the count instances,
+// hand the dense proofs to `verify`, override the undecodable items.  The pre side is either pre_trackers (src == null), uploaded and
+// decoded in front of post | M into the planes R | S, or the run's source list `src` (pre_trackers == null): then only post | M go up, at
+// offsets that are tracker_bytes() lower, into the planes T | U and the M slots, and k_run_gather fills R | S from the candidate planes
+// and from T | U.  Ends synchronised, the planes still in sh_.pts.
+void Engine::shuffle_verify_body(CallScope& call, ShuffleVerifyHost& h, const ShufflePlan& pl, const Aff& G, const uint8_t* pre_trackers, const uint32_t* src,
+                                 const uint8_t* post_trackers, const uint8_t* proofs, int* verdict, const ShuffleVerifyFn& verify) {
+  const size_t count = pl.count, psz = proof_size(), rec = 48 + psz, pp = pl.plane_points(), tb = pl.tracker_bytes();
+  const size_t first = src ? 2 * pp : 0, skip = src ? tb : 0, npts = pl.points() - first;   // the encodings decoded here, the bytes in front of them that are not uploaded
+  // strict_infinity = 0: non-canonical infinity encodings are rewritten in COPIES of the inputs (canonical_infinities)
+  if (!src) pre_trackers = canonical_infinities(pre_trackers, tb, pp, 96, {0, 48}, h.canon[0]);
+  post_trackers = canonical_infinities(post_trackers, tb, pp, 96, {0, 48}, h.canon[1]);
+  proofs = canonical_infinities(proofs, count * rec, count, rec, {0}, h.canon[2]);   // M; the proof points behind it are batch_verify's
+  h.dense.resize(count * psz);                                                      // CurdleproofsProof::deserialize reads the bytes behind M (whisk.rs:122)
+  for (size_t i = 0; i < count; i++) memcpy(h.dense.data() + i * psz, proofs + i * rec + 48, psz);
+  h.off.resize(npts);
+  for (size_t j = 0; j < npts; j++) h.off[j] = (uint32_t)(pl.src_offset(first + j) - skip);
+  sh_.bytes.ensure(pl.upload_bytes() - skip);
   sh_.status.ensure(pl.points());
-  sh_.off.ensure(pl.points());
+  sh_.off.ensure(npts);
+  if (src) sh_.perm.ensure(3 * pp);   // the source list | the commit list's destinations | its positions
   sh_.pts.ensure(pl.points());
   sh_.bad.ensure(count);
   sh_.mjac.ensure(count);
-  shuffle_point_offsets(pl, off);
-  CPX_HIP(hipMemcpyAsync(sh_.bytes.p, pre_trackers, tb, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(sh_.bytes.p + tb, post_trackers, tb, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpy2DAsync(sh_.bytes.p + 2 * tb, 48, proofs, rec, 48, count, hipMemcpyHostToDevice, stream_));   // the M prefixes only
-  CPX_HIP(hipMemcpyAsync(sh_.off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  tick("k_decompress", 0, (double)pl.points());
-  launch_decompress(opt_, sh_.bytes.p, (int)pl.points(), sh_.pts.p, nullptr, sh_.status.p, 1, stream_, sh_.off.p);
+  uint8_t* d_post = sh_.bytes.p + (tb - skip);
+  if (!src) CPX_HIP(hipMemcpyAsync(sh_.bytes.p, pre_trackers, tb, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(d_post, post_trackers, tb, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpy2DAsync(d_post + tb, 48, proofs, rec, 48, count, hipMemcpyHostToDevice, stream_));   // the M prefixes only
+  CPX_HIP(hipMemcpyAsync(sh_.off.p, h.off.data(), npts * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  if (src) CPX_HIP(hipMemcpyAsync(sh_.perm.p, src, pp * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  tick("k_decompress", 0, (double)npts);
+  launch_decompress(opt_, sh_.bytes.p, (int)npts, sh_.pts.p + first, nullptr, sh_.status.p + first, 1, stream_, sh_.off.p);
   tock();
+  if (src) {
+    tick("k_run_gather", (double)pp * (4 * sizeof(Aff) + 4 + sizeof(uint32_t)), (double)pp);   // two points and two status bytes read and written, one list entry
+    launch_run_gather((uint32_t)pp, (uint32_t)cand_.n, sh_.perm.p, cand_.pts.p, cand_.status.p, sh_.pts.p, sh_.status.p, stream_);
+    tock();
+  }
   tick("k_shuffle_status", 0, (double)count);
   launch_shuffle_status(pl, sh_.status.p, sh_.pts.p, G, nullptr, nullptr, nullptr, sh_.mjac.p, sh_.bad.p, stream_);
   tock();
   const Aff* d = sh_.pts.p;
   load_rows(count, reinterpret_cast<const uint8_t*>(d), reinterpret_cast<const uint8_t*>(d + pp), reinterpret_cast<const uint8_t*>(d + 2 * pp),
             reinterpret_cast<const uint8_t*>(d + 3 * pp), reinterpret_cast<const uint8_t*>(sh_.mjac.p), true);
-  bad.resize(count);
-  CPX_HIP(hipMemcpyAsync(bad.data(), sh_.bad.p, count, hipMemcpyDeviceToHost, stream_));
+  h.bad.resize(count);
+  CPX_HIP(hipMemcpyAsync(h.bad.data(), sh_.bad.p, count, hipMemcpyDeviceToHost, stream_));
   call.finish();
-  verify(dense.data(), verdict);
+  verify(h.dense.data(), verdict);
   for (size_t i = 0; i < count; i++)
-    if (bad[i]) verdict[i] = CPX_ERR_DESERIALIZE;   // an undecodable tracker or M: Err(SerializationError), whatever the placeholder's verdict
+    if (h.bad[i]) verdict[i] = CPX_ERR_DESERIALIZE;   // an undecodable tracker or M: Err(SerializationError), whatever the placeholder's verdict
 }
 
 // ---------------------------------------------------------------- a run of shuffles against the resident candidate list (run.hip, run_plan.hpp)
@@ -1188,15 +1127,9 @@ void Engine::whisk_candidates_load(size_t n, const uint8_t* trackers, uint8_t* s
     cand_.n = 0;
     return;
   }
-  const uint8_t* given = trackers;
-  trackers = canonical_infinities(trackers, n * 96, n, 96, {0, 48});
-  std::vector<uint32_t> off(2 * n);
-  for (size_t i = 0; i < n; i++) {   // plane-major, as the run's own planes: every r_G, then every k_r_G
-    off[i] = (uint32_t)(i * 96);
-    off[n + i] = (uint32_t)(i * 96 + 48);
-  }
-  std::vector<uint8_t> st;
-  std::vector<uint8_t> mirror(given, given + n * 96);
+  std::vector<uint8_t> st, canon;
+  std::vector<uint8_t> mirror(trackers, trackers + n * 96);   // (as given)
+  std::vector<uint32_t> off;
   DevBuf<Aff> pts;   // the new list replaces the old one only once it is complete
   DevBuf<uint8_t> dst;
   {
@@ -1205,11 +1138,7 @@ void Engine::whisk_candidates_load(size_t n, const uint8_t* trackers, uint8_t* s
     dst.ensure(2 * n);
     sh_.bytes.ensure(n * 96);
     sh_.off.ensure(2 * n);
-    CPX_HIP(hipMemcpyAsync(sh_.bytes.p, trackers, n * 96, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(sh_.off.p, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-    tick("k_decompress", 0, (double)(2 * n));
-    launch_decompress(opt_, sh_.bytes.p, (int)(2 * n), pts.p, nullptr, dst.p, 1, stream_, sh_.off.p);
-    tock();
+    decode_tracker_planes(n, trackers, canon, off, sh_.bytes.p, sh_.off.p, pts.p, dst.p);   // plane-major, as the run's own planes
     st.resize(2 * n);
     CPX_HIP(hipMemcpyAsync(st.data(), dst.p, 2 * n, hipMemcpyDeviceToHost, stream_));
     call.finish();
@@ -1242,68 +1171,26 @@ void Engine::whisk_verify_shuffle_run_grouped(size_t count, const uint32_t* indi
   whisk_verify_shuffle_run_with(count, indices, post_trackers, proofs, verdict, n_applied,
                                 [&](const uint8_t* dense, int* v) { batch_verify_grouped(dense, rand, v, n_rechecked); });
 }
-// The shared body.  As whisk_verify_shuffle_proofs_with, except that only the post side and M are uploaded and decoded (planes T | U and the
-// M slots); the planes R | S are gathered from the candidate planes and from T | U through the source list, and the accepted prefix is
-// written back through the commit list as the last step.
+// The pre side comes from the resident list: the planes R | S are gathered from the candidate planes and from T | U through the source
+// list, and the accepted prefix is written back through the commit list as the last step.
 void Engine::whisk_verify_shuffle_run_with(size_t count, const uint32_t* indices, const uint8_t* post_trackers, const uint8_t* proofs, int* verdict, size_t* n_applied,
-                                           const std::function<void(const uint8_t* dense, int* verdict)>& verify) {
-  for (size_t i = 0; i < count; i++) verdict[i] = CPX_ERR_INTERNAL;   // an entry the device never wrote is never read as accepted
+                                           const ShuffleVerifyFn& verify) {
   if (n_applied) *n_applied = 0;
-  if (!count) return;
-  if (!ell_) throw std::logic_error("set_crs first");
+  if (!shuffle_verify_begin(count, verdict)) return;
   if (!cand_.n) throw std::logic_error("cpx_whisk_candidates_load first");
   if (cand_.strict != opt_.strict_infinity) throw std::logic_error("option strict_infinity changed since the candidate list was loaded");
-  const size_t ell = ell_, psz = proof_size(), rec = 48 + psz, n = cand_.n;
+  const size_t ell = ell_, n = cand_.n;
   const ShufflePlan pl(count, ell, true);
   if (!pl.fits()) throw ArgError("shuffle run: count * ell exceeds the 32-bit index range of one call");
   const RunPlan rp(count, ell, n);
   if (!rp.indices_valid(indices)) throw ArgError("shuffle run: an index is outside the candidate list");
-  const Aff G = generator();   // (before canonical_infinities and the scope, as above)
-  const size_t pp = pl.plane_points(), tb = pl.tracker_bytes(), npts = 2 * pp + count;
-  const uint8_t* post_given = post_trackers;   // the list keeps the bytes as the items spelt them
-  std::vector<uint8_t> keep;
-  post_trackers = canonical_infinities(post_trackers, tb, pp, 96, {0, 48});
-  if (post_trackers != post_given) {   // (canon_bytes_ is reused by the next array)
-    keep.assign(post_trackers, post_trackers + tb);
-    post_trackers = keep.data();
-  }
-  proofs = canonical_infinities(proofs, count * rec, count, rec, {0});   // M; the proof points behind it are batch_verify's
-  std::vector<uint8_t> dense(count * psz);
-  for (size_t i = 0; i < count; i++) memcpy(dense.data() + i * psz, proofs + i * rec + 48, psz);
-  std::vector<uint32_t> off(npts), lists(3 * pp), last(n);
-  std::vector<uint8_t> bad;
-  for (size_t j = 0; j < npts; j++) off[j] = (uint32_t)(pl.src_offset(2 * pp + j) - tb);   // the upload holds post | M: the pre side's bytes are not there
+  const Aff G = generator();   // (before the scope, as above)
+  const size_t pp = pl.plane_points();
+  std::vector<uint32_t> lists(3 * pp), last(n);
   rp.resolve(indices, lists.data(), last.data());
+  ShuffleVerifyHost host;
   CallScope call(this);
-  sh_.bytes.ensure(tb + count * 48);
-  sh_.status.ensure(pl.points());
-  sh_.off.ensure(npts);
-  sh_.perm.ensure(3 * pp);   // the source list | the commit list's destinations | its positions
-  sh_.pts.ensure(pl.points());
-  sh_.bad.ensure(count);
-  sh_.mjac.ensure(count);
-  CPX_HIP(hipMemcpyAsync(sh_.bytes.p, post_trackers, tb, hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpy2DAsync(sh_.bytes.p + tb, 48, proofs, rec, 48, count, hipMemcpyHostToDevice, stream_));   // the M prefixes only
-  CPX_HIP(hipMemcpyAsync(sh_.off.p, off.data(), npts * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(sh_.perm.p, lists.data(), pp * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  tick("k_decompress", 0, (double)npts);
-  launch_decompress(opt_, sh_.bytes.p, (int)npts, sh_.pts.p + 2 * pp, nullptr, sh_.status.p + 2 * pp, 1, stream_, sh_.off.p);
-  tock();
-  tick("k_run_gather", (double)pp * (4 * sizeof(Aff) + 4 + sizeof(uint32_t)), (double)pp);   // two points and two status bytes read and written, one list entry
-  launch_run_gather((uint32_t)pp, (uint32_t)n, sh_.perm.p, cand_.pts.p, cand_.status.p, sh_.pts.p, sh_.status.p, stream_);
-  tock();
-  tick("k_shuffle_status", 0, (double)count);
-  launch_shuffle_status(pl, sh_.status.p, sh_.pts.p, G, nullptr, nullptr, nullptr, sh_.mjac.p, sh_.bad.p, stream_);
-  tock();
-  const Aff* d = sh_.pts.p;
-  load_rows(count, reinterpret_cast<const uint8_t*>(d), reinterpret_cast<const uint8_t*>(d + pp), reinterpret_cast<const uint8_t*>(d + 2 * pp),
-            reinterpret_cast<const uint8_t*>(d + 3 * pp), reinterpret_cast<const uint8_t*>(sh_.mjac.p), true);
-  bad.resize(count);
-  CPX_HIP(hipMemcpyAsync(bad.data(), sh_.bad.p, count, hipMemcpyDeviceToHost, stream_));
-  call.finish();
-  verify(dense.data(), verdict);
-  for (size_t i = 0; i < count; i++)
-    if (bad[i]) verdict[i] = CPX_ERR_DESERIALIZE;   // an undecodable tracker or M: Err(SerializationError), whatever the placeholder's verdict
+  shuffle_verify_body(call, host, pl, G, nullptr, lists.data(), post_trackers, proofs, verdict, verify);
   if (!n_applied) return;   // a dry run
   size_t lead = 0;
   while (lead < count && verdict[lead] == CPX_OK) lead++;
@@ -1318,7 +1205,7 @@ void Engine::whisk_verify_shuffle_run_with(size_t count, const uint32_t* indices
     launch_run_commit((uint32_t)len, (uint32_t)pp, (uint32_t)n, sh_.perm.p + pp, sh_.perm.p + 2 * pp, sh_.pts.p, sh_.status.p, cand_.pts.p, cand_.status.p, stream_);
     tock();
     call.finish();
-    for (size_t t = 0; t < len; t++) memcpy(cand_.bytes.data() + (size_t)dst[t] * 96, post_given + (size_t)pos[t] * 96, 96);
+    for (size_t t = 0; t < len; t++) memcpy(cand_.bytes.data() + (size_t)dst[t] * 96, post_trackers + (size_t)pos[t] * 96, 96);   // the list keeps the bytes as the items spelt them
   }
   *n_applied = lead;
 }

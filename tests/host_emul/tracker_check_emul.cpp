@@ -37,6 +37,10 @@ int main(int argc, char** argv) {
       for (size_t g = 0; g < pl.tasks(); g++) printf("group %zu %zu %zu %zu %zu %zu\n", g, pl.lp.group_first(g), pl.lp.group_count(g), pl.task_off(g), pl.task_n(g), pl.gen_slot(g));
       printf("sizes %zu %zu %zu %zu %zu %zu\n", pl.max_n(), pl.points(), pl.input_bytes(), pl.weight_scalars(), pl.result_points(), (size_t)kTrackerCheckMax);
       printf("planes %d %d %d %d %d\n", tck_plane(TCK_K_G), tck_plane(TCK_A), tck_plane(TCK_R_G), tck_plane(TCK_K_R_G), tck_plane(TCK_B));
+      const TrackerInputLayout in = tracker_input_layout(count);
+      printf("layout %zu %zu %zu %zu", in.trackers, in.k_commitments, in.proofs, in.bytes);
+      for (int q = 0; q < TCK_PLANES; q++) printf(" %zu %zu", in.plane_off[q], in.plane_rec[q]);
+      printf("\n");
       return 0;
     }
     for (int i = 4; i < argc; i++) {

@@ -259,3 +259,93 @@ def test_launch_count_does_not_depend_on_the_count(data):
         assert seen[9][1] == {"k_tracker_challenge": 1, "k_tracker_relations": 0, "k_decompress": 1, "k_smul": 1, "k_compress": 1}
     finally:
         c.close()
+
+
+# ---- more than one rewritten array in one call ----
+# Non-canonical encodings of the infinity (compression and infinity flag set, anything else behind them): three different spellings
+NONCANONICAL = (bytes([0xe0]) + bytes(47), bytes([0xc0]) + bytes(46) + b"\x01", b"\xff" * 48)
+_ANSWER = {0: 1, -5: -1}      # CPX_OK, CPX_ERR_DESERIALIZE; anything else a rejection
+
+
+def _oracle_under(orc, strict, ask):
+    orc.set_strict_infinity(bool(strict))
+    try:
+        return ask()
+    finally:
+        orc.set_strict_infinity(False)
+
+
+def _codes(verdict):
+    import curdleproofs_amd as cpx
+    assert cpx.CPX_OK == 0 and cpx.CPX_ERR_DESERIALIZE == -5
+    assert all(v in (cpx.CPX_OK, cpx.CPX_ERR_VERIFY, cpx.CPX_ERR_DESERIALIZE) for v in verdict), list(verdict)
+    return [_ANSWER.get(v, 0) for v in verdict]
+
+
+def test_noncanonical_infinities_in_three_arrays_of_one_call(data, orc):
+    """item 1's r_G (trackers), item 3's k_commitment and item 5's A (proofs) are non-canonical infinities at once: with strict_infinity = 0
+    every one of the three arrays is rewritten in a copy of its own, and all three copies are read by the same call.  Verdicts from the
+    oracle under the same setting; the caller's buffers are left as they were."""
+    import ctypes
+    import curdleproofs_amd as cpx
+    from curdleproofs_amd import whisk
+    count = 8
+    vt, vc, vp = list(data.vt[:count]), list(data.vc[:count]), list(data.vp[:count])
+    assert all(j not in MUTATED for j in range(count))
+    vt[1] = whisk.WhiskTracker(NONCANONICAL[0], vt[1].k_r_G)
+    vc[3] = NONCANONICAL[1]
+    vp[5] = NONCANONICAL[2] + vp[5][48:]
+    want = {s: _oracle_under(orc, s, lambda: [orc.is_valid_whisk_tracker_proof(vt[j].to_bytes(), vc[j], vp[j]) for j in range(count)]) for s in (0, 1)}
+    assert [a != b for a, b in zip(want[0], want[1])] == [j in (1, 3, 5) for j in range(count)]
+    assert [want[1][j] for j in (1, 3, 5)] == [-1] * 3 and -1 not in want[0]
+    tr, kc, pf = b"".join(t.to_bytes() for t in vt), b"".join(vc), b"".join(vp)
+    weights = orc.rng(778).fr(2 * count)
+    for strict, grouped in ((0, False), (1, False), (0, True)):
+        c = cpx.Context(0, options={"strict_infinity": strict, "locate_groups_max": 2})      # grouped: two groups of four items
+        try:
+            b_tr, b_kc, b_pf = cpx._in(tr), cpx._in(kc), cpx._in(pf)
+            verdict = (ctypes.c_int * count)(*([77] * count))
+            if grouped:
+                rechecked = ctypes.c_size_t(0)
+                rc = c._L.cpx_whisk_verify_tracker_proofs_grouped(c._h, count, b_tr, b_kc, b_pf, cpx._in(weights), verdict, ctypes.byref(rechecked))
+            else:
+                rc = c._L.cpx_whisk_verify_tracker_proofs(c._h, count, b_tr, b_kc, b_pf, verdict)
+        finally:
+            c.close()
+        assert rc == cpx.CPX_OK
+        assert _codes(verdict) == want[strict], (strict, grouped, list(verdict))
+        assert (bytes(b_tr), bytes(b_kc), bytes(b_pf)) == (tr, kc, pf)
+
+
+def test_noncanonical_infinities_in_three_arrays_of_one_shuffle_call(orc):
+    """the same for the shuffle verifier at ell = 28: item 0 has a pre tracker, item 1 a post tracker and item 2 an M that is a non-canonical
+    infinity"""
+    import ctypes
+    import curdleproofs_amd as cpx
+    from tests.test_gpu_whisk_shuffle_batch import ELL, _item
+    count = 3
+    crs = orc.generate_crs_points(ELL)
+    rng = orc.rng(20262)
+    items = [_item(orc, ELL, crs, rng) for _ in range(count)]
+    pre, post, proofs = ([it[key] for it in items] for key in ("pre", "post", "proof"))
+    put = lambda blob, at, enc: blob[:at] + enc + blob[at + 48:]
+    pre[0] = put(pre[0], 96 * 3, NONCANONICAL[0])                     # r_G of tracker 3
+    post[1] = put(post[1], 96 * (ELL - 1) + 48, NONCANONICAL[1])      # k_r_G of the last tracker
+    proofs[2] = put(proofs[2], 0, NONCANONICAL[2])
+    vrand = [it["vrand"] for it in items]
+    want = {s: _oracle_under(orc, s, lambda: [orc.is_valid_whisk_shuffle_proof(ELL, crs, pre[j], post[j], proofs[j], vrand[j]) for j in range(count)])
+            for s in (0, 1)}
+    assert want[1] == [-1] * count and -1 not in want[0]
+    b = [b"".join(x) for x in (pre, post, proofs)]
+    for strict in (0, 1):
+        c = cpx.Context(0, options={"strict_infinity": strict})
+        try:
+            c.set_crs(ELL, crs)
+            bufs = [cpx._in(x) for x in b]
+            verdict = (ctypes.c_int * count)(*([77] * count))
+            rc = c._L.cpx_whisk_verify_shuffle_proofs(c._h, count, bufs[0], bufs[1], bufs[2], cpx._in(b"".join(vrand)), verdict)
+        finally:
+            c.close()
+        assert rc == cpx.CPX_OK
+        assert _codes(verdict) == want[strict], (strict, list(verdict))
+        assert [bytes(x) for x in bufs] == b

@@ -146,6 +146,9 @@ def test_task_layout_matches_python_integers(emul, count, groups_max):
     assert sizes == [1 + 5 * G if count else 0, NT + 5 * count, 272 * count, 2 * count, NT, 1 << 21]
     assert want_off == NT + 5 * count <= (1 << 24)
     assert next(ln for ln in lines if ln.startswith("planes")).split()[1:] == ["4", "0", "3", "2", "1"]   # k_decompress leaves A, B, k_r_G, r_G, k_G
+    layout = [int(x) for x in next(ln for ln in lines if ln.startswith("layout")).split()[1:]]
+    assert layout[:4] == [0, 96 * count, 144 * count, 272 * count]           # trackers | k_commitments | proofs
+    assert list(zip(layout[4::2], layout[5::2])) == [(144 * count, 128), (144 * count + 48, 128), (48, 96), (0, 96), (96 * count, 48)]
     if not count:
         return
     # slots: every item of a small batch, the first and last item of every group of a large one
