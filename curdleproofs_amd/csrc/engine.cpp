@@ -2,6 +2,7 @@
 // the group arithmetic exists here; every point operation below is a kernel launch (kernels.hip).
 #include "engine.hpp"
 #include "canon_infinity.hpp"
+#include "host_prove.hpp"
 #include "host_verify.hpp"
 #include <algorithm>
 #include <atomic>
@@ -14,11 +15,7 @@
 namespace cpx {
 
 using host::S;
-using host::S_from_wire;
 using host::SVec;
-using host::Transcript;
-
-static const size_t N_BLINDERS = 4;   // /root/reference/src/lib.rs:35
 
 std::atomic<int>& Engine::live_engines() {
   static std::atomic<int> n{0};
@@ -1060,21 +1057,6 @@ void Engine::batch_load_end() {
 }
 
 // ---------------------------------------------------------------- prover
-namespace {
-struct ProverState {
-  Transcript tr{"curdleproofs"};
-  // the scalars under the names the device-resident prover keeps them by (protocol.h, layout.hpp): the RandIdx row, the vectors V_*
-  // (V_FACT: its first ell entries — the host-driven B is a sum of points, not the commitment form that reads the blinder entries),
-  // the small scalars SC_*
-  SVec rnd;
-  SVec vec[V_COUNT];
-  S sc[SC_COUNT];
-  S k;
-  SVec vec_a, rb_plus_alpha;
-  std::vector<uint8_t> comp;        // compressed bytes of every slot (count * 48)
-};
-}  // namespace
-
 void Engine::batch_prove(const uint32_t* permutation, const uint8_t* k_in, const uint8_t* m_blinders, const uint8_t* rand, uint8_t* proofs_out) {
   if (!B_) throw std::logic_error("batch_load first");
   if (device_prefix(B_)) batch_prove_device(ProveDraws{permutation, k_in, m_blinders, hipMemcpyHostToDevice, rand, nullptr, nullptr}, proofs_out);   // the whole protocol on the GPU (engine_device.cpp)
@@ -1151,20 +1133,14 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   const RandIdx ri((int)n);
   const PtabRow row(n);
   const size_t nrand = ri.count();
-  const int NS = sm.count();
   const size_t NP = np();
-  std::vector<ProverState> st(B);
+  std::vector<host::ProveState> st(B);
   std::vector<uint8_t> comp;
   const int ni = (int)n, Li = (int)L;
   // where a request's scalars are staged from: the proof's host state (make_reqs points the round phases at d_rout_ itself)
   const ScalAt scal = [&](size_t p, const ReqScal& sc) {
-    const ProverState& s = st[p];
+    const host::ProveState& s = st[p];
     return ScalAddr{sc.kind == SCAL_RAND ? &s.rnd[(size_t)sc.at] : sc.kind == SCAL_VEC ? s.vec[sc.at].data() : &s.sc[sc.at], nullptr};
-  };
-  // the compressed results of a phase (request order, in `src`) into the slots its requests name
-  auto take = [&](size_t p, const ReqList& l, const uint8_t* src) {
-    for (int i = 0; i < l.n; i++)
-      if (l.r[i].out >= 0) memcpy(&st[p].comp[(size_t)l.r[i].out * 48], src + (p * (size_t)l.n + i) * 48, 48);
   };
   int side_slots[6];   // R, S and the four T_2 commitments: the side stream's
   side_stream_slots(Li, side_slots);
@@ -1209,24 +1185,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     const uint8_t* mcomp = h_mcomp_.p;
     wait_side();
     parallel_for(B, [&](size_t p) {
-      ProverState& s = st[p];
-      s.rnd.resize(nrand);
-      for (size_t i = 0; i < nrand; i++) s.rnd[i] = S_from_wire(rand + (p * nrand + i) * 32);
-      s.k = S_from_wire(k_in + 32 * p);
-      s.comp.assign((size_t)NS * 48, 0);
-      memcpy(&s.comp[SL_M * 48], &mcomp[p * 48], 48);
-      {   // curdleproofs.rs:78-83
-        const uint8_t* ic = &inst_comp[p * 4 * ell * 48];
-        for (int v = 0; v < 4; v++) s.tr.append_point_vec_bytes("curdleproofs_step1", ic + v * ell * 48, ell);
-        s.tr.append_point_bytes("curdleproofs_step1", &s.comp[SL_M * 48]);
-        s.vec_a = s.tr.get_and_append_challenges("curdleproofs_vec_a", ell);
-      }
-      // the scalars of A: vec_a permuted, then the two vec_a_blinders and two zeros (curdleproofs.rs:85-93)
-      const uint32_t* perm = permutation + p * ell;
-      SVec& ap = s.vec[V_APERM];
-      ap.resize(n);
-      for (size_t i = 0; i < ell; i++) ap[i] = s.vec_a[perm[i]];
-      for (size_t i = 0; i < N_BLINDERS; i++) ap[ell + i] = i < 2 ? s.rnd[ri.AB() + i] : S::zero();
+      host::prove_begin(st[p], ell, L, rand + p * nrand * 32, k_in + 32 * p, permutation + p * ell, &inst_comp[p * 4 * ell * 48], &mcomp[p * 48]);
     });
   }
 
@@ -1252,12 +1211,7 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     MsmTask* ht = reinterpret_cast<MsmTask*>(side_.stage.p + o_tasks);
     uint32_t* hd = reinterpret_cast<uint32_t*>(side_.stage.p + o_dst);   // [nt] destination slots, [nt] addend slots
     parallel_for(B, [&](size_t p) {
-      const S kk = st[p].k, r_k = st[p].rnd[ri.RK()];
-      for (size_t i = 0; i < ell; i++) {
-        hs[p * ell + i] = st[p].vec_a[i].f;
-        hs[total + p * ell + i] = (st[p].vec_a[i] * kk).f;
-        hs[2 * total + p * ell + i] = (st[p].vec_a[i] * r_k).f;
-      }
+      host::prove_side_scalars(st[p], ell, hs + p * ell, hs + total + p * ell, hs + 2 * total + p * ell);
       // tasks [0, 2B): R, S; tasks [2B, 6B): k R, k S, r_k R, r_k S (finalised later, on top of the r H points of phase 1)
       for (int j = 0; j < 6; j++) {
         const size_t t = j < 2 ? 2 * p + j : 2 * B + 4 * p + (j - 2);
@@ -1293,27 +1247,8 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     const ReqList p1 = prove_phase1b(ni, Li).then(prove_phase1(ni, Li));   // A, then what depends on the randomness only
     run_tbl_phase(make_reqs(p1, scal), &comp);
     parallel_for(B, [&](size_t p) {
-      ProverState& s = st[p];
-      take(p, p1, comp.data());
-      // same_permutation_argument.rs:60-83
-      s.tr.append_point_bytes("same_perm_step1", &s.comp[SL_A * 48]);
-      s.tr.append_point_bytes("same_perm_step1", &s.comp[SL_M * 48]);
-      s.tr.append_scalar_vec("same_perm_step1", s.vec_a);
-      s.sc[SC_ALPHA_SP] = s.tr.get_and_append_challenge("same_perm_alpha");
-      s.sc[SC_BETA_SP] = s.tr.get_and_append_challenge("same_perm_beta");
-      const uint32_t* perm = permutation + p * ell;
-      s.vec[V_FACT].resize(ell);
-      s.sc[SC_GPROD] = S::one();
-      for (size_t i = 0; i < ell; i++) {
-        s.vec[V_FACT][i] = s.vec[V_APERM][i] + S::from_u64(perm[i]) * s.sc[SC_ALPHA_SP] + s.sc[SC_BETA_SP];
-        s.sc[SC_GPROD] *= s.vec[V_FACT][i];
-      }
-      // (B = A + alpha M + beta * sum(G) (same_permutation_argument.rs:75-76): the point A of phase 1 plus two single-point terms
-      // with the scalars beta, alpha — G_sum sits in the CRS tables)
-      // the partial products c (grand_product_argument.rs:66-75) need the factors only, so C joins the phase of B and A'
-      s.vec[V_C].assign(1, S::one());
-      for (size_t i = 0; i + 1 < ell; i++) s.vec[V_C].push_back(s.vec[V_C][i] * s.vec[V_FACT][i]);
-      s.vec[V_C].insert(s.vec[V_C].end(), &s.rnd[ri.CB()], &s.rnd[ri.CB()] + N_BLINDERS);   // vec_c_blinders
+      host::take(st[p], p1, &comp[p * (size_t)p1.n * 48]);
+      host::prove_after_phase1(st[p], ell, permutation + p * ell);
     });
   }
 
@@ -1329,60 +1264,14 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   }
 
   // -- P2: B, A' = A + cm_T.T_1 + cm_U.T_1 (curdleproofs.rs:134) as a sum of three points of phase 1, and C = msm(G | Hvec, c)
-  //    (grand_product_argument.rs:76).  The transcript takes B, draws alpha, then takes C: an order of hashing, not of computing.
+  //    (grand_product_argument.rs:76).
   {
     const ReqList p2 = prove_phase2(ni, Li, false);
     CPX_HIP(hipStreamWaitEvent(stream_, tab_.ev_m, 0));   // M's table row (table stream)
     run_tbl_phase(make_reqs(p2, scal), &comp);
     parallel_for(B, [&](size_t p) {
-      ProverState& s = st[p];
-      take(p, p2, comp.data());
-      s.tr.append_point_bytes("gprod_step1", &s.comp[SL_B * 48]);
-      s.tr.append_scalar("gprod_step1", s.sc[SC_GPROD]);
-      s.sc[SC_ALPHA_G] = s.tr.get_and_append_challenge("gprod_alpha");
-      const S mb[4] = {S_from_wire(m_blinders + (p * 4 + 0) * 32), S_from_wire(m_blinders + (p * 4 + 1) * 32),
-                       S_from_wire(m_blinders + (p * 4 + 2) * 32), S_from_wire(m_blinders + (p * 4 + 3) * 32)};
-      const S* ab = &s.vec[V_APERM][ell];   // vec_a_blinders | 0 0
-      s.rb_plus_alpha.resize(N_BLINDERS);
-      for (size_t i = 0; i < N_BLINDERS; i++) s.rb_plus_alpha[i] = (ab[i] + s.sc[SC_ALPHA_SP] * mb[i]) + s.sc[SC_ALPHA_G];
-      s.sc[SC_RP] = host::inner_product(s.rb_plus_alpha.data(), &s.rnd[ri.CB()], N_BLINDERS);
-      s.tr.append_point_bytes("gprod_step2", &s.comp[SL_C * 48]);
-      s.tr.append_scalar("gprod_step2", s.sc[SC_RP]);
-      s.sc[SC_BETA_G] = s.tr.get_and_append_challenge("gprod_beta");
-      s.sc[SC_BETA_G_INV] = s.sc[SC_BETA_G].inverse();
-      s.vec[V_U].resize(n);
-      S pw = s.sc[SC_BETA_G_INV];
-      for (size_t i = 0; i < ell; i++) {
-        s.vec[V_U][i] = pw;
-        pw *= s.sc[SC_BETA_G_INV];
-      }
-      for (size_t i = ell; i < n; i++) s.vec[V_U][i] = pw;
-      s.vec[V_D].resize(n);
-      S pb = s.sc[SC_BETA_G], pbm = S::one();
-      for (size_t i = 0; i < ell; i++) {
-        s.vec[V_D][i] = s.vec[V_FACT][i] * pb - pbm;
-        pbm = pb;
-        pb *= s.sc[SC_BETA_G];
-      }
-      const S beta_l1 = pbm * s.sc[SC_BETA_G], beta_l = pbm;
-      for (size_t i = 0; i < N_BLINDERS; i++) s.vec[V_D][ell + i] = beta_l1 * s.rb_plus_alpha[i];
-      s.sc[SC_ZIP] = s.sc[SC_RP] * beta_l1 + s.sc[SC_GPROD] * beta_l - S::one();
-      // D = B - beta^-1 sum(G) + alpha sum(Hvec) (grand_product_argument.rs:132): the point B plus two single-point terms
-      s.sc[SC_NEG_BETA_G_INV] = -s.sc[SC_BETA_G_INV];
-      // generate_ipa_blinders (inner_product_argument.rs:42-82)
-      const S* r = &s.rnd[ri.IR()];
-      SVec& zz = s.vec[V_ZZ];
-      zz.assign(&s.rnd[ri.IZ()], &s.rnd[ri.IZ()] + n - 2);
-      zz.resize(n);   // (the last two entries are solved for)
-      const S omega = host::inner_product(r, s.vec[V_D].data(), n) + host::inner_product(zz.data(), s.vec[V_C].data(), n - 2);
-      const S delta = host::inner_product(r, zz.data(), n - 2);
-      const S inv_c = s.vec[V_C][n - 2].inverse();
-      const S last_z = (r[n - 2] * inv_c * omega - delta) * ((-r[n - 2]) * inv_c * s.vec[V_C][n - 1] + r[n - 1]).inverse();
-      const S pen_z = (-inv_c) * (last_z * s.vec[V_C][n - 1] + omega);
-      zz[n - 2] = pen_z;
-      zz[n - 1] = last_z;
-      s.vec[V_ZZU].resize(n);                             // B_d = msm(G', r_d) = msm(G, r_d o u)
-      for (size_t i = 0; i < n; i++) s.vec[V_ZZU][i] = zz[i] * s.vec[V_U][i];
+      host::take(st[p], p2, &comp[p * (size_t)p2.n * 48]);
+      host::prove_after_phase2(st[p], ell, m_blinders + p * 4 * 32);
     });
   }
 
@@ -1397,26 +1286,9 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
   {
     const ReqList p3 = prove_phase3(ni, Li);
     run_tbl_phase(make_reqs(p3, scal), &comp);
-    parallel_for(B, [&](size_t p) {
-      ProverState& s = st[p];
-      take(p, p3, comp.data());
-      s.tr.append_point_bytes("ipa_step1", &s.comp[SL_C * 48]);
-      s.tr.append_point_bytes("ipa_step1", &s.comp[sm.D() * 48]);
-      s.tr.append_scalar("ipa_step1", s.sc[SC_ZIP]);
-      s.tr.append_point_bytes("ipa_step1", &s.comp[SL_BC * 48]);
-      s.tr.append_point_bytes("ipa_step1", &s.comp[SL_BD * 48]);
-      s.sc[SC_ALPHA_I] = s.tr.get_and_append_challenge("ipa_alpha");
-      s.sc[SC_BETA_I] = s.tr.get_and_append_challenge("ipa_beta");
-      // the round vectors live on the device from here on: c | d | S_G | S_G' (inner_product_argument.rs:129-148; the fold coefficients
-      // start at 1 and at u)
-      Fr* v = h_rvec_.p + p * 4 * n;
-      for (size_t i = 0; i < n; i++) {
-        v[i] = (s.rnd[ri.IR() + i] + s.sc[SC_ALPHA_I] * s.vec[V_C][i]).f;
-        v[n + i] = (s.vec[V_ZZ][i] + s.sc[SC_ALPHA_I] * s.vec[V_D][i]).f;
-        v[2 * n + i] = S::one().f;
-        v[3 * n + i] = s.vec[V_U][i].f;
-      }
-      h_rgam_.p[p] = s.sc[SC_BETA_I].f;
+    parallel_for(B, [&](size_t p) {   // the round vectors live on the device from here on: c | d | S_G | S_G'
+      host::take(st[p], p3, &comp[p * (size_t)p3.n * 48]);
+      host::prove_ipa_setup(st[p], ell, L, h_rvec_.p + p * 4 * n, h_rgam_.p + p);
     });
     CPX_HIP(hipMemcpyAsync(d_rvec_.p, h_rvec_.p, B * 4 * n * sizeof(Fr), hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(d_rbeta_.p, h_rgam_.p, B * sizeof(Fr), hipMemcpyHostToDevice, stream_));
@@ -1432,14 +1304,8 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     launch_ipa_round_scalars(d_rvec_.p, (int)B, (int)n, (int)half, d_rbeta_.p, d_rout_.p, stream_);
     run_tbl_phase(make_reqs(rd, scal), &comp);
     parallel_for(B, [&](size_t p) {
-      ProverState& s = st[p];
-      take(p, rd, comp.data());
-      int order[4];
-      sm.ipa_round((int)j, order);
-      for (int q : order) s.tr.append_point_bytes("ipa_loop", &s.comp[(size_t)q * 48]);
-      const S gamma = s.tr.get_and_append_challenge("ipa_gamma");
-      h_rgam_.p[2 * p] = gamma.f;
-      h_rgam_.p[2 * p + 1] = gamma.inverse().f;
+      host::take(st[p], rd, &comp[p * (size_t)rd.n * 48]);
+      host::prove_ipa_round(st[p], L, (int)j, h_rgam_.p + 2 * p);
     });
     CPX_HIP(hipMemcpyAsync(d_rgam_.p, h_rgam_.p, B * 2 * sizeof(Fr), hipMemcpyHostToDevice, stream_));
     launch_ipa_round_fold(d_rvec_.p, (int)B, (int)n, (int)half, d_rgam_.p, stream_);
@@ -1453,52 +1319,16 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
 
   // -- P6 (host only): SameScalar transcript, SameMSM step 1
   {
-    std::vector<uint8_t> id_comp(48, 0);
-    id_comp[0] = kCompIdentity;
     wait_side();   // R, S and the four T_2 commitments from the side stream
     {
       HostSpan w(this, "host_wait_device");
       CPX_HIP(hipEventSynchronize(tab_.ev_done));   // the tables of T and U, B_t and B_u from the table stream
     }
     CPX_HIP(hipStreamWaitEvent(stream_, tab_.ev_done, 0));
-    parallel_for(B, [&](size_t p) {
-      ProverState& s = st[p];
-      take(p, p1t, tab_.hcomp.p);   // B_t, B_u
-      memcpy(s.sc[SC_CFIN].f.v, &h_rfin_.p[3 * p], sizeof(Fr));       // c[0], d[0] after the last fold (device-resident vectors)
-      memcpy(s.sc[SC_DFIN].f.v, &h_rfin_.p[3 * p + 1], sizeof(Fr));
-      for (int q : side_slots) memcpy(&s.comp[(size_t)q * 48], side_.hcomp.p + (p * (size_t)CWN + (q - CW0)) * 48, 48);
-      int pts[10];
-      sm.sameexp_points(pts);
-      for (int q : pts) s.tr.append_point_bytes("sameexp_points", &s.comp[(size_t)q * 48]);
-      const S alpha = s.sc[SC_ALPHA_S] = s.tr.get_and_append_challenge("same_scalar_alpha");
-      s.sc[SC_ZK] = s.rnd[ri.RK()] + s.k * alpha;
-      s.sc[SC_ZT] = s.rnd[ri.RA()] + s.rnd[ri.RT()] * alpha;
-      s.sc[SC_ZU] = s.rnd[ri.RB()] + s.rnd[ri.RU()] * alpha;
-      s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.APRIME() * 48]);
-      s.tr.append_point_bytes("same_msm_step1", &s.comp[SL_CMT2 * 48]);
-      s.tr.append_point_bytes("same_msm_step1", &s.comp[SL_CMU2 * 48]);
-      std::vector<uint8_t> vb(n * 48);
-      const uint8_t* ic = &inst_comp[p * 4 * ell * 48];
-      memcpy(vb.data(), ic + 2 * ell * 48, ell * 48);
-      const uint8_t* tailT[4] = {id_comp.data(), id_comp.data(), crs_H_comp_, id_comp.data()};
-      for (int i = 0; i < 4; i++) memcpy(&vb[(ell + i) * 48], tailT[i], 48);
-      s.tr.append_point_vec_bytes("same_msm_step1", vb.data(), n);
-      memcpy(vb.data(), ic + 3 * ell * 48, ell * 48);
-      const uint8_t* tailU[4] = {id_comp.data(), id_comp.data(), id_comp.data(), crs_H_comp_};
-      for (int i = 0; i < 4; i++) memcpy(&vb[(ell + i) * 48], tailU[i], 48);
-      s.tr.append_point_vec_bytes("same_msm_step1", vb.data(), n);
-      s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.BA() * 48]);
-      s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.BT() * 48]);
-      s.tr.append_point_bytes("same_msm_step1", &s.comp[(size_t)sm.BU() * 48]);
-      s.sc[SC_ALPHA_M] = s.tr.get_and_append_challenge("same_msm_alpha");
-      // device-resident round vectors: the witness x = vec_r + alpha (a_sigma | a_blinders 0 0) with r_t, r_u on the last two bases
-      // (same_multiscalar_argument.rs:93-95, curdleproofs.rs:136-143) | the fold coefficients S_M, which start at 1
-      Fr* v = h_rvec_.p + p * 2 * n;
-      for (size_t i = 0; i < n; i++) {
-        const S& w = i + 2 < n ? s.vec[V_APERM][i] : s.rnd[i + 2 == n ? ri.RT() : ri.RU()];
-        v[i] = (s.rnd[ri.VR() + i] + s.sc[SC_ALPHA_M] * w).f;
-        v[n + i] = S::one().f;
-      }
+    parallel_for(B, [&](size_t p) {   // c[0], d[0] after the last fold; the round vectors x | S_M for the device
+      host::take(st[p], p1t, tab_.hcomp.p + p * (size_t)p1t.n * 48);   // B_t, B_u
+      host::take(st[p], side_slots, 6, side_.hcomp.p + p * (size_t)CWN * 48, CW0);
+      host::prove_smsm_setup(st[p], ell, L, h_rfin_.p[3 * p], h_rfin_.p[3 * p + 1], &inst_comp[p * 4 * ell * 48], crs_H_comp_, h_rvec_.p + p * 2 * n);
     });
     CPX_HIP(hipMemcpyAsync(d_rvec_.p, h_rvec_.p, B * 2 * n * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   }
@@ -1510,14 +1340,8 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     launch_smsm_round_scalars(d_rvec_.p, (int)B, (int)n, (int)half, d_rout_.p, stream_);
     run_tbl_phase(make_reqs(rd, scal), &comp);
     parallel_for(B, [&](size_t p) {
-      ProverState& s = st[p];
-      take(p, rd, comp.data());
-      int order[6];
-      sm.same_msm_round((int)j, order);
-      for (int q : order) s.tr.append_point_bytes("same_msm_loop", &s.comp[(size_t)q * 48]);
-      const S gamma = s.tr.get_and_append_challenge("same_msm_gamma");
-      h_rgam_.p[2 * p] = gamma.f;
-      h_rgam_.p[2 * p + 1] = gamma.inverse().f;
+      host::take(st[p], rd, &comp[p * (size_t)rd.n * 48]);
+      host::prove_smsm_round(st[p], L, (int)j, h_rgam_.p + 2 * p);
     });
     CPX_HIP(hipMemcpyAsync(d_rgam_.p, h_rgam_.p, B * 2 * sizeof(Fr), hipMemcpyHostToDevice, stream_));
     launch_smsm_round_fold(d_rvec_.p, (int)B, (int)n, (int)half, d_rgam_.p, stream_);
@@ -1527,38 +1351,12 @@ void Engine::batch_prove_tables(const uint32_t* permutation, const uint8_t* k_in
     }
   }
 
-  if (opt_.trace) {
-    const ProverState& s = st[0];
-    trace_scalar("beta_sp", s.sc[SC_BETA_SP].f);
-    trace_scalar("alpha_sp", s.sc[SC_ALPHA_SP].f);
-    trace_scalar("-beta_g_inv", (-s.sc[SC_BETA_G_INV]).f);
-    trace_scalar("alpha_g", s.sc[SC_ALPHA_G].f);
-    trace_scalar("gprod", s.sc[SC_GPROD].f);
-    trace_scalar("beta_g", s.sc[SC_BETA_G].f);
-    trace_scalar("beta_g_inv", s.sc[SC_BETA_G_INV].f);
-    trace_scalar("r_p", s.sc[SC_RP].f);
-    trace_scalar("z_ip", s.sc[SC_ZIP].f);
-    trace_scalar("alpha_i", s.sc[SC_ALPHA_I].f);
-    trace_scalar("beta_i", s.sc[SC_BETA_I].f);
-    trace_scalar("alpha_m", s.sc[SC_ALPHA_M].f);
-    trace_scalar("z_k", s.sc[SC_ZK].f);
-    trace_scalar("z_t", s.sc[SC_ZT].f);
-    trace_scalar("z_u", s.sc[SC_ZU].f);
-    trace_scalar("c_final", s.sc[SC_CFIN].f);
-    trace_scalar("d_final", s.sc[SC_DFIN].f);
-  }
-  // -- serialise
-  const ProofLayout pl(L);
-  const size_t psz = pl.size();
-  parallel_for(B, [&](size_t p) {
-    const ProverState& s = st[p];
-    uint8_t* o = proofs_out + p * psz;
-    for (int q = 0; q < pl.n_points(); q++) memcpy(o + pl.point_offset(q), &s.comp[(size_t)(SL_A + q) * 48], 48);
-    S xf;   // x[0] after the last fold (device-resident vector)
-    memcpy(xf.f.v, &h_rfin_.p[3 * p + 2], sizeof(Fr));
-    const S* vals[ProofLayout::N_SCALARS] = {&s.sc[SC_RP], &s.sc[SC_CFIN], &s.sc[SC_DFIN], &s.sc[SC_ZK], &s.sc[SC_ZT], &s.sc[SC_ZU], &xf};
-    for (int i = 0; i < ProofLayout::N_SCALARS; i++) vals[i]->to_le_bytes(o + pl.scalar_offset(i));
-  });
+  // -- serialise (x[0] after the last fold: the device-resident vector)
+  const size_t psz = ProofLayout(L).size();
+  parallel_for(B, [&](size_t p) { host::prove_serialize(st[p], L, h_rfin_.p[3 * p + 2], proofs_out + p * psz); });
+  if (opt_.trace)
+    for (int i = 0; i < SC_COUNT; i++)
+      if (kScNames[i]) trace_scalar(kScNames[i], st[0].sc[i].f);
   flush_timers();
 }
 

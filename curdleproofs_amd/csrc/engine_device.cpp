@@ -624,10 +624,8 @@ void Engine::batch_prove_device(const ProveDraws& dr, uint8_t* proofs_out) {
   if (opt_.trace) {   // debugging aid: the challenges and responses of proof 0, same format as the host-driven prover prints
     std::vector<Fr> sc(SC_COUNT);
     CPX_HIP(hipMemcpy(sc.data(), dp.sc.p, SC_COUNT * sizeof(Fr), hipMemcpyDeviceToHost));
-    const char* names[SC_COUNT] = {"beta_sp", "alpha_sp", "-beta_g_inv", "alpha_g", "gprod", "beta_g", "beta_g_inv", "r_p", "z_ip", "alpha_i", "beta_i",
-                                   "alpha_s", "alpha_m", "z_k", "z_t", "z_u", "c_final", "d_final", "x_final"};
     for (int i = 0; i < SC_COUNT; i++)
-      if (names[i]) trace_scalar(names[i], sc[i]);
+      if (kScNames[i]) trace_scalar(kScNames[i], sc[i]);
   }
 }
 

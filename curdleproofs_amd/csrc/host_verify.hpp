@@ -4,7 +4,7 @@
 // work in k_vs_prefix / k_vs_scalars (protocol.hip).  No HIP: the tests compile this for the CPU.
 #pragma once
 #include "check_weights.hpp"
-#include "host_math.hpp"
+#include "host_transcript.hpp"
 
 namespace cpx {
 namespace host {
@@ -22,35 +22,32 @@ struct VerifyState {
   SVec scal[3];
 };
 
+// the 48 bytes of a slot as the verifier has them: M, a proof point, or one of the two points it computed, D and A'
+struct VerifySlots {
+  const uint8_t* pb;
+  ProofLayout pl;
+  SlotMap sm;
+  const uint8_t *mcomp, *d_comp, *aprime_comp;
+  const uint8_t* operator()(int q) const { return q == SL_M ? mcomp : q == sm.D() ? d_comp : q == sm.APRIME() ? aprime_comp : pb + pl.point_offset(q - SL_A); }
+};
+
 // V1a: the proof's scalars, the transcript up to the grand-product beta, the scalars of D.
 // pb: the proof; ic: the compressed instance rows R | S | T | U (ell points each); mcomp: the compressed M.
 inline void verify_prefix(VerifyState& s, size_t ell, size_t L, const uint8_t* pb, const uint8_t* ic, const uint8_t* mcomp) {
   const ProofLayout pl(L);
   s.pb = pb;
-  auto P = [&](int slot_id) { return pb + pl.point_offset(slot_id - SL_A); };
+  const VerifySlots P{pb, pl, SlotMap(L), mcomp, nullptr, nullptr};
   S* vals[ProofLayout::N_SCALARS] = {&s.r_p, &s.c_fin, &s.d_fin, &s.z_k, &s.z_t, &s.z_u, &s.x_fin};
   for (int i = 0; i < ProofLayout::N_SCALARS; i++)
     if (!S::from_le_bytes(pb + pl.scalar_offset(i), vals[i])) s.bad = true;
   // curdleproofs.rs:218: the randomiser must not have wiped the ciphertexts
   if (ic[2 * ell * 48] == kCompIdentity) s.reject = true;
-  for (int v = 0; v < 4; v++) s.tr.append_point_vec_bytes("curdleproofs_step1", ic + v * ell * 48, ell);   // curdleproofs.rs:213-222
-  s.tr.append_point_bytes("curdleproofs_step1", mcomp);
-  s.vec_a = s.tr.get_and_append_challenges("curdleproofs_vec_a", ell);
-  // same_permutation_argument.rs:131-145
-  s.tr.append_point_bytes("same_perm_step1", P(SL_A));
-  s.tr.append_point_bytes("same_perm_step1", mcomp);
-  s.tr.append_scalar_vec("same_perm_step1", s.vec_a);
-  s.alpha_sp = s.tr.get_and_append_challenge("same_perm_alpha");
-  s.beta_sp = s.tr.get_and_append_challenge("same_perm_beta");
-  s.gprod = S::one();
+  s.vec_a = absorb_instance(s.tr, ell, ic, mcomp);
+  same_perm_challenges(s.tr, P, s.vec_a, &s.alpha_sp, &s.beta_sp);
+  s.gprod = S::one();   // same_permutation_argument.rs:139-145
   for (size_t i = 0; i < ell; i++) s.gprod *= s.vec_a[i] + S::from_u64(i) * s.alpha_sp + s.beta_sp;
-  // grand_product_argument.rs:200-209
-  s.tr.append_point_bytes("gprod_step1", P(SL_B));
-  s.tr.append_scalar("gprod_step1", s.gprod);
-  s.alpha_g = s.tr.get_and_append_challenge("gprod_alpha");
-  s.tr.append_point_bytes("gprod_step2", P(SL_C));
-  s.tr.append_scalar("gprod_step2", s.r_p);
-  s.beta_g = s.tr.get_and_append_challenge("gprod_beta");
+  s.alpha_g = gprod_step1(s.tr, P, s.gprod);
+  s.beta_g = gprod_step2(s.tr, P, s.r_p);
   s.beta_g_inv = s.beta_g.inverse();
   s.scal[0] = {S::one(), -s.beta_g_inv, s.alpha_g};    // D = B - beta^-1 sum(G) + alpha sum(H)  (grand_product_argument.rs:223)
 }
@@ -60,62 +57,21 @@ inline void verify_prefix(VerifyState& s, size_t ell, size_t L, const uint8_t* p
 // factors: the proof's random factors in wire form, VF_FUSED_COUNT of them for a fused batch, else VF_COUNT.
 inline void verify_scalars(VerifyState& s, size_t ell, size_t L, const uint8_t* ic, const uint8_t* crs_h_comp, const uint8_t* d_comp, const uint8_t* aprime_comp,
                            const uint8_t* factors, bool fused) {
-  const size_t n = ell + 4;
+  const size_t n = ell + N_BLINDERS;
   const SlotMap sm(L);
   const ProofLayout pl(L);
-  const uint8_t* pb = s.pb;
-  auto P = [&](int slot_id) { return pb + pl.point_offset(slot_id - SL_A); };
-  const S beta_l = s.beta_g.pow_u64(ell), beta_l1 = beta_l * s.beta_g;
-  s.z_ip = s.r_p * beta_l1 + s.gprod * beta_l - S::one();
-  // inner_product_argument.rs:283-290, 202-250
-  s.tr.append_point_bytes("ipa_step1", P(SL_C));
-  s.tr.append_point_bytes("ipa_step1", d_comp);
-  s.tr.append_scalar("ipa_step1", s.z_ip);
-  s.tr.append_point_bytes("ipa_step1", P(SL_BC));
-  s.tr.append_point_bytes("ipa_step1", P(SL_BD));
-  s.alpha_i = s.tr.get_and_append_challenge("ipa_alpha");
-  s.beta_i = s.tr.get_and_append_challenge("ipa_beta");
+  const VerifySlots P{s.pb, pl, sm, nullptr, d_comp, aprime_comp};
+  S beta_l1;
+  s.z_ip = gprod_inner_product(s.r_p, s.gprod, s.beta_g, ell, &beta_l1);
+  ipa_step1(s.tr, sm, P, s.z_ip, &s.alpha_i, &s.beta_i);
   s.gam_i.resize(L);
-  for (size_t j = 0; j < L; j++) {
-    int four[4];
-    sm.ipa_round((int)j, four);
-    for (int q : four) s.tr.append_point_bytes("ipa_loop", P(q));
-    s.gam_i[j] = s.tr.get_and_append_challenge("ipa_gamma");
-  }
+  for (size_t j = 0; j < L; j++) s.gam_i[j] = ipa_round_gamma(s.tr, sm, (int)j, P);
   s.gam_i_inv = s.gam_i;
   batch_inverse(s.gam_i_inv);
-  // same_scalar_argument.rs:112-128
-  int sp[10];
-  sm.sameexp_points(sp);
-  for (int q : sp) s.tr.append_point_bytes("sameexp_points", P(q));
-  s.alpha_s = s.tr.get_and_append_challenge("same_scalar_alpha");
-  // same_multiscalar_argument.rs:229-233, 167-186
-  s.tr.append_point_bytes("same_msm_step1", aprime_comp);
-  s.tr.append_point_bytes("same_msm_step1", P(SL_CMT2));
-  s.tr.append_point_bytes("same_msm_step1", P(SL_CMU2));
-  {
-    std::vector<uint8_t> vb(n * 48, 0);
-    memcpy(vb.data(), ic + 2 * ell * 48, ell * 48);
-    for (int i = 0; i < 4; i++) vb[(ell + i) * 48] = kCompIdentity;
-    memcpy(&vb[(ell + 2) * 48], crs_h_comp, 48);
-    s.tr.append_point_vec_bytes("same_msm_step1", vb.data(), n);
-    std::fill(vb.begin() + ell * 48, vb.end(), 0);
-    memcpy(vb.data(), ic + 3 * ell * 48, ell * 48);
-    for (int i = 0; i < 4; i++) vb[(ell + i) * 48] = kCompIdentity;
-    memcpy(&vb[(ell + 3) * 48], crs_h_comp, 48);
-    s.tr.append_point_vec_bytes("same_msm_step1", vb.data(), n);
-  }
-  s.tr.append_point_bytes("same_msm_step1", P(sm.BA()));
-  s.tr.append_point_bytes("same_msm_step1", P(sm.BT()));
-  s.tr.append_point_bytes("same_msm_step1", P(sm.BU()));
-  s.alpha_m = s.tr.get_and_append_challenge("same_msm_alpha");
+  s.alpha_s = same_scalar_alpha(s.tr, sm, P);
+  s.alpha_m = same_msm_step1(s.tr, sm, P, ell, ic, crs_h_comp);
   s.gam_m.resize(L);
-  for (size_t j = 0; j < L; j++) {
-    int six[6];
-    sm.same_msm_round((int)j, six);
-    for (int q : six) s.tr.append_point_bytes("same_msm_loop", P(q));
-    s.gam_m[j] = s.tr.get_and_append_challenge("same_msm_gamma");
-  }
+  for (size_t j = 0; j < L; j++) s.gam_m[j] = smsm_round_gamma(s.tr, sm, (int)j, P);
   s.gam_m_inv = s.gam_m;
   batch_inverse(s.gam_m_inv);
 
@@ -133,16 +89,8 @@ inline void verify_scalars(VerifyState& s, size_t ell, size_t L, const uint8_t* 
   const SVec s_i = svec(s.gam_i), s_m = svec(s.gam_m);
   SVec s_i_inv = s_i;
   batch_inverse(s_i_inv);
-  // u (grand_product_argument.rs:211-219)
   SVec u(n);
-  {
-    S pw = s.beta_g_inv;
-    for (size_t i = 0; i < ell; i++) {
-      u[i] = pw;
-      pw *= s.beta_g_inv;
-    }
-    for (size_t i = ell; i < n; i++) u[i] = pw;
-  }
+  u_powers(s.beta_g_inv, ell, u.data());
   // ---- flattened accumulated check: one weight per point ----
   CheckTerms<S> t;
   t.alpha_sp = s.alpha_sp, t.beta_sp = s.beta_sp, t.alpha_g = s.alpha_g, t.beta_g_inv = s.beta_g_inv;

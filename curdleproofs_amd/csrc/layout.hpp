@@ -9,6 +9,8 @@
 
 namespace cpx {
 
+static constexpr size_t N_BLINDERS = 4;   // lib.rs:35: n = ell + N_BLINDERS bases, the last four carry the blinders
+
 // ---- per-proof point registry ("slots") that follows the 4*ell instance points in d_pp_ ----
 // CRS singles, M, then every proof point in serialisation order (curdleproofs.rs:300-310), then scratch.
 enum { SL_H = 0, SL_GT, SL_GU, SL_GSUM, SL_HSUM, SL_M, SL_A, SL_CMT1, SL_CMT2, SL_CMU1, SL_CMU2, SL_R, SL_S, SL_B, SL_C, SL_BC, SL_BD, SL_IPA0 };

@@ -21,6 +21,9 @@ enum {
   SC_GPROD, SC_BETA_G, SC_BETA_G_INV, SC_RP, SC_ZIP, SC_ALPHA_I, SC_BETA_I, SC_ALPHA_S, SC_ALPHA_M,
   SC_ZK, SC_ZT, SC_ZU, SC_CFIN, SC_DFIN, SC_XFIN, SC_COUNT = 24
 };
+// the names CPX_TRACE prints them under, for both provers (no name: an unused index)
+static constexpr const char* kScNames[SC_COUNT] = {"beta_sp", "alpha_sp", "-beta_g_inv", "alpha_g", "gprod", "beta_g", "beta_g_inv", "r_p", "z_ip", "alpha_i", "beta_i",
+                                                   "alpha_s", "alpha_m", "z_k", "z_t", "z_u", "c_final", "d_final", "x_final"};
 // vectors of n scalars, vec[p][V_COUNT][n]
 enum { V_APERM = 0, V_FACT, V_C, V_D, V_U, V_ZZ, V_ZZU, V_COUNT };
 

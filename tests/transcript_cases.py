@@ -258,7 +258,7 @@ def helper_records():
 # ---------------------------------------------------------------- the real transcripts' schedule (for the coverage count)
 def proof_schedule(ell):
     """the operations of one Curdleproofs proof transcript for ell ciphertexts (n = ell + 4 = 2^L), as the verifier walks them
-    (curdleproofs_amd/csrc/host_verify.hpp): only lengths and labels matter for the positions, the data is zero"""
+    (curdleproofs_amd/csrc/host_transcript.hpp): only lengths and labels matter for the positions, the data is zero"""
     n = ell + 4
     L = n.bit_length() - 1
     assert 1 << L == n
