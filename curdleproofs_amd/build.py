@@ -22,26 +22,12 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-
          "-Xarch_host", "-march=x86-64-v3", "-Xarch_host", "-madx"]
 
 SELFCHECK = os.path.join(OUT_DIR, "quad_selfcheck")
-# test-only device program: every field and point operation on raw limbs, one kernel each (tests/test_gpu_field.py).  The
-# library does not depend on it: a tree without the tests' source builds libcpx.so alone.
-FIELDCHECK = os.path.join(OUT_DIR, "field_check")
-FIELDCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "field_check.hip")
-# test-only device program: the three transcript implementations at every position of the rate (tests/test_gpu_transcript.py)
-TRANSCRIPTCHECK = os.path.join(OUT_DIR, "transcript_check")
-TRANSCRIPTCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "transcript_check.hip")
-# test-only device program: every function of the scalar-side headers on raw words (tests/test_gpu_scalar.py)
-SCALARCHECK = os.path.join(OUT_DIR, "scalar_check")
-SCALARCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "scalar_check.hip")
-# test-only device program: every function of rng.hpp on raw words (tests/test_gpu_rng.py)
-RNGCHECK = os.path.join(OUT_DIR, "rng_check")
-RNGCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "rng_check.hip")
-# test-only device program: the pieces of G1::rand on raw words (tests/test_gpu_rng_g1.py)
-RNGG1CHECK = os.path.join(OUT_DIR, "rng_g1_check")
-RNGG1CHECK_SRC = os.path.join(HERE, "..", "tests", "device", "rng_g1_check.hip")
-# test-only device program: the MSM wave bodies of msm_body.hpp bucket by bucket and the library's own reducers on crafted sets
-# (tests/test_gpu_msm_waves.py); it calls the launchers of kernels.h, so it is linked against the finished libcpx.so beside it
-MSMCHECK = os.path.join(OUT_DIR, "msm_check")
-MSMCHECK_SRC = os.path.join(HERE, "..", "tests", "device", "msm_check.hip")
+# test-only device programs (tests/device/<name>.hip, one per tests/test_gpu_*.py that names it): every function of a header on raw
+# words.  The library does not depend on them: a tree without the tests' sources builds libcpx.so alone.  A `standalone` program is one
+# hipcc line; the `linked` one calls the launchers of kernels.h, so it is linked against the finished libcpx.so beside it.
+CHECKS = {name: (os.path.join(HERE, "..", "tests", "device", name + ".hip"), kind) for name, kind in (
+    ("field_check", "standalone"), ("transcript_check", "standalone"), ("scalar_check", "standalone"), ("rng_check", "standalone"),
+    ("rng_g1_check", "standalone"), ("msm_check", "linked"))}
 DEVICE_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-I", CSRC]   # the library's device flags
 
 
@@ -52,19 +38,44 @@ def _hipcc():
     raise RuntimeError("hipcc not found: the MI355X core cannot be built (there is no CPU fallback)")
 
 
+def check_path(name):
+    return os.path.join(OUT_DIR, name)
+
+
+def check_source(name):
+    return CHECKS[name][0]
+
+
+# the programs' paths under the names they had before check_path() / check_source(): the tests of the previous commit import them,
+# and those tests are run against this build as they stand
+FIELDCHECK, TRANSCRIPTCHECK, SCALARCHECK, RNGCHECK, RNGG1CHECK, MSMCHECK = (check_path(name) for name in CHECKS)
+MSMCHECK_SRC = check_source("msm_check")
+
+
+def _check_cmds(name, out, lib_dir):
+    """the command lines that make the check program `name` at `out`: the compile (for the linked kind: to out + ".o") and, for the
+    linked kind, the link against the libcpx.so of `lib_dir`"""
+    compile_ = [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS
+    if CHECKS[name][1] == "standalone":
+        return compile_ + [check_source(name), "-o", out], None
+    # libcpx.so carries no soname: the program records the bare file name and finds the library in its own directory
+    return compile_ + ["-c", check_source(name), "-o", out + ".o"], [_hipcc(), "--offload-arch=" + ARCH, out + ".o", "-L", lib_dir, "-lcpx", "-Wl,-rpath,$ORIGIN", "-o", out]
+
+
+def _present_checks():
+    return [name for name in CHECKS if os.path.exists(check_source(name))]
+
+
 def _stale():
-    check = os.path.exists(FIELDCHECK_SRC)
-    tcheck = os.path.exists(TRANSCRIPTCHECK_SRC)
-    scheck = os.path.exists(SCALARCHECK_SRC)
-    rcheck = os.path.exists(RNGCHECK_SRC)
-    mcheck = os.path.exists(MSMCHECK_SRC)
-    gcheck = os.path.exists(RNGG1CHECK_SRC)
-    outs = ([RNGG1CHECK] if gcheck else []) + [LIB] + ([FIELDCHECK] if check else []) + ([TRANSCRIPTCHECK] if tcheck else []) + ([SCALARCHECK] if scheck else []) + ([RNGCHECK] if rcheck else []) + ([MSMCHECK] if mcheck else [])
+    checks = _present_checks()
+    outs = [LIB] + [check_path(c) for c in checks]
     if not all(os.path.exists(o) for o in outs):
         return True
     t = min(os.path.getmtime(o) for o in outs)
-    deps = ([RNGG1CHECK_SRC] if gcheck else []) + [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + ([FIELDCHECK_SRC] if check else []) + ([TRANSCRIPTCHECK_SRC] if tcheck else []) + ([SCALARCHECK_SRC] if scheck else []) + ([RNGCHECK_SRC] if rcheck else []) + ([MSMCHECK_SRC] if mcheck else [])
-    return any(os.path.getmtime(d) > t for d in deps)
+    # what the check programs share, counted where it exists: a check program whose source is complete in itself builds without it
+    harness = os.path.join(HERE, "..", "tests", "device", "check_harness.hpp")
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "cpx.h"), __file__] + [check_source(c) for c in checks]
+    return any(os.path.getmtime(d) > t for d in deps + ([harness] if os.path.exists(harness) else []))
 
 
 def build_variant(name, defines, verbose=False):
@@ -106,30 +117,9 @@ def build(force=False, verbose=False):
                     print(" ".join(cmd))
                 procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
                 objs.append(obj)
-            tmp_check = os.path.join(work, "field_check")   # compiles beside the library's sources
-            check = os.path.exists(FIELDCHECK_SRC)
-            if check:
-                procs.append(("field_check.hip", subprocess.Popen(_fieldcheck_cmd(tmp_check), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-            tmp_tcheck = os.path.join(work, "transcript_check")
-            tcheck = os.path.exists(TRANSCRIPTCHECK_SRC)
-            if tcheck:
-                procs.append(("transcript_check.hip", subprocess.Popen(_transcriptcheck_cmd(tmp_tcheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-            tmp_scheck = os.path.join(work, "scalar_check")
-            scheck = os.path.exists(SCALARCHECK_SRC)
-            if scheck:
-                procs.append(("scalar_check.hip", subprocess.Popen(_scalarcheck_cmd(tmp_scheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-            tmp_rcheck = os.path.join(work, "rng_check")
-            rcheck = os.path.exists(RNGCHECK_SRC)
-            if rcheck:
-                procs.append(("rng_check.hip", subprocess.Popen(_rngcheck_cmd(tmp_rcheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-            tmp_gcheck = os.path.join(work, "rng_g1_check")
-            gcheck = os.path.exists(RNGG1CHECK_SRC)
-            if gcheck:
-                procs.append(("rng_g1_check.hip", subprocess.Popen(_rngg1check_cmd(tmp_gcheck), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-            tmp_mobj, tmp_mcheck = os.path.join(work, "msm_check.o"), os.path.join(work, "msm_check")
-            mcheck = os.path.exists(MSMCHECK_SRC)
-            if mcheck:
-                procs.append(("msm_check.hip", subprocess.Popen(_msmcheck_compile_cmd(tmp_mobj), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
+            checks = {name: _check_cmds(name, os.path.join(work, name), work) for name in _present_checks()}   # compile beside the library's sources
+            for name, (compile_, _) in checks.items():
+                procs.append((name + ".hip", subprocess.Popen(compile_, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
             for src, p in procs:
                 out, _ = p.communicate()
                 if p.returncode != 0:
@@ -139,21 +129,12 @@ def build(force=False, verbose=False):
                     print(out.decode())
             tmp_lib = os.path.join(work, "libcpx.so")
             subprocess.check_call([hipcc, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", tmp_lib] + objs + ["-lpthread"])
-            if mcheck:
-                subprocess.check_call(_msmcheck_link_cmd(tmp_mobj, work, tmp_mcheck))
+            for _, link in checks.values():
+                if link:
+                    subprocess.check_call(link)
             os.replace(tmp_lib, LIB)
-            if mcheck:
-                os.replace(tmp_mcheck, MSMCHECK)
-            if check:
-                os.replace(tmp_check, FIELDCHECK)
-            if tcheck:
-                os.replace(tmp_tcheck, TRANSCRIPTCHECK)
-            if scheck:
-                os.replace(tmp_scheck, SCALARCHECK)
-            if rcheck:
-                os.replace(tmp_rcheck, RNGCHECK)
-            if gcheck:
-                os.replace(tmp_gcheck, RNGG1CHECK)
+            for name in checks:
+                os.replace(os.path.join(work, name), check_path(name))
         finally:
             shutil.rmtree(work, ignore_errors=True)
         build_selfcheck()
@@ -169,106 +150,24 @@ def build_selfcheck():
     return SELFCHECK
 
 
-def _fieldcheck_cmd(out):
-    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [FIELDCHECK_SRC, "-o", out]
-
-
-def build_fieldcheck():
-    """The device build of tests/device/field_check.hip alone (build() compiles it with the library; the host twin is compiled by
-    the tests with g++): cross-compiled here, it travels with the library."""
-    if not os.path.exists(FIELDCHECK_SRC):
-        raise RuntimeError("tests/device/field_check.hip is missing: the device field check cannot be built")
-    os.makedirs(OUT_DIR, exist_ok=True)
-    subprocess.check_call(_fieldcheck_cmd(FIELDCHECK + ".tmp"))
-    os.replace(FIELDCHECK + ".tmp", FIELDCHECK)
-    return FIELDCHECK
-
-
-def _transcriptcheck_cmd(out):
-    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [TRANSCRIPTCHECK_SRC, "-o", out]
-
-
-def build_transcriptcheck():
-    """The device build of tests/device/transcript_check.hip alone (build() compiles it with the library; the host twin is compiled
-    by the tests with g++): cross-compiled here, it travels with the library."""
-    if not os.path.exists(TRANSCRIPTCHECK_SRC):
-        raise RuntimeError("tests/device/transcript_check.hip is missing: the device transcript check cannot be built")
-    os.makedirs(OUT_DIR, exist_ok=True)
-    subprocess.check_call(_transcriptcheck_cmd(TRANSCRIPTCHECK + ".tmp"))
-    os.replace(TRANSCRIPTCHECK + ".tmp", TRANSCRIPTCHECK)
-    return TRANSCRIPTCHECK
-
-
-def _scalarcheck_cmd(out):
-    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [SCALARCHECK_SRC, "-o", out]
-
-
-def build_scalarcheck():
-    """The device build of tests/device/scalar_check.hip alone (build() compiles it with the library; the host twin is compiled by
-    the tests with g++): cross-compiled here, it travels with the library."""
-    if not os.path.exists(SCALARCHECK_SRC):
-        raise RuntimeError("tests/device/scalar_check.hip is missing: the device scalar check cannot be built")
-    os.makedirs(OUT_DIR, exist_ok=True)
-    subprocess.check_call(_scalarcheck_cmd(SCALARCHECK + ".tmp"))
-    os.replace(SCALARCHECK + ".tmp", SCALARCHECK)
-    return SCALARCHECK
-
-
-def _rngcheck_cmd(out):
-    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [RNGCHECK_SRC, "-o", out]
-
-
-def build_rngcheck():
-    """The device build of tests/device/rng_check.hip alone (build() compiles it with the library; the host twin is compiled by the
-    tests with g++): cross-compiled here, it travels with the library."""
-    if not os.path.exists(RNGCHECK_SRC):
-        raise RuntimeError("tests/device/rng_check.hip is missing: the device rng check cannot be built")
-    os.makedirs(OUT_DIR, exist_ok=True)
-    subprocess.check_call(_rngcheck_cmd(RNGCHECK + ".tmp"))
-    os.replace(RNGCHECK + ".tmp", RNGCHECK)
-    return RNGCHECK
-
-
-def _rngg1check_cmd(out):
-    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + [RNGG1CHECK_SRC, "-o", out]
-
-
-def build_rngg1check():
-    """The device build of tests/device/rng_g1_check.hip alone (build() compiles it with the library; the host twin is compiled by the
-    tests with g++): cross-compiled here, it travels with the library."""
-    if not os.path.exists(RNGG1CHECK_SRC):
-        raise RuntimeError("tests/device/rng_g1_check.hip is missing: the device G1 rng check cannot be built")
-    os.makedirs(OUT_DIR, exist_ok=True)
-    subprocess.check_call(_rngg1check_cmd(RNGG1CHECK + ".tmp"))
-    os.replace(RNGG1CHECK + ".tmp", RNGG1CHECK)
-    return RNGG1CHECK
-
-
-def _msmcheck_compile_cmd(obj):
-    return [_hipcc(), "--offload-arch=" + ARCH] + DEVICE_FLAGS + ["-c", MSMCHECK_SRC, "-o", obj]
-
-
-def _msmcheck_link_cmd(obj, lib_dir, out):
-    # libcpx.so carries no soname: the program records the bare file name and finds the library in its own directory
-    return [_hipcc(), "--offload-arch=" + ARCH, obj, "-L", lib_dir, "-lcpx", "-Wl,-rpath,$ORIGIN", "-o", out]
-
-
-def build_msmcheck():
-    """The device build of tests/device/msm_check.hip alone (build() compiles it with the library): cross-compiled here and linked
-    against the libcpx.so beside it, it travels with the library."""
-    if not os.path.exists(MSMCHECK_SRC):
-        raise RuntimeError("tests/device/msm_check.hip is missing: the device MSM check cannot be built")
-    if not os.path.exists(LIB):
+def build_check(name):
+    """The device build of tests/device/<name>.hip alone (build() compiles it with the library; a host twin is compiled by the tests
+    with g++): cross-compiled here, it travels with the library.  The linked kind needs the finished libcpx.so beside it."""
+    if not os.path.exists(check_source(name)):
+        raise RuntimeError("tests/device/%s.hip is missing: the device check cannot be built" % name)
+    if CHECKS[name][1] == "linked" and not os.path.exists(LIB):
         raise RuntimeError("libcpx.so is missing: build the library first")
-    obj = MSMCHECK + ".tmp.o"
+    os.makedirs(OUT_DIR, exist_ok=True)
+    tmp = check_path(name) + ".tmp"
     try:
-        subprocess.check_call(_msmcheck_compile_cmd(obj))
-        subprocess.check_call(_msmcheck_link_cmd(obj, OUT_DIR, MSMCHECK + ".tmp"))
+        for cmd in _check_cmds(name, tmp, OUT_DIR):
+            if cmd:
+                subprocess.check_call(cmd)
     finally:
-        if os.path.exists(obj):
-            os.remove(obj)
-    os.replace(MSMCHECK + ".tmp", MSMCHECK)
-    return MSMCHECK
+        if os.path.exists(tmp + ".o"):
+            os.remove(tmp + ".o")
+    os.replace(tmp, check_path(name))
+    return check_path(name)
 
 
 if __name__ == "__main__":

@@ -6,21 +6,14 @@
 // tests/test_field_check_cpu.py and tests/test_gpu_field.py feed both the same rows and compare the results with each other
 // and with Python integers.  Nothing in curdleproofs_amd/ links it.
 //
-//   field_check IN OUT      runs every record of IN and writes one record per input record to OUT
-//   field_check --list      prints the operation table: name, input words per row, output words per row
+// The command line, the record format, the exit codes and the runner are those of check_harness.hpp; --list prints name, input
+// words per row, output words per row.
 //
-// Record (little-endian): char name[48] (zero-padded) | u32 words per row | u32 reserved (0) | u64 rows | rows x words x u32.
-// An input record carries the operation's input words per row, the output record its output words per row.  Exit code 0 only
-// if every record named a known operation with the right row width and (device build) every HIP call succeeded.
-//
-// Every (operation, body) pair is a type of its own: the kernel template is instantiated once per pair and picked on the
-// host, so each body is compiled on its own as it is inside the product's kernels.
+// Every (operation, body) pair is a type of its own, so each body is compiled on its own as it is inside the product's kernels.
 // Body numbers as in tests/host_emul/f28_redc_bodies.cpp: 0 = schoolbook, 1 = Karatsuba a b columns with the schoolbook
 // reduction, 2 = Karatsuba a b columns and Karatsuba reduction (squares: 0 = schoolbook, 2 = Karatsuba), -1 = the default.
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
+#define CHECK_PROG "field_check"
+#include "check_harness.hpp"
 #include "../../curdleproofs_amd/csrc/mont32.hpp"
 #include "../../curdleproofs_amd/csrc/fp28.hpp"
 #include "../../curdleproofs_amd/csrc/g1_28.hpp"
@@ -58,13 +51,6 @@ CPX_HD void stxyzz(uint32_t* w, const Xyzz28& p) {
   st28(w + 28, p.zz);
   st28(w + 42, p.zzz);
 }
-
-// ---- operations: NI input words, NO output words, run() maps one row ----
-#define OP(NAME, NI_, NO_, ...)                                       \
-  struct NAME {                                                       \
-    static constexpr int NI = NI_, NO = NO_;                          \
-    static CPX_HD void run(const uint32_t* in, uint32_t* out) { __VA_ARGS__ } \
-  };
 
 // fp28.hpp products, every body, inlined (_body) and through the out-of-line register entry
 template <bool K, bool RK> OP(F28MulBody, 28, 14, st28(out, f28_mul_body<K, RK>(ld28(in), ld28(in + 14)));)
@@ -120,56 +106,6 @@ OP(JacDbl, 42, 42, stjac(out, jac28_dbl(ldjac(in)));)
 OP(JacAddMixed, 70, 42, stjac(out, jac28_add_mixed(ldjac(in), ldaff(in + 42)));)
 OP(JacAdd, 84, 42, stjac(out, jac28_add(ldjac(in), ldjac(in + 42)));)
 
-// ---- running one operation over n rows ----
-#if defined(__HIPCC__)
-#define HIPCHECK(x)                                                                  \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      fprintf(stderr, "field_check: %s: %s\n", #x, hipGetErrorString(e_));           \
-      return false;                                                                  \
-    }                                                                                \
-  } while (0)
-
-template <class Op> __global__ __launch_bounds__(64) void k_rows(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n) {
-  const uint64_t row = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  if (row >= n) return;
-  uint32_t a[Op::NI], r[Op::NO];
-  CPX_UNROLL for (int i = 0; i < Op::NI; i++) a[i] = in[row * Op::NI + i];
-  Op::run(a, r);
-  CPX_UNROLL for (int i = 0; i < Op::NO; i++) out[row * Op::NO + i] = r[i];
-}
-template <class Op> static bool run_rows(const uint32_t* in, uint32_t* out, uint64_t n) {
-  if (n == 0) return true;
-  uint32_t *din = nullptr, *dout = nullptr;
-  HIPCHECK(hipMalloc(&din, n * Op::NI * sizeof(uint32_t)));
-  HIPCHECK(hipMalloc(&dout, n * Op::NO * sizeof(uint32_t)));
-  HIPCHECK(hipMemcpy(din, in, n * Op::NI * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIPCHECK(hipMemset(dout, 0xa5, n * Op::NO * sizeof(uint32_t)));
-  hipLaunchKernelGGL(k_rows<Op>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, din, dout, n);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipDeviceSynchronize());
-  HIPCHECK(hipMemcpy(out, dout, n * Op::NO * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIPCHECK(hipFree(din));
-  HIPCHECK(hipFree(dout));
-  return true;
-}
-static const char* const BUILD = "device";
-#else
-template <class Op> static bool run_rows(const uint32_t* in, uint32_t* out, uint64_t n) {
-  for (uint64_t i = 0; i < n; i++) Op::run(in + i * Op::NI, out + i * Op::NO);
-  return true;
-}
-static const char* const BUILD = "host";
-#endif
-
-struct Entry {
-  const char* name;
-  int ni, no;
-  bool (*run)(const uint32_t*, uint32_t*, uint64_t);
-};
-template <class Op> static Entry entry(const char* name) { return Entry{name, Op::NI, Op::NO, run_rows<Op>}; }
-
 static const Entry TABLE[] = {
     entry<F28MulBody<false, false>>("f28_mul_body/0"), entry<F28MulBody<true, false>>("f28_mul_body/1"),
     entry<F28MulBody<true, true>>("f28_mul_body/2"), entry<F28MulBodyDef>("f28_mul_body/-1"),
@@ -199,59 +135,4 @@ static const Entry TABLE[] = {
     entry<JacDbl>("jac28_dbl"), entry<JacAddMixed>("jac28_add_mixed"), entry<JacAdd>("jac28_add"),
 };
 
-struct Header {
-  char name[48];
-  uint32_t words, reserved;
-  uint64_t rows;
-};
-static_assert(sizeof(Header) == 64, "record header layout");
-
-int main(int argc, char** argv) {
-  if (argc == 2 && !strcmp(argv[1], "--list")) {
-    for (const Entry& e : TABLE) printf("%s %d %d\n", e.name, e.ni, e.no);
-    return 0;
-  }
-  if (argc != 3) {
-    fprintf(stderr, "usage: field_check IN OUT | field_check --list\n");
-    return 2;
-  }
-  FILE* fi = fopen(argv[1], "rb");
-  FILE* fo = fopen(argv[2], "wb");
-  if (!fi || !fo) {
-    fprintf(stderr, "field_check: cannot open %s\n", fi ? argv[2] : argv[1]);
-    return 2;
-  }
-  Header h;
-  size_t records = 0, rows = 0, got;
-  while ((got = fread(&h, 1, sizeof h, fi)) == sizeof h) {
-    h.name[sizeof h.name - 1] = 0;
-    const Entry* op = nullptr;
-    for (const Entry& e : TABLE)
-      if (!strcmp(e.name, h.name)) op = &e;
-    if (!op || h.words != (uint32_t)op->ni || h.rows > (1u << 24)) {
-      fprintf(stderr, "field_check: bad record '%s' (%u words per row, %llu rows)\n", h.name, h.words, (unsigned long long)h.rows);
-      return 3;
-    }
-    std::vector<uint32_t> in((size_t)h.rows * op->ni), out((size_t)h.rows * op->no);
-    if (fread(in.data(), sizeof(uint32_t), in.size(), fi) != in.size()) {
-      fprintf(stderr, "field_check: record '%s' is truncated\n", h.name);
-      return 3;
-    }
-    if (!op->run(in.data(), out.data(), h.rows)) return 4;
-    h.words = (uint32_t)op->no;
-    if (fwrite(&h, 1, sizeof h, fo) != sizeof h || fwrite(out.data(), sizeof(uint32_t), out.size(), fo) != out.size()) {
-      fprintf(stderr, "field_check: cannot write %s\n", argv[2]);
-      return 2;
-    }
-    records++;
-    rows += h.rows;
-  }
-  if (got != 0) {
-    fprintf(stderr, "field_check: trailing bytes after the last record\n");
-    return 3;
-  }
-  if (fclose(fo) != 0) return 2;
-  fclose(fi);
-  printf("field_check (%s): %zu records, %zu rows\n", BUILD, records, rows);
-  return 0;
-}
+int main(int argc, char** argv) { return rows_main(argc, argv, TABLE); }

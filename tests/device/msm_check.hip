@@ -3,34 +3,23 @@
 // tests/msm_check_lib.py plus the oracle.  The bodies are wrapped in kernels of this file with the library's launch bounds and dynamic
 // LDS sizes; the reducers, the finalisation and the Horner tail are the library's own (libcpx.so, kernels.h), on crafted inputs.
 //
-//   msm_check IN OUT      runs every record of IN and writes one record per input record to OUT
-//   msm_check --list      prints the operation table: name, group
+// The command line, the exit codes and the record loop are those of check_harness.hpp; --list prints name, group.
 //
 // Record (little-endian): char name[48] (zero-padded) | u32 1 | u32 reserved (0) | u64 words | words x u32 — the record format of
-// field_check.hip with one word per row; the payload of every operation is described beside its runner.  Points enter as standard-form
+// check_harness.hpp with one word per row; the payload of every operation is described beside its runner.  Points enter as standard-form
 // words (Aff: 24, Jac: 36) and are converted on the host (t_from_std); raw-set entries leave as standard-form Jacobian points
 // (t_acc_to_jac, t_jac_to_std) followed by a flag word (bit 0: the raw entry is the identity, bit 1: it still holds the poison).
 // A "pool" record holds the points the later records of the file name by index; a reference is a pool index, bit 31 set for the
 // negated point, ~0u for the identity.
 // Every HIP call is checked: on an error the program stops with a nonzero status and starts no further kernel.  Every index of a case
 // is checked against the size of what it addresses before anything is launched (exit 3).
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <string>
-#include <vector>
+#define CHECK_PROG "msm_check"
+#include "check_harness.hpp"
 #include "../../curdleproofs_amd/csrc/msm_body.hpp"
 
 using namespace cpx;
 
-#define HIPCHECK(x)                                                          \
-  do {                                                                       \
-    hipError_t e_ = (x);                                                     \
-    if (e_ != hipSuccess) {                                                  \
-      fprintf(stderr, "msm_check: %s: %s\n", #x, hipGetErrorString(e_));     \
-      return false;                                                          \
-    }                                                                        \
-  } while (0)
 #define REQUIRE(c)                                                           \
   do {                                                                       \
     if (!(c)) {                                                              \
@@ -617,12 +606,12 @@ static bool run_tail(const std::string& name, Reader& r, std::vector<uint32_t>& 
   return true;
 }
 
-struct Entry {
+struct MsmEntry {
   const char* name;
   const char* group;
   bool (*run)(const std::string&, Reader&, std::vector<uint32_t>&);
 };
-static const Entry TABLE[] = {
+static const MsmEntry TABLE[] = {
     {"pool", "pool", run_pool},
     // tbw_sort<WPW, PERWIN, NBINS, CACHE> as msm_tblw_body instantiates it for the kernels the library launches
     {"sort/2,0,128", "sort", run_sort<2, false, 128>},
@@ -663,62 +652,27 @@ static const Entry TABLE[] = {
     {"tail/lanes", "finalize", run_tail},
 };
 
-struct Header {
-  char name[48];
-  uint32_t words, reserved;
-  uint64_t rows;
-};
-static_assert(sizeof(Header) == 64, "record header layout");
+static const MsmEntry* find_op(const char* name) {
+  const MsmEntry* op = nullptr;
+  for (const MsmEntry& e : TABLE)
+    if (!strcmp(e.name, name)) op = &e;
+  return op;
+}
 
 int main(int argc, char** argv) {
-  if (argc == 2 && !strcmp(argv[1], "--list")) {
-    for (const Entry& e : TABLE) printf("%s %s\n", e.name, e.group);
-    return 0;
-  }
-  if (argc != 3) {
-    fprintf(stderr, "usage: msm_check IN OUT | msm_check --list\n");
-    return 2;
-  }
-  FILE* fi = fopen(argv[1], "rb");
-  FILE* fo = fopen(argv[2], "wb");
-  if (!fi || !fo) {
-    fprintf(stderr, "msm_check: cannot open %s\n", fi ? argv[2] : argv[1]);
-    return 2;
-  }
-  Header h;
-  size_t records = 0, got;
-  while ((got = fread(&h, 1, sizeof h, fi)) == sizeof h) {
-    h.name[sizeof h.name - 1] = 0;
-    const Entry* op = nullptr;
-    for (const Entry& e : TABLE)
-      if (!strcmp(e.name, h.name)) op = &e;
-    if (!op || h.words != 1 || h.rows > MAX_WORDS) {
-      fprintf(stderr, "msm_check: bad record '%s' (%u words per row, %llu rows)\n", h.name, h.words, (unsigned long long)h.rows);
-      return 3;
-    }
-    std::vector<uint32_t> in((size_t)h.rows), out;
-    if (fread(in.data(), sizeof(uint32_t), in.size(), fi) != in.size()) {
-      fprintf(stderr, "msm_check: record '%s' is truncated\n", h.name);
-      return 3;
-    }
-    Reader r{in.data(), in.size()};
-    if (!op->run(h.name, r, out)) {
-      fprintf(stderr, "msm_check: record %zu '%s' failed\n", records, h.name);
-      return g_bad_case ? 3 : 4;
-    }
-    h.rows = out.size();
-    if (fwrite(&h, 1, sizeof h, fo) != sizeof h || fwrite(out.data(), sizeof(uint32_t), out.size(), fo) != out.size()) {
-      fprintf(stderr, "msm_check: cannot write %s\n", argv[2]);
-      return 2;
-    }
-    records++;
-  }
-  if (got != 0) {
-    fprintf(stderr, "msm_check: trailing bytes after the last record\n");
-    return 3;
-  }
-  if (fclose(fo) != 0) return 2;
-  fclose(fi);
-  printf("msm_check (device): %zu records\n", records);
-  return 0;
+  return check_main(
+      argc, argv, false,
+      [] {
+        for (const MsmEntry& e : TABLE) printf("%s %s\n", e.name, e.group);
+      },
+      [](const Header& h) -> int64_t { return find_op(h.name) && h.words == 1 && h.rows <= MAX_WORDS ? (int64_t)h.rows : -1; },
+      [](Header& h, std::vector<uint32_t>& in, std::vector<uint32_t>& out, const CheckLoop& loop) -> int {
+        Reader r{in.data(), in.size()};
+        if (!find_op(h.name)->run(h.name, r, out)) {   // (never null: the payload callback has accepted the name)
+          fprintf(stderr, "msm_check: record %zu '%s' failed\n", loop.records, h.name);
+          return g_bad_case ? CHECK_BAD : CHECK_FAILED;
+        }
+        h.rows = out.size();
+        return CHECK_OK;
+      });
 }

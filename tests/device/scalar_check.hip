@@ -6,16 +6,10 @@
 // tests/test_scalar_check_cpu.py and tests/test_gpu_scalar.py feed both the same rows (tests/scalar_cases.py) and compare the results
 // with each other and with Python integers (tests/scalar_check_lib.py).  Nothing in curdleproofs_amd/ links it.
 //
-//   scalar_check IN OUT      runs every record of IN and writes one record per input record to OUT
-//   scalar_check --list      prints the operation table: name, input words per row, output words per row
-//
-// Record (little-endian): char name[48] (zero-padded) | u32 words per row | u32 reserved (0) | u64 rows | rows x words x u32: the
-// format of field_check.hip.  Rows are u32 words; narrow digits (int8_t, int16_t, int) travel one per word, sign-extended.  Exit code 0
-// only if every record named a known operation with the right row width and (device build) every HIP call succeeded.
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
+// The command line, the record format, the exit codes and the runner are those of check_harness.hpp; --list prints name, input words
+// per row, output words per row.  Rows are u32 words; narrow digits (int8_t, int16_t, int) travel one per word, sign-extended.
+#define CHECK_PROG "scalar_check"
+#include "check_harness.hpp"
 #include "../../curdleproofs_amd/csrc/mont32.hpp"
 #include "../../curdleproofs_amd/csrc/glv.hpp"
 #include "../../curdleproofs_amd/csrc/recode.hpp"
@@ -41,13 +35,6 @@ CPX_HD void st_naf(uint32_t* w, const SmulNaf& o) {           // nz[0], nz[1], n
       w[10 + 5 * h + i] = o.ng[h][i];
     }
 }
-
-// ---- operations: NI input words, NO output words, run() maps one row ----
-#define OP(NAME, NI_, NO_, ...)                                       \
-  struct NAME {                                                       \
-    static constexpr int NI = NI_, NO = NO_;                          \
-    static CPX_HD void run(const uint32_t* in, uint32_t* out) { __VA_ARGS__ } \
-  };
 
 // glv.hpp
 OP(GlvSplit, 8, 10, uint32_t nk, nt; glv_split(in, out, out + 4, nk, nt); out[8] = nk; out[9] = nt;)
@@ -111,56 +98,6 @@ OP(WordsInvModP, 12, 12, words_inv_mod_p(in, out);)
 OP(FpInvEuclid, 12, 12, stfe<FpCfg>(out, fe_inv_euclid(ldfe<FpCfg>(in)));)
 template <class C> OP(FeRawGt, 2 * C::N, 1, out[0] = fe_raw_gt(ldfe<C>(in), ldfe<C>(in + C::N)) ? 1u : 0u;)
 
-// ---- running one operation over n rows ----
-#if defined(__HIPCC__)
-#define HIPCHECK(x)                                                                  \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      fprintf(stderr, "scalar_check: %s: %s\n", #x, hipGetErrorString(e_));          \
-      return false;                                                                  \
-    }                                                                                \
-  } while (0)
-
-template <class Op> __global__ __launch_bounds__(64) void k_rows(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n) {
-  const uint64_t row = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  if (row >= n) return;
-  uint32_t a[Op::NI], r[Op::NO];
-  CPX_UNROLL for (int i = 0; i < Op::NI; i++) a[i] = in[row * Op::NI + i];
-  Op::run(a, r);
-  for (int i = 0; i < Op::NO; i++) out[row * Op::NO + i] = r[i];
-}
-template <class Op> static bool run_rows(const uint32_t* in, uint32_t* out, uint64_t n) {
-  if (n == 0) return true;
-  uint32_t *din = nullptr, *dout = nullptr;
-  HIPCHECK(hipMalloc(&din, n * Op::NI * sizeof(uint32_t)));
-  HIPCHECK(hipMalloc(&dout, n * Op::NO * sizeof(uint32_t)));
-  HIPCHECK(hipMemcpy(din, in, n * Op::NI * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIPCHECK(hipMemset(dout, 0xa5, n * Op::NO * sizeof(uint32_t)));
-  hipLaunchKernelGGL(k_rows<Op>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, din, dout, n);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipDeviceSynchronize());
-  HIPCHECK(hipMemcpy(out, dout, n * Op::NO * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIPCHECK(hipFree(din));
-  HIPCHECK(hipFree(dout));
-  return true;
-}
-static const char* const BUILD = "device";
-#else
-template <class Op> static bool run_rows(const uint32_t* in, uint32_t* out, uint64_t n) {
-  for (uint64_t i = 0; i < n; i++) Op::run(in + i * Op::NI, out + i * Op::NO);
-  return true;
-}
-static const char* const BUILD = "host";
-#endif
-
-struct Entry {
-  const char* name;
-  int ni, no;
-  bool (*run)(const uint32_t*, uint32_t*, uint64_t);
-};
-template <class Op> static Entry entry(const char* name) { return Entry{name, Op::NI, Op::NO, run_rows<Op>}; }
-
 static const Entry TABLE[] = {
     entry<GlvSplit>("glv_split"), entry<GlvBiasedBytes>("glv_biased_bytes"),
     entry<RecodeSigned16>("recode_signed16"), entry<RecodeSigned16Stride>("recode_signed16/stride3"), entry<RecodeNaf>("recode_naf"),
@@ -182,59 +119,4 @@ static const Entry TABLE[] = {
     entry<FeRawGt<FrCfg>>("fr_raw_gt"),
 };
 
-struct Header {
-  char name[48];
-  uint32_t words, reserved;
-  uint64_t rows;
-};
-static_assert(sizeof(Header) == 64, "record header layout");
-
-int main(int argc, char** argv) {
-  if (argc == 2 && !strcmp(argv[1], "--list")) {
-    for (const Entry& e : TABLE) printf("%s %d %d\n", e.name, e.ni, e.no);
-    return 0;
-  }
-  if (argc != 3) {
-    fprintf(stderr, "usage: scalar_check IN OUT | scalar_check --list\n");
-    return 2;
-  }
-  FILE* fi = fopen(argv[1], "rb");
-  FILE* fo = fopen(argv[2], "wb");
-  if (!fi || !fo) {
-    fprintf(stderr, "scalar_check: cannot open %s\n", fi ? argv[2] : argv[1]);
-    return 2;
-  }
-  Header h;
-  size_t records = 0, rows = 0, got;
-  while ((got = fread(&h, 1, sizeof h, fi)) == sizeof h) {
-    h.name[sizeof h.name - 1] = 0;
-    const Entry* op = nullptr;
-    for (const Entry& e : TABLE)
-      if (!strcmp(e.name, h.name)) op = &e;
-    if (!op || h.words != (uint32_t)op->ni || h.rows > (1u << 24)) {
-      fprintf(stderr, "scalar_check: bad record '%s' (%u words per row, %llu rows)\n", h.name, h.words, (unsigned long long)h.rows);
-      return 3;
-    }
-    std::vector<uint32_t> in((size_t)h.rows * op->ni), out((size_t)h.rows * op->no);
-    if (fread(in.data(), sizeof(uint32_t), in.size(), fi) != in.size()) {
-      fprintf(stderr, "scalar_check: record '%s' is truncated\n", h.name);
-      return 3;
-    }
-    if (!op->run(in.data(), out.data(), h.rows)) return 4;
-    h.words = (uint32_t)op->no;
-    if (fwrite(&h, 1, sizeof h, fo) != sizeof h || fwrite(out.data(), sizeof(uint32_t), out.size(), fo) != out.size()) {
-      fprintf(stderr, "scalar_check: cannot write %s\n", argv[2]);
-      return 2;
-    }
-    records++;
-    rows += h.rows;
-  }
-  if (got != 0) {
-    fprintf(stderr, "scalar_check: trailing bytes after the last record\n");
-    return 3;
-  }
-  if (fclose(fo) != 0) return 2;
-  fclose(fi);
-  printf("scalar_check (%s): %zu records, %zu rows\n", BUILD, records, rows);
-  return 0;
-}
+int main(int argc, char** argv) { return rows_main(argc, argv, TABLE); }

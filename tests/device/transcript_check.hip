@@ -5,11 +5,9 @@
 // tests/test_transcript_check_cpu.py and tests/test_gpu_transcript.py feed both the same cases and compare the results with each other
 // and with tests/strobe_ref.py.  Nothing in curdleproofs_amd/ links it.
 //
-//   transcript_check IN OUT      runs every record of IN and writes one record per input record to OUT
-//   transcript_check --list      prints the table: name, input words per row, output words per row (0 0 for an engine)
-//
-// Record (little-endian): char name[48] (zero-padded) | u32 words per row | u32 reserved (0) | u64 rows, then
-//   helper operation: rows x words x u32 (the output record carries the output words per row)
+// The command line, the record header, the exit codes and the record loop are those of check_harness.hpp; --list prints name, input
+// words per row, output words per row (0 0 for an engine).  After the header:
+//   helper operation: rows x words x u32, a row operation of the harness
 //   engine (words = 0): `rows` cases, each
 //       u32 nops | u32 blob bytes | u32 message offset (0..15) | u32 reserved (0) | 27 x u64 start state (25 words, pos, pos_begin)
 //       nops x { u32 code, a, b, c } | the blob, zero-padded to a multiple of 8 bytes
@@ -35,11 +33,8 @@
 // The device engines place a case's blob at (16-byte boundary + message offset), so that LaneStrobe's aligned 8-byte read and its
 // byte-wise path both run.  Exit code 0 only if every record was well formed (known name, offsets inside the blob, labels without NUL
 // and shorter than 64 bytes, pos <= 165, pos_begin <= 166) and (device build) every HIP call succeeded.
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#include "../../curdleproofs_amd/csrc/mont32.hpp"
+#define CHECK_PROG "transcript_check"
+#include "check_harness.hpp"
 #include "../../curdleproofs_amd/csrc/strobe.hpp"
 #include "../../curdleproofs_amd/csrc/bit_interleave.hpp"
 #if defined(__HIPCC__)
@@ -159,15 +154,6 @@ static bool run_strobe_host(Batch& b) {
 }
 
 #if defined(__HIPCC__)
-#define HIPCHECK(x)                                                                  \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      fprintf(stderr, "transcript_check: %s: %s\n", #x, hipGetErrorString(e_));      \
-      return false;                                                                  \
-    }                                                                                \
-  } while (0)
-
 struct WaveEngine {
   WaveStrobe t;
   uint8_t* scratch;   // 64 bytes of LDS, as the product's kernels pass
@@ -331,81 +317,31 @@ static bool run_device(Batch& b, int engine, const std::vector<uint32_t>& blob_l
   HIPCHECK(hipFree(d_chal));
   return true;
 }
-static const char* const BUILD = "device";
-#else
-static const char* const BUILD = "host";
 #endif
 
 // ---- the bit helpers as row operations ----
-#define ROWOP(NAME, NI_, NO_, ...)                                    \
-  struct NAME {                                                       \
-    static constexpr int NI = NI_, NO = NO_;                          \
-    static CPX_HD void run(const uint32_t* in, uint32_t* out) { __VA_ARGS__ } \
-  };
-ROWOP(Unshuffle32, 1, 1, out[0] = bits_unshuffle32(in[0]);)
-ROWOP(Shuffle32, 1, 1, out[0] = bits_shuffle32(in[0]);)
-ROWOP(Split64, 2, 2, bits_split64((uint64_t)in[0] | ((uint64_t)in[1] << 32), out[0], out[1]);)                       // (lo, hi) -> (even, odd)
-ROWOP(Join64, 2, 2, const uint64_t v = bits_join64(in[0], in[1]); out[0] = (uint32_t)v; out[1] = (uint32_t)(v >> 32);)   // (even, odd) -> (lo, hi)
+OP(Unshuffle32, 1, 1, out[0] = bits_unshuffle32(in[0]);)
+OP(Shuffle32, 1, 1, out[0] = bits_shuffle32(in[0]);)
+OP(Split64, 2, 2, bits_split64((uint64_t)in[0] | ((uint64_t)in[1] << 32), out[0], out[1]);)                       // (lo, hi) -> (even, odd)
+OP(Join64, 2, 2, const uint64_t v = bits_join64(in[0], in[1]); out[0] = (uint32_t)v; out[1] = (uint32_t)(v >> 32);)   // (even, odd) -> (lo, hi)
 
-#if defined(__HIPCC__)
-template <class R> __global__ __launch_bounds__(64) void k_rows(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n) {
-  const uint64_t row = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  if (row >= n) return;
-  uint32_t a[R::NI], r[R::NO];
-  CPX_UNROLL for (int i = 0; i < R::NI; i++) a[i] = in[row * R::NI + i];
-  R::run(a, r);
-  CPX_UNROLL for (int i = 0; i < R::NO; i++) out[row * R::NO + i] = r[i];
-}
-template <class R> static bool run_rows(const uint32_t* in, uint32_t* out, uint64_t n) {
-  if (n == 0) return true;
-  uint32_t *din = nullptr, *dout = nullptr;
-  HIPCHECK(hipMalloc(&din, n * R::NI * sizeof(uint32_t)));
-  HIPCHECK(hipMalloc(&dout, n * R::NO * sizeof(uint32_t)));
-  HIPCHECK(hipMemcpy(din, in, n * R::NI * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIPCHECK(hipMemset(dout, 0xa5, n * R::NO * sizeof(uint32_t)));
-  hipLaunchKernelGGL(k_rows<R>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, din, dout, n);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipDeviceSynchronize());
-  HIPCHECK(hipMemcpy(out, dout, n * R::NO * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIPCHECK(hipFree(din));
-  HIPCHECK(hipFree(dout));
-  return true;
-}
-#else
-template <class R> static bool run_rows(const uint32_t* in, uint32_t* out, uint64_t n) {
-  for (uint64_t i = 0; i < n; i++) R::run(in + i * R::NI, out + i * R::NO);
-  return true;
-}
-#endif
-
-struct Entry {
+struct Engine {
   const char* name;
-  int ni, no;                                            // 0, 0: an engine
-  bool (*rows)(const uint32_t*, uint32_t*, uint64_t);    // helper operations
-  int engine;                                            // engines: -1 = strobe_host, else the device engine
+  int id;   // -1 = strobe_host, else the device engine
 };
-template <class R> static Entry row_entry(const char* name) { return Entry{name, R::NI, R::NO, run_rows<R>, 0}; }
-
-static const Entry TABLE[] = {
+static const Engine ENGINES[] = {
 #if defined(__HIPCC__)
-    Entry{"wave", 0, 0, nullptr, ENG_WAVE},
-    Entry{"wave_lds", 0, 0, nullptr, ENG_WAVE_LDS},
-    Entry{"lane", 0, 0, nullptr, ENG_LANE},
-    Entry{"strobe_dev", 0, 0, nullptr, ENG_STROBE_DEV},
+    {"wave", ENG_WAVE}, {"wave_lds", ENG_WAVE_LDS}, {"lane", ENG_LANE}, {"strobe_dev", ENG_STROBE_DEV},
 #endif
-    Entry{"strobe_host", 0, 0, nullptr, -1},
-    row_entry<Unshuffle32>("bits_unshuffle32"),
-    row_entry<Shuffle32>("bits_shuffle32"),
-    row_entry<Split64>("bits_split64"),
-    row_entry<Join64>("bits_join64"),
+    {"strobe_host", -1},
+};
+static const Entry TABLE[] = {
+    entry<Unshuffle32>("bits_unshuffle32"),
+    entry<Shuffle32>("bits_shuffle32"),
+    entry<Split64>("bits_split64"),
+    entry<Join64>("bits_join64"),
 };
 
-struct Header {
-  char name[48];
-  uint32_t words, reserved;
-  uint64_t rows;
-};
-static_assert(sizeof(Header) == 64, "record header layout");
 struct CaseHeader {
   uint32_t nops, blob_len, msg_offset, reserved;
 };
@@ -465,78 +401,54 @@ static bool read_cases(FILE* fi, const Header& h, bool lds_copy, Batch& b, std::
   return true;
 }
 
+static const Engine* find_engine(const char* name) {
+  for (const Engine& e : ENGINES)
+    if (!strcmp(e.name, name)) return &e;
+  return nullptr;
+}
+
+// one engine record: the cases are decoded from the input file behind the header, the output is the record's payload as u32 words
+static int run_engine(const Engine& eng, const Header& h, FILE* fi, std::vector<uint32_t>& out) {
+  Batch b;
+  std::vector<uint32_t> blob_len;
+#if defined(__HIPCC__)
+  if (!read_cases(fi, h, eng.id == ENG_WAVE_LDS, b, blob_len)) return CHECK_BAD;
+  if (!(eng.id < 0 ? run_strobe_host(b) : run_device(b, eng.id, blob_len))) return CHECK_FAILED;
+#else
+  if (!read_cases(fi, h, false, b, blob_len)) return CHECK_BAD;
+  if (!run_strobe_host(b)) return CHECK_FAILED;
+#endif
+  auto put64 = [&](const uint64_t* p, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+      out.push_back((uint32_t)p[i]);
+      out.push_back((uint32_t)(p[i] >> 32));
+    }
+  };
+  for (size_t i = 0; i < b.cases.size(); i++) {
+    const Case& c = b.cases[i];
+    const uint32_t nchal = (i + 1 < b.cases.size() ? b.cases[i + 1].chal0 : (uint32_t)(b.chal.size() / 5)) - c.chal0;
+    out.push_back(nchal);
+    out.push_back(0);
+    put64(&b.st_out[27 * i], 27);
+    if (nchal) put64(&b.chal[5 * (size_t)c.chal0], 5 * (size_t)nchal);
+  }
+  return CHECK_OK;
+}
+
 int main(int argc, char** argv) {
-  if (argc == 2 && !strcmp(argv[1], "--list")) {
-    for (const Entry& e : TABLE) printf("%s %d %d\n", e.name, e.ni, e.no);
-    return 0;
-  }
-  if (argc != 3) {
-    fprintf(stderr, "usage: transcript_check IN OUT | transcript_check --list\n");
-    return 2;
-  }
-  FILE* fi = fopen(argv[1], "rb");
-  FILE* fo = fopen(argv[2], "wb");
-  if (!fi || !fo) {
-    fprintf(stderr, "transcript_check: cannot open %s\n", fi ? argv[2] : argv[1]);
-    return 2;
-  }
-  Header h;
-  size_t records = 0, rows = 0, got;
-  while ((got = fread(&h, 1, sizeof h, fi)) == sizeof h) {
-    h.name[sizeof h.name - 1] = 0;
-    const Entry* op = nullptr;
-    for (const Entry& e : TABLE)
-      if (!strcmp(e.name, h.name)) op = &e;
-    if (!op || h.words != (uint32_t)op->ni || h.reserved != 0 || h.rows > (1u << 24)) {
-      fprintf(stderr, "transcript_check: bad record '%s' (%u words per row, %llu rows)\n", h.name, h.words, (unsigned long long)h.rows);
-      return 3;
-    }
-    bool wrote = true;
-    if (op->rows) {
-      std::vector<uint32_t> in((size_t)h.rows * op->ni), out((size_t)h.rows * op->no);
-      if (fread(in.data(), sizeof(uint32_t), in.size(), fi) != in.size()) {
-        fprintf(stderr, "transcript_check: record '%s' is truncated\n", h.name);
-        return 3;
-      }
-      if (!op->rows(in.data(), out.data(), h.rows)) return 4;
-      h.words = (uint32_t)op->no;
-      wrote = fwrite(&h, 1, sizeof h, fo) == sizeof h && fwrite(out.data(), sizeof(uint32_t), out.size(), fo) == out.size();
-    } else {
-      Batch b;
-      std::vector<uint32_t> blob_len;
-#if defined(__HIPCC__)
-      const bool lds_copy = op->engine == ENG_WAVE_LDS;
-#else
-      const bool lds_copy = false;
-#endif
-      if (!read_cases(fi, h, lds_copy, b, blob_len)) return 3;
-#if defined(__HIPCC__)
-      if (!(op->engine < 0 ? run_strobe_host(b) : run_device(b, op->engine, blob_len))) return 4;
-#else
-      if (!run_strobe_host(b)) return 4;
-#endif
-      wrote = fwrite(&h, 1, sizeof h, fo) == sizeof h;
-      for (size_t i = 0; wrote && i < b.cases.size(); i++) {
-        const Case& c = b.cases[i];
-        const uint32_t nchal = (i + 1 < b.cases.size() ? b.cases[i + 1].chal0 : (uint32_t)(b.chal.size() / 5)) - c.chal0;
-        const uint32_t head[2] = {nchal, 0};
-        wrote = fwrite(head, 1, sizeof head, fo) == sizeof head && fwrite(&b.st_out[27 * i], sizeof(uint64_t), 27, fo) == 27 &&
-                (nchal == 0 || fwrite(&b.chal[5 * (size_t)c.chal0], sizeof(uint64_t), 5 * (size_t)nchal, fo) == 5 * (size_t)nchal);
-      }
-    }
-    if (!wrote) {
-      fprintf(stderr, "transcript_check: cannot write %s\n", argv[2]);
-      return 2;
-    }
-    records++;
-    rows += h.rows;
-  }
-  if (got != 0) {
-    fprintf(stderr, "transcript_check: trailing bytes after the last record\n");
-    return 3;
-  }
-  if (fclose(fo) != 0) return 2;
-  fclose(fi);
-  printf("transcript_check (%s): %zu records, %zu rows\n", BUILD, records, rows);
-  return 0;
+  return check_main(
+      argc, argv, true,
+      [] {
+        for (const Engine& e : ENGINES) printf("%s 0 0\n", e.name);
+        rows_list(TABLE);
+      },
+      [](const Header& h) -> int64_t {
+        if (h.reserved != 0) return -1;
+        if (find_engine(h.name)) return h.words == 0 && h.rows <= (1u << 24) ? 0 : -1;
+        return rows_payload(TABLE, h);
+      },
+      [](Header& h, std::vector<uint32_t>& in, std::vector<uint32_t>& out, const CheckLoop& loop) {
+        const Engine* eng = find_engine(h.name);
+        return eng ? run_engine(*eng, h, loop.in, out) : rows_run(TABLE, h, in, out);
+      });
 }

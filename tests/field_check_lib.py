@@ -1,14 +1,13 @@
 """Harness of tests/device/field_check.hip for tests/test_field_check_cpu.py (host twin, g++) and tests/test_gpu_field.py (gfx950
-build): the record file format, the operation table, the rows of every operation group (tests/f28_vectors.py) and the checks of
+build): the operation table, the rows of every operation group (tests/f28_vectors.py) and the checks of
 every operation's result against Python integers and, for the point formulas, against the oracle as points."""
+import functools
 import os
 import random
-import struct
-import subprocess
 
-import numpy as np
-
+from tests import check_harness as ch
 from tests import f28_vectors as fv
+from tests.check_harness import list_operations, read_records, assert_same, _fmt   # noqa: F401
 from tests.f28_vectors import MASK, P, R392, RMOD, limbs, value, cneg_lazy, lazy_diff, check_montgomery
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -55,73 +54,15 @@ def group_of(name):
 
 # ---------------------------------------------------------------- building and running
 
-def build_host_twin(out_dir, extra=()):
-    """the host twin: the same source through g++ as plain C++"""
-    exe = os.path.join(str(out_dir), "field_check_host")
-    subprocess.check_call(["g++", "-x", "c++", "-O2", "-std=c++17"] + list(extra) + ["-o", exe, SRC])
-    return exe
+build_host_twin = functools.partial(ch.build_host_twin, SRC, name="field_check_host")      # (out_dir, extra=())
 
 
-def list_operations(exe):
-    out = subprocess.run([exe, "--list"], capture_output=True, text=True, timeout=120, check=True).stdout
-    return {l.split()[0]: (int(l.split()[1]), int(l.split()[2])) for l in out.splitlines()}
-
-
-def write_records(path, records):
-    """records: list of (operation, rows) with every row a flat list of integers in [-2^31, 2^32)"""
-    with open(path, "wb") as f:
-        for name, rows in records:
-            ni = TABLE[name][0]
-            a = np.array(rows, dtype=np.int64).reshape(len(rows), ni)
-            assert a.min(initial=0) >= -(1 << 31) and a.max(initial=0) < (1 << 32), name
-            f.write(struct.pack("<48sIIQ", name.encode(), ni, 0, len(rows)))
-            f.write((a & 0xffffffff).astype("<u4").tobytes())
-
-
-def read_records(path):
-    """list of (operation, array rows x output words, uint32)"""
-    out = []
-    with open(path, "rb") as f:
-        data = f.read()
-    o = 0
-    while o < len(data):
-        name, words, _, rows = struct.unpack_from("<48sIIQ", data, o)
-        o += 64
-        a = np.frombuffer(data, dtype="<u4", count=rows * words, offset=o).reshape(rows, words)
-        o += 4 * rows * words
-        out.append((name.rstrip(b"\0").decode(), a))
-    return out
+def write_records(path, records):      # (tests/host_emul/sanitize.sh writes the extreme products with it)
+    ch.write_records(path, TABLE, records)
 
 
 def run(exe, records, work_dir, tag, timeout=120):
-    """one process: every record through `exe`; the outputs in order, one per record, row counts checked"""
-    inp, outp = os.path.join(str(work_dir), tag + ".in"), os.path.join(str(work_dir), tag + ".out")
-    write_records(inp, records)
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, "%s exited with %d: %s" % (os.path.basename(exe), r.returncode, (r.stdout + r.stderr)[-2000:])
-    res = read_records(outp)
-    assert [n for n, _ in res] == [n for n, _ in records]
-    for (name, rows), (_, a) in zip(records, res):
-        assert a.shape == (len(rows), TABLE[name][1]), name
-    assert "%d records, %d rows" % (len(records), sum(len(r) for _, r in records)) in r.stdout, r.stdout
-    return res
-
-
-def _fmt(row):
-    return "[" + ", ".join(hex(x) if x >= 0 else "-" + hex(-x) for x in row) + "]"
-
-
-def assert_same(records, got, want, who=("device", "host twin")):
-    """bit for bit, every row of every record; returns the number of rows compared"""
-    n = 0
-    for (name, rows), (_, g), (_, w) in zip(records, got, want):
-        assert g.shape == w.shape, name
-        if not np.array_equal(g, w):
-            i = int(np.nonzero((g != w).any(axis=1))[0][0])
-            raise AssertionError("%s row %d: %s and %s differ\n  in  %s\n  %s %s\n  %s %s" % (
-                name, i, who[0], who[1], _fmt(rows[i]), who[0], _fmt(g[i].tolist()), who[1], _fmt(w[i].tolist())))
-        n += len(rows)
-    return n
+    return ch.run(exe, TABLE, records, work_dir, tag, timeout)
 
 
 # ---------------------------------------------------------------- integer checks, one per operation

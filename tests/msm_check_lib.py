@@ -8,12 +8,12 @@ negative entry enters as the negated point).  The device's entries are compared 
 order of the LDS atomics inside a list is free."""
 import os
 import struct
-import subprocess
 
 import numpy as np
 
+from tests import check_harness as ch
 from tests import msm_cases as mc
-from tests.field_check_lib import read_records
+from tests.check_harness import list_operations, read_records   # noqa: F401
 from tests.msm_cases import NONE, NEG, CANONICAL, TBW_CAP, ROUND_PTS, ROUND_PTS_PERWIN, FIX_CHUNK, POOL
 from tests.scalar_cases import P, R, py_split
 
@@ -26,11 +26,7 @@ TABLE.update({op: ("pair" if op == "pair" else "tblw") for op in mc.FORMS})
 TABLE.update({op: "fix" for op in mc.FIX_FORMS})
 TABLE.update({"reduce/wave": "reduce", "reduce/sets": "reduce", "finalize/wave": "finalize", "finalize/ranges": "finalize", "tail/wave": "finalize", "tail/lanes": "finalize"})
 AFF, JAC = 96, 144
-
-
-def list_operations(exe):
-    out = subprocess.run([exe, "--list"], capture_output=True, text=True, timeout=120, check=True).stdout
-    return {l.split()[0]: l.split()[1] for l in out.splitlines()}
+ONE_WORD = {op: (1, 1) for op in TABLE}      # the record format of tests/check_harness.py with one word per row
 
 
 def words(v, n):
@@ -557,22 +553,13 @@ def check_tail(pool, op, tc, out):
 
 # ---------------------------------------------------------------- running
 
-def write_records(path, records):
-    with open(path, "wb") as f:
-        for name, w in records:
-            a = np.asarray(w, dtype=np.uint64)
-            assert a.max(initial=0) < (1 << 32), name
-            f.write(struct.pack("<48sIIQ", name.encode(), 1, 0, len(a)))
-            f.write(a.astype("<u4").tobytes())
+def pack_records(records):
+    """records: list of (operation, words): a record of one word per row"""
+    return ch.pack_records(ONE_WORD, [(name, np.asarray(w, dtype=np.int64).reshape(-1, 1)) for name, w in records])
 
 
 def run(exe, records, work_dir, tag, timeout=120):
     """one process: every record through `exe`; the outputs in order, one per record.  A nonzero exit fails at once; nothing is retried."""
-    inp, outp = os.path.join(str(work_dir), tag + ".in"), os.path.join(str(work_dir), tag + ".out")
-    write_records(inp, records)
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, "%s exited with %d: %s" % (os.path.basename(exe), r.returncode, (r.stdout + r.stderr)[-2000:])
-    res = read_records(outp)
+    res = read_records(ch.run_file(exe, pack_records(records), work_dir, tag, timeout, "%d records" % len(records)))
     assert [n for n, _ in res] == [n for n, _ in records]
-    assert "%d records" % len(records) in r.stdout, r.stdout
     return [a for _, a in res]

@@ -3,9 +3,14 @@ tests/device/rng_check.hip, tests/test_gpu_rng.py runs the same ones through the
 Everything is derived from fixed seeds by the Python model (tests/stdrng_ref.py); the few cases that need a particular accident of the
 stream (a draw that ends exactly at a window's edge) are found by a search over seeds 0, 1, 2, ... that stops at the first hit."""
 import functools
+import os
 import struct
 
+import numpy as np
+
+from tests import check_harness as ch
 from tests import stdrng_ref as sr
+from tests.check_harness import list_operations, read_records   # noqa: F401
 from tests.stdrng_ref import R, StdRng
 
 WINDOW = 64                       # candidates k_rng_draw tests per window (curdleproofs_amd/csrc/rng.hip)
@@ -184,41 +189,13 @@ def expected_row(name, row):
     return out + words(rng.word_pos, 2)
 
 
-# ---------------------------------------------------------------- building and running rng_check (file format and reader: tests/field_check_lib.py)
-import os
-import subprocess
-
-import numpy as np
-
-from tests.field_check_lib import read_records, list_operations   # noqa: E402,F401
-
+# ---------------------------------------------------------------- building and running rng_check (tests/check_harness.py)
 SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "device", "rng_check.hip")
-
-
-def build_host_twin(out_dir, extra=(), name="rng_check_host"):
-    """the host twin: the same source through g++ as plain C++"""
-    exe = os.path.join(str(out_dir), name)
-    subprocess.check_call(["g++", "-x", "c++", "-O2", "-std=c++17"] + list(extra) + ["-o", exe, SRC])
-    return exe
+build_host_twin = functools.partial(ch.build_host_twin, SRC, name="rng_check_host")      # (out_dir, extra=(), name=...)
 
 
 def run_check(exe, records, work_dir, tag, timeout=120):
-    """one process: every record through `exe`; returns [(operation, array rows x output words)]"""
-    inp, outp = os.path.join(str(work_dir), tag + ".in"), os.path.join(str(work_dir), tag + ".out")
-    with open(inp, "wb") as f:
-        for name, rows in records:
-            a = np.array(rows, dtype=np.uint64).reshape(len(rows), TABLE[name][0])
-            assert a.max(initial=0) < (1 << 32), name
-            f.write(struct.pack("<48sIIQ", name.encode(), TABLE[name][0], 0, len(rows)))
-            f.write(a.astype("<u4").tobytes())
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, "%s exited with %d: %s" % (os.path.basename(exe), r.returncode, (r.stdout + r.stderr)[-2000:])
-    res = read_records(outp)
-    assert [n for n, _ in res] == [n for n, _ in records]
-    for (name, rows), (_, a) in zip(records, res):
-        assert a.shape == (len(rows), TABLE[name][1]), name
-    assert "%d records, %d rows" % (len(records), sum(len(r) for _, r in records)) in r.stdout, r.stdout
-    return res
+    return ch.run(exe, TABLE, records, work_dir, tag, timeout)
 
 
 @functools.lru_cache(maxsize=None)
@@ -227,14 +204,4 @@ def check_expected():
     return tuple((n, np.array([expected_row(n, r) for r in rows], dtype=np.uint32)) for n, rows in check_records())
 
 
-def assert_rows(records, got, want, who):
-    """row by row, bit for bit; returns the number of rows compared"""
-    n = 0
-    for (name, rows), (_, g), (_, w) in zip(records, got, want):
-        assert g.shape == w.shape, name
-        if not np.array_equal(g, w):
-            i = int(np.nonzero((g != w).any(axis=1))[0][0])
-            raise AssertionError("%s row %d: %s and %s differ\n  in  %s\n  %s\n  %s" % (name, i, who[0], who[1], [hex(x) for x in rows[i]],
-                                                                                         [hex(int(x)) for x in g[i]], [hex(int(x)) for x in w[i]]))
-        n += len(rows)
-    return n
+assert_rows = ch.assert_same

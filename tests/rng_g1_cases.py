@@ -10,14 +10,14 @@ import functools
 import math
 import os
 import struct
-import subprocess
 
 import numpy as np
 
+from tests import check_harness as ch
 from tests import rng_cases as rc
 from tests import stdrng_g1_ref as g1
 from tests import stdrng_ref as sr
-from tests.field_check_lib import list_operations, read_records   # noqa: F401
+from tests.check_harness import list_operations, read_records   # noqa: F401
 from tests.stdrng_ref import StdRng
 
 WINDOW_WORDS = 64 * 16            # the scan window of k_rng_g1_scan (curdleproofs_amd/csrc/rng_g1_plan.hpp): 64 blocks from the block of the next token
@@ -259,30 +259,11 @@ def check_expected():
 SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "device", "rng_g1_check.hip")
 
 
-def build_host_twin(out_dir, extra=(), name="rng_g1_check_host"):
-    """the host twin: the same source through g++ as plain C++"""
-    exe = os.path.join(str(out_dir), name)
-    subprocess.check_call(["g++", "-x", "c++", "-O2", "-std=c++17"] + list(extra) + ["-o", exe, SRC])
-    return exe
+build_host_twin = functools.partial(ch.build_host_twin, SRC, name="rng_g1_check_host")      # (out_dir, extra=(), name=...)
 
 
 def run_check(exe, records, work_dir, tag, timeout=300):
-    """one process: every record through `exe`; returns [(operation, array rows x output words)]"""
-    inp, outp = os.path.join(str(work_dir), tag + ".in"), os.path.join(str(work_dir), tag + ".out")
-    with open(inp, "wb") as f:
-        for name, rows in records:
-            a = np.array(rows, dtype=np.uint64).reshape(len(rows), TABLE[name][0])
-            assert a.max(initial=0) < (1 << 32), name
-            f.write(struct.pack("<48sIIQ", name.encode(), TABLE[name][0], 0, len(rows)))
-            f.write(a.astype("<u4").tobytes())
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, "%s exited with %d: %s" % (os.path.basename(exe), r.returncode, (r.stdout + r.stderr)[-2000:])
-    res = read_records(outp)
-    assert [n for n, _ in res] == [n for n, _ in records]
-    for (name, rows), (_, a) in zip(records, res):
-        assert a.shape == (len(rows), TABLE[name][1]), name
-    assert "%d records, %d rows" % (len(records), sum(len(r) for _, r in records)) in r.stdout, r.stdout
-    return res
+    return ch.run(exe, TABLE, records, work_dir, tag, timeout)
 
 
-assert_rows = rc.assert_rows
+assert_rows = ch.assert_same

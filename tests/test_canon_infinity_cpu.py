@@ -2,14 +2,13 @@
 strict_infinity = 0, to every input of compressed points: run on the CPU by tests/host_emul/canon_infinity_emul.cpp, once plain and once
 with -fsanitize=address,undefined, and compared with the rule stated in Python.  The store is the caller's: what one call returned is
 still intact after the next call has rewritten another array into another store."""
-import os
 import random
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from tests.check_harness import build_emul
+
 CANON = bytes([0xc0]) + bytes(47)
 # tests/test_gpu_parity.py, test_noncanonical_infinity_encodings_follow_the_option: sort flag set, the last bit of x, every bit, a high bit of x
 VARIANTS = [bytes([0xe0]) + bytes(47), bytes([0xc0]) + bytes(46) + b"\x01", bytes([0xff]) + b"\xff" * 47, bytes([0xc0, 0x01]) + bytes(46)]
@@ -30,13 +29,7 @@ def rule(blob, nrec, stride, offsets):
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def emul(request):
-    src = os.path.join(HERE, "host_emul", "canon_infinity_emul.cpp")
-    san = request.param == "sanitized"
-    exe = os.path.join(HERE, "host_emul", "_canon_infinity_san" if san else "_canon_infinity")
-    deps = [src, os.path.join(ROOT, "curdleproofs_amd", "csrc", "canon_infinity.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags + ["-o", exe, src])
+    exe = build_emul("canon_infinity_emul.cpp", ["canon_infinity.hpp"], request.param == "sanitized", hip=False)
 
     def run(arrays):
         """arrays: (blob, nrec, stride, offsets), each rewritten into a store of its own, one call after the other.  Returns per array

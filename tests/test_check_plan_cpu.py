@@ -4,10 +4,11 @@ FixTask of the per-proof, the fused and the two stages of the grouped check look
 tests/host_emul/check_plan_emul.cpp, once plain and once with -fsanitize=address,undefined (the planner makes no HIP call; the HIP headers
 are only needed for the task types of kernels.h), and compared with the same rules restated here in plain Python."""
 import os
-import shutil
 import subprocess
 
 import pytest
+
+from tests.check_harness import build_emul
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -23,22 +24,9 @@ GROUPS_MAX = (1, 4, 256)
 FIX_PARTS = (1, 8)
 
 
-def _hip_include():
-    for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if c and os.path.exists(c):
-            return os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(c))), "include")
-    raise RuntimeError("the HIP headers (kernels.h includes hip_runtime.h) were not found")
-
-
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def emul(request):
-    src = os.path.join(HERE, "host_emul", "check_plan_emul.cpp")
-    san = request.param == "sanitized"
-    exe = os.path.join(HERE, "host_emul", "_check_plan_san" if san else "_check_plan")
-    deps = [src, os.path.join(ROOT, "include", "cpx.h")] + [os.path.join(CSRC, f) for f in ("check_plan.hpp", "locate_plan.hpp", "layout.hpp", "kernels.h", "g1.hpp", "g1_28.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags + ["-D__HIP_PLATFORM_AMD__", "-isystem", _hip_include(), "-o", exe, src])
+    exe = build_emul("check_plan_emul.cpp", ["include/cpx.h", "check_plan.hpp", "locate_plan.hpp", "layout.hpp", "kernels.h", "g1.hpp", "g1_28.hpp"], request.param == "sanitized")
 
     def run(B, groups_max, fix_parts, suspects):
         out = subprocess.run([exe] + [str(a) for a in (B, groups_max, ELL, L, fix_parts, STRIDE)] + ["".join(str(int(b)) for b in suspects)], check=True,

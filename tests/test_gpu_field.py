@@ -23,9 +23,9 @@ def twin(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def device():
-    from curdleproofs_amd.build import FIELDCHECK
-    assert os.path.exists(FIELDCHECK), "run python -m curdleproofs_amd.build"
-    return FIELDCHECK
+    from curdleproofs_amd.build import check_path
+    assert os.path.exists(check_path("field_check")), "run python -m curdleproofs_amd.build"
+    return check_path("field_check")
 
 
 def test_device_program_has_the_operation_table(device):

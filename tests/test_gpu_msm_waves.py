@@ -24,9 +24,9 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def device():
-    from curdleproofs_amd.build import MSMCHECK
-    assert os.path.exists(MSMCHECK), "run python -m curdleproofs_amd.build"
-    return MSMCHECK
+    from curdleproofs_amd.build import check_path
+    assert os.path.exists(check_path("msm_check")), "run python -m curdleproofs_amd.build"
+    return check_path("msm_check")
 
 
 @pytest.fixture(scope="module")

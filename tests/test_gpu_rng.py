@@ -52,10 +52,10 @@ def ctx28(request, cpx, crs28):
 def test_device_build_of_rng_check(tmp_path):
     """every function of rng.hpp on the device, bit for bit against the host twin and the model"""
     from curdleproofs_amd import build
-    assert os.path.exists(build.RNGCHECK), "curdleproofs_amd/_lib/rng_check is missing: build() makes it"
-    assert rc.list_operations(build.RNGCHECK) == rc.TABLE
+    assert os.path.exists(build.check_path("rng_check")), "curdleproofs_amd/_lib/rng_check is missing: build() makes it"
+    assert rc.list_operations(build.check_path("rng_check")) == rc.TABLE
     records = rc.check_records()
-    dev = rc.run_check(build.RNGCHECK, records, tmp_path, "dev")
+    dev = rc.run_check(build.check_path("rng_check"), records, tmp_path, "dev")
     twin = rc.run_check(rc.build_host_twin(tmp_path), records, tmp_path, "twin")
     total = sum(len(r) for _, r in records)
     assert rc.assert_rows(records, dev, twin, ("device", "host twin")) == total

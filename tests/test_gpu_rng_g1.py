@@ -37,10 +37,10 @@ def plain(cpx):
 def test_device_build_of_rng_g1_check(tmp_path):
     """the pieces of G1::rand on the device, bit for bit against the host twin and the model"""
     from curdleproofs_amd import build
-    assert os.path.exists(build.RNGG1CHECK), "curdleproofs_amd/_lib/rng_g1_check is missing: build() makes it"
-    assert gc.list_operations(build.RNGG1CHECK) == gc.TABLE
+    assert os.path.exists(build.check_path("rng_g1_check")), "curdleproofs_amd/_lib/rng_g1_check is missing: build() makes it"
+    assert gc.list_operations(build.check_path("rng_g1_check")) == gc.TABLE
     records = gc.check_records()
-    dev = gc.run_check(build.RNGG1CHECK, records, tmp_path, "dev")
+    dev = gc.run_check(build.check_path("rng_g1_check"), records, tmp_path, "dev")
     twin = gc.run_check(gc.build_host_twin(tmp_path), records, tmp_path, "twin")
     total = sum(len(r) for _, r in records)
     assert gc.assert_rows(records, dev, twin, ("device", "host twin")) == total

@@ -24,9 +24,9 @@ def twin(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def device():
-    from curdleproofs_amd.build import SCALARCHECK
-    assert os.path.exists(SCALARCHECK), "run python -m curdleproofs_amd.build"
-    return SCALARCHECK
+    from curdleproofs_amd.build import check_path
+    assert os.path.exists(check_path("scalar_check")), "run python -m curdleproofs_amd.build"
+    return check_path("scalar_check")
 
 
 def test_device_program_has_the_operation_table(device):

@@ -25,9 +25,9 @@ def twin(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def device():
-    from curdleproofs_amd.build import TRANSCRIPTCHECK
-    assert os.path.exists(TRANSCRIPTCHECK), "run python -m curdleproofs_amd.build"
-    return TRANSCRIPTCHECK
+    from curdleproofs_amd.build import check_path
+    assert os.path.exists(check_path("transcript_check")), "run python -m curdleproofs_amd.build"
+    return check_path("transcript_check")
 
 
 @pytest.fixture(scope="module")

@@ -5,17 +5,14 @@ compressed by the oracle, D and A' are oracle MSMs as in test_check_weights_cpu.
 its outputs are held against the oracle's proof: the serialised bytes, the round vectors folded in Python integers, and the commitments
 the staged vectors feed."""
 import ctypes
-import os
-import shutil
 import subprocess
 
 import pytest
 
+from tests.check_harness import build_emul
+
 from tests.test_check_weights_cpu import _slots, emul  # noqa: F401  (emul: host_verify.hpp's twin, the source of D's scalars)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, "..", "curdleproofs_amd", "csrc")
-SRC = os.path.join(HERE, "host_emul", "host_prove_emul.cpp")
 FR, AFF = 32, 96
 R_MOD = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 R_INV = pow(1 << 256, -1, R_MOD)      # wire form is the Montgomery residue x * 2^256 mod r
@@ -43,22 +40,11 @@ def layout(L):
     return off, o
 
 
-def _hip_include():   # (protocol.h, which names the SC_* / V_* scalars, includes hip_runtime.h)
-    for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if c and os.path.exists(c):
-            return os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(c))), "include")
-    raise RuntimeError("the HIP headers were not found")
-
-
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def twin(request):
-    san = request.param == "sanitized"
-    exe = os.path.join(HERE, "host_emul", "_host_prove_san" if san else "_host_prove")
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("host_prove.hpp", "host_transcript.hpp", "host_math.hpp", "prove_reqs.hpp", "layout.hpp", "protocol.h",
-                                                     "mont32.hpp", "strobe.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags + ["-D__HIP_PLATFORM_AMD__", "-isystem", _hip_include(), "-o", exe, SRC])
+    # (protocol.h, which names the SC_* / V_* scalars, includes hip_runtime.h)
+    exe = build_emul("host_prove_emul.cpp", ["host_prove.hpp", "host_transcript.hpp", "host_math.hpp", "prove_reqs.hpp", "layout.hpp", "protocol.h", "mont32.hpp",
+                                             "strobe.hpp"], request.param == "sanitized")
 
     def run(case):
         text = "".join("%s %s\n" % (k, v if isinstance(v, str) else v.hex()) for k, v in case.items())

@@ -277,8 +277,8 @@ def test_device_program_is_built_for_gfx950_with_the_operation_table():
     """build() leaves _lib/msm_check beside the library (linked against it); its table is the one the tests drive.  The source passes the
     compiler's front end for the host and for gfx950 with the library's device flags."""
     from curdleproofs_amd import build as b
-    assert os.path.exists(b.MSMCHECK), "run python -m curdleproofs_amd.build"
-    assert ml.list_operations(b.MSMCHECK) == ml.TABLE
-    with open(b.MSMCHECK, "rb") as f:
+    assert os.path.exists(b.check_path("msm_check")), "run python -m curdleproofs_amd.build"
+    assert ml.list_operations(b.check_path("msm_check")) == ml.TABLE
+    with open(b.check_path("msm_check"), "rb") as f:
         assert b"gfx950" in f.read()
-    subprocess.check_call([b._hipcc(), "--offload-arch=" + b.ARCH] + b.DEVICE_FLAGS + ["-fsyntax-only", b.MSMCHECK_SRC])
+    subprocess.check_call([b._hipcc(), "--offload-arch=" + b.ARCH] + b.DEVICE_FLAGS + ["-fsyntax-only", b.check_source("msm_check")])

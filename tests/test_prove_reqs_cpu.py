@@ -3,17 +3,11 @@ prover / verifier and the device-resident plans materialise.  Compiled with the 
 which flattens the descriptors into integers; everything asserted here is written from the protocol's tables of requests — which
 bases, which scalars, which kept point, which output slot, which addends — not read back from the header."""
 import ctypes
-import os
-import shutil
-import subprocess
 from collections import Counter, namedtuple
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_emul", "prove_reqs_emul.cpp")
-LIB = os.path.join(HERE, "host_emul", "_prove_reqs.so")
-CSRC = os.path.join(HERE, "..", "curdleproofs_amd", "csrc")
+from tests.check_harness import build_emul
 
 NAMES = ("SL_A SL_CMT1 SL_CMT2 SL_CMU1 SL_CMU2 SL_R SL_S SL_B SL_C SL_BC SL_BD CMA1 CMA2 CMB1 CMB2 BA BT BU D APRIME TMP0 NSLOTS NPOINTS "
          "VR IR RT RU RA RB NRAND M T U H G_t G_u G_sum H_sum V_APERM V_FACT V_C V_ZZU V_COUNT SC_BETA_SP SC_ALPHA_SP SC_NEG_BETA_G_INV SC_ALPHA_G "
@@ -27,19 +21,9 @@ Seg = namedtuple("Seg", "kind gather off n arg")
 Req = namedtuple("Req", "seg0 seg1 scal_kind scal_at keep out add")
 
 
-def _hip_include():
-    for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if c and os.path.exists(c):
-            return os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(c))), "include")
-    raise RuntimeError("the HIP headers (protocol.h includes hip_runtime.h) were not found")
-
-
 @pytest.fixture(scope="module")
 def lib():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("prove_reqs.hpp", "layout.hpp", "protocol.h", "mont32.hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I", _hip_include(), "-o", LIB, SRC])
-    return ctypes.CDLL(LIB)
+    return ctypes.CDLL(build_emul("prove_reqs_emul.cpp", ["prove_reqs.hpp", "layout.hpp", "protocol.h", "mont32.hpp"], shared=True))
 
 
 class Shape:

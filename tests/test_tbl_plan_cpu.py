@@ -3,33 +3,18 @@ phases and the device-resident plans turn a list of requests into tasks of k_msm
 k_finalize_ranges.  Compiled with the host compiler by tests/host_emul/tbl_plan_emul.cpp (the planner makes no HIP call; the HIP
 headers are only needed for the task types of kernels.h)."""
 import ctypes
-import os
 import random
-import shutil
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_emul", "tbl_plan_emul.cpp")
-LIB = os.path.join(HERE, "host_emul", "_tbl_plan.so")
-CSRC = os.path.join(HERE, "..", "curdleproofs_amd", "csrc")
+from tests.check_harness import build_emul
+
 NONE, CRS, TAB = 0, 1, 2
-
-
-def _hip_include():
-    for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if c and os.path.exists(c):
-            return os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(c))), "include")
-    raise RuntimeError("the HIP headers (kernels.h includes hip_runtime.h) were not found")
 
 
 @pytest.fixture(scope="module")
 def planner():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("tbl_plan.hpp", "kernels.h", "host_math.hpp", "g1.hpp", "g1_28.hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I", _hip_include(), "-o", LIB, SRC])
-    L = ctypes.CDLL(LIB)
+    L = ctypes.CDLL(build_emul("tbl_plan_emul.cpp", ["tbl_plan.hpp", "kernels.h", "host_math.hpp", "g1.hpp", "g1_28.hpp"], shared=True))
     L.emul_tbl_plan.restype = ctypes.c_int
     return L
 

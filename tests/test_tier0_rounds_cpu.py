@@ -9,6 +9,8 @@ import subprocess
 
 import pytest
 
+from tests.check_harness import build_emul
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 NAMES = ("cpx_g1_msm_many", "cpx_g1_fold_many")
@@ -100,13 +102,7 @@ def test_the_option_is_listed_beside_the_others():
 # ---- tier0_plan.hpp on the CPU ----
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def emul(request):
-    src = os.path.join(HERE, "host_emul", "tier0_plan_emul.cpp")
-    san = request.param == "sanitized"
-    exe = os.path.join(HERE, "host_emul", "_tier0_plan_san" if san else "_tier0_plan")
-    deps = [src, os.path.join(ROOT, "curdleproofs_amd", "csrc", "tier0_plan.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags + ["-o", exe, src])
+    exe = build_emul("tier0_plan_emul.cpp", ["tier0_plan.hpp"], request.param == "sanitized", hip=False)
 
     def run(*args):
         out = subprocess.run([exe] + [str(a) for a in args], check=True, capture_output=True, text=True).stdout       # a sanitizer report is a non-zero exit

@@ -10,6 +10,8 @@ import subprocess
 
 import pytest
 
+from tests.check_harness import build_emul
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 NAMES = ("cpx_whisk_verify_tracker_proofs_fused", "cpx_whisk_verify_tracker_proofs_grouped")
@@ -104,14 +106,7 @@ def test_python_wrappers_check_lengths_before_touching_the_library():
 # ---- the g++ twin of tracker_check_plan.hpp ----
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def emul(request):
-    src = os.path.join(HERE, "host_emul", "tracker_check_emul.cpp")
-    san = request.param == "sanitized"
-    exe = os.path.join(HERE, "host_emul", "_tracker_check_san" if san else "_tracker_check")
-    csrc = os.path.join(ROOT, "curdleproofs_amd", "csrc")
-    deps = [src, os.path.join(ROOT, "include", "cpx.h")] + [os.path.join(csrc, f) for f in ("tracker_check_plan.hpp", "locate_plan.hpp", "mont32.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags + ["-o", exe, src])
+    exe = build_emul("tracker_check_emul.cpp", ["include/cpx.h", "tracker_check_plan.hpp", "locate_plan.hpp", "mont32.hpp"], request.param == "sanitized", hip=False)
 
     def run(args, stdin=None):
         return subprocess.run([exe] + [str(a) for a in args], input=stdin, check=True, capture_output=True, text=True).stdout   # a sanitizer report is a non-zero exit

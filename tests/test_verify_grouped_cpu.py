@@ -10,6 +10,8 @@ import subprocess
 
 import pytest
 
+from tests.check_harness import build_emul
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 NAMES = ("cpx_batch_verify_grouped", "cpx_whisk_verify_shuffle_proofs_grouped")
@@ -124,13 +126,7 @@ def test_the_option_is_listed_and_bounded(lib):
 # ---- locate_plan.hpp on the CPU ----
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def emul(request):
-    src = os.path.join(HERE, "host_emul", "locate_plan_emul.cpp")
-    san = request.param == "sanitized"
-    exe = os.path.join(HERE, "host_emul", "_locate_plan_san" if san else "_locate_plan")
-    deps = [src, os.path.join(ROOT, "curdleproofs_amd", "csrc", "locate_plan.hpp"), os.path.join(ROOT, "include", "cpx.h")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags + ["-o", exe, src])
+    exe = build_emul("locate_plan_emul.cpp", ["locate_plan.hpp", "include/cpx.h"], request.param == "sanitized", hip=False)
 
     def run(B, groups_max, flags, group_ok, own_ok):
         s = lambda bits: "".join(str(int(b)) for b in bits) or "-"

@@ -12,6 +12,8 @@ import types
 
 import pytest
 
+from tests.check_harness import build_emul
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 NAMES = ("cpx_whisk_candidates_load", "cpx_whisk_candidates_size", "cpx_whisk_candidates_read", "cpx_whisk_verify_shuffle_run",
@@ -134,14 +136,7 @@ def replay(n, ell, table, n_applied):
 
 @pytest.fixture(scope="module", params=["plain", "sanitized"])
 def emul(request):
-    src = os.path.join(HERE, "host_emul", "run_plan_emul.cpp")
-    san = request.param == "sanitized"
-    exe = os.path.join(HERE, "host_emul", "_run_plan_san" if san else "_run_plan")
-    csrc = os.path.join(ROOT, "curdleproofs_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in ("run_plan.hpp", "mont32.hpp")]
-    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
-        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
-        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + flags + ["-o", exe, src])
+    exe = build_emul("run_plan_emul.cpp", ["run_plan.hpp", "mont32.hpp"], request.param == "sanitized", hip=False)
 
     def run(n, ell, table, n_applied):
         text = "%d %d %d %d\n%s\n" % (len(table), ell, n, n_applied, " ".join(str(i) for row in table for i in row))

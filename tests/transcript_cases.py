@@ -9,14 +9,14 @@ lies below pos once the second header byte is written.  The sweep takes pos_begi
 reachable between operations, pos_begin = 0 or pos_begin < pos; pos_begin = pos and 166 occur only inside begin_op and are left out
 when generating (the program itself accepts any pos <= 165, pos_begin <= 166).
 """
+import functools
 import os
 import random
 import struct
-import subprocess
 
-import numpy as np
-
+from tests import check_harness as ch
 from tests import strobe_ref as sr
+from tests.check_harness import list_operations   # noqa: F401
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(_ROOT, "tests", "device", "transcript_check.hip")
@@ -297,15 +297,7 @@ def proof_schedule(ell):
 
 
 # ---------------------------------------------------------------- the program: build, file format, run
-def build_host_twin(out_dir, extra=()):
-    exe = os.path.join(str(out_dir), "transcript_check_host")
-    subprocess.check_call(["g++", "-x", "c++", "-O2", "-std=c++17"] + list(extra) + ["-o", exe, SRC])
-    return exe
-
-
-def list_operations(exe):
-    out = subprocess.run([exe, "--list"], capture_output=True, text=True, timeout=120, check=True).stdout
-    return {l.split()[0]: (int(l.split()[1]), int(l.split()[2])) for l in out.splitlines()}
+build_host_twin = functools.partial(ch.build_host_twin, SRC, name="transcript_check_host")      # (out_dir, extra=())
 
 
 def encode_case(case):
@@ -338,29 +330,14 @@ def encode_case(case):
 
 
 def engine_record(engine, cases):
-    return struct.pack("<48sIIQ", engine.encode(), 0, 0, len(cases)) + b"".join(encode_case(c) for c in cases)
-
-
-def row_record(name, rows):
-    a = np.array(rows, dtype=np.uint64).reshape(len(rows), HELPERS[name][0])
-    return struct.pack("<48sIIQ", name.encode(), HELPERS[name][0], 0, len(rows)) + a.astype("<u4").tobytes()
-
-
-def run_file(exe, blob, work_dir, tag, timeout=120):
-    inp, outp = os.path.join(str(work_dir), tag + ".in"), os.path.join(str(work_dir), tag + ".out")
-    with open(inp, "wb") as f:
-        f.write(blob)
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, "%s exited with %d: %s" % (os.path.basename(exe), r.returncode, (r.stdout + r.stderr)[-2000:])
-    with open(outp, "rb") as f:
-        return f.read(), r.stdout
+    return ch.pack_record(engine, 0, len(cases), b"".join(encode_case(c) for c in cases))
 
 
 def run_engine(exe, engine, cases, work_dir, tag, timeout=120):
     """one process: every case through `engine`; [(27 words, [(scalar, attempts)])], one per case"""
-    data, stdout = run_file(exe, engine_record(engine, cases), work_dir, tag, timeout)
-    assert "1 records, %d rows" % len(cases) in stdout, stdout
-    name, words, _, rows = struct.unpack_from("<48sIIQ", data, 0)
+    with open(ch.run_file(exe, engine_record(engine, cases), work_dir, tag, timeout, "1 records, %d rows" % len(cases)), "rb") as f:
+        data = f.read()
+    name, words, _, rows = struct.unpack_from(ch.HEADER, data, 0)
     assert name.rstrip(b"\0").decode() == engine and rows == len(cases)
     o, out = 64, []
     for c in cases:
@@ -379,16 +356,7 @@ def run_engine(exe, engine, cases, work_dir, tag, timeout=120):
 
 
 def run_rows(exe, records, work_dir, tag, timeout=120):
-    data, stdout = run_file(exe, b"".join(row_record(n, r) for n, r in records), work_dir, tag, timeout)
-    assert "%d records, %d rows" % (len(records), sum(len(r) for _, r in records)) in stdout, stdout
-    o, out = 0, []
-    for name, rows in records:
-        got, words, _, n = struct.unpack_from("<48sIIQ", data, o)
-        assert got.rstrip(b"\0").decode() == name and words == HELPERS[name][1] and n == len(rows)
-        out.append((name, np.frombuffer(data, dtype="<u4", count=n * words, offset=o + 64).reshape(n, words)))
-        o += 64 + 4 * n * words
-    assert o == len(data)
-    return out
+    return ch.run(exe, HELPERS, records, work_dir, tag, timeout)
 
 
 # ---------------------------------------------------------------- comparison
