@@ -27,6 +27,7 @@ FR = 32
 AFF = 96
 JAC = 144
 N_BLINDERS = 4   # reference src/lib.rs:35
+TRANSCRIPT_BYTES = 216   # a transcript state: 25 Keccak lanes, pos, pos_begin as 27 u64 LE (include/cpx.h)
 
 CPX_OK = 0
 CPX_ERR_ARG = -1
@@ -58,7 +59,9 @@ _libs = {}   # realpath -> loaded library (the default one and build variants fo
 
 EXPORTS = [
     "cpx_host_alloc", "cpx_host_free", "cpx_ctx_create", "cpx_ctx_destroy", "cpx_last_error", "cpx_device_count", "cpx_ctx_set_option", "cpx_ctx_get_option", "cpx_ctx_set_crs", "cpx_crs_sums", "cpx_proof_size", "cpx_batch_size",
-    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_g1_normalize", "cpx_g1_decompress", "cpx_g1_decompress_status",
+    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_ipa_rounds", "cpx_same_msm_rounds",
+    "cpx_transcript_new", "cpx_transcript_append_message", "cpx_transcript_append_scalar", "cpx_transcript_challenge_bytes", "cpx_transcript_challenge_scalar",
+    "cpx_g1_normalize", "cpx_g1_decompress", "cpx_g1_decompress_status",
     "cpx_accum_new", "cpx_accum_free", "cpx_accum_check", "cpx_accum_verify",
     "cpx_batch_load", "cpx_batch_load_begin", "cpx_batch_load_end", "cpx_batch_prove", "cpx_batch_verify", "cpx_batch_verify_fused", "cpx_batch_verify_grouped", "cpx_g1_sum_jac",
     "cpx_whisk_generate_shuffle_proof", "cpx_whisk_is_valid_shuffle_proof", "cpx_whisk_generate_tracker_proof", "cpx_whisk_is_valid_tracker_proof",
@@ -112,6 +115,13 @@ def load_library(path=None):
     L.cpx_g1_msm_many.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     L.cpx_g1_fold_many.argtypes = [vp, sz, sz, vp, vp, vp]
     L.cpx_g1_normalize.argtypes = [vp, vp, sz, vp, vp]
+    L.cpx_ipa_rounds.argtypes = [vp, sz, sz] + [vp] * 10
+    L.cpx_same_msm_rounds.argtypes = [vp, sz, sz] + [vp] * 9
+    L.cpx_transcript_new.argtypes = [vp, sz, vp]
+    L.cpx_transcript_append_message.argtypes = [vp, vp, sz, vp, sz]
+    L.cpx_transcript_append_scalar.argtypes = [vp, vp, sz, vp]
+    L.cpx_transcript_challenge_bytes.argtypes = [vp, vp, sz, vp, sz]
+    L.cpx_transcript_challenge_scalar.argtypes = [vp, vp, sz, vp]
     L.cpx_g1_decompress.argtypes = [vp, vp, sz, vp, ci]
     L.cpx_g1_decompress_status.argtypes = [vp, vp, sz, vp, ci, vp]
     L.cpx_accum_new.argtypes = [vp, ctypes.POINTER(vp)]
@@ -357,6 +367,41 @@ class Context:
         b = _in(b"".join(bytes(v) for v in PL_list))
         self._check(self._L.cpx_g1_fold_many(self._h, families, half, b, _in(b"".join(bytes(v) for v in PR_list)), _in(gammas)))
         return [bytes(b)[size * f: size * (f + 1)] for f in range(families)]
+
+    def _loop_rounds(self, fn, terms, count, n, inputs, nvec, states, affine):
+        if count < 0 or n < 0:
+            raise ValueError("count and n are not negative")
+        L = max(n.bit_length() - 1, 0)
+        if len(states) != count * TRANSCRIPT_BYTES:
+            raise ValueError("one 216-byte transcript state per item")
+        st = (ctypes.c_uint8 * max(len(states), 1)).from_buffer_copy(bytes(states) if count else b"\0")   # in/out: a copy, the caller's stay
+        comp, aff = _out(count * L * terms * 48), _out(count * L * terms * AFF)
+        fin, gam = _out(count * nvec * FR), _out(count * L * FR)
+        self._check(fn(self._h, count, n, *[_in(b) for b in inputs], st, comp, aff if affine else None, fin, gam))
+        out = dict(states=bytes(st)[:count * TRANSCRIPT_BYTES], compressed=bytes(comp)[:count * L * terms * 48], finals=bytes(fin)[:count * nvec * FR],
+                   gammas=bytes(gam)[:count * L * FR])
+        if affine:
+            out["affine"] = bytes(aff)[:count * L * terms * AFF]
+        return out
+
+    def ipa_rounds(self, n, G, G_prime, H, vec_c, vec_d, states, affine=False):
+        """inner_product_argument.rs:150-186 for len(H) // 96 independent items of n elements in ONE call (cpx_ipa_rounds): all log2 n
+        rounds on the device, transcript included.  G, G_prime: the bases as they enter the loop, item after item; H: the loop's point
+        (crs_H * beta) per item; vec_c, vec_d: the vectors as they enter the loop; states: the 216-byte transcript states at loop entry
+        (curdleproofs_amd.transcript.Transcript.state).  Returns a dict: "states" (advanced by every round), "compressed" (per item and
+        round L_C, L_D, R_C, R_D, 48 bytes each), "finals" (per item c_final, d_final), "gammas", and with affine=True "affine"."""
+        count = len(H) // AFF
+        if len(H) != count * AFF or len(G) != count * n * AFF or len(G_prime) != count * n * AFF or len(vec_c) != count * n * FR or len(vec_d) != count * n * FR:
+            raise ValueError("ipa_rounds: per item n points in G and G_prime, one point H, n scalars in vec_c and vec_d")
+        return self._loop_rounds(self._L.cpx_ipa_rounds, 4, count, n, (G, G_prime, H, vec_c, vec_d), 2, states, affine)
+
+    def same_msm_rounds(self, n, G, T, U, vec_x, states, affine=False):
+        """same_multiscalar_argument.rs:99-136 likewise (cpx_same_msm_rounds), len(states) // 216 items: per round L_A, L_T, L_U, R_A,
+        R_T, R_U; "finals" holds x_final per item."""
+        count = len(states) // TRANSCRIPT_BYTES
+        if any(len(v) != count * n * AFF for v in (G, T, U)) or len(vec_x) != count * n * FR:
+            raise ValueError("same_msm_rounds: per item n points in G, T and U and n scalars in vec_x")
+        return self._loop_rounds(self._L.cpx_same_msm_rounds, 6, count, n, (G, T, U, vec_x), 1, states, affine)
 
     def normalize(self, jac, compressed=False):
         n = len(jac) // JAC

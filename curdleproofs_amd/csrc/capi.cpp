@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include "engine.hpp"
 #include "find_plan.hpp"
+#include "transcript_state.hpp"
 
 using namespace cpx;
 
@@ -74,6 +75,19 @@ template <class F> int guarded(cpx_ctx* ctx, F&& f) {
     ctx->err = "unknown failure";
     return CPX_ERR_INTERNAL;
   }
+}
+}  // namespace
+
+// the transcript as a 216-byte value (transcript_state.hpp; cpx_transcript_* below)
+namespace {
+// one operation on a copy of the state, written back when it succeeds: an error leaves the caller's state as it was
+template <class F> int on_transcript(uint8_t* state, const uint8_t* label, size_t label_len, size_t len, F&& f) {
+  Strobe s;
+  if (!state || (label_len && !label) || len > 0xffffffffu) return CPX_ERR_ARG;   // (merlin encodes a length as LE32)
+  if (!transcript_state_load(state, s)) return CPX_ERR_ARG;
+  f(s, reinterpret_cast<const char*>(label ? label : state));   // (an empty label is never read)
+  transcript_state_store(s, state);
+  return CPX_OK;
 }
 }  // namespace
 
@@ -571,6 +585,55 @@ int cpx_batch_prove_rng(cpx_ctx* ctx, const uint32_t* permutation, const uint8_t
     for (size_t i = 0; i < B * ell; i++)
       if (permutation[i] >= ell) return (int)CPX_ERR_ARG;
     ctx->eng->batch_prove_rng(permutation, k, vec_m_blinders, states, proofs_out);
+    return (int)CPX_OK;
+  });
+}
+
+// ---- the reference's `transcript: &mut merlin::Transcript` as a 216-byte value (transcript_state.hpp; the operations are strobe.hpp's) ----
+int cpx_transcript_new(const uint8_t* label, size_t label_len, uint8_t state_out[CPX_TRANSCRIPT_BYTES]) {
+  if (!state_out || (label_len && !label) || label_len > 0xffffffffu) return CPX_ERR_ARG;
+  Strobe s;
+  s.init(reinterpret_cast<const char*>(label_len ? label : state_out), label_len);   // (an empty label is never read)
+  transcript_state_store(s, state_out);
+  return CPX_OK;
+}
+int cpx_transcript_append_message(uint8_t state[CPX_TRANSCRIPT_BYTES], const uint8_t* label, size_t label_len, const uint8_t* msg, size_t len) {
+  if (len && !msg) return CPX_ERR_ARG;
+  return on_transcript(state, label, label_len, len, [&](Strobe& s, const char* l) { s.append_message(l, label_len, msg, len); });
+}
+int cpx_transcript_append_scalar(uint8_t state[CPX_TRANSCRIPT_BYTES], const uint8_t* label, size_t label_len, const uint8_t scalar_mont[32]) {
+  if (!scalar_mont || !fr_wire_reduced(scalar_mont)) return CPX_ERR_ARG;
+  uint8_t b[32];
+  host::S_from_wire(scalar_mont).to_le_bytes(b);
+  return on_transcript(state, label, label_len, 32, [&](Strobe& s, const char* l) { s.append_message(l, label_len, b, 32); });
+}
+int cpx_transcript_challenge_bytes(uint8_t state[CPX_TRANSCRIPT_BYTES], const uint8_t* label, size_t label_len, uint8_t* out, size_t len) {
+  if (len && !out) return CPX_ERR_ARG;
+  return on_transcript(state, label, label_len, len, [&](Strobe& s, const char* l) { s.challenge_bytes(l, label_len, out, len); });
+}
+int cpx_transcript_challenge_scalar(uint8_t state[CPX_TRANSCRIPT_BYTES], const uint8_t* label, size_t label_len, uint8_t out_mont[32]) {
+  if (!out_mont) return CPX_ERR_ARG;
+  return on_transcript(state, label, label_len, 64, [&](Strobe& s, const char* l) {
+    Fr e;
+    while (!s.challenge_attempt_canonical(l, label_len, e.v)) {
+    }
+    e = fe_to_mont(e);
+    memcpy(out_mont, e.v, 32);
+  });
+}
+int cpx_ipa_rounds(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* H, const uint8_t* vec_c, const uint8_t* vec_d,
+                   uint8_t* transcripts, uint8_t* rounds_compressed, uint8_t* rounds_affine, uint8_t* finals, uint8_t* gammas) {
+  if (count && n && (!G || !G_prime || !H || !vec_c || !vec_d || !transcripts || !finals)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->ipa_rounds(count, n, G, G_prime, H, vec_c, vec_d, transcripts, rounds_compressed, rounds_affine, finals, gammas);
+    return (int)CPX_OK;
+  });
+}
+int cpx_same_msm_rounds(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* vec_x, uint8_t* transcripts,
+                        uint8_t* rounds_compressed, uint8_t* rounds_affine, uint8_t* finals, uint8_t* gammas) {
+  if (count && n && (!G || !T || !U || !vec_x || !transcripts || !finals)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->same_msm_rounds(count, n, G, T, U, vec_x, transcripts, rounds_compressed, rounds_affine, finals, gammas);
     return (int)CPX_OK;
   });
 }

@@ -858,17 +858,145 @@ void Engine::msm_chain_reserve(const Tier0MsmPlan& pl) {
 // points at offset pl.conv_off[i] of both; d_res receives pl.count sums in Jacobian standard form.  `tasks` is the caller's, declared above
 // its scope (an enqueued copy reads it).
 void Engine::msm_chain(const Tier0MsmPlan& pl, const uint32_t* lens, const Aff* d_bases, const Fr* d_scalars, Jac* d_res, std::vector<MsmTask>& tasks) {
-  const size_t count = pl.count, np = pl.points;
+  const size_t count = pl.count;
   tasks.resize(count);
   for (size_t i = 0; i < count; i++) tasks[i] = MsmTask{d_bases + pl.conv_off[i], nullptr, d_scalars + pl.conv_off[i], lens[i], 0, pl.conv_off[i]};
   CPX_HIP(hipMemcpyAsync(t0_.mtask.p, tasks.data(), count * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+  msm_chain_run(pl, t0_.mtask.p, d_res);
+}
+// ... whose launches take any pl.count uploaded tasks laid out by the plan (task i's conv_off = pl.conv_off[i]; gather lists allowed)
+void Engine::msm_chain_run(const Tier0MsmPlan& pl, const MsmTask* d_tasks, Jac* d_res) {
+  const size_t count = pl.count, np = pl.points;
   tick("k_msm_tblw<2, true>", 128.0 * np, (double)np);
-  launch_msm_endo(t0_.mtask.p, (int)count, (int)pl.max_n, t0_.conv.p, t0_.dig.p, t0_.ttask.p, main_.raw.p, main_.rawslot.p, stream_, pl.slices);
+  launch_msm_endo(d_tasks, (int)count, (int)pl.max_n, t0_.conv.p, t0_.dig.p, t0_.ttask.p, main_.raw.p, main_.rawslot.p, stream_, pl.slices);
   tock();
   reduce_sets(stream_, main_, 0, pl.sets(), t0_.part.p);
   tick("k_msm_tail", 0, (double)count);
   launch_msm_tail(opt_, t0_.part.p, nullptr, d_res, (int)count, 16, 8, stream_, nullptr, 0, pl.tail_dup());
   tock();
+}
+// The log-round loops as one call each (include/cpx.h cpx_ipa_rounds, cpx_same_msm_rounds): inner_product_argument.rs:150-186 /
+// same_multiscalar_argument.rs:99-136 for `count` independent items in the all-MSM form, laid out by loop_plan.hpp.  Per round the chain
+// above over the round's 4 / 6 count cross terms (gathered from the uploaded bases: nothing is folded), k_finalize for their encodings,
+// and one k_loop_step (loop.hip) for the transcript step, the folds and the next round's scalars: launches whose number does not
+// depend on count, nothing returning to the host between the one upload and the one download.  fam: G | G' | H resp. G | T | U;
+// vec: c | d resp. x.  The outputs are written when the call has succeeded, never before.
+void Engine::ipa_rounds(size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* H, const uint8_t* vec_c, const uint8_t* vec_d,
+                        uint8_t* transcripts, uint8_t* rounds_comp, uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas) {
+  const uint8_t *fam[3] = {G, G_prime, H}, *vec[2] = {vec_c, vec_d};
+  loop_rounds(true, count, n, fam, vec, transcripts, rounds_comp, rounds_aff, finals, gammas);
+}
+void Engine::same_msm_rounds(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* vec_x, uint8_t* transcripts,
+                             uint8_t* rounds_comp, uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas) {
+  const uint8_t *fam[3] = {G, T, U}, *vec[2] = {vec_x, nullptr};
+  loop_rounds(false, count, n, fam, vec, transcripts, rounds_comp, rounds_aff, finals, gammas);
+}
+void Engine::loop_rounds(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const vec[2], uint8_t* transcripts, uint8_t* rounds_comp,
+                         uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas) {
+  if (!count) return;
+  LoopPlan lp;
+  switch (loop_plan(ipa, count, n, lp)) {
+    case LOOP_NOT_POW2: throw std::invalid_argument("the log-round loops take n = 2^L elements per item, L >= 0");
+    case LOOP_TOO_LARGE: throw ArgError(ipa ? "cpx_ipa_rounds: at most 16384 items and count (2 n + 2) <= 2^24 points per round"
+                                            : "cpx_same_msm_rounds: at most 10922 items and 3 count n <= 2^24 points per round");
+    default: break;
+  }
+  const size_t nvec = ipa ? 2 : 1, L = lp.L, NT = lp.tasks(), terms = (size_t)lp.terms();
+  for (size_t v = 0; v < nvec; v++)
+    for (size_t i = 0; i < count * n; i++)
+      if (!fr_wire_reduced(vec[v] + i * sizeof(Fr))) throw ArgError("a scalar of a log-round loop is not reduced");
+  for (size_t i = 0; i < count; i++)
+    if (!transcript_state_valid(transcripts + i * kTranscriptBytes)) throw ArgError("a transcript state with pos > 165 or pos_begin > 166");
+  if (n == 1) {   // no round: the finals are the inputs, the states stay
+    for (size_t i = 0; i < count; i++)
+      for (size_t v = 0; v < nvec; v++) memcpy(finals + (i * nvec + v) * sizeof(Fr), vec[v] + i * sizeof(Fr), sizeof(Fr));
+    return;
+  }
+  // host memory the enqueued copies read or write: above the scope
+  std::vector<MsmTask> tasks;
+  std::vector<uint32_t> idx, lens;
+  std::vector<Fr> hvec;
+  std::vector<uint8_t> h_comp, h_aff, h_states, h_fr;
+  Tier0MsmPlan pl;
+  if (!lp.round_msm(pl, lens)) throw ArgError("a round of the loop exceeds the limits of cpx_g1_msm_many");
+  CallScope call(this);
+  pl.slices = msm_tblw_slices(opt_, (int)NT, 2, (int)pl.max_n);   // (every round has the same lengths)
+  DevBuf<Aff>&db = t0_.a0, &daff = t0_.a1;
+  DevBuf<Fr>& dfr = t0_.fr;
+  DevBuf<Jac>& res = t0_.res;
+  DevBuf<uint8_t>& dcomp = t0_.bytes;
+  db.ensure(count * lp.base_stride());
+  dfr.ensure(lp.fr_total());
+  res.ensure(lp.results());
+  daff.ensure(lp.results());
+  dcomp.ensure(lp.results() * 48);
+  t0_.lidx.ensure(lp.idx_total());
+  t0_.lstate.ensure(count * kTranscriptWords);
+  msm_chain_reserve(pl);
+  t0_.mtask.ensure(L * NT);
+  // ---- the one upload: bases item by item, vectors with unit fold coefficients, index lists, every round's tasks, states
+  const size_t pitch = lp.base_stride() * sizeof(Aff);
+  for (int f = 0; f < 3; f++) {
+    const size_t each = ipa && f == 2 ? 1 : n, off = ipa && f == 2 ? lp.h_index() : lp.family_off(f);
+    CPX_HIP(hipMemcpy2DAsync(db.p + off, pitch, fam[f], each * sizeof(Aff), each * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
+  }
+  hvec.assign(count * lp.vec_words() + (ipa ? count : 0), Fr::one());
+  for (size_t i = 0; i < count; i++)
+    for (size_t v = 0; v < nvec; v++) memcpy(&hvec[i * lp.vec_words() + v * n], vec[v] + i * n * sizeof(Fr), n * sizeof(Fr));
+  Fr* const d_vec = dfr.p + lp.fr_vec();
+  Fr* const d_rows = dfr.p + lp.fr_rows();
+  Fr* const d_ones = dfr.p + lp.fr_ones();
+  CPX_HIP(hipMemcpyAsync(d_vec, hvec.data(), count * lp.vec_words() * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  if (ipa) CPX_HIP(hipMemcpyAsync(d_ones, hvec.data() + count * lp.vec_words(), count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  lp.fill_idx(idx);
+  CPX_HIP(hipMemcpyAsync(t0_.lidx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  tasks.resize(L * NT);
+  for (size_t j = 0; j < L; j++)
+    for (size_t i = 0; i < count; i++)
+      for (int q = 0; q < (int)terms; q++) {
+        const size_t k = i * terms + (size_t)q;
+        tasks[j * NT + k] = MsmTask{db.p + i * lp.base_stride() + lp.family_off(lp.term_family(q)), t0_.lidx.p + lp.idx_off(j, lp.term_hi(q)),
+                                    d_rows + i * lp.row_words() + lp.scal_off(q), lp.term_len(q), 0, pl.conv_off[k]};
+      }
+  CPX_HIP(hipMemcpyAsync(t0_.mtask.p, tasks.data(), tasks.size() * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(t0_.lstate.p, transcripts, count * kTranscriptBytes, hipMemcpyHostToDevice, stream_));
+  // ---- the rounds
+  const LoopDev ld{d_vec, d_rows, dfr.p + lp.fr_gammas(), dfr.p + lp.fr_finals(), t0_.lstate.p, dcomp.p, (int)count, (int)n, (int)L};
+  if (ipa) launch_ipa_round_scalars(d_vec, (int)count, (int)n, (int)(n / 2), d_ones, d_rows, stream_);
+  else launch_smsm_round_scalars(d_vec, (int)count, (int)n, (int)(n / 2), d_rows, stream_);
+  for (size_t j = 0; j < L; j++) {
+    msm_chain_run(pl, t0_.mtask.p + j * NT, res.p + j * NT);
+    tick("k_finalize", 0, (double)NT);
+    launch_finalize(res.p + j * NT, (int)NT, daff.p + j * NT, nullptr, dcomp.p + j * NT * 48, stream_);
+    tock();
+    tick("k_loop_step", 0, (double)count, true);
+    launch_loop_step(ipa, ld, (int)j, stream_);
+    tock();
+  }
+  // ---- the one download, into host memory of the call: the caller's buffers are written once everything has arrived
+  h_states.resize(count * kTranscriptBytes);
+  h_fr.resize((count * L + count * lp.finals_each()) * sizeof(Fr));   // gammas | finals, as they sit in the Fr memory
+  CPX_HIP(hipMemcpyAsync(h_states.data(), t0_.lstate.p, h_states.size(), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(h_fr.data(), dfr.p + lp.fr_gammas(), h_fr.size(), hipMemcpyDeviceToHost, stream_));
+  if (rounds_comp) {
+    h_comp.resize(lp.results() * 48);
+    CPX_HIP(hipMemcpyAsync(h_comp.data(), dcomp.p, h_comp.size(), hipMemcpyDeviceToHost, stream_));
+  }
+  if (rounds_aff) {
+    h_aff.resize(lp.results() * sizeof(Aff));
+    CPX_HIP(hipMemcpyAsync(h_aff.data(), daff.p, h_aff.size(), hipMemcpyDeviceToHost, stream_));
+  }
+  call.finish();
+  memcpy(transcripts, h_states.data(), h_states.size());
+  memcpy(finals, h_fr.data() + count * L * sizeof(Fr), count * lp.finals_each() * sizeof(Fr));
+  if (gammas) memcpy(gammas, h_fr.data(), count * L * sizeof(Fr));
+  // device order [L][count][terms] -> the caller's [count][L][terms]
+  for (size_t i = 0; i < count; i++)
+    for (size_t j = 0; j < L; j++) {
+      const size_t src = lp.result_index(j, i, 0), dst = (i * L + j) * terms;
+      if (rounds_comp) memcpy(rounds_comp + dst * 48, h_comp.data() + src * 48, terms * 48);
+      if (rounds_aff) memcpy(rounds_aff + dst * sizeof(Aff), h_aff.data() + src * sizeof(Aff), terms * sizeof(Aff));
+    }
 }
 // The basis folds of one log round (inner_product_argument.rs:177-178: 2 families, same_multiscalar_argument.rs:128-130: 3) as ONE call:
 // a SmulTask per family, each with its own gamma shared by its `half` elements, in one launch_smul.  A round's folds are small (3 x 128

@@ -33,6 +33,8 @@
 #include "shuffle_plan.hpp"
 #include "tbl_plan.hpp"
 #include "tier0_plan.hpp"
+#include "loop_plan.hpp"
+#include "transcript_state.hpp"
 
 namespace cpx {
 
@@ -175,6 +177,12 @@ class Engine {
   // the calls of one log round, many per call (tier0_plan.hpp): ONE upload, kernel chain, download and stream synchronisation each
   void msm_many(size_t count, const uint32_t* lens, const uint8_t* bases, const uint8_t* scalars, uint8_t* out_jac, uint8_t* out_comp);   // the cross terms: inner_product_argument.rs:158-161, same_multiscalar_argument.rs:107-112
   void fold_many(size_t families, size_t half, uint8_t* PL, const uint8_t* PR, const uint8_t* gammas);                                      // the basis folds: inner_product_argument.rs:177-178, same_multiscalar_argument.rs:128-130
+  // the log-round loops themselves, `count` independent items per call (loop_plan.hpp, loop.hip; include/cpx.h cpx_ipa_rounds /
+  // cpx_same_msm_rounds): states in/out, every round's cross terms, the finals and the challenges; no CRS, the batch is left alone
+  void ipa_rounds(size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* H, const uint8_t* vec_c, const uint8_t* vec_d, uint8_t* transcripts,
+                  uint8_t* rounds_comp, uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas);                                              // inner_product_argument.rs:150-186
+  void same_msm_rounds(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* vec_x, uint8_t* transcripts, uint8_t* rounds_comp,
+                       uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas);                                                               // same_multiscalar_argument.rs:99-136
   void normalize(const uint8_t* jac, size_t n, uint8_t* out_aff, uint8_t* out_comp);                   // normalize_batch (+compress)
   int decompress(const uint8_t* comp, size_t n, uint8_t* out_aff, int check_subgroup, uint8_t* status_out = nullptr);   // whisk.rs:318-320
 
@@ -428,8 +436,12 @@ class Engine {
     DevBuf<Aff> tbase;
     DevBuf<Fr> tscal, tw;
     DevBuf<Jac> tres;
+    // what the log-round loops need beside the MSM chain's buffers (loop_plan.hpp): the index lists of every round, the transcript states
+    DevBuf<uint32_t> lidx;
+    DevBuf<uint64_t> lstate;
     template <class Self, class F> static void each(Self& s, F&& f) {   // (Self: Tier0 or const Tier0)
-      each_buf(f, s.a0, s.a1, s.fr, s.mtask, s.stask, s.w, s.pt, s.part, s.res, s.jin, s.conv, s.ttask, s.dig, s.bytes, s.status, s.flag, s.gen, s.tbase, s.tscal, s.tw, s.tres);
+      each_buf(f, s.a0, s.a1, s.fr, s.mtask, s.stask, s.w, s.pt, s.part, s.res, s.jin, s.conv, s.ttask, s.dig, s.bytes, s.status, s.flag, s.gen, s.tbase, s.tscal, s.tw, s.tres,
+               s.lidx, s.lstate);
     }
   } t0_;
   // Scratch of the batched shuffle calls (whisk.cpp), kept and trimmed like the tier-0 set
@@ -471,6 +483,10 @@ class Engine {
   // device-resident bases and scalars, inside the caller's scope
   void msm_chain_reserve(const Tier0MsmPlan& pl);
   void msm_chain(const Tier0MsmPlan& pl, const uint32_t* lens, const Aff* d_bases, const Fr* d_scalars, Jac* d_res, std::vector<MsmTask>& tasks);
+  void msm_chain_run(const Tier0MsmPlan& pl, const MsmTask* d_tasks, Jac* d_res);   // its launches, on pl.count uploaded tasks
+  // the one body of ipa_rounds / same_msm_rounds (engine.cpp).  fam: G | G' | H resp. G | T | U; vec: c | d resp. x
+  void loop_rounds(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const vec[2], uint8_t* transcripts, uint8_t* rounds_comp,
+                   uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas);
   // n trackers -> the planes r_G | k_r_G: upload + k_decompress of the tracker prover, find-trackers and the candidate list (whisk.cpp)
   void decode_tracker_planes(size_t n, const uint8_t* trackers, std::vector<uint8_t>& canon, std::vector<uint32_t>& off, uint8_t* d_bytes, uint32_t* d_off, Aff* d_pts,
                              uint8_t* d_status);

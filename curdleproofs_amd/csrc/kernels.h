@@ -234,6 +234,16 @@ void launch_ipa_round_scalars(const Fr* d_vec, int nproofs, int n, int half, con
 void launch_ipa_round_fold(Fr* d_vec, int nproofs, int n, int half, const Fr* d_gam, hipStream_t s, int active = 0);
 void launch_smsm_round_scalars(const Fr* d_vec, int nproofs, int n, int half, Fr* d_out, hipStream_t s, int active = 0);
 void launch_smsm_round_fold(Fr* d_vec, int nproofs, int n, int half, const Fr* d_gam, hipStream_t s, int active = 0);
+// The tail of round j of cpx_ipa_rounds / cpx_same_msm_rounds for `count` items of n elements (loop.hip, layouts: loop_plan.hpp): hashes
+// the round's 4 / 6 encodings comp[(j count + item) terms ..] into the item's transcript state, draws gamma (kept in gammas[item L + j]),
+// folds vec, writes the next round's scalar row, or after the last round the finals
+struct LoopDev {
+  Fr *vec, *rows, *gammas, *finals;
+  uint64_t* states;      // [count][27]
+  const uint8_t* comp;   // [L][count][terms][48]
+  int count, n, L;
+};
+void launch_loop_step(bool ipa, const LoopDev& d, int j, hipStream_t s);
 // transcript prefix of every proof: absorbs the compressed instance ([nproofs][4*ell*48] + [nproofs][48] for M), draws vec_a;
 // d_state: [nproofs][27] u64 (25 STROBE lanes, pos, pos_begin), d_vec_a: [nproofs][ell] Fr
 // lane_per_proof: one lane instead of 32 per transcript (large batches: a fifth of the wave instructions, a longer chain)

@@ -42,6 +42,7 @@
 #include "kernels.h"
 #include "block_inverse.hpp"
 #include "msm_body.hpp"
+#include "round_algebra.hpp"
 #include "tier0_plan.hpp"
 
 namespace cpx {
@@ -1061,80 +1062,28 @@ __global__ __launch_bounds__(128) void k_ipa_round_scalars(const Fr* __restrict_
   __shared__ Fr red[2][128];
   const int p = blockIdx.x, hn = n / 2;
   const Fr* c = vec + (size_t)p * 4 * stride;
-  const Fr* d = c + stride;
-  const Fr* SG = d + stride;
-  const Fr* SGp = SG + stride;
-  Fr* o = out + (size_t)p * (4 * hn + 2);
-  Fr ip1 = Fr::zero(), ip2 = Fr::zero();
-  for (int t = threadIdx.x; t < hn; t += blockDim.x) {
-    const int kl = (t / half) * 2 * half + (t % half), kh = kl + half;
-    const int ih = kh & (half - 1), il = kl & (half - 1);
-    o[t] = fe_mul(c[ih], SG[kh]);                          // L_C : right-half bases with c_L
-    o[hn + 1 + t] = fe_mul(d[half + il], SGp[kl]);         // L_D : left-half bases (rescaled) with d_R
-    o[2 * hn + 1 + t] = fe_mul(c[half + il], SG[kl]);      // R_C : left-half bases with c_R
-    o[3 * hn + 2 + t] = fe_mul(d[ih], SGp[kh]);            // R_D : right-half bases with d_L
-  }
-  for (int i = threadIdx.x; i < half; i += blockDim.x) {
-    ip1 = fe_add(ip1, fe_mul(c[i], d[half + i]));
-    ip2 = fe_add(ip2, fe_mul(c[half + i], d[i]));
-  }
-  red[0][threadIdx.x] = ip1;
-  red[1][threadIdx.x] = ip2;
-  __syncthreads();
-  for (int sft = blockDim.x / 2; sft >= 1; sft >>= 1) {
-    if ((int)threadIdx.x < sft) {
-      red[0][threadIdx.x] = fe_add(red[0][threadIdx.x], red[0][threadIdx.x + sft]);
-      red[1][threadIdx.x] = fe_add(red[1][threadIdx.x], red[1][threadIdx.x + sft]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    o[hn] = fe_mul(beta[p], red[0][0]);
-    o[3 * hn + 1] = fe_mul(beta[p], red[1][0]);
-  }
+  ipa_round_scalars_body(c, c + stride, c + 2 * stride, c + 3 * stride, n, half, beta[p], out + (size_t)p * (4 * hn + 2), &red[0][0]);
 }
 // gam: [B][2] = gamma, gamma^-1.  c_L += gamma^-1 c_R, d_L += gamma d_R, SG[hi] *= gamma, SGp[hi] *= gamma^-1
 __global__ __launch_bounds__(128) void k_ipa_round_fold(Fr* __restrict__ vec, int stride, int n, int half, const Fr* __restrict__ gam) {
-  const int p = blockIdx.x, hn = n / 2;
+  const int p = blockIdx.x;
   Fr* c = vec + (size_t)p * 4 * stride;
-  Fr* d = c + stride;
-  Fr* SG = d + stride;
-  Fr* SGp = SG + stride;
   const Fr g = gam[2 * p], gi = gam[2 * p + 1];
-  for (int i = threadIdx.x; i < half; i += blockDim.x) {
-    c[i] = fe_add(c[i], fe_mul(gi, c[half + i]));
-    d[i] = fe_add(d[i], fe_mul(g, d[half + i]));
-  }
-  for (int t = threadIdx.x; t < hn; t += blockDim.x) {
-    const int kh = (t / half) * 2 * half + (t % half) + half;
-    SG[kh] = fe_mul(SG[kh], g);
-    SGp[kh] = fe_mul(SGp[kh], gi);
-  }
+  ipa_round_fold_body(c, c + stride, c + 2 * stride, c + 3 * stride, n, half, g, gi);
 }
 // SameMSM (same_multiscalar_argument.rs:99-136 in all-MSM form).  vec: [B][2][n] = x | SM.
 // out per proof: [ L_* scalars (n/2) | R_* scalars (n/2) ]
 __global__ __launch_bounds__(128) void k_smsm_round_scalars(const Fr* __restrict__ vec, int stride, int n, int half, Fr* __restrict__ out) {
   const int p = blockIdx.x, hn = n / 2;
   const Fr* x = vec + (size_t)p * 2 * stride;
-  const Fr* SM = x + stride;
-  Fr* o = out + (size_t)p * 2 * hn;
-  for (int t = threadIdx.x; t < hn; t += blockDim.x) {
-    const int kl = (t / half) * 2 * half + (t % half), kh = kl + half;
-    o[t] = fe_mul(x[kh & (half - 1)], SM[kh]);                    // L_* : right-half bases with x_L
-    o[hn + t] = fe_mul(x[(kl & (half - 1)) + half], SM[kl]);      // R_* : left-half bases with x_R
-  }
+  smsm_round_scalars_body(x, x + stride, n, half, out + (size_t)p * 2 * hn);
 }
 // gam: [B][2] = gamma, gamma^-1.  x_L += gamma^-1 x_R, SM[hi] *= gamma
 __global__ __launch_bounds__(128) void k_smsm_round_fold(Fr* __restrict__ vec, int stride, int n, int half, const Fr* __restrict__ gam) {
-  const int p = blockIdx.x, hn = n / 2;
+  const int p = blockIdx.x;
   Fr* x = vec + (size_t)p * 2 * stride;
-  Fr* SM = x + stride;
   const Fr g = gam[2 * p], gi = gam[2 * p + 1];
-  for (int i = threadIdx.x; i < half; i += blockDim.x) x[i] = fe_add(x[i], fe_mul(gi, x[half + i]));
-  for (int t = threadIdx.x; t < hn; t += blockDim.x) {
-    const int kh = (t / half) * 2 * half + (t % half) + half;
-    SM[kh] = fe_mul(SM[kh], g);
-  }
+  smsm_round_fold_body(x, x + stride, n, half, g, gi);
 }
 
 // ------------------------------------------------------------------ transcript prefix on the device

@@ -105,29 +105,34 @@ struct Strobe {
   }
 
   // merlin::Transcript::new(label)
-  CPX_HD void init(const char* label) {
+  CPX_HD void init(const char* label) { init(label, label_len(label)); }
+  CPX_HD void init(const char* label, size_t llen) {
     for (int i = 0; i < 25; i++) st[i] = 0;
     const uint8_t ini[18] = {1, 168, 1, 0, 1, 96, 'S', 'T', 'R', 'O', 'B', 'E', 'v', '1', '.', '0', '.', '2'};
     for (int i = 0; i < 18; i++) xor_byte(i, ini[i]);
     keccak_f1600(st);
     pos = pos_begin = 0;
     meta_ad("Merlin v1.0", 11, false);
-    append_message("dom-sep", reinterpret_cast<const uint8_t*>(label), label_len(label));
+    append_message("dom-sep", reinterpret_cast<const uint8_t*>(label), llen);
   }
   // append_message split in two so that long messages can be streamed: begin(label, total length) then absorb(...)
-  CPX_HD void append_begin(const char* label, size_t len) {
+  // (the forms with an explicit label length serve the transcript values of the C ABI, include/cpx.h cpx_transcript_*: a caller's
+  // label is a byte string with a length; the forms on a C string are those with the string's length)
+  CPX_HD void append_begin(const char* label, size_t llen, size_t len) {
     const uint8_t l4[4] = {(uint8_t)len, (uint8_t)(len >> 8), (uint8_t)(len >> 16), (uint8_t)(len >> 24)};
-    meta_ad(label, label_len(label), false);
+    meta_ad(label, llen, false);
     meta_ad(l4, 4, true);
     begin_op(FLAG_A, false);
   }
-  CPX_HD void append_message(const char* label, const uint8_t* m, size_t len) {
-    append_begin(label, len);
+  CPX_HD void append_begin(const char* label, size_t len) { append_begin(label, label_len(label), len); }
+  CPX_HD void append_message(const char* label, size_t llen, const uint8_t* m, size_t len) {
+    append_begin(label, llen, len);
     absorb(m, len);
   }
-  CPX_HD void challenge_bytes(const char* label, uint8_t* out, size_t len) {
+  CPX_HD void append_message(const char* label, const uint8_t* m, size_t len) { append_message(label, label_len(label), m, len); }
+  CPX_HD void challenge_bytes(const char* label, size_t llen, uint8_t* out, size_t len) {
     const uint8_t l4[4] = {(uint8_t)len, (uint8_t)(len >> 8), (uint8_t)(len >> 16), (uint8_t)(len >> 24)};
-    meta_ad(label, label_len(label), false);
+    meta_ad(label, llen, false);
     meta_ad(l4, 4, true);
     begin_op(FLAG_I | FLAG_A | FLAG_C, false);
     for (size_t i = 0; i < len; i++) {
@@ -135,13 +140,15 @@ struct Strobe {
       if (++pos == RATE) run_f();
     }
   }
+  CPX_HD void challenge_bytes(const char* label, uint8_t* out, size_t len) { challenge_bytes(label, label_len(label), out, len); }
   // CurdleproofsTranscript::get_and_append_challenge (transcript.rs:40-60): 64 challenge bytes, Fr::from_random_bytes
   // on them (first 32 bytes, top bit cleared, must be canonical), retried until non-zero; the scalar is appended
   // back under the same label.  Output: canonical little-endian limbs (NOT Montgomery).
   // One attempt: false when the bytes were refused (the caller retries; nothing was appended).
-  CPX_HD bool challenge_attempt_canonical(const char* label, uint32_t e[8]) {
+  CPX_HD bool challenge_attempt_canonical(const char* label, uint32_t e[8]) { return challenge_attempt_canonical(label, label_len(label), e); }
+  CPX_HD bool challenge_attempt_canonical(const char* label, size_t llen, uint32_t e[8]) {
     uint8_t buf[64];
-    challenge_bytes(label, buf, 64);
+    challenge_bytes(label, llen, buf, 64);
     buf[31] &= 0x7f;
     bool nz = false;
     for (int i = 0; i < 8; i++) {
@@ -156,7 +163,7 @@ struct Strobe {
       }
     }
     if (!(lt && nz)) return false;
-    append_message(label, buf, 32);   // append_scalar: the canonical 32 bytes
+    append_message(label, llen, buf, 32);   // append_scalar: the canonical 32 bytes
     return true;
   }
   CPX_HD void challenge_scalar_canonical(const char* label, uint32_t e[8]) {

@@ -123,6 +123,54 @@ int cpx_g1_msm_many(cpx_ctx* ctx, size_t count, const uint32_t* lens /* count */
  * cpx_g1_fold always takes.  At most 2^24 elements per call (CPX_ERR_ARG, PL untouched). */
 int cpx_g1_fold_many(cpx_ctx* ctx, size_t families, size_t half, uint8_t* PL /* families*half*96 */, const uint8_t* PR /* families*half*96 */,
                      const uint8_t* gammas /* families*32 */);
+/* ---- The log-round loops themselves, one call each, and the transcript as a value ----
+ * The reference's sub-argument provers spend their time in two loops: InnerProductProof::new (inner_product_argument.rs:150-186) and
+ * SameMultiscalarProof::new (same_multiscalar_argument.rs:99-136).  Through the two calls above a round still crosses the bus and
+ * synchronises twice, because the Fiat-Shamir challenge between them is drawn on the host.  The two calls below run all L = log2 n rounds of
+ * `count` independent items on the device, transcript included: one upload, one download, ONE stream synchronisation per call, and a number
+ * of kernel launches that depends on L only (per round the chain of cpx_g1_msm_many, k_finalize and one k_loop_step), never on count.  What that saves is measured by
+ * scripts/loop_rounds_timing.py (profiles/loop_rounds.md).
+ *
+ * A transcript state is CPX_TRANSCRIPT_BYTES = 216 bytes = 27 little-endian u64: the 25 Keccak lanes of merlin's STROBE-128 state, then
+ * `pos`, then `pos_begin`.  merlin's `cur_flags` is not part of it: between whole Merlin messages it has no effect.  The five
+ * cpx_transcript_* calls are host only (no context, no GPU, like cpx_rng_from_u64) and are merlin::Transcript / the crate's
+ * CurdleproofsTranscript operation by operation; labels are byte strings with a length.  A state with pos > 165 or pos_begin > 166 is
+ * CPX_ERR_ARG in every call that takes one, the two device calls included (checked on the host before anything is launched: pos indexes
+ * the state); so are a NULL with work to do and a message or challenge longer than 2^32 - 1 bytes.  On any error the state is left as it was. */
+#define CPX_TRANSCRIPT_BYTES 216
+int cpx_transcript_new(const uint8_t* label, size_t label_len, uint8_t state_out[CPX_TRANSCRIPT_BYTES]);   /* merlin::Transcript::new */
+int cpx_transcript_append_message(uint8_t state[CPX_TRANSCRIPT_BYTES], const uint8_t* label, size_t label_len, const uint8_t* msg, size_t len);
+/* transcript.rs:29-33 `append` on an Fr: its 32 canonical little-endian bytes as one message.  A scalar >= r is CPX_ERR_ARG. */
+int cpx_transcript_append_scalar(uint8_t state[CPX_TRANSCRIPT_BYTES], const uint8_t* label, size_t label_len, const uint8_t scalar_mont[32]);
+int cpx_transcript_challenge_bytes(uint8_t state[CPX_TRANSCRIPT_BYTES], const uint8_t* label, size_t label_len, uint8_t* out, size_t len);
+/* transcript.rs:41-54 `get_and_append_challenge`: 64 challenge bytes, Fr::from_random_bytes, retried until canonical and non-zero, and the
+ * accepted scalar appended back under the same label.  out_mont: Montgomery limbs. */
+int cpx_transcript_challenge_scalar(uint8_t state[CPX_TRANSCRIPT_BYTES], const uint8_t* label, size_t label_len, uint8_t out_mont[32]);
+/* inner_product_argument.rs:150-186 for `count` items of n = 2^L elements each, item by item exactly the reference's loop:
+ *   every round appends L_C, L_D, R_C, R_D (one append_message of the 48 compressed bytes each, label "ipa_loop"; the identity as
+ *   0xc0 || 0^47), draws gamma under "ipa_gamma" (retries and the append-back included), and folds c_L += gamma^-1 c_R, d_L += gamma d_R.
+ *   G, G_prime  the bases as they enter the loop, item after item          H       the point the loop uses (the reference's local
+ *   vec_c, vec_d  the vectors as they enter the loop (:136-139)                    `H = crs_H.mul(beta)`, :140), one per item
+ *   transcripts  in: the states at loop entry; out: advanced by all L rounds
+ *   rounds_compressed / rounds_affine  per item and round L_C, L_D, R_C, R_D; either may be NULL
+ *   finals  per item c_final, d_final                                      gammas  per item the L challenges; may be NULL
+ * The outputs are the group elements the reference computes, so the bytes are bit-exact, though no basis is ever folded here: every cross
+ * term is an MSM over the uploaded bases (curdleproofs_amd/csrc/loop_plan.hpp).  Conventions of the batched tier-0 calls: scalars are
+ * Montgomery limbs, and a scalar >= r is CPX_ERR_ARG for the whole call; points must lie in the subgroup; the identity (96 zero bytes) is a
+ * legal base; count = 0 is a no-op returning CPX_OK; n = 1 runs no round (finals = the inputs, states unchanged); n = 0 or not a power of
+ * two is CPX_ERR_NOT_POW2; NULL with work to do is CPX_ERR_ARG; on any return other than CPX_OK nothing is written, states included; no CRS
+ * is needed and the loaded batch is untouched.  A round is one cpx_g1_msm_many of 4 count tasks: at most 16384 items and
+ * count (2 n + 2) <= 2^24 points per round; more is CPX_ERR_ARG before anything is read.  Scratch is the tier-0 set (two of its 23 buffers
+ * serve these calls alone), trimmed by the same 64 MiB rule. */
+int cpx_ipa_rounds(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G /* count*n*96 */, const uint8_t* G_prime /* count*n*96 */, const uint8_t* H /* count*96 */,
+                   const uint8_t* vec_c /* count*n*32 */, const uint8_t* vec_d /* count*n*32 */, uint8_t* transcripts /* count*216, in/out */,
+                   uint8_t* rounds_compressed /* count*L*4*48, may be NULL */, uint8_t* rounds_affine /* count*L*4*96, may be NULL */,
+                   uint8_t* finals /* count*2*32 */, uint8_t* gammas /* count*L*32, may be NULL */);
+/* same_multiscalar_argument.rs:99-136 likewise: per round L_A, L_T, L_U, R_A, R_T, R_U under "same_msm_loop", gamma under "same_msm_gamma",
+ * x_L += gamma^-1 x_R; finals = x_final.  At most 10922 items and 3 count n <= 2^24 points per round. */
+int cpx_same_msm_rounds(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U /* count*n*96 each */,
+                        const uint8_t* vec_x /* count*n*32 */, uint8_t* transcripts /* count*216, in/out */, uint8_t* rounds_compressed /* count*L*6*48, may be NULL */,
+                        uint8_t* rounds_affine /* count*L*6*96, may be NULL */, uint8_t* finals /* count*32 */, uint8_t* gammas /* count*L*32, may be NULL */);
 /* ark_ec `CurveGroup::normalize_batch` (+ optional `serialize_compressed`); either output may be NULL */
 int cpx_g1_normalize(cpx_ctx* ctx, const uint8_t* jac /* n*144 */, size_t n, uint8_t* out_affine /* n*96 */, uint8_t* out_compressed /* n*48 */);
 /* whisk.rs:318-320 `from_bytes_g1affine` = deserialize_compressed with on-curve + subgroup validation */
@@ -280,7 +328,7 @@ int cpx_whisk_verify_tracker_proofs(cpx_ctx* ctx, size_t count, const uint8_t* t
  * Conventions of the batched tracker calls: count = 0 is a no-op returning CPX_OK; NULL with work to do is CPX_ERR_ARG and nothing is written;
  * no CRS is needed and the loaded batch is untouched; the number of kernel launches does not depend on count.  At most 2^21 items per call
  * (5 count + 256 points within the 2^24 of cpx_g1_msm_many); more is CPX_ERR_ARG before anything is read.  Scratch is the tier-0 set and is
- * trimmed on every exit path: "tier0_scratch_bytes" stays within 33 buffers x 64 MiB afterwards (21 of the tier-0 set, 12 of the shuffle set).  Measurements: profiles/tracker_proofs_grouped.md. */
+ * trimmed on every exit path: "tier0_scratch_bytes" stays within 35 buffers x 64 MiB afterwards (23 of the tier-0 set, 12 of the shuffle set).  Measurements: profiles/tracker_proofs_grouped.md. */
 /* Fused: partial_jac = the sum over all unflagged items (Jacobian, standard form; Z = 0 for the identity), *n_invalid = the flagged items.  The
  * batch is accepted iff n_invalid == 0 and the partials of all calls / contexts / GPUs — these and those of cpx_batch_verify_fused — add up to
  * the identity (cpx_g1_sum_jac).  count = 0: the identity and n_invalid = 0 (both outputs are always required).  ONE stream synchronisation. */

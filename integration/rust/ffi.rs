@@ -54,6 +54,17 @@ extern "C" {
     // one log round in two calls: the cross terms (inner_product_argument.rs:158-161, same_multiscalar_argument.rs:107-112), then the basis folds (:177-178, :128-130)
     pub fn cpx_g1_msm_many(ctx: *mut cpx_ctx, count: usize, lens: *const u32, bases: *const u8, scalars: *const u8, out_jac: *mut u8, out_compressed: *mut u8) -> c_int;
     pub fn cpx_g1_fold_many(ctx: *mut cpx_ctx, families: usize, half: usize, pl: *mut u8, pr: *const u8, gammas: *const u8) -> c_int;
+    // the log-round loops themselves in one call each (inner_product_argument.rs:150-186, same_multiscalar_argument.rs:99-136), `count` items per call,
+    // and the transcript as a 216-byte value (25 Keccak lanes, pos, pos_begin as u64 LE): subargs_mi355x.rs
+    pub fn cpx_transcript_new(label: *const u8, label_len: usize, state_out: *mut u8) -> c_int;
+    pub fn cpx_transcript_append_message(state: *mut u8, label: *const u8, label_len: usize, msg: *const u8, len: usize) -> c_int;
+    pub fn cpx_transcript_append_scalar(state: *mut u8, label: *const u8, label_len: usize, scalar_mont: *const u8) -> c_int;
+    pub fn cpx_transcript_challenge_bytes(state: *mut u8, label: *const u8, label_len: usize, out: *mut u8, len: usize) -> c_int;
+    pub fn cpx_transcript_challenge_scalar(state: *mut u8, label: *const u8, label_len: usize, out_mont: *mut u8) -> c_int;
+    pub fn cpx_ipa_rounds(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, g_prime: *const u8, h: *const u8, vec_c: *const u8, vec_d: *const u8,
+                          transcripts: *mut u8, rounds_compressed: *mut u8, rounds_affine: *mut u8, finals: *mut u8, gammas: *mut u8) -> c_int;
+    pub fn cpx_same_msm_rounds(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, t: *const u8, u: *const u8, vec_x: *const u8, transcripts: *mut u8,
+                               rounds_compressed: *mut u8, rounds_affine: *mut u8, finals: *mut u8, gammas: *mut u8) -> c_int;
     pub fn cpx_g1_normalize(ctx: *mut cpx_ctx, jac: *const u8, n: usize, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
     pub fn cpx_g1_decompress(ctx: *mut cpx_ctx, compressed: *const u8, n: usize, out_affine: *mut u8, check_subgroup: c_int) -> c_int;
     // one verdict per point (0 ok, 1 malformed / not on the curve, 2 outside the subgroup): the square root behind tests/crs.rs:13-52
