@@ -59,7 +59,7 @@ _libs = {}   # realpath -> loaded library (the default one and build variants fo
 
 EXPORTS = [
     "cpx_host_alloc", "cpx_host_free", "cpx_ctx_create", "cpx_ctx_destroy", "cpx_last_error", "cpx_device_count", "cpx_ctx_set_option", "cpx_ctx_get_option", "cpx_ctx_set_crs", "cpx_crs_sums", "cpx_proof_size", "cpx_batch_size",
-    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_ipa_rounds", "cpx_same_msm_rounds",
+    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_ipa_rounds", "cpx_same_msm_rounds", "cpx_ipa_verify", "cpx_same_msm_verify",
     "cpx_transcript_new", "cpx_transcript_append_message", "cpx_transcript_append_scalar", "cpx_transcript_challenge_bytes", "cpx_transcript_challenge_scalar",
     "cpx_g1_normalize", "cpx_g1_decompress", "cpx_g1_decompress_status",
     "cpx_accum_new", "cpx_accum_free", "cpx_accum_check", "cpx_accum_verify",
@@ -117,6 +117,8 @@ def load_library(path=None):
     L.cpx_g1_normalize.argtypes = [vp, vp, sz, vp, vp]
     L.cpx_ipa_rounds.argtypes = [vp, sz, sz] + [vp] * 10
     L.cpx_same_msm_rounds.argtypes = [vp, sz, sz] + [vp] * 9
+    L.cpx_ipa_verify.argtypes = [vp, sz, sz] + [vp] * 11
+    L.cpx_same_msm_verify.argtypes = [vp, sz, sz] + [vp] * 11
     L.cpx_transcript_new.argtypes = [vp, sz, vp]
     L.cpx_transcript_append_message.argtypes = [vp, vp, sz, vp, sz]
     L.cpx_transcript_append_scalar.argtypes = [vp, vp, sz, vp]
@@ -403,6 +405,46 @@ class Context:
             raise ValueError("same_msm_rounds: per item n points in G, T and U and n scalars in vec_x")
         return self._loop_rounds(self._L.cpx_same_msm_rounds, 6, count, n, (G, T, U, vec_x), 1, states, affine)
 
+    def _subarg_verify(self, fn, name, count, n, points, scalars, proofs, rand, states, checks, nchal, proof_bytes, challenges):
+        if n < 0:
+            raise ValueError("n is not negative")
+        if len(states) != count * TRANSCRIPT_BYTES or len(proofs) != count * proof_bytes or len(rand) != count * checks * FR:
+            raise ValueError("%s: per item one 216-byte transcript state, %d proof bytes and %d random factors" % (name, proof_bytes, checks))
+        st = (ctypes.c_uint8 * max(len(states), 1)).from_buffer_copy(bytes(states) if count else b"\0")   # in/out: a copy, the caller's stay
+        chal = _out(count * nchal * FR)
+        ver = (ctypes.c_int * max(count, 1))()
+        self._check(fn(self._h, count, n, *[_in(b) for b in points + scalars], _in(proofs), _in(rand), st, chal if challenges else None, ver))
+        from .whisk import SerializationError
+        marks = {CPX_OK: lambda i: True, CPX_ERR_VERIFY: lambda i: False, CPX_ERR_DESERIALIZE: lambda i: SerializationError("%s: proof %d" % (name, i))}
+        out = dict(verdicts=[marks[ver[i]](i) for i in range(count)], states=bytes(st)[:count * TRANSCRIPT_BYTES])
+        if challenges:
+            out["challenges"] = bytes(chal)[:count * nchal * FR]
+        return out
+
+    def ipa_verify(self, n, G, crs_H, C, D, z, vec_u, proofs, rand, states, challenges=False):
+        """InnerProductProof::verify (inner_product_argument.rs:202-326) for len(z) // 32 independent stand-alone proofs of n elements in ONE
+        call (cpx_ipa_verify), each against an accumulator of its own.  G: the affine bases, item after item; crs_H, C, D: 144-byte Jacobian
+        points; z, vec_u: Montgomery limbs; proofs: the reference's `serialize` bytes; rand: two non-zero random factors per item;
+        states: the 216-byte transcript states before `verify`.  Returns a dict: "verdicts" (per item True, False or a whisk.SerializationError INSTANCE),
+        "states" (advanced by the whole verify; unchanged for an item that does not deserialise), and with challenges=True "challenges"
+        (per item alpha, beta, gamma_1..L)."""
+        count = len(z) // FR
+        L = max(n.bit_length() - 1, 0)
+        if len(z) != count * FR or len(G) != count * n * AFF or len(vec_u) != count * n * FR or any(len(p) != count * JAC for p in (crs_H, C, D)):
+            raise ValueError("ipa_verify: per item n points in G, n scalars in vec_u, one scalar z and one Jacobian point in crs_H, C and D")
+        return self._subarg_verify(self._L.cpx_ipa_verify, "ipa_verify", count, n, (G, crs_H, C, D), (z, vec_u), proofs, rand, states, 2, 2 + L,
+                                   48 * (2 + 4 * L) + 64, challenges)
+
+    def same_msm_verify(self, n, G, T, U, A, Z_t, Z_u, proofs, rand, states, challenges=False):
+        """SameMultiscalarProof::verify (same_multiscalar_argument.rs:153-261) likewise (cpx_same_msm_verify), len(A) // 144 items: three
+        random factors per item; "challenges" holds alpha, gamma_1..L."""
+        count = len(A) // JAC
+        L = max(n.bit_length() - 1, 0)
+        if any(len(p) != count * JAC for p in (A, Z_t, Z_u)) or any(len(v) != count * n * AFF for v in (G, T, U)):
+            raise ValueError("same_msm_verify: per item n points in G, T and U and one Jacobian point in A, Z_t and Z_u")
+        return self._subarg_verify(self._L.cpx_same_msm_verify, "same_msm_verify", count, n, (G, T, U, A, Z_t, Z_u), (), proofs, rand, states, 3, 1 + L,
+                                   48 * (3 + 6 * L) + 32, challenges)
+
     def normalize(self, jac, compressed=False):
         n = len(jac) // JAC
         a, c = _out(AFF * n), _out(48 * n)
@@ -603,7 +645,7 @@ class Context:
         return dict(launches=n.value, ms=ms.value, alg_bytes=by.value, units=un.value)
 
     KERNELS = ("k_msm_tblw<32, false>", "k_reduce_sets", "k_msm_tblw<16, false>", "k_msm_tblw<8, false>", "k_msm_tblw<4, false>", "k_msm_tblw<2, false>", "k_msm_fix<19, 7>", "k_msm_fix<16, 4>", "k_msm_fix<16, 2>", "k_msm_fix<16, 16>", "k_msm_fix<16, 8>", "k_msm_fix<8, 16>", "k_msm_fix<8, 8>",
-               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_run_gather", "k_run_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
+               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_run_gather", "k_run_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor", "k_subarg_scalars", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
 
     def stats(self):
         return {k: self.stat(k) for k in self.KERNELS}

@@ -638,6 +638,23 @@ int cpx_same_msm_rounds(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, 
   });
 }
 
+int cpx_ipa_verify(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D, const uint8_t* z, const uint8_t* vec_u,
+                   const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
+  if (count && n && (!G || !crs_H || !C || !D || !z || !vec_u || !proofs || !rand || !transcripts || !verdicts)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->ipa_verify(count, n, G, crs_H, C, D, z, vec_u, proofs, rand, transcripts, challenges, verdicts);
+    return (int)CPX_OK;
+  });
+}
+int cpx_same_msm_verify(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t, const uint8_t* Z_u,
+                        const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
+  if (count && n && (!G || !T || !U || !A || !Z_t || !Z_u || !proofs || !rand || !transcripts || !verdicts)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->same_msm_verify(count, n, G, T, U, A, Z_t, Z_u, proofs, rand, transcripts, challenges, verdicts);
+    return (int)CPX_OK;
+  });
+}
+
 int cpx_set_profiling(cpx_ctx* ctx, int on) {
   if (!ctx || !ctx->eng) return CPX_ERR_ARG;
   ctx->eng->set_profiling(on != 0);

@@ -998,6 +998,118 @@ void Engine::loop_rounds(bool ipa, size_t count, size_t n, const uint8_t* const 
       if (rounds_aff) memcpy(rounds_aff + dst * sizeof(Aff), h_aff.data() + src * sizeof(Aff), terms * sizeof(Aff));
     }
 }
+// The stand-alone sub-argument verifiers (include/cpx.h cpx_ipa_verify, cpx_same_msm_verify): InnerProductProof::verify
+// (inner_product_argument.rs:202-326) / SameMultiscalarProof::verify (same_multiscalar_argument.rs:153-261) for `count` independent items,
+// each against an MsmAccumulator of its own, flattened by subarg_check_plan.hpp into one MSM per item.  One upload; k_decompress with
+// status over every proof point of the call, k_finalize over the statement points (their affine forms into the items' rows, their encodings
+// for the transcript), for SameMSM k_compress over T | U, k_subarg_scalars (subarg.hip), the MSM chain above with one task per item; one
+// download of the sums, flags, states and challenges; one synchronisation.  The launches do not depend on count.  fam: G resp. G | T | U;
+// stmt: crs_H | C | D resp. A | Z_t | Z_u.  The outputs are written when the call has succeeded, never before.
+void Engine::ipa_verify(size_t count, size_t n, const uint8_t* G, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D, const uint8_t* z, const uint8_t* vec_u,
+                        const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
+  const uint8_t *fam[3] = {G, nullptr, nullptr}, *stmt[3] = {crs_H, C, D};
+  subarg_verify(true, count, n, fam, stmt, z, vec_u, proofs, rand, transcripts, challenges, verdicts);
+}
+void Engine::same_msm_verify(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t, const uint8_t* Z_u,
+                             const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
+  const uint8_t *fam[3] = {G, T, U}, *stmt[3] = {A, Z_t, Z_u};
+  subarg_verify(false, count, n, fam, stmt, nullptr, nullptr, proofs, rand, transcripts, challenges, verdicts);
+}
+void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* vec_u,
+                           const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
+  if (!count) return;
+  SubargCheckPlan sp;
+  switch (subarg_check_plan(ipa, count, n, sp)) {
+    case SUBARG_NOT_POW2: throw std::invalid_argument("the sub-argument verifiers take n = 2^L elements per item, L >= 0");
+    case SUBARG_TOO_LARGE: throw ArgError(ipa ? "cpx_ipa_verify: at most 65536 items and count (n + 4 L + 5) <= 2^24 points"
+                                              : "cpx_same_msm_verify: at most 65536 items and count (3 n + 6 L + 6) <= 2^24 points");
+    default: break;
+  }
+  const size_t NP = sp.points(), PP = sp.proof_points(), PB = sp.proof_bytes(), NC = sp.challenges(), K = SubargCheckPlan::kStatement;
+  for (size_t i = 0; i < count * (size_t)sp.checks(); i++)
+    if (!host::is_valid_factor(rand + 32 * i)) throw ArgError("the random factors of a sub-argument check must be non-zero reduced field elements");
+  if (ipa) {
+    for (size_t i = 0; i < count; i++)
+      if (!fr_wire_reduced(z + i * sizeof(Fr))) throw ArgError("a scalar z of cpx_ipa_verify is not reduced");
+    for (size_t i = 0; i < count * n; i++)
+      if (!fr_wire_reduced(vec_u + i * sizeof(Fr))) throw ArgError("a scalar of vec_u is not reduced");
+  }
+  for (size_t i = 0; i < count; i++)
+    if (!transcript_state_valid(transcripts + i * kTranscriptBytes)) throw ArgError("a transcript state with pos > 165 or pos_begin > 166");
+  // host memory the enqueued copies read or write: above the scope
+  std::vector<MsmTask> tasks;
+  std::vector<uint32_t> ix, lens;
+  std::vector<uint8_t> canon, h_states, h_bad;
+  std::vector<size_t> point_bytes(PP);
+  std::vector<Fr> h_chal;
+  std::vector<Jac> h_res;
+  Tier0MsmPlan pl;
+  if (!sp.msm(pl, lens)) throw ArgError("the items exceed the limits of cpx_g1_msm_many");
+  for (size_t s = 0; s < PP; s++) point_bytes[s] = sp.point_byte(s);
+  proofs = canonical_infinities(proofs, count * PB, count, PB, point_bytes, canon);
+  CallScope call(this);
+  pl.slices = msm_tblw_slices(opt_, (int)count, 2, (int)pl.max_n);
+  DevBuf<Aff>& rows = t0_.a0;
+  DevBuf<Fr>& dfr = t0_.fr;
+  DevBuf<uint8_t>&db = t0_.bytes, &dst = t0_.status;   // dst: the decoder's verdicts [count][PP] | the items' flags [count]
+  DevBuf<Jac>&din = t0_.jin, &res = t0_.res;
+  rows.ensure(count * NP);
+  dfr.ensure(sp.fr_total());
+  db.ensure(sp.by_total());
+  dst.ensure(count * PP + count);
+  din.ensure(count * K);
+  res.ensure(count);
+  t0_.lidx.ensure(sp.ix_total());
+  t0_.lstate.ensure(count * kTranscriptWords);
+  msm_chain_reserve(pl);
+  // ---- the one upload: bases and statement points into their places, proofs, scalars, index words, states
+  for (int f = 0; f < sp.families(); f++)
+    CPX_HIP(hipMemcpy2DAsync(rows.p + sp.base_off(f), NP * sizeof(Aff), fam[f], n * sizeof(Aff), n * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
+  for (size_t k = 0; k < K; k++)
+    CPX_HIP(hipMemcpy2DAsync(din.p + k, K * sizeof(Jac), stmt[k], sizeof(Jac), sizeof(Jac), count, hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(db.p + sp.by_proofs(), proofs, count * PB, hipMemcpyHostToDevice, stream_));
+  if (ipa) {
+    CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_z(), z, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_u(), vec_u, count * n * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  }
+  CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_rand(), rand, count * (size_t)sp.checks() * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  sp.fill_idx(ix);
+  CPX_HIP(hipMemcpyAsync(t0_.lidx.p, ix.data(), ix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(t0_.lstate.p, transcripts, count * kTranscriptBytes, hipMemcpyHostToDevice, stream_));
+  // ---- the device work
+  tick("k_decompress", 0, (double)(count * PP));
+  launch_decompress(opt_, db.p, (int)(count * PP), rows.p, t0_.lidx.p + sp.ix_dst(), dst.p, 1, stream_, t0_.lidx.p + sp.ix_src());
+  tock();
+  tick("k_finalize", 0, (double)(count * K));
+  launch_finalize(din.p, (int)(count * K), rows.p, t0_.lidx.p + sp.ix_statement(), db.p + sp.by_statement(), stream_);
+  tock();
+  if (!ipa) {
+    tick("k_compress", 0, 2.0 * count * n, true);
+    for (size_t i = 0; i < count; i += 65535) {   // (a row per item in the grid's second dimension: 65535 at most; 2^16 items take two launches)
+      const size_t rows_now = std::min<size_t>(count - i, 65535);
+      launch_compress(rows.p + i * NP + sp.base_off(1), (int)(2 * n), (int)NP, (int)rows_now, db.p + sp.by_tu() + i * 2 * n * 48, stream_);
+    }
+    tock();
+  }
+  uint8_t* const d_bad = dst.p + count * PP;
+  tick("k_subarg_scalars", 0, (double)count, true);
+  launch_subarg_scalars(SubargDev{sp, dfr.p, db.p, dst.p, d_bad, t0_.lstate.p}, stream_);
+  tock();
+  msm_chain(pl, lens.data(), rows.p, dfr.p + sp.fr_weights(), res.p, tasks);
+  // ---- the one download, into host memory of the call: the caller's buffers are written once everything has arrived
+  h_res.resize(count);
+  h_bad.resize(count);
+  h_states.resize(count * kTranscriptBytes);
+  h_chal.resize(count * NC);
+  CPX_HIP(hipMemcpyAsync(h_res.data(), res.p, count * sizeof(Jac), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(h_bad.data(), d_bad, count, hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(h_states.data(), t0_.lstate.p, h_states.size(), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(h_chal.data(), dfr.p + sp.fr_challenges(), count * NC * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
+  call.finish();
+  memcpy(transcripts, h_states.data(), h_states.size());
+  if (challenges) memcpy(challenges, h_chal.data(), count * NC * sizeof(Fr));
+  for (size_t i = 0; i < count; i++) verdicts[i] = h_bad[i] ? CPX_ERR_DESERIALIZE : h_res[i].is_identity() ? CPX_OK : CPX_ERR_VERIFY;
+}
 // The basis folds of one log round (inner_product_argument.rs:177-178: 2 families, same_multiscalar_argument.rs:128-130: 3) as ONE call:
 // a SmulTask per family, each with its own gamma shared by its `half` elements, in one launch_smul.  A round's folds are small (3 x 128
 // elements at ell = 252), so up to option fold_quad_max elements the launch takes the quad-per-element form (tier0_plan.hpp).

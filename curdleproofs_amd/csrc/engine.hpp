@@ -34,6 +34,7 @@
 #include "tbl_plan.hpp"
 #include "tier0_plan.hpp"
 #include "loop_plan.hpp"
+#include "subarg_check_plan.hpp"
 #include "transcript_state.hpp"
 
 namespace cpx {
@@ -183,6 +184,13 @@ class Engine {
                   uint8_t* rounds_comp, uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas);                                              // inner_product_argument.rs:150-186
   void same_msm_rounds(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* vec_x, uint8_t* transcripts, uint8_t* rounds_comp,
                        uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas);                                                               // same_multiscalar_argument.rs:99-136
+  // the verifiers of the two sub-arguments on the caller's bases, `count` independent items per call, each against an accumulator of its own
+  // (subarg_check_plan.hpp, subarg.hip; include/cpx.h cpx_ipa_verify / cpx_same_msm_verify): states in/out, per-item verdicts; no CRS, the
+  // batch is left alone
+  void ipa_verify(size_t count, size_t n, const uint8_t* G, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D, const uint8_t* z, const uint8_t* vec_u,
+                  const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts);                     // inner_product_argument.rs:202-326
+  void same_msm_verify(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t, const uint8_t* Z_u,
+                       const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts);                // same_multiscalar_argument.rs:153-261
   void normalize(const uint8_t* jac, size_t n, uint8_t* out_aff, uint8_t* out_comp);                   // normalize_batch (+compress)
   int decompress(const uint8_t* comp, size_t n, uint8_t* out_aff, int check_subgroup, uint8_t* status_out = nullptr);   // whisk.rs:318-320
 
@@ -487,6 +495,9 @@ class Engine {
   // the one body of ipa_rounds / same_msm_rounds (engine.cpp).  fam: G | G' | H resp. G | T | U; vec: c | d resp. x
   void loop_rounds(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const vec[2], uint8_t* transcripts, uint8_t* rounds_comp,
                    uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas);
+  // the one body of ipa_verify / same_msm_verify (engine.cpp).  fam: G resp. G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u
+  void subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* vec_u,
+                     const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts);
   // n trackers -> the planes r_G | k_r_G: upload + k_decompress of the tracker prover, find-trackers and the candidate list (whisk.cpp)
   void decode_tracker_planes(size_t n, const uint8_t* trackers, std::vector<uint8_t>& canon, std::vector<uint32_t>& off, uint8_t* d_bytes, uint32_t* d_off, Aff* d_pts,
                              uint8_t* d_status);

@@ -4,6 +4,7 @@
 #include <initializer_list>
 #include "g1.hpp"
 #include "g1_28.hpp"
+#include "subarg_check_plan.hpp"
 
 namespace cpx {
 
@@ -244,6 +245,18 @@ struct LoopDev {
   int count, n, L;
 };
 void launch_loop_step(bool ipa, const LoopDev& d, int j, hipStream_t s);
+// The transcript and scalar step of cpx_ipa_verify / cpx_same_msm_verify for pl.count items (subarg.hip; every layout: subarg_check_plan.hpp):
+// from the decoder's verdicts, the proofs' bytes and the encodings of the statement points (and of T | U) it writes per item the
+// deserialisation flag, the advanced transcript state, the challenges and the row of weights of the flattened check
+struct SubargDev {
+  SubargCheckPlan pl;
+  Fr* fr;                  // weights | z | vec_u | random factors | challenges
+  const uint8_t* bytes;    // proofs | statement encodings | T, U encodings
+  const uint8_t* status;   // [count][proof_points]: k_decompress
+  uint8_t* bad;            // [count]: 1 = the item does not deserialise
+  uint64_t* states;        // [count][27]
+};
+void launch_subarg_scalars(const SubargDev& d, hipStream_t s);
 // transcript prefix of every proof: absorbs the compressed instance ([nproofs][4*ell*48] + [nproofs][48] for M), draws vec_a;
 // d_state: [nproofs][27] u64 (25 STROBE lanes, pos, pos_begin), d_vec_a: [nproofs][ell] Fr
 // lane_per_proof: one lane instead of 32 per transcript (large batches: a fifth of the wave instructions, a longer chain)

@@ -15,6 +15,8 @@
 #include "protocol.h"
 #include "kernels.h"   // take_launch_events: the profiling hook of the launchers
 #include "check_weights.hpp"
+#include "round_algebra.hpp"       // load_scalar
+#include "subarg_check_plan.hpp"   // verification_scalar
 
 namespace cpx {
 
@@ -422,20 +424,6 @@ struct VerifyView {
   __device__ uint64_t* tstate() const { return d.tstate + (size_t)p * 27; }
   __device__ const Fr* rnd() const { return d.rnd + (size_t)p * d.rand_stride; }
 };
-// canonical little-endian scalar -> Montgomery; false (and zero) if >= r  (Fr::deserialize_compressed)
-__device__ bool load_scalar(const uint8_t* b, Fr& out) {
-  Fr c;
-  CPX_UNROLL for (int j = 0; j < 8; j++) c.v[j] = (uint32_t)b[4 * j] | ((uint32_t)b[4 * j + 1] << 8) | ((uint32_t)b[4 * j + 2] << 16) | ((uint32_t)b[4 * j + 3] << 24);
-  bool lt = false;
-  for (int j = 7; j >= 0; j--) {
-    if (c.v[j] != FrCfg::P[j]) {
-      lt = c.v[j] < FrCfg::P[j];
-      break;
-    }
-  }
-  out = lt ? fe_to_mont(c) : Fr::zero();
-  return lt;
-}
 __device__ Fr fr_pow_u32(const Fr& a, uint32_t e) {
   Fr r = Fr::one();
   for (int i = 31; i >= 0; i--) {
@@ -614,12 +602,7 @@ __global__ __launch_bounds__(64) void k_vs_scalars(const VerifyDev d) {
   Fr* out = d.scal + (size_t)v.p * NPT;
   Fr* out_crs = d.scal_crs + (size_t)v.p * n;
   // verification scalars s_i = prod_{j : bit (L-1-j) of i set} gamma_j  (util.rs:40-64)
-  auto svec = [&](const Fr* g, int i) {
-    Fr r = Fr::one();
-    for (int j = 0; j < L; j++)
-      if ((i >> (L - 1 - j)) & 1) r = fe_mul(r, g[j]);
-    return r;
-  };
+  auto svec = [&](const Fr* g, int i) { return verification_scalar(g, L, i); };
   Fr sm_l2 = Fr::zero(), sm_l3 = Fr::zero();   // s_m[ell + 2], s_m[ell + 3]
   for (int i = lane; i < n; i += 64) {
     const Fr s_i = svec(w.gam_i, i), s_i_inv = svec(w.gam_i_inv, i), s_m = svec(w.gam_m, i);

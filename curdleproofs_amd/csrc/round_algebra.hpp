@@ -1,6 +1,7 @@
 // Fr algebra of one log round of the all-MSM form for ONE item on the threads of its work-group — device code.
 // The bodies of k_ipa_round_scalars / k_ipa_round_fold / k_smsm_round_scalars / k_smsm_round_fold (kernels.hip: the batch prover's
 // stand-alone launches) and of k_loop_step (loop.hip: the whole tail of a round of cpx_ipa_rounds / cpx_same_msm_rounds), written once.
+// At the end load_scalar, a proof's scalar off the wire, for the verifier kernels (protocol.hip k_vs_prefix, subarg.hip k_subarg_scalars).
 //
 // Round j of n = 2^L elements: half = n >> (j+1); original base k has bit `half` set (hi) or clear (lo); the t-th lo index is
 // kl = (t / half) * 2 half + t % half, the t-th hi index kh = kl + half (t < n/2) — the lists loop_plan.hpp hands the MSM tasks.
@@ -78,6 +79,22 @@ __device__ __forceinline__ void smsm_round_fold_body(Fr* __restrict__ x, Fr* __r
     const int kh = (t / half) * 2 * half + (t % half) + half;
     SM[kh] = fe_mul(SM[kh], g);
   }
+}
+
+// ---- a scalar of a proof off the wire ----
+// canonical little-endian scalar -> Montgomery; false (and zero) if >= r  (Fr::deserialize_compressed)
+__device__ inline bool load_scalar(const uint8_t* b, Fr& out) {
+  Fr c;
+  CPX_UNROLL for (int j = 0; j < 8; j++) c.v[j] = (uint32_t)b[4 * j] | ((uint32_t)b[4 * j + 1] << 8) | ((uint32_t)b[4 * j + 2] << 16) | ((uint32_t)b[4 * j + 3] << 24);
+  bool lt = false;
+  for (int j = 7; j >= 0; j--) {
+    if (c.v[j] != FrCfg::P[j]) {
+      lt = c.v[j] < FrCfg::P[j];
+      break;
+    }
+  }
+  out = lt ? fe_to_mont(c) : Fr::zero();
+  return lt;
 }
 
 }  // namespace cpx

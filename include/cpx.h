@@ -171,6 +171,37 @@ int cpx_ipa_rounds(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G /* cou
 int cpx_same_msm_rounds(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U /* count*n*96 each */,
                         const uint8_t* vec_x /* count*n*32 */, uint8_t* transcripts /* count*216, in/out */, uint8_t* rounds_compressed /* count*L*6*48, may be NULL */,
                         uint8_t* rounds_affine /* count*L*6*96, may be NULL */, uint8_t* finals /* count*32 */, uint8_t* gammas /* count*L*32, may be NULL */);
+/* InnerProductProof::verify (inner_product_argument.rs:202-326, its scalars :202-262) for `count` independent stand-alone proofs over n = 2^L
+ * bases each, item by item what the reference computes against an MsmAccumulator of its own (msm_accumulator.rs:37-68):
+ *   G, crs_H     the bases (`crs_G_vec`, affine) and the point crs_H     C, D, z   the statement; vec_u as in :262, :308-317
+ *   proofs       the reference's own `serialize` bytes (inner_product_argument.rs:328-338): B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D
+ *                compressed, then c_final, d_final as canonical little-endian scalars
+ *   rand         per item the two values `accumulate_check` would draw (msm_accumulator.rs:44), in call order; a zero or unreduced value
+ *                is CPX_ERR_ARG for the whole call, as in cpx_accum_check
+ *   transcripts  in: the states before `verify`; out: advanced by the whole `verify`, step 1 (:283-287) included, whatever the verdict
+ *   challenges   per item alpha, beta, gamma_1..L (Montgomery limbs); may be NULL
+ *   verdicts     per item CPX_OK, CPX_ERR_VERIFY (the item's accumulator does not verify, :55-68), or CPX_ERR_DESERIALIZE: a point that
+ *                does not decode or lies outside the subgroup, or a scalar >= r.  The reference never reaches `verify` for such bytes: the
+ *                item's state is returned unchanged and its challenges are zero.
+ * crs_H, C, D are 144-byte Jacobian points, any representative, Z = 0 for the identity (what cpx_g1_msm* return and cpx_accum_check takes);
+ * G is affine under the tier-0 precondition (in the subgroup, the identity legal); z, vec_u are Montgomery limbs, a value >= r is CPX_ERR_ARG.
+ * Encodings of the identity inside a proof follow option strict_infinity as in the batched verifiers.  n = 1 is a real check (L = 0, no round
+ * points, s = [1]); n = 0 or not a power of two is CPX_ERR_NOT_POW2; count = 0 is a no-op returning CPX_OK; NULL with work to do and an
+ * invalid transcript state are CPX_ERR_ARG.  An item is one task of one cpx_g1_msm_many over its n + 4 L + 5 points
+ * (curdleproofs_amd/csrc/subarg_check_plan.hpp): at most 2^16 items and 2^24 points per call, checked before anything is read.  On any
+ * return other than CPX_OK nothing is written.  One upload, one download, one stream synchronisation; launches that depend on L only; no
+ * CRS is needed and the loaded batch is untouched.  Scratch is the tier-0 set. */
+int cpx_ipa_verify(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G /* count*n*96 */, const uint8_t* crs_H /* count*144 */, const uint8_t* C /* count*144 */,
+                   const uint8_t* D /* count*144 */, const uint8_t* z /* count*32 */, const uint8_t* vec_u /* count*n*32 */,
+                   const uint8_t* proofs /* count*(48*(2+4L)+64) */, const uint8_t* rand /* count*2*32 */, uint8_t* transcripts /* count*216, in/out */,
+                   uint8_t* challenges /* count*(2+L)*32, may be NULL */, int* verdicts /* count */);
+/* SameMultiscalarProof::verify (same_multiscalar_argument.rs:153-261) likewise: bases G, T, U (vec_T and vec_U are hashed in step 1 from
+ * their encodings, :230-233), statement A, Z_t, Z_u; proofs are B_a, B_t, B_u, vec_L_A, vec_L_T, vec_L_U, vec_R_A, vec_R_T, vec_R_U, x_final
+ * (same_multiscalar_argument.rs:263-275); three random factors per item; challenges are alpha, gamma_1..L; 3 n + 6 L + 6 points per item. */
+int cpx_same_msm_verify(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U /* count*n*96 each */, const uint8_t* A,
+                        const uint8_t* Z_t, const uint8_t* Z_u /* count*144 each */, const uint8_t* proofs /* count*(48*(3+6L)+32) */,
+                        const uint8_t* rand /* count*3*32 */, uint8_t* transcripts /* count*216, in/out */, uint8_t* challenges /* count*(1+L)*32, may be NULL */,
+                        int* verdicts /* count */);
 /* ark_ec `CurveGroup::normalize_batch` (+ optional `serialize_compressed`); either output may be NULL */
 int cpx_g1_normalize(cpx_ctx* ctx, const uint8_t* jac /* n*144 */, size_t n, uint8_t* out_affine /* n*96 */, uint8_t* out_compressed /* n*48 */);
 /* whisk.rs:318-320 `from_bytes_g1affine` = deserialize_compressed with on-curve + subgroup validation */

@@ -65,6 +65,12 @@ extern "C" {
                           transcripts: *mut u8, rounds_compressed: *mut u8, rounds_affine: *mut u8, finals: *mut u8, gammas: *mut u8) -> c_int;
     pub fn cpx_same_msm_rounds(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, t: *const u8, u: *const u8, vec_x: *const u8, transcripts: *mut u8,
                                rounds_compressed: *mut u8, rounds_affine: *mut u8, finals: *mut u8, gammas: *mut u8) -> c_int;
+    // the verifiers of the two sub-arguments on the caller's bases (inner_product_argument.rs:202-326, same_multiscalar_argument.rs:153-261), `count`
+    // stand-alone proofs per call, each against an accumulator of its own; verdicts[i] = CPX_OK / CPX_ERR_VERIFY / CPX_ERR_DESERIALIZE: subargs_mi355x.rs
+    pub fn cpx_ipa_verify(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, crs_h: *const u8, c: *const u8, d: *const u8, z: *const u8, vec_u: *const u8,
+                          proofs: *const u8, rand: *const u8, transcripts: *mut u8, challenges: *mut u8, verdicts: *mut c_int) -> c_int;
+    pub fn cpx_same_msm_verify(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, t: *const u8, u: *const u8, a: *const u8, z_t: *const u8, z_u: *const u8,
+                               proofs: *const u8, rand: *const u8, transcripts: *mut u8, challenges: *mut u8, verdicts: *mut c_int) -> c_int;
     pub fn cpx_g1_normalize(ctx: *mut cpx_ctx, jac: *const u8, n: usize, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
     pub fn cpx_g1_decompress(ctx: *mut cpx_ctx, compressed: *const u8, n: usize, out_affine: *mut u8, check_subgroup: c_int) -> c_int;
     // one verdict per point (0 ok, 1 malformed / not on the curve, 2 outside the subgroup): the square root behind tests/crs.rs:13-52

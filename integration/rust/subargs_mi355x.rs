@@ -1,6 +1,6 @@
 //! The two sub-argument provers with their log-round loops replaced by ONE library call each, and `transcript.rs` backed by the
-//! 216-byte transcript value of the C ABI (include/cpx.h `cpx_transcript_*`, `cpx_ipa_rounds`, `cpx_same_msm_rounds`), under
-//! `--features mi355x`.  NOT COMPILED in the build image.
+//! 216-byte transcript value of the C ABI (include/cpx.h `cpx_transcript_*`, `cpx_ipa_rounds`, `cpx_same_msm_rounds`), and the two
+//! verifiers as ONE library call each (`cpx_ipa_verify`, `cpx_same_msm_verify`), under `--features mi355x`.  NOT COMPILED in the build image.
 //!
 //! `merlin::Transcript` keeps its state private, so a transcript that the library is to continue has to live on the library's side of
 //! the boundary from the start: `Transcript216` below holds the value and implements the crate's `CurdleproofsTranscript` on it.  The
@@ -10,7 +10,9 @@
 
 use ark_bls12_381::{Fr, G1Affine, G1Projective};
 use ark_ff::BigInt;
-use ark_serialize::CanonicalSerialize;
+use ark_serialize::{CanonicalSerialize, SerializationError};
+use ark_std::rand::RngCore;
+use ark_std::UniformRand;
 
 use crate::ffi::*;
 
@@ -123,4 +125,57 @@ pub fn ipa_rounds_many(n: usize, G: &[u8], G_prime: &[u8], H: &[u8], vec_c: &[Fr
                        affine_out.as_mut_ptr(), finals_out.as_mut_ptr(), std::ptr::null_mut())
     };
     assert_eq!(rc, CPX_OK, "cpx_ipa_rounds");
+}
+
+/// `count` non-zero draws of `Fr::rand`, what `MsmAccumulator::accumulate_check` would draw (msm_accumulator.rs:44), as wire bytes
+fn draw_factors<T: RngCore>(rng: &mut T, count: usize) -> Vec<u8> {
+    let mut drawn = Vec::with_capacity(count);
+    while drawn.len() < count {
+        let a = Fr::rand(rng);
+        if a != Fr::from(0u64) {
+            drawn.push(a);
+        }
+    }
+    let mut out = vec![0u8; count * FR];
+    out.copy_from_slice(unsafe { std::slice::from_raw_parts(scalars_ptr(&drawn), count * FR) });
+    out
+}
+
+fn verdict(rc: std::os::raw::c_int, v: std::os::raw::c_int, what: &str) -> Result<bool, SerializationError> {
+    assert_eq!(rc, CPX_OK, "{}", what);
+    match v {
+        CPX_OK => Ok(true),
+        CPX_ERR_VERIFY => Ok(false),
+        _ => Err(SerializationError::InvalidData), // CPX_ERR_DESERIALIZE: the reference fails in `deserialize`, before `verify`
+    }
+}
+
+/// InnerProductProof::deserialize + verify (inner_product_argument.rs:340-352, :264-326) against an MsmAccumulator of its own, in one
+/// call: `proof` holds the bytes `serialize` wrote (:328-338).  Ok(true): the accumulator verifies; Ok(false): it does not; Err: the bytes
+/// do not decode, and the transcript is as it was.  Otherwise the transcript is advanced by the whole `verify`.
+pub fn ipa_verify<T: RngCore>(proof: &[u8], crs_G_vec: &[G1Affine], crs_H: &G1Projective, C: &G1Projective, D: &G1Projective, z: &Fr, vec_u: &[Fr],
+                              transcript: &mut Transcript216, rng: &mut T) -> Result<bool, SerializationError> {
+    let n = crs_G_vec.len();
+    let rand = draw_factors(rng, 2);
+    let mut v: std::os::raw::c_int = CPX_ERR_VERIFY;
+    let rc = unsafe {
+        cpx_ipa_verify(ctx(), 1, n, affine_to_wire(crs_G_vec).as_ptr(), projective_to_wire(std::slice::from_ref(crs_H)).as_ptr(),
+                       projective_to_wire(std::slice::from_ref(C)).as_ptr(), projective_to_wire(std::slice::from_ref(D)).as_ptr(), scalars_ptr(std::slice::from_ref(z)),
+                       scalars_ptr(vec_u), proof.as_ptr(), rand.as_ptr(), transcript.0.as_mut_ptr(), std::ptr::null_mut(), &mut v)
+    };
+    verdict(rc, v, "cpx_ipa_verify")
+}
+
+/// SameMultiscalarProof::deserialize + verify (same_multiscalar_argument.rs:276-290, :213-261) likewise; three draws.
+pub fn same_msm_verify<T: RngCore>(proof: &[u8], crs_G_vec: &[G1Affine], A: &G1Projective, Z_t: &G1Projective, Z_u: &G1Projective, vec_T: &[G1Affine], vec_U: &[G1Affine],
+                                   transcript: &mut Transcript216, rng: &mut T) -> Result<bool, SerializationError> {
+    let n = vec_T.len();
+    let rand = draw_factors(rng, 3);
+    let mut v: std::os::raw::c_int = CPX_ERR_VERIFY;
+    let rc = unsafe {
+        cpx_same_msm_verify(ctx(), 1, n, affine_to_wire(crs_G_vec).as_ptr(), affine_to_wire(vec_T).as_ptr(), affine_to_wire(vec_U).as_ptr(),
+                            projective_to_wire(std::slice::from_ref(A)).as_ptr(), projective_to_wire(std::slice::from_ref(Z_t)).as_ptr(),
+                            projective_to_wire(std::slice::from_ref(Z_u)).as_ptr(), proof.as_ptr(), rand.as_ptr(), transcript.0.as_mut_ptr(), std::ptr::null_mut(), &mut v)
+    };
+    verdict(rc, v, "cpx_same_msm_verify")
 }
