@@ -54,7 +54,7 @@ Engine::~Engine() {
     if (e) (void)hipEventDestroy(e);
   if (tab_.stream) (void)hipStreamDestroy(tab_.stream);
   if (tab_.dstream) (void)hipStreamDestroy(tab_.dstream);
-  for (hipEvent_t e : {dprove_.ev_a, dprove_.ev_b, dprove_.ev_c, dprove_.ev_d, dprove_.ev_t1, dprove_.ev_t2, dprove_.ev_a2, dverify_.ev_a, dverify_.ev_b})
+  for (hipEvent_t e : {dprove_.ev_a, dprove_.ev_b, dprove_.ev_c, dprove_.ev_d, dprove_.ev_t1, dprove_.ev_t2, dprove_.ev_a2, dprove_.ev_ap, dprove_.ev_rs, dverify_.ev_a, dverify_.ev_b})
     if (e) (void)hipEventDestroy(e);
   if (stage_.uploaded) (void)hipEventDestroy(stage_.uploaded);
   if (stage_.consumed) (void)hipEventDestroy(stage_.consumed);

@@ -418,6 +418,13 @@ class Engine {
       const uint32_t* gb_cols = nullptr;
     } late;
     const uint32_t* side_cols = nullptr;
+    // R and S from the per-proof tables (option rs_from_tables; prove_reqs.hpp prove_rs_tables / prove_rs_sums): k R, k S as table requests
+    // behind the table build, cm_T.T_2 and cm_U.T_2 as sums on the side stream, whose four scalar multiplications become stasks_tbl
+    TblPlan prs, prs_sum;
+    DevBuf<SmulTask> stasks_tbl;
+    const uint32_t* side_cols_tbl = nullptr;   // R, S, cm_A.T_2, cm_B.T_2: the side stream's points that prs_sum has not compressed
+    bool rs_tables = false;                    // this prove takes that path (batch_prove_device decides: the option, no k = 0, k on the host)
+    hipEvent_t ev_ap = nullptr, ev_rs = nullptr;   // ap: V_APERM and the side stream's scalars are there, rs: k R and k S are in their slots
     hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr, ev_t1 = nullptr, ev_t2 = nullptr, ev_a2 = nullptr;   // t1: tables built, t2: B_t, B_u in the registry, a2: the prefix stream is about to launch
   };
   DevProver dprove_;
@@ -599,6 +606,7 @@ class Engine {
     ~Untimed() { on = was; }
   };
   void prepare_device_prover();
+  void ensure_rs_scratch();
   // Where the device-resident prover finds its witnesses and draws.  kind: the side of perm / k / mbl (host: uploaded, device: copied on the
   // device).  rand: the 3n + 9 draws per proof on the host, or null: k_rng_draw makes them in dp.rnd from the states in rng_.states, which
   // states_in (host, nullable: they are there already) fills first and states_out (host) receives, advanced, when the prove has ended.

@@ -129,13 +129,12 @@ void Engine::prepare_device_prover() {
   side_.stasks.ensure(4 * B);
   side_.res.ensure(2 * B);
   side_.dst.ensure(2 * B);
-  side_.conv.ensure(4 * B * ell);
   side_.ttasks.ensure(2 * B);
-  side_.digits.ensure(9 * 2 * B * ell);
-  side_.scr.ensure(2 * B * 32, 2 * B * 32);
+  dp.stasks_tbl.ensure(4 * B);
+  if (!opt_.rs_from_tables) ensure_rs_scratch();   // (else on demand: a batch that falls back to the bucket MSMs)
   const std::vector<const void*> sig = {d_pp_.p,     d_ptab_.p,    d_psrc_.p,  d_bytes_.p,  d_mcomp_.p,   d_tstate_.p,   d_veca_.p,      d_rvec_.p,
                                         dp.rvec2.p,  d_rgam_.p,    d_rbeta_.p, d_rout_.p,   dp.perm.p,    dp.k.p,        dp.mbl.p,       dp.rnd.p,
-                                        dp.vec.p,    dp.sc.p,      dp.slotcomp.p, dp.proofs.p, side_.tasks.p, side_.stasks.p, side_.dst.p, side_.conv.p,
+                                        dp.vec.p,    dp.sc.p,      dp.slotcomp.p, dp.proofs.p, side_.tasks.p, side_.stasks.p, side_.dst.p, dp.stasks_tbl.p,
                                         ctab(),      fixtab(),     (const void*)(uintptr_t)B, (const void*)(uintptr_t)ell, (const void*)(uintptr_t)fix_bits_,
                                         (const void*)(uintptr_t)pcopies_};
   if (sig == dp.signature) return;
@@ -146,6 +145,7 @@ void Engine::prepare_device_prover() {
   d.n = (int)n;
   d.L = (int)L;
   d.NS = (int)NS;
+  d.rs_tables = 0;   // (enqueue_prove_device sets it in its copy for the proves that take R and S from the tables)
   d.psz = proof_size();
   d.perm = dp.perm.p;
   d.k = dp.k.p;
@@ -220,7 +220,12 @@ void Engine::prepare_device_prover() {
   //    the main stream goes on with the CRS-only commitments at once
   dp.p1t.table_stream = true;
   build_plan(dp.p1t, prove_phase1t(ni, Li), scal);
-  tab_.scr.ensure(dp.p1t.fix_sets + dp.p1t.tbl_sets, dp.p1t.nparts);
+  // -- R and S from the tables (option rs_from_tables): k R = msm(T, a_sigma), k S = msm(U, a_sigma) — table requests like phase 1t, behind
+  //    it on the same stream once V_APERM is there; then cm_T.T_2 = k R + r_t H, cm_U.T_2 = k S + r_u H as sums of kept points on the side stream
+  dp.prs.table_stream = true;
+  build_plan(dp.prs, prove_rs_tables(ni, Li), scal);
+  build_plan(dp.prs_sum, prove_rs_sums(ni, Li), scal);
+  tab_.scr.ensure(std::max(dp.p1t.fix_sets + dp.p1t.tbl_sets, dp.prs.fix_sets + dp.prs.tbl_sets), std::max(dp.p1t.nparts, dp.prs.nparts));
   // -- phase 1b (option p1_split): A = msm(G | Hvec, a_sigma | blinders) (curdleproofs.rs:93) alone — the one commitment of phase 1
   //    that needs vec_a; the rest of the phase then runs before the main stream waits for the transcript prefix
   build_plan(dp.p1b, opt_.p1_split ? prove_phase1b(ni, Li) : ReqList(), scal);
@@ -343,12 +348,29 @@ void Engine::prepare_device_prover() {
     int side[6];
     side_stream_slots(Li, side);
     dp.side_cols = idx_list(std::vector<uint32_t>(side, side + 6));
+    // ... and with R and S from the tables (prove_reqs.hpp): R = k^-1 Rk, S = k^-1 Sk, cm_A.T_2 = (r_k k^-1) Rk + r_a H, cm_B.T_2 likewise;
+    // the scalars are k_ps_aperm's (cm_T.T_2 and cm_U.T_2 are the sums of dp.prs_sum, which compresses them as well)
+    std::vector<SmulTask> sv(4 * B);
+    for (size_t p = 0; p < B; p++) {
+      const Fr* k_inv = dp.sc.p + p * SC_COUNT + SC_K_INV;
+      const Fr* rk_k_inv = dp.sc.p + p * SC_COUNT + SC_RK_K_INV;
+      Aff* const rk = slot(p, rs_tables_slot(Li, 0));
+      Aff* const sk = slot(p, rs_tables_slot(Li, 1));
+      sv[4 * p + 0] = SmulTask{nullptr, rk, slot(p, SL_R), k_inv, 0, 0};
+      sv[4 * p + 1] = SmulTask{nullptr, sk, slot(p, SL_S), k_inv, 0, 0};
+      sv[4 * p + 2] = SmulTask{slot(p, sm.TMP(2)), rk, slot(p, sm.CMA2()), rk_k_inv, 0, 0};
+      sv[4 * p + 3] = SmulTask{slot(p, sm.TMP(3)), sk, slot(p, sm.CMB2()), rk_k_inv, 0, 0};
+    }
+    CPX_HIP(hipMemcpy(dp.stasks_tbl.p, sv.data(), sv.size() * sizeof(SmulTask), hipMemcpyHostToDevice));
+    dp.side_cols_tbl = idx_list({(uint32_t)SL_R, (uint32_t)SL_S, (uint32_t)sm.CMA2(), (uint32_t)sm.CMB2()});
   }
   if (!tab_.dstream) CPX_HIP(hipStreamCreateWithFlags(&tab_.dstream, hipStreamNonBlocking));
   if (!dp.ev_t1) {
     CPX_HIP(hipEventCreateWithFlags(&dp.ev_t1, hipEventDisableTiming));
     CPX_HIP(hipEventCreateWithFlags(&dp.ev_t2, hipEventDisableTiming));
     CPX_HIP(hipEventCreateWithFlags(&dp.ev_a2, hipEventDisableTiming));
+    CPX_HIP(hipEventCreateWithFlags(&dp.ev_ap, hipEventDisableTiming));
+    CPX_HIP(hipEventCreateWithFlags(&dp.ev_rs, hipEventDisableTiming));
   }
   if (!dp.ev_a) {
     CPX_HIP(hipEventCreateWithFlags(&dp.ev_a, hipEventDisableTiming));
@@ -367,6 +389,7 @@ void Engine::prepare_device_prover() {
     upd(dp.p1);
     upd(dp.p1b);
     upd(dp.p1t);   // (in line on the main stream when the table stream is off: large batches, serial_streams)
+    upd(dp.prs);   // (likewise)
     upd(dp.p2);
     upd(dp.p3);
     for (auto& pl : dp.ipa)
@@ -383,6 +406,14 @@ void Engine::prepare_device_prover() {
                               (3 * B * (size_t)lt.m + 63) / 64 * 64 * late_tmp_per_lane()));               // ... or the multiples of the late rounds' materialised points
   }
   dp.signature = sig;
+}
+
+// The side scratch of the one-off bucket MSMs R = msm(vec_R, a), S = msm(vec_S, a) (launch_rs) for the loaded batch: with R and S from the
+// tables only the batches that fall back need it
+void Engine::ensure_rs_scratch() {
+  side_.conv.ensure(4 * B_ * ell_);
+  side_.digits.ensure(9 * 2 * B_ * ell_);
+  side_.scr.ensure(2 * B_ * 32, 2 * B_ * 32);
 }
 
 // Whether the loaded batch runs its table build and phase 1t on the table stream (option table_stream_max, stated for n <= 256)
@@ -439,7 +470,11 @@ void Engine::enqueue_prove_device() {
   tock();
   CPX_HIP(hipEventRecord(dp.ev_b, pre));
   if (pre != side) CPX_HIP(hipStreamWaitEvent(side, dp.ev_b, 0));
-  launch_rs(2 * B, 2 * B, 1, opt_.rs_pairs != 0, side, true);
+  // R and S: from the per-proof tables further down (dp.rs_tables), or here as one-off bucket MSMs over vec_R and vec_S
+  const bool rs_tbl = dp.rs_tables;
+  if (!rs_tbl) launch_rs(2 * B, 2 * B, 1, opt_.rs_pairs != 0, side, true);
+  ProveDev d_aperm = d;
+  d_aperm.rs_tables = rs_tbl ? 1 : 0;
   // table stream: the per-proof tables, then B_t and B_u (phase 1t) — nothing on the main stream needs a table before phase 2 (M's row)
   // nor B_t, B_u before the SameMSM transcript step
   hipStream_t const tabs = table_stream_on() ? tab_.dstream : stream_;
@@ -461,20 +496,33 @@ void Engine::enqueue_prove_device() {
     exec_plan(dp.p1, dp.slotcomp.p);
     CPX_HIP(hipEventRecord(dp.ev_c, stream_));
     CPX_HIP(hipStreamWaitEvent(stream_, dp.ev_b, 0));
-    launch_ps_aperm(d, Bi, stream_);
+    launch_ps_aperm(d_aperm, Bi, stream_);
+    if (rs_tbl && tabs != stream_) CPX_HIP(hipEventRecord(dp.ev_ap, stream_));
     exec_plan(dp.p1b, dp.slotcomp.p);
   } else {
     CPX_HIP(hipStreamWaitEvent(stream_, dp.ev_b, 0));   // vec_a and the transcript states
     // -- P1
-    launch_ps_aperm(d, Bi, stream_);
+    launch_ps_aperm(d_aperm, Bi, stream_);
+    if (rs_tbl && tabs != stream_) CPX_HIP(hipEventRecord(dp.ev_ap, stream_));
     exec_plan(dp.p1, dp.slotcomp.p);
     CPX_HIP(hipEventRecord(dp.ev_c, stream_));           // the r * H points of the T_2 commitments are in TMP0..3
   }
+  if (rs_tbl) {   // k R = msm(T, a_sigma), k S = msm(U, a_sigma): behind the tables, B_t, B_u (same stream) and V_APERM
+    if (tabs != stream_) CPX_HIP(hipStreamWaitEvent(tabs, dp.ev_ap, 0));
+    exec_plan(dp.prs, dp.slotcomp.p, true);
+    CPX_HIP(hipEventRecord(dp.ev_rs, tabs));
+    CPX_HIP(hipStreamWaitEvent(side, dp.ev_rs, 0));
+  }
   CPX_HIP(hipStreamWaitEvent(side, dp.ev_c, 0));
   tick("k_smul", 0, (double)(4 * B));
-  count_smul_quad(launch_smul(side_.stasks.p, 4 * Bi, 1, side, /*exclusive_simd=*/side != stream_, opt_.serial_streams ? 0 : opt_.smul_quad_max));   // (a small batch: at most 16 waves, each on a SIMD of its own)
+  count_smul_quad(launch_smul(rs_tbl ? dp.stasks_tbl.p : side_.stasks.p, 4 * Bi, 1, side, /*exclusive_simd=*/side != stream_, opt_.serial_streams ? 0 : opt_.smul_quad_max));   // (a small batch: at most 16 waves, each on a SIMD of its own)
   tock();
-  launch_compress_cols(d_pp_.p + 4 * ell, dp.side_cols, 6, (int)pp_stride_, Bi, dp.slotcomp.p, (int)NS, side);
+  if (rs_tbl) {   // cm_T.T_2 = k R + r_t H, cm_U.T_2 = k S + r_u H: sums, compressed into their slots (no MSM task: the scratch is not touched)
+    launch_tbl_phase(dp.prs_sum, dp.prs_sum.ttasks.p, dp.prs_sum.ftasks.p, dp.prs_sum.meta.p, dp.slotcomp.p, side, main_);
+    launch_compress_cols(d_pp_.p + 4 * ell, dp.side_cols_tbl, 4, (int)pp_stride_, Bi, dp.slotcomp.p, (int)NS, side);
+  } else {
+    launch_compress_cols(d_pp_.p + 4 * ell, dp.side_cols, 6, (int)pp_stride_, Bi, dp.slotcomp.p, (int)NS, side);
+  }
   CPX_HIP(hipEventRecord(dp.ev_d, side));
   launch_ps_sameperm(d, Bi, stream_);
   // -- P2, P3
@@ -598,6 +646,15 @@ void Engine::batch_prove_device(const ProveDraws& dr, uint8_t* proofs_out) {
   const size_t B = B_, ell = ell_, n = n_, nrand = 3 * n + 9;
   prepare_device_prover();
   DevProver& dp = dprove_;
+  // R and S from the per-proof tables (option rs_from_tables) need k^-1: a batch in which some k is zero — the reference proves such a
+  // witness, T and U all identity — takes the one-off bucket MSMs as a whole, and so does one whose k is already on the device (no look
+  // without a synchronisation).  (Fr::zero() is all-zero bytes in Montgomery form, too.)
+  dp.rs_tables = opt_.rs_from_tables != 0 && dr.kind == hipMemcpyHostToDevice;
+  for (size_t p = 0; p < B && dp.rs_tables; p++) {
+    static const uint8_t zero[sizeof(Fr)] = {};
+    if (!memcmp(dr.k + p * sizeof(Fr), zero, sizeof(Fr))) dp.rs_tables = false;
+  }
+  if (!dp.rs_tables) ensure_rs_scratch();   // (allocates on the first such batch only)
 
   // witnesses and the prover's random draws: the only host -> device traffic of a prove (with states: 40 bytes of randomness per proof)
   CPX_HIP(hipMemcpyAsync(dp.perm.p, dr.perm, B * ell * sizeof(uint32_t), dr.kind, stream_));

@@ -45,6 +45,9 @@ struct Options {
   long late_min_batch = 2048;      // ... for batches of at least this many proofs (n <= 256; scaled by 256 / n above: 512 at ell = 1020); the lane-per-output kernels need a full GPU to pay
   long late_slices = 8;            // lanes per cross term of a late round (1, 2, 4, 8): 15.3 k proofs/s at 8, 14.9 k at 4 and 2, 14.3 k at 1
   long rs_pairs = 1;               // 1: the prover's R and S MSMs of a proof share their waves (same scalars: one digit sort for both); 0: two separate tasks
+  long rs_from_tables = 1;         // 1: the device-resident prover takes k R = msm(T, a_sigma) and k S = msm(U, a_sigma) from the per-proof tables (prove_reqs.hpp prove_rs_tables) and R, S and the
+                                   // four T_2 commitments from those — same proof bytes for a consistent witness (T = k sigma(R), U = k sigma(S)); 0, a batch with a k = 0 and witnesses
+                                   // that are already on the device: the one-off bucket MSMs R = msm(vec_R, a), S = msm(vec_S, a) (rs_pairs)
   long table_chunks = 0;           // launches of the device prover's per-proof table build: 0 = all rows at once while the scratch stays below 16 GiB (8192 proofs of ell = 252: 13.5 GB), k = exactly k equal chunks (2: round 5's default, 6.7 GB, 0.5 % slower in the round-6 A/B)
   long tbl_segments = 0;           // weight classes of the per-proof tables (below, "table-backed MSM"): 1 = 16 + 16 copies, 2 = 8 + 8 copies wherever the batch's path supports them
                                    // (read-only `tbl_segments_effective`: the layout the loaded batch proves with), 0 = by the proof size

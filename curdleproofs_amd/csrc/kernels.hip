@@ -1235,6 +1235,7 @@ const OptField kOptFields[] = {
     {"tbl_segments", &Options::tbl_segments, 0, 2},                {"fold_quad_max", &Options::fold_quad_max, 0, 1L << 30},
     {"locate_groups_max", &Options::locate_groups_max, 1, 256},    {"find_table_min_keys", &Options::find_table_min_keys, 1, (1L << 20) + 1},
     {"find_table_mb", &Options::find_table_mb, 1, 65536},          {"rng_g1_round_cap", &Options::rng_g1_round_cap, 0, 1L << 20},
+    {"rs_from_tables", &Options::rs_from_tables, 0, 1},
 };
 bool option_value_ok(const OptField& f, long v) {
   if (v < f.lo || v > f.hi) return false;

@@ -19,7 +19,9 @@ enum {
   SC_BETA_SP = 0, SC_ALPHA_SP,          // B = A + alpha M + beta sum(G): request scalars [beta | alpha]
   SC_NEG_BETA_G_INV, SC_ALPHA_G,        // D = B - beta^-1 sum(G) + alpha sum(H): request scalars [-beta^-1 | alpha]
   SC_GPROD, SC_BETA_G, SC_BETA_G_INV, SC_RP, SC_ZIP, SC_ALPHA_I, SC_BETA_I, SC_ALPHA_S, SC_ALPHA_M,
-  SC_ZK, SC_ZT, SC_ZU, SC_CFIN, SC_DFIN, SC_XFIN, SC_COUNT = 24
+  SC_ZK, SC_ZT, SC_ZU, SC_CFIN, SC_DFIN, SC_XFIN,
+  SC_K_INV, SC_RK_K_INV,                // k^-1 and r_k k^-1: the side stream's scalars when R and S come from the tables (ProveDev::rs_tables)
+  SC_COUNT = 24
 };
 // the names CPX_TRACE prints them under, for both provers (no name: an unused index)
 static constexpr const char* kScNames[SC_COUNT] = {"beta_sp", "alpha_sp", "-beta_g_inv", "alpha_g", "gprod", "beta_g", "beta_g_inv", "r_p", "z_ip", "alpha_i", "beta_i",
@@ -29,6 +31,7 @@ enum { V_APERM = 0, V_FACT, V_C, V_D, V_U, V_ZZ, V_ZZU, V_COUNT };
 
 struct ProveDev {
   int ell, n, L, NS;              // NS = SlotMap(L).count()
+  int rs_tables;                  // != 0: k_ps_aperm also leaves SC_K_INV, SC_RK_K_INV (prove_reqs.hpp prove_rs_tables)
   size_t psz;                     // proof size in bytes
   const uint32_t* perm;           // [B][ell]
   const Fr* k;                    // [B]

@@ -98,6 +98,13 @@ __global__ __launch_bounds__(64) void k_ps_aperm(const ProveDev d) {
   for (int i = threadIdx.x; i < ell; i += 64) ap[i] = veca[perm[i]];
   if (threadIdx.x < 2) ap[ell + threadIdx.x] = v.rnd()[ri.AB() + threadIdx.x];
   else if (threadIdx.x < 4) ap[ell + threadIdx.x] = Fr::zero();
+  // R and S from the tables: R = k^-1 Rk, cm_A.T_2 = (r_k k^-1) Rk + r_a H (prove_reqs.hpp) — the side stream's two scalars, in
+  // Montgomery form like k and the draws (k = 0 never comes here: such a batch takes the bucket MSMs)
+  if (d.rs_tables && threadIdx.x == 4) {
+    const Fr k_inv = fr_inv_divsteps(d.k[v.p]);
+    v.sc()[SC_K_INV] = k_inv;
+    v.sc()[SC_RK_K_INV] = fe_mul(v.rnd()[ri.RK()], k_inv);
+  }
 }
 
 // S2 (after phase 1: A, B_a, B_t, B_u, B_c, the T_1 commitments): SamePerm challenges, the grand-product factors and the

@@ -182,10 +182,38 @@ inline ReqList prove_smsm_round(int n, int L, int j) {
 }
 // the six proof points the side stream computes outside the table-backed requests: R = a x vec_R, S = a x vec_S (curdleproofs.rs:112-113)
 // and the four T_2 = s * {R, S} + r * H (curdleproofs.rs:115-116, same_scalar_argument.rs:60-61), on top of TMP(0..3) of phase 1
+// (with R and S from the tables, below: the same six slots from k R and k S — prove_rs_tables, prove_rs_sums)
 inline void side_stream_slots(int L, int q[6]) {
   const SlotMap sm(L);
   const int s[6] = {SL_R, SL_S, SL_CMT2, SL_CMU2, sm.CMA2(), sm.CMB2()};
   for (int i = 0; i < 6; i++) q[i] = s[i];
+}
+
+// R and S from the per-proof tables (option rs_from_tables, the device-resident prover): the witness says T_j = k R_sigma(j) and
+// U_j = k S_sigma(j) (util.rs:94-95), and V_APERM is a_sigma(j), the same permutation applied to vec_a (curdleproofs.rs:93).  Hence
+//     Rk = msm(T, a_sigma) = sum_j a_sigma(j) k R_sigma(j) = k msm(vec_R, a) = k R   and likewise   Sk = msm(U, a_sigma) = k S,
+// over bases whose shifted tables the SameMSM rounds need anyway — in place of the one-off bucket MSMs R = msm(vec_R, a),
+// S = msm(vec_S, a) (curdleproofs.rs:112-113).  The first ell entries of the rows only: the last four are the blinder slots
+// (0, 0, H, 0 / 0, 0, 0, H), which V_APERM pairs with vec_a_blinders.  T and U in their given order — the permutation is in the
+// scalars.  The two points stay in scratch slots no other request writes; no proof bytes come from them directly.
+inline int rs_tables_slot(int L, int which) { return SlotMap(L).TMP(which ? 6 : 4); }   // Rk | Sk (TMP(5), TMP(7): the plans' write-only slots)
+inline ReqList prove_rs_tables(int n, int L) {
+  const PtabRow row(n);
+  const int ell = n - (int)N_BLINDERS;
+  ReqList l;
+  l.push(rq::ptab(row.T(), ell), rq::vec(V_APERM), -1, rs_tables_slot(L, 0));
+  l.push(rq::ptab(row.U(), ell), rq::vec(V_APERM), -1, rs_tables_slot(L, 1));
+  return l;
+}
+// ... and the two commitments that need no scalar multiplication then: cm_T.T_2 = k R + r_t H = Rk + TMP(0), cm_U.T_2 = k S + r_u H =
+// Sk + TMP(1) (curdleproofs.rs:115-116) — sums of kept points.  (R = k^-1 Rk, S = k^-1 Sk and cm_A.T_2 = r_k R + r_a H = (r_k k^-1) Rk +
+// TMP(2), cm_B.T_2 likewise (same_scalar_argument.rs:60-61) are the side stream's four scalar multiplications.)
+inline ReqList prove_rs_sums(int, int L) {
+  const SlotMap sm(L);
+  ReqList l;
+  rq::add3(l.push(ReqSeg{}, ReqScal{}, SL_CMT2, SL_CMT2), rs_tables_slot(L, 0), sm.TMP(0));
+  rq::add3(l.push(ReqSeg{}, ReqScal{}, SL_CMU2, SL_CMU2), rs_tables_slot(L, 1), sm.TMP(1));
+  return l;
 }
 
 // ---- the verifier: D = B - beta^-1 sum(G) + alpha sum(H) (grand_product_argument.rs:223) and A' = A + cm_T.T_1 + cm_U.T_1

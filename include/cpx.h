@@ -246,7 +246,14 @@ int cpx_batch_load_end(cpx_ctx* ctx);
  *                vec_a_blinders[2] (curdleproofs.rs:86), vec_c_blinders[4] (grand_product_argument.rs:75),
  *                IPA r[n], z[n-2] (inner_product_argument.rs:46-47), r_t, r_u (curdleproofs.rs:110-111),
  *                r_a, r_b, r_k (same_scalar_argument.rs:56-58), vec_r[n] (same_multiscalar_argument.rs:78)
- *   proofs_out   batch*cpx_proof_size() bytes = `CurdleproofsProof::serialize` (curdleproofs.rs:300-310) */
+ *   proofs_out   batch*cpx_proof_size() bytes = `CurdleproofsProof::serialize` (curdleproofs.rs:300-310)
+ * The witness is taken to be CONSISTENT with the loaded instance: vec_T[j] = k vec_R[permutation[j]], vec_U[j] = k vec_S[permutation[j]]
+ * (util.rs:94-95).  From option "device_min_batch" proofs on (option "rs_from_tables", default 1) the prover then takes k R = msm(vec_T,
+ * a_sigma) and k S = msm(vec_U, a_sigma) from the per-proof tables and R, S, cm_T.T_2, cm_U.T_2, cm_A.T_2, cm_B.T_2 from those: the same
+ * group elements, hence the reference's proof bytes.  For an INCONSISTENT witness the reference emits a proof that does not verify, and
+ * this call emits another proof that does not verify; with "rs_from_tables" = 0 R and S are msm(vec_R, a), msm(vec_S, a) as the reference
+ * computes them and the bytes are the reference's for every witness.  A batch in which some k is zero (the reference proves it: vec_T and
+ * vec_U all identity) is proved that way as a whole, whatever the option. */
 int cpx_batch_prove(cpx_ctx* ctx, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders, const uint8_t* rand,
                     uint8_t* proofs_out);
 /* curdleproofs.rs:197 `verify` (after `deserialize`, :312-323) for every loaded instance.
@@ -530,7 +537,9 @@ int cpx_rng_shuffle_draws(cpx_ctx* ctx, size_t count, uint8_t* states /* count*4
 int cpx_whisk_generate_shuffle_proofs_rng(cpx_ctx* ctx, size_t count, const uint8_t* pre_trackers /* count*ell*96 */, uint8_t* states /* count*40, in/out */,
                                           uint8_t* post_trackers_out /* count*ell*96 */, uint8_t* proofs_out /* count*(48+cpx_proof_size) */, int* status /* count */);
 /* cpx_batch_prove on the loaded instances with `rand` replaced by one state per instance: only the 3n + 9 draws of CurdleproofsProof::new
- * are taken from each stream; the witnesses stay arguments. */
+ * are taken from each stream; the witnesses stay arguments — and are taken to be consistent with the instance, as cpx_batch_prove says
+ * (option "rs_from_tables"; 0 gives the reference's bytes for every witness).  (cpx_whisk_generate_shuffle_proofs_rng, whose witnesses
+ * never leave the device, keeps the reference's evaluation order: there k cannot be looked at without a synchronisation.) */
 int cpx_batch_prove_rng(cpx_ctx* ctx, const uint32_t* permutation, const uint8_t* k, const uint8_t* vec_m_blinders, uint8_t* states /* batch*40, in/out */,
                         uint8_t* proofs_out);
 
