@@ -14,6 +14,13 @@
 // data, i.e. identically in the four lanes, and the doubling is then done by every lane on its own from the operands in memory.
 // Magnitudes (units of p): products lie in (-0.81, 1.81); P, R within +-3.62; X3 in (-6.24, 4.24); Q - X3 within +-8.1;
 // Y3 within +-2.62 — every operand product stays far below the 2^11.3 p^2 the lazy multiplication allows (fp28.hpp).
+// Operands: a RESULT of these formulas has |X| <= 6.3, |Y| <= 2.7 (g1_28.hpp), but an operand may be wider: xyzz28_from_jac below hands
+// the X and Y of a Jacobian point on unchanged, |X|, |Y| <= 15.4, and k_finalize_ranges_wave and k_msm_tail_wave add and double such
+// points.  X and Y of an operand only ever enter products: X ZZ', Y ZZZ' (15.4 x 1.81 = 27.9) in the addition, X^2 (237.2), (2 Y)^2
+// (948.7, the largest, still below 2^11), X V, W Y in the doubling, so every formula here accepts |X|, |Y| <= 15.4 and returns a
+// result in the narrow ranges above whatever the operands' width.  jac28_dbl_quad: X3 = F - 2 D and Y3 = E (D - X3) - 8 C lie in
+// (-15.29, 8.29), Z3 = 2 Y Z in (-0.05, 2.05) (|Y Z| <= 15.4 x 3.6 p^2 moves a product by 0.022 p) for operands in the Jacobian ranges
+// |X|, |Y| <= 15.4, |Z| <= 3.6, so its result is a legal operand again (the chains of k_table_build_quad).  tests/device/quad_check.hip checks all of this on raw limbs.
 // Every function here must be called by all 64 lanes of the wave together (DPP reads from disabled lanes are undefined).
 #pragma once
 #include "g1_28.hpp"
@@ -104,7 +111,8 @@ __device__ __forceinline__ Jac28 jac28_dbl_quad(const Jac28& p) {
   return r;
 }
 
-// Jacobian (X, Y, Z) <-> XYZZ (X, Y, Z^2, Z^3): the partial-sum arrays between the kernels stay Jacobian
+// Jacobian (X, Y, Z) <-> XYZZ (X, Y, Z^2, Z^3): the partial-sum arrays between the kernels stay Jacobian.  X and Y are handed on as they
+// are, in the Jacobian range (the wide operands of the note on magnitudes above); ZZ and ZZZ are products.
 __device__ __forceinline__ Xyzz28 xyzz28_from_jac(const Jac28& p) {
   if (p.is_identity()) return Xyzz28::identity();
   const F28 zz = f28_sqr(p.z);

@@ -1,5 +1,5 @@
-"""The Python side of tests/device/check_harness.hpp, shared by the libraries of the six check programs (field_check_lib,
-scalar_check_lib, rng_cases, rng_g1_cases, transcript_cases, msm_check_lib): building a host twin, the record file format, running a
+"""The Python side of tests/device/check_harness.hpp, shared by the libraries of the seven check programs (field_check_lib,
+scalar_check_lib, rng_cases, rng_g1_cases, transcript_cases, msm_check_lib, quad_check_lib): building a host twin, the record file format, running a
 program over a record file and the bit-for-bit comparison.  build_emul() compiles the CPU twins of the plan headers
 (tests/host_emul/*_emul.cpp) for the tests/test_*_cpu.py files."""
 import os

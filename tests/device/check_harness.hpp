@@ -1,5 +1,5 @@
 // TEST-ONLY: the runner shared by the check programs of tests/device/ (field_check, scalar_check, transcript_check, rng_check,
-// rng_g1_check, msm_check).  A program defines CHECK_PROG (its name, in every message), includes this header and calls check_main();
+// rng_g1_check, msm_check, quad_check).  A program defines CHECK_PROG (its name, in every message), includes this header and calls check_main();
 // a program whose operations all map one row of words to one row of words needs only OP(...) lines, a TABLE and rows_main().
 // Nothing in curdleproofs_amd/ includes it.
 //

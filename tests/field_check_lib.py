@@ -327,11 +327,12 @@ class PointVectors:
         self.pts = [(int.from_bytes(raw[96 * i:96 * i + 48], "little") * Ri % P, int.from_bytes(raw[96 * i + 48:96 * i + 96], "little") * Ri % P)
                     for i in range(24)]
 
-    def lazy(self, v, lo, hi):
-        """limbs of a representative of the residue v 2^392 in (lo p, hi p) (hundredths of p), at random"""
+    def lazy(self, v, lo, hi, pick=None):
+        """limbs of a representative of the residue v 2^392 in (lo p, hi p) (hundredths of p): at random, or (pick "lo" / "hi") the
+        lowest / the highest one of the range"""
         m = v * R392 % P
         ks = [k for k in range(lo // 100 - 1, hi // 100 + 1) if lo * P < 100 * (m + k * P) < hi * P]
-        return limbs(m + self.rng.choice(ks) * P)
+        return limbs(m + (self.rng.choice(ks) if pick is None else ks[0] if pick == "lo" else ks[-1]) * P)
 
     def aff(self, a, lazy_neg=False):
         """a table entry; lazy_neg: a given as the limb-wise negated stored y of -a (f28_cneg_lazy, the bucket loops)"""
@@ -341,21 +342,25 @@ class PointVectors:
             return self.lazy(a[0], -81, 181) + [-x for x in self.lazy(-a[1], -81, 181)]
         return self.lazy(a[0], -81, 181) + self.lazy(a[1], -81, 181)
 
-    def xyzz(self, acc, scale=1):
-        """an accumulator (X, Y, ZZ, ZZZ), optionally moved to the equivalent (X s^2, Y s^3, ZZ s^2, ZZZ s^3)"""
+    def xyzz(self, acc, scale=1, pick=(None,) * 4, wide=False):
+        """an accumulator (X, Y, ZZ, ZZZ), optionally moved to the equivalent (X s^2, Y s^3, ZZ s^2, ZZZ s^3); pick: per coordinate,
+        None = a representative at random, "lo" / "hi" = the lowest / highest of its documented range; wide: X and Y in the range of a
+        Jacobian point, +-15.4 p (what xyzz28_from_jac hands on)"""
         if acc is None:
             return limbs(R392 % P) * 2 + [0] * 28
         X, Y, ZZ, ZZZ = acc
         s2, s3 = scale * scale % P, scale ** 3 % P
-        return self.lazy(X * s2, -630, 630) + self.lazy(Y * s3, -270, 270) + self.lazy(ZZ * s2, -81, 181) + self.lazy(ZZZ * s3, -81, 181)
+        bx, by = (1540, 1540) if wide else (630, 270)
+        return (self.lazy(X * s2, -bx, bx, pick[0]) + self.lazy(Y * s3, -by, by, pick[1]) + self.lazy(ZZ * s2, -81, 181, pick[2])
+                + self.lazy(ZZZ * s3, -81, 181, pick[3]))
 
-    def jac(self, acc, scale=1):
-        """the Jacobian point (X ZZ, Y ZZZ, ZZ) of an accumulator: Z = ZZ"""
+    def jac(self, acc, scale=1, pick=(None,) * 3):
+        """the Jacobian point (X ZZ, Y ZZZ, ZZ) of an accumulator: Z = ZZ; pick as for xyzz(), for X, Y and Z"""
         if acc is None:
             return limbs(R392 % P) * 2 + [0] * 14
         X, Y, ZZ, ZZZ = acc
         X, Y, Z = X * ZZ * scale * scale % P, Y * ZZZ * scale ** 3 % P, ZZ * scale % P
-        return self.lazy(X, -1540, 1540) + self.lazy(Y, -1540, 1540) + self.lazy(Z, -360, 360)
+        return self.lazy(X, -1540, 1540, pick[0]) + self.lazy(Y, -1540, 1540, pick[1]) + self.lazy(Z, -360, 360, pick[2])
 
     def accumulators(self):
         """(accumulator, its affine point): sums of one to five of the oracle's points, built by mixed additions: ZZ = 1 after the
