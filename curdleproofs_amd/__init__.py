@@ -59,7 +59,7 @@ _libs = {}   # realpath -> loaded library (the default one and build variants fo
 
 EXPORTS = [
     "cpx_host_alloc", "cpx_host_free", "cpx_ctx_create", "cpx_ctx_destroy", "cpx_last_error", "cpx_device_count", "cpx_ctx_set_option", "cpx_ctx_get_option", "cpx_ctx_set_crs", "cpx_crs_sums", "cpx_proof_size", "cpx_batch_size",
-    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_ipa_rounds", "cpx_same_msm_rounds", "cpx_ipa_verify", "cpx_same_msm_verify",
+    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_ipa_rounds", "cpx_same_msm_rounds", "cpx_ipa_verify", "cpx_same_msm_verify", "cpx_ipa_prove", "cpx_same_msm_prove", "cpx_ipa_prove_rng", "cpx_same_msm_prove_rng",
     "cpx_transcript_new", "cpx_transcript_append_message", "cpx_transcript_append_scalar", "cpx_transcript_challenge_bytes", "cpx_transcript_challenge_scalar",
     "cpx_g1_normalize", "cpx_g1_decompress", "cpx_g1_decompress_status",
     "cpx_accum_new", "cpx_accum_free", "cpx_accum_check", "cpx_accum_verify",
@@ -119,6 +119,11 @@ def load_library(path=None):
     L.cpx_same_msm_rounds.argtypes = [vp, sz, sz] + [vp] * 9
     L.cpx_ipa_verify.argtypes = [vp, sz, sz] + [vp] * 11
     L.cpx_same_msm_verify.argtypes = [vp, sz, sz] + [vp] * 11
+    if hasattr(L, "cpx_ipa_prove"):   # (an older build loaded beside this one for an A/B run, scripts/subarg_prove_timing.py, lacks the four)
+        L.cpx_ipa_prove.argtypes = [vp, sz, sz] + [vp] * 13
+        L.cpx_ipa_prove_rng.argtypes = [vp, sz, sz] + [vp] * 13
+        L.cpx_same_msm_prove.argtypes = [vp, sz, sz] + [vp] * 12
+        L.cpx_same_msm_prove_rng.argtypes = [vp, sz, sz] + [vp] * 12
     L.cpx_transcript_new.argtypes = [vp, sz, vp]
     L.cpx_transcript_append_message.argtypes = [vp, vp, sz, vp, sz]
     L.cpx_transcript_append_scalar.argtypes = [vp, vp, sz, vp]
@@ -445,6 +450,66 @@ class Context:
         return self._subarg_verify(self._L.cpx_same_msm_verify, "same_msm_verify", count, n, (G, T, U, A, Z_t, Z_u), (), proofs, rand, states, 3, 1 + L,
                                    48 * (3 + 6 * L) + 32, challenges)
 
+    def _subarg_prove(self, fns, name, count, n, inputs, draws_each, states, rand, rngs, nchal, proof_bytes, challenges):
+        if n < 0:
+            raise ValueError("n is not negative")
+        if (rand is None) == (rngs is None):
+            raise ValueError("%s: exactly one of rand and rngs" % name)
+        if len(states) != count * TRANSCRIPT_BYTES:
+            raise ValueError("%s: one 216-byte transcript state per item" % name)
+        st = (ctypes.c_uint8 * max(len(states), 1)).from_buffer_copy(bytes(states) if count else b"\0")   # in/out: a copy, the caller's stay
+        proofs, chal = _out(count * proof_bytes), _out(count * nchal * FR)
+        status = (ctypes.c_int * max(count, 1))(*([CPX_ERR_INTERNAL] * max(count, 1)))   # an entry the library does not write is never read as a proof
+        tail = (st, proofs, chal if challenges else None, status)
+        if rngs is not None:
+            from . import rng as _rng
+            if len(rngs) != count:
+                raise ValueError("%s: one rng per item" % name)
+            if len({r.state for r in rngs}) != count:
+                raise ValueError("rngs: identical states draw identical blinders; derive the streams with StdRng.split")
+            rs = _rng.load_states(rngs)
+            self._check(fns[1](self._h, count, n, *[_in(b) for b in inputs], rs, *tail))
+            _rng.store_states(rngs, rs)
+        else:
+            if len(rand) != count * max(draws_each, 0) * FR:
+                raise ValueError("%s: %d draws per item" % (name, draws_each))
+            self._check(fns[0](self._h, count, n, *[_in(b) for b in inputs], _in(rand), *tail))
+        marks = {CPX_OK: lambda i: True, CPX_ERR_ARG: lambda i: ValueError("%s: item %d has no blinders (the reference panics in generate_ipa_blinders)" % (name, i))}
+        out = dict(proofs=[bytes(proofs)[proof_bytes * i:proof_bytes * (i + 1)] for i in range(count)], states=bytes(st)[:count * TRANSCRIPT_BYTES],
+                   status=[marks[status[i]](i) for i in range(count)])
+        if challenges:
+            out["challenges"] = bytes(chal)[:count * nchal * FR]
+        if rngs is not None:
+            out["rngs"] = b"".join(r.state for r in rngs)
+        return out
+
+    def ipa_prove(self, n, G, G_prime, crs_H, C, D, z, vec_c, vec_d, states, rand=None, rngs=None, challenges=False):
+        """InnerProductProof::new (inner_product_argument.rs:98-199) for len(z) // 32 independent stand-alone statements of n elements in ONE
+        call (cpx_ipa_prove / cpx_ipa_prove_rng).  G, G_prime: the affine bases, item after item; crs_H, C, D: 144-byte Jacobian points;
+        z, vec_c, vec_d: Montgomery limbs; states: the 216-byte transcript states before `new`.  Exactly one of rand (per item the 2 n - 2
+        draws of generate_ipa_blinders: r, then z) and rngs (one curdleproofs_amd.rng.StdRng per item, DISTINCT streams: the draws are made
+        on the device and every stream advances).  Returns a dict: "proofs" (per item the reference's `serialize` bytes, what ipa_verify
+        takes), "states" (advanced by the whole `new`), "status" (per item True, or a ValueError INSTANCE where the reference panics in
+        generate_ipa_blinders: that item's proof is zero bytes and its state unchanged), with challenges=True "challenges" (per item alpha,
+        beta, gamma_1..L), and with rngs "rngs" (the advanced 40-byte states, as the StdRng objects now hold them)."""
+        count = len(z) // FR
+        L = max(n.bit_length() - 1, 0)
+        if len(z) != count * FR or any(len(v) != count * n * AFF for v in (G, G_prime)) or any(len(v) != count * n * FR for v in (vec_c, vec_d)) or \
+                any(len(p) != count * JAC for p in (crs_H, C, D)):
+            raise ValueError("ipa_prove: per item n points in G and G_prime, n scalars in vec_c and vec_d, one scalar z and one Jacobian point in crs_H, C and D")
+        return self._subarg_prove((self._L.cpx_ipa_prove, self._L.cpx_ipa_prove_rng), "ipa_prove", count, n, (G, G_prime, crs_H, C, D, z, vec_c, vec_d), 2 * n - 2,
+                                  states, rand, rngs, 2 + L, 48 * (2 + 4 * L) + 64, challenges)
+
+    def same_msm_prove(self, n, G, T, U, A, Z_t, Z_u, vec_x, states, rand=None, rngs=None, challenges=False):
+        """SameMultiscalarProof::new (same_multiscalar_argument.rs:69-150) likewise (cpx_same_msm_prove / cpx_same_msm_prove_rng), len(A) // 144
+        items: rand is vec_r, n draws per item; "challenges" holds alpha, gamma_1..L; every status is True."""
+        count = len(A) // JAC
+        L = max(n.bit_length() - 1, 0)
+        if any(len(p) != count * JAC for p in (A, Z_t, Z_u)) or any(len(v) != count * n * AFF for v in (G, T, U)) or len(vec_x) != count * n * FR:
+            raise ValueError("same_msm_prove: per item n points in G, T and U, n scalars in vec_x and one Jacobian point in A, Z_t and Z_u")
+        return self._subarg_prove((self._L.cpx_same_msm_prove, self._L.cpx_same_msm_prove_rng), "same_msm_prove", count, n, (G, T, U, A, Z_t, Z_u, vec_x), n,
+                                  states, rand, rngs, 1 + L, 48 * (3 + 6 * L) + 32, challenges)
+
     def normalize(self, jac, compressed=False):
         n = len(jac) // JAC
         a, c = _out(AFF * n), _out(48 * n)
@@ -645,7 +710,7 @@ class Context:
         return dict(launches=n.value, ms=ms.value, alg_bytes=by.value, units=un.value)
 
     KERNELS = ("k_msm_tblw<32, false>", "k_reduce_sets", "k_msm_tblw<16, false>", "k_msm_tblw<8, false>", "k_msm_tblw<4, false>", "k_msm_tblw<2, false>", "k_msm_fix<19, 7>", "k_msm_fix<16, 4>", "k_msm_fix<16, 2>", "k_msm_fix<16, 16>", "k_msm_fix<16, 8>", "k_msm_fix<8, 16>", "k_msm_fix<8, 8>",
-               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_run_gather", "k_run_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor", "k_subarg_scalars", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
+               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_run_gather", "k_run_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor", "k_subarg_scalars", "k_loop_step", "k_smul_quad", "k_subarg_blinders", "k_subarg_prove_setup", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
 
     def stats(self):
         return {k: self.stat(k) for k in self.KERNELS}

@@ -655,6 +655,41 @@ int cpx_same_msm_verify(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, 
   });
 }
 
+int cpx_ipa_prove(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D,
+                  const uint8_t* z, const uint8_t* vec_c, const uint8_t* vec_d, const uint8_t* rand, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges,
+                  int* status) {
+  if (count && n && (!G || !G_prime || !crs_H || !C || !D || !z || !vec_c || !vec_d || !rand || !transcripts || !proofs || !status)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->ipa_prove(count, n, G, G_prime, crs_H, C, D, z, vec_c, vec_d, rand, nullptr, transcripts, proofs, challenges, status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_ipa_prove_rng(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D,
+                      const uint8_t* z, const uint8_t* vec_c, const uint8_t* vec_d, uint8_t* states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges,
+                      int* status) {
+  if (count && n && (!G || !G_prime || !crs_H || !C || !D || !z || !vec_c || !vec_d || !states || !transcripts || !proofs || !status)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->ipa_prove(count, n, G, G_prime, crs_H, C, D, z, vec_c, vec_d, nullptr, states, transcripts, proofs, challenges, status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_same_msm_prove(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t,
+                       const uint8_t* Z_u, const uint8_t* vec_x, const uint8_t* rand, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status) {
+  if (count && n && (!G || !T || !U || !A || !Z_t || !Z_u || !vec_x || !rand || !transcripts || !proofs || !status)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->same_msm_prove(count, n, G, T, U, A, Z_t, Z_u, vec_x, rand, nullptr, transcripts, proofs, challenges, status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_same_msm_prove_rng(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t,
+                           const uint8_t* Z_u, const uint8_t* vec_x, uint8_t* states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status) {
+  if (count && n && (!G || !T || !U || !A || !Z_t || !Z_u || !vec_x || !states || !transcripts || !proofs || !status)) return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->same_msm_prove(count, n, G, T, U, A, Z_t, Z_u, vec_x, nullptr, states, transcripts, proofs, challenges, status);
+    return (int)CPX_OK;
+  });
+}
+
 int cpx_set_profiling(cpx_ctx* ctx, int on) {
   if (!ctx || !ctx->eng) return CPX_ERR_ARG;
   ctx->eng->set_profiling(on != 0);

@@ -944,35 +944,12 @@ void Engine::loop_rounds(bool ipa, size_t count, size_t n, const uint8_t* const 
   for (size_t i = 0; i < count; i++)
     for (size_t v = 0; v < nvec; v++) memcpy(&hvec[i * lp.vec_words() + v * n], vec[v] + i * n * sizeof(Fr), n * sizeof(Fr));
   Fr* const d_vec = dfr.p + lp.fr_vec();
-  Fr* const d_rows = dfr.p + lp.fr_rows();
   Fr* const d_ones = dfr.p + lp.fr_ones();
   CPX_HIP(hipMemcpyAsync(d_vec, hvec.data(), count * lp.vec_words() * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   if (ipa) CPX_HIP(hipMemcpyAsync(d_ones, hvec.data() + count * lp.vec_words(), count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  lp.fill_idx(idx);
-  CPX_HIP(hipMemcpyAsync(t0_.lidx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  tasks.resize(L * NT);
-  for (size_t j = 0; j < L; j++)
-    for (size_t i = 0; i < count; i++)
-      for (int q = 0; q < (int)terms; q++) {
-        const size_t k = i * terms + (size_t)q;
-        tasks[j * NT + k] = MsmTask{db.p + i * lp.base_stride() + lp.family_off(lp.term_family(q)), t0_.lidx.p + lp.idx_off(j, lp.term_hi(q)),
-                                    d_rows + i * lp.row_words() + lp.scal_off(q), lp.term_len(q), 0, pl.conv_off[k]};
-      }
-  CPX_HIP(hipMemcpyAsync(t0_.mtask.p, tasks.data(), tasks.size() * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+  loop_rounds_lists(lp, pl, idx, tasks);
   CPX_HIP(hipMemcpyAsync(t0_.lstate.p, transcripts, count * kTranscriptBytes, hipMemcpyHostToDevice, stream_));
-  // ---- the rounds
-  const LoopDev ld{d_vec, d_rows, dfr.p + lp.fr_gammas(), dfr.p + lp.fr_finals(), t0_.lstate.p, dcomp.p, (int)count, (int)n, (int)L};
-  if (ipa) launch_ipa_round_scalars(d_vec, (int)count, (int)n, (int)(n / 2), d_ones, d_rows, stream_);
-  else launch_smsm_round_scalars(d_vec, (int)count, (int)n, (int)(n / 2), d_rows, stream_);
-  for (size_t j = 0; j < L; j++) {
-    msm_chain_run(pl, t0_.mtask.p + j * NT, res.p + j * NT);
-    tick("k_finalize", 0, (double)NT);
-    launch_finalize(res.p + j * NT, (int)NT, daff.p + j * NT, nullptr, dcomp.p + j * NT * 48, stream_);
-    tock();
-    tick("k_loop_step", 0, (double)count, true);
-    launch_loop_step(ipa, ld, (int)j, stream_);
-    tock();
-  }
+  loop_rounds_resident(lp, pl);
   // ---- the one download, into host memory of the call: the caller's buffers are written once everything has arrived
   h_states.resize(count * kTranscriptBytes);
   h_fr.resize((count * L + count * lp.finals_each()) * sizeof(Fr));   // gammas | finals, as they sit in the Fr memory
@@ -997,6 +974,227 @@ void Engine::loop_rounds(bool ipa, size_t count, size_t n, const uint8_t* const 
       if (rounds_comp) memcpy(rounds_comp + dst * 48, h_comp.data() + src * 48, terms * 48);
       if (rounds_aff) memcpy(rounds_aff + dst * sizeof(Aff), h_aff.data() + src * sizeof(Aff), terms * sizeof(Aff));
     }
+}
+// The two halves of the loop that cpx_ipa_rounds / cpx_same_msm_rounds share with cpx_ipa_prove / cpx_same_msm_prove, inside the caller's
+// scope and after its last ensure(), on the tier-0 buffers at the offsets of loop_plan.hpp: bases in t0_.a0, Fr memory in t0_.fr, sums in
+// t0_.res, their affine forms in t0_.a1 and encodings in t0_.bytes, states in t0_.lstate.
+// ... what of the upload depends on (count, n) alone: the index lists of every round and every round's tasks.  idx, tasks: the caller's,
+// declared above its scope (enqueued copies read them)
+void Engine::loop_rounds_lists(const LoopPlan& lp, const Tier0MsmPlan& pl, std::vector<uint32_t>& idx, std::vector<MsmTask>& tasks) {
+  const size_t count = lp.count, L = lp.L, NT = lp.tasks(), terms = (size_t)lp.terms();
+  Fr* const d_rows = t0_.fr.p + lp.fr_rows();
+  lp.fill_idx(idx);
+  CPX_HIP(hipMemcpyAsync(t0_.lidx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+  tasks.resize(L * NT);
+  for (size_t j = 0; j < L; j++)
+    for (size_t i = 0; i < count; i++)
+      for (int q = 0; q < (int)terms; q++) {
+        const size_t k = i * terms + (size_t)q;
+        tasks[j * NT + k] = MsmTask{t0_.a0.p + i * lp.base_stride() + lp.family_off(lp.term_family(q)), t0_.lidx.p + lp.idx_off(j, lp.term_hi(q)),
+                                    d_rows + i * lp.row_words() + lp.scal_off(q), lp.term_len(q), 0, pl.conv_off[k]};
+      }
+  CPX_HIP(hipMemcpyAsync(t0_.mtask.p, tasks.data(), tasks.size() * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+}
+// ... and the rounds themselves, on vectors, unit coefficients, bases, lists, tasks and states that are on the device
+void Engine::loop_rounds_resident(const LoopPlan& lp, const Tier0MsmPlan& pl) {
+  const bool ipa = lp.ipa;
+  const size_t count = lp.count, n = lp.n, L = lp.L, NT = lp.tasks();
+  Fr* const d_vec = t0_.fr.p + lp.fr_vec();
+  Fr* const d_rows = t0_.fr.p + lp.fr_rows();
+  Jac* const res = t0_.res.p;
+  Aff* const daff = t0_.a1.p;
+  uint8_t* const dcomp = t0_.bytes.p;
+  const LoopDev ld{d_vec, d_rows, t0_.fr.p + lp.fr_gammas(), t0_.fr.p + lp.fr_finals(), t0_.lstate.p, dcomp, (int)count, (int)n, (int)L};
+  if (ipa) launch_ipa_round_scalars(d_vec, (int)count, (int)n, (int)(n / 2), t0_.fr.p + lp.fr_ones(), d_rows, stream_);
+  else launch_smsm_round_scalars(d_vec, (int)count, (int)n, (int)(n / 2), d_rows, stream_);
+  for (size_t j = 0; j < L; j++) {
+    msm_chain_run(pl, t0_.mtask.p + j * NT, res + j * NT);
+    tick("k_finalize", 0, (double)NT);
+    launch_finalize(res + j * NT, (int)NT, daff + j * NT, nullptr, dcomp + j * NT * 48, stream_);
+    tock();
+    tick("k_loop_step", 0, (double)count, true);
+    launch_loop_step(ipa, ld, (int)j, stream_);
+    tock();
+  }
+}
+// The stand-alone sub-argument provers (include/cpx.h cpx_ipa_prove, cpx_same_msm_prove and their _rng forms): InnerProductProof::new
+// (inner_product_argument.rs:98-199) / SameMultiscalarProof::new (same_multiscalar_argument.rs:69-150) for `count` independent items, laid
+// out by subarg_prove_plan.hpp on top of loop_plan.hpp.  One upload (the bases straight into the loop's item rows); the draws uploaded or
+// made by k_rng_draw; IPA: k_subarg_blinders; the MSM chain over the 2 / 3 count B points; k_finalize over them and the 3 count statement
+// points; SameMSM: k_compress over T | U; k_subarg_prove_setup (subarg_prove.hip); IPA: k_smul for H = beta crs_H into the items' rows;
+// then the rounds of loop_rounds_resident; one download; one synchronisation.  The launches do not depend on count.  fam: G | G' resp.
+// G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u; vec: c | d resp. x; exactly one of rand and rng_states is given.  The outputs are
+// written when the call has succeeded, never before.
+void Engine::ipa_prove(size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D, const uint8_t* z,
+                       const uint8_t* vec_c, const uint8_t* vec_d, const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs,
+                       uint8_t* challenges, int* status) {
+  const uint8_t *fam[3] = {G, G_prime, nullptr}, *stmt[3] = {crs_H, C, D}, *vec[2] = {vec_c, vec_d};
+  subarg_prove(true, count, n, fam, stmt, z, vec, rand, rng_states, transcripts, proofs, challenges, status);
+}
+void Engine::same_msm_prove(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t, const uint8_t* Z_u,
+                            const uint8_t* vec_x, const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status) {
+  const uint8_t *fam[3] = {G, T, U}, *stmt[3] = {A, Z_t, Z_u}, *vec[2] = {vec_x, nullptr};
+  subarg_prove(false, count, n, fam, stmt, nullptr, vec, rand, rng_states, transcripts, proofs, challenges, status);
+}
+void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* const vec[2],
+                          const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status) {
+  if (!count) return;
+  SubargProvePlan sp;
+  switch (subarg_prove_plan(ipa, count, n, sp)) {
+    case LOOP_NOT_POW2: throw std::invalid_argument("the sub-argument provers take n = 2^L elements per item, L >= 0");
+    case LOOP_TOO_LARGE: throw ArgError(ipa ? "cpx_ipa_prove: at most 16384 items and count (2 n + 2) <= 2^24 points per round"
+                                            : "cpx_same_msm_prove: at most 10922 items and 3 count n <= 2^24 points per round");
+    default: break;
+  }
+  if (ipa && n == 1) throw ArgError("cpx_ipa_prove: n = 1 has no blinders (the reference's n - 2 underflows)");
+  const LoopPlan& lp = sp.lp;
+  const size_t nvec = sp.nvec(), L = lp.L, NT = lp.tasks(), NF = sp.first(), K = SubargProvePlan::kStatement, DE = sp.draws_each(), NC = sp.challenges(),
+               PB = sp.proof_bytes();
+  if (rng_states) {   // (the limits of one k_rng_draw launch, as cpx_rng_fr has them)
+    if (DE > ((size_t)1 << 20) || count * DE > ((size_t)1 << 26)) throw ArgError("rng draws: at most 2^20 draws per stream and 2^26 per call");
+    for (size_t i = 0; i < count; i++) {
+      uint64_t pos;
+      memcpy(&pos, rng_states + i * RNG_STATE_BYTES + 32, 8);
+      if (!rng_pos_valid(pos)) throw ArgError("rng state: word_pos within 2^32 words of 2^64");
+    }
+  } else {
+    for (size_t i = 0; i < count * DE; i++)
+      if (!fr_wire_reduced(rand + i * sizeof(Fr))) throw ArgError("a draw of a sub-argument prover is not reduced");
+  }
+  for (size_t v = 0; v < nvec; v++)
+    for (size_t i = 0; i < count * n; i++)
+      if (!fr_wire_reduced(vec[v] + i * sizeof(Fr))) throw ArgError("a witness scalar of a sub-argument prover is not reduced");
+  if (ipa)
+    for (size_t i = 0; i < count; i++)
+      if (!fr_wire_reduced(z + i * sizeof(Fr))) throw ArgError("a scalar z of cpx_ipa_prove is not reduced");
+  for (size_t i = 0; i < count; i++)
+    if (!transcript_state_valid(transcripts + i * kTranscriptBytes)) throw ArgError("a transcript state with pos > 165 or pos_begin > 166");
+  // host memory the enqueued copies read or write: above the scope
+  std::vector<MsmTask> tasks, btasks;
+  std::vector<SmulTask> stasks;
+  std::vector<uint32_t> idx, lens, blens;
+  std::vector<Fr> hwit, h_fr, h_ab;
+  std::vector<uint8_t> h_comp, h_states, h_flags, h_rng;
+  Tier0MsmPlan pl, plb;
+  if (L && !lp.round_msm(pl, lens)) throw ArgError("a round of the loop exceeds the limits of cpx_g1_msm_many");
+  if (!sp.first_msm(plb, blens)) throw ArgError("the B points exceed the limits of cpx_g1_msm_many");
+  CallScope call(this);
+  if (L) pl.slices = msm_tblw_slices(opt_, (int)NT, 2, (int)pl.max_n);
+  plb.slices = msm_tblw_slices(opt_, (int)plb.count, 2, (int)plb.max_n);
+  DevBuf<Aff>&db = t0_.a0, &daff = t0_.a1;
+  DevBuf<Fr>& dfr = t0_.fr;
+  DevBuf<Jac>&res = t0_.res, &din = t0_.jin;
+  DevBuf<uint8_t>&dby = t0_.bytes, &dflag = t0_.status;
+  db.ensure(count * lp.base_stride());
+  dfr.ensure(sp.fr_total());
+  res.ensure(std::max<size_t>(lp.results(), 1));
+  din.ensure(sp.points());
+  daff.ensure(sp.aff_total());
+  dby.ensure(sp.by_total());
+  dflag.ensure(count);
+  t0_.lidx.ensure(std::max<size_t>(lp.idx_total(), 1));
+  t0_.lstate.ensure(count * kTranscriptWords);
+  if (L) msm_chain_reserve(pl);
+  msm_chain_reserve(plb);
+  t0_.mtask.ensure(sp.task_total());
+  if (ipa) t0_.stask.ensure(count);
+  // ---- the one upload: bases into the loop's item rows, statement points, witness, z, draws or rng states, lists, tasks, states
+  const size_t pitch = lp.base_stride() * sizeof(Aff);
+  for (int f = 0; f < (ipa ? 2 : 3); f++)
+    CPX_HIP(hipMemcpy2DAsync(db.p + lp.family_off(f), pitch, fam[f], n * sizeof(Aff), n * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
+  Jac* const d_stmt = din.p + sp.pt_statement(0, 0);
+  for (size_t k = 0; k < K; k++)
+    CPX_HIP(hipMemcpy2DAsync(d_stmt + k, K * sizeof(Jac), stmt[k], sizeof(Jac), sizeof(Jac), count, hipMemcpyHostToDevice, stream_));
+  hwit.resize(count * nvec * n);
+  for (size_t i = 0; i < count; i++)
+    for (size_t v = 0; v < nvec; v++) memcpy(&hwit[(i * nvec + v) * n], vec[v] + i * n * sizeof(Fr), n * sizeof(Fr));
+  CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_wit(), hwit.data(), hwit.size() * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  if (ipa) CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_z(), z, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  uint8_t* const d_rng = dby.p + sp.by_rng();
+  if (rng_states) CPX_HIP(hipMemcpyAsync(d_rng, rng_states, count * RNG_STATE_BYTES, hipMemcpyHostToDevice, stream_));
+  else CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_draws(), rand, count * DE * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  if (L) loop_rounds_lists(lp, pl, idx, tasks);
+  btasks.resize(count * NF);
+  for (size_t i = 0; i < count; i++)
+    for (size_t b = 0; b < NF; b++) {   // IPA: G r_c, G' r_d; SameMSM: G r, T r, U r
+      const Fr* sc = ipa && b == 1 ? dfr.p + sp.fr_rd() + i * n : dfr.p + sp.fr_draws() + i * DE;
+      btasks[i * NF + b] = MsmTask{db.p + i * lp.base_stride() + lp.family_off(sp.first_family(b)), nullptr, sc, (uint32_t)n, 0, plb.conv_off[i * NF + b]};
+    }
+  MsmTask* const d_btasks = t0_.mtask.p + sp.task_first();
+  CPX_HIP(hipMemcpyAsync(d_btasks, btasks.data(), btasks.size() * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+  CPX_HIP(hipMemcpyAsync(t0_.lstate.p, transcripts, count * kTranscriptBytes, hipMemcpyHostToDevice, stream_));
+  // ---- the steps before the loop
+  if (rng_states) {
+    tick("k_rng_draw", (double)(count * DE * sizeof(Fr)), (double)(count * DE));
+    launch_rng_draw(rng_draw_args(d_rng, nullptr, count, 0, nullptr, {{DE, dfr.p + sp.fr_draws()}}), stream_);
+    tock();
+  }
+  const SubargProveDev sd{sp, dfr.p, dfr.p + lp.fr_vec(), dfr.p + lp.fr_ones(), dfr.p + lp.fr_finals(), dby.p, dflag.p, t0_.lstate.p};
+  if (ipa) {
+    tick("k_subarg_blinders", 0, (double)count, true);
+    launch_subarg_blinders(sd, stream_);
+    tock();
+  } else {
+    CPX_HIP(hipMemsetAsync(dflag.p, 0, count, stream_));
+  }
+  msm_chain_run(plb, d_btasks, din.p);
+  tick("k_finalize", 0, (double)sp.points());
+  launch_finalize(din.p, (int)sp.points(), daff.p + sp.aff_points(), nullptr, dby.p + sp.by_points(), stream_);
+  tock();
+  if (!ipa) {
+    tick("k_compress", 0, 2.0 * count * n, true);
+    launch_compress(db.p + lp.family_off(1), (int)(2 * n), (int)lp.base_stride(), (int)count, dby.p + sp.by_tu(), stream_);
+    tock();
+  }
+  tick("k_subarg_prove_setup", 0, (double)count, true);
+  launch_subarg_prove_setup(sd, stream_);
+  tock();
+  if (ipa) {   // H = beta crs_H (inner_product_argument.rs:140) into slot h_index() of the item's row
+    stasks.resize(count);
+    for (size_t i = 0; i < count; i++)
+      stasks[i] = SmulTask{nullptr, daff.p + sp.aff_points() + sp.pt_statement(i, 0), db.p + i * lp.base_stride() + lp.h_index(), dfr.p + sp.fr_ab() + 2 * i + 1, 0, smul_flag()};
+    CPX_HIP(hipMemcpyAsync(t0_.stask.p, stasks.data(), count * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
+    smul_tasks(t0_.stask.p, count, 1, (double)count);
+  }
+  if (L) loop_rounds_resident(lp, pl);
+  // ---- the one download, into host memory of the call: the caller's buffers are written once everything has arrived
+  h_states.resize(count * kTranscriptBytes);
+  h_fr.resize(count * L + count * lp.finals_each());   // gammas | finals, as they sit in the Fr memory
+  h_ab.resize(count * sp.ab_each());
+  h_comp.resize(sp.by_tu());                           // the round encodings | the B and statement encodings
+  h_flags.resize(count);
+  CPX_HIP(hipMemcpyAsync(h_states.data(), t0_.lstate.p, h_states.size(), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(h_fr.data(), dfr.p + lp.fr_gammas(), h_fr.size() * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(h_ab.data(), dfr.p + sp.fr_ab(), h_ab.size() * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(h_comp.data(), dby.p, h_comp.size(), hipMemcpyDeviceToHost, stream_));
+  CPX_HIP(hipMemcpyAsync(h_flags.data(), dflag.p, count, hipMemcpyDeviceToHost, stream_));
+  if (rng_states) {
+    h_rng.resize(count * RNG_STATE_BYTES);
+    CPX_HIP(hipMemcpyAsync(h_rng.data(), d_rng, h_rng.size(), hipMemcpyDeviceToHost, stream_));
+  }
+  call.finish();
+  if (rng_states) memcpy(rng_states, h_rng.data(), h_rng.size());   // (a refused item's stream has drawn too)
+  const Fr* h_gam = h_fr.data();
+  const Fr* h_fin = h_fr.data() + count * L;
+  for (size_t i = 0; i < count; i++) {
+    uint8_t* o = proofs + i * PB;
+    if (h_flags[i]) {   // the reference panics in generate_ipa_blinders: zero bytes, zero challenges, the state as it came
+      memset(o, 0, PB);
+      if (challenges) memset(challenges + i * NC * sizeof(Fr), 0, NC * sizeof(Fr));
+      status[i] = CPX_ERR_ARG;
+      continue;
+    }
+    for (size_t b = 0; b < NF; b++) memcpy(o + sp.point_byte(b), h_comp.data() + sp.by_points() + sp.pt_first(i, b) * 48, 48);
+    for (size_t b = 0; b < sp.blocks(); b++)
+      for (size_t j = 0; j < L; j++) memcpy(o + sp.point_byte(sp.round_slot(j, b)), h_comp.data() + lp.result_index(j, i, sp.block_term(b)) * 48, 48);
+    for (size_t v = 0; v < lp.finals_each(); v++) host::S(h_fin[i * lp.finals_each() + v]).to_le_bytes(o + sp.scalar_byte(v));
+    memcpy(transcripts + i * kTranscriptBytes, h_states.data() + i * kTranscriptBytes, kTranscriptBytes);
+    if (challenges) {
+      memcpy(challenges + i * NC * sizeof(Fr), h_ab.data() + i * sp.ab_each(), sp.ab_each() * sizeof(Fr));
+      memcpy(challenges + (i * NC + sp.ab_each()) * sizeof(Fr), h_gam + i * L, L * sizeof(Fr));
+    }
+    status[i] = CPX_OK;
+  }
 }
 // The stand-alone sub-argument verifiers (include/cpx.h cpx_ipa_verify, cpx_same_msm_verify): InnerProductProof::verify
 // (inner_product_argument.rs:202-326) / SameMultiscalarProof::verify (same_multiscalar_argument.rs:153-261) for `count` independent items,

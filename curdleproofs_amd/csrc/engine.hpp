@@ -191,6 +191,16 @@ class Engine {
                   const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts);                     // inner_product_argument.rs:202-326
   void same_msm_verify(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t, const uint8_t* Z_u,
                        const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts);                // same_multiscalar_argument.rs:153-261
+  // the provers of the two sub-arguments on the caller's bases, `count` independent items per call (subarg_prove_plan.hpp, subarg_prove.hip;
+  // include/cpx.h cpx_ipa_prove / cpx_same_msm_prove and their _rng forms): the reference's `serialize` bytes, states in/out, per-item status.
+  // Exactly one of rand (the draws) and rng_states (count x 40 bytes, in/out: the draws are made on the device) is non-null; no CRS, the
+  // batch is left alone
+  void ipa_prove(size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D, const uint8_t* z,
+                 const uint8_t* vec_c, const uint8_t* vec_d, const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges,
+                 int* status);                                                                                                               // inner_product_argument.rs:98-199
+  void same_msm_prove(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t, const uint8_t* Z_u,
+                      const uint8_t* vec_x, const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges,
+                      int* status);                                                                                                          // same_multiscalar_argument.rs:69-150
   void normalize(const uint8_t* jac, size_t n, uint8_t* out_aff, uint8_t* out_comp);                   // normalize_batch (+compress)
   int decompress(const uint8_t* comp, size_t n, uint8_t* out_aff, int check_subgroup, uint8_t* status_out = nullptr);   // whisk.rs:318-320
 
@@ -502,6 +512,13 @@ class Engine {
   // the one body of ipa_rounds / same_msm_rounds (engine.cpp).  fam: G | G' | H resp. G | T | U; vec: c | d resp. x
   void loop_rounds(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const vec[2], uint8_t* transcripts, uint8_t* rounds_comp,
                    uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas);
+  // its two halves, which the sub-argument provers share (engine.cpp): the index lists and tasks of every round, uploaded; the rounds
+  // themselves on device-resident vectors, bases and states
+  void loop_rounds_lists(const LoopPlan& lp, const Tier0MsmPlan& pl, std::vector<uint32_t>& idx, std::vector<MsmTask>& tasks);
+  void loop_rounds_resident(const LoopPlan& lp, const Tier0MsmPlan& pl);
+  // the one body of ipa_prove / same_msm_prove (engine.cpp).  fam: G | G' resp. G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u; vec: c | d resp. x
+  void subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* const vec[2],
+                    const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status);
   // the one body of ipa_verify / same_msm_verify (engine.cpp).  fam: G resp. G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u
   void subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* vec_u,
                      const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts);

@@ -5,6 +5,7 @@
 #include "g1.hpp"
 #include "g1_28.hpp"
 #include "subarg_check_plan.hpp"
+#include "subarg_prove_plan.hpp"
 
 namespace cpx {
 
@@ -260,6 +261,20 @@ struct SubargDev {
   uint64_t* states;        // [count][27]
 };
 void launch_subarg_scalars(const SubargDev& d, hipStream_t s);
+// The steps of cpx_ipa_prove / cpx_same_msm_prove before the log-round loop for pl.count() items (subarg_prove.hip; every layout:
+// subarg_prove_plan.hpp).  launch_subarg_blinders (IPA only): r_d and the per-item flag from the witness and the draws.
+// launch_subarg_prove_setup: step 1 on the item's transcript state from the encodings of the statement and B points (and of T | U),
+// alpha (, beta), and the loop's vectors r + alpha v with unit fold coefficients; a flagged item keeps its state
+struct SubargProveDev {
+  SubargProvePlan pl;
+  Fr* fr;                  // the loop's Fr memory | witness | draws | r_d | z | alpha (, beta)
+  Fr *vec, *ones, *finals; // of the loop's memory (loop_plan.hpp): the vectors [count][4 n resp. 2 n], IPA: the ones [count], the finals
+  const uint8_t* bytes;    // the loop's round encodings | B and statement encodings | T, U encodings | rng states
+  uint8_t* flags;          // [count]: 1 = the reference panics in generate_ipa_blinders
+  uint64_t* states;        // [count][27]
+};
+void launch_subarg_blinders(const SubargProveDev& d, hipStream_t s);
+void launch_subarg_prove_setup(const SubargProveDev& d, hipStream_t s);
 // transcript prefix of every proof: absorbs the compressed instance ([nproofs][4*ell*48] + [nproofs][48] for M), draws vec_a;
 // d_state: [nproofs][27] u64 (25 STROBE lanes, pos, pos_begin), d_vec_a: [nproofs][ell] Fr
 // lane_per_proof: one lane instead of 32 per transcript (large batches: a fifth of the wave instructions, a longer chain)

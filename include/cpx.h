@@ -202,6 +202,52 @@ int cpx_same_msm_verify(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, 
                         const uint8_t* Z_t, const uint8_t* Z_u /* count*144 each */, const uint8_t* proofs /* count*(48*(3+6L)+32) */,
                         const uint8_t* rand /* count*3*32 */, uint8_t* transcripts /* count*216, in/out */, uint8_t* challenges /* count*(1+L)*32, may be NULL */,
                         int* verdicts /* count */);
+/* InnerProductProof::new (inner_product_argument.rs:98-199) for `count` independent stand-alone statements over n = 2^L bases each, the
+ * whole function in ONE call: generate_ipa_blinders (:42-82), B_c = <r_c, G>, B_d = <r_d, G'>, step 1 of the transcript (C, D, z, B_c, B_d
+ * under "ipa_step1", alpha under "ipa_alpha", beta under "ipa_beta"), the rewrite of the vectors by alpha, H = beta crs_H, and the L rounds
+ * of cpx_ipa_rounds on the same device memory.
+ *   G, G_prime   the bases (`crs_G_vec`, `crs_G_prime_vec`), affine          crs_H, C, D   144-byte Jacobian points, any representative,
+ *   z, vec_c, vec_d  the statement's scalar and the witness                                Z = 0 for the identity
+ *   rand         per item the 2 n - 2 values the reference draws, in its order: r [n], then z [n - 2] (:46-47)
+ *   transcripts  in: the states before `new`; out: advanced by the whole `new`: step 1, alpha, beta and all L rounds
+ *   proofs       the reference's `serialize` of what `new` returns (:328-338): B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D compressed,
+ *                then c_final, d_final as canonical little-endian scalars — what cpx_ipa_verify takes
+ *   challenges   per item alpha, beta, gamma_1..L (Montgomery limbs); may be NULL
+ *   status       per item CPX_OK, or CPX_ERR_ARG where the reference panics in generate_ipa_blinders: c[n-2] = 0 (:69) or the denominator
+ *                -r[n-2] c[n-2]^-1 c[n-1] + r[n-1] = 0 (:71).  Such an item's proof bytes and challenges are zero and its transcript state
+ *                is unchanged; the other items are unaffected and the call returns CPX_OK.  Pre-fill `status` with a non-zero code, as for
+ *                the other batched calls: an entry the library has not written is then never read as a proof.
+ * Conventions of cpx_ipa_rounds / cpx_ipa_verify: scalars are Montgomery limbs and a value >= r anywhere is CPX_ERR_ARG for the call; the
+ * identity is a legal base and a legal statement point; count = 0 is a no-op returning CPX_OK; n = 0 or not a power of two is
+ * CPX_ERR_NOT_POW2; n = 1 is CPX_ERR_ARG (the reference's n - 2 underflows), n = 2 is real (no free z draw, delta an empty sum); NULL with
+ * work to do and an invalid transcript state are CPX_ERR_ARG; the limits are those of one cpx_ipa_rounds (16384 items,
+ * count (2 n + 2) <= 2^24), checked before anything is read; on any return other than CPX_OK nothing is written, states included.  One
+ * upload, one download, ONE stream synchronisation; launches that depend on L only (curdleproofs_amd/csrc/subarg_prove_plan.hpp,
+ * subarg_prove.hip); no CRS is needed and the loaded batch is untouched.  Scratch is the tier-0 set (no buffer beyond its 23), trimmed by
+ * the same 64 MiB rule.  Measurements: profiles/subarg_prove.md. */
+int cpx_ipa_prove(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime /* count*n*96 each */, const uint8_t* crs_H, const uint8_t* C,
+                  const uint8_t* D /* count*144 each */, const uint8_t* z /* count*32 */, const uint8_t* vec_c, const uint8_t* vec_d /* count*n*32 each */,
+                  const uint8_t* rand /* count*(2n-2)*32 */, uint8_t* transcripts /* count*216, in/out */, uint8_t* proofs /* count*(48*(2+4L)+64) */,
+                  uint8_t* challenges /* count*(2+L)*32, may be NULL */, int* status /* count */);
+/* SameMultiscalarProof::new (same_multiscalar_argument.rs:69-150) likewise: bases G, T, U, statement A, Z_t, Z_u, witness vec_x; rand is
+ * vec_r, n values per item (:78); step 1 hashes A, Z_t, Z_u, vec_T, vec_U, B_a, B_t, B_u under "same_msm_step1" and draws alpha under
+ * "same_msm_alpha"; proofs are B_a, B_t, B_u, vec_L_A, vec_L_T, vec_L_U, vec_R_A, vec_R_T, vec_R_U, x_final (:263-275); challenges are
+ * alpha, gamma_1..L.  n = 1 is real: L = 0, the proof is the three B points and x_final = r_0 + alpha x_0.  Every item's status is CPX_OK.
+ * Limits of one cpx_same_msm_rounds: 10922 items, 3 count n <= 2^24. */
+int cpx_same_msm_prove(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U /* count*n*96 each */, const uint8_t* A,
+                       const uint8_t* Z_t, const uint8_t* Z_u /* count*144 each */, const uint8_t* vec_x /* count*n*32 */, const uint8_t* rand /* count*n*32 */,
+                       uint8_t* transcripts /* count*216, in/out */, uint8_t* proofs /* count*(48*(3+6L)+32) */, uint8_t* challenges /* count*(1+L)*32, may be NULL */,
+                       int* status /* count */);
+/* The same two with the reference's `rng: &mut T` in place of the draws ("the reference's rng as a ChaCha12 state", below): item i draws
+ * Fr::rand 2 n - 2 (IPA) or n (SameMSM) times from states[i] on the device — the stream cpx_rng_fr would give — and the 40-byte state comes
+ * back advanced; the draws never leave the device.  A refused IPA item's state is advanced too: the reference had drawn before it panicked.
+ * A state whose word_pos is within 2^32 words of 2^64 is CPX_ERR_ARG, as are more than 2^20 draws per stream or 2^26 per call. */
+int cpx_ipa_prove_rng(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D,
+                      const uint8_t* z, const uint8_t* vec_c, const uint8_t* vec_d, uint8_t* states /* count*40, in/out */, uint8_t* transcripts, uint8_t* proofs,
+                      uint8_t* challenges, int* status);
+int cpx_same_msm_prove_rng(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t,
+                           const uint8_t* Z_u, const uint8_t* vec_x, uint8_t* states /* count*40, in/out */, uint8_t* transcripts, uint8_t* proofs,
+                           uint8_t* challenges, int* status);
 /* ark_ec `CurveGroup::normalize_batch` (+ optional `serialize_compressed`); either output may be NULL */
 int cpx_g1_normalize(cpx_ctx* ctx, const uint8_t* jac /* n*144 */, size_t n, uint8_t* out_affine /* n*96 */, uint8_t* out_compressed /* n*48 */);
 /* whisk.rs:318-320 `from_bytes_g1affine` = deserialize_compressed with on-curve + subgroup validation */

@@ -71,6 +71,17 @@ extern "C" {
                           proofs: *const u8, rand: *const u8, transcripts: *mut u8, challenges: *mut u8, verdicts: *mut c_int) -> c_int;
     pub fn cpx_same_msm_verify(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, t: *const u8, u: *const u8, a: *const u8, z_t: *const u8, z_u: *const u8,
                                proofs: *const u8, rand: *const u8, transcripts: *mut u8, challenges: *mut u8, verdicts: *mut c_int) -> c_int;
+    // the provers of the two sub-arguments on the caller's bases (inner_product_argument.rs:98-199, same_multiscalar_argument.rs:69-150), `count`
+    // stand-alone statements per call: the reference's `serialize` bytes out; status[i] = CPX_OK / CPX_ERR_ARG (generate_ipa_blinders panics);
+    // the _rng forms draw on the device from 40-byte ChaCha12 states: subargs_mi355x.rs
+    pub fn cpx_ipa_prove(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, g_prime: *const u8, crs_h: *const u8, c: *const u8, d: *const u8, z: *const u8,
+                         vec_c: *const u8, vec_d: *const u8, rand: *const u8, transcripts: *mut u8, proofs: *mut u8, challenges: *mut u8, status: *mut c_int) -> c_int;
+    pub fn cpx_same_msm_prove(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, t: *const u8, u: *const u8, a: *const u8, z_t: *const u8, z_u: *const u8,
+                              vec_x: *const u8, rand: *const u8, transcripts: *mut u8, proofs: *mut u8, challenges: *mut u8, status: *mut c_int) -> c_int;
+    pub fn cpx_ipa_prove_rng(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, g_prime: *const u8, crs_h: *const u8, c: *const u8, d: *const u8, z: *const u8,
+                             vec_c: *const u8, vec_d: *const u8, states: *mut u8, transcripts: *mut u8, proofs: *mut u8, challenges: *mut u8, status: *mut c_int) -> c_int;
+    pub fn cpx_same_msm_prove_rng(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, t: *const u8, u: *const u8, a: *const u8, z_t: *const u8, z_u: *const u8,
+                                  vec_x: *const u8, states: *mut u8, transcripts: *mut u8, proofs: *mut u8, challenges: *mut u8, status: *mut c_int) -> c_int;
     pub fn cpx_g1_normalize(ctx: *mut cpx_ctx, jac: *const u8, n: usize, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
     pub fn cpx_g1_decompress(ctx: *mut cpx_ctx, compressed: *const u8, n: usize, out_affine: *mut u8, check_subgroup: c_int) -> c_int;
     // one verdict per point (0 ok, 1 malformed / not on the curve, 2 outside the subgroup): the square root behind tests/crs.rs:13-52

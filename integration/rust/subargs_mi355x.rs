@@ -1,6 +1,8 @@
 //! The two sub-argument provers with their log-round loops replaced by ONE library call each, and `transcript.rs` backed by the
 //! 216-byte transcript value of the C ABI (include/cpx.h `cpx_transcript_*`, `cpx_ipa_rounds`, `cpx_same_msm_rounds`), and the two
-//! verifiers as ONE library call each (`cpx_ipa_verify`, `cpx_same_msm_verify`), under `--features mi355x`.  NOT COMPILED in the build image.
+//! verifiers as ONE library call each (`cpx_ipa_verify`, `cpx_same_msm_verify`), and the two `new` functions whole as ONE library call each
+//! (`cpx_ipa_prove`, `cpx_same_msm_prove`: `ipa_new`, `same_msm_new` at the end of this file), under `--features mi355x`.  NOT COMPILED in the
+//! build image.
 //!
 //! `merlin::Transcript` keeps its state private, so a transcript that the library is to continue has to live on the library's side of
 //! the boundary from the start: `Transcript216` below holds the value and implements the crate's `CurdleproofsTranscript` on it.  The
@@ -178,4 +180,63 @@ pub fn same_msm_verify<T: RngCore>(proof: &[u8], crs_G_vec: &[G1Affine], A: &G1P
                             projective_to_wire(std::slice::from_ref(Z_u)).as_ptr(), proof.as_ptr(), rand.as_ptr(), transcript.0.as_mut_ptr(), std::ptr::null_mut(), &mut v)
     };
     verdict(rc, v, "cpx_same_msm_verify")
+}
+
+/// The draws of one `new` in the reference's order, as wire bytes: `generate_blinders(rng, count)` (util.rs:32-34)
+fn draw_scalars<T: RngCore>(rng: &mut T, count: usize) -> Vec<u8> {
+    let drawn: Vec<Fr> = (0..count).map(|_| Fr::rand(rng)).collect();
+    let mut out = vec![0u8; count * FR];
+    out.copy_from_slice(unsafe { std::slice::from_raw_parts(scalars_ptr(&drawn), count * FR) });
+    out
+}
+
+/// InnerProductProof::new + serialize (inner_product_argument.rs:98-199, :328-338) in one call: blinders, B_c, B_d, step 1, alpha, beta,
+/// H and all rounds run on the device; the bytes are what `ipa_verify` above takes.  The reference panics where generate_ipa_blinders
+/// finds no inverse (:69, :71); so does this, after the call (the transcript is then as it was).  Draws: r [n], then z [n - 2] (:46-47).
+pub fn ipa_new<T: RngCore>(crs_G_vec: &[G1Affine], crs_G_prime_vec: &[G1Affine], crs_H: &G1Projective, C: &G1Projective, D: &G1Projective, z: &Fr, vec_c: &[Fr],
+                           vec_d: &[Fr], transcript: &mut Transcript216, rng: &mut T) -> Vec<u8> {
+    let n = vec_c.len();
+    let rounds = n.trailing_zeros() as usize;
+    let rand = draw_scalars(rng, 2 * n - 2);
+    let mut proof = vec![0u8; 48 * (2 + 4 * rounds) + 2 * FR];
+    let mut status: std::os::raw::c_int = CPX_ERR_INTERNAL;
+    let rc = unsafe {
+        cpx_ipa_prove(ctx(), 1, n, affine_to_wire(crs_G_vec).as_ptr(), affine_to_wire(crs_G_prime_vec).as_ptr(), projective_to_wire(std::slice::from_ref(crs_H)).as_ptr(),
+                      projective_to_wire(std::slice::from_ref(C)).as_ptr(), projective_to_wire(std::slice::from_ref(D)).as_ptr(), scalars_ptr(std::slice::from_ref(z)),
+                      scalars_ptr(vec_c), scalars_ptr(vec_d), rand.as_ptr(), transcript.0.as_mut_ptr(), proof.as_mut_ptr(), std::ptr::null_mut(), &mut status)
+    };
+    assert_eq!(rc, CPX_OK, "cpx_ipa_prove");
+    assert_eq!(status, CPX_OK, "generate_ipa_blinders: no inverse (inner_product_argument.rs:69, :71)");
+    proof
+}
+
+/// SameMultiscalarProof::new + serialize (same_multiscalar_argument.rs:69-150, :263-275) likewise; the draws are vec_r (:78).
+pub fn same_msm_new<T: RngCore>(crs_G_vec: &[G1Affine], A: &G1Projective, Z_t: &G1Projective, Z_u: &G1Projective, vec_T: &[G1Affine], vec_U: &[G1Affine], vec_x: &[Fr],
+                                transcript: &mut Transcript216, rng: &mut T) -> Vec<u8> {
+    let n = vec_x.len();
+    let rounds = n.trailing_zeros() as usize;
+    let rand = draw_scalars(rng, n);
+    let mut proof = vec![0u8; 48 * (3 + 6 * rounds) + FR];
+    let mut status: std::os::raw::c_int = CPX_ERR_INTERNAL;
+    let rc = unsafe {
+        cpx_same_msm_prove(ctx(), 1, n, affine_to_wire(crs_G_vec).as_ptr(), affine_to_wire(vec_T).as_ptr(), affine_to_wire(vec_U).as_ptr(),
+                           projective_to_wire(std::slice::from_ref(A)).as_ptr(), projective_to_wire(std::slice::from_ref(Z_t)).as_ptr(),
+                           projective_to_wire(std::slice::from_ref(Z_u)).as_ptr(), scalars_ptr(vec_x), rand.as_ptr(), transcript.0.as_mut_ptr(), proof.as_mut_ptr(),
+                           std::ptr::null_mut(), &mut status)
+    };
+    assert_eq!(rc, CPX_OK, "cpx_same_msm_prove");
+    assert_eq!(status, CPX_OK, "cpx_same_msm_prove: item status");
+    proof
+}
+
+/// Many statements of one kind at once with the library's rng (include/cpx.h "the reference's rng as a ChaCha12 state"): one 40-byte state
+/// and one transcript state per item, both in/out; `status[i]` as in include/cpx.h, pre-filled by the caller with a non-zero code.
+pub fn ipa_new_many_rng(n: usize, G: &[u8], G_prime: &[u8], crs_H: &[u8], C: &[u8], D: &[u8], z: &[Fr], vec_c: &[Fr], vec_d: &[Fr], rng_states: &mut [u8],
+                        states: &mut [u8], proofs_out: &mut [u8], status: &mut [std::os::raw::c_int]) {
+    let count = states.len() / TRANSCRIPT_BYTES;
+    let rc = unsafe {
+        cpx_ipa_prove_rng(ctx(), count, n, G.as_ptr(), G_prime.as_ptr(), crs_H.as_ptr(), C.as_ptr(), D.as_ptr(), scalars_ptr(z), scalars_ptr(vec_c), scalars_ptr(vec_d),
+                          rng_states.as_mut_ptr(), states.as_mut_ptr(), proofs_out.as_mut_ptr(), std::ptr::null_mut(), status.as_mut_ptr())
+    };
+    assert_eq!(rc, CPX_OK, "cpx_ipa_prove_rng");
 }
