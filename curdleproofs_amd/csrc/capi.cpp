@@ -689,6 +689,38 @@ int cpx_same_msm_prove_rng(cpx_ctx* ctx, size_t count, size_t n, const uint8_t* 
     return (int)CPX_OK;
   });
 }
+int cpx_gprod_prove(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* B,
+                    const uint8_t* gprod_result, const uint8_t* vec_b, const uint8_t* vec_b_blinders, const uint8_t* rand, uint8_t* transcripts, uint8_t* proofs,
+                    uint8_t* challenges, int* status) {
+  if (count && ell &&
+      (!G || (n_blinders && (!H || !vec_b_blinders)) || !crs_U || !B || !gprod_result || !vec_b || !rand || !transcripts || !proofs || !status))
+    return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->gprod_prove(count, ell, n_blinders, G, H, crs_U, B, gprod_result, vec_b, vec_b_blinders, rand, nullptr, transcripts, proofs, challenges, status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_gprod_prove_rng(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* B,
+                        const uint8_t* gprod_result, const uint8_t* vec_b, const uint8_t* vec_b_blinders, uint8_t* states, uint8_t* transcripts, uint8_t* proofs,
+                        uint8_t* challenges, int* status) {
+  if (count && ell &&
+      (!G || (n_blinders && (!H || !vec_b_blinders)) || !crs_U || !B || !gprod_result || !vec_b || !states || !transcripts || !proofs || !status))
+    return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->gprod_prove(count, ell, n_blinders, G, H, crs_U, B, gprod_result, vec_b, vec_b_blinders, nullptr, states, transcripts, proofs, challenges, status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_gprod_verify(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* crs_G_sum,
+                     const uint8_t* crs_H_sum, const uint8_t* B, const uint8_t* gprod_result, const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts,
+                     uint8_t* challenges, int* verdicts) {
+  if (count && ell && (!G || (n_blinders && !H) || !crs_U || !crs_G_sum || !crs_H_sum || !B || !gprod_result || !proofs || !rand || !transcripts || !verdicts))
+    return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->gprod_verify(count, ell, n_blinders, G, H, crs_U, crs_G_sum, crs_H_sum, B, gprod_result, proofs, rand, transcripts, challenges, verdicts);
+    return (int)CPX_OK;
+  });
+}
 
 int cpx_set_profiling(cpx_ctx* ctx, int on) {
   if (!ctx || !ctx->eng) return CPX_ERR_ARG;

@@ -201,6 +201,14 @@ class Engine {
   void same_msm_prove(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t, const uint8_t* Z_u,
                       const uint8_t* vec_x, const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges,
                       int* status);                                                                                                          // same_multiscalar_argument.rs:69-150
+  // the grand-product prover on the caller's bases likewise (gprod_plan.hpp, gprod.hip; include/cpx.h cpx_gprod_prove and its _rng form):
+  // ell factors and n_blinders blinders per item, rand = vec_c_blinders then the inner-product prover's draws
+  void gprod_prove(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* B, const uint8_t* gprod_result,
+                   const uint8_t* vec_b, const uint8_t* vec_b_blinders, const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs,
+                   uint8_t* challenges, int* status);                                                                                        // grand_product_argument.rs:43-166
+  void gprod_verify(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* crs_G_sum,
+                    const uint8_t* crs_H_sum, const uint8_t* B, const uint8_t* gprod_result, const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts,
+                    uint8_t* challenges, int* verdicts);                                                                                     // grand_product_argument.rs:180-246
   void normalize(const uint8_t* jac, size_t n, uint8_t* out_aff, uint8_t* out_comp);                   // normalize_batch (+compress)
   int decompress(const uint8_t* comp, size_t n, uint8_t* out_aff, int check_subgroup, uint8_t* status_out = nullptr);   // whisk.rs:318-320
 
@@ -517,11 +525,21 @@ class Engine {
   void loop_rounds_lists(const LoopPlan& lp, const Tier0MsmPlan& pl, std::vector<uint32_t>& idx, std::vector<MsmTask>& tasks);
   void loop_rounds_resident(const LoopPlan& lp, const Tier0MsmPlan& pl);
   // the one body of ipa_prove / same_msm_prove (engine.cpp).  fam: G | G' resp. G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u; vec: c | d resp. x
+  // ... and, with gp, of gprod_prove: the inner-product prover behind the grand-product layer, whose inputs stand in gp (fam, stmt, z, vec: null)
+  struct GprodCall {
+    size_t ell, nb;
+    const uint8_t *G, *H, *crs_U, *B, *result, *vec_b, *vec_b_blinders;
+  };
   void subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* const vec[2],
-                    const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status);
+                    const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status, const GprodCall* gp = nullptr);
   // the one body of ipa_verify / same_msm_verify (engine.cpp).  fam: G resp. G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u
+  // ... and, with gp, of gprod_verify: the inner-product check behind the grand-product steps, whose inputs stand in gp (fam, stmt, z, vec_u: null)
+  struct GprodCheck {
+    size_t ell, nb;
+    const uint8_t *G, *H, *crs_U, *g_sum, *h_sum, *B, *result;
+  };
   void subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* vec_u,
-                     const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts);
+                     const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts, const GprodCheck* gp = nullptr);
   // n trackers -> the planes r_G | k_r_G: upload + k_decompress of the tracker prover, find-trackers and the candidate list (whisk.cpp)
   void decode_tracker_planes(size_t n, const uint8_t* trackers, std::vector<uint8_t>& canon, std::vector<uint32_t>& off, uint8_t* d_bytes, uint32_t* d_off, Aff* d_pts,
                              uint8_t* d_status);

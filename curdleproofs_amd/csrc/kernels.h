@@ -6,6 +6,7 @@
 #include "g1_28.hpp"
 #include "subarg_check_plan.hpp"
 #include "subarg_prove_plan.hpp"
+#include "gprod_plan.hpp"
 
 namespace cpx {
 
@@ -272,9 +273,35 @@ struct SubargProveDev {
   const uint8_t* bytes;    // the loop's round encodings | B and statement encodings | T, U encodings | rng states
   uint8_t* flags;          // [count]: 1 = the reference panics in generate_ipa_blinders
   uint64_t* states;        // [count][27]
+  const Fr* sgp_seed;      // nullable, IPA: [count][n] fold coefficients G' starts from instead of 1 (cpx_gprod_prove: G' = u o G is never formed)
 };
 void launch_subarg_blinders(const SubargProveDev& d, hipStream_t s);
 void launch_subarg_prove_setup(const SubargProveDev& d, hipStream_t s);
+// The grand-product layer of cpx_gprod_prove ahead of those steps for pl.count() items (gprod.hip; every layout: gprod_plan.hpp).
+// launch_gprod_products: vec_c | vec_c_blinders into the IPA's witness c.  launch_gprod_setup: steps 1 and 2 on the item's transcript state
+// from the encodings of B and C, alpha, r_p, beta, then u, vec_d | vec_d_blinders into the IPA's witness d, inner_prod into its z, the D
+// task's scalars and the flag of beta = 0.  launch_gprod_rdu: r_d o u, once launch_subarg_blinders has made r_d.
+constexpr int GPROD_THREADS = 128;
+struct GprodDev {
+  GprodProvePlan pl;
+  Fr* fr;                  // the IPA prover's Fr memory | the regions of gprod_plan.hpp
+  const uint8_t* bytes;    // the IPA prover's bytes | B and C encodings
+  uint8_t* flags;          // [2][count]: generate_ipa_blinders panics | beta = 0
+  uint64_t* states;        // [count][27]
+};
+// The steps of cpx_gprod_verify ahead of those of cpx_ipa_verify (gprod.hip k_gprod_verify_steps): per item the flag of C / r_p, steps 1 and
+// 2 on the transcript state, then z and vec_u into the IPA check's regions (subarg_check_plan.hpp) and the scalars of D
+struct GprodVerifyDev {
+  GprodCheckPlan pl;         // gprod_plan.hpp: the inner-product check on n = ell + n_blinders elements and the regions behind its own
+  Fr* fr;
+  const uint8_t* bytes;
+  uint8_t* status;           // reads the decoder's verdict of C, writes the flag of C / r_p
+  uint64_t* states;          // [count][27]
+};
+void launch_gprod_verify_steps(const GprodVerifyDev& d, hipStream_t s);
+void launch_gprod_products(const GprodDev& d, hipStream_t s);
+void launch_gprod_setup(const GprodDev& d, hipStream_t s);
+void launch_gprod_rdu(const GprodDev& d, hipStream_t s);
 // transcript prefix of every proof: absorbs the compressed instance ([nproofs][4*ell*48] + [nproofs][48] for M), draws vec_a;
 // d_state: [nproofs][27] u64 (25 STROBE lanes, pos, pos_begin), d_vec_a: [nproofs][ell] Fr
 // lane_per_proof: one lane instead of 32 per transcript (large batches: a fifth of the wave instructions, a longer chain)

@@ -110,11 +110,12 @@ template <bool IPA> __global__ __launch_bounds__(SPROVE_THREADS) void k_subarg_p
   Fr* vec = d.vec + item * (IPA ? 4 : 2) * (size_t)n;
   if (IPA) {
     const Fr* rd = d.fr + pl.fr_rd() + item * (size_t)n;
+    const Fr* seed = d.sgp_seed ? d.sgp_seed + item * (size_t)n : nullptr;   // (uniform over the launch)
     for (int i = tid; i < n; i += SPROVE_THREADS) {
       vec[i] = flagged ? Fr::zero() : fe_add(r[i], fe_mul(alpha, wit[i]));
       vec[n + i] = flagged ? Fr::zero() : fe_add(rd[i], fe_mul(alpha, wit[n + i]));
       vec[2 * (size_t)n + i] = one;
-      vec[3 * (size_t)n + i] = one;
+      vec[3 * (size_t)n + i] = seed ? seed[i] : one;
     }
     if (tid == 0) d.ones[item] = one;   // (H is beta crs_H already: the rounds' shared formulas multiply by 1)
   } else {

@@ -82,6 +82,18 @@ extern "C" {
                              vec_c: *const u8, vec_d: *const u8, states: *mut u8, transcripts: *mut u8, proofs: *mut u8, challenges: *mut u8, status: *mut c_int) -> c_int;
     pub fn cpx_same_msm_prove_rng(ctx: *mut cpx_ctx, count: usize, n: usize, g: *const u8, t: *const u8, u: *const u8, a: *const u8, z_t: *const u8, z_u: *const u8,
                                   vec_x: *const u8, states: *mut u8, transcripts: *mut u8, proofs: *mut u8, challenges: *mut u8, status: *mut c_int) -> c_int;
+    // the grand-product prover on the caller's bases (grand_product_argument.rs:43-166), `count` stand-alone statements of ell factors and
+    // n_blinders blinders per call: C, r_p and the InnerProductProof bytes out; rand = vec_c_blinders, then the inner-product prover's draws
+    pub fn cpx_gprod_prove(ctx: *mut cpx_ctx, count: usize, ell: usize, n_blinders: usize, g: *const u8, h: *const u8, crs_u: *const u8, b: *const u8,
+                           gprod_result: *const u8, vec_b: *const u8, vec_b_blinders: *const u8, rand: *const u8, transcripts: *mut u8, proofs: *mut u8,
+                           challenges: *mut u8, status: *mut c_int) -> c_int;
+    pub fn cpx_gprod_prove_rng(ctx: *mut cpx_ctx, count: usize, ell: usize, n_blinders: usize, g: *const u8, h: *const u8, crs_u: *const u8, b: *const u8,
+                               gprod_result: *const u8, vec_b: *const u8, vec_b_blinders: *const u8, states: *mut u8, transcripts: *mut u8, proofs: *mut u8,
+                               challenges: *mut u8, status: *mut c_int) -> c_int;
+    // GrandProductProof::verify on those bytes (grand_product_argument.rs:180-246): crs_g_sum / crs_h_sum affine, taken from the caller
+    pub fn cpx_gprod_verify(ctx: *mut cpx_ctx, count: usize, ell: usize, n_blinders: usize, g: *const u8, h: *const u8, crs_u: *const u8, crs_g_sum: *const u8,
+                            crs_h_sum: *const u8, b: *const u8, gprod_result: *const u8, proofs: *const u8, rand: *const u8, transcripts: *mut u8,
+                            challenges: *mut u8, verdicts: *mut c_int) -> c_int;
     pub fn cpx_g1_normalize(ctx: *mut cpx_ctx, jac: *const u8, n: usize, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
     pub fn cpx_g1_decompress(ctx: *mut cpx_ctx, compressed: *const u8, n: usize, out_affine: *mut u8, check_subgroup: c_int) -> c_int;
     // one verdict per point (0 ok, 1 malformed / not on the curve, 2 outside the subgroup): the square root behind tests/crs.rs:13-52

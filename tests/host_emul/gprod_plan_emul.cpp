@@ -1,0 +1,157 @@
+// g++ program over curdleproofs_amd/csrc/gprod_plan.hpp and gprod_algebra.hpp (tests/test_gprod_cpu.py): the layout of cpx_gprod_prove
+// exactly as the engine and the kernels of gprod.hip use it, and the grand-product layer's algebra computed the way k_gprod_products and
+// k_gprod_setup compute it (`workers` threads, each with its chunk), printed as plain "key value..." lines.  The test builds it twice,
+// the second time with -fsanitize=address,undefined.
+//   gprod_plan_emul plan <count> <ell> <nb>                       the whole plan, or the status alone where it is not GPROD_OK
+//   gprod_plan_emul check <count> <ell> <nb>                      the verifier's plan (GprodCheckPlan)
+//   gprod_plan_emul scan <workers> <ell> <hex>...                 b [ell] as canonical hexadecimal integers: "c" with the ell prefix products, the
+//                                                                 chunk products combined in log steps; "differ" 1 if the serial combination disagrees
+//   gprod_plan_emul layer <workers> <ell> <nb> <hex>...           alpha, beta, gprod_result, b [ell], rb [nb], c_blinders [nb]:
+//                                                                 "r_p", "inner_prod", "u" [n], "d" [n], "dsc" [n], "uv" [n] (the verifier's vec_u)
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "../../curdleproofs_amd/csrc/modinv30.hpp"
+#include "../../curdleproofs_amd/csrc/gprod_algebra.hpp"
+#include "../../curdleproofs_amd/csrc/gprod_plan.hpp"
+
+using namespace cpx;
+
+static Fr from_hex(const char* s) {   // canonical integer -> Montgomery
+  Fr c = Fr::zero();
+  const size_t len = strlen(s);
+  for (size_t i = 0; i < len && i < 64; i++) {
+    const char ch = s[len - 1 - i];
+    const uint32_t d = ch >= '0' && ch <= '9' ? (uint32_t)(ch - '0') : (uint32_t)((ch | 0x20) - 'a' + 10);
+    c.v[i / 8] |= (d & 15u) << (4 * (i % 8));
+  }
+  return fe_to_mont(c);
+}
+static void print_hex(const Fr& mont) {
+  const Fr c = fe_from_mont(mont);
+  printf(" ");
+  for (int j = 7; j >= 0; j--) printf("%08x", c.v[j]);
+}
+static void print_vec(const char* name, const std::vector<Fr>& v) {
+  printf("%s", name);
+  for (const Fr& x : v) print_hex(x);
+  printf("\n");
+}
+
+int main(int argc, char** argv) {
+  if (argc >= 4 && !strcmp(argv[1], "scan")) {
+    const int workers = atoi(argv[2]), ell = atoi(argv[3]);
+    if (workers < 1 || ell < 1 || argc != 4 + ell) {
+      fprintf(stderr, "scan: workers >= 1, ell >= 1 and ell scalars expected\n");
+      return 2;
+    }
+    std::vector<Fr> b((size_t)ell), c((size_t)ell, Fr::zero()), part((size_t)workers);
+    for (int i = 0; i < ell; i++) b[(size_t)i] = from_hex(argv[4 + i]);
+    int lo, hi;
+    for (int t = 0; t < workers; t++) {   // the work-group's threads, its one combining thread, the threads again
+      gprod_chunk(ell, workers, t, lo, hi);
+      part[(size_t)t] = gprod_chunk_product(b.data(), lo, hi);
+    }
+    std::vector<Fr> serial = part, step = part, next((size_t)workers);
+    gprod_scan_exclusive(serial.data(), workers);                 // one worker after the other ...
+    for (int off = 1; off < workers; off <<= 1) {                 // ... and the work-group's log steps (k_gprod_products), which must agree
+      for (int t = 0; t < workers; t++) next[(size_t)t] = gprod_scan_step(step.data(), t, off);
+      step.swap(next);
+    }
+    int differ = 0;
+    for (int t = 0; t < workers; t++) {
+      const Fr before = t ? step[(size_t)t - 1] : Fr::one();
+      for (int j = 0; j < 8; j++) differ |= before.v[j] != serial[(size_t)t].v[j];
+      gprod_chunk(ell, workers, t, lo, hi);
+      gprod_chunk_fixup(b.data(), lo, hi, before, c.data());
+    }
+    printf("differ %d\n", differ);
+    print_vec("c", c);
+    return 0;
+  }
+  if (argc >= 5 && !strcmp(argv[1], "layer")) {
+    const int workers = atoi(argv[2]), ell = atoi(argv[3]), nb = atoi(argv[4]), n = ell + nb;
+    if (workers < 1 || ell < 1 || nb < 0 || argc != 5 + 3 + ell + 2 * nb) {
+      fprintf(stderr, "layer: workers >= 1, ell >= 1 and 3 + ell + 2 nb scalars expected\n");
+      return 2;
+    }
+    std::vector<Fr> in((size_t)(3 + ell + 2 * nb));
+    for (size_t i = 0; i < in.size(); i++) in[i] = from_hex(argv[5 + i]);
+    const Fr alpha = in[0], beta = in[1], result = in[2];
+    const Fr *b = in.data() + 3, *rb = b + ell, *cbl = rb + nb;
+    const Fr beta_inv = fr_inv_divsteps(beta), beta_l = gprod_pow(beta, (uint64_t)ell);
+    const Fr r_p = gprod_r_p(rb, cbl, nb, alpha);
+    std::vector<Fr> u((size_t)n), d((size_t)n), dsc((size_t)n);
+    for (int t = 0; t < workers; t++) {
+      int lo, hi;
+      gprod_chunk(ell, workers, t, lo, hi);
+      gprod_fill_chunk(b, lo, hi, beta, beta_inv, u.data(), d.data(), dsc.data());
+      gprod_fill_blinders(rb, ell, nb, t, workers, alpha, fe_mul(beta_l, beta), gprod_pow(beta_inv, (uint64_t)ell + 1), u.data(), d.data(), dsc.data());
+    }
+    printf("r_p");
+    print_hex(r_p);
+    printf("\ninner_prod");
+    print_hex(gprod_inner_prod(r_p, result, beta_l, beta));
+    printf("\n");
+    print_vec("u", u);
+    print_vec("d", d);
+    print_vec("dsc", dsc);
+    std::vector<Fr> uv((size_t)n);   // the verifier's vec_u, chunks over all n positions (k_gprod_verify_steps)
+    for (int t = 0; t < workers; t++) {
+      int lo, hi;
+      gprod_chunk(n, workers, t, lo, hi);
+      gprod_fill_u(lo, hi, ell, beta_inv, gprod_pow(beta_inv, (uint64_t)ell + 1), uv.data());
+    }
+    print_vec("uv", uv);
+    return 0;
+  }
+  if (argc == 5 && !strcmp(argv[1], "check")) {   // the verifier's plan
+    GprodCheckPlan gp;
+    const int status = (int)gprod_check_plan((size_t)strtoull(argv[2], nullptr, 10), (size_t)strtoull(argv[3], nullptr, 10), (size_t)strtoull(argv[4], nullptr, 10), gp);
+    printf("status %d\n", status);
+    if (status != SUBARG_OK) return 0;
+    printf("sp %zu %zu %zu %zu %zu %zu %zu\n", gp.sp.points(), gp.sp.proof_points(), gp.sp.by_total(), gp.sp.fr_total(), gp.sp.ix_total(), gp.sp.fr_z(), gp.sp.fr_u());
+    printf("proof %zu %zu %zu\n", gp.proof_bytes(), gp.rp_byte(), gp.challenges());
+    printf("by %zu %zu %zu %zu\n", gp.by_heads(), gp.by_B(), gp.by_D(), gp.by_total());
+    printf("st %zu %zu %zu\n", gp.st_C(), gp.st_bad(), gp.st_total());
+    printf("fr %zu %zu %zu %zu %zu\n", gp.fr_result(), gp.fr_neg_beta_inv(), gp.fr_alpha(), gp.fr_chal(), gp.fr_total());
+    printf("ix %zu %zu %zu %zu\n", gp.ix_C_src(), gp.ix_C_dst(), gp.ix_U_dst(), gp.ix_total());
+    printf("aff %zu %zu %zu %zu %zu %zu\n", gp.aff_B(), gp.aff_g_sum(), gp.aff_h_sum(), gp.aff_partial(), gp.aff_D(), gp.aff_total());
+    std::vector<uint32_t> ix;
+    gp.fill_idx(ix);
+    printf("lists");
+    for (uint32_t v : ix) printf(" %u", v);
+    printf("\n");
+    return 0;
+  }
+  if (argc != 5 || strcmp(argv[1], "plan")) {
+    fprintf(stderr, "usage: gprod_plan_emul plan <count> <ell> <nb> | scan <workers> <ell> <hex>... | layer <workers> <ell> <nb> <hex>...\n");
+    return 2;
+  }
+  const size_t count = (size_t)strtoull(argv[2], nullptr, 10), ell = (size_t)strtoull(argv[3], nullptr, 10), nb = (size_t)strtoull(argv[4], nullptr, 10);
+  GprodProvePlan gp;
+  const int status = (int)gprod_prove_plan(count, ell, nb, gp);
+  printf("status %d\n", status);
+  if (status != GPROD_OK) return 0;
+  printf("n %zu\nL %zu\ndraws_each %zu\nchallenges %zu\nproof_bytes %zu\nbytes %zu %zu %zu\n", gp.n(), gp.sp.L(), gp.draws_each(), gp.challenges(), gp.proof_bytes(),
+         gp.byte_C(), gp.byte_rp(), gp.byte_ipa());
+  printf("sp %zu %zu %zu %zu %zu\n", gp.sp.fr_wit(), gp.sp.fr_draws(), gp.sp.fr_rd(), gp.sp.fr_z(), gp.sp.fr_ab());
+  printf("fr %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", gp.fr_result(), gp.fr_b(), gp.fr_rb(), gp.fr_cbl(), gp.fr_u(), gp.fr_dsc(), gp.fr_rdu(), gp.fr_rp(), gp.fr_chal(),
+         gp.fr_total());
+  printf("pt %zu %zu %zu\n", gp.pt_B(0), gp.jac_total(), gp.aff_total());
+  printf("res %zu %zu %zu\n", gp.res_C(0), gp.res_D(0), gp.res_total());
+  printf("by %zu %zu %zu\n", gp.by_B(), gp.by_C(), gp.by_total());
+  printf("flags %zu %zu\n", gp.flag_beta(), gp.flags_total());
+  printf("ix %zu %zu\n", gp.ix_addend(), gp.ix_total());
+  printf("task %zu %zu %zu\n", gp.task_C(), gp.task_D(), gp.task_total());
+  std::vector<uint32_t> ix, lens;
+  gp.fill_addend(ix);
+  printf("addend");
+  for (uint32_t v : ix) printf(" %u", v);
+  printf("\n");
+  Tier0MsmPlan pl;
+  const bool ok = gp.item_msm(pl, lens);
+  printf("msm %d %zu %zu %u\n", ok ? 1 : 0, pl.count, pl.points, pl.max_n);
+  return 0;
+}
