@@ -59,7 +59,7 @@ _libs = {}   # realpath -> loaded library (the default one and build variants fo
 
 EXPORTS = [
     "cpx_host_alloc", "cpx_host_free", "cpx_ctx_create", "cpx_ctx_destroy", "cpx_last_error", "cpx_device_count", "cpx_ctx_set_option", "cpx_ctx_get_option", "cpx_ctx_set_crs", "cpx_crs_sums", "cpx_proof_size", "cpx_batch_size",
-    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_ipa_rounds", "cpx_same_msm_rounds", "cpx_ipa_verify", "cpx_same_msm_verify", "cpx_ipa_prove", "cpx_same_msm_prove", "cpx_ipa_prove_rng", "cpx_same_msm_prove_rng", "cpx_gprod_prove", "cpx_gprod_prove_rng", "cpx_gprod_verify",
+    "cpx_g1_msm", "cpx_g1_msm_jac", "cpx_g1_fold", "cpx_g1_scale", "cpx_g1_msm_many", "cpx_g1_fold_many", "cpx_ipa_rounds", "cpx_same_msm_rounds", "cpx_ipa_verify", "cpx_same_msm_verify", "cpx_ipa_prove", "cpx_same_msm_prove", "cpx_ipa_prove_rng", "cpx_same_msm_prove_rng", "cpx_gprod_prove", "cpx_gprod_prove_rng", "cpx_gprod_verify", "cpx_same_perm_prove", "cpx_same_perm_prove_rng", "cpx_same_perm_verify",
     "cpx_transcript_new", "cpx_transcript_append_message", "cpx_transcript_append_scalar", "cpx_transcript_challenge_bytes", "cpx_transcript_challenge_scalar",
     "cpx_g1_normalize", "cpx_g1_decompress", "cpx_g1_decompress_status",
     "cpx_accum_new", "cpx_accum_free", "cpx_accum_check", "cpx_accum_verify",
@@ -128,6 +128,10 @@ def load_library(path=None):
         L.cpx_gprod_prove.argtypes = [vp, sz, sz, sz] + [vp] * 12
         L.cpx_gprod_prove_rng.argtypes = [vp, sz, sz, sz] + [vp] * 12
         L.cpx_gprod_verify.argtypes = [vp, sz, sz, sz] + [vp] * 12
+    if hasattr(L, "cpx_same_perm_prove"):   # (likewise: scripts/same_perm_timing.py)
+        L.cpx_same_perm_prove.argtypes = [vp, sz, sz, sz] + [vp] * 14
+        L.cpx_same_perm_prove_rng.argtypes = [vp, sz, sz, sz] + [vp] * 14
+        L.cpx_same_perm_verify.argtypes = [vp, sz, sz, sz] + [vp] * 13
     L.cpx_transcript_new.argtypes = [vp, sz, vp]
     L.cpx_transcript_append_message.argtypes = [vp, vp, sz, vp, sz]
     L.cpx_transcript_append_scalar.argtypes = [vp, vp, sz, vp]
@@ -551,6 +555,50 @@ class Context:
         return self._subarg_verify(fn, "gprod_verify", count, n, (G, H, crs_U, crs_G_sum, crs_H_sum, B), (gprod_result,), proofs, rand, states, 2, 4 + L,
                                    48 * (3 + 4 * L) + 96, challenges)
 
+    def same_perm_prove(self, ell, G, H, crs_U, A, M, vec_a, permutation, vec_a_blinders, vec_m_blinders, states, rand=None, rngs=None, challenges=False):
+        """SamePermutationProof::new (same_permutation_argument.rs:40-99) for len(A) // 144 independent stand-alone statements of ell
+        elements each in ONE call (cpx_same_perm_prove / cpx_same_perm_prove_rng); n_blinders is what vec_a_blinders holds per item, and
+        n = ell + n_blinders a power of two.  G (ell per item), H (n_blinders per item): the affine bases, item after item; crs_U, A, M:
+        144-byte Jacobian points; vec_a, vec_a_blinders, vec_m_blinders: Montgomery limbs; permutation: ell values below ell per item,
+        a sequence of integers or their little-endian u32 bytes; states: the 216-byte transcript states before `new`.  Exactly one of
+        rand (the draws of gprod_prove: this layer draws nothing) and rngs (as ipa_prove).  Returns the dict of gprod_prove: "proofs" are B
+        and the GrandProductProof bytes, "challenges" per item same-perm alpha, beta, then those of gprod_prove."""
+        import struct
+        count = len(A) // JAC
+        if not isinstance(permutation, (bytes, bytearray, memoryview)):
+            permutation = list(permutation)
+            if any(not 0 <= int(v) < 1 << 32 for v in permutation):
+                raise ValueError("same_perm_prove: the permutation's entries are u32 values")
+            permutation = struct.pack("<%dI" % len(permutation), *permutation)
+        nb = len(vec_a_blinders) // (count * FR) if count else 0
+        n = ell + nb
+        L = max(n.bit_length() - 1, 0)
+        if len(G) != count * ell * AFF or len(H) != count * nb * AFF or len(vec_a) != count * ell * FR or len(permutation) != count * ell * 4 or \
+                any(len(v) != count * nb * FR for v in (vec_a_blinders, vec_m_blinders)) or any(len(p) != count * JAC for p in (crs_U, A, M)):
+            raise ValueError("same_perm_prove: per item ell points in G, scalars in vec_a and entries in permutation, n_blinders points in H and scalars in "
+                             "vec_a_blinders and vec_m_blinders, and one Jacobian point in crs_U, A and M")
+        fns = tuple((lambda h, cnt, _n, *rest, fn=fn: fn(h, cnt, ell, nb, *rest)) for fn in (self._L.cpx_same_perm_prove, self._L.cpx_same_perm_prove_rng))
+        return self._subarg_prove(fns, "same_perm_prove", count, n, (G, H, crs_U, A, M, vec_a, permutation, vec_a_blinders, vec_m_blinders), nb + 2 * n - 2, states,
+                                  rand, rngs, 6 + L, 48 * (4 + 4 * L) + 96, challenges)
+
+    def same_perm_verify(self, ell, G, H, crs_U, crs_G_sum, crs_H_sum, A, M, vec_a, proofs, rand, states, challenges=False):
+        """SamePermutationProof::verify (same_permutation_argument.rs:112-171) for len(A) // 144 independent stand-alone proofs of ell
+        elements in ONE call (cpx_same_perm_verify); n_blinders is what H holds per item.  crs_G_sum, crs_H_sum: the affine sums, taken
+        from the caller as in the reference; proofs: what same_perm_prove returns; rand: THREE non-zero factors per item, the
+        same-permutation check's first.  Returns the dict of gprod_verify; "challenges" per item same-perm alpha, beta, then those of
+        gprod_verify."""
+        count = len(A) // JAC
+        nb = len(H) // (count * AFF) if count else 0
+        n = ell + nb
+        L = max(n.bit_length() - 1, 0)
+        if len(G) != count * ell * AFF or len(H) != count * nb * AFF or len(vec_a) != count * ell * FR or any(len(p) != count * JAC for p in (crs_U, A, M)) or \
+                any(len(p) != count * AFF for p in (crs_G_sum, crs_H_sum)):
+            raise ValueError("same_perm_verify: per item ell points in G and scalars in vec_a, n_blinders points in H, one Jacobian point in crs_U, A and M and "
+                             "one affine point in crs_G_sum and crs_H_sum")
+        fn = lambda h, cnt, _n, *rest: self._L.cpx_same_perm_verify(h, cnt, ell, nb, *rest)
+        return self._subarg_verify(fn, "same_perm_verify", count, n, (G, H, crs_U, crs_G_sum, crs_H_sum, A, M), (vec_a,), proofs, rand, states, 3, 6 + L,
+                                   48 * (4 + 4 * L) + 96, challenges)
+
     def normalize(self, jac, compressed=False):
         n = len(jac) // JAC
         a, c = _out(AFF * n), _out(48 * n)
@@ -751,7 +799,7 @@ class Context:
         return dict(launches=n.value, ms=ms.value, alg_bytes=by.value, units=un.value)
 
     KERNELS = ("k_msm_tblw<32, false>", "k_reduce_sets", "k_msm_tblw<16, false>", "k_msm_tblw<8, false>", "k_msm_tblw<4, false>", "k_msm_tblw<2, false>", "k_msm_fix<19, 7>", "k_msm_fix<16, 4>", "k_msm_fix<16, 2>", "k_msm_fix<16, 16>", "k_msm_fix<16, 8>", "k_msm_fix<8, 16>", "k_msm_fix<8, 8>",
-               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_run_gather", "k_run_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor", "k_subarg_scalars", "k_loop_step", "k_smul_quad", "k_subarg_blinders", "k_subarg_prove_setup", "k_gprod_products", "k_gprod_setup", "k_gprod_rdu", "k_gprod_verify_steps", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
+               "k_transcript_step1", "k_msm_tblw_pair", "k_late_fix", "k_late_uniform", "k_late_tables", "k_late_msm", "k_finalize_ranges", "k_table_build", "k_msm_accw", "k_msm_tblw<2, true>", "k_msm_tail", "k_smul", "k_finalize", "k_compress", "k_decompress", "k_tracker_challenge", "k_tracker_relations", "k_shuffle_status", "k_shuffle_gather", "k_shuffle_commit", "k_run_gather", "k_run_commit", "k_gen_table", "k_gen_mul", "k_fix_build", "k_find_scan", "k_find_compare", "k_tracker_check_scalars", "k_tracker_gather", "k_vs_crs_sum_groups", "k_rng_draw", "k_rng_g1_scan", "k_rng_g1_sqrt", "k_rng_g1_select", "k_clear_cofactor", "k_subarg_scalars", "k_loop_step", "k_smul_quad", "k_subarg_blinders", "k_subarg_prove_setup", "k_gprod_products", "k_gprod_setup", "k_gprod_rdu", "k_gprod_verify_steps", "k_same_perm_step", "k_same_perm_verify_step", "k_same_perm_weights", "host_parallel_for", "host_wait_device", "host_prove_wall", "host_verify_wall")
 
     def stats(self):
         return {k: self.stat(k) for k in self.KERNELS}

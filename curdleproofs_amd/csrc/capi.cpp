@@ -721,6 +721,40 @@ int cpx_gprod_verify(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, 
     return (int)CPX_OK;
   });
 }
+int cpx_same_perm_prove(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* A,
+                        const uint8_t* M, const uint8_t* vec_a, const uint32_t* permutation, const uint8_t* vec_a_blinders, const uint8_t* vec_m_blinders,
+                        const uint8_t* rand, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status) {
+  if (count && ell &&
+      (!G || (n_blinders && (!H || !vec_a_blinders || !vec_m_blinders)) || !crs_U || !A || !M || !vec_a || !permutation || !rand || !transcripts || !proofs || !status))
+    return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->same_perm_prove(count, ell, n_blinders, G, H, crs_U, A, M, vec_a, permutation, vec_a_blinders, vec_m_blinders, rand, nullptr, transcripts, proofs, challenges,
+                              status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_same_perm_prove_rng(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* A,
+                            const uint8_t* M, const uint8_t* vec_a, const uint32_t* permutation, const uint8_t* vec_a_blinders, const uint8_t* vec_m_blinders,
+                            uint8_t* states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status) {
+  if (count && ell &&
+      (!G || (n_blinders && (!H || !vec_a_blinders || !vec_m_blinders)) || !crs_U || !A || !M || !vec_a || !permutation || !states || !transcripts || !proofs || !status))
+    return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->same_perm_prove(count, ell, n_blinders, G, H, crs_U, A, M, vec_a, permutation, vec_a_blinders, vec_m_blinders, nullptr, states, transcripts, proofs, challenges,
+                              status);
+    return (int)CPX_OK;
+  });
+}
+int cpx_same_perm_verify(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* crs_G_sum,
+                         const uint8_t* crs_H_sum, const uint8_t* A, const uint8_t* M, const uint8_t* vec_a, const uint8_t* proofs, const uint8_t* rand,
+                         uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
+  if (count && ell && (!G || (n_blinders && !H) || !crs_U || !crs_G_sum || !crs_H_sum || !A || !M || !vec_a || !proofs || !rand || !transcripts || !verdicts))
+    return CPX_ERR_ARG;
+  return guarded(ctx, [&] {
+    ctx->eng->same_perm_verify(count, ell, n_blinders, G, H, crs_U, crs_G_sum, crs_H_sum, A, M, vec_a, proofs, rand, transcripts, challenges, verdicts);
+    return (int)CPX_OK;
+  });
+}
 
 int cpx_set_profiling(cpx_ctx* ctx, int on) {
   if (!ctx || !ctx->eng) return CPX_ERR_ARG;

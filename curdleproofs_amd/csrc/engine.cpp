@@ -1048,10 +1048,23 @@ void Engine::gprod_prove(size_t count, size_t ell, size_t n_blinders, const uint
   const GprodCall gp{ell, n_blinders, G, H, crs_U, B, gprod_result, vec_b, vec_b_blinders};
   subarg_prove(true, count, ell + n_blinders, nullptr, nullptr, nullptr, nullptr, rand, rng_states, transcripts, proofs, challenges, status, &gp);
 }
+// The same-permutation prover (include/cpx.h cpx_same_perm_prove and its _rng form): SamePermutationProof::new
+// (same_permutation_argument.rs:40-99) for `count` independent items, laid out by same_perm_plan.hpp on top of gprod_plan.hpp.  It is
+// gprod_prove above with the same-permutation layer ahead: k_finalize over A | M, k_same_perm_step (same_perm.hip) and the MSM chain over
+// the B tasks, whose sums land where the grand-product layer reads B; its k_finalize adds A.  Nothing returns to the host in between.
+void Engine::same_perm_prove(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* A, const uint8_t* M,
+                             const uint8_t* vec_a, const uint32_t* permutation, const uint8_t* vec_a_blinders, const uint8_t* vec_m_blinders, const uint8_t* rand,
+                             uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status) {
+  const GprodCall gp{ell, n_blinders, G, H, crs_U, nullptr, nullptr, nullptr, nullptr};
+  const SamePermCall sm{A, M, vec_a, permutation, vec_a_blinders, vec_m_blinders};
+  subarg_prove(true, count, ell + n_blinders, nullptr, nullptr, nullptr, nullptr, rand, rng_states, transcripts, proofs, challenges, status, &gp, &sm);
+}
 void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* const vec[2],
-                          const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status, const GprodCall* gp) {
+                          const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status, const GprodCall* gp,
+                          const SamePermCall* sm) {
   if (!count) return;
-  GprodProvePlan gpl;
+  SamePermProvePlan spl;   // (sm: the regions of the same-permutation layer behind those of the grand-product layer, gp: those behind the inner-product prover's)
+  GprodProvePlan& gpl = spl.gp;
   SubargProvePlan& sp = gpl.sp;
   if (gp) {
     switch (gprod_prove_plan(count, gp->ell, gp->nb, gpl)) {
@@ -1085,7 +1098,15 @@ void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const
     for (size_t i = 0; i < count * DT; i++)
       if (!fr_wire_reduced(rand + i * sizeof(Fr))) throw ArgError("a draw of a sub-argument prover is not reduced");
   }
-  if (gp) {
+  if (sm) {
+    const uint8_t* const sc[3] = {sm->vec_a, sm->vec_a_blinders, sm->vec_m_blinders};
+    const size_t each[3] = {ell, nb, nb};
+    for (int v = 0; v < 3; v++)
+      for (size_t i = 0; i < count * each[v]; i++)
+        if (!fr_wire_reduced(sc[v] + i * sizeof(Fr))) throw ArgError("a scalar of cpx_same_perm_prove is not reduced");
+    for (size_t i = 0; i < count * ell; i++)   // the reference indexes vec_a out of bounds (util.rs:78)
+      if (sm->perm[i] >= ell) throw ArgError("cpx_same_perm_prove: a permutation entry >= ell");
+  } else if (gp) {
     const uint8_t* const sc[3] = {gp->result, gp->vec_b, gp->vec_b_blinders};
     const size_t each[3] = {1, ell, nb};
     for (int v = 0; v < 3; v++)
@@ -1102,36 +1123,39 @@ void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const
   for (size_t i = 0; i < count; i++)
     if (!transcript_state_valid(transcripts + i * kTranscriptBytes)) throw ArgError("a transcript state with pos > 165 or pos_begin > 166");
   // host memory the enqueued copies read or write: above the scope
-  std::vector<MsmTask> tasks, btasks, gtasks;
+  std::vector<MsmTask> tasks, btasks, gtasks, mtasks;
   std::vector<SmulTask> stasks;
-  std::vector<uint32_t> idx, lens, blens, glens, addend;
-  std::vector<Fr> hwit, h_fr, h_ab, h_gp;
-  std::vector<uint8_t> h_comp, h_states, h_flags, h_rng;
-  Tier0MsmPlan pl, plb, plg;
+  std::vector<uint32_t> idx, lens, blens, glens, addend, mlens, m_gather, m_addend;
+  std::vector<Fr> hwit, h_fr, h_ab, h_gp, h_sm;
+  std::vector<uint8_t> h_comp, h_states, h_flags, h_rng, h_smB;
+  Tier0MsmPlan pl, plb, plg, plm;
   if (L && !lp.round_msm(pl, lens)) throw ArgError("a round of the loop exceeds the limits of cpx_g1_msm_many");
   if (!sp.first_msm(plb, blens)) throw ArgError("the B points exceed the limits of cpx_g1_msm_many");
   if (gp && !gpl.item_msm(plg, glens)) throw ArgError("the C and D tasks exceed the limits of cpx_g1_msm_many");
+  if (sm && !spl.item_msm(plm, mlens)) throw ArgError("the B tasks exceed the limits of cpx_g1_msm_many");
   CallScope call(this);
   if (L) pl.slices = msm_tblw_slices(opt_, (int)NT, 2, (int)pl.max_n);
   plb.slices = msm_tblw_slices(opt_, (int)plb.count, 2, (int)plb.max_n);
   if (gp) plg.slices = msm_tblw_slices(opt_, (int)plg.count, 2, (int)plg.max_n);
+  if (sm) plm.slices = msm_tblw_slices(opt_, (int)plm.count, 2, (int)plm.max_n);
   DevBuf<Aff>&db = t0_.a0, &daff = t0_.a1;
   DevBuf<Fr>& dfr = t0_.fr;
   DevBuf<Jac>&res = t0_.res, &din = t0_.jin;
   DevBuf<uint8_t>&dby = t0_.bytes, &dflag = t0_.status;
   db.ensure(count * lp.base_stride());
-  dfr.ensure(gp ? gpl.fr_total() : sp.fr_total());
+  dfr.ensure(sm ? spl.fr_total() : gp ? gpl.fr_total() : sp.fr_total());
   res.ensure(std::max<size_t>(std::max(lp.results(), gp ? gpl.res_total() : 0), 1));
-  din.ensure(gp ? gpl.jac_total() : sp.points());
-  daff.ensure(gp ? gpl.aff_total() : sp.aff_total());
-  dby.ensure(gp ? gpl.by_total() : sp.by_total());
+  din.ensure(sm ? spl.jac_total() : gp ? gpl.jac_total() : sp.points());
+  daff.ensure(sm ? spl.aff_total() : gp ? gpl.aff_total() : sp.aff_total());
+  dby.ensure(sm ? spl.by_total() : gp ? gpl.by_total() : sp.by_total());
   dflag.ensure(gp ? gpl.flags_total() : count);
-  t0_.lidx.ensure(std::max<size_t>(gp ? gpl.ix_total() : lp.idx_total(), 1));
+  t0_.lidx.ensure(std::max<size_t>(sm ? spl.ix_total() : gp ? gpl.ix_total() : lp.idx_total(), 1));
   t0_.lstate.ensure(count * kTranscriptWords);
   if (L) msm_chain_reserve(pl);
   msm_chain_reserve(plb);
   if (gp) msm_chain_reserve(plg);
-  t0_.mtask.ensure(gp ? gpl.task_total() : sp.task_total());
+  if (sm) msm_chain_reserve(plm);
+  t0_.mtask.ensure(sm ? spl.task_total() : gp ? gpl.task_total() : sp.task_total());
   if (ipa) t0_.stask.ensure(count);
   // ---- the one upload: bases into the loop's item rows, statement points, witness, z, draws or rng states, lists, tasks, states
   const size_t pitch = lp.base_stride() * sizeof(Aff);
@@ -1144,10 +1168,28 @@ void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const
       if (nb) CPX_HIP(hipMemcpy2DAsync(db.p + lp.family_off(f) + ell, pitch, gp->H, nb * sizeof(Aff), nb * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
     }
     CPX_HIP(hipMemcpy2DAsync(d_stmt, K * sizeof(Jac), gp->crs_U, sizeof(Jac), sizeof(Jac), count, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(din.p + gpl.pt_B(0), gp->B, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_result(), gp->result, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_b(), gp->vec_b, count * ell * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-    if (nb) CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_rb(), gp->vec_b_blinders, count * nb * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+    if (sm) {   // A, M, vec_a, the permutation and the two blinder vectors instead of B, gprod_result, vec_b and vec_b_blinders; the B tasks and their lists
+      CPX_HIP(hipMemcpyAsync(din.p + spl.jac_A(), sm->A, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(din.p + spl.jac_M(), sm->M, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(dfr.p + spl.fr_a(), sm->vec_a, count * ell * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(t0_.lidx.p + spl.ix_perm(), sm->perm, count * ell * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+      if (nb) {
+        CPX_HIP(hipMemcpyAsync(dfr.p + spl.fr_ra(), sm->vec_a_blinders, count * nb * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+        CPX_HIP(hipMemcpyAsync(dfr.p + spl.fr_rm(), sm->vec_m_blinders, count * nb * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+      }
+      spl.fill_lists(m_gather, m_addend);
+      CPX_HIP(hipMemcpyAsync(t0_.lidx.p + spl.ix_gather(), m_gather.data(), m_gather.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(t0_.lidx.p + spl.ix_addend(), m_addend.data(), m_addend.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+      mtasks.resize(count);
+      for (size_t i = 0; i < count; i++)   // B - A = beta sum G + alpha M
+        mtasks[i] = MsmTask{db.p + i * lp.base_stride(), t0_.lidx.p + spl.ix_gather(), dfr.p + spl.fr_bsc() + i * (ell + 1), (uint32_t)(ell + 1), 0, plm.conv_off[i]};
+      CPX_HIP(hipMemcpyAsync(t0_.mtask.p + spl.task_B(), mtasks.data(), mtasks.size() * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
+    } else {
+      CPX_HIP(hipMemcpyAsync(din.p + gpl.pt_B(0), gp->B, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_result(), gp->result, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_b(), gp->vec_b, count * ell * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+      if (nb) CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_rb(), gp->vec_b_blinders, count * nb * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+    }
     if (!rng_states) {   // per item vec_c_blinders | the IPA's draws
       if (nb) CPX_HIP(hipMemcpy2DAsync(dfr.p + gpl.fr_cbl(), nb * sizeof(Fr), rand, DT * sizeof(Fr), nb * sizeof(Fr), count, hipMemcpyHostToDevice, stream_));
       CPX_HIP(hipMemcpy2DAsync(dfr.p + sp.fr_draws(), DE * sizeof(Fr), rand + nb * sizeof(Fr), DT * sizeof(Fr), DE * sizeof(Fr), count, hipMemcpyHostToDevice, stream_));
@@ -1191,9 +1233,20 @@ void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const
   }
   const SubargProveDev sd{sp, dfr.p, dfr.p + lp.fr_vec(), dfr.p + lp.fr_ones(), dfr.p + lp.fr_finals(), dby.p, dflag.p, t0_.lstate.p, gp ? dfr.p + gpl.fr_u() : nullptr};
   const GprodDev gd{gpl, dfr.p, dby.p, dflag.p, t0_.lstate.p};
-  if (gp) {   // the grand-product layer: B's encoding, vec_c, C, steps 1 and 2 with vec_d and inner_prod, D - B
+  if (sm) {   // the same-permutation layer: the encodings of A and M, step 1 with the factors, their product and vec_b_blinders, B - A
+    tick("k_finalize", 0, 2.0 * count);
+    launch_finalize(din.p + spl.jac_A(), (int)(2 * count), daff.p + spl.aff_A(), nullptr, dby.p + spl.by_A(), stream_);
+    tock();
+    CPX_HIP(hipMemcpy2DAsync(db.p + lp.h_index(), pitch, daff.p + spl.aff_M(), sizeof(Aff), sizeof(Aff), count, hipMemcpyDeviceToDevice, stream_));
+    tick("k_same_perm_step", 0, (double)count, true);
+    launch_same_perm_step(SamePermDev{spl, dfr.p, dby.p, t0_.lidx.p + spl.ix_perm(), t0_.lstate.p}, stream_);
+    tock();
+    msm_chain_run(plm, t0_.mtask.p + spl.task_B(), din.p + gpl.pt_B(0));
+  }
+  if (gp) {   // the grand-product layer: B's encoding (same-permutation: A is added first), vec_c, C, steps 1 and 2 with vec_d and inner_prod, D - B
     tick("k_finalize", 0, (double)count);
-    launch_finalize(din.p + gpl.pt_B(0), (int)count, daff.p + sp.aff_points() + gpl.pt_B(0), nullptr, dby.p + gpl.by_B(), stream_);
+    launch_finalize(din.p + gpl.pt_B(0), (int)count, daff.p + sp.aff_points() + gpl.pt_B(0), nullptr, dby.p + gpl.by_B(), stream_,
+                    sm ? t0_.lidx.p + spl.ix_addend() : nullptr);
     tock();
     tick("k_gprod_products", 0, (double)count, true);
     launch_gprod_products(gd, stream_);
@@ -1256,6 +1309,12 @@ void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const
     h_gp.resize(3 * count);   // r_p | alpha, beta, as they sit in the Fr memory
     CPX_HIP(hipMemcpyAsync(h_gp.data(), dfr.p + gpl.fr_rp(), h_gp.size() * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
   }
+  if (sm) {
+    h_sm.resize(2 * count);     // alpha, beta per item
+    h_smB.resize(count * 48);   // B's encodings
+    CPX_HIP(hipMemcpyAsync(h_sm.data(), dfr.p + spl.fr_chal(), h_sm.size() * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
+    CPX_HIP(hipMemcpyAsync(h_smB.data(), dby.p + gpl.by_B(), h_smB.size(), hipMemcpyDeviceToHost, stream_));
+  }
   if (rng_states) {
     h_rng.resize(count * RNG_STATE_BYTES);
     CPX_HIP(hipMemcpyAsync(h_rng.data(), d_rng, h_rng.size(), hipMemcpyDeviceToHost, stream_));
@@ -1264,7 +1323,8 @@ void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const
   if (rng_states) memcpy(rng_states, h_rng.data(), h_rng.size());   // (a refused item's stream has drawn too)
   const Fr* h_gam = h_fr.data();
   const Fr* h_fin = h_fr.data() + count * L;
-  const size_t lead = gp ? gpl.byte_ipa() : 0, nlead = gp ? 2 : 0;   // the grand product's bytes and challenges ahead of the IPA's
+  const size_t slead = sm ? spl.byte_gprod() : 0, snlead = sm ? 2 : 0;   // the same-permutation layer's B and challenges ahead of the grand product's
+  const size_t lead = slead + (gp ? gpl.byte_ipa() : 0), nlead = snlead + (gp ? 2 : 0);   // ... and the grand product's ahead of the IPA's
   for (size_t i = 0; i < count; i++) {
     uint8_t* o = proofs + i * (lead + PB);
     uint8_t* const ch = challenges ? challenges + i * (nlead + NC) * sizeof(Fr) : nullptr;
@@ -1274,10 +1334,14 @@ void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const
       status[i] = CPX_ERR_ARG;
       continue;
     }
+    if (sm) {   // same_permutation_argument.rs:173-177: B, then the GrandProductProof
+      memcpy(o + spl.byte_B(), h_smB.data() + i * 48, 48);
+      if (ch) memcpy(ch, h_sm.data() + 2 * i, 2 * sizeof(Fr));
+    }
     if (gp) {   // grand_product_argument.rs:248-253: C, r_p, then the InnerProductProof
-      memcpy(o + gpl.byte_C(), h_comp.data() + sp.by_points() + sp.pt_statement(i, 1) * 48, 48);
-      host::S(h_gp[i]).to_le_bytes(o + gpl.byte_rp());
-      if (ch) memcpy(ch, h_gp.data() + count + 2 * i, 2 * sizeof(Fr));
+      memcpy(o + slead + gpl.byte_C(), h_comp.data() + sp.by_points() + sp.pt_statement(i, 1) * 48, 48);
+      host::S(h_gp[i]).to_le_bytes(o + slead + gpl.byte_rp());
+      if (ch) memcpy(ch + snlead * sizeof(Fr), h_gp.data() + count + 2 * i, 2 * sizeof(Fr));
       o += lead;
     }
     for (size_t b = 0; b < NF; b++) memcpy(o + sp.point_byte(b), h_comp.data() + sp.by_points() + sp.pt_first(i, b) * 48, 48);
@@ -1324,21 +1388,43 @@ void Engine::gprod_verify(size_t count, size_t ell, size_t n_blinders, const uin
   const GprodCheck gp{ell, n_blinders, G, H, crs_U, crs_G_sum, crs_H_sum, B, gprod_result};
   subarg_verify(true, count, ell + n_blinders, nullptr, nullptr, nullptr, nullptr, proofs, rand, transcripts, challenges, verdicts, &gp);
 }
-void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* vec_u,
-                           const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts, const GprodCheck* gp) {
+// The same-permutation verifier (include/cpx.h cpx_same_perm_verify): SamePermutationProof::verify (same_permutation_argument.rs:112-171) for
+// `count` independent items.  It is gprod_verify above with B taken from the proof (k_decompress, with a verdict), k_finalize over A | M into
+// three further slots of every row, k_same_perm_verify_step ahead of k_gprod_verify_steps and k_same_perm_weights behind k_subarg_scalars
+// (same_perm.hip): the relation of :149 joins the item's one MSM with the first of the item's three factors.
+void Engine::same_perm_verify(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* crs_G_sum,
+                              const uint8_t* crs_H_sum, const uint8_t* A, const uint8_t* M, const uint8_t* vec_a, const uint8_t* proofs, const uint8_t* rand,
+                              uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
   if (!count) return;
-  GprodCheckPlan gpl;   // (gp: the regions of the grand-product steps behind those of the inner-product check)
+  if (!ell) throw ArgError("cpx_same_perm_verify: ell = 0 (the reference's prover cannot make such a proof: its ell - 1 underflows)");
+  if (ell + n_blinders < ell) throw ArgError("cpx_same_perm_verify: ell + n_blinders overflows");
+  const GprodCheck gp{ell, n_blinders, G, H, crs_U, crs_G_sum, crs_H_sum, nullptr, nullptr};
+  const SamePermCheck sm{A, M, vec_a};
+  subarg_verify(true, count, ell + n_blinders, nullptr, nullptr, nullptr, nullptr, proofs, rand, transcripts, challenges, verdicts, &gp, &sm);
+}
+void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* vec_u,
+                           const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts, const GprodCheck* gp,
+                           const SamePermCheck* sm) {
+  if (!count) return;
+  SamePermCheckPlan spl;   // (sm: the regions of the same-permutation steps behind those of the grand-product steps and the three further points of every row)
+  GprodCheckPlan& gpl = spl.gp;   // (gp: the regions of the grand-product steps behind those of the inner-product check)
   SubargCheckPlan& sp = gpl.sp;
-  switch (gp ? gprod_check_plan(count, gp->ell, gp->nb, gpl) : subarg_check_plan(ipa, count, n, sp)) {
+  switch (sm   ? same_perm_check_plan(count, gp->ell, gp->nb, spl)
+          : gp ? gprod_check_plan(count, gp->ell, gp->nb, gpl)
+               : subarg_check_plan(ipa, count, n, sp)) {
     case SUBARG_NOT_POW2: throw std::invalid_argument("the sub-argument verifiers take n = 2^L elements per item, L >= 0");
     case SUBARG_TOO_LARGE: throw ArgError(ipa ? "cpx_ipa_verify: at most 65536 items and count (n + 4 L + 5) <= 2^24 points"
                                               : "cpx_same_msm_verify: at most 65536 items and count (3 n + 6 L + 6) <= 2^24 points");
     default: break;
   }
   const size_t NP = sp.points(), PP = sp.proof_points(), PB = sp.proof_bytes(), NC = sp.challenges(), K = SubargCheckPlan::kStatement;
-  for (size_t i = 0; i < count * (size_t)sp.checks(); i++)
+  const size_t NR = sm ? (size_t)spl.checks() : (size_t)sp.checks();   // the caller's factors per item: the same-permutation check's ahead of the IPA's two
+  for (size_t i = 0; i < count * NR; i++)
     if (!host::is_valid_factor(rand + 32 * i)) throw ArgError("the random factors of a sub-argument check must be non-zero reduced field elements");
-  if (gp) {
+  if (sm) {
+    for (size_t i = 0; i < count * gp->ell; i++)
+      if (!fr_wire_reduced(sm->vec_a + i * sizeof(Fr))) throw ArgError("a scalar of vec_a of cpx_same_perm_verify is not reduced");
+  } else if (gp) {
     for (size_t i = 0; i < count; i++)
       if (!fr_wire_reduced(gp->result + i * sizeof(Fr))) throw ArgError("a scalar gprod_result of cpx_gprod_verify is not reduced");
   } else if (ipa) {
@@ -1357,14 +1443,18 @@ void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* cons
   std::vector<Fr> h_chal, h_gchal;
   std::vector<Jac> h_res;
   std::vector<SmulTask> stasks;
-  std::vector<uint32_t> gix;
-  std::vector<uint8_t> h_gbad;
+  std::vector<uint32_t> gix, six;
+  std::vector<uint8_t> h_gbad, h_sbad;
+  std::vector<Fr> h_schal;
   Tier0MsmPlan pl;
   if (!sp.msm(pl, lens)) throw ArgError("the items exceed the limits of cpx_g1_msm_many");
   // the grand product's proof is C, r_p, then the InnerProductProof's bytes (grand_product_argument.rs:248-253)
-  const size_t lead = gp ? GprodCheckPlan::kHead : 0, PBT = lead + PB, ell = gp ? gp->ell : 0, nb = gp ? gp->nb : 0;
+  // ... and the same-permutation proof is B, then the grand product's (same_permutation_argument.rs:173-177)
+  const size_t slead = sm ? SamePermCheckPlan::kHead : 0, glead = gp ? GprodCheckPlan::kHead : 0, lead = slead + glead, PBT = lead + PB, ell = gp ? gp->ell : 0,
+               nb = gp ? gp->nb : 0;
   for (size_t s = 0; s < PP; s++) point_bytes[s] = lead + sp.point_byte(s);
-  if (gp) point_bytes.push_back(0);
+  if (gp) point_bytes.push_back(slead);
+  if (sm) point_bytes.push_back(0);
   proofs = canonical_infinities(proofs, count * PBT, count, PBT, point_bytes, canon);
   CallScope call(this);
   pl.slices = msm_tblw_slices(opt_, (int)count, 2, (int)pl.max_n);
@@ -1373,12 +1463,12 @@ void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* cons
   DevBuf<uint8_t>&db = t0_.bytes, &dst = t0_.status;   // dst: the decoder's verdicts [count][PP] | the items' flags [count]
   DevBuf<Jac>&din = t0_.jin, &res = t0_.res;
   rows.ensure(count * NP);
-  dfr.ensure(gp ? gpl.fr_total() : sp.fr_total());
-  db.ensure(gp ? gpl.by_total() : sp.by_total());
-  dst.ensure(gp ? gpl.st_total() : count * PP + count);
-  din.ensure(count * K);
+  dfr.ensure(sm ? spl.fr_total() : gp ? gpl.fr_total() : sp.fr_total());
+  db.ensure(sm ? spl.by_total() : gp ? gpl.by_total() : sp.by_total());
+  dst.ensure(sm ? spl.st_total() : gp ? gpl.st_total() : count * PP + count);
+  din.ensure(sm ? spl.jac_total() : count * K);
   res.ensure(count);
-  t0_.lidx.ensure(gp ? gpl.ix_total() : sp.ix_total());
+  t0_.lidx.ensure(sm ? spl.ix_total() : gp ? gpl.ix_total() : sp.ix_total());
   t0_.lstate.ensure(count * kTranscriptWords);
   if (gp) {
     t0_.a1.ensure(gpl.aff_total());
@@ -1391,12 +1481,22 @@ void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* cons
     CPX_HIP(hipMemcpy2DAsync(rows.p, NP * sizeof(Aff), gp->G, ell * sizeof(Aff), ell * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
     if (nb) CPX_HIP(hipMemcpy2DAsync(rows.p + ell, NP * sizeof(Aff), gp->H, nb * sizeof(Aff), nb * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(din.p, gp->crs_U, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(din.p + count, gp->B, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
+    if (sm) {   // B is the proof's first point, gprod_result is made on the device; A | M, vec_a, the first factor of every item, the row slots of A and M
+      CPX_HIP(hipMemcpy2DAsync(db.p + gpl.by_B(), 48, proofs, PBT, 48, count, hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(din.p + spl.jac_A(), sm->A, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(din.p + spl.jac_A() + count, sm->M, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(dfr.p + spl.fr_a(), sm->vec_a, count * ell * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpy2DAsync(dfr.p + spl.fr_a0(), sizeof(Fr), rand, NR * sizeof(Fr), sizeof(Fr), count, hipMemcpyHostToDevice, stream_));
+      spl.fill_idx(six);
+      CPX_HIP(hipMemcpyAsync(t0_.lidx.p + spl.ix_AM_dst(), six.data(), six.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    } else {
+      CPX_HIP(hipMemcpyAsync(din.p + count, gp->B, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
+      CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_result(), gp->result, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+    }
     CPX_HIP(hipMemcpyAsync(g_aff + gpl.aff_g_sum(), gp->g_sum, count * sizeof(Aff), hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(g_aff + gpl.aff_h_sum(), gp->h_sum, count * sizeof(Aff), hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpy2DAsync(db.p + sp.by_proofs(), PB, proofs + lead, PBT, PB, count, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpy2DAsync(db.p + gpl.by_heads(), lead, proofs, PBT, lead, count, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_result(), gp->result, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+    CPX_HIP(hipMemcpy2DAsync(db.p + gpl.by_heads(), glead, proofs + slead, PBT, glead, count, hipMemcpyHostToDevice, stream_));
     gpl.fill_idx(gix);
     CPX_HIP(hipMemcpyAsync(t0_.lidx.p + gpl.ix_C_src(), gix.data(), gix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
   } else {
@@ -1410,7 +1510,9 @@ void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* cons
     CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_z(), z, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
     CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_u(), vec_u, count * n * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   }
-  CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_rand(), rand, count * (size_t)sp.checks() * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  if (sm) CPX_HIP(hipMemcpy2DAsync(dfr.p + sp.fr_rand(), (size_t)sp.checks() * sizeof(Fr), rand + sizeof(Fr), NR * sizeof(Fr), (size_t)sp.checks() * sizeof(Fr), count,
+                                   hipMemcpyHostToDevice, stream_));
+  else CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_rand(), rand, count * (size_t)sp.checks() * sizeof(Fr), hipMemcpyHostToDevice, stream_));
   sp.fill_idx(ix);
   CPX_HIP(hipMemcpyAsync(t0_.lidx.p, ix.data(), ix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
   CPX_HIP(hipMemcpyAsync(t0_.lstate.p, transcripts, count * kTranscriptBytes, hipMemcpyHostToDevice, stream_));
@@ -1427,8 +1529,21 @@ void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* cons
     tock();
     tick("k_finalize", 0, 2.0 * count);
     launch_finalize(din.p, (int)count, rows.p, ix + gpl.ix_U_dst(), nullptr, stream_);                          // crs_U into the rows
-    launch_finalize(din.p + count, (int)count, g_aff + gpl.aff_B(), nullptr, db.p + gpl.by_B(), stream_);       // B: affine and encoding
+    if (!sm) launch_finalize(din.p + count, (int)count, g_aff + gpl.aff_B(), nullptr, db.p + gpl.by_B(), stream_);   // B: affine and encoding
     tock();
+    const SamePermVerifyDev smd{spl, dfr.p, db.p, t0_.lstate.p};
+    if (sm) {   // B from its encoding, with a verdict; A | M into the rows behind the statement slots, their encodings for step 1; the step
+      tick("k_decompress", 0, (double)count);
+      launch_decompress(opt_, db.p + gpl.by_B(), (int)count, g_aff + gpl.aff_B(), nullptr, dst.p + spl.st_B(), 1, stream_);
+      tock();
+      tick("k_finalize", 0, 2.0 * count);
+      launch_finalize(din.p + spl.jac_A(), (int)(2 * count), rows.p, ix + spl.ix_AM_dst(), db.p + spl.by_A(), stream_);
+      tock();
+      CPX_HIP(hipMemcpy2DAsync(rows.p + spl.row_B(), NP * sizeof(Aff), g_aff + gpl.aff_B(), sizeof(Aff), sizeof(Aff), count, hipMemcpyDeviceToDevice, stream_));
+      tick("k_same_perm_verify_step", 0, (double)count, true);
+      launch_same_perm_verify_step(smd, stream_);
+      tock();
+    }
     tick("k_gprod_verify_steps", 0, (double)count, true);
     launch_gprod_verify_steps(GprodVerifyDev{gpl, dfr.p, db.p, dst.p, t0_.lstate.p}, stream_);
     tock();
@@ -1442,7 +1557,7 @@ void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* cons
     launch_compress(g_aff + gpl.aff_D(), (int)count, (int)count, 1, g_denc, stream_);
     tock();
     uint8_t* const d_stmt_enc = db.p + sp.by_statement();   // [count][3][48]: (crs_U: not hashed) | C | D
-    CPX_HIP(hipMemcpy2DAsync(d_stmt_enc + 48, K * 48, g_heads, lead, 48, count, hipMemcpyDeviceToDevice, stream_));
+    CPX_HIP(hipMemcpy2DAsync(d_stmt_enc + 48, K * 48, g_heads, glead, 48, count, hipMemcpyDeviceToDevice, stream_));
     CPX_HIP(hipMemcpy2DAsync(d_stmt_enc + 96, K * 48, g_denc, 48, 48, count, hipMemcpyDeviceToDevice, stream_));
     CPX_HIP(hipMemcpy2DAsync(rows.p + sp.statement_off() + 2, NP * sizeof(Aff), g_aff + gpl.aff_D(), sizeof(Aff), sizeof(Aff), count, hipMemcpyDeviceToDevice, stream_));
   } else {
@@ -1462,6 +1577,11 @@ void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* cons
   tick("k_subarg_scalars", 0, (double)count, true);
   launch_subarg_scalars(SubargDev{sp, dfr.p, db.p, dst.p, d_bad, t0_.lstate.p}, stream_);
   tock();
+  if (sm) {   // same_permutation_argument.rs:149 joins the item's one MSM
+    tick("k_same_perm_weights", 0, (double)count, true);
+    launch_same_perm_weights(SamePermVerifyDev{spl, dfr.p, db.p, t0_.lstate.p}, stream_);
+    tock();
+  }
   msm_chain(pl, lens.data(), rows.p, dfr.p + sp.fr_weights(), res.p, tasks);
   // ---- the one download, into host memory of the call: the caller's buffers are written once everything has arrived
   h_res.resize(count);
@@ -1478,16 +1598,24 @@ void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* cons
     CPX_HIP(hipMemcpyAsync(h_gbad.data(), dst.p + gpl.st_bad(), count, hipMemcpyDeviceToHost, stream_));
     CPX_HIP(hipMemcpyAsync(h_gchal.data(), dfr.p + gpl.fr_chal(), 2 * count * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
   }
+  if (sm) {
+    h_sbad.resize(count);
+    h_schal.resize(2 * count);
+    CPX_HIP(hipMemcpyAsync(h_sbad.data(), dst.p + spl.st_B(), count, hipMemcpyDeviceToHost, stream_));
+    CPX_HIP(hipMemcpyAsync(h_schal.data(), dfr.p + spl.fr_chal(), 2 * count * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
+  }
   call.finish();
   if (gp) {   // an item that does not deserialise keeps the state it came with (the device had advanced it by steps 1 and 2) and gets zero challenges
+    const size_t sn = sm ? 2 : 0;   // the same-permutation challenges ahead of the grand product's
     for (size_t i = 0; i < count; i++) {
-      const bool bad = h_bad[i] || h_gbad[i];
-      uint8_t* const ch = challenges ? challenges + i * (2 + NC) * sizeof(Fr) : nullptr;
+      const bool bad = h_bad[i] || h_gbad[i] || (sm && h_sbad[i]);
+      uint8_t* const ch = challenges ? challenges + i * (sn + 2 + NC) * sizeof(Fr) : nullptr;
       if (!bad) memcpy(transcripts + i * kTranscriptBytes, h_states.data() + i * kTranscriptBytes, kTranscriptBytes);
-      if (ch && bad) memset(ch, 0, (2 + NC) * sizeof(Fr));
+      if (ch && bad) memset(ch, 0, (sn + 2 + NC) * sizeof(Fr));
       if (ch && !bad) {
-        memcpy(ch, h_gchal.data() + 2 * i, 2 * sizeof(Fr));
-        memcpy(ch + 2 * sizeof(Fr), h_chal.data() + i * NC, NC * sizeof(Fr));
+        if (sm) memcpy(ch, h_schal.data() + 2 * i, 2 * sizeof(Fr));
+        memcpy(ch + sn * sizeof(Fr), h_gchal.data() + 2 * i, 2 * sizeof(Fr));
+        memcpy(ch + (sn + 2) * sizeof(Fr), h_chal.data() + i * NC, NC * sizeof(Fr));
       }
       verdicts[i] = bad ? CPX_ERR_DESERIALIZE : h_res[i].is_identity() ? CPX_OK : CPX_ERR_VERIFY;
     }

@@ -209,6 +209,14 @@ class Engine {
   void gprod_verify(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* crs_G_sum,
                     const uint8_t* crs_H_sum, const uint8_t* B, const uint8_t* gprod_result, const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts,
                     uint8_t* challenges, int* verdicts);                                                                                     // grand_product_argument.rs:180-246
+  // the same-permutation prover and verifier on the caller's bases likewise (same_perm_plan.hpp, same_perm.hip; include/cpx.h
+  // cpx_same_perm_prove, its _rng form and cpx_same_perm_verify): the layer above the grand-product one, which draws nothing
+  void same_perm_prove(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* A, const uint8_t* M,
+                       const uint8_t* vec_a, const uint32_t* permutation, const uint8_t* vec_a_blinders, const uint8_t* vec_m_blinders, const uint8_t* rand,
+                       uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status);                        // same_permutation_argument.rs:40-99
+  void same_perm_verify(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* crs_G_sum,
+                        const uint8_t* crs_H_sum, const uint8_t* A, const uint8_t* M, const uint8_t* vec_a, const uint8_t* proofs, const uint8_t* rand,
+                        uint8_t* transcripts, uint8_t* challenges, int* verdicts);                                                           // same_permutation_argument.rs:112-171
   void normalize(const uint8_t* jac, size_t n, uint8_t* out_aff, uint8_t* out_comp);                   // normalize_batch (+compress)
   int decompress(const uint8_t* comp, size_t n, uint8_t* out_aff, int check_subgroup, uint8_t* status_out = nullptr);   // whisk.rs:318-320
 
@@ -530,16 +538,28 @@ class Engine {
     size_t ell, nb;
     const uint8_t *G, *H, *crs_U, *B, *result, *vec_b, *vec_b_blinders;
   };
+  // ... and, with gp and sm, of same_perm_prove: gp's B, result, vec_b and vec_b_blinders are null, the same-permutation layer makes them on the device
+  struct SamePermCall {
+    const uint8_t *A, *M, *vec_a;
+    const uint32_t* perm;
+    const uint8_t *vec_a_blinders, *vec_m_blinders;
+  };
   void subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* const vec[2],
-                    const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status, const GprodCall* gp = nullptr);
+                    const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status, const GprodCall* gp = nullptr,
+                    const SamePermCall* sm = nullptr);
   // the one body of ipa_verify / same_msm_verify (engine.cpp).  fam: G resp. G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u
   // ... and, with gp, of gprod_verify: the inner-product check behind the grand-product steps, whose inputs stand in gp (fam, stmt, z, vec_u: null)
   struct GprodCheck {
     size_t ell, nb;
     const uint8_t *G, *H, *crs_U, *g_sum, *h_sum, *B, *result;
   };
+  // ... and, with gp and sm, of same_perm_verify: gp's B and result are null (B is the proof's first point, the result is made on the device)
+  struct SamePermCheck {
+    const uint8_t *A, *M, *vec_a;
+  };
   void subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* vec_u,
-                     const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts, const GprodCheck* gp = nullptr);
+                     const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts, const GprodCheck* gp = nullptr,
+                     const SamePermCheck* sm = nullptr);
   // n trackers -> the planes r_G | k_r_G: upload + k_decompress of the tracker prover, find-trackers and the candidate list (whisk.cpp)
   void decode_tracker_planes(size_t n, const uint8_t* trackers, std::vector<uint8_t>& canon, std::vector<uint32_t>& off, uint8_t* d_bytes, uint32_t* d_off, Aff* d_pts,
                              uint8_t* d_status);

@@ -7,6 +7,7 @@
 #include "subarg_check_plan.hpp"
 #include "subarg_prove_plan.hpp"
 #include "gprod_plan.hpp"
+#include "same_perm_plan.hpp"
 
 namespace cpx {
 
@@ -302,6 +303,29 @@ void launch_gprod_verify_steps(const GprodVerifyDev& d, hipStream_t s);
 void launch_gprod_products(const GprodDev& d, hipStream_t s);
 void launch_gprod_setup(const GprodDev& d, hipStream_t s);
 void launch_gprod_rdu(const GprodDev& d, hipStream_t s);
+// The same-permutation layer of cpx_same_perm_prove ahead of the grand-product layer for pl.count() items (same_perm.hip; every layout:
+// same_perm_plan.hpp).  launch_same_perm_step: step 1 on the item's transcript state from the encodings of A and M and the scalars of vec_a,
+// alpha, beta, then the factors, their product and vec_b_blinders where the grand-product layer reads vec_b, gprod_result and
+// vec_b_blinders, and the scalars of the B task.  perm: every entry < ell (the engine has looked)
+struct SamePermDev {
+  SamePermProvePlan pl;
+  Fr* fr;                  // the grand-product prover's Fr memory | the regions of same_perm_plan.hpp
+  const uint8_t* bytes;    // the grand-product prover's bytes | A and M encodings
+  const uint32_t* perm;    // [count][ell]
+  uint64_t* states;        // [count][27]
+};
+// The steps of cpx_same_perm_verify around those of cpx_gprod_verify.  launch_same_perm_verify_step (ahead of k_gprod_verify_steps): step 1,
+// alpha, beta and gprod_result.  launch_same_perm_weights (behind k_subarg_scalars): the relation of same_permutation_argument.rs:149 with
+// the item's first factor into the row of weights
+struct SamePermVerifyDev {
+  SamePermCheckPlan pl;
+  Fr* fr;
+  const uint8_t* bytes;
+  uint64_t* states;        // [count][27]
+};
+void launch_same_perm_step(const SamePermDev& d, hipStream_t s);
+void launch_same_perm_verify_step(const SamePermVerifyDev& d, hipStream_t s);
+void launch_same_perm_weights(const SamePermVerifyDev& d, hipStream_t s);
 // transcript prefix of every proof: absorbs the compressed instance ([nproofs][4*ell*48] + [nproofs][48] for M), draws vec_a;
 // d_state: [nproofs][27] u64 (25 STROBE lanes, pos, pos_begin), d_vec_a: [nproofs][ell] Fr
 // lane_per_proof: one lane instead of 32 per transcript (large batches: a fifth of the wave instructions, a longer chain)

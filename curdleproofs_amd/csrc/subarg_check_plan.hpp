@@ -33,6 +33,7 @@ enum SubargPlanStatus { SUBARG_OK = 0, SUBARG_NOT_POW2 = 1, SUBARG_TOO_LARGE = 2
 struct SubargCheckPlan {
   bool ipa = true;
   size_t count = 0, n = 0, L = 0;
+  size_t extra = 0;   // further points behind the statement slots, weighted by the caller's own kernel (same_perm_plan.hpp); 0 for every other check
 
   // ---- what an item consists of ----
   CPX_HD int checks() const { return ipa ? 2 : 3; }                     // accumulate_check calls = random factors per item
@@ -57,7 +58,7 @@ struct SubargCheckPlan {
   CPX_HD size_t base_off(int f) const { return (size_t)f * n; }
   CPX_HD size_t proof_off() const { return (size_t)families() * n; }
   CPX_HD size_t statement_off() const { return proof_off() + proof_points(); }
-  CPX_HD size_t points() const { return statement_off() + kStatement; }
+  CPX_HD size_t points() const { return statement_off() + kStatement + extra; }
   // ---- Fr memory of the call: weights [count][points] | z [count] | vec_u [count][n] (IPA) | factors [count][checks] | challenges ----
   CPX_HD size_t fr_weights() const { return 0; }
   CPX_HD size_t fr_z() const { return count * points(); }
@@ -95,9 +96,10 @@ struct SubargCheckPlan {
 
 // An item is one task of one cpx_g1_msm_many: at most kTier0ManyTasks items of together count * points() <= kTier0ManyPoints points (which
 // also keeps every byte offset of the call below 2^32).  Looked at before anything is read.
-inline SubargPlanStatus subarg_check_plan(bool ipa, size_t count, size_t n, SubargCheckPlan& pl) {
+inline SubargPlanStatus subarg_check_plan(bool ipa, size_t count, size_t n, SubargCheckPlan& pl, size_t extra = 0) {
   if (!n || (n & (n - 1))) return SUBARG_NOT_POW2;
   pl.ipa = ipa;
+  pl.extra = extra;
   pl.count = count;
   pl.n = n;
   pl.L = 0;

@@ -306,6 +306,59 @@ int cpx_gprod_verify(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, 
                      const uint8_t* crs_U /* count*144 */, const uint8_t* crs_G_sum, const uint8_t* crs_H_sum /* count*96 each */, const uint8_t* B /* count*144 */,
                      const uint8_t* gprod_result /* count*32 */, const uint8_t* proofs /* count*(48*(3+4L)+96) */, const uint8_t* rand /* count*2*32 */,
                      uint8_t* transcripts /* count*216, in/out */, uint8_t* challenges /* count*(4+L)*32, may be NULL */, int* verdicts /* count */);
+/* SamePermutationProof::new (same_permutation_argument.rs:40-99) for `count` independent stand-alone statements of ell elements and
+ * n_blinders blinders each, n = ell + n_blinders = 2^L, the whole function in ONE call: step 1 of the transcript (A, M under
+ * "same_perm_step1", then vec_a as ONE message under the same label — its u64 little-endian length, then the canonical scalars, 8 + 32 ell
+ * bytes —, alpha under "same_perm_alpha", beta under "same_perm_beta", :60-63), the permuted factors a_sigma(i) + sigma(i) alpha + beta and
+ * their product (:66-73), B = A + alpha M + beta sum G (:76) — formed literally for arbitrary A and M: one multi-scalar multiplication over
+ * G and M, to which A is added —, vec_b_blinders = vec_a_blinders + alpha vec_m_blinders (:78-81), and then everything cpx_gprod_prove does
+ * (:83-93) on B, the product, the factors and vec_b_blinders, which stay in device memory.
+ *   G, H         the bases (`crs_G_vec`, ell per item; `crs_H_vec`, n_blinders per item), affine
+ *   crs_U, A, M  144-byte Jacobian points, any representative, Z = 0 for the identity
+ *   vec_a, vec_a_blinders, vec_m_blinders   the statement's scalars and the witness's blinders
+ *   permutation  ell u32 values per item.  An entry >= ell is CPX_ERR_ARG for the call (the reference indexes out of bounds, util.rs:78),
+ *                found before anything is uploaded or written.  Repeated entries are legal, as in the reference, which does not check
+ *                bijectivity: such an item gets the reference's bytes, and the proof does not verify.
+ *   rand         the draws of cpx_gprod_prove, in its order: this layer draws nothing
+ *   transcripts  in: the states before `new`; out: advanced by the whole `new`
+ *   proofs       the reference's `serialize` (:173-177): B compressed, then the grand-product proof bytes exactly as cpx_gprod_prove writes them
+ *   challenges   per item same-perm alpha, beta, then the 4 + L of cpx_gprod_prove (Montgomery limbs); may be NULL
+ *   status       as cpx_gprod_prove: CPX_OK, or CPX_ERR_ARG where the reference panics; such an item's proof bytes and challenges are zero
+ *                and its transcript state is unchanged
+ * Conventions of cpx_gprod_prove: a scalar >= r anywhere is CPX_ERR_ARG for the call; the identity is a legal base and a legal A or M;
+ * count = 0 is a no-op; ell = 0 and n = 1 are CPX_ERR_ARG, n not a power of two is CPX_ERR_NOT_POW2; n_blinders = 0 is legal, H and the two
+ * blinder vectors may then be NULL; the limits are those of cpx_gprod_prove, checked before anything is read; on any return other than
+ * CPX_OK nothing is written, states included.  There is no further cap on ell: vec_a is converted and absorbed in pieces of 128 scalars
+ * (curdleproofs_amd/csrc/same_perm_plan.hpp, same_perm.hip).  One upload, one download, ONE stream synchronisation; launches that depend on
+ * L only; no CRS is needed and the loaded batch is untouched.  The _rng form draws cpx_gprod_prove_rng's stream; a refused item's stream has
+ * drawn too.  Measurements: profiles/same_perm.md. */
+int cpx_same_perm_prove(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, const uint8_t* G /* count*ell*96 */, const uint8_t* H /* count*n_blinders*96 */,
+                        const uint8_t* crs_U, const uint8_t* A, const uint8_t* M /* count*144 each */, const uint8_t* vec_a /* count*ell*32 */,
+                        const uint32_t* permutation /* count*ell */, const uint8_t* vec_a_blinders, const uint8_t* vec_m_blinders /* count*n_blinders*32 each */,
+                        const uint8_t* rand /* count*(n_blinders+2n-2)*32 */, uint8_t* transcripts /* count*216, in/out */,
+                        uint8_t* proofs /* count*(48*(4+4L)+96) */, uint8_t* challenges /* count*(6+L)*32, may be NULL */, int* status /* count */);
+int cpx_same_perm_prove_rng(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* A,
+                            const uint8_t* M, const uint8_t* vec_a, const uint32_t* permutation, const uint8_t* vec_a_blinders, const uint8_t* vec_m_blinders,
+                            uint8_t* states /* count*40, in/out */, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status);
+/* SamePermutationProof::verify (same_permutation_argument.rs:112-171) for `count` independent stand-alone proofs given as the bytes
+ * cpx_same_perm_prove writes (:173-177), each against an MsmAccumulator of its own with the caller's THREE draws, in draw order: the factor
+ * of the same-permutation check (:149), then the two of the inner-product check.  In ONE call: step 1 as in the prover (:134-137),
+ * gprod_result = prod (a_i + i alpha + beta) (:140-145), the relation beta <1, G> - (B - A - alpha M) == O (:149), which joins the item's
+ * single multi-scalar multiplication — a_0 beta more on the weights of G_0..G_{ell-1}, and B, A, M behind the statement points of the item's
+ * row with the weights -a_0, +a_0, +a_0 alpha —, and then everything cpx_gprod_verify does on the proof's B and gprod_result.
+ *   crs_G_sum, crs_H_sum   the caller's, as in cpx_gprod_verify: a wrong sum gives CPX_ERR_VERIFY
+ *   rand         three non-zero reduced factors per item         challenges   as cpx_same_perm_prove returns them; may be NULL
+ *   verdicts     per item CPX_OK, CPX_ERR_VERIFY, or CPX_ERR_DESERIALIZE where B, C or a point of the inner-product proof does not decode
+ *                or lies outside the subgroup, or a proof scalar is >= r: that item's state is unchanged and its challenges are zero.  A
+ *                proof that deserialises advances its state by the whole `verify`, whatever the verdict.
+ * Conventions of cpx_gprod_verify: count = 0 is a no-op; ell = 0 is CPX_ERR_ARG; n = 1 (ell = 1, n_blinders = 0) is a real check; n not a
+ * power of two is CPX_ERR_NOT_POW2; a scalar of vec_a >= r is CPX_ERR_ARG; the limits are those of cpx_ipa_verify on n elements with three
+ * more points per item; nothing is written on any return other than CPX_OK.  Launches that do not depend on count. */
+int cpx_same_perm_verify(cpx_ctx* ctx, size_t count, size_t ell, size_t n_blinders, const uint8_t* G /* count*ell*96 */, const uint8_t* H /* count*n_blinders*96 */,
+                         const uint8_t* crs_U /* count*144 */, const uint8_t* crs_G_sum, const uint8_t* crs_H_sum /* count*96 each */, const uint8_t* A,
+                         const uint8_t* M /* count*144 each */, const uint8_t* vec_a /* count*ell*32 */, const uint8_t* proofs /* count*(48*(4+4L)+96) */,
+                         const uint8_t* rand /* count*3*32 */, uint8_t* transcripts /* count*216, in/out */, uint8_t* challenges /* count*(6+L)*32, may be NULL */,
+                         int* verdicts /* count */);
 /* ark_ec `CurveGroup::normalize_batch` (+ optional `serialize_compressed`); either output may be NULL */
 int cpx_g1_normalize(cpx_ctx* ctx, const uint8_t* jac /* n*144 */, size_t n, uint8_t* out_affine /* n*96 */, uint8_t* out_compressed /* n*48 */);
 /* whisk.rs:318-320 `from_bytes_g1affine` = deserialize_compressed with on-curve + subgroup validation */

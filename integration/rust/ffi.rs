@@ -94,6 +94,18 @@ extern "C" {
     pub fn cpx_gprod_verify(ctx: *mut cpx_ctx, count: usize, ell: usize, n_blinders: usize, g: *const u8, h: *const u8, crs_u: *const u8, crs_g_sum: *const u8,
                             crs_h_sum: *const u8, b: *const u8, gprod_result: *const u8, proofs: *const u8, rand: *const u8, transcripts: *mut u8,
                             challenges: *mut u8, verdicts: *mut c_int) -> c_int;
+    // the same-permutation prover on the caller's bases (same_permutation_argument.rs:40-99), `count` stand-alone statements per call: B and
+    // the GrandProductProof bytes out; permutation: ell u32 values below ell per item; rand = the draws of cpx_gprod_prove
+    pub fn cpx_same_perm_prove(ctx: *mut cpx_ctx, count: usize, ell: usize, n_blinders: usize, g: *const u8, h: *const u8, crs_u: *const u8, a: *const u8,
+                               m: *const u8, vec_a: *const u8, permutation: *const u32, vec_a_blinders: *const u8, vec_m_blinders: *const u8, rand: *const u8,
+                               transcripts: *mut u8, proofs: *mut u8, challenges: *mut u8, status: *mut c_int) -> c_int;
+    pub fn cpx_same_perm_prove_rng(ctx: *mut cpx_ctx, count: usize, ell: usize, n_blinders: usize, g: *const u8, h: *const u8, crs_u: *const u8, a: *const u8,
+                                   m: *const u8, vec_a: *const u8, permutation: *const u32, vec_a_blinders: *const u8, vec_m_blinders: *const u8, states: *mut u8,
+                                   transcripts: *mut u8, proofs: *mut u8, challenges: *mut u8, status: *mut c_int) -> c_int;
+    // SamePermutationProof::verify on those bytes (same_permutation_argument.rs:112-171): three factors per item in rand
+    pub fn cpx_same_perm_verify(ctx: *mut cpx_ctx, count: usize, ell: usize, n_blinders: usize, g: *const u8, h: *const u8, crs_u: *const u8, crs_g_sum: *const u8,
+                                crs_h_sum: *const u8, a: *const u8, m: *const u8, vec_a: *const u8, proofs: *const u8, rand: *const u8, transcripts: *mut u8,
+                                challenges: *mut u8, verdicts: *mut c_int) -> c_int;
     pub fn cpx_g1_normalize(ctx: *mut cpx_ctx, jac: *const u8, n: usize, out_affine: *mut u8, out_compressed: *mut u8) -> c_int;
     pub fn cpx_g1_decompress(ctx: *mut cpx_ctx, compressed: *const u8, n: usize, out_affine: *mut u8, check_subgroup: c_int) -> c_int;
     // one verdict per point (0 ok, 1 malformed / not on the curve, 2 outside the subgroup): the square root behind tests/crs.rs:13-52
