@@ -875,756 +875,6 @@ void Engine::msm_chain_run(const Tier0MsmPlan& pl, const MsmTask* d_tasks, Jac* 
   launch_msm_tail(opt_, t0_.part.p, nullptr, d_res, (int)count, 16, 8, stream_, nullptr, 0, pl.tail_dup());
   tock();
 }
-// The log-round loops as one call each (include/cpx.h cpx_ipa_rounds, cpx_same_msm_rounds): inner_product_argument.rs:150-186 /
-// same_multiscalar_argument.rs:99-136 for `count` independent items in the all-MSM form, laid out by loop_plan.hpp.  Per round the chain
-// above over the round's 4 / 6 count cross terms (gathered from the uploaded bases: nothing is folded), k_finalize for their encodings,
-// and one k_loop_step (loop.hip) for the transcript step, the folds and the next round's scalars: launches whose number does not
-// depend on count, nothing returning to the host between the one upload and the one download.  fam: G | G' | H resp. G | T | U;
-// vec: c | d resp. x.  The outputs are written when the call has succeeded, never before.
-void Engine::ipa_rounds(size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* H, const uint8_t* vec_c, const uint8_t* vec_d,
-                        uint8_t* transcripts, uint8_t* rounds_comp, uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas) {
-  const uint8_t *fam[3] = {G, G_prime, H}, *vec[2] = {vec_c, vec_d};
-  loop_rounds(true, count, n, fam, vec, transcripts, rounds_comp, rounds_aff, finals, gammas);
-}
-void Engine::same_msm_rounds(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* vec_x, uint8_t* transcripts,
-                             uint8_t* rounds_comp, uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas) {
-  const uint8_t *fam[3] = {G, T, U}, *vec[2] = {vec_x, nullptr};
-  loop_rounds(false, count, n, fam, vec, transcripts, rounds_comp, rounds_aff, finals, gammas);
-}
-void Engine::loop_rounds(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const vec[2], uint8_t* transcripts, uint8_t* rounds_comp,
-                         uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas) {
-  if (!count) return;
-  LoopPlan lp;
-  switch (loop_plan(ipa, count, n, lp)) {
-    case LOOP_NOT_POW2: throw std::invalid_argument("the log-round loops take n = 2^L elements per item, L >= 0");
-    case LOOP_TOO_LARGE: throw ArgError(ipa ? "cpx_ipa_rounds: at most 16384 items and count (2 n + 2) <= 2^24 points per round"
-                                            : "cpx_same_msm_rounds: at most 10922 items and 3 count n <= 2^24 points per round");
-    default: break;
-  }
-  const size_t nvec = ipa ? 2 : 1, L = lp.L, NT = lp.tasks(), terms = (size_t)lp.terms();
-  for (size_t v = 0; v < nvec; v++)
-    for (size_t i = 0; i < count * n; i++)
-      if (!fr_wire_reduced(vec[v] + i * sizeof(Fr))) throw ArgError("a scalar of a log-round loop is not reduced");
-  for (size_t i = 0; i < count; i++)
-    if (!transcript_state_valid(transcripts + i * kTranscriptBytes)) throw ArgError("a transcript state with pos > 165 or pos_begin > 166");
-  if (n == 1) {   // no round: the finals are the inputs, the states stay
-    for (size_t i = 0; i < count; i++)
-      for (size_t v = 0; v < nvec; v++) memcpy(finals + (i * nvec + v) * sizeof(Fr), vec[v] + i * sizeof(Fr), sizeof(Fr));
-    return;
-  }
-  // host memory the enqueued copies read or write: above the scope
-  std::vector<MsmTask> tasks;
-  std::vector<uint32_t> idx, lens;
-  std::vector<Fr> hvec;
-  std::vector<uint8_t> h_comp, h_aff, h_states, h_fr;
-  Tier0MsmPlan pl;
-  if (!lp.round_msm(pl, lens)) throw ArgError("a round of the loop exceeds the limits of cpx_g1_msm_many");
-  CallScope call(this);
-  pl.slices = msm_tblw_slices(opt_, (int)NT, 2, (int)pl.max_n);   // (every round has the same lengths)
-  DevBuf<Aff>&db = t0_.a0, &daff = t0_.a1;
-  DevBuf<Fr>& dfr = t0_.fr;
-  DevBuf<Jac>& res = t0_.res;
-  DevBuf<uint8_t>& dcomp = t0_.bytes;
-  db.ensure(count * lp.base_stride());
-  dfr.ensure(lp.fr_total());
-  res.ensure(lp.results());
-  daff.ensure(lp.results());
-  dcomp.ensure(lp.results() * 48);
-  t0_.lidx.ensure(lp.idx_total());
-  t0_.lstate.ensure(count * kTranscriptWords);
-  msm_chain_reserve(pl);
-  t0_.mtask.ensure(L * NT);
-  // ---- the one upload: bases item by item, vectors with unit fold coefficients, index lists, every round's tasks, states
-  const size_t pitch = lp.base_stride() * sizeof(Aff);
-  for (int f = 0; f < 3; f++) {
-    const size_t each = ipa && f == 2 ? 1 : n, off = ipa && f == 2 ? lp.h_index() : lp.family_off(f);
-    CPX_HIP(hipMemcpy2DAsync(db.p + off, pitch, fam[f], each * sizeof(Aff), each * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
-  }
-  hvec.assign(count * lp.vec_words() + (ipa ? count : 0), Fr::one());
-  for (size_t i = 0; i < count; i++)
-    for (size_t v = 0; v < nvec; v++) memcpy(&hvec[i * lp.vec_words() + v * n], vec[v] + i * n * sizeof(Fr), n * sizeof(Fr));
-  Fr* const d_vec = dfr.p + lp.fr_vec();
-  Fr* const d_ones = dfr.p + lp.fr_ones();
-  CPX_HIP(hipMemcpyAsync(d_vec, hvec.data(), count * lp.vec_words() * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  if (ipa) CPX_HIP(hipMemcpyAsync(d_ones, hvec.data() + count * lp.vec_words(), count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  loop_rounds_lists(lp, pl, idx, tasks);
-  CPX_HIP(hipMemcpyAsync(t0_.lstate.p, transcripts, count * kTranscriptBytes, hipMemcpyHostToDevice, stream_));
-  loop_rounds_resident(lp, pl);
-  // ---- the one download, into host memory of the call: the caller's buffers are written once everything has arrived
-  h_states.resize(count * kTranscriptBytes);
-  h_fr.resize((count * L + count * lp.finals_each()) * sizeof(Fr));   // gammas | finals, as they sit in the Fr memory
-  CPX_HIP(hipMemcpyAsync(h_states.data(), t0_.lstate.p, h_states.size(), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipMemcpyAsync(h_fr.data(), dfr.p + lp.fr_gammas(), h_fr.size(), hipMemcpyDeviceToHost, stream_));
-  if (rounds_comp) {
-    h_comp.resize(lp.results() * 48);
-    CPX_HIP(hipMemcpyAsync(h_comp.data(), dcomp.p, h_comp.size(), hipMemcpyDeviceToHost, stream_));
-  }
-  if (rounds_aff) {
-    h_aff.resize(lp.results() * sizeof(Aff));
-    CPX_HIP(hipMemcpyAsync(h_aff.data(), daff.p, h_aff.size(), hipMemcpyDeviceToHost, stream_));
-  }
-  call.finish();
-  memcpy(transcripts, h_states.data(), h_states.size());
-  memcpy(finals, h_fr.data() + count * L * sizeof(Fr), count * lp.finals_each() * sizeof(Fr));
-  if (gammas) memcpy(gammas, h_fr.data(), count * L * sizeof(Fr));
-  // device order [L][count][terms] -> the caller's [count][L][terms]
-  for (size_t i = 0; i < count; i++)
-    for (size_t j = 0; j < L; j++) {
-      const size_t src = lp.result_index(j, i, 0), dst = (i * L + j) * terms;
-      if (rounds_comp) memcpy(rounds_comp + dst * 48, h_comp.data() + src * 48, terms * 48);
-      if (rounds_aff) memcpy(rounds_aff + dst * sizeof(Aff), h_aff.data() + src * sizeof(Aff), terms * sizeof(Aff));
-    }
-}
-// The two halves of the loop that cpx_ipa_rounds / cpx_same_msm_rounds share with cpx_ipa_prove / cpx_same_msm_prove, inside the caller's
-// scope and after its last ensure(), on the tier-0 buffers at the offsets of loop_plan.hpp: bases in t0_.a0, Fr memory in t0_.fr, sums in
-// t0_.res, their affine forms in t0_.a1 and encodings in t0_.bytes, states in t0_.lstate.
-// ... what of the upload depends on (count, n) alone: the index lists of every round and every round's tasks.  idx, tasks: the caller's,
-// declared above its scope (enqueued copies read them)
-void Engine::loop_rounds_lists(const LoopPlan& lp, const Tier0MsmPlan& pl, std::vector<uint32_t>& idx, std::vector<MsmTask>& tasks) {
-  const size_t count = lp.count, L = lp.L, NT = lp.tasks(), terms = (size_t)lp.terms();
-  Fr* const d_rows = t0_.fr.p + lp.fr_rows();
-  lp.fill_idx(idx);
-  CPX_HIP(hipMemcpyAsync(t0_.lidx.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  tasks.resize(L * NT);
-  for (size_t j = 0; j < L; j++)
-    for (size_t i = 0; i < count; i++)
-      for (int q = 0; q < (int)terms; q++) {
-        const size_t k = i * terms + (size_t)q;
-        tasks[j * NT + k] = MsmTask{t0_.a0.p + i * lp.base_stride() + lp.family_off(lp.term_family(q)), t0_.lidx.p + lp.idx_off(j, lp.term_hi(q)),
-                                    d_rows + i * lp.row_words() + lp.scal_off(q), lp.term_len(q), 0, pl.conv_off[k]};
-      }
-  CPX_HIP(hipMemcpyAsync(t0_.mtask.p, tasks.data(), tasks.size() * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
-}
-// ... and the rounds themselves, on vectors, unit coefficients, bases, lists, tasks and states that are on the device
-void Engine::loop_rounds_resident(const LoopPlan& lp, const Tier0MsmPlan& pl) {
-  const bool ipa = lp.ipa;
-  const size_t count = lp.count, n = lp.n, L = lp.L, NT = lp.tasks();
-  Fr* const d_vec = t0_.fr.p + lp.fr_vec();
-  Fr* const d_rows = t0_.fr.p + lp.fr_rows();
-  Jac* const res = t0_.res.p;
-  Aff* const daff = t0_.a1.p;
-  uint8_t* const dcomp = t0_.bytes.p;
-  const LoopDev ld{d_vec, d_rows, t0_.fr.p + lp.fr_gammas(), t0_.fr.p + lp.fr_finals(), t0_.lstate.p, dcomp, (int)count, (int)n, (int)L};
-  if (ipa) launch_ipa_round_scalars(d_vec, (int)count, (int)n, (int)(n / 2), t0_.fr.p + lp.fr_ones(), d_rows, stream_);
-  else launch_smsm_round_scalars(d_vec, (int)count, (int)n, (int)(n / 2), d_rows, stream_);
-  for (size_t j = 0; j < L; j++) {
-    msm_chain_run(pl, t0_.mtask.p + j * NT, res + j * NT);
-    tick("k_finalize", 0, (double)NT);
-    launch_finalize(res + j * NT, (int)NT, daff + j * NT, nullptr, dcomp + j * NT * 48, stream_);
-    tock();
-    tick("k_loop_step", 0, (double)count, true);
-    launch_loop_step(ipa, ld, (int)j, stream_);
-    tock();
-  }
-}
-// The stand-alone sub-argument provers (include/cpx.h cpx_ipa_prove, cpx_same_msm_prove and their _rng forms): InnerProductProof::new
-// (inner_product_argument.rs:98-199) / SameMultiscalarProof::new (same_multiscalar_argument.rs:69-150) for `count` independent items, laid
-// out by subarg_prove_plan.hpp on top of loop_plan.hpp.  One upload (the bases straight into the loop's item rows); the draws uploaded or
-// made by k_rng_draw; IPA: k_subarg_blinders; the MSM chain over the 2 / 3 count B points; k_finalize over them and the 3 count statement
-// points; SameMSM: k_compress over T | U; k_subarg_prove_setup (subarg_prove.hip); IPA: k_smul for H = beta crs_H into the items' rows;
-// then the rounds of loop_rounds_resident; one download; one synchronisation.  The launches do not depend on count.  fam: G | G' resp.
-// G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u; vec: c | d resp. x; exactly one of rand and rng_states is given.  The outputs are
-// written when the call has succeeded, never before.
-void Engine::ipa_prove(size_t count, size_t n, const uint8_t* G, const uint8_t* G_prime, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D, const uint8_t* z,
-                       const uint8_t* vec_c, const uint8_t* vec_d, const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs,
-                       uint8_t* challenges, int* status) {
-  const uint8_t *fam[3] = {G, G_prime, nullptr}, *stmt[3] = {crs_H, C, D}, *vec[2] = {vec_c, vec_d};
-  subarg_prove(true, count, n, fam, stmt, z, vec, rand, rng_states, transcripts, proofs, challenges, status);
-}
-void Engine::same_msm_prove(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t, const uint8_t* Z_u,
-                            const uint8_t* vec_x, const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status) {
-  const uint8_t *fam[3] = {G, T, U}, *stmt[3] = {A, Z_t, Z_u}, *vec[2] = {vec_x, nullptr};
-  subarg_prove(false, count, n, fam, stmt, nullptr, vec, rand, rng_states, transcripts, proofs, challenges, status);
-}
-// The grand-product prover (include/cpx.h cpx_gprod_prove and its _rng form): GrandProductProof::new (grand_product_argument.rs:43-166) for
-// `count` independent items, laid out by gprod_plan.hpp on top of subarg_prove_plan.hpp.  It is subarg_prove below with the grand-product
-// layer ahead of the inner-product prover's steps: G | H uploaded into both families of the loop's item rows (G' is never formed),
-// k_finalize over B, k_gprod_products, the MSM chain over the C tasks, k_finalize over C, k_gprod_setup (gprod.hip), the MSM chain over
-// the D tasks — B is added to their sums by the k_finalize that normalises the statement points —, then the inner-product prover with
-// k_gprod_rdu behind k_subarg_blinders (B_d's scalars are r_d o u) and u as the fold coefficients of G'.
-void Engine::gprod_prove(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* B, const uint8_t* gprod_result,
-                         const uint8_t* vec_b, const uint8_t* vec_b_blinders, const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs,
-                         uint8_t* challenges, int* status) {
-  const GprodCall gp{ell, n_blinders, G, H, crs_U, B, gprod_result, vec_b, vec_b_blinders};
-  subarg_prove(true, count, ell + n_blinders, nullptr, nullptr, nullptr, nullptr, rand, rng_states, transcripts, proofs, challenges, status, &gp);
-}
-// The same-permutation prover (include/cpx.h cpx_same_perm_prove and its _rng form): SamePermutationProof::new
-// (same_permutation_argument.rs:40-99) for `count` independent items, laid out by same_perm_plan.hpp on top of gprod_plan.hpp.  It is
-// gprod_prove above with the same-permutation layer ahead: k_finalize over A | M, k_same_perm_step (same_perm.hip) and the MSM chain over
-// the B tasks, whose sums land where the grand-product layer reads B; its k_finalize adds A.  Nothing returns to the host in between.
-void Engine::same_perm_prove(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* A, const uint8_t* M,
-                             const uint8_t* vec_a, const uint32_t* permutation, const uint8_t* vec_a_blinders, const uint8_t* vec_m_blinders, const uint8_t* rand,
-                             uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status) {
-  const GprodCall gp{ell, n_blinders, G, H, crs_U, nullptr, nullptr, nullptr, nullptr};
-  const SamePermCall sm{A, M, vec_a, permutation, vec_a_blinders, vec_m_blinders};
-  subarg_prove(true, count, ell + n_blinders, nullptr, nullptr, nullptr, nullptr, rand, rng_states, transcripts, proofs, challenges, status, &gp, &sm);
-}
-void Engine::subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* const vec[2],
-                          const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status, const GprodCall* gp,
-                          const SamePermCall* sm) {
-  if (!count) return;
-  SamePermProvePlan spl;   // (sm: the regions of the same-permutation layer behind those of the grand-product layer, gp: those behind the inner-product prover's)
-  GprodProvePlan& gpl = spl.gp;
-  SubargProvePlan& sp = gpl.sp;
-  if (gp) {
-    switch (gprod_prove_plan(count, gp->ell, gp->nb, gpl)) {
-      case GPROD_NO_FACTOR: throw ArgError("cpx_gprod_prove: ell = 0 has no first prefix product (the reference's ell - 1 underflows)");
-      case GPROD_NOT_POW2: throw std::invalid_argument("the grand-product prover takes ell + n_blinders = 2^L elements per item");
-      case GPROD_TOO_LARGE: throw ArgError("cpx_gprod_prove: at most 16384 items and count (2 n + 2) <= 2^24 points per round");
-      case GPROD_NO_BLINDERS: throw ArgError("cpx_gprod_prove: n = 1 has no blinders (the reference's n - 2 underflows)");
-      default: break;
-    }
-  } else {
-    switch (subarg_prove_plan(ipa, count, n, sp)) {
-      case LOOP_NOT_POW2: throw std::invalid_argument("the sub-argument provers take n = 2^L elements per item, L >= 0");
-      case LOOP_TOO_LARGE: throw ArgError(ipa ? "cpx_ipa_prove: at most 16384 items and count (2 n + 2) <= 2^24 points per round"
-                                              : "cpx_same_msm_prove: at most 10922 items and 3 count n <= 2^24 points per round");
-      default: break;
-    }
-    if (ipa && n == 1) throw ArgError("cpx_ipa_prove: n = 1 has no blinders (the reference's n - 2 underflows)");
-  }
-  const LoopPlan& lp = sp.lp;
-  const size_t nvec = sp.nvec(), L = lp.L, NT = lp.tasks(), NF = sp.first(), K = SubargProvePlan::kStatement, DE = sp.draws_each(), NC = sp.challenges(),
-               PB = sp.proof_bytes();
-  const size_t ell = gp ? gp->ell : 0, nb = gp ? gp->nb : 0, DT = DE + nb;   // DT: the caller's draws per item, the grand product's nb ahead of the IPA's
-  if (rng_states) {   // (the limits of one k_rng_draw launch, as cpx_rng_fr has them)
-    if (DT > ((size_t)1 << 20) || count * DT > ((size_t)1 << 26)) throw ArgError("rng draws: at most 2^20 draws per stream and 2^26 per call");
-    for (size_t i = 0; i < count; i++) {
-      uint64_t pos;
-      memcpy(&pos, rng_states + i * RNG_STATE_BYTES + 32, 8);
-      if (!rng_pos_valid(pos)) throw ArgError("rng state: word_pos within 2^32 words of 2^64");
-    }
-  } else {
-    for (size_t i = 0; i < count * DT; i++)
-      if (!fr_wire_reduced(rand + i * sizeof(Fr))) throw ArgError("a draw of a sub-argument prover is not reduced");
-  }
-  if (sm) {
-    const uint8_t* const sc[3] = {sm->vec_a, sm->vec_a_blinders, sm->vec_m_blinders};
-    const size_t each[3] = {ell, nb, nb};
-    for (int v = 0; v < 3; v++)
-      for (size_t i = 0; i < count * each[v]; i++)
-        if (!fr_wire_reduced(sc[v] + i * sizeof(Fr))) throw ArgError("a scalar of cpx_same_perm_prove is not reduced");
-    for (size_t i = 0; i < count * ell; i++)   // the reference indexes vec_a out of bounds (util.rs:78)
-      if (sm->perm[i] >= ell) throw ArgError("cpx_same_perm_prove: a permutation entry >= ell");
-  } else if (gp) {
-    const uint8_t* const sc[3] = {gp->result, gp->vec_b, gp->vec_b_blinders};
-    const size_t each[3] = {1, ell, nb};
-    for (int v = 0; v < 3; v++)
-      for (size_t i = 0; i < count * each[v]; i++)
-        if (!fr_wire_reduced(sc[v] + i * sizeof(Fr))) throw ArgError("a scalar of cpx_gprod_prove is not reduced");
-  } else {
-    for (size_t v = 0; v < nvec; v++)
-      for (size_t i = 0; i < count * n; i++)
-        if (!fr_wire_reduced(vec[v] + i * sizeof(Fr))) throw ArgError("a witness scalar of a sub-argument prover is not reduced");
-    if (ipa)
-      for (size_t i = 0; i < count; i++)
-        if (!fr_wire_reduced(z + i * sizeof(Fr))) throw ArgError("a scalar z of cpx_ipa_prove is not reduced");
-  }
-  for (size_t i = 0; i < count; i++)
-    if (!transcript_state_valid(transcripts + i * kTranscriptBytes)) throw ArgError("a transcript state with pos > 165 or pos_begin > 166");
-  // host memory the enqueued copies read or write: above the scope
-  std::vector<MsmTask> tasks, btasks, gtasks, mtasks;
-  std::vector<SmulTask> stasks;
-  std::vector<uint32_t> idx, lens, blens, glens, addend, mlens, m_gather, m_addend;
-  std::vector<Fr> hwit, h_fr, h_ab, h_gp, h_sm;
-  std::vector<uint8_t> h_comp, h_states, h_flags, h_rng, h_smB;
-  Tier0MsmPlan pl, plb, plg, plm;
-  if (L && !lp.round_msm(pl, lens)) throw ArgError("a round of the loop exceeds the limits of cpx_g1_msm_many");
-  if (!sp.first_msm(plb, blens)) throw ArgError("the B points exceed the limits of cpx_g1_msm_many");
-  if (gp && !gpl.item_msm(plg, glens)) throw ArgError("the C and D tasks exceed the limits of cpx_g1_msm_many");
-  if (sm && !spl.item_msm(plm, mlens)) throw ArgError("the B tasks exceed the limits of cpx_g1_msm_many");
-  CallScope call(this);
-  if (L) pl.slices = msm_tblw_slices(opt_, (int)NT, 2, (int)pl.max_n);
-  plb.slices = msm_tblw_slices(opt_, (int)plb.count, 2, (int)plb.max_n);
-  if (gp) plg.slices = msm_tblw_slices(opt_, (int)plg.count, 2, (int)plg.max_n);
-  if (sm) plm.slices = msm_tblw_slices(opt_, (int)plm.count, 2, (int)plm.max_n);
-  DevBuf<Aff>&db = t0_.a0, &daff = t0_.a1;
-  DevBuf<Fr>& dfr = t0_.fr;
-  DevBuf<Jac>&res = t0_.res, &din = t0_.jin;
-  DevBuf<uint8_t>&dby = t0_.bytes, &dflag = t0_.status;
-  db.ensure(count * lp.base_stride());
-  dfr.ensure(sm ? spl.fr_total() : gp ? gpl.fr_total() : sp.fr_total());
-  res.ensure(std::max<size_t>(std::max(lp.results(), gp ? gpl.res_total() : 0), 1));
-  din.ensure(sm ? spl.jac_total() : gp ? gpl.jac_total() : sp.points());
-  daff.ensure(sm ? spl.aff_total() : gp ? gpl.aff_total() : sp.aff_total());
-  dby.ensure(sm ? spl.by_total() : gp ? gpl.by_total() : sp.by_total());
-  dflag.ensure(gp ? gpl.flags_total() : count);
-  t0_.lidx.ensure(std::max<size_t>(sm ? spl.ix_total() : gp ? gpl.ix_total() : lp.idx_total(), 1));
-  t0_.lstate.ensure(count * kTranscriptWords);
-  if (L) msm_chain_reserve(pl);
-  msm_chain_reserve(plb);
-  if (gp) msm_chain_reserve(plg);
-  if (sm) msm_chain_reserve(plm);
-  t0_.mtask.ensure(sm ? spl.task_total() : gp ? gpl.task_total() : sp.task_total());
-  if (ipa) t0_.stask.ensure(count);
-  // ---- the one upload: bases into the loop's item rows, statement points, witness, z, draws or rng states, lists, tasks, states
-  const size_t pitch = lp.base_stride() * sizeof(Aff);
-  Jac* const d_stmt = din.p + sp.pt_statement(0, 0);
-  uint8_t* const d_rng = dby.p + sp.by_rng();
-  if (rng_states) CPX_HIP(hipMemcpyAsync(d_rng, rng_states, count * RNG_STATE_BYTES, hipMemcpyHostToDevice, stream_));
-  if (gp) {   // G | H is family 0 and family 1; crs_U into the IPA's crs_H slot; C and D are made below
-    for (int f = 0; f < 2; f++) {
-      CPX_HIP(hipMemcpy2DAsync(db.p + lp.family_off(f), pitch, gp->G, ell * sizeof(Aff), ell * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
-      if (nb) CPX_HIP(hipMemcpy2DAsync(db.p + lp.family_off(f) + ell, pitch, gp->H, nb * sizeof(Aff), nb * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
-    }
-    CPX_HIP(hipMemcpy2DAsync(d_stmt, K * sizeof(Jac), gp->crs_U, sizeof(Jac), sizeof(Jac), count, hipMemcpyHostToDevice, stream_));
-    if (sm) {   // A, M, vec_a, the permutation and the two blinder vectors instead of B, gprod_result, vec_b and vec_b_blinders; the B tasks and their lists
-      CPX_HIP(hipMemcpyAsync(din.p + spl.jac_A(), sm->A, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(din.p + spl.jac_M(), sm->M, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(dfr.p + spl.fr_a(), sm->vec_a, count * ell * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(t0_.lidx.p + spl.ix_perm(), sm->perm, count * ell * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-      if (nb) {
-        CPX_HIP(hipMemcpyAsync(dfr.p + spl.fr_ra(), sm->vec_a_blinders, count * nb * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-        CPX_HIP(hipMemcpyAsync(dfr.p + spl.fr_rm(), sm->vec_m_blinders, count * nb * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-      }
-      spl.fill_lists(m_gather, m_addend);
-      CPX_HIP(hipMemcpyAsync(t0_.lidx.p + spl.ix_gather(), m_gather.data(), m_gather.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(t0_.lidx.p + spl.ix_addend(), m_addend.data(), m_addend.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-      mtasks.resize(count);
-      for (size_t i = 0; i < count; i++)   // B - A = beta sum G + alpha M
-        mtasks[i] = MsmTask{db.p + i * lp.base_stride(), t0_.lidx.p + spl.ix_gather(), dfr.p + spl.fr_bsc() + i * (ell + 1), (uint32_t)(ell + 1), 0, plm.conv_off[i]};
-      CPX_HIP(hipMemcpyAsync(t0_.mtask.p + spl.task_B(), mtasks.data(), mtasks.size() * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
-    } else {
-      CPX_HIP(hipMemcpyAsync(din.p + gpl.pt_B(0), gp->B, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_result(), gp->result, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_b(), gp->vec_b, count * ell * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-      if (nb) CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_rb(), gp->vec_b_blinders, count * nb * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-    }
-    if (!rng_states) {   // per item vec_c_blinders | the IPA's draws
-      if (nb) CPX_HIP(hipMemcpy2DAsync(dfr.p + gpl.fr_cbl(), nb * sizeof(Fr), rand, DT * sizeof(Fr), nb * sizeof(Fr), count, hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpy2DAsync(dfr.p + sp.fr_draws(), DE * sizeof(Fr), rand + nb * sizeof(Fr), DT * sizeof(Fr), DE * sizeof(Fr), count, hipMemcpyHostToDevice, stream_));
-    }
-    gpl.fill_addend(addend);
-    CPX_HIP(hipMemcpyAsync(t0_.lidx.p + gpl.ix_addend(), addend.data(), addend.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-    gtasks.resize(2 * count);
-    for (size_t i = 0; i < count; i++) {   // C = <c, G | H>; D - B = <D's scalars, G | H>
-      gtasks[i] = MsmTask{db.p + i * lp.base_stride() + lp.family_off(0), nullptr, dfr.p + sp.fr_wit() + i * 2 * n, (uint32_t)n, 0, plg.conv_off[i]};
-      gtasks[count + i] = MsmTask{db.p + i * lp.base_stride() + lp.family_off(0), nullptr, dfr.p + gpl.fr_dsc() + i * n, (uint32_t)n, 0, plg.conv_off[i]};
-    }
-    CPX_HIP(hipMemcpyAsync(t0_.mtask.p + gpl.task_C(), gtasks.data(), gtasks.size() * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
-  } else {
-    for (int f = 0; f < (ipa ? 2 : 3); f++)
-      CPX_HIP(hipMemcpy2DAsync(db.p + lp.family_off(f), pitch, fam[f], n * sizeof(Aff), n * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
-    for (size_t k = 0; k < K; k++)
-      CPX_HIP(hipMemcpy2DAsync(d_stmt + k, K * sizeof(Jac), stmt[k], sizeof(Jac), sizeof(Jac), count, hipMemcpyHostToDevice, stream_));
-    hwit.resize(count * nvec * n);
-    for (size_t i = 0; i < count; i++)
-      for (size_t v = 0; v < nvec; v++) memcpy(&hwit[(i * nvec + v) * n], vec[v] + i * n * sizeof(Fr), n * sizeof(Fr));
-    CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_wit(), hwit.data(), hwit.size() * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-    if (ipa) CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_z(), z, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-    if (!rng_states) CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_draws(), rand, count * DE * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  }
-  if (L) loop_rounds_lists(lp, pl, idx, tasks);
-  btasks.resize(count * NF);
-  for (size_t i = 0; i < count; i++)
-    for (size_t b = 0; b < NF; b++) {   // IPA: G r_c, G' r_d (grand product: G (r_d o u)); SameMSM: G r, T r, U r
-      const Fr* sc = ipa && b == 1 ? (gp ? dfr.p + gpl.fr_rdu() : dfr.p + sp.fr_rd()) + i * n : dfr.p + sp.fr_draws() + i * DE;
-      btasks[i * NF + b] = MsmTask{db.p + i * lp.base_stride() + lp.family_off(sp.first_family(b)), nullptr, sc, (uint32_t)n, 0, plb.conv_off[i * NF + b]};
-    }
-  MsmTask* const d_btasks = t0_.mtask.p + sp.task_first();
-  CPX_HIP(hipMemcpyAsync(d_btasks, btasks.data(), btasks.size() * sizeof(MsmTask), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(t0_.lstate.p, transcripts, count * kTranscriptBytes, hipMemcpyHostToDevice, stream_));
-  // ---- the steps before the loop
-  if (rng_states) {
-    tick("k_rng_draw", (double)(count * DT * sizeof(Fr)), (double)(count * DT));
-    if (nb) launch_rng_draw(rng_draw_args(d_rng, nullptr, count, 0, nullptr, {{nb, dfr.p + gpl.fr_cbl()}, {DE, dfr.p + sp.fr_draws()}}), stream_);
-    else launch_rng_draw(rng_draw_args(d_rng, nullptr, count, 0, nullptr, {{DE, dfr.p + sp.fr_draws()}}), stream_);
-    tock();
-  }
-  const SubargProveDev sd{sp, dfr.p, dfr.p + lp.fr_vec(), dfr.p + lp.fr_ones(), dfr.p + lp.fr_finals(), dby.p, dflag.p, t0_.lstate.p, gp ? dfr.p + gpl.fr_u() : nullptr};
-  const GprodDev gd{gpl, dfr.p, dby.p, dflag.p, t0_.lstate.p};
-  if (sm) {   // the same-permutation layer: the encodings of A and M, step 1 with the factors, their product and vec_b_blinders, B - A
-    tick("k_finalize", 0, 2.0 * count);
-    launch_finalize(din.p + spl.jac_A(), (int)(2 * count), daff.p + spl.aff_A(), nullptr, dby.p + spl.by_A(), stream_);
-    tock();
-    CPX_HIP(hipMemcpy2DAsync(db.p + lp.h_index(), pitch, daff.p + spl.aff_M(), sizeof(Aff), sizeof(Aff), count, hipMemcpyDeviceToDevice, stream_));
-    tick("k_same_perm_step", 0, (double)count, true);
-    launch_same_perm_step(SamePermDev{spl, dfr.p, dby.p, t0_.lidx.p + spl.ix_perm(), t0_.lstate.p}, stream_);
-    tock();
-    msm_chain_run(plm, t0_.mtask.p + spl.task_B(), din.p + gpl.pt_B(0));
-  }
-  if (gp) {   // the grand-product layer: B's encoding (same-permutation: A is added first), vec_c, C, steps 1 and 2 with vec_d and inner_prod, D - B
-    tick("k_finalize", 0, (double)count);
-    launch_finalize(din.p + gpl.pt_B(0), (int)count, daff.p + sp.aff_points() + gpl.pt_B(0), nullptr, dby.p + gpl.by_B(), stream_,
-                    sm ? t0_.lidx.p + spl.ix_addend() : nullptr);
-    tock();
-    tick("k_gprod_products", 0, (double)count, true);
-    launch_gprod_products(gd, stream_);
-    tock();
-    msm_chain_run(plg, t0_.mtask.p + gpl.task_C(), res.p + gpl.res_C(0));
-    tick("k_finalize", 0, (double)count);
-    launch_finalize(res.p + gpl.res_C(0), (int)count, nullptr, nullptr, dby.p + gpl.by_C(), stream_);
-    tock();
-    tick("k_gprod_setup", 0, (double)count, true);
-    launch_gprod_setup(gd, stream_);
-    tock();
-    msm_chain_run(plg, t0_.mtask.p + gpl.task_D(), res.p + gpl.res_D(0));
-    CPX_HIP(hipMemcpy2DAsync(d_stmt + 1, K * sizeof(Jac), res.p + gpl.res_C(0), sizeof(Jac), sizeof(Jac), count, hipMemcpyDeviceToDevice, stream_));
-    CPX_HIP(hipMemcpy2DAsync(d_stmt + 2, K * sizeof(Jac), res.p + gpl.res_D(0), sizeof(Jac), sizeof(Jac), count, hipMemcpyDeviceToDevice, stream_));
-  }
-  if (ipa) {
-    tick("k_subarg_blinders", 0, (double)count, true);
-    launch_subarg_blinders(sd, stream_);
-    tock();
-    if (gp) {
-      tick("k_gprod_rdu", 0, (double)count, true);
-      launch_gprod_rdu(gd, stream_);
-      tock();
-    }
-  } else {
-    CPX_HIP(hipMemsetAsync(dflag.p, 0, count, stream_));
-  }
-  msm_chain_run(plb, d_btasks, din.p);
-  tick("k_finalize", 0, (double)sp.points());
-  launch_finalize(din.p, (int)sp.points(), daff.p + sp.aff_points(), nullptr, dby.p + sp.by_points(), stream_, gp ? t0_.lidx.p + gpl.ix_addend() : nullptr);
-  tock();
-  if (!ipa) {
-    tick("k_compress", 0, 2.0 * count * n, true);
-    launch_compress(db.p + lp.family_off(1), (int)(2 * n), (int)lp.base_stride(), (int)count, dby.p + sp.by_tu(), stream_);
-    tock();
-  }
-  tick("k_subarg_prove_setup", 0, (double)count, true);
-  launch_subarg_prove_setup(sd, stream_);
-  tock();
-  if (ipa) {   // H = beta crs_H (inner_product_argument.rs:140) into slot h_index() of the item's row
-    stasks.resize(count);
-    for (size_t i = 0; i < count; i++)
-      stasks[i] = SmulTask{nullptr, daff.p + sp.aff_points() + sp.pt_statement(i, 0), db.p + i * lp.base_stride() + lp.h_index(), dfr.p + sp.fr_ab() + 2 * i + 1, 0, smul_flag()};
-    CPX_HIP(hipMemcpyAsync(t0_.stask.p, stasks.data(), count * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
-    smul_tasks(t0_.stask.p, count, 1, (double)count);
-  }
-  if (L) loop_rounds_resident(lp, pl);
-  // ---- the one download, into host memory of the call: the caller's buffers are written once everything has arrived
-  h_states.resize(count * kTranscriptBytes);
-  h_fr.resize(count * L + count * lp.finals_each());   // gammas | finals, as they sit in the Fr memory
-  h_ab.resize(count * sp.ab_each());
-  h_comp.resize(sp.by_tu());                           // the round encodings | the B and statement encodings
-  h_flags.resize(gp ? gpl.flags_total() : count);   // gp: behind the blinders' flags those of beta = 0
-  CPX_HIP(hipMemcpyAsync(h_states.data(), t0_.lstate.p, h_states.size(), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipMemcpyAsync(h_fr.data(), dfr.p + lp.fr_gammas(), h_fr.size() * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipMemcpyAsync(h_ab.data(), dfr.p + sp.fr_ab(), h_ab.size() * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipMemcpyAsync(h_comp.data(), dby.p, h_comp.size(), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipMemcpyAsync(h_flags.data(), dflag.p, h_flags.size(), hipMemcpyDeviceToHost, stream_));
-  if (gp) {
-    h_gp.resize(3 * count);   // r_p | alpha, beta, as they sit in the Fr memory
-    CPX_HIP(hipMemcpyAsync(h_gp.data(), dfr.p + gpl.fr_rp(), h_gp.size() * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
-  }
-  if (sm) {
-    h_sm.resize(2 * count);     // alpha, beta per item
-    h_smB.resize(count * 48);   // B's encodings
-    CPX_HIP(hipMemcpyAsync(h_sm.data(), dfr.p + spl.fr_chal(), h_sm.size() * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
-    CPX_HIP(hipMemcpyAsync(h_smB.data(), dby.p + gpl.by_B(), h_smB.size(), hipMemcpyDeviceToHost, stream_));
-  }
-  if (rng_states) {
-    h_rng.resize(count * RNG_STATE_BYTES);
-    CPX_HIP(hipMemcpyAsync(h_rng.data(), d_rng, h_rng.size(), hipMemcpyDeviceToHost, stream_));
-  }
-  call.finish();
-  if (rng_states) memcpy(rng_states, h_rng.data(), h_rng.size());   // (a refused item's stream has drawn too)
-  const Fr* h_gam = h_fr.data();
-  const Fr* h_fin = h_fr.data() + count * L;
-  const size_t slead = sm ? spl.byte_gprod() : 0, snlead = sm ? 2 : 0;   // the same-permutation layer's B and challenges ahead of the grand product's
-  const size_t lead = slead + (gp ? gpl.byte_ipa() : 0), nlead = snlead + (gp ? 2 : 0);   // ... and the grand product's ahead of the IPA's
-  for (size_t i = 0; i < count; i++) {
-    uint8_t* o = proofs + i * (lead + PB);
-    uint8_t* const ch = challenges ? challenges + i * (nlead + NC) * sizeof(Fr) : nullptr;
-    if (h_flags[i] || (gp && h_flags[gpl.flag_beta() + i])) {   // the reference panics (generate_ipa_blinders; beta = 0): zero bytes, zero challenges, the state as it came
-      memset(o, 0, lead + PB);
-      if (ch) memset(ch, 0, (nlead + NC) * sizeof(Fr));
-      status[i] = CPX_ERR_ARG;
-      continue;
-    }
-    if (sm) {   // same_permutation_argument.rs:173-177: B, then the GrandProductProof
-      memcpy(o + spl.byte_B(), h_smB.data() + i * 48, 48);
-      if (ch) memcpy(ch, h_sm.data() + 2 * i, 2 * sizeof(Fr));
-    }
-    if (gp) {   // grand_product_argument.rs:248-253: C, r_p, then the InnerProductProof
-      memcpy(o + slead + gpl.byte_C(), h_comp.data() + sp.by_points() + sp.pt_statement(i, 1) * 48, 48);
-      host::S(h_gp[i]).to_le_bytes(o + slead + gpl.byte_rp());
-      if (ch) memcpy(ch + snlead * sizeof(Fr), h_gp.data() + count + 2 * i, 2 * sizeof(Fr));
-      o += lead;
-    }
-    for (size_t b = 0; b < NF; b++) memcpy(o + sp.point_byte(b), h_comp.data() + sp.by_points() + sp.pt_first(i, b) * 48, 48);
-    for (size_t b = 0; b < sp.blocks(); b++)
-      for (size_t j = 0; j < L; j++) memcpy(o + sp.point_byte(sp.round_slot(j, b)), h_comp.data() + lp.result_index(j, i, sp.block_term(b)) * 48, 48);
-    for (size_t v = 0; v < lp.finals_each(); v++) host::S(h_fin[i * lp.finals_each() + v]).to_le_bytes(o + sp.scalar_byte(v));
-    memcpy(transcripts + i * kTranscriptBytes, h_states.data() + i * kTranscriptBytes, kTranscriptBytes);
-    if (ch) {
-      memcpy(ch + nlead * sizeof(Fr), h_ab.data() + i * sp.ab_each(), sp.ab_each() * sizeof(Fr));
-      memcpy(ch + (nlead + sp.ab_each()) * sizeof(Fr), h_gam + i * L, L * sizeof(Fr));
-    }
-    status[i] = CPX_OK;
-  }
-}
-// The stand-alone sub-argument verifiers (include/cpx.h cpx_ipa_verify, cpx_same_msm_verify): InnerProductProof::verify
-// (inner_product_argument.rs:202-326) / SameMultiscalarProof::verify (same_multiscalar_argument.rs:153-261) for `count` independent items,
-// each against an MsmAccumulator of its own, flattened by subarg_check_plan.hpp into one MSM per item.  One upload; k_decompress with
-// status over every proof point of the call, k_finalize over the statement points (their affine forms into the items' rows, their encodings
-// for the transcript), for SameMSM k_compress over T | U, k_subarg_scalars (subarg.hip), the MSM chain above with one task per item; one
-// download of the sums, flags, states and challenges; one synchronisation.  The launches do not depend on count.  fam: G resp. G | T | U;
-// stmt: crs_H | C | D resp. A | Z_t | Z_u.  The outputs are written when the call has succeeded, never before.
-void Engine::ipa_verify(size_t count, size_t n, const uint8_t* G, const uint8_t* crs_H, const uint8_t* C, const uint8_t* D, const uint8_t* z, const uint8_t* vec_u,
-                        const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
-  const uint8_t *fam[3] = {G, nullptr, nullptr}, *stmt[3] = {crs_H, C, D};
-  subarg_verify(true, count, n, fam, stmt, z, vec_u, proofs, rand, transcripts, challenges, verdicts);
-}
-void Engine::same_msm_verify(size_t count, size_t n, const uint8_t* G, const uint8_t* T, const uint8_t* U, const uint8_t* A, const uint8_t* Z_t, const uint8_t* Z_u,
-                             const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
-  const uint8_t *fam[3] = {G, T, U}, *stmt[3] = {A, Z_t, Z_u};
-  subarg_verify(false, count, n, fam, stmt, nullptr, nullptr, proofs, rand, transcripts, challenges, verdicts);
-}
-// The grand-product verifier (include/cpx.h cpx_gprod_verify): GrandProductProof::verify (grand_product_argument.rs:180-246) for `count`
-// independent items.  It is subarg_verify below on G | H, crs_U, the proof's C and D = B - beta^-1 crs_G_sum + alpha crs_H_sum, with the
-// steps that make z, vec_u and D on the device ahead of it: k_decompress over C into the items' rows, k_finalize over crs_U (into the rows)
-// and B (its encoding for step 1), k_gprod_verify_steps (gprod.hip), two k_smul launches for D and k_compress for its encoding, which
-// ipa_step1 hashes — so D is formed, and once it is, it takes the IPA's own weight in the row.  A wrong crs_G_sum or crs_H_sum gives
-// another D and CPX_ERR_VERIFY.
-void Engine::gprod_verify(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* crs_G_sum,
-                          const uint8_t* crs_H_sum, const uint8_t* B, const uint8_t* gprod_result, const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts,
-                          uint8_t* challenges, int* verdicts) {
-  if (!count) return;
-  if (!ell) throw ArgError("cpx_gprod_verify: ell = 0 (the reference's prover cannot make such a proof: its ell - 1 underflows)");
-  if (ell + n_blinders < ell) throw ArgError("cpx_gprod_verify: ell + n_blinders overflows");
-  const GprodCheck gp{ell, n_blinders, G, H, crs_U, crs_G_sum, crs_H_sum, B, gprod_result};
-  subarg_verify(true, count, ell + n_blinders, nullptr, nullptr, nullptr, nullptr, proofs, rand, transcripts, challenges, verdicts, &gp);
-}
-// The same-permutation verifier (include/cpx.h cpx_same_perm_verify): SamePermutationProof::verify (same_permutation_argument.rs:112-171) for
-// `count` independent items.  It is gprod_verify above with B taken from the proof (k_decompress, with a verdict), k_finalize over A | M into
-// three further slots of every row, k_same_perm_verify_step ahead of k_gprod_verify_steps and k_same_perm_weights behind k_subarg_scalars
-// (same_perm.hip): the relation of :149 joins the item's one MSM with the first of the item's three factors.
-void Engine::same_perm_verify(size_t count, size_t ell, size_t n_blinders, const uint8_t* G, const uint8_t* H, const uint8_t* crs_U, const uint8_t* crs_G_sum,
-                              const uint8_t* crs_H_sum, const uint8_t* A, const uint8_t* M, const uint8_t* vec_a, const uint8_t* proofs, const uint8_t* rand,
-                              uint8_t* transcripts, uint8_t* challenges, int* verdicts) {
-  if (!count) return;
-  if (!ell) throw ArgError("cpx_same_perm_verify: ell = 0 (the reference's prover cannot make such a proof: its ell - 1 underflows)");
-  if (ell + n_blinders < ell) throw ArgError("cpx_same_perm_verify: ell + n_blinders overflows");
-  const GprodCheck gp{ell, n_blinders, G, H, crs_U, crs_G_sum, crs_H_sum, nullptr, nullptr};
-  const SamePermCheck sm{A, M, vec_a};
-  subarg_verify(true, count, ell + n_blinders, nullptr, nullptr, nullptr, nullptr, proofs, rand, transcripts, challenges, verdicts, &gp, &sm);
-}
-void Engine::subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* vec_u,
-                           const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts, const GprodCheck* gp,
-                           const SamePermCheck* sm) {
-  if (!count) return;
-  SamePermCheckPlan spl;   // (sm: the regions of the same-permutation steps behind those of the grand-product steps and the three further points of every row)
-  GprodCheckPlan& gpl = spl.gp;   // (gp: the regions of the grand-product steps behind those of the inner-product check)
-  SubargCheckPlan& sp = gpl.sp;
-  switch (sm   ? same_perm_check_plan(count, gp->ell, gp->nb, spl)
-          : gp ? gprod_check_plan(count, gp->ell, gp->nb, gpl)
-               : subarg_check_plan(ipa, count, n, sp)) {
-    case SUBARG_NOT_POW2: throw std::invalid_argument("the sub-argument verifiers take n = 2^L elements per item, L >= 0");
-    case SUBARG_TOO_LARGE: throw ArgError(ipa ? "cpx_ipa_verify: at most 65536 items and count (n + 4 L + 5) <= 2^24 points"
-                                              : "cpx_same_msm_verify: at most 65536 items and count (3 n + 6 L + 6) <= 2^24 points");
-    default: break;
-  }
-  const size_t NP = sp.points(), PP = sp.proof_points(), PB = sp.proof_bytes(), NC = sp.challenges(), K = SubargCheckPlan::kStatement;
-  const size_t NR = sm ? (size_t)spl.checks() : (size_t)sp.checks();   // the caller's factors per item: the same-permutation check's ahead of the IPA's two
-  for (size_t i = 0; i < count * NR; i++)
-    if (!host::is_valid_factor(rand + 32 * i)) throw ArgError("the random factors of a sub-argument check must be non-zero reduced field elements");
-  if (sm) {
-    for (size_t i = 0; i < count * gp->ell; i++)
-      if (!fr_wire_reduced(sm->vec_a + i * sizeof(Fr))) throw ArgError("a scalar of vec_a of cpx_same_perm_verify is not reduced");
-  } else if (gp) {
-    for (size_t i = 0; i < count; i++)
-      if (!fr_wire_reduced(gp->result + i * sizeof(Fr))) throw ArgError("a scalar gprod_result of cpx_gprod_verify is not reduced");
-  } else if (ipa) {
-    for (size_t i = 0; i < count; i++)
-      if (!fr_wire_reduced(z + i * sizeof(Fr))) throw ArgError("a scalar z of cpx_ipa_verify is not reduced");
-    for (size_t i = 0; i < count * n; i++)
-      if (!fr_wire_reduced(vec_u + i * sizeof(Fr))) throw ArgError("a scalar of vec_u is not reduced");
-  }
-  for (size_t i = 0; i < count; i++)
-    if (!transcript_state_valid(transcripts + i * kTranscriptBytes)) throw ArgError("a transcript state with pos > 165 or pos_begin > 166");
-  // host memory the enqueued copies read or write: above the scope
-  std::vector<MsmTask> tasks;
-  std::vector<uint32_t> ix, lens;
-  std::vector<uint8_t> canon, h_states, h_bad;
-  std::vector<size_t> point_bytes(PP);
-  std::vector<Fr> h_chal, h_gchal;
-  std::vector<Jac> h_res;
-  std::vector<SmulTask> stasks;
-  std::vector<uint32_t> gix, six;
-  std::vector<uint8_t> h_gbad, h_sbad;
-  std::vector<Fr> h_schal;
-  Tier0MsmPlan pl;
-  if (!sp.msm(pl, lens)) throw ArgError("the items exceed the limits of cpx_g1_msm_many");
-  // the grand product's proof is C, r_p, then the InnerProductProof's bytes (grand_product_argument.rs:248-253)
-  // ... and the same-permutation proof is B, then the grand product's (same_permutation_argument.rs:173-177)
-  const size_t slead = sm ? SamePermCheckPlan::kHead : 0, glead = gp ? GprodCheckPlan::kHead : 0, lead = slead + glead, PBT = lead + PB, ell = gp ? gp->ell : 0,
-               nb = gp ? gp->nb : 0;
-  for (size_t s = 0; s < PP; s++) point_bytes[s] = lead + sp.point_byte(s);
-  if (gp) point_bytes.push_back(slead);
-  if (sm) point_bytes.push_back(0);
-  proofs = canonical_infinities(proofs, count * PBT, count, PBT, point_bytes, canon);
-  CallScope call(this);
-  pl.slices = msm_tblw_slices(opt_, (int)count, 2, (int)pl.max_n);
-  DevBuf<Aff>& rows = t0_.a0;
-  DevBuf<Fr>& dfr = t0_.fr;
-  DevBuf<uint8_t>&db = t0_.bytes, &dst = t0_.status;   // dst: the decoder's verdicts [count][PP] | the items' flags [count]
-  DevBuf<Jac>&din = t0_.jin, &res = t0_.res;
-  rows.ensure(count * NP);
-  dfr.ensure(sm ? spl.fr_total() : gp ? gpl.fr_total() : sp.fr_total());
-  db.ensure(sm ? spl.by_total() : gp ? gpl.by_total() : sp.by_total());
-  dst.ensure(sm ? spl.st_total() : gp ? gpl.st_total() : count * PP + count);
-  din.ensure(sm ? spl.jac_total() : count * K);
-  res.ensure(count);
-  t0_.lidx.ensure(sm ? spl.ix_total() : gp ? gpl.ix_total() : sp.ix_total());
-  t0_.lstate.ensure(count * kTranscriptWords);
-  if (gp) {
-    t0_.a1.ensure(gpl.aff_total());
-    t0_.stask.ensure(2);
-  }
-  msm_chain_reserve(pl);
-  // ---- the one upload: bases and statement points into their places, proofs, scalars, index words, states
-  if (gp) {
-    Aff* const g_aff = t0_.a1.p;   // G | H; crs_U and B (din: crs_U [count] | B [count]); the sums; the proofs in two parts; gprod_result
-    CPX_HIP(hipMemcpy2DAsync(rows.p, NP * sizeof(Aff), gp->G, ell * sizeof(Aff), ell * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
-    if (nb) CPX_HIP(hipMemcpy2DAsync(rows.p + ell, NP * sizeof(Aff), gp->H, nb * sizeof(Aff), nb * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(din.p, gp->crs_U, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
-    if (sm) {   // B is the proof's first point, gprod_result is made on the device; A | M, vec_a, the first factor of every item, the row slots of A and M
-      CPX_HIP(hipMemcpy2DAsync(db.p + gpl.by_B(), 48, proofs, PBT, 48, count, hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(din.p + spl.jac_A(), sm->A, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(din.p + spl.jac_A() + count, sm->M, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(dfr.p + spl.fr_a(), sm->vec_a, count * ell * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpy2DAsync(dfr.p + spl.fr_a0(), sizeof(Fr), rand, NR * sizeof(Fr), sizeof(Fr), count, hipMemcpyHostToDevice, stream_));
-      spl.fill_idx(six);
-      CPX_HIP(hipMemcpyAsync(t0_.lidx.p + spl.ix_AM_dst(), six.data(), six.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-    } else {
-      CPX_HIP(hipMemcpyAsync(din.p + count, gp->B, count * sizeof(Jac), hipMemcpyHostToDevice, stream_));
-      CPX_HIP(hipMemcpyAsync(dfr.p + gpl.fr_result(), gp->result, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-    }
-    CPX_HIP(hipMemcpyAsync(g_aff + gpl.aff_g_sum(), gp->g_sum, count * sizeof(Aff), hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(g_aff + gpl.aff_h_sum(), gp->h_sum, count * sizeof(Aff), hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpy2DAsync(db.p + sp.by_proofs(), PB, proofs + lead, PBT, PB, count, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpy2DAsync(db.p + gpl.by_heads(), glead, proofs + slead, PBT, glead, count, hipMemcpyHostToDevice, stream_));
-    gpl.fill_idx(gix);
-    CPX_HIP(hipMemcpyAsync(t0_.lidx.p + gpl.ix_C_src(), gix.data(), gix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  } else {
-    for (int f = 0; f < sp.families(); f++)
-      CPX_HIP(hipMemcpy2DAsync(rows.p + sp.base_off(f), NP * sizeof(Aff), fam[f], n * sizeof(Aff), n * sizeof(Aff), count, hipMemcpyHostToDevice, stream_));
-    for (size_t k = 0; k < K; k++)
-      CPX_HIP(hipMemcpy2DAsync(din.p + k, K * sizeof(Jac), stmt[k], sizeof(Jac), sizeof(Jac), count, hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(db.p + sp.by_proofs(), proofs, count * PB, hipMemcpyHostToDevice, stream_));
-  }
-  if (ipa && !gp) {
-    CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_z(), z, count * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-    CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_u(), vec_u, count * n * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  }
-  if (sm) CPX_HIP(hipMemcpy2DAsync(dfr.p + sp.fr_rand(), (size_t)sp.checks() * sizeof(Fr), rand + sizeof(Fr), NR * sizeof(Fr), (size_t)sp.checks() * sizeof(Fr), count,
-                                   hipMemcpyHostToDevice, stream_));
-  else CPX_HIP(hipMemcpyAsync(dfr.p + sp.fr_rand(), rand, count * (size_t)sp.checks() * sizeof(Fr), hipMemcpyHostToDevice, stream_));
-  sp.fill_idx(ix);
-  CPX_HIP(hipMemcpyAsync(t0_.lidx.p, ix.data(), ix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-  CPX_HIP(hipMemcpyAsync(t0_.lstate.p, transcripts, count * kTranscriptBytes, hipMemcpyHostToDevice, stream_));
-  // ---- the device work
-  tick("k_decompress", 0, (double)(count * PP));
-  launch_decompress(opt_, db.p, (int)(count * PP), rows.p, t0_.lidx.p + sp.ix_dst(), dst.p, 1, stream_, t0_.lidx.p + sp.ix_src());
-  tock();
-  if (gp) {
-    Aff* const g_aff = t0_.a1.p;
-    uint8_t *const g_heads = db.p + gpl.by_heads(), *const g_denc = db.p + gpl.by_D();
-    const uint32_t* const ix = t0_.lidx.p;
-    tick("k_decompress", 0, (double)count);
-    launch_decompress(opt_, g_heads, (int)count, rows.p, ix + gpl.ix_C_dst(), dst.p + gpl.st_C(), 1, stream_, ix + gpl.ix_C_src());   // C into the rows' C slots
-    tock();
-    tick("k_finalize", 0, 2.0 * count);
-    launch_finalize(din.p, (int)count, rows.p, ix + gpl.ix_U_dst(), nullptr, stream_);                          // crs_U into the rows
-    if (!sm) launch_finalize(din.p + count, (int)count, g_aff + gpl.aff_B(), nullptr, db.p + gpl.by_B(), stream_);   // B: affine and encoding
-    tock();
-    const SamePermVerifyDev smd{spl, dfr.p, db.p, t0_.lstate.p};
-    if (sm) {   // B from its encoding, with a verdict; A | M into the rows behind the statement slots, their encodings for step 1; the step
-      tick("k_decompress", 0, (double)count);
-      launch_decompress(opt_, db.p + gpl.by_B(), (int)count, g_aff + gpl.aff_B(), nullptr, dst.p + spl.st_B(), 1, stream_);
-      tock();
-      tick("k_finalize", 0, 2.0 * count);
-      launch_finalize(din.p + spl.jac_A(), (int)(2 * count), rows.p, ix + spl.ix_AM_dst(), db.p + spl.by_A(), stream_);
-      tock();
-      CPX_HIP(hipMemcpy2DAsync(rows.p + spl.row_B(), NP * sizeof(Aff), g_aff + gpl.aff_B(), sizeof(Aff), sizeof(Aff), count, hipMemcpyDeviceToDevice, stream_));
-      tick("k_same_perm_verify_step", 0, (double)count, true);
-      launch_same_perm_verify_step(smd, stream_);
-      tock();
-    }
-    tick("k_gprod_verify_steps", 0, (double)count, true);
-    launch_gprod_verify_steps(GprodVerifyDev{gpl, dfr.p, db.p, dst.p, t0_.lstate.p}, stream_);
-    tock();
-    // D = (B - beta^-1 crs_G_sum) + alpha crs_H_sum (:223), one element per item in each launch; then its encoding and its place in the rows
-    stasks = {SmulTask{g_aff + gpl.aff_B(), g_aff + gpl.aff_g_sum(), g_aff + gpl.aff_partial(), dfr.p + gpl.fr_neg_beta_inv(), 1, smul_flag()},
-              SmulTask{g_aff + gpl.aff_partial(), g_aff + gpl.aff_h_sum(), g_aff + gpl.aff_D(), dfr.p + gpl.fr_alpha(), 1, smul_flag()}};
-    CPX_HIP(hipMemcpyAsync(t0_.stask.p, stasks.data(), 2 * sizeof(SmulTask), hipMemcpyHostToDevice, stream_));
-    smul_tasks(t0_.stask.p, 1, count, (double)count);
-    smul_tasks(t0_.stask.p + 1, 1, count, (double)count);
-    tick("k_compress", 0, (double)count, true);
-    launch_compress(g_aff + gpl.aff_D(), (int)count, (int)count, 1, g_denc, stream_);
-    tock();
-    uint8_t* const d_stmt_enc = db.p + sp.by_statement();   // [count][3][48]: (crs_U: not hashed) | C | D
-    CPX_HIP(hipMemcpy2DAsync(d_stmt_enc + 48, K * 48, g_heads, glead, 48, count, hipMemcpyDeviceToDevice, stream_));
-    CPX_HIP(hipMemcpy2DAsync(d_stmt_enc + 96, K * 48, g_denc, 48, 48, count, hipMemcpyDeviceToDevice, stream_));
-    CPX_HIP(hipMemcpy2DAsync(rows.p + sp.statement_off() + 2, NP * sizeof(Aff), g_aff + gpl.aff_D(), sizeof(Aff), sizeof(Aff), count, hipMemcpyDeviceToDevice, stream_));
-  } else {
-    tick("k_finalize", 0, (double)(count * K));
-    launch_finalize(din.p, (int)(count * K), rows.p, t0_.lidx.p + sp.ix_statement(), db.p + sp.by_statement(), stream_);
-    tock();
-  }
-  if (!ipa) {
-    tick("k_compress", 0, 2.0 * count * n, true);
-    for (size_t i = 0; i < count; i += 65535) {   // (a row per item in the grid's second dimension: 65535 at most; 2^16 items take two launches)
-      const size_t rows_now = std::min<size_t>(count - i, 65535);
-      launch_compress(rows.p + i * NP + sp.base_off(1), (int)(2 * n), (int)NP, (int)rows_now, db.p + sp.by_tu() + i * 2 * n * 48, stream_);
-    }
-    tock();
-  }
-  uint8_t* const d_bad = dst.p + count * PP;
-  tick("k_subarg_scalars", 0, (double)count, true);
-  launch_subarg_scalars(SubargDev{sp, dfr.p, db.p, dst.p, d_bad, t0_.lstate.p}, stream_);
-  tock();
-  if (sm) {   // same_permutation_argument.rs:149 joins the item's one MSM
-    tick("k_same_perm_weights", 0, (double)count, true);
-    launch_same_perm_weights(SamePermVerifyDev{spl, dfr.p, db.p, t0_.lstate.p}, stream_);
-    tock();
-  }
-  msm_chain(pl, lens.data(), rows.p, dfr.p + sp.fr_weights(), res.p, tasks);
-  // ---- the one download, into host memory of the call: the caller's buffers are written once everything has arrived
-  h_res.resize(count);
-  h_bad.resize(count);
-  h_states.resize(count * kTranscriptBytes);
-  h_chal.resize(count * NC);
-  CPX_HIP(hipMemcpyAsync(h_res.data(), res.p, count * sizeof(Jac), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipMemcpyAsync(h_bad.data(), d_bad, count, hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipMemcpyAsync(h_states.data(), t0_.lstate.p, h_states.size(), hipMemcpyDeviceToHost, stream_));
-  CPX_HIP(hipMemcpyAsync(h_chal.data(), dfr.p + sp.fr_challenges(), count * NC * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
-  if (gp) {
-    h_gbad.resize(count);
-    h_gchal.resize(2 * count);
-    CPX_HIP(hipMemcpyAsync(h_gbad.data(), dst.p + gpl.st_bad(), count, hipMemcpyDeviceToHost, stream_));
-    CPX_HIP(hipMemcpyAsync(h_gchal.data(), dfr.p + gpl.fr_chal(), 2 * count * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
-  }
-  if (sm) {
-    h_sbad.resize(count);
-    h_schal.resize(2 * count);
-    CPX_HIP(hipMemcpyAsync(h_sbad.data(), dst.p + spl.st_B(), count, hipMemcpyDeviceToHost, stream_));
-    CPX_HIP(hipMemcpyAsync(h_schal.data(), dfr.p + spl.fr_chal(), 2 * count * sizeof(Fr), hipMemcpyDeviceToHost, stream_));
-  }
-  call.finish();
-  if (gp) {   // an item that does not deserialise keeps the state it came with (the device had advanced it by steps 1 and 2) and gets zero challenges
-    const size_t sn = sm ? 2 : 0;   // the same-permutation challenges ahead of the grand product's
-    for (size_t i = 0; i < count; i++) {
-      const bool bad = h_bad[i] || h_gbad[i] || (sm && h_sbad[i]);
-      uint8_t* const ch = challenges ? challenges + i * (sn + 2 + NC) * sizeof(Fr) : nullptr;
-      if (!bad) memcpy(transcripts + i * kTranscriptBytes, h_states.data() + i * kTranscriptBytes, kTranscriptBytes);
-      if (ch && bad) memset(ch, 0, (sn + 2 + NC) * sizeof(Fr));
-      if (ch && !bad) {
-        if (sm) memcpy(ch, h_schal.data() + 2 * i, 2 * sizeof(Fr));
-        memcpy(ch + sn * sizeof(Fr), h_gchal.data() + 2 * i, 2 * sizeof(Fr));
-        memcpy(ch + (sn + 2) * sizeof(Fr), h_chal.data() + i * NC, NC * sizeof(Fr));
-      }
-      verdicts[i] = bad ? CPX_ERR_DESERIALIZE : h_res[i].is_identity() ? CPX_OK : CPX_ERR_VERIFY;
-    }
-    return;
-  }
-  memcpy(transcripts, h_states.data(), h_states.size());
-  if (challenges) memcpy(challenges, h_chal.data(), count * NC * sizeof(Fr));
-  for (size_t i = 0; i < count; i++) verdicts[i] = h_bad[i] ? CPX_ERR_DESERIALIZE : h_res[i].is_identity() ? CPX_OK : CPX_ERR_VERIFY;
-}
 // The basis folds of one log round (inner_product_argument.rs:177-178: 2 families, same_multiscalar_argument.rs:128-130: 3) as ONE call:
 // a SmulTask per family, each with its own gamma shared by its `half` elements, in one launch_smul.  A round's folds are small (3 x 128
 // elements at ell = 252), so up to option fold_quad_max elements the launch takes the quad-per-element form (tier0_plan.hpp).

@@ -43,6 +43,10 @@ struct HipError : std::runtime_error {
   hipError_t code;
   HipError(hipError_t c, const char* what) : std::runtime_error(what), code(c) {}
 };
+struct SubargProveArgs;   // (engine_subarg.cpp)
+struct SubargProveCall;
+struct SubargVerifyArgs;
+struct SubargVerifyCall;
 // a caller-supplied value is out of range (-> CPX_ERR_ARG)
 struct ArgError : std::runtime_error {
   explicit ArgError(const char* what) : std::runtime_error(what) {}
@@ -525,41 +529,46 @@ class Engine {
   void msm_chain_reserve(const Tier0MsmPlan& pl);
   void msm_chain(const Tier0MsmPlan& pl, const uint32_t* lens, const Aff* d_bases, const Fr* d_scalars, Jac* d_res, std::vector<MsmTask>& tasks);
   void msm_chain_run(const Tier0MsmPlan& pl, const MsmTask* d_tasks, Jac* d_res);   // its launches, on pl.count uploaded tasks
-  // the one body of ipa_rounds / same_msm_rounds (engine.cpp).  fam: G | G' | H resp. G | T | U; vec: c | d resp. x
+  // the one body of ipa_rounds / same_msm_rounds (engine_subarg.cpp).  fam: G | G' | H resp. G | T | U; vec: c | d resp. x
   void loop_rounds(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const vec[2], uint8_t* transcripts, uint8_t* rounds_comp,
                    uint8_t* rounds_aff, uint8_t* finals, uint8_t* gammas);
-  // its two halves, which the sub-argument provers share (engine.cpp): the index lists and tasks of every round, uploaded; the rounds
+  // its two halves, which the sub-argument provers share (engine_subarg.cpp): the index lists and tasks of every round, uploaded; the rounds
   // themselves on device-resident vectors, bases and states
   void loop_rounds_lists(const LoopPlan& lp, const Tier0MsmPlan& pl, std::vector<uint32_t>& idx, std::vector<MsmTask>& tasks);
   void loop_rounds_resident(const LoopPlan& lp, const Tier0MsmPlan& pl);
-  // the one body of ipa_prove / same_msm_prove (engine.cpp).  fam: G | G' resp. G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u; vec: c | d resp. x
-  // ... and, with gp, of gprod_prove: the inner-product prover behind the grand-product layer, whose inputs stand in gp (fam, stmt, z, vec: null)
-  struct GprodCall {
-    size_t ell, nb;
-    const uint8_t *G, *H, *crs_U, *B, *result, *vec_b, *vec_b_blinders;
-  };
-  // ... and, with gp and sm, of same_perm_prove: gp's B, result, vec_b and vec_b_blinders are null, the same-permutation layer makes them on the device
-  struct SamePermCall {
-    const uint8_t *A, *M, *vec_a;
-    const uint32_t* perm;
-    const uint8_t *vec_a_blinders, *vec_m_blinders;
-  };
-  void subarg_prove(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* const vec[2],
-                    const uint8_t* rand, uint8_t* rng_states, uint8_t* transcripts, uint8_t* proofs, uint8_t* challenges, int* status, const GprodCall* gp = nullptr,
-                    const SamePermCall* sm = nullptr);
-  // the one body of ipa_verify / same_msm_verify (engine.cpp).  fam: G resp. G | T | U; stmt: crs_H | C | D resp. A | Z_t | Z_u
-  // ... and, with gp, of gprod_verify: the inner-product check behind the grand-product steps, whose inputs stand in gp (fam, stmt, z, vec_u: null)
-  struct GprodCheck {
-    size_t ell, nb;
-    const uint8_t *G, *H, *crs_U, *g_sum, *h_sum, *B, *result;
-  };
-  // ... and, with gp and sm, of same_perm_verify: gp's B and result are null (B is the proof's first point, the result is made on the device)
-  struct SamePermCheck {
-    const uint8_t *A, *M, *vec_a;
-  };
-  void subarg_verify(bool ipa, size_t count, size_t n, const uint8_t* const fam[3], const uint8_t* const stmt[3], const uint8_t* z, const uint8_t* vec_u,
-                     const uint8_t* proofs, const uint8_t* rand, uint8_t* transcripts, uint8_t* challenges, int* verdicts, const GprodCheck* gp = nullptr,
-                     const SamePermCheck* sm = nullptr);
+  // The one driver of ipa_prove / same_msm_prove / gprod_prove / same_perm_prove and the one of the four verifiers (engine_subarg.cpp): a
+  // fixed list of phases, in each of them the parts of the layers in use — same permutation, grand product, then the core (inner product
+  // or same multiscalar).  The entry points name the depth in the argument struct; one call's plans, totals, host memory and device
+  // pointers are one SubargProveCall / SubargVerifyCall, constructed above the CallScope.
+  void subarg_prove(const SubargProveArgs& a);
+  void subarg_prove_reserve(SubargProveCall& c);
+  void gprod_prove_upload_bases(SubargProveCall& c);
+  void same_perm_prove_upload(SubargProveCall& c);
+  void gprod_prove_upload(SubargProveCall& c);
+  void core_prove_upload(SubargProveCall& c);
+  void subarg_prove_upload_tasks(SubargProveCall& c);
+  void subarg_prove_draw(SubargProveCall& c);
+  void same_perm_prove_steps(SubargProveCall& c);
+  void gprod_prove_steps(SubargProveCall& c);
+  void core_prove_blinders(SubargProveCall& c);
+  void gprod_prove_rdu(SubargProveCall& c);
+  void core_prove_steps(SubargProveCall& c);
+  void subarg_prove_download(SubargProveCall& c);
+  void subarg_verify(const SubargVerifyArgs& a);
+  void subarg_verify_reserve(SubargVerifyCall& c);
+  void gprod_verify_upload_bases(SubargVerifyCall& c);
+  void same_perm_verify_upload(SubargVerifyCall& c);
+  void gprod_verify_upload(SubargVerifyCall& c);
+  void core_verify_upload(SubargVerifyCall& c);
+  void subarg_verify_upload_lists(SubargVerifyCall& c);
+  void core_verify_decode(SubargVerifyCall& c);
+  void gprod_verify_decode(SubargVerifyCall& c);
+  void same_perm_verify_steps(SubargVerifyCall& c);
+  void gprod_verify_steps(SubargVerifyCall& c);
+  void core_verify_statement(SubargVerifyCall& c);
+  void core_verify_scalars(SubargVerifyCall& c);
+  void same_perm_verify_weights(SubargVerifyCall& c);
+  void subarg_verify_download(SubargVerifyCall& c);
   // n trackers -> the planes r_G | k_r_G: upload + k_decompress of the tracker prover, find-trackers and the candidate list (whisk.cpp)
   void decode_tracker_planes(size_t n, const uint8_t* trackers, std::vector<uint8_t>& canon, std::vector<uint32_t>& off, uint8_t* d_bytes, uint32_t* d_off, Aff* d_pts,
                              uint8_t* d_status);

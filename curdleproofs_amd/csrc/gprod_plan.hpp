@@ -1,4 +1,4 @@
-// Planner of the stand-alone grand-product prover (cpx_gprod_prove; Engine::subarg_prove with a GprodCall) — host code without a HIP call.
+// Planner of the stand-alone grand-product prover (cpx_gprod_prove; the grand-product layer of Engine::subarg_prove, engine_subarg.cpp) — host code without a HIP call.
 // GrandProductProof::new (grand_product_argument.rs:43-166) for `count` independent items of ell factors and n_blinders blinders,
 // n = ell + n_blinders = 2^L, is the grand-product layer — prefix products, C, r_p, the two challenges, vec_d, D — followed by
 // InnerProductProof::new on G | H, G' = u o (G | H), crs_U, C, D, inner_prod and c = vec_c | vec_c_blinders, d = vec_d | vec_d_blinders.
@@ -81,6 +81,10 @@ struct GprodProvePlan {
     lens.assign(count(), (uint32_t)n());
     return tier0_msm_plan(lens.size(), lens.data(), pl);
   }
+  SubargTotals totals() const {                                                      // (C and D land in the loop's result memory: the larger of the two)
+    const size_t res = sp.lp.results() > res_total() ? sp.lp.results() : res_total();
+    return {fr_total(), jac_total(), aff_total(), by_total(), flags_total(), ix_total(), task_total(), res, byte_ipa(), 2};
+  }
 };
 
 enum GprodPlanStatus { GPROD_OK = 0, GPROD_NOT_POW2 = 1, GPROD_TOO_LARGE = 2, GPROD_NO_FACTOR = 3, GPROD_NO_BLINDERS = 4 };
@@ -104,7 +108,7 @@ inline GprodPlanStatus gprod_prove_plan(size_t count, size_t ell, size_t n_blind
   return GPROD_OK;
 }
 
-// The stand-alone grand-product verifier (cpx_gprod_verify; Engine::subarg_verify with a GprodCheck): GrandProductProof::verify
+// The stand-alone grand-product verifier (cpx_gprod_verify; the grand-product layer of Engine::subarg_verify, engine_subarg.cpp): GrandProductProof::verify
 // (grand_product_argument.rs:180-246) is the inner-product check of subarg_check_plan.hpp on G | H, crs_U, the proof's C and
 // D = B - beta^-1 crs_G_sum + alpha crs_H_sum, whose row, weights and regions are used as they are; what the steps ahead of it need lies
 // BEHIND its regions:
@@ -128,7 +132,7 @@ struct GprodCheckPlan {
   CPX_HD size_t by_D() const { return by_B() + count() * 48; }
   CPX_HD size_t by_total() const { return by_D() + count() * 48; }
   // ---- status bytes ----
-  CPX_HD size_t st_C() const { return count() * sp.proof_points() + count(); }
+  CPX_HD size_t st_C() const { return sp.st_total(); }
   CPX_HD size_t st_bad() const { return st_C() + count(); }
   CPX_HD size_t st_total() const { return st_bad() + count(); }
   // ---- Fr memory ----
@@ -157,6 +161,10 @@ struct GprodCheckPlan {
   CPX_HD size_t aff_partial() const { return 3 * count(); }
   CPX_HD size_t aff_D() const { return 4 * count(); }
   CPX_HD size_t aff_total() const { return 5 * count(); }
+  SubargTotals totals() const {                                                      // (crs_U and B lie within the check's Jacobian inputs)
+    const SubargTotals t = sp.totals();
+    return {fr_total(), t.jac, aff_total(), by_total(), st_total(), ix_total(), t.tasks, t.res, kHead, 2};
+  }
 };
 
 // ell = 0 is refused (no prover can make such a proof); n = 1 is a real check.  The limits are those of the inner-product check.

@@ -1,5 +1,5 @@
-// Planner of the stand-alone same-permutation prover and verifier (cpx_same_perm_prove, cpx_same_perm_verify; Engine::subarg_prove with a
-// SamePermCall, Engine::subarg_verify with a SamePermCheck) — host and device code without a HIP call.  SamePermutationProof::new
+// Planner of the stand-alone same-permutation prover and verifier (cpx_same_perm_prove, cpx_same_perm_verify; the same-permutation layer of
+// Engine::subarg_prove and Engine::subarg_verify, engine_subarg.cpp) — host and device code without a HIP call.  SamePermutationProof::new
 // (same_permutation_argument.rs:40-99) is step 1 of the transcript, the permuted factors, their product, vec_b_blinders and
 // B = A + alpha M + beta sum G, then GrandProductProof::new on B, the product, the factors and vec_b_blinders; ::verify (:112-171) is step
 // 1, the index factors and their product, one accumulate_check (:149) and GrandProductProof::verify.  This header says where that layer
@@ -80,6 +80,10 @@ struct SamePermProvePlan {
     lens.assign(count(), (uint32_t)(ell() + 1));
     return tier0_msm_plan(lens.size(), lens.data(), pl);
   }
+  SubargTotals totals() const {                                          // (the B sums land in gp's B slots, the layer raises no flag)
+    const SubargTotals t = gp.totals();
+    return {fr_total(), jac_total(), aff_total(), by_total(), t.flags, ix_total(), task_total(), t.res, byte_gprod() + t.lead_bytes, 2 + t.lead_challenges};
+  }
 };
 
 // the argument rules are those of the grand-product prover
@@ -131,6 +135,10 @@ struct SamePermCheckPlan {
       ix[i] = (uint32_t)(i * gp.sp.points() + row_A());
       ix[count() + i] = (uint32_t)(i * gp.sp.points() + row_M());
     }
+  }
+  SubargTotals totals() const {                                          // (the dense affine points are gp's)
+    const SubargTotals t = gp.totals();
+    return {fr_total(), jac_total(), t.aff, by_total(), st_total(), ix_total(), t.tasks, t.res, kHead + t.lead_bytes, 2 + t.lead_challenges};
   }
 };
 

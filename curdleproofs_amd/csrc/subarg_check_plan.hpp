@@ -1,5 +1,5 @@
-// Planner of the stand-alone sub-argument verifiers (cpx_ipa_verify, cpx_same_msm_verify; Engine::subarg_verify) — host code without a
-// HIP call.  `count` independent items of n = 2^L elements: InnerProductProof::verify (inner_product_argument.rs:202-326) or
+// Planner of the stand-alone sub-argument verifiers (cpx_ipa_verify, cpx_same_msm_verify; the core layer of Engine::subarg_verify,
+// engine_subarg.cpp) — host code without a HIP call.  `count` independent items of n = 2^L elements: InnerProductProof::verify (inner_product_argument.rs:202-326) or
 // SameMultiscalarProof::verify (same_multiscalar_argument.rs:153-261), each against an MsmAccumulator of its own
 // (msm_accumulator.rs:37-68) whose random factors a_1, a_2 (, a_3) the caller drew.  The accumulator's verdict is flattened into ONE
 // multi-scalar multiplication per item:
@@ -76,6 +76,12 @@ struct SubargCheckPlan {
   CPX_HD size_t ix_dst() const { return count * proof_points(); }
   CPX_HD size_t ix_statement() const { return 2 * count * proof_points(); }
   CPX_HD size_t ix_total() const { return ix_statement() + count * kStatement; }
+  // ---- status bytes: the decoder's verdicts [count][proof_points] | the items' flags [count]; Jacobian inputs: the statement points
+  // [count][3]; dense affine points: none (gprod_plan.hpp has some) ----
+  CPX_HD size_t st_bad() const { return count * proof_points(); }
+  CPX_HD size_t st_total() const { return st_bad() + count; }
+  CPX_HD size_t jac_total() const { return count * kStatement; }
+  CPX_HD size_t aff_total() const { return 0; }
   void fill_idx(std::vector<uint32_t>& ix) const {
     ix.resize(ix_total());
     const size_t pp = proof_points();
@@ -92,6 +98,7 @@ struct SubargCheckPlan {
     lens.assign(count, (uint32_t)points());
     return tier0_msm_plan(count, lens.data(), pl);
   }
+  SubargTotals totals() const { return {fr_total(), jac_total(), aff_total(), by_total(), st_total(), ix_total(), count, count, 0, 0}; }   // one task, one sum per item
 };
 
 // An item is one task of one cpx_g1_msm_many: at most kTier0ManyTasks items of together count * points() <= kTier0ManyPoints points (which

@@ -1,4 +1,5 @@
-// Planner of the stand-alone sub-argument provers (cpx_ipa_prove, cpx_same_msm_prove; Engine::subarg_prove) — host code without a HIP call.
+// Planner of the stand-alone sub-argument provers (cpx_ipa_prove, cpx_same_msm_prove; the core layer of Engine::subarg_prove,
+// engine_subarg.cpp) — host code without a HIP call.
 // InnerProductProof::new (inner_product_argument.rs:98-199) and SameMultiscalarProof::new (same_multiscalar_argument.rs:69-150) for `count`
 // independent items are the steps before the log-round loop — blinders, the B points, step 1 of the transcript, the rewrite of the
 // vectors by alpha, for the IPA H = beta crs_H — followed by the loop of loop_plan.hpp on the same device memory.  This header says where
@@ -73,6 +74,7 @@ struct SubargProvePlan {
     lens.assign(count() * first(), (uint32_t)n());
     return tier0_msm_plan(lens.size(), lens.data(), pl);
   }
+  SubargTotals totals() const { return {fr_total(), points(), aff_total(), by_total(), count(), lp.idx_total(), task_total(), lp.results(), 0, 0}; }   // flags: one per item
 };
 
 // Same limits and verdicts as the loop's plan: a prover call is one loop call with a B-point MSM of count * first() tasks of n points

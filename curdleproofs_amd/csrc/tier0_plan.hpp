@@ -71,4 +71,13 @@ inline long tier0_fold_quad_max(size_t total, long fold_quad_max, bool plain) {
   return !plain && fold_quad_max > 0 && total <= (size_t)fold_quad_max ? fold_quad_max : 0;
 }
 
+// What a sub-argument call needs of every kind of tier-0 scratch, and what leads the inner proof in its outputs.  Every plan of the stack
+// (subarg_prove_plan.hpp / subarg_check_plan.hpp -> gprod_plan.hpp -> same_perm_plan.hpp) answers with its totals(): the end of the last
+// region of each kind at its depth, a layer taking the totals of the plan it wraps and moving those ends it lies behind.  The engine asks
+// the outermost plan in use (engine_subarg.cpp).
+struct SubargTotals {
+  size_t fr, jac, aff, bytes, flags, ix, tasks, res;   // elements of Fr memory, Jacobian inputs, affine points, bytes, flag / status bytes, index words, MSM tasks, MSM sums
+  size_t lead_bytes, lead_challenges;                  // ahead of the inner-product / same-multiscalar proof's bytes resp. challenges, per item
+};
+
 }  // namespace cpx

@@ -9,7 +9,7 @@ C=$R/curdleproofs_amd/csrc
 O=$R/curdleproofs_amd/_lib
 mkdir -p $O
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
-SRCS="kernels.hip late.hip protocol.hip round.hip loop.hip subarg.hip subarg_prove.hip gprod.hip same_perm.hip tracker.hip shuffle.hip run.hip genmul.hip find.hip rng.hip rng_g1.hip engine.cpp engine_device.cpp whisk.cpp capi.cpp"
+SRCS="kernels.hip late.hip protocol.hip round.hip loop.hip subarg.hip subarg_prove.hip gprod.hip same_perm.hip tracker.hip shuffle.hip run.hip genmul.hip find.hip rng.hip rng_g1.hip engine.cpp engine_subarg.cpp engine_device.cpp whisk.cpp capi.cpp"
 build_one() {   # name, sanitizer
   local W=$O/san_$1.tmp
   rm -rf $W && mkdir -p $W

@@ -17,6 +17,11 @@ the median of `--runs` runs on the host clock:
 Before anything is timed the two routes' proof bytes and end states are compared for every item: they must be equal.
 The per-kernel times of k_subarg_blinders / k_subarg_prove_setup come from one profiled call per shape (Context.stat).
 Points are multiples of the generator by seeded scalars.  A record, not a threshold: no test depends on a time.
+
+    python scripts/subarg_prove_timing.py --layers-ab --parent-lib PATH [--runs 20] [--out FILE]
+
+instead compares this build with the parent's call for call — the four provers, their _rng forms and the four verifiers at count = 1 and
+64 — and says how far two contexts of the parent's build lie apart on the same calls (layers_ab below; profiles/subarg_layers.md).
 """
 import argparse
 import ctypes
@@ -157,12 +162,94 @@ class Case:
         return b"".join(proofs), bytes(st_all)
 
 
+def layer_calls(count, points, rnd, maker):
+    """[(name, call(ctx))]: the eight sub-argument calls and the four _rng prover forms on `count` items of n = N (ell = 252, 4 blinders), on
+    seeded inputs that every context gets alike; the verifiers read what `maker`'s provers made of them (the statements are not consistent,
+    so the verdicts are rejections: the work is the same).  Every context draws from rng streams of its own."""
+    import struct
+    from curdleproofs_amd.rng import StdRng
+    n, ell, nb = N, N - 4, 4
+    one = params.fp_to_wire(1)
+    pts = lambda k, shift: ((points[AFF * shift:] + points[:AFF * shift]) * (k * AFF // len(points) + 1))[:k * AFF]
+    jac = lambda k, shift: b"".join(pts(k, shift)[AFF * i:AFF * (i + 1)] + one for i in range(k))
+    frs = lambda k: b"".join(fr_to_wire(rnd.randrange(1, R)) for _ in range(k))
+    states = Transcript.new(b"subarg_layers").state * count
+    G, Gp, T, U = (pts(count * n, 7 * f) for f in range(4))
+    Ge, He, g_sum, h_sum = pts(count * ell, 3), pts(count * nb, 11), pts(count, 301), pts(count, 302)
+    P = [jac(count, 100 + 31 * k) for k in range(3)]
+    z, c, d = frs(count), frs(count * n), frs(count * n)
+    res, b, rb, va, ra, rm = frs(count), frs(count * ell), frs(count * nb), frs(count * ell), frs(count * nb), frs(count * nb)
+    perm = b"".join(struct.pack("<%dI" % ell, *rnd.sample(range(ell), ell)) for _ in range(count))
+    draws = {"ipa": frs(count * (2 * n - 2)), "same_msm": frs(count * n), "gprod": frs(count * (nb + 2 * n - 2))}
+    draws["same_perm"] = draws["gprod"]
+    prove = {"ipa": lambda cx, **kw: cx.ipa_prove(n, G, Gp, *P, z, c, d, states, **kw),
+             "same_msm": lambda cx, **kw: cx.same_msm_prove(n, G, T, U, *P, c, states, **kw),
+             "gprod": lambda cx, **kw: cx.gprod_prove(ell, Ge, He, P[0], P[1], res, b, rb, states, **kw),
+             "same_perm": lambda cx, **kw: cx.same_perm_prove(ell, Ge, He, P[0], P[1], P[2], va, perm, ra, rm, states, **kw)}
+    proofs = {k: b"".join(prove[k](maker, rand=draws[k])["proofs"]) for k in prove}
+    f2, f3 = frs(2 * count), frs(3 * count)
+    verify = {"ipa": lambda cx: cx.ipa_verify(n, G, *P, z, d, proofs["ipa"], f2, states),
+              "same_msm": lambda cx: cx.same_msm_verify(n, G, T, U, *P, proofs["same_msm"], f3, states),
+              "gprod": lambda cx: cx.gprod_verify(ell, Ge, He, P[0], g_sum, h_sum, P[1], res, proofs["gprod"], f2, states),
+              "same_perm": lambda cx: cx.same_perm_verify(ell, Ge, He, P[0], g_sum, h_sum, P[1], P[2], va, proofs["same_perm"], f3, states)}
+    streams = {}
+    own = lambda cx: streams.setdefault(id(cx), [StdRng(rnd.randbytes(32) + bytes(8)) for _ in range(count)])
+    calls = []
+    for k in prove:
+        calls.append((k + "_prove", lambda cx, k=k: prove[k](cx, rand=draws[k])))
+        calls.append((k + "_prove_rng", lambda cx, k=k: prove[k](cx, rngs=own(cx))))
+        calls.append((k + "_verify", verify[k]))
+    return calls
+
+
+def layers_ab(a):
+    """--layers-ab: host time per call of this build against the parent's (--parent-lib), call for call, in one process.  Three contexts — the
+    parent's build, a second context of the parent's build, this build — take every call in turn, runs alternating; the medians of the two
+    parent contexts against each other (A/A) say how far two medians of the same code lie apart, the largest such spread over all shapes is
+    the margin this build's median is held to against the parent's (A/B)."""
+    ctxs = [("parent", cpx.Context(0, lib=a.parent_lib)), ("parent again", cpx.Context(0, lib=a.parent_lib)), ("this build", cpx.Context(0))]
+    rnd = random.Random(20261021)
+    points = ctxs[0][1].generator_mul(params.random_fr_wire(rnd, 2048))
+    lines = ["sub-argument calls at n = %d (ell = %d, 4 blinders), ms per call over all items on the host clock, median of %d runs after %d warm-up runs," % (N, N - 4, a.runs, WARMUP),
+             "the three contexts in turn within every run",
+             "%-20s %6s | %10s %12s %8s | %10s %8s" % ("call", "count", "parent", "parent again", "A/A", "this build", "A/B")]
+    spread, worst = 0.0, 0.0
+    for count in (1, 64):
+        for name, call in layer_calls(count, points, rnd, ctxs[0][1]):
+            times = [[] for _ in ctxs]
+            for run in range(WARMUP + a.runs):
+                for k in range(len(ctxs)):
+                    at = (k + run) % len(ctxs)   # the order within a run rotates
+                    t0 = time.perf_counter()
+                    call(ctxs[at][1])
+                    if run >= WARMUP:
+                        times[at].append(time.perf_counter() - t0)
+            p, p2, t = (1e3 * statistics.median(v) for v in times)
+            spread, worst = max(spread, abs(p2 / p - 1)), max(worst, t / p - 1)
+            lines.append("%-20s %6d | %10.3f %12.3f %+7.2f%% | %10.3f %+7.2f%%" % (name, count, p, p2, 100 * (p2 / p - 1), t, 100 * (t / p - 1)))
+    lines.append("margin (the largest A/A spread): %.2f%%; this build's largest excess over the parent: %+.2f%%: %s" % (100 * spread, 100 * worst,
+                                                                                                                  "within the margin" if worst <= spread else "OUTSIDE the margin"))
+    for _, cx in ctxs:
+        cx.close()
+    return "\n".join(lines)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--parent-lib", help="libcpx.so of the parent commit: the composed route runs on a context of that build")
+    ap.add_argument("--layers-ab", action="store_true", help="instead: all eight sub-argument calls and the _rng prover forms, this build against --parent-lib")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.layers_ab:
+        if not a.parent_lib:
+            ap.error("--layers-ab needs --parent-lib")
+        text = layers_ab(a)
+        print(text)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(text + "\n")
+        return 0
     ctx = cpx.Context(0)
     old = cpx.Context(0, lib=a.parent_lib) if a.parent_lib else ctx
     rnd = random.Random(20261021)

@@ -38,6 +38,9 @@ static void print_vec(const char* name, const std::vector<Fr>& v) {
   for (const Fr& x : v) print_hex(x);
   printf("\n");
 }
+static void print_totals(const char* name, const SubargTotals& t) {   // what the engine reserves at a depth, and what leads the inner proof
+  printf("%s %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", name, t.fr, t.jac, t.aff, t.bytes, t.flags, t.ix, t.tasks, t.res, t.lead_bytes, t.lead_challenges);
+}
 
 int main(int argc, char** argv) {
   if (argc >= 4 && !strcmp(argv[1], "scan")) {
@@ -118,6 +121,8 @@ int main(int argc, char** argv) {
     printf("fr %zu %zu %zu %zu %zu\n", gp.fr_result(), gp.fr_neg_beta_inv(), gp.fr_alpha(), gp.fr_chal(), gp.fr_total());
     printf("ix %zu %zu %zu %zu\n", gp.ix_C_src(), gp.ix_C_dst(), gp.ix_U_dst(), gp.ix_total());
     printf("aff %zu %zu %zu %zu %zu %zu\n", gp.aff_B(), gp.aff_g_sum(), gp.aff_h_sum(), gp.aff_partial(), gp.aff_D(), gp.aff_total());
+    print_totals("totals", gp.totals());
+    print_totals("totals_core", gp.sp.totals());
     std::vector<uint32_t> ix;
     gp.fill_idx(ix);
     printf("lists");
@@ -145,6 +150,9 @@ int main(int argc, char** argv) {
   printf("flags %zu %zu\n", gp.flag_beta(), gp.flags_total());
   printf("ix %zu %zu\n", gp.ix_addend(), gp.ix_total());
   printf("task %zu %zu %zu\n", gp.task_C(), gp.task_D(), gp.task_total());
+  print_totals("totals", gp.totals());
+  print_totals("totals_core", gp.sp.totals());
+  printf("loop_results %zu\n", gp.sp.lp.results());
   std::vector<uint32_t> ix, lens;
   gp.fill_addend(ix);
   printf("addend");

@@ -39,6 +39,9 @@ static void print_vec(const char* name, const std::vector<Fr>& v) {
   printf("\n");
 }
 static void region(const char* name, size_t start, size_t end) { printf("%s %zu %zu\n", name, start, end - start); }
+static void print_totals(const char* name, const SubargTotals& t) {   // what the engine reserves at a depth, and what leads the inner proof
+  printf("%s %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", name, t.fr, t.jac, t.aff, t.bytes, t.flags, t.ix, t.tasks, t.res, t.lead_bytes, t.lead_challenges);
+}
 
 // the product of the factors the way the work-group forms it; `factors` may be empty (the verifier keeps none)
 static Fr product(int workers, int ell, const Fr* a, const uint32_t* perm, const Fr& alpha, const Fr& beta, Fr* factors, Fr& serial) {
@@ -136,6 +139,10 @@ int main(int argc, char** argv) {
     region("task.gp", 0, gp.task_total());
     region("task.B", pl.task_B(), pl.task_total());
     printf("aff_B %zu\nrow %zu %zu\n", pl.aff_B(), gp.sp.lp.base_stride(), gp.sp.lp.h_index());
+    print_totals("totals", pl.totals());
+    print_totals("totals_gp", gp.totals());
+    print_totals("totals_core", gp.sp.totals());
+    printf("flags_total %zu\nres_end %zu %zu\n", gp.flags_total(), gp.res_total(), gp.sp.lp.results());
     std::vector<uint32_t> gather, addend, lens;
     pl.fill_lists(gather, addend);
     printf("gather");
@@ -169,6 +176,10 @@ int main(int argc, char** argv) {
   region("jac.stmt", 0, pl.jac_A());
   region("jac.AM", pl.jac_A(), pl.jac_total());
   printf("fr_weights_end %zu\n", gp.sp.fr_z());
+  print_totals("totals", pl.totals());
+  print_totals("totals_gp", gp.totals());
+  print_totals("totals_core", gp.sp.totals());
+  printf("aff_total %zu\n", gp.aff_total());
   std::vector<uint32_t> ix;
   pl.fill_idx(ix);
   printf("lists");

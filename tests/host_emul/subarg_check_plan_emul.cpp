@@ -87,6 +87,9 @@ int main(int argc, char** argv) {
   printf("fr %zu %zu %zu %zu %zu %zu\n", sp.fr_weights(), sp.fr_z(), sp.fr_u(), sp.fr_rand(), sp.fr_challenges(), sp.fr_total());
   printf("by %zu %zu %zu %zu\n", sp.by_proofs(), sp.by_statement(), sp.by_tu(), sp.by_total());
   printf("ix %zu %zu %zu %zu\n", sp.ix_src(), sp.ix_dst(), sp.ix_statement(), sp.ix_total());
+  printf("st %zu %zu\njac %zu\naff %zu\n", sp.st_bad(), sp.st_total(), sp.jac_total(), sp.aff_total());
+  const SubargTotals t = sp.totals();   // what the engine reserves at this depth, and what leads the proof
+  printf("totals %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", t.fr, t.jac, t.aff, t.bytes, t.flags, t.ix, t.tasks, t.res, t.lead_bytes, t.lead_challenges);
   for (int f = 0; f < sp.families(); f++) printf("base_off %d %zu\n", f, sp.base_off(f));
   for (size_t i = 0; i < sp.proof_scalars(); i++) printf("scalar_byte %zu %zu\n", i, sp.scalar_byte(i));
   for (int b = 0; b < sp.terms(); b++) printf("block %d %d %d %zu\n", b, sp.block_is_right(b) ? 1 : 0, sp.block_check(b), sp.L ? sp.block_slot(b, 0) : 0);

@@ -75,7 +75,8 @@ int main(int argc, char** argv) {
   printf("by %zu %zu %zu %zu\n", sp.by_points(), sp.by_tu(), sp.by_rng(), sp.by_total());
   printf("aff %zu %zu\n", sp.aff_points(), sp.aff_total());
   printf("task %zu %zu\n", sp.task_first(), sp.task_total());
-  if (count) printf("pt %zu %zu %zu %zu\n", sp.pt_first(0, 0), sp.pt_first(count - 1, sp.first() - 1), sp.pt_statement(0, 0), sp.pt_statement(count - 1, 2));
+  const SubargTotals t = sp.totals();   // what the engine reserves at this depth, and what leads the proof
+  printf("totals %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", t.fr, t.jac, t.aff, t.bytes, t.flags, t.ix, t.tasks, t.res, t.lead_bytes, t.lead_challenges);  if (count) printf("pt %zu %zu %zu %zu\n", sp.pt_first(0, 0), sp.pt_first(count - 1, sp.first() - 1), sp.pt_statement(0, 0), sp.pt_statement(count - 1, 2));
   for (size_t b = 0; b < sp.first(); b++) printf("first_family %zu %d\n", b, sp.first_family(b));
   for (size_t i = 0; i < sp.nvec(); i++) printf("scalar_byte %zu %zu\n", i, sp.scalar_byte(i));
   for (size_t b = 0; b < sp.blocks(); b++) {

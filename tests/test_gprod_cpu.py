@@ -174,6 +174,13 @@ def test_plan_matches_the_model(emul, count, ell, nb):
     assert p["ix"] == [m.ix_addend, m.ix_total] and p["addend"] == m.addend
     assert p["task"] == [m.task_C, m.task_D, m.task_total]
     assert p["msm"] == [1, count, count * m.n, m.n]
+    # the totals the engine reserves by: the end of the last region of every kind at this depth — C and D share the loop's result memory,
+    # so the sums end at the larger of the two — with C and r_p and two challenges ahead of the inner-product proof's; the IPA prover's
+    # own totals end where this layer's regions begin, and nothing leads there
+    assert p["totals"] == [m.fr_total, m.jac_total, m.aff_total, m.by_total, p["flags"][1], m.ix_total, m.task_total, max(p["loop_results"], p["res"][2]), 80, 2]
+    assert p["loop_results"] == m.L * count * 4
+    core = p["totals_core"]
+    assert core[:4] == [m.fr["result"][0], m.pt_B0, m.aff_total - count, m.by_B] and core[4:] == [count, m.ix_addend, m.task_C, p["loop_results"], 0, 0]
     # the proof bytes: C, r_p, then the inner-product proof of tests/subarg_verify_lib.py
     assert m.proof_bytes == 80 + sv.proof_bytes(IPA, m.L)
 
@@ -195,6 +202,10 @@ def test_verifier_plan_lies_behind_the_inner_product_check(emul, count, ell, nb)
     assert p["aff"] == [k * count for k in range(6)]
     stmt = n + PP                                                                     # the row: G | H, the inner proof's points, crs_U C D
     assert p["lists"] == [80 * i for i in range(count)] + [i * NP + stmt + 1 for i in range(count)] + [i * NP + stmt for i in range(count)]
+    # the totals: the end of the last region of every kind (crs_U and B lie within the check's 3 count Jacobian inputs; one task and one
+    # sum per item), the head of 80 bytes and two challenges ahead of the inner-product proof's; the check's own totals below them
+    assert p["totals"] == [p["fr"][4], 3 * count, p["aff"][5], p["by"][3], p["st"][2], p["ix"][3], count, count, 80, 2]
+    assert p["totals_core"] == [fr, 3 * count, 0, by, count * PP + count, ix, count, count, 0, 0]
     assert emul("check", 1, 3, 0)["status"] == 1 and emul("check", 65537, 3, 1)["status"] == 2
 
 

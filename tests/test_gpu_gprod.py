@@ -94,6 +94,20 @@ def test_every_thread_scans_several_elements(ctx, orc):
     check(ctx, items, seeded(orc, items, 79))
 
 
+def launches(ctx):
+    return {k: v["launches"] for k, v in ctx.stats().items() if v["launches"]}
+
+
+# Every kernel's launches in one call, as the library of the commit before the engine's sub-argument stack was split into layers made
+# them: recorded by running this test's code with CPX_LIB pointing at that build.  The prover at (6, 2) with counts 1 and 5 and at
+# (1, 1) and (2, 0); the verifier at (6, 2) and at (1, 0)
+_PROVE = lambda L: {"k_finalize": 3 + L, "k_gprod_products": 1, "k_gprod_rdu": 1, "k_gprod_setup": 1, "k_loop_step": L, "k_msm_tail": 3 + L, "k_msm_tblw<2, true>": 3 + L,
+                    "k_reduce_sets": 3 + L, "k_smul": 1, "k_smul_quad": 1, "k_subarg_blinders": 1, "k_subarg_prove_setup": 1}
+_VERIFY = {"k_compress": 1, "k_decompress": 2, "k_finalize": 1, "k_gprod_verify_steps": 1, "k_msm_tail": 1, "k_msm_tblw<2, true>": 1, "k_reduce_sets": 1, "k_smul": 2,
+           "k_smul_quad": 2, "k_subarg_scalars": 1}
+LAUNCHES = {1: _PROVE(3), 5: _PROVE(3), (1, 1): _PROVE(1), (2, 0): _PROVE(1), "verify": _VERIFY, ("verify", 1, 0): _VERIFY}
+
+
 def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc):
     import curdleproofs_amd as cpx
     ell, nb = 6, 2
@@ -109,12 +123,26 @@ def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc):
             ctx.reset_stats()
             got = check(ctx, items, [d] + seeded(orc, others, 700)[:count - 1])
             proofs[count] = got[0]
-            seen[count] = {k: v["launches"] for k, v in ctx.stats().items() if v["launches"]}
+            seen[count] = launches(ctx)
             assert ctx.stat("k_gprod_setup")["units"] == count
         assert proofs[1] == proofs[5]                                          # the same bytes alone as in a call of five
         assert seen[1] == seen[5]
         assert all(seen[1][k] == 1 for k in ("k_gprod_products", "k_gprod_setup", "k_gprod_rdu", "k_subarg_blinders", "k_subarg_prove_setup"))
         assert seen[1]["k_loop_step"] == 3
+        for shape in ((1, 1), (2, 0)):                                         # the single round of n = 2, with a blinder and without H
+            it = gl.gp_inputs(41, *shape)
+            ctx.reset_stats()
+            check(ctx, [it], [gl.seeded_draws(orc, 41, *shape)])
+            seen[shape] = launches(ctx)
+        ctx.reset_stats()
+        vcheck(ctx, orc, [c], [got[0]["proof"]], [OK_])
+        seen["verify"] = launches(ctx)
+        p = got[0]["proof"]                                                    # n = 1: no round, no H; another proof's head and finals
+        ctx.reset_stats()
+        vcheck(ctx, orc, [gl.gp_inputs(42, 1, 0)], [p[:80 + 96] + p[-64:]], [REJ])
+        seen["verify", 1, 0] = launches(ctx)
+        print("LAUNCHES", seen)
+        assert seen == LAUNCHES
         assert ctx.get_option("tier0_scratch_bytes") <= SCRATCH_BUFFERS * KEEP
     finally:
         ctx.close()

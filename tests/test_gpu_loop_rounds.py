@@ -97,6 +97,19 @@ def test_n_1_runs_no_round(ctx, orc, kind):
         assert g["finals"] == b"".join(it["vecs"]) and g["state"] == it["state"] and g["rounds"] == b"" and g["gammas"] == b""
 
 
+def launches(ctx):
+    return {k: v["launches"] for k, v in ctx.stats().items() if v["launches"]}
+
+
+# Every kernel's launches in one call, as the library of the commit before the engine's sub-argument stack was split into layers made
+# them: recorded by running this test's code with CPX_LIB pointing at that build.  n = 8 at counts 1 and 5; "small": IPA n = 2, SameMSM n = 1
+_ROUNDS = lambda L: {"k_finalize": L, "k_loop_step": L, "k_msm_tail": L, "k_msm_tblw<2, true>": L, "k_reduce_sets": L}
+LAUNCHES = {
+    IPA: {1: _ROUNDS(3), 5: _ROUNDS(3), "small": _ROUNDS(1)},
+    SMSM: {1: _ROUNDS(3), 5: _ROUNDS(3), "small": {}},
+}
+
+
 @KINDS
 def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc, kind):
     import curdleproofs_amd as cpx
@@ -106,15 +119,26 @@ def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc, kind):
     ctx = cpx.Context(0)
     try:
         ctx.set_profiling(True)
-        seen = {}
+        seen, table = {}, {}
         for count in (1, 5):
             ctx.reset_stats()
             got = run(ctx, kind, n, [item(c)] * count)
             for g in got:
                 same(g, oracle_of(c), "count %d" % count)
             seen[count] = {k: ctx.stat(k)["launches"] for k in names}
+            table[count] = launches(ctx)
             assert ctx.stat("k_loop_step")["units"] == L * count
         assert seen[1] == seen[5] == {k: L for k in names}
+        ctx.reset_stats()
+        if kind == IPA:                                                          # the single round of n = 2
+            small = case(kind, 33, 2)
+            same(run(ctx, kind, 2, [item(small)])[0], oracle_of(small), "n = 2")
+        else:                                                                    # n = 1: no round, nothing launched
+            rng = orc.rng(78)
+            run(ctx, kind, 1, [dict(bases=tuple(rng.g1_affine(1) for _ in range(3)), vecs=(rng.fr(1),), state=subarg_lib.entry_state(b""))])
+        table["small"] = launches(ctx)
+        print("LAUNCHES", kind, table)
+        assert table == LAUNCHES[kind]
         assert ctx.get_option("tier0_scratch_bytes") <= SCRATCH_BUFFERS * KEEP
     finally:
         ctx.close()

@@ -94,6 +94,21 @@ def test_every_thread_scans_several_elements(ctx, orc):
     check(ctx, items, seeded(orc, items, 79))
 
 
+def launches(ctx):
+    return {k: v["launches"] for k, v in ctx.stats().items() if v["launches"]}
+
+
+# Every kernel's launches in one call, as the library of the commit before the engine's sub-argument stack was split into layers made
+# them: recorded by running this test's code with CPX_LIB pointing at that build.  Prover and verifier at (6, 2) with counts 1 and 5, the
+# prover at (1, 1) and (2, 0), the verifier at (1, 0)
+_PROVE = lambda L: {"k_finalize": 4 + L, "k_gprod_products": 1, "k_gprod_rdu": 1, "k_gprod_setup": 1, "k_loop_step": L, "k_msm_tail": 4 + L, "k_msm_tblw<2, true>": 4 + L,
+                    "k_reduce_sets": 4 + L, "k_same_perm_step": 1, "k_smul": 1, "k_smul_quad": 1, "k_subarg_blinders": 1, "k_subarg_prove_setup": 1}
+_VERIFY = {"k_compress": 1, "k_decompress": 3, "k_finalize": 2, "k_gprod_verify_steps": 1, "k_msm_tail": 1, "k_msm_tblw<2, true>": 1, "k_reduce_sets": 1,
+           "k_same_perm_verify_step": 1, "k_same_perm_weights": 1, "k_smul": 2, "k_smul_quad": 2, "k_subarg_scalars": 1}
+LAUNCHES = {("prove", 1): _PROVE(3), ("prove", 5): _PROVE(3), ("prove", (1, 1)): _PROVE(1), ("prove", (2, 0)): _PROVE(1),
+            ("verify", 1): _VERIFY, ("verify", 5): _VERIFY, ("verify", (1, 0)): _VERIFY}
+
+
 def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc):
     import curdleproofs_amd as cpx
     ell, nb = 6, 2
@@ -119,6 +134,18 @@ def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc):
         assert all(seen[1][k] == 1 for k in ("k_same_perm_step", "k_gprod_products", "k_gprod_setup", "k_gprod_rdu", "k_subarg_blinders", "k_subarg_prove_setup"))
         assert seen[1]["k_loop_step"] == 3
         assert all(vseen[1][k] == 1 for k in ("k_same_perm_verify_step", "k_same_perm_weights", "k_gprod_verify_steps", "k_subarg_scalars"))
+        table = {("prove", 1): seen[1], ("prove", 5): seen[5], ("verify", 1): vseen[1], ("verify", 5): vseen[5]}
+        for shape in ((1, 1), (2, 0)):                                         # the single round of n = 2, with a blinder and without H
+            it = sl.sp_inputs(41, *shape)
+            ctx.reset_stats()
+            check(ctx, [it], [sl.seeded_draws(orc, 41, *shape)])
+            table["prove", shape] = launches(ctx)
+        p = got[0]["proof"]                                                    # n = 1: no round, no H; another proof's head and finals
+        ctx.reset_stats()
+        vcheck(ctx, orc, [sl.sp_inputs(42, 1, 0)], [p[:HEAD + 96] + p[-64:]], [REJ])
+        table["verify", (1, 0)] = launches(ctx)
+        print("LAUNCHES", table)
+        assert table == LAUNCHES
         assert ctx.get_option("tier0_scratch_bytes") <= SCRATCH_BUFFERS * KEEP
     finally:
         ctx.close()

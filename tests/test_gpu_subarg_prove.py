@@ -94,6 +94,20 @@ def test_rows_wider_than_a_wave_and_than_the_group(ctx, orc, kind, n):
     check(ctx, orc, kind, n, items, seeded(orc, kind, n, items, 60 + n))
 
 
+# Every kernel's launches in one call, as the library of the commit before the engine's sub-argument stack was split into layers made
+# them: recorded by running this test's code with CPX_LIB pointing at that build.  n = 8 at counts 1 and 5; "small": IPA n = 2, SameMSM n = 1
+_IPA_8 = {"k_finalize": 4, "k_loop_step": 3, "k_msm_tail": 4, "k_msm_tblw<2, true>": 4, "k_reduce_sets": 4, "k_smul": 1, "k_smul_quad": 1, "k_subarg_blinders": 1,
+          "k_subarg_prove_setup": 1}
+_SMSM_8 = {"k_compress": 1, "k_finalize": 4, "k_loop_step": 3, "k_msm_tail": 4, "k_msm_tblw<2, true>": 4, "k_reduce_sets": 4, "k_subarg_prove_setup": 1}
+LAUNCHES = {
+    IPA: {1: _IPA_8, 5: _IPA_8,
+          "small": {"k_finalize": 2, "k_loop_step": 1, "k_msm_tail": 2, "k_msm_tblw<2, true>": 2, "k_reduce_sets": 2, "k_smul": 1, "k_smul_quad": 1, "k_subarg_blinders": 1,
+                    "k_subarg_prove_setup": 1}},
+    SMSM: {1: _SMSM_8, 5: _SMSM_8,
+           "small": {"k_compress": 1, "k_finalize": 1, "k_msm_tail": 1, "k_msm_tblw<2, true>": 1, "k_reduce_sets": 1, "k_subarg_prove_setup": 1}},
+}
+
+
 @KINDS
 def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc, kind):
     import curdleproofs_amd as cpx
@@ -115,6 +129,12 @@ def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc, kind):
         assert proofs[1] == proofs[5]                                          # the same bytes alone as in a call of five
         assert seen[1] == seen[5]
         assert seen[1]["k_subarg_prove_setup"] == 1 and seen[1]["k_loop_step"] == 3 and seen[1].get("k_subarg_blinders", 0) == (1 if kind == IPA else 0)
+        m = 2 if kind == IPA else 1                                            # the single round of n = 2; n = 1: no round at all
+        ctx.reset_stats()
+        check(ctx, orc, kind, m, [sp.sp_inputs(kind, 41 + kind, m)], [sp.seeded_draws(orc, kind, 41 + kind, m)])
+        seen["small"] = {k: v["launches"] for k, v in ctx.stats().items() if v["launches"]}
+        print("LAUNCHES", kind, seen)
+        assert seen == LAUNCHES[kind]
         assert ctx.get_option("tier0_scratch_bytes") <= SCRATCH_BUFFERS * KEEP
     finally:
         ctx.close()

@@ -97,6 +97,16 @@ def test_rows_wider_than_a_wave_and_than_the_group(ctx, orc, kind, n):
     check(ctx, orc, kind, n, items, 60 + n, expect=[sv.OK] * 2)
 
 
+# Every kernel's launches in one call, as the library of the commit before the engine's sub-argument stack was split into layers made
+# them: recorded by running this test's code with CPX_LIB pointing at that build.  n = 8 at counts 1 and 5; "small": IPA n = 2, SameMSM n = 1
+_IPA_ANY = {"k_decompress": 1, "k_finalize": 1, "k_msm_tail": 1, "k_msm_tblw<2, true>": 1, "k_reduce_sets": 1, "k_subarg_scalars": 1}
+_SMSM_ANY = {"k_compress": 1, "k_decompress": 1, "k_finalize": 1, "k_msm_tail": 1, "k_msm_tblw<2, true>": 1, "k_reduce_sets": 1, "k_subarg_scalars": 1}
+LAUNCHES = {
+    IPA: {1: _IPA_ANY, 5: _IPA_ANY, "small": _IPA_ANY},
+    SMSM: {1: _SMSM_ANY, 5: _SMSM_ANY, "small": _SMSM_ANY},
+}
+
+
 @KINDS
 def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc, kind):
     import curdleproofs_amd as cpx
@@ -106,13 +116,20 @@ def test_count_1_equals_count_5_and_the_launches_depend_on_L_only(orc, kind):
     ctx = cpx.Context(0)
     try:
         ctx.set_profiling(True)
-        seen = {}
+        seen, table = {}, {}
         for count in (1, 5):
             ctx.reset_stats()
             check(ctx, orc, kind, n, [c] * count, 70 + count, expect=[sv.OK] * count)
             seen[count] = {k: ctx.stat(k)["launches"] for k in names}
+            table[count] = {k: v["launches"] for k, v in ctx.stats().items() if v["launches"]}
             assert ctx.stat("k_subarg_scalars")["units"] == count and "k_subarg_scalars" in ctx.stats()
         assert seen[1] == seen[5] == {k: 1 for k in names}
+        m = 2 if kind == IPA else 1                                            # one round's points; n = 1: none
+        ctx.reset_stats()
+        check(ctx, orc, kind, m, [sv.make(kind, 41 + kind, m)], 76, expect=[sv.OK])
+        table["small"] = {k: v["launches"] for k, v in ctx.stats().items() if v["launches"]}
+        print("LAUNCHES", kind, table)
+        assert table == LAUNCHES[kind]
         assert ctx.get_option("tier0_scratch_bytes") <= SCRATCH_BUFFERS * KEEP
     finally:
         ctx.close()

@@ -149,12 +149,22 @@ def test_prover_plan_regions_do_not_overlap_and_the_proof_byte_order(emul, count
     out = emul("plan", count, ell, nb)
     L = sl.log2(ell + nb)
     assert out["status"] == [0]
+    end = {}
     for kind in ("fr", "ix", "jac", "aff", "by", "task"):
         at = 0
         for start, size, name in _regions(out, kind):
             assert start == at, (kind, name)                                      # back to back, the grand-product plan's total first
             at = start + size
+        end[kind] = at
     sizes = {k: v[1] for k, v in out.items() if "." in k}
+    # the totals the engine reserves by are the end of the last region of every kind: this layer's, the grand-product layer's below it
+    # (the layer raises no flag and its B sums land in the grand-product layer's B slots: those two ends are the layer's below)
+    flags, res = out["flags_total"][0], max(out["res_end"])
+    assert out["totals"][:8] == [end["fr"], end["jac"], end["aff"], end["by"], flags, end["ix"], end["task"], res]
+    assert out["totals_gp"][:8] == [sizes["fr.gp"], sizes["jac.gp"], sizes["aff.gp"], sizes["by.gp"], flags, sizes["ix.gp"], sizes["task.gp"], res]
+    assert flags == 2 * count and out["res_end"] == [2 * count, L * count * 4] and out["totals_core"][4] == count and out["totals_core"][7] == L * count * 4
+    # ... and what leads the inner-product proof's bytes and challenges at the three depths
+    assert [out[k][8:] for k in ("totals_core", "totals_gp", "totals")] == [[0, 0], [80, 2], [128, 4]]
     assert sizes["fr.a"] == count * ell and sizes["fr.ra"] == sizes["fr.rm"] == count * nb and sizes["fr.bsc"] == count * (ell + 1) and sizes["fr.chal"] == 2 * count
     assert sizes["ix.perm"] == count * ell and sizes["ix.gather"] == ell + 1 and sizes["ix.addend"] == count
     assert sizes["jac.A"] == sizes["jac.M"] == sizes["aff.A"] == sizes["aff.M"] == sizes["task.B"] == count and sizes["by.A"] == sizes["by.M"] == 48 * count
@@ -175,11 +185,22 @@ def test_verifier_plan_regions_do_not_overlap_and_the_row_grows_by_three(emul, c
     n = ell + nb
     L = sl.log2(n)
     assert out["status"] == [0]
+    end = {}
     for kind in ("fr", "by", "st", "ix", "jac"):
         at = 0
         for start, size, name in _regions(out, kind):
             assert start == at, (kind, name)
             at = start + size
+        end[kind] = at
+    # the totals the engine reserves by are the end of the last region of every kind (the dense affine points are the grand-product
+    # layer's; one task and one sum per item) ...
+    sizes = {k: v[1] for k, v in out.items() if "." in k}
+    aff = out["aff_total"][0]
+    assert out["totals"][:8] == [end["fr"], end["jac"], aff, end["by"], end["st"], end["ix"], count, count] and aff == 5 * count
+    assert out["totals_gp"][:8] == [sizes["fr.gp"], sizes["jac.stmt"], aff, sizes["by.gp"], sizes["st.gp"], sizes["ix.gp"], count, count]
+    assert out["totals_core"][1:3] == [3 * count, 0] and out["totals_core"][4] == sizes["st.gp"] - 2 * count
+    # ... and what leads the inner-product proof's bytes and challenges at the three depths
+    assert [out[k][8:] for k in ("totals_core", "totals_gp", "totals")] == [[0, 0], [80, 2], [128, 4]]
     assert out["checks"] == [3] and out["challenges"] == [6 + L] and out["proof_bytes"] == [sl.proof_bytes(L)]
     inner = n + 4 * L + 5                                                         # the inner-product check's row (subarg_check_plan.hpp)
     assert out["points"] == [inner + 3] and out["row"] == [inner - 3, inner, inner + 1, inner + 2]

@@ -167,6 +167,10 @@ def test_plan_layout(emul, kind, count, n):
     assert p["pt"] == [0, count * first - 1, count * first, count * (first + 3) - 1]
     assert p["first_family"] == {b: b for b in range(first)}
     assert p["msm"] == [1, count * first, count * first * n, n]              # the B points: item-major tasks of n points
+    # the totals the engine reserves by: the end of the last region of every kind (Fr, Jacobian, affine, bytes, flags: one per item, index
+    # words: the loop's lists, tasks, sums: the loop's results), and nothing leads the proof or its challenges at this depth
+    idx = 2 * L * (n // 2 + (1 if kind == IPA else 0))
+    assert p["totals"] == [total, count * (first + 3), p["aff"][1], btotal, count, idx, p["task"][1], results, 0, 0]
 
 
 @pytest.mark.parametrize("n", [1, 2, 8])

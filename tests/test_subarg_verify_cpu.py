@@ -81,6 +81,11 @@ def test_plan_layout(emul, kind, count, n):
     assert p["idx_dst"] == [i * points + fam * n + s for i in range(count) for s in range(pp)]
     assert p["idx_statement"] == [i * points + fam * n + pp + k for i in range(count) for k in range(3)]
     assert p["msm"] == [1, count, count * points, points]                                           # one task per item, its row
+    # status bytes: the decoder's verdicts, then the items' flags; Jacobian inputs: the statement points; no dense affine points
+    assert p["st"] == [count * pp, count * pp + count] and p["jac"] == 3 * count and p["aff"] == 0
+    # the totals the engine reserves by: the end of the last region of every kind (Fr, Jacobian, affine, bytes, status, index words; one
+    # task and one sum per item), and nothing leads the proof or its challenges at this depth
+    assert p["totals"] == [total, p["jac"], p["aff"], btotal, p["st"][1], p["ix"][3], count, count, 0, 0]
 
 
 @KINDS
